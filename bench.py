@@ -7,25 +7,28 @@ One "step" = one pass of the hot path over one resident batch of synthetic read 
 search, indel joins, recursion, mate rescue, pairing, sink feedback) — h2g_align_pairs_run: the fast pass (h2g_k_go_fast.hip:
 the dominant traces with a compact per-read state), the general machine's pass over the reads the fast pass handed on, and the
 large-workspace pass over what overflowed that.  The machine's pass of step k runs on machine stream k mod 8 next to the fast passes of
-the following steps (up to eight in flight; the process asks for 16 hardware queues); the K timed steps are bracketed by a full
+the following steps (up to eight in flight); the K timed steps are bracketed by a full
 synchronisation of every stream, so the drain of the last machine passes is inside the timed region.
 
 Parity at the size that is timed: every record of the batch the timed steps ran on goes through the product's sink + SAM text and is
 compared with oracle/_ref/hisat2-align-s over the same reads, byte for byte (`parity_whole_batch`; a mismatch prints the line and fails
 the run) — the reference binary is the checker, never inside a timed region.
 
-Workload at N=1 = BASELINE.json configs[2]: GRCh38-SIZE linear index (3.1 Gbp, 4.7 GB resident), 101 bp paired-end reads,
+Workload at N=1 = BASELINE.json configs[2]'s shape: a linear index in the GRCh38 contig profile, 101 bp paired-end reads,
 --no-spliced-alignment.  The index is the reference builder's (oracle/_ref/hisat2-build-s) over a seeded uniform-random genome in
-24 human-profile contigs (no network: GRCh38 itself cannot be fetched), built on the box (~18 min at -p 64) and cached in
-.bench_cache/; a staged grch38sim<len>_* index of at least the wanted size is used when present.  H2G_BENCH_GENOME overrides the
-size (e.g. 256e6 for a quick run); the size actually used is named in config.workload.  configs[1] (E. coli-size, single-end)
-runs as the extra leg "ecoli_se"; the extra legs are skipped when the run is past H2G_BENCH_DEADLINE seconds (default 1150), the two
-companion legs with an index build of their own (repeat_pe, graph256_pe) when they would end past H2G_BENCH_BIG_DEADLINE (1250): both are measured by
-`bench.py --only-legs` / tools/queued_steps.py in profiles/ whether or not a run reaches them.
+24 human-profile contigs (no network: GRCh38 itself cannot be fetched), built where the bench runs and cached (bench_cache_dir:
+.bench_cache/ in a writable tree).  --genome (or H2G_BENCH_GENOME) sets its size: by default 256 Mbp (0.4 GB resident), which a fresh checkout
+builds in under two minutes; GRCh38 size is --genome 3.1e9 (4.7 GB resident; the build takes 17-40 min, so stage it with tools/build_bench_index.py
+first).  A staged grch38sim<len>_* index of exactly the wanted size, else of at least it, is used when present; the size actually used is named in
+config.workload.  --extras adds the other legs: configs[1] (E. coli-size, single-end) as "ecoli_se", the graph and spliced legs and the micro-benchmarks;
+they are skipped when the run is past H2G_BENCH_DEADLINE seconds (default 1150), the two companion legs with an index build of their own
+(repeat_pe, graph256_pe) when they would end past H2G_BENCH_BIG_DEADLINE (1250): both are measured by `bench.py --only-legs` /
+tools/queued_steps.py in profiles/ whether or not a run reaches them.
 
 Launch:  python bench.py [--gpus N --steps K --warmup W]        (N > 1: N ranks, one per GPU — under torch.distributed.run, or spawned by this
 program when it is started on its own; fewer than N visible devices is an error, never a silent N = 1)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step computed (a fixed seeded sample of its pairs' records) as .npy
+files, so that two builds can be compared output for output on identical inputs (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -38,9 +41,6 @@ import tempfile
 import time
 
 import numpy as np
-
-# (before torch / HIP initialise: one h2g stream is 1 + M HIP streams that must run side by side; ROCclr's default 4 hardware queues would serialise them)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -79,11 +79,26 @@ def _builder_threads():
     return BB.usable_cpus()
 
 
+def bench_cache_dir():
+    """where the generated indexes are cached: H2G_BENCH_CACHE when set, else .bench_cache/ in the tree when the tree is writable, else a directory of
+    this user's under the system's temporary directory (a checkout the benchmark may only read).  Runs that share the cache share its indexes, so they
+    run on the same inputs and only the first pays for the builds."""
+    d = os.environ.get("H2G_BENCH_CACHE")
+    if d:
+        return d
+    d = os.path.join(ROOT, ".bench_cache")
+    if os.access(d if os.path.isdir(d) else ROOT, os.W_OK):
+        return d
+    return os.path.join(tempfile.gettempdir(), "hisat2_amd_bench_cache_%d" % os.getuid())
+
+
 def headline_index(cache, want_total):
     """(base, total bases, how it was obtained): the largest staged GRCh38-scale index, else build `want_total` — inside a budget: the box's
     builder time varies 2.3x between leases (1010 s and 2320 s measured, profiles/r04_NOTES.md §4) and a run that never prints is worth less than
     one that says plainly it fell back.  H2G_BENCH_BUILD_BUDGET seconds (default 1250) for the build; past it the run continues on a
-    H2G_BENCH_FALLBACK_GENOME (default 256 Mbp, ~80 s to build) genome of the same contig profile and the line says so in metric and config."""
+    H2G_BENCH_FALLBACK_GENOME (default 256 Mbp, ~80 s to build) genome of the same contig profile and the line says so in metric and config.
+    A build stopped at its budget leaves a marker in the cache: a later run with no larger budget goes straight to the fallback genome, so the
+    runs that share a cache run on the same index (what --dump-outputs compares) and none of them spends the budget again."""
     import glob
     import build_bench_index as BB
     staged = []
@@ -92,21 +107,31 @@ def headline_index(cache, want_total):
         if BB.have(BB.index_base(tot, cache)):
             staged.append(tot)
     if staged and max(staged) >= want_total:
-        tot = max(staged)
+        tot = want_total if want_total in staged else max(staged)
         return BB.index_base(tot, cache), tot, "staged"
     budget = float(os.environ.get("H2G_BENCH_BUILD_BUDGET", "1250"))
-    t0 = time.time()
+    marker = BB.index_base(want_total, cache) + ".over_budget"
     try:
-        base = BB.build(want_total, cache=cache, timeout=budget)
-        return base, want_total, "built in %.0f s" % (time.time() - t0)
-    except subprocess.TimeoutExpired:
-        pass
+        tried = float(open(marker).read())
+    except (OSError, ValueError):
+        tried = -1.0
+    if tried >= budget:
+        why = "an earlier run's %d bp build passed its %.0f s budget on this box and was stopped (%s)" % (want_total, tried, os.path.basename(marker))
+    else:
+        t0 = time.time()
+        try:
+            base = BB.build(want_total, cache=cache, timeout=budget)
+            return base, want_total, "built in %.0f s" % (time.time() - t0)
+        except subprocess.TimeoutExpired:
+            with open(marker, "w") as f:
+                f.write("%.0f\n" % budget)
+        why = "the %d bp build passed its %.0f s budget on this box and was stopped" % (want_total, budget)
     small = int(float(os.environ.get("H2G_BENCH_FALLBACK_GENOME", "256e6")))
     if small >= want_total:
-        raise SystemExit("bench.py: the %d bp index did not build within %.0f s" % (want_total, budget))
+        raise SystemExit("bench.py: %s" % why)
     t1 = time.time()
     base = BB.build(small, cache=cache)
-    return base, small, "FALLBACK: the %d bp build passed its %.0f s budget on this box and was stopped; this index built in %.0f s" % (want_total, budget, time.time() - t1)
+    return base, small, "FALLBACK: %s; this index built in %.0f s" % (why, time.time() - t1)
 
 
 def reference_pairs(base, m1, m2, opts, threads, sam_path=None, upto=None):
@@ -222,6 +247,79 @@ def whole_batch_parity(api, base, st, codes1, offs1, codes2, offs2, names, khits
         out["first_differing_reads"] = bad
     return out
 
+
+DUMP_BLOCK = 64                  # --dump-outputs: pairs per sampled block of consecutive pairs
+DUMP_PAIRS = 1 << 14             # pairs sampled (all of them when the batch is smaller)
+DUMP_MAX_BYTES = 64 << 20        # the files together: blocks past this are left out (in sample order, so the cut is the same for equal outputs)
+
+
+def dump_outputs(api, st, npairs, id0, out_dir):
+    """--dump-outputs: what a caller of the timed path receives for the batch of the last timed step (h2g_align_pairs_fetch_dense: per pair the report
+    events and the pairing of each mate's records, with a long edit list read out of the stream's long-edit area), for a fixed sample of DUMP_PAIRS pairs
+    in blocks of DUMP_BLOCK consecutive ones drawn with the bench's seed.  Written as float64 .npy (every value is an integer that float64 holds exactly):
+      pair_ids            [S]     global id of each sampled pair (its reads' FASTA name)
+      pair_results        [S, 5]  nres mate 1, nres mate 2, npairs, overflow, rnd_state
+      concordant_pairs    [P, 3]  sample row, pair_i, pair_j (the first min(npairs, 32) entries of each pair)
+      mateM_alignments    [R, 9]  sample row, fw, tidx, toff, len, trim5, trim3, nedits, score   (M = 1, 2; dense order)
+      mateM_edits         [E, 6]  alignment row, pos, chr, qchr, type, snp
+    The per-pair work counters (nrank, nsteps, depth, nside) say how the answer was found, not what it is, and are left out.  -> dict for the result line."""
+    edit_t = np.dtype([("pos", np.uint32), ("chr", np.uint8), ("qchr", np.uint8), ("type", np.uint8), ("pad", np.uint8), ("snp", np.uint32)])
+    aln_t = np.dtype([(f, np.uint32) for f in ("fw", "tidx", "toff", "len", "trim5", "trim3", "nedits", "pad")] + [("score", np.int64), ("edits", edit_t, (api.MAX_EDITS,))])
+    pair_t = np.dtype([("nres", np.uint32, (2,))] + [(f, np.uint32) for f in ("npairs", "overflow", "nrank", "nsteps", "depth", "nside", "rnd_state", "pad")]
+                      + [("pair_i", np.uint8, (api.PAIR_CAP,)), ("pair_j", np.uint8, (api.PAIR_CAP,))])
+    assert aln_t.itemsize == C.sizeof(api.AlnRes) and pair_t.itemsize == C.sizeof(api.PairResult) and edit_t.itemsize == C.sizeof(api.Edit)
+    long_edits, nlong = st.align_fetch_long_edits()
+    long_edits = np.frombuffer(long_edits, dtype=edit_t) if nlong else np.zeros(0, dtype=edit_t)
+    nblk = (npairs + DUMP_BLOCK - 1) // DUMP_BLOCK
+    blocks = np.sort(np.random.default_rng(SEED).choice(nblk, min(nblk, DUMP_PAIRS // DUMP_BLOCK), replace=False))
+    cols = {"pair_ids": 1, "pair_results": 5, "concordant_pairs": 3, "mate1_alignments": 9, "mate2_alignments": 9, "mate1_edits": 6, "mate2_edits": 6}
+    parts = {k: [] for k in cols}
+    rows = {k: 0 for k in cols}
+    nbytes = 0
+    for b in blocks:
+        first = int(b) * DUMP_BLOCK
+        n = min(DUMP_BLOCK, npairs - first)
+        res, a1, o1, a2, o2 = st.align_pairs_fetch_dense(first, n)
+        res = np.frombuffer(res, dtype=pair_t)
+        s0 = rows["pair_ids"]
+        blk = {"pair_ids": (id0 + first + np.arange(n, dtype=np.float64))[:, None],
+               "pair_results": np.stack([res["nres"][:, 0], res["nres"][:, 1], res["npairs"], res["overflow"], res["rnd_state"]], axis=1).astype(np.float64)}
+        npr = np.minimum(res["npairs"], api.PAIR_CAP)
+        sel = np.arange(api.PAIR_CAP)[None, :] < npr[:, None]
+        blk["concordant_pairs"] = np.stack([np.nonzero(sel)[0] + s0, res["pair_i"][sel], res["pair_j"][sel]], axis=1).astype(np.float64)
+        for m, (aln, offs) in ((1, (a1, o1)), (2, (a2, o2))):
+            nrec = int(offs[n])
+            aln = np.frombuffer(aln, dtype=aln_t, count=nrec)
+            who = np.repeat(np.arange(n), np.diff(offs.astype(np.int64))) + s0
+            blk["mate%d_alignments" % m] = np.stack([who] + [aln[f] for f in ("fw", "tidx", "toff", "len", "trim5", "trim3", "nedits", "score")], axis=1).astype(np.float64)
+            eds = []
+            r0 = rows["mate%d_alignments" % m]
+            for r in range(nrec):
+                ne = int(aln["nedits"][r])
+                if ne > api.MAX_EDITS:              # its edits live in the long-edit area, at edits[0].pos
+                    e = long_edits[int(aln["edits"][r][0]["pos"]):int(aln["edits"][r][0]["pos"]) + ne]
+                else:
+                    e = aln["edits"][r][:ne]
+                if len(e):
+                    eds.append(np.stack([np.full(len(e), r0 + r), e["pos"], e["chr"], e["qchr"], e["type"], e["snp"]], axis=1).astype(np.float64))
+            blk["mate%d_edits" % m] = np.concatenate(eds) if eds else np.zeros((0, 6))
+        add = sum(x.nbytes for x in blk.values())
+        if nbytes + add > DUMP_MAX_BYTES:
+            break
+        nbytes += add
+        for k, x in blk.items():
+            parts[k].append(x)
+            rows[k] += len(x)
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for k, c in cols.items():
+        x = np.concatenate(parts[k]) if parts[k] else np.zeros((0, c))
+        if c == 1:
+            x = x[:, 0]
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+        files[k] = list(x.shape)
+    return {"dir": os.path.abspath(out_dir), "pairs": rows["pair_ids"], "of_pairs": npairs, "bytes": nbytes, "dtype": "float64", "files": files,
+            "what": "h2g_align_pairs_fetch_dense of the last timed step for %d blocks of %d consecutive pairs drawn with the bench seed" % (len(parts["pair_ids"]), DUMP_BLOCK)}
 
 
 KERNEL_SOURCES = ("h2g_k_go_fast.hip", "h2g_k_go_fast_am.hip", "h2g_fast.h", "h2g_core.h", "h2g_align.h", "h2g_graph.h", "h2g_go_args.h", "Makefile")
@@ -362,16 +460,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pairs", type=int, default=1_000_000, help="read pairs per GPU per step")
     ap.add_argument("--batches", type=int, default=10, help="distinct resident batches of --pairs pairs the timed steps walk over (1..16)")
-    ap.add_argument("--genome", type=float, default=float(os.environ.get("H2G_BENCH_GENOME", "3.1e9")))
+    ap.add_argument("--genome", type=float, default=float(os.environ.get("H2G_BENCH_GENOME", "256e6")),
+                    help="bases of the headline index (default 256e6; GRCh38 size: 3.1e9, best staged beforehand with tools/build_bench_index.py)")
     ap.add_argument("--strong", action="store_true", help="one global batch of --pairs split over the ranks instead of --pairs per rank")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-whole-parity", action="store_true", help="skip the whole-batch device-vs-reference SAM comparison of each leg (the 3 000 / 20 000-pair command-line samples stay)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (E. coli SE, graph index, micro-benchmarks)")
+    ap.add_argument("--extras", action="store_true", help="also run the extra legs (E. coli SE, graph index, spliced, companions, micro-benchmarks: up to ~25 min more)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (the default; overrides --extras)")
     ap.add_argument("--rank-queries", type=int, default=1 << 28)
     ap.add_argument("--only-legs", default="", help="comma-separated big legs (repeat_pe, graph256_pe) to run INSTEAD of the headline: prints {leg: ...} and exits")
     ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="pairs available to the reference CPU runs (each thread count takes what ~6 s of it)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercises the launch path only (spawn, rendezvous over gloo, shard ranges, the counter all-reduce) and prints a line marked dry_run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the records of a fixed seeded sample of its pairs) as float64 DIR/<name>.npy; "
+                         "runs that share the index cache (bench_cache_dir) run on the same inputs")
     a = ap.parse_args()
+    if not a.extras:
+        a.no_extras = True
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import torch
     from hisat2_amd import shard
@@ -409,7 +518,7 @@ def main():
         # single-GPU items (they run at N = 1: SURVEY §8(d)) and would only keep N - 1 ranks waiting at the last barrier
         a.no_extras = True
         a.no_cpu_baseline = True
-    cache = os.path.join(ROOT, ".bench_cache")
+    cache = bench_cache_dir()
     if a.only_legs:
         out = {}
         for name in a.only_legs.split(","):
@@ -476,6 +585,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     cnt = st.counters()                        # counters + HIP-event kernel times (stream events) of the LAST step
+    dumped = None
+    if a.dump_outputs is not None:             # (outside the timed region: the stream still holds the last step's results)
+        dumped = dump_outputs(api, st, npairs, id0, a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, "rank%d" % rank))
     if dist is not None:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -529,13 +641,15 @@ def main():
                        "genome_bases": total, "index_device_bytes": int(ix.info.device_bytes), "pairs_per_gpu": npairs, "read_len": 101, "sub_rate": 0.005,
                        "fragment": "N(300, 30) clipped to [150, 600]",
                        "stage": "HI_Aligner::go for both mates + pairing; report events stay in HBM (finishRead / SAM text are host code, SURVEY §8(f) N1)",
-                       "pipelining": "the general machine's pass over step k's hand-ons runs on machine stream k mod 8 next to the fast passes of the following steps (up to 8 such passes in flight, buffers 9 deep, 16 hardware queues); all K steps complete inside the timed region",
+                       "pipelining": "the general machine's pass over step k's hand-ons runs on machine stream k mod 8 next to the fast passes of the following steps (up to 8 such passes in flight, buffers 9 deep); all K steps complete inside the timed region",
                        "sharding": f"pairs by id range across {world} GPU(s) ({'one global batch split' if a.strong else 'fixed work per GPU'}), index replicated; RCCL all-reduce of the summary counters only"},
             "roofline": roofline,
             "counters": {"pairs": int(summ[0]), "pairs_with_concordant": int(summ[1]), "pairs_still_flagged_overflow": int(summ[2]),
                          "pairs_second_pass": int(summ[3]), "second_pass_rate": float(summ[3]) / max(1, int(summ[0])),
                          "sides_per_pair": float(summ[4]) / int(summ[0]), "sa_steps_per_pair": float(summ[5]) / int(summ[0])},
         })
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         exe = os.path.join(REF, "hisat2-align-s")
         cli = os.path.join(ROOT, "hisat2_amd", "hisat2-align-amd")
         tmp = tempfile.mkdtemp(prefix="h2bench")

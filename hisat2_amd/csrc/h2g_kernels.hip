@@ -580,10 +580,8 @@ extern "C" h2g_status h2g_index_synth_graph_sides(uint64_t num_sides, uint64_t s
 // ------------------------------------------------------------------------------------------ stream
 // A stream of this library is 2 + H2G_MSTREAMS_MAX HIP streams (the fast launches', the drain launches', one per machine pass in flight) whose kernels must be able to run side by side.  ROCclr maps HIP streams onto
 // GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue serialise — measured: four machine passes "in flight" on the
-// default 4 queues ran one after the other (repeat-structured leg: 127 ms per step against 78 ms with 16 queues; profiles/r05_NOTES.md).  The variable is
-// read when the HIP runtime initialises, so it is set when this library is loaded (never overriding the caller's own setting); a process that
-// initialises HIP before loading libh2g.so sets it itself (bench.py, hisat2-align-amd and hisat2_amd/api.py do).
-__attribute__((constructor)) static void h2g_want_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
+// default 4 queues ran one after the other (repeat-structured leg: 127 ms per step against 78 ms with 16 queues; profiles/r05_NOTES.md).  The library
+// does not set the variable: the number of hardware queues a process opens is the host's and the caller's choice, and results do not depend on it.
 
 extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t max_bases, h2g_stream** out) {
 	if(!ix || !out) return H2G_ERR_ARG;
