@@ -189,7 +189,8 @@ class AlignParams(C.Structure):
                 ("pen_canintronlen_type", u32), ("pen_noncanintronlen_type", u32), ("first_read_id", u32),
                 ("pen_canintronlen_const", C.c_double), ("pen_canintronlen_coeff", C.c_double),
                 ("pen_noncanintronlen_const", C.c_double), ("pen_noncanintronlen_coeff", C.c_double),
-                ("min_anchor_len", u32), ("min_anchor_len_noncan", u32), ("xs_only", u32), ("use_haplotype", u32), ("max_alts_tried", u32), ("max_frag_len", u32), ("min_frag_len", u32), ("pe_orientation", u32), ("nofw", u32), ("norc", u32)]
+                ("min_anchor_len", u32), ("min_anchor_len_noncan", u32), ("xs_only", u32), ("use_haplotype", u32), ("max_alts_tried", u32), ("max_frag_len", u32), ("min_frag_len", u32), ("pe_orientation", u32), ("nofw", u32), ("norc", u32),
+                ("avoid_pseudogene", u32), ("transcriptome_mapping_only", u32), ("no_anchorstop", u32), ("pen_conflictsplice", C.c_int32)]
 
     def apply_options(self, opts, linear=None):
         """apply a list of reference command-line options (['-k', '3', '--mp', '4,2', ...]) to this block; returns leftovers.
@@ -251,6 +252,18 @@ class AlignParams(C.Structure):
                 self.nofw = 1; i += 1
             elif o == "--norc":
                 self.norc = 1; i += 1
+            elif o == "--avoid-pseudogene":
+                self.avoid_pseudogene = 1; i += 1
+            elif o in ("--tmo", "--transcriptome-mapping-only"):
+                self.transcriptome_mapping_only = 1; i += 1
+            elif o == "--no-anchorstop":
+                self.no_anchorstop = 1; i += 1
+            elif o == "--splicesite-db-only":   # accepted and read nowhere by the reference (hisat2.cpp:1706-1708)
+                i += 1
+            elif o == "--pen-conflictsplice":
+                if int(v) < 0:
+                    raise ValueError("--pen-conflictsplice arg must be at least 0")
+                self.pen_conflictsplice = int(v); i += 2
             elif o in ("-X", "--maxins"):
                 self.max_frag_len = int(v); i += 2
             elif o == "--max-altstried":

@@ -756,6 +756,16 @@ H2G_HD bool hit_equal(const h2g_ghit* a, const h2g_ghit* b) {
 #endif
 #endif
 #define H2G_PE_DEFAULT 1u
+// --avoid-pseudogene (with spliced alignment on) and --tmo ride in bits 5 and 6 of AlnParams::xs_only (aln_params_from); they need the H2G_EXT_OPTS units
+#define H2G_TP_AVOID_PSEUDOGENE 32u
+#define H2G_TP_TMO 64u
+// Under --avoid-pseudogene / --tmo an AlnRec's fw carries the transcript class al_report gave it above the strand (include/h2g.h, H2G_FW_TCLASS):
+// in the H2G_EXT_OPTS units every reader of its strand goes through rec_fw.  The other units never see those options and keep their code.
+#if H2G_EXT_OPTS
+H2G_HD uint32_t rec_fw(uint32_t fw) { return fw & H2G_FW_STRAND; }
+#else
+H2G_HD uint32_t rec_fw(uint32_t fw) { return fw; }
+#endif
 H2G_HD uint32_t pe_flags_from(const h2g_align_params& p) {
 	const uint32_t m1 = p.pe_orientation == 1 ? 0u : 1u, m2 = p.pe_orientation == 0 ? 0u : 1u;   // fr: 1,0  rf: 0,1  ff: 1,1
 	return m1 | (m2 << 1) | (p.nofw ? 4u : 0u) | (p.norc ? 8u : 0u);
@@ -789,13 +799,15 @@ inline AlnParams aln_params_from(const h2g_align_params& p, bool no_spliced, boo
 	// xs_only also carries the options of H2G_EXT_OPTS (ctx_ext_opts below): bits 1-4 = pe_flags ^ default, bits 8.. = -I.  The kernel argument
 	// block keeps its size and offsets that way, and with them the code of the units built without those options (which only ever see 0 / 1)
 	P.xs_only = (p.xs_only ? 1u : 0u) | ((pe_flags_from(p) ^ H2G_PE_DEFAULT) << 1) | (p.min_frag_len << 8);   // tp.h, hi_aligner.h:3986
-	P.pseudogeneStop = (linear && !no_spliced) ? 1 : 0; P.anchorStop = 1; P.maxFragLen = p.max_frag_len ? p.max_frag_len : 1000;
+	// reportHit applies avoid_pseudogene only with spliced alignment on (hi_aligner.h:6105), transcriptome_mapping_only always (:6126)
+	P.xs_only |= (p.avoid_pseudogene && !no_spliced ? H2G_TP_AVOID_PSEUDOGENE : 0u) | (p.transcriptome_mapping_only ? H2G_TP_TMO : 0u);
+	P.pseudogeneStop = (linear && !no_spliced) ? 1 : 0; P.anchorStop = p.no_anchorstop ? 0 : 1; P.maxFragLen = p.max_frag_len ? p.max_frag_len : 1000;
 	P.bowtie2_dp = p.bowtie2_dp;
 	P.scoreMinType = p.score_min_type; P.scoreMinConst = p.score_min_const; P.scoreMinCoeff = p.score_min_coeff;
 	P.sc.mmpMax = p.mm_max; P.sc.mmpMin = p.mm_min; P.sc.nPen = p.n_pen; P.sc.rdGapConst = p.rdg_const; P.sc.rdGapLinear = p.rdg_linear;
 	P.sc.rfGapConst = p.rfg_const; P.sc.rfGapLinear = p.rfg_linear; P.sc.scMax = p.sc_max; P.sc.scMin = p.sc_min;
 	P.sc.minAnchorLen = P.minAnchorLen; P.sc.minAnchorLen_noncan = P.minAnchorLen_noncan; P.sc.maxIntronLen = P.maxIntronLen;
-	P.sc.cp = p.pen_cansplice; P.sc.ncp = p.pen_noncansplice;
+	P.sc.cp = p.pen_cansplice; P.sc.ncp = p.pen_noncansplice; P.sc.csp = p.pen_conflictsplice;
 	P.sc.icpT = p.pen_canintronlen_type; P.sc.icpC = p.pen_canintronlen_const; P.sc.icpL = p.pen_canintronlen_coeff;
 	P.sc.incpT = p.pen_noncanintronlen_type; P.sc.incpC = p.pen_noncanintronlen_const; P.sc.incpL = p.pen_noncanintronlen_coeff;
 	return P;
@@ -811,6 +823,7 @@ inline void align_params_defaults(h2g_align_params* p, bool linear) {
 	p->pen_canintronlen_type = 4; p->pen_canintronlen_const = -8.0; p->pen_canintronlen_coeff = 1.0;
 	p->pen_noncanintronlen_type = 4; p->pen_noncanintronlen_const = -8.0; p->pen_noncanintronlen_coeff = 1.0;
 	p->min_anchor_len = 7; p->min_anchor_len_noncan = 14; p->xs_only = 0; p->use_haplotype = 0; p->max_alts_tried = 16; p->max_frag_len = 1000; p->min_frag_len = 0; p->pe_orientation = 0; p->nofw = 0; p->norc = 0;
+	p->avoid_pseudogene = 0; p->transcriptome_mapping_only = 0; p->no_anchorstop = 0; p->pen_conflictsplice = 1000000;   // hisat2.cpp:495, :507-512
 }
 
 // One reported alignment = the arguments reportHit (hi_aligner.h:6064-6166) hands to AlnRes::init
@@ -920,7 +933,7 @@ H2G_HD bool al_redundant(const MateWS* ws, const h2g_ghit* hit, uint32_t rdlen) 
 	if(ws->sink_hidden) return false;
 	for(uint32_t i = 0; i < ws->nres; i++) {
 		const AlnRec& r = ws->res[i];
-		if(r.tidx != hit->tidx || r.toff != hit->toff || r.fw != hit->fw) continue;
+		if(r.tidx != hit->tidx || r.toff != hit->toff || rec_fw(r.fw) != hit->fw) continue;
 		if(r.nedits != hit->nedits) continue;
 		uint32_t k = 0;
 		for(; k < r.nedits; k++) {
@@ -943,8 +956,10 @@ H2G_HD void al_add_searched(AlignWS* aw, MateWS* ws, const h2g_ghit* hit) {
 	hit_copy(&ws->searched[ws->nsearched++], hit);
 }
 
-// reportHit hi_aligner.h:6064-6166 + AlnSinkWrap::report aln_sink.h:2565-2650 (unpaired mate 1)
-H2G_HD bool al_report(AlignWS* aw, MateWS* ws, const h2g_ghit* hit, uint32_t rdlen, int64_t minsc, bool xs_only = false) {
+// reportHit hi_aligner.h:6064-6166 + AlnSinkWrap::report aln_sink.h:2565-2650 (unpaired mate 1).  tpol: the H2G_TP_* bits of AlnParams::xs_only,
+// with the database (`ssdb`) and the index's exons (`exons`) the transcriptome policy queries (H2G_EXT_OPTS units only)
+H2G_HD bool al_report(AlignWS* aw, MateWS* ws, const h2g_ghit* hit, uint32_t rdlen, int64_t minsc, bool xs_only = false,
+                      uint32_t tpol = 0, const DSpliceDB* ssdb = nullptr, const DExonTbl* exons = nullptr) {
 	if(xs_only) {   // reportHit hi_aligner.h:6101 over GenomeHit::splicing_dir :1128: a spliced alignment whose strand is unknown or mixed
 		uint32_t dir = H2G_SPL_UNKNOWN; bool spliced = false, mixed = false;
 		for(uint32_t i = 0; i < hit->nedits && !mixed; i++) {
@@ -962,11 +977,31 @@ H2G_HD bool al_report(AlignWS* aw, MateWS* ws, const h2g_ghit* hit, uint32_t rdl
 	}
 	if(hit->rdoff - hit->trim5 > 0 || hit->len + hit->trim5 + hit->trim3 < rdlen) return false;
 	if(hit->score < minsc) return false;
+#if H2G_EXT_OPTS
+	// the transcript class: GenomeHit::spliced() (hi_aligner.h:1086) = (spliced, spliced through database sites only), then :6105-6127
+	uint32_t tclass = 0;
+	if(tpol) {
+		bool spliced = false, known = true;
+		for(uint32_t i = 0; i < hit->nedits; i++) if(hit->edits[i].type == H2G_EDIT_SPL) { spliced = true; known = known && spl_known(hit->edits[i]); }
+		known = known && spliced;
+		if((tpol & H2G_TP_AVOID_PSEUDOGENE) && !spliced) {
+			const uint32_t max_exon_size = 10000;
+			const uint32_t left = hit->toff > max_exon_size ? hit->toff - max_exon_size : 0, right = hit->toff + hit->len + max_exon_size;
+			spliced = ssdb != nullptr && ss_any_in(*ssdb, hit->tidx, left, right);
+			if(exons != nullptr && exons->n) known = exon_inside(*exons, hit->tidx, hit->toff, hit->toff + hit->len - 1);
+		}
+		if((tpol & H2G_TP_TMO) && !known) return false;
+		tclass = H2G_FW_TCLASS | ((known ? 2u : spliced ? 1u : 0u) << H2G_FW_TCLASS_SHIFT);
+	}
+#endif
 	if(ws->nres >= AL_MAX_RESULTS) { aw->overflow |= 4; return false; }
 	AL_TRACE("  REPORT fw %u tidx %u toff %u len %u trim %u/%u score %lld nedits %u\n", hit->fw, hit->tidx, hit->toff, hit->len, hit->trim5, hit->trim3, (long long)hit->score, hit->nedits);
 	for(uint32_t q_ = 0; q_ < hit->nedits; q_++) AL_TRACE("      edit pos %u type %u chr %u qchr %u pad %u snp %x\n", hit->edits[q_].pos, hit->edits[q_].type, hit->edits[q_].chr, hit->edits[q_].qchr, hit->edits[q_].pad, hit->edits[q_].snp);
 	AlnRec& r = ws->res[ws->nres++];
 	r.fw = hit->fw; r.tidx = hit->tidx; r.toff = hit->toff; r.len = hit->len; r.trim5 = hit->trim5; r.trim3 = hit->trim3;
+#if H2G_EXT_OPTS
+	r.fw |= tclass;                 // (0 without the policy: the record is what it always was)
+#endif
 	r.nedits = hit->nedits; r.splicescore = hit->splicescore; r.score = hit->score;
 	// reportHit shifts by trim5 and inverts for !fw (hi_aligner.h:6093-6101); AlnRes::setShape then shifts the
 	// stored copy by the 5' trim in read orientation (aligner_result.cpp:110-118)
@@ -1003,10 +1038,14 @@ struct AlnCtx {
 	bool graph = false;               // set from a kernel template constant so that the linear kernels carry no graph code
 #if H2G_EXT_OPTS
 	uint32_t pe_flags = H2G_PE_DEFAULT, min_frag_len = 0;
+	uint32_t tpol = 0;                // H2G_TP_AVOID_PSEUDOGENE | H2G_TP_TMO
+	const DExonTbl* exons = nullptr;  // the index's exons (--ss/--exon index); nullptr or n == 0: none
 #endif
 };
 #if H2G_EXT_OPTS
-H2G_HD void ctx_ext_opts(AlnCtx& C, const AlnParams& P) { C.pe_flags = ((P.xs_only >> 1) & 15u) ^ H2G_PE_DEFAULT; C.min_frag_len = P.xs_only >> 8; }
+H2G_HD void ctx_ext_opts(AlnCtx& C, const AlnParams& P) {
+	C.pe_flags = ((P.xs_only >> 1) & 15u) ^ H2G_PE_DEFAULT; C.min_frag_len = P.xs_only >> 8; C.tpol = P.xs_only & (H2G_TP_AVOID_PSEUDOGENE | H2G_TP_TMO);
+}
 #endif
 
 // Per-lane scratch of the graph paths (allocated only for graph indexes, so the linear workspace keeps its size):
@@ -1233,9 +1272,9 @@ H2G_HD void al_pair_reads(const AlnParams& P, AlignWS* ws, uint32_t rdlen1, uint
 			int64_t l = r1.toff, r = (int64_t)r1.toff + e1 - 1, l2 = r2.toff, rr2 = (int64_t)r2.toff + e2 - 1;
 #if H2G_EXT_OPTS
 			const bool m1fw = (pe_flags & 1u) != 0, m2fw = (pe_flags & 2u) != 0;
-			if((r1.fw != 0) == m1fw) { if((r2.fw != 0) != m2fw) continue; }
+			if((rec_fw(r1.fw) != 0) == m1fw) { if((rec_fw(r2.fw) != 0) != m2fw) continue; }
 			else {
-				if((r2.fw != 0) == m2fw) continue;
+				if((rec_fw(r2.fw) != 0) == m2fw) continue;
 				int64_t t = l; l = l2; l2 = t; t = r; r = rr2; rr2 = t;
 			}
 #else
@@ -1251,8 +1290,8 @@ H2G_HD void al_pair_reads(const AlnParams& P, AlignWS* ws, uint32_t rdlen1, uint
 			bool pass = true;
 			if(P.no_spliced) {
 #if H2G_EXT_OPTS
-				if(r1.toff < r2.toff) pass = pe_concordant_ext(r1.toff, e1, r1.fw != 0, r2.toff, e2, r2.fw != 0, P.maxFragLen, min_frag_len, pe_flags);
-				else                  pass = pe_concordant_ext(r2.toff, e2, r2.fw != 0, r1.toff, e1, r1.fw != 0, P.maxFragLen, min_frag_len, pe_flags);
+				if(r1.toff < r2.toff) pass = pe_concordant_ext(r1.toff, e1, rec_fw(r1.fw) != 0, r2.toff, e2, rec_fw(r2.fw) != 0, P.maxFragLen, min_frag_len, pe_flags);
+				else                  pass = pe_concordant_ext(r2.toff, e2, rec_fw(r2.fw) != 0, r1.toff, e1, rec_fw(r1.fw) != 0, P.maxFragLen, min_frag_len, pe_flags);
 #else
 				if(r1.toff < r2.toff) pass = pe_concordant(r1.toff, e1, r1.fw != 0, r2.toff, e2, r2.fw != 0, P.maxFragLen);
 				else                  pass = pe_concordant(r2.toff, e2, r2.fw != 0, r1.toff, e1, r1.fw != 0, P.maxFragLen);
@@ -1286,9 +1325,15 @@ H2G_HD int64_t hisat2_score(const AlnRec& r) {   // AlnScore::calculate_hisat2_s
 	// transcript score (reportHit hi_aligner.h:6100-6143 over GenomeHit::spliced() :1086): 2 = spliced through database sites only
 	// ("known transcripts"), 1 = spliced, 0 = not (the near-a-splice-site case needs --avoid-pseudogene)
 	int64_t tscore = 0;
-	bool all_known = true;
-	for(uint32_t k = 0; k < r.nedits; k++) if(r.edits[k].type == H2G_EDIT_SPL) { tscore = 1; all_known = all_known && spl_known(r.edits[k]); }
-	if(tscore && all_known) tscore = 2;
+#if H2G_EXT_OPTS
+	if(r.fw & H2G_FW_TCLASS) tscore = (r.fw >> H2G_FW_TCLASS_SHIFT) & 3u;   // the class al_report gave it (--avoid-pseudogene / --tmo)
+	else
+#endif
+	{
+		bool all_known = true;
+		for(uint32_t k = 0; k < r.nedits; k++) if(r.edits[k].type == H2G_EDIT_SPL) { tscore = 1; all_known = all_known && spl_known(r.edits[k]); }
+		if(tscore && all_known) tscore = 2;
+	}
 	int64_t spl = (int64_t)r.splicescore / 100;
 	spl = spl > 255 ? 0 : 255 - spl;
 	return (int64_t)((uint64_t)score << 32) | (0ll << 28) | (tscore << 24) | (spl << 16) | trim;

@@ -259,6 +259,7 @@ int main(int argc, char** argv) {
 	bool phred64 = false, ignore_quals = false, quiet = false, raw_input = false, cmdline_input = false;
 	bool report_mixed = true, report_discordant = true;
 	bool dta = false, xs_only = false;
+	bool avoid_pseudogene = false, tmo = false, no_anchorstop = false;
 	int strandness = 0;
 	uint64_t skip = 0, upto = ~0ull;
 	uint32_t trim5 = 0, trim3 = 0;
@@ -294,6 +295,10 @@ int main(int argc, char** argv) {
 			strandness = v == "F" ? 1 : v == "R" ? 2 : v == "FR" ? 3 : v == "RF" ? 4 : 0;
 			if(!strandness) { fprintf(stderr, "Error: should be one of F, R, FR, or RF \n"); return 1; }
 		}
+		else if(a == "--avoid-pseudogene") avoid_pseudogene = true;               // TranscriptomePolicy (tp.h), reportHit hi_aligner.h:6105-6127
+		else if(a == "--tmo" || a == "--transcriptome-mapping-only") tmo = true;
+		else if(a == "--no-anchorstop") no_anchorstop = true;                     // hisat2.cpp:1710-1712
+		else if(a == "--splicesite-db-only") {}                                   // accepted and read nowhere by the reference (hisat2.cpp:1706-1708)
 		else if(a == "--known-splicesite-infile") known_ss = need("--known-splicesite-infile");
 		else if(a == "--novel-splicesite-infile") novel_ss = need("--novel-splicesite-infile");
 		else if(a == "--novel-splicesite-outfile") novel_out = need("--novel-splicesite-outfile");
@@ -322,7 +327,7 @@ int main(int argc, char** argv) {
 		else if(a == "--haplotype") use_haplotype = true;                      // hisat2.cpp:1749 (ARG_HAPLOTYPE)
 		else if(a == "--bowtie2-dp") dp = (uint32_t)atoi(need("--bowtie2-dp"));
 		else if(a == "-k" || a == "--max-seeds" || a == "--mp" || a == "--sp" || a == "--np" || a == "--rdg" || a == "--rfg" || a == "--score-min" ||
-		        a == "--min-intronlen" || a == "--max-intronlen" || a == "--pen-cansplice" || a == "--pen-noncansplice" ||
+		        a == "--min-intronlen" || a == "--max-intronlen" || a == "--pen-cansplice" || a == "--pen-noncansplice" || a == "--pen-conflictsplice" ||
 		        a == "--pen-canintronlen" || a == "--pen-intronlen" || a == "--pen-noncanintronlen") {
 			opts.push_back(a); opts.push_back(need(a.c_str()));
 		}
@@ -482,10 +487,10 @@ int main(int argc, char** argv) {
 			if(v < 20) { fprintf(stderr, "%s arg must be at least 20\n", o.c_str()); return 1; }
 			(o == "--min-intronlen" ? P.min_intronlen : P.max_intronlen) = (uint32_t)v;
 		}
-		else if(o == "--pen-cansplice" || o == "--pen-noncansplice") {
+		else if(o == "--pen-cansplice" || o == "--pen-noncansplice" || o == "--pen-conflictsplice") {
 			const int v = atoi(opts[++i].c_str());
 			if(v < 0) { fprintf(stderr, "%s arg must be at least 0\n", o.c_str()); return 1; }
-			(o == "--pen-cansplice" ? P.pen_cansplice : P.pen_noncansplice) = v;
+			(o == "--pen-cansplice" ? P.pen_cansplice : o == "--pen-noncansplice" ? P.pen_noncansplice : P.pen_conflictsplice) = v;
 		}
 		else if(o == "--pen-canintronlen" || o == "--pen-intronlen" || o == "--pen-noncanintronlen") {   // PARSE_FUNC: only the given fields change
 			const bool nc = o == "--pen-noncanintronlen";
@@ -512,6 +517,7 @@ int main(int argc, char** argv) {
 		if(ignore_quals && !saw_mp) P.mm_min = P.mm_max;
 	}
 	P.xs_only = xs_only ? 1 : 0;
+	P.avoid_pseudogene = avoid_pseudogene ? 1 : 0; P.transcriptome_mapping_only = tmo ? 1 : 0; P.no_anchorstop = no_anchorstop ? 1 : 0;
 	P.use_haplotype = use_haplotype ? 1 : 0;
 	P.max_alts_tried = (uint32_t)max_alts_tried;
 	P.max_frag_len = (uint32_t)max_frag_len;

@@ -143,6 +143,38 @@ H2G_HD uint32_t ss_right_sites(const DSpliceDB& db, uint32_t tidx, uint32_t righ
 	if(!db.n) return 0;
 	return ss_range(db.fw, db.fw_first[tidx], db.fw_first[tidx + 1], false, right, right + range - 1, db, rdid, out, cap);
 }
+// SpliceSiteDB::hasSpliceSites(ref, L, R, L, R, includeNovel = true) splice_site.cpp:436-506: is there a site whose right end (_bwIndex)
+// or left end (_fwIndex) lies in [L, R]?  Unfiltered: the reference's query takes no read id, so ss_visible does not apply.
+H2G_HD bool ss_any_in(const DSpliceDB& db, uint32_t tidx, uint32_t L, uint32_t R) {
+	if(!db.n || L >= R) return false;
+	uint32_t x = db.bw_first[tidx], y = db.bw_first[tidx + 1];
+	while(x < y) { const uint32_t m = x + ((y - x) >> 1); if(db.bw[m].right < L) x = m + 1; else y = m; }
+	if(x < db.bw_first[tidx + 1] && db.bw[x].right <= R) return true;
+	x = db.fw_first[tidx]; y = db.fw_first[tidx + 1];
+	while(x < y) { const uint32_t m = x + ((y - x) >> 1); if(db.fw[m].left < L) x = m + 1; else y = m; }
+	return x < db.fw_first[tidx + 1] && db.fw[x].left <= R;
+}
+// The exons of a --ss/--exon index (SpliceSiteDB::read(gfm, alts) splice_site.cpp:655-725): every ALT_EXON as (text, left - 10, right + 10)
+// clamped to the text, ONE array sorted by (text, left, right) (Exon::operator< splice_site.h:426).  Empty (n == 0) for indexes without exons.
+struct DExon { uint32_t tidx, left, right; };
+struct DExonTbl { const DExon* e = nullptr; uint32_t n = 0; };
+// SpliceSiteDB::insideExon splice_site.cpp:508-526: from the lower bound of (tidx, l + 1, 0) backwards, stopping at the FIRST exon whose
+// right end lies before l even when an earlier one would hold [l, r] — and without a text check, as the reference walks its one sorted list.
+H2G_HD bool exon_inside(const DExonTbl& t, uint32_t tidx, uint32_t l, uint32_t r) {
+	uint32_t x = 0, y = t.n;
+	while(x < y) {
+		const uint32_t m = x + ((y - x) >> 1);
+		const DExon& e = t.e[m];
+		const bool less = e.tidx != tidx ? e.tidx < tidx : e.left != l + 1 ? e.left < l + 1 : false;   // e < (tidx, l + 1, 0): right >= 0 always
+		if(less) x = m + 1; else y = m;
+	}
+	for(; x > 0; x--) {
+		const DExon& e = t.e[x - 1];
+		if(e.right < l) break;
+		if(e.left <= l && r <= e.right) return true;
+	}
+	return false;
+}
 // MaxIntronLen / MaxIntronLen_noncan hi_aligner.h:48-79
 H2G_HD uint32_t max_intron_len(uint32_t anchor, uint32_t minAnchorLen) {
 	if(anchor < minAnchorLen) return 0;

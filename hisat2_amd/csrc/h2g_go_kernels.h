@@ -152,9 +152,18 @@ __device__ __forceinline__ unsigned long long mach_rings_of_op(uint32_t op) {
 #define H2G_GO_TOPUP 40      // a trip that popped fewer slots than this from the longest ring is topped up from the other rings of the same primitive
 #endif
 
+// The index's exons (--avoid-pseudogene) are a kernel argument of their own behind GoArgs, in the units that read them (H2G_EXT_OPTS): the
+// other units keep their argument block, and with it their code
+#if H2G_EXT_OPTS
+#define H2G_GO_EXONS_PARAM , DExonTbl X
+#define H2G_GO_EXONS_ARG(x_) , *(x_)
+#else
+#define H2G_GO_EXONS_PARAM
+#define H2G_GO_EXONS_ARG(x_)
+#endif
 // UNIT tells the builds of different translation units (capacities) apart: same template arguments would be ONE symbol
 template <bool GRAPH, int WAVES_PER_SIMD, int UNIT>
-__global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A)
+__global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A H2G_GO_EXONS_PARAM)
 {
 	extern __shared__ uint32_t s_mem[];
 	GoLds* Q = reinterpret_cast<GoLds*>(s_mem);
@@ -175,6 +184,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A)
 	C.ssdb = &A.ssdb; C.rdid_base = A.rdid_base;
 #if H2G_EXT_OPTS
 	ctx_ext_opts(C, A.P);
+	C.exons = &X;
 #endif
 	C.alts = &A.alts; C.gws = A.gws_base ? (GraphWS*)(A.gws_base + tid * A.gws_stride) : nullptr; C.graph = GRAPH;
 	const size_t slot0 = (size_t)blockIdx.x * H2G_GO_SLOTS;
@@ -342,10 +352,10 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A)
 	extern "C" void h2g_go_geometry_##NAME(uint32_t* g) { g[0] = H2G_GO_THREADS; g[1] = H2G_GO_SLOTS; \
 		g[2] = (uint32_t)((sizeof(GoLds) + 3) / 4 * 4); g[3] = H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; /* LDS: rings + one pack region per mate */ } \
 	extern "C" void h2g_go_caps_##NAME(uint32_t* c) { c[0] = AL_MAX_GHITS; c[1] = AL_MAX_RESULTS; c[2] = AL_MAX_SEARCHED; c[3] = AL_MAX_DEPTH; c[4] = AL_MAX_PARTIAL; } \
-	extern "C" int h2g_go_launch_##NAME(const GoArgs* a, unsigned grid, hipStream_t st) { \
+	extern "C" int h2g_go_launch_##NAME(const GoArgs* a, const DExonTbl* x, unsigned grid, hipStream_t st) { \
 		const unsigned lds = (unsigned)((sizeof(GoLds) + 3) / 4 * 4) + (a->paired ? 2u : 1u) * H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; \
 		static std::atomic<unsigned long long> lds_ok{0};   /* more than 64 KB of dynamic LDS is an opt-in, per device: a mask over device ids */ \
 		int dev_ = 0; (void)hipGetDevice(&dev_); const unsigned long long bit_ = 1ull << (dev_ & 63); \
 		if(!(lds_ok.load(std::memory_order_relaxed) & bit_)) { if(hipFuncSetAttribute((const void*)k_go<GRAPH, WAVES, UNIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit_, std::memory_order_relaxed); } \
-		hipLaunchKernelGGL((k_go<GRAPH, WAVES, UNIT>), dim3(grid), dim3(H2G_GO_THREADS), lds, st, *a); \
+		(void)x; hipLaunchKernelGGL((k_go<GRAPH, WAVES, UNIT>), dim3(grid), dim3(H2G_GO_THREADS), lds, st, *a H2G_GO_EXONS_ARG(x)); \
 		return (int)hipGetLastError(); }

@@ -51,6 +51,7 @@ struct h2g_index {
 	bool has_splice_alts = false;                         // the ALT list holds splice sites / exons (a _tran index)
 	std::vector<h2g_splice_site> alt_sites;               // splice-site ALTs of a --ss index: part of every database (SpliceSiteDB::read(gfm, alts))
 	DSpliceDB dssdb;                                       // h2g_index_set_splice_sites (device arrays; freed and replaced on every call)
+	DExonTbl dexons;                                       // the exons of a --ss/--exon index (--avoid-pseudogene); n == 0 without
 	void* d_ssdb[4] = {nullptr, nullptr, nullptr, nullptr};
 	size_t ssdb_cap[4] = {0, 0, 0, 0};                     // bytes behind each (they grow by doubling: temporary splice sites arrive wave after wave)
 	HostSpliceDB h_ssdb;                                   // the host copy h2g_index_add_splice_sites merges into
@@ -346,6 +347,14 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 		// a --ss index: its splice-site ALTs are graph edges AND known sites of the database (SpliceSiteDB::read(gfm, alts))
 		splice_sites_of_alts(reinterpret_cast<const uint32_t*>(ix->host.alts.data()), ix->host.alts.size(), sizeof(HostAlt) / 4, g.rstarts.data(), g.nFrag, g.p.len, ix->alt_sites);
 		for(const HostAlt& a : ix->host.alts) if(a.type == 5) ix->dalts.has_splice = 1;
+		// ... and its exons, for --avoid-pseudogene (SpliceSiteDB::insideExon): allocated only when the index has some
+		std::vector<DExon> ex;
+		exons_of_alts(reinterpret_cast<const uint32_t*>(ix->host.alts.data()), ix->host.alts.size(), sizeof(HostAlt) / 4, g.rstarts.data(), g.nFrag, g.p.len, g.plen.data(), g.nPat, ex);
+		if(!ex.empty()) {
+			const DExon* de = nullptr;
+			if((s = upload(ix, ex, &de))) { h2g_index_free(ix); return s; }
+			ix->dexons.e = de; ix->dexons.n = (uint32_t)ex.size();
+		}
 	}
 	memset(&ix->dls, 0, sizeof ix->dls);
 	if(tlocal.joinable()) tlocal.join();
@@ -1995,7 +2004,7 @@ static int need_alignable(h2g_stream* s) {
 
 // the go() units: [linear?][big?]
 struct GoUnit {
-	size_t (*ws_bytes)(); size_t (*gws_bytes)(); int (*waves)(); void (*caps)(uint32_t*); int (*launch)(const GoArgs*, unsigned, hipStream_t);
+	size_t (*ws_bytes)(); size_t (*gws_bytes)(); int (*waves)(); void (*caps)(uint32_t*); int (*launch)(const GoArgs*, const DExonTbl*, unsigned, hipStream_t);
 	size_t (*slot_off)(); size_t (*gsl_off)(); void (*geometry)(uint32_t*); size_t (*sw_bytes)(uint32_t, int);
 };
 static const GoUnit& go_unit(bool linear, bool big, bool spliced = false) {
@@ -2067,7 +2076,8 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	const bool linear = s->ix->dg.linear != 0;
 	// --haplotype is compiled into the units that also carry the splice-site database (H2G_HAPLOTYPE, h2g_graph.h); they run either mode
 	// ... and so are -I, --rf / --ff, --nofw / --norc (H2G_EXT_OPTS, h2g_align.h)
-	const bool ext_opts = pe_flags_from(*p) != H2G_PE_DEFAULT || p->min_frag_len != 0;
+	// ... and --avoid-pseudogene / --tmo (al_report's transcriptome policy; --tmo also under --no-spliced-alignment)
+	const bool ext_opts = pe_flags_from(*p) != H2G_PE_DEFAULT || p->min_frag_len != 0 || p->transcriptome_mapping_only || (p->avoid_pseudogene && !p->no_spliced_alignment);
 	const bool spl = !p->no_spliced_alignment || (p->use_haplotype && !linear) || ext_opts;
 	if(!p->no_spliced_alignment) {
 		// spliced alignment: combineWith places introns (hi_aligner.h:1588-1739) and every read is independent when novel splice
@@ -2094,6 +2104,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		return H2G_ERR_ARG;
 	}
 	if(p->bowtie2_dp > 2 || p->pe_orientation > 2 || p->min_frag_len >= (1u << 24)) return H2G_ERR_ARG;
+	if(p->pen_conflictsplice < 0) { snprintf(g_err, sizeof g_err, "align: --pen-conflictsplice arg must be at least 0"); return H2G_ERR_ARG; }
 	if(p->max_alts_tried && p->max_alts_tried < 8) { snprintf(g_err, sizeof g_err, "align: --max-altstried arg must be at least 8"); return H2G_ERR_ARG; }
 	if(p->bowtie2_dp) {
 		if(s->max_read_len == 0) return H2G_ERR_ARG;
@@ -2134,6 +2145,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	if(paired) { A.rd2.codes = s->d_codes2; A.rd2.offs = s->d_offs2; A.rd2.quals = s->has_quals2 ? s->d_quals2 : nullptr; }
 	A.P = aln_params_from(*p, p->no_spliced_alignment != 0, linear);
 	if(!p->no_spliced_alignment) { A.ssdb = s->ix->dssdb; A.rdid_base = p->first_read_id; }
+	const DExonTbl X = p->no_spliced_alignment ? DExonTbl() : s->ix->dexons;   // (--avoid-pseudogene: the units that read it take it as an argument of its own)
 	if(!p->no_spliced_alignment) { A.P.sc.donor_sum = s->ix->d_spl[0]; A.P.sc.acc_sum1 = s->ix->d_spl[1]; A.P.sc.acc_sum2 = s->ix->d_spl[2]; }
 	A.names1 = s->d_names; A.noffs1 = s->d_name_offs; A.names2 = s->d_names2; A.noffs2 = s->d_name_offs2;
 	A.paired = paired ? 1u : 0u;
@@ -2465,19 +2477,19 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 			W1.list = s->d_ovf_list[m_]; W1.nlist = s->d_ovf_list[m_] + s->max_reads;                                       // a count of zero (memset on this stream above)
 			W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 124); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 126);
 			W1.defer_overflow = 0; W1.O.defer_list = nullptr; W1.O.defer_count = nullptr;
-			if(U.launch(&W1, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+			if(U.launch(&W1, &X, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 			if(second) {
 				GoArgs W2 = W1;
 				if((rc = go_pool_for(s, 2 * (int)m_ + 1, Bw, (size_t)wgeo[1], (size_t)wgeo[0], p->bowtie2_dp, &W2))) return rc;
 				W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 15);
-				if(Bw.launch(&W2, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+				if(Bw.launch(&W2, &X, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 			}
 		}
 		s->st2_busy = true;
 		s->mstreams_warm = true;
 	}
 	HIPCHK(hipEventRecord(s->ev[7], ms));
-	if(U.launch(&A, mach_grid, ms) != 0) return set_err("go() launch", hipGetLastError());
+	if(U.launch(&A, &X, mach_grid, ms) != 0) return set_err("go() launch", hipGetLastError());
 	HIPCHK(hipEventRecord(s->ev[6], ms));
 	if(second) {
 		const GoUnit& B = go_unit(linear, true, spl);
@@ -2490,7 +2502,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		A2.work = reinterpret_cast<uint32_t*>(cblk + 15);
 		A2.list = ovl; A2.nlist = cnt;
 		A2.defer_overflow = 0; A2.O.defer_list = nullptr; A2.O.defer_count = nullptr;
-		if(B.launch(&A2, bgrid, ms) != 0) return set_err("go() second pass launch", hipGetLastError());
+		if(B.launch(&A2, &X, bgrid, ms) != 0) return set_err("go() second pass launch", hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(s->ev[8], ms));
 	if(fast) HIPCHK(hipEventRecord(s->ev_mach[gsel], ms));

@@ -224,9 +224,11 @@ H2G_MACH_FN void mach_begin(Mach& M, uint32_t read, bool paired_input) {
 		gv.rc_cushion = (no_spliced && (MATE)) ? (int64_t)((double)mach_sv(M).len * 0.03 * (double)sc.mmpMax) : 0; \
 		M_GOTO(PC_RC_ENTRY); } while(0)
 #if H2G_EXT_OPTS
-#define H2G_XS_ONLY(P_) (((P_).xs_only & 1u) != 0)      // the upper bits carry -I and the pair orientation (aln_params_from)
+#define H2G_XS_ONLY(P_) (((P_).xs_only & 1u) != 0)      // the upper bits carry -I, the pair orientation and the transcriptome policy (aln_params_from)
+#define H2G_TPOL_ARGS(C_) , (C_).tpol, (C_).ssdb, (C_).exons   // al_report's transcriptome policy (--avoid-pseudogene, --tmo)
 #else
 #define H2G_XS_ONLY(P_) ((P_).xs_only != 0)
+#define H2G_TPOL_ARGS(C_)
 #endif
 // sink.bestSplicedUnp1/2() (aln_sink.h:2618-2637): the number of introns of the alignment that set bestUnp — the FIRST reported one with
 // that score, the update being a strict '>'.  nextBWT (hi_aligner.h:4680) and align (:5520) let a strand run that many more partial
@@ -400,7 +402,7 @@ again:
 		}
 		if(gv.mp_j >= gv.mp_rs[gv.mp_i]) { gv.mp_i++; gv.mp_j = 0; M_GOTO(PC_MP_LOOP); }
 		const AlnRec& r = ws->m[gv.mp_i].res[gv.mp_j];
-		const bool fw = r.fw != 0;
+		const bool fw = rec_fw(r.fw) != 0;
 		AL_TRACE(" alignMate anchor mate %u res %u fw %d toff %u\n", gv.mp_i, gv.mp_j, (int)fw, r.toff);
 		// alignMate hi_aligner.h:5579-5770: anchor the OTHER mate near (tidx, toff) through the local index
 		gv.am_fw = fw; gv.am_tidx = r.tidx; gv.am_toff = r.toff;
@@ -728,7 +730,7 @@ again:
 					M_GOTO(PC_FS_L_LOOP);
 				}
 #endif
-				al_report(ws, mw, &hit, rdlen, minsc, H2G_XS_ONLY(P));
+				al_report(ws, mw, &hit, rdlen, minsc, H2G_XS_ONLY(P) H2G_TPOL_ARGS(C));
 				if(hit.score > f.maxsc) f.maxsc = hit.score;
 			}
 			RC_RET(f.maxsc);
@@ -899,7 +901,7 @@ again:
 			if(!P.secondary && can->score < f.prev_score) continue;
 			if(i > 0 && !al_is_searched(mw, can)) al_add_searched(ws, mw, can);
 			if(!al_redundant(mw, can, rdlen)) {
-				al_report(ws, mw, can, rdlen, gv.rc_minsc, H2G_XS_ONLY(P));
+				al_report(ws, mw, can, rdlen, gv.rc_minsc, H2G_XS_ONLY(P) H2G_TPOL_ARGS(C));
 				if(can->score > f.maxsc) f.maxsc = can->score;
 			}
 		}
@@ -1609,7 +1611,8 @@ H2G_MACH_FN void mach_op_sw(const AlnCtx& C, Mach& M) {
 	}
 }
 
-// returns false when a long record found no room in the long-edit area (the caller flags the read)
+// returns false when a long record found no room in the long-edit area (the caller flags the read).  fw travels whole: under --avoid-pseudogene /
+// --tmo it carries the transcript class to the host (H2G_FW_TCLASS, include/h2g.h)
 H2G_HD bool mach_copy_rec(h2g_alnres& d, const AlnRec& r, const MachOut& O) {
 	d.fw = r.fw; d.tidx = r.tidx; d.toff = r.toff; d.len = r.len; d.trim5 = r.trim5; d.trim3 = r.trim3;
 	d.nedits = r.nedits; d.splicescore = r.splicescore; d.score = r.score;

@@ -94,6 +94,8 @@ inline const h2g_edit* ED(const h2g_alnres& r) {
 	if(!tl_long_edits || (size_t)r.edits[0].pos + r.nedits > tl_long_edits_n) return none;      // (format_* refuses such a batch before any line is written)
 	return tl_long_edits + r.edits[0].pos;
 }
+// the strand of a record: fw may carry the transcript class above it (H2G_FW_TCLASS, include/h2g.h)
+inline bool FW(const h2g_alnres& r) { return (r.fw & H2G_FW_STRAND) != 0; }
 int64_t hisat2_score(int64_t sc, uint32_t trim, int transcript = 0, uint32_t splicescore = 0) {
 	if(sc > INT32_MAX) sc = INT32_MAX; else if(sc < INT32_MIN) sc = INT32_MIN;
 	const int64_t t = trim > 0xFFFF ? 0 : 0xFFFF - (int64_t)trim;
@@ -104,9 +106,12 @@ int64_t hisat2_score(int64_t sc, uint32_t trim, int transcript = 0, uint32_t spl
 Score score_of(const h2g_alnres& r) {
 	Score s; s.valid = true; s.score = r.score;
 	int transcript = 0;                  // 2: every splice is a database site, 1: spliced (GenomeHit::spliced hi_aligner.h:1086)
-	bool all_known = true;
-	for(uint32_t i = 0; i < r.nedits; i++) if(ED(r)[i].type == EDIT_SPL) { transcript = 1; all_known = all_known && (ED(r)[i].pad >> 7) != 0; }
-	if(transcript && all_known) transcript = 2;
+	if(r.fw & H2G_FW_TCLASS) transcript = (int)((r.fw >> H2G_FW_TCLASS_SHIFT) & 3u);   // the class reportHit gave it (--avoid-pseudogene / --tmo)
+	else {
+		bool all_known = true;
+		for(uint32_t i = 0; i < r.nedits; i++) if(ED(r)[i].type == EDIT_SPL) { transcript = 1; all_known = all_known && (ED(r)[i].pad >> 7) != 0; }
+		if(transcript && all_known) transcript = 2;
+	}
 	s.h2 = hisat2_score(r.score, r.trim5 + r.trim3, transcript, r.splicescore);
 	return s;
 }
@@ -197,7 +202,7 @@ void stack_alignment(const h2g_alnres& r, const std::string& seq /* aligned stra
 	// h2g_alnres trims are those of the GenomeHit (left / right of the aligned strand) == trimLS / trimRS after the swap
 	st.trimLS = r.trim5; st.trimRS = r.trim3;
 	const uint32_t len_trimmed = (uint32_t)seq.size() - st.trimLS - st.trimRS;
-	if(!r.fw) invert(ed, len_trimmed);
+	if(!FW(r)) invert(ed, len_trimmed);
 	st.ref.clear(); st.rel.clear(); st.read.clear(); st.snp.clear(); st.skip.clear();
 	size_t rdoff = st.trimLS;
 	auto match_to = [&](size_t pos) { while(rdoff < pos) { const char c = seq[rdoff++]; st.ref.push_back(c); st.rel.push_back('='); st.snp.push_back(0); st.read.push_back(c); } };
@@ -312,8 +317,8 @@ int64_t fragment_length(const h2g_alnres& me, const h2g_alnres& o, bool meMate1,
 	bool imUpstream;
 	if(st < ost) imUpstream = true;
 	else if(st == ost) {
-		if(me.fw && o.fw && meMate1) imUpstream = true;
-		else if(me.fw && !o.fw) imUpstream = true;
+		if(FW(me) && FW(o) && meMate1) imUpstream = true;
+		else if(FW(me) && !FW(o)) imUpstream = true;
 		else imUpstream = false;
 	} else imUpstream = false;
 	const int64_t up = imUpstream ? std::min(st2, ost) : std::min(st, ost2);
@@ -352,7 +357,7 @@ void add_splice_sites(const h2g_alnres& r, uint32_t rdlen, uint64_t rdid, std::v
 	for(uint32_t i = 0; i < r.nedits; i++) { ed[i].pos = ED(r)[i].pos; ed[i].chr = (char)ED(r)[i].chr; ed[i].qchr = (char)ED(r)[i].qchr; ed[i].type = ED(r)[i].type; ed[i].snp = ED(r)[i].snp; ed[i].skip = ED(r)[i].type == EDIT_SPL ? spl_len(ED(r)[i]) : 0; }
 	std::vector<uint32_t> dirs(r.nedits);
 	for(uint32_t i = 0; i < r.nedits; i++) dirs[i] = spl_dir(ED(r)[i]);
-	if(!r.fw) { invert(ed, rdlen); std::reverse(dirs.begin(), dirs.end()); }
+	if(!FW(r)) { invert(ed, rdlen); std::reverse(dirs.begin(), dirs.end()); }
 	const uint32_t minAnchorLen = 15, SPL_UNKNOWN = 1;
 	auto is_mm_gap = [](const Ed& e) { return e.type == EDIT_MM || e.type == EDIT_READ_GAP || e.type == EDIT_REF_GAP; };
 	uint32_t editdist = 0;
@@ -400,7 +405,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	if(rs == nullptr && S.no_unal) return;                 // aln_sink.h:3040
 	static thread_local Stacked st;                       // scratch reused across lines (no per-line allocations)
 	static thread_local std::string seq, qual;
-	seq_ascii(rd, rs == nullptr || rs->fw, seq, qual);
+	seq_ascii(rd, rs == nullptr || FW(*rs), seq, qual);
 	// an alignment whose edits are all mismatches (nearly every line) needs no stacked form: its CIGAR is one M run between the soft
 	// clips and its MD:Z follows from the mismatch positions; what buildCigar / buildMdz would make of the stacked strings is written directly
 	bool simple = rs != nullptr;
@@ -415,10 +420,10 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 		if(fl.concordant()) f |= 2;
 		if(!fl.oppAligned) f |= 8;
 		f |= fl.readMate1() ? 0x40 : 0x80;
-		if(fl.oppAligned && rso != nullptr && !rso->fw) f |= 0x20;
+		if(fl.oppAligned && rso != nullptr && !FW(*rso)) f |= 0x20;
 	}
 	if(!fl.primary) f |= 0x100;
-	if(rs && !rs->fw) f |= 0x10;
+	if(rs && !FW(*rs)) f |= 0x10;
 	if(!rs) f |= 4;
 	put(o, f); o.push_back('\t');
 	if(rs) put_ref_name(o, S.refnames[rs->tidx]);
@@ -491,8 +496,8 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 		const uint32_t lt = rd.len - rs->trim5 - rs->trim3;
 		uint32_t at = 0;                                               // the next position of the aligned strand not yet accounted for
 		for(uint32_t k = 0; k < rs->nedits; k++) {
-			const h2g_edit& e = ED(*rs)[rs->fw ? k : rs->nedits - 1 - k];
-			const uint32_t pos = rs->fw ? e.pos : lt - 1 - e.pos;
+			const h2g_edit& e = ED(*rs)[FW(*rs) ? k : rs->nedits - 1 - k];
+			const uint32_t pos = FW(*rs) ? e.pos : lt - 1 - e.pos;
 			if(pos > at) put(o, (int64_t)(pos - at)); else o.push_back('0');
 			o.push_back((char)e.chr);
 			at = pos + 1;
@@ -508,8 +513,8 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 		char strand = '+';
 		const bool m1 = fl.pairing == PAIR_UNPAIRED || fl.readMate1();   // unpaired reads are ALN_RES_TYPE_UNPAIRED_MATE1 (aln_sink.h:2368)
 		const int rs_ = S.rna_strandness;
-		if(m1) { if(rs->fw) { if(rs_ == 2 || rs_ == 4) strand = '-'; } else if(rs_ == 1 || rs_ == 3) strand = '-'; }
-		else   { if(rs->fw) { if(rs_ == 3) strand = '-'; } else if(rs_ == 4) strand = '-'; }
+		if(m1) { if(FW(*rs)) { if(rs_ == 2 || rs_ == 4) strand = '-'; } else if(rs_ == 1 || rs_ == 3) strand = '-'; }
+		else   { if(FW(*rs)) { if(rs_ == 3) strand = '-'; } else if(rs_ == 4) strand = '-'; }
 		o += "\tXS:A:"; o.push_back(strand);
 	} else {   // XS:A: sam.h:925-940 with AlnRes::spliced_whichsense_transcript aligner_result.h:1289 (unstranded library)
 		uint32_t sense = 1;
@@ -531,7 +536,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 		ed.resize(rs->nedits);
 		for(uint32_t i = 0; i < rs->nedits; i++) { ed[i].pos = ED(*rs)[i].pos; ed[i].type = ED(*rs)[i].type; ed[i].snp = ED(*rs)[i].type == EDIT_SPL ? 0xffffffffu : ED(*rs)[i].snp /* a splice edit keeps its probscore there */; ed[i].chr = ed[i].qchr = 0; }
 		const uint32_t len_trimmed = rd.len - rs->trim5 - rs->trim3;
-		if(!rs->fw) invert(ed, len_trimmed);
+		if(!FW(*rs)) invert(ed, len_trimmed);
 		bool snp_first = true;
 		uint32_t prev = 0xffffffffu;
 		for(size_t i = 0; i < ed.size(); i++) {

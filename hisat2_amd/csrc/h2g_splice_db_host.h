@@ -111,30 +111,59 @@ inline void merge_splice_db(HostSpliceDB& db, const h2g_splice_site* delta, size
 // SpliceSiteDB::read(gfm, alts) splice_site.cpp:653-725: the splice-site ALTs of a --ss index enter the database as known sites
 // read from a file (the forward copies only: left < right); joined coordinates become (text, offset), exon flanks = left - 1 / right + 1.
 // `rstarts` = GFM::rstarts() (nFrag triples), `len` = the joined length.
+// GFM::joinedToTextOff(1, off, ..., rejectStraddle = true) gfm.h:5527-5599: false when `off` lies in no fragment
+inline bool joined_to_text(const uint32_t* rstarts, uint32_t nFrag, uint32_t joined_len, uint32_t off, uint32_t& tidx, uint32_t& toff) {
+	uint32_t top = 0, bot = nFrag, elt = 0xffffffffu;
+	tidx = 0xffffffffu; toff = 0;
+	while(true) {
+		const uint32_t oldelt = elt;
+		elt = top + ((bot - top) >> 1);
+		if(oldelt == elt) break;
+		const uint32_t lower = rstarts[elt * 3], upper = (elt == nFrag - 1) ? joined_len : rstarts[(elt + 1) * 3];
+		if(lower <= off) {
+			if(upper > off) { if(off + 1 <= upper) { tidx = rstarts[elt * 3 + 1]; toff = (off - lower) + rstarts[elt * 3 + 2]; } break; }
+			top = elt;
+		} else bot = elt;
+	}
+	return tidx != 0xffffffffu;
+}
 inline void splice_sites_of_alts(const uint32_t* alts /* {pos, type, len, pad, seq lo, seq hi} x n */, size_t n, size_t stride_words,
                                  const uint32_t* rstarts, uint32_t nFrag, uint32_t joined_len, std::vector<h2g_splice_site>& out) {
 	for(size_t i = 0; i < n; i++) {
 		const uint32_t* a = alts + i * stride_words;
 		const uint32_t left_j = a[0], type = a[1], right_j = a[2];
-		if(type != 5) continue;                                    // ALT_SPLICESITE (exons only matter under --avoid-pseudogene)
+		if(type != 5) continue;                                    // ALT_SPLICESITE (the exons: exons_of_alts)
 		if(left_j > right_j) continue;
-		// joinedToTextOff(1, left, ..., rejectStraddle = true)
-		uint32_t top = 0, bot = nFrag, elt = 0xffffffffu, tidx = 0xffffffffu, toff = 0;
-		while(true) {
-			const uint32_t oldelt = elt;
-			elt = top + ((bot - top) >> 1);
-			if(oldelt == elt) break;
-			const uint32_t lower = rstarts[elt * 3], upper = (elt == nFrag - 1) ? joined_len : rstarts[(elt + 1) * 3];
-			if(lower <= left_j) {
-				if(upper > left_j) { if(left_j + 1 <= upper) { tidx = rstarts[elt * 3 + 1]; toff = (left_j - lower) + rstarts[elt * 3 + 2]; } break; }
-				top = elt;
-			} else bot = elt;
-		}
-		if(tidx == 0xffffffffu) continue;
+		uint32_t tidx, toff;
+		if(!joined_to_text(rstarts, nFrag, joined_len, left_j, tidx, toff)) continue;
 		h2g_splice_site x;
 		x.tidx = tidx; x.left = toff - 1; x.right = toff + (right_j - left_j) + 1; x.readid = 0;
 		x.dir = (a[4] & 0xff) ? 2 : 3; x.fromfile = 1; x.known = 1; x.editdist = 0;   // SPL_FW : SPL_RC
 		out.push_back(x);
 	}
+}
+// ... and its ALT_EXON entries (splice_site.cpp:708-716): (text, left - 10, right + 10), clamped to [0, plen[text] - 1], sorted by
+// (text, left, right) — DExonTbl (h2g_core.h).  Empty for an index without exons.
+inline void exons_of_alts(const uint32_t* alts, size_t n, size_t stride_words, const uint32_t* rstarts, uint32_t nFrag, uint32_t joined_len,
+                          const uint32_t* plen, uint32_t nPat, std::vector<DExon>& out) {
+	out.clear();
+	for(size_t i = 0; i < n; i++) {
+		const uint32_t* a = alts + i * stride_words;
+		const uint32_t left_j = a[0], type = a[1], right_j = a[2];
+		if(type != 6) continue;                                    // ALT_EXON alt.h:39
+		if(left_j > right_j) continue;
+		uint32_t tidx, left;
+		if(!joined_to_text(rstarts, nFrag, joined_len, left_j, tidx, left) || tidx >= nPat) continue;
+		const uint32_t tlen = plen[tidx];
+		uint32_t right = left + (right_j - left_j);
+		left = left >= 10 ? left - 10 : 0;
+		right = right + 10 < tlen ? right + 10 : tlen - 1;
+		out.push_back(DExon{tidx, left, right});
+	}
+	std::sort(out.begin(), out.end(), [](const DExon& x, const DExon& y) {
+		if(x.tidx != y.tidx) return x.tidx < y.tidx;
+		if(x.left != y.left) return x.left < y.left;
+		return x.right < y.right;
+	});
 }
 }  // namespace h2g

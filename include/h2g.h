@@ -273,9 +273,16 @@ H2G_EXPORT h2g_status h2g_seed_extend_fetch(h2g_stream*, h2g_seed_result* out, s
  * filters: rnd.init(genRandSeed(read)) (pat.h:55), splicedAligner.go(...) (hi_aligner.h:4048), and the selection
  * half of AlnSinkWrap::finishRead (aln_sink.h:1939 -> selectByScore :2680).  Built so far: linear (HFM) and SNP-graph
  * (GFM + ALT database) indexes, --no-spliced-alignment, default scoring, --bowtie2-dp 0/1/2. */
+#define H2G_FW_STRAND 1u
+#define H2G_FW_TCLASS 2u
+#define H2G_FW_TCLASS_SHIFT 2
 #define H2G_ALN_CAP 10             /* alignments returned per read (>= -k: 5 on linear, 10 on graph indexes) */
 typedef struct {                   /* == the arguments reportHit (hi_aligner.h:6064-6166) passes to AlnRes::init */
 	uint32_t fw, tidx, toff, len, trim5, trim3, nedits, splicescore;   /* splicescore: AlnScore::splicescore_ (aligner_result.h:322) */
+	/* fw: bit 0 (H2G_FW_STRAND) is the strand, 1 = patFw.  Under avoid_pseudogene / transcriptome_mapping_only bit 1 (H2G_FW_TCLASS) is set
+	 * and bits 2-3 hold the transcript class reportHit gave the alignment (0 none, 1 spliced or near splice sites, 2 known transcripts:
+	 * AlnScore::calculate_hisat2_score bits 24-27, aligner_result.h:335-337); without those options fw is 0 / 1 and the class follows from
+	 * the splice edits (2: every splice a database site, 1: spliced).  Read the strand as (fw & H2G_FW_STRAND). */
 	int64_t  score;                /* AS:i */
 	h2g_edit edits[H2G_MAX_EDITS]; /* as stored in the AlnRes (aligner_result.cpp:110-118): positions along the original read
 	                                * 5'->3', relative to its first aligned (non-soft-clipped) base */
@@ -329,6 +336,14 @@ typedef struct {
 	 * the strand pair a concordant pair has, hi_aligner.h:5605, :6003, pe.cpp:59-83); --nofw / --norc: the strand of the READ (of mate 1's
 	 * fragment strand for pairs, hisat2.cpp:3449-3452) that is not searched (hi_aligner.h:4875) */
 	uint32_t min_frag_len, pe_orientation, nofw, norc;
+	/* TranscriptomePolicy (tp.h) in reportHit (hi_aligner.h:6105-6127).  avoid_pseudogene (--avoid-pseudogene, spliced alignment only): an
+	 * unspliced alignment with a splice site of the database within 10 kbp of either end ranks as "near splice sites", one inside an exon of the
+	 * index (widened by 10) as "known transcripts" (AlnScore bits 24-27: the tie-break between equally scored placements).
+	 * transcriptome_mapping_only (--tmo): only alignments spliced through known sites only, or (with avoid_pseudogene) inside an exon, are
+	 * reported.  no_anchorstop (--no-anchorstop): anchorStop = false (hisat2.cpp:1710).  pen_conflictsplice (--pen-conflictsplice, >= 0,
+	 * default 1000000): Scoring::csp, the penalty of an alignment whose splices disagree in direction. */
+	uint32_t avoid_pseudogene, transcriptome_mapping_only, no_anchorstop;
+	int32_t  pen_conflictsplice;
 } h2g_align_params;
 /* number of visible HIP devices (0 without a GPU: the library has no CPU path) */
 H2G_EXPORT int        h2g_device_count(void);
