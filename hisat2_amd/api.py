@@ -338,6 +338,10 @@ class AlignParams(C.Structure):
 
 PAIR_RES_CAP = 16
 PAIR_CAP = 32
+KHITS_MAX = 128              # h2g_align_*run's range: 1 <= khits <= KHITS_MAX, khits <= kseeds <= KSEEDS_MAX (include/h2g.h)
+KSEEDS_MAX = 256
+PAIR_TRAILER_TAG = 0x52494150   # nedits of the concordant-list trailer behind mate 1's compact records (XL runs)
+OVF_PAIR_LIST = 4096         # overflow bit of the slot / dense paired fetches: the pair's list only travels compact
 
 
 class PairResult(C.Structure):

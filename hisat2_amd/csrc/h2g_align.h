@@ -36,6 +36,9 @@ namespace h2g {
 #define AL_MAX_PARTIAL  16
 #endif
 #define H2G_SELECT_CAP 32      // alignments selected per read: >= the largest -k (30: --very-sensitive); fixed in every unit
+#ifndef H2G_XL
+#define H2G_XL 0               // 1 in the extra-large units (h2g_go_xl.h): -k above H2G_SELECT_CAP, selection and pair lists in the workspace
+#endif
 
 // ---------------------------------------------------------------------------------------- local indexes (a13)
 // LocalGFM (hgfm.h:35): 16-bit words.  Linear local side = 64 B = 56 B payload (224 symbols) + u16 occ[4].
@@ -855,7 +858,23 @@ struct RBHit {               // ReadBWTHit hi_aligner.h:216 (the BWTHit list its
 	PartialHit* partial;     // -> MateArr::partial[strand]
 };
 
-#define AL_MAX_PAIRS 32
+#define AL_MAX_PAIRS 32         // concordant pairs PairOut carries (H2G_PAIR_CAP)
+#ifndef AL_WS_PAIRS
+#define AL_WS_PAIRS AL_MAX_PAIRS   // concordant pairs the workspace holds: the XL units keep the whole list (h2g_go_xl.h)
+#endif
+#if H2G_XL
+typedef uint16_t al_pidx_t;     // a mate's report list passes 255 rows at large -k
+#else
+typedef uint8_t al_pidx_t;
+#endif
+// The XL units' side area of the stream for the concordant lists PairOut cannot carry (more than AL_MAX_PAIRS pairs, or an index past 255):
+// at[read] = 0, or 1 + the list's start in `list`; a list is its length, then one word per pair, mate-1 index | mate-2 index << 16
+struct XlPairs {
+	uint32_t* at;
+	uint32_t* list;
+	uint32_t* cursor;
+	uint32_t  cap;                // end of this run's part of `list` (words)
+};
 struct MateArr {             // the big lists of one mate (cold part of the workspace)
 	PartialHit partial[2][AL_MAX_PARTIAL];       // _hits[rdi][fwi]
 	h2g_ghit   searched[AL_MAX_SEARCHED];        // _hits_searched[rdi]
@@ -911,13 +930,17 @@ struct AlignWS {
 	uint64_t   localindexatts, max_localindexatts;
 	uint32_t   overflow;
 	uint32_t   nrank, nside, nsteps, nframes_max;   // nrank, nside adjacent: gfm_search updates both through &nrank
-	uint8_t    pair_i[AL_MAX_PAIRS], pair_j[AL_MAX_PAIRS];
+	al_pidx_t  pair_i[AL_WS_PAIRS], pair_j[AL_WS_PAIRS];
 	// ---- lists
 	h2g_ghit   tmp, tmp2;                        // scratch hits
 	h2g_ghit   ghits[AL_MAX_GHITS];              // _genomeHits (hitcount lives in .read)
 	h2g_coord  am_co[AL_MAX_GHITS];              // alignMate's coordinate list
 	Frame      stack[AL_MAX_DEPTH];
 	MateArr    marr[2];
+#if H2G_XL
+	int64_t    sel_key[AL_MAX_RESULTS];          // al_select's sort, and the selection it leaves: sel_idx[0 .. nselect)
+	uint16_t   sel_idx[AL_MAX_RESULTS];
+#endif
 };
 
 // Edit::invertPoss edit.cpp:70-111 applied to the k-th element of the inverted list
@@ -1040,6 +1063,9 @@ struct AlnCtx {
 	uint32_t pe_flags = H2G_PE_DEFAULT, min_frag_len = 0;
 	uint32_t tpol = 0;                // H2G_TP_AVOID_PSEUDOGENE | H2G_TP_TMO
 	const DExonTbl* exons = nullptr;  // the index's exons (--ss/--exon index); nullptr or n == 0: none
+#endif
+#if H2G_XL
+	const XlPairs* xlp = nullptr;     // the side area of the concordant lists (paired runs)
 #endif
 };
 #if H2G_EXT_OPTS
@@ -1305,7 +1331,7 @@ H2G_HD void al_pair_reads(const AlnParams& P, AlignWS* ws, uint32_t rdlen1, uint
 				}
 				const int64_t score = r1.score + r2.score;
 				if(score >= threshold || P.secondary) {   // sink.report(0, &r1, &r2) aln_sink.h:2590-2612
-					if(ws->npairs < AL_MAX_PAIRS) { ws->pair_i[ws->npairs] = (uint8_t)i; ws->pair_j[ws->npairs] = (uint8_t)j; ws->npairs++; }
+					if(ws->npairs < AL_WS_PAIRS) { ws->pair_i[ws->npairs] = (al_pidx_t)i; ws->pair_j[ws->npairs] = (al_pidx_t)j; ws->npairs++; }
 					else ws->overflow |= 128;
 					if(score > ws->bestPair) { ws->best2Pair = ws->bestPair; ws->bestPair = score; }
 					else if(score > ws->best2Pair) ws->best2Pair = score;
@@ -1377,6 +1403,63 @@ H2G_HD uint32_t al_select(const MateWS* ws, const AlnParams& P, Rng* rnd, uint8_
 	}
 	return nsel;
 }
+
+#if H2G_XL
+// al_select for the XL units: the same key, order and shufflePortion draws over up to AL_MAX_RESULTS results, sorted in O(R log R) by a heap sort
+// (the insertion sort above costs R^2 / 4 steps of one lane: 65 000 at 512 results).  The order is total — key descending, then index descending, which
+// is what buf.sort(); buf.reverse() leaves and what the insertion sort keeps — so any correct sort gives the same sequence.  The selection stays in the
+// workspace: ws->sel_idx[0 .. return value), 16-bit indexes into m.res.
+H2G_HD bool al_sel_before(const int64_t* key, const uint16_t* idx, uint32_t a, uint32_t b) {   // a sorts before b
+	return key[a] > key[b] || (key[a] == key[b] && idx[a] > idx[b]);
+}
+H2G_HD void al_sel_sift(int64_t* key, uint16_t* idx, uint32_t root, uint32_t n) {   // max-heap of "sorts after": the last element of the order at the root
+	for(;;) {
+		uint32_t c = 2 * root + 1;
+		if(c >= n) return;
+		if(c + 1 < n && al_sel_before(key, idx, c, c + 1)) c++;
+		if(!al_sel_before(key, idx, root, c)) return;
+		const int64_t tk = key[root]; key[root] = key[c]; key[c] = tk;
+		const uint16_t ti = idx[root]; idx[root] = idx[c]; idx[c] = ti;
+		root = c;
+	}
+}
+H2G_HD uint32_t al_select_xl(AlignWS* aw, const MateWS* ws, const AlnParams& P, Rng* rnd) {
+	const uint32_t sz = ws->nres;
+	if(sz < 1) return 0;
+	const uint32_t num = P.khits < sz ? P.khits : sz;
+	int64_t* const key = aw->sel_key;
+	uint16_t* const idx = aw->sel_idx;
+	for(uint32_t i = 0; i < sz; i++) { key[i] = hisat2_score(ws->res[i]); idx[i] = (uint16_t)i; }
+	for(uint32_t r = sz / 2; r-- > 0;) al_sel_sift(key, idx, r, sz);
+	for(uint32_t end = sz; end > 1;) {
+		end--;
+		const int64_t tk = key[0]; key[0] = key[end]; key[end] = tk;
+		const uint16_t ti = idx[0]; idx[0] = idx[end]; idx[end] = ti;
+		al_sel_sift(key, idx, 0, end);
+	}
+	uint32_t streak = 0;                      // shufflePortion over streaks of equal score, as al_select
+	for(uint32_t i = 1; i <= sz; i++) {
+		if(i < sz && key[i] == key[i - 1]) { if(streak == 0) streak = 1; streak++; }
+		else {
+			if(streak > 1) {
+				const uint32_t begin = i - streak;
+				uint32_t left = streak;
+				for(uint32_t q = begin; q + 1 < begin + streak; q++) {
+					uint32_t r = rnd->nextU32() % left;
+					if(r > 0) { int64_t tk = key[q]; key[q] = key[q + r]; key[q + r] = tk; uint16_t ti = idx[q]; idx[q] = idx[q + r]; idx[q + r] = ti; }
+					left--;
+				}
+			}
+			streak = 0;
+		}
+	}
+	uint32_t nsel = num;
+	if(!P.secondary) {
+		for(uint32_t i = 0; i + 1 < nsel; i++) if(key[i] != key[i + 1]) { nsel = i + 1; break; }
+	}
+	return nsel;
+}
+#endif
 
 // Whole per-read pipeline of the worker loop body (hisat2.cpp:3380-3640) for an unpaired read that passed
 // the filters: seed the PRNG, go(), select.

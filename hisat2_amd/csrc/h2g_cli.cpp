@@ -265,6 +265,7 @@ int main(int argc, char** argv) {
 	uint32_t trim5 = 0, trim3 = 0;
 	uint32_t dp = 0;
 	size_t batch = 1u << 20;
+	bool saw_batch = false;
 	int device = 0, threads = 1, gpus = 1;
 	uint32_t ss_window_opt = 0;
 	std::string cmdline;
@@ -335,7 +336,7 @@ int main(int argc, char** argv) {
 		else if(a == "--sensitive") sensitive = true;
 		else if(a == "--very-sensitive") very_sensitive = true;
 		else if(a == "--no-hd" || a == "--no-head") nohead = true;
-		else if(a == "--batch") batch = (size_t)atoll(need("--batch"));
+		else if(a == "--batch") { batch = (size_t)atoll(need("--batch")); saw_batch = true; }
 		else if(a == "--device") device = atoi(need("--device"));
 		else if(a == "--gpus") gpus = atoi(need("--gpus"));                        // batches round-robin over <int> devices, output in read order
 		else if(a == "-s" || a == "--skip") skip = (uint64_t)atoll(need("-s"));     // skip the first <int> reads / pairs (hisat2.cpp:3319)
@@ -531,10 +532,15 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "--min-intronlen(%u) should not be greater than --max-intronlen(%u)\n", P.min_intronlen, P.max_intronlen);
 		return 1;
 	}
-	if(P.khits > 30 || P.kseeds > 64 || P.kseeds < P.khits) {
-		fprintf(stderr, "hisat2-align-amd: -k %u / --max-seeds %u is outside the built range (-k <= 30, -k <= --max-seeds <= 64)\n", P.khits, P.kseeds);
+	if(P.khits < 1 || P.khits > H2G_KHITS_MAX || P.kseeds > H2G_KSEEDS_MAX || P.kseeds < P.khits) {
+		fprintf(stderr, "hisat2-align-amd: -k %u / --max-seeds %u is outside the built range (1 <= -k <= %u, -k <= --max-seeds <= %u)\n", P.khits, P.kseeds,
+		        (unsigned)H2G_KHITS_MAX, (unsigned)H2G_KSEEDS_MAX);
 		return 1;
 	}
+	// -k above 32 or --max-seeds above 64 runs on the extra-large units, whose result rows grow with -k (2 k + 4 records of 424 bytes per mate and pair):
+	// 64 k reads per batch keep them near 14 GB at -k 128 where the default batch would need 220 GB
+	// (not in the temporary-splice-site mode: there a batch is one wave)
+	if((P.khits > 32 || P.kseeds > 64) && !saw_batch && ss_wave == 0 && batch > (1u << 16)) batch = 1u << 16;
 	// splice sites from files (hisat2.cpp:4100-4120): one database for go() on every device and for TLEN
 	std::vector<h2g_splice_site> sites;                  // the splice-site database: file sites, then the temporary ones by first appearance
 	std::map<std::array<uint32_t, 4>, size_t> site_at;    // (text, left, right, dir) -> position in `sites`

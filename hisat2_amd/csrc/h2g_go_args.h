@@ -38,9 +38,10 @@ struct GoArgs {
 #define H2G_GO_DECLARE(NAME) \
 	extern "C" size_t h2g_go_ws_bytes_##NAME(); extern "C" size_t h2g_go_gws_bytes_##NAME(); extern "C" int h2g_go_waves_##NAME(); \
 	extern "C" size_t h2g_go_slot_off_##NAME(); extern "C" size_t h2g_go_gsl_off_##NAME(); extern "C" void h2g_go_geometry_##NAME(uint32_t*); extern "C" size_t h2g_go_sw_bytes_##NAME(uint32_t, int); \
-	extern "C" void h2g_go_caps_##NAME(uint32_t*); extern "C" int h2g_go_launch_##NAME(const GoArgs*, const h2g::DExonTbl*, unsigned, hipStream_t);
+	extern "C" void h2g_go_caps_##NAME(uint32_t*); extern "C" int h2g_go_launch_##NAME(const GoArgs*, const h2g::DExonTbl*, const h2g::XlPairs*, unsigned, hipStream_t);
 H2G_GO_DECLARE(linear) H2G_GO_DECLARE(graph) H2G_GO_DECLARE(linear_big) H2G_GO_DECLARE(graph_big)
 H2G_GO_DECLARE(linear_spl) H2G_GO_DECLARE(linear_spl_big) H2G_GO_DECLARE(graph_spl) H2G_GO_DECLARE(graph_spl_big)   // spliced alignment (linear indexes): with the splice-site database joins
+H2G_GO_DECLARE(linear_xl) H2G_GO_DECLARE(graph_xl) H2G_GO_DECLARE(linear_spl_xl) H2G_GO_DECLARE(graph_spl_xl)       // -k / --max-seeds beyond the large workspace (h2g_go_xl.h)
 
 // ---- the fast pass (h2g_fast.h / h2g_k_go_fast.hip): one read / pair per lane, state on chip; what it cannot hold goes to `bail_list`
 struct FastArgs {

@@ -11,7 +11,7 @@
 //
 // Compiled once per translation unit with that unit's capacities (-DAL_MAX_*): h2g_k_go_linear.hip, h2g_k_go_graph.hip and
 // their *_big.hip siblings (large workspaces: the second pass over reads whose lists overflowed, and option sets beyond the
-// default capacities).  h2g_kernels.hip sees only GoArgs and the extern "C" launchers of H2G_GO_UNIT.
+// default capacities) and *_xl.hip siblings (h2g_go_xl.h: -k / --max-seeds beyond the large workspace).  h2g_kernels.hip sees only GoArgs and the extern "C" launchers of H2G_GO_UNIT.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -161,9 +161,17 @@ __device__ __forceinline__ unsigned long long mach_rings_of_op(uint32_t op) {
 #define H2G_GO_EXONS_PARAM
 #define H2G_GO_EXONS_ARG(x_)
 #endif
+// ... and so is the side area of the XL units' concordant lists (H2G_XL)
+#if H2G_XL
+#define H2G_GO_XL_PARAM , XlPairs XP
+#define H2G_GO_XL_ARG(p_) , *(p_)
+#else
+#define H2G_GO_XL_PARAM
+#define H2G_GO_XL_ARG(p_)
+#endif
 // UNIT tells the builds of different translation units (capacities) apart: same template arguments would be ONE symbol
 template <bool GRAPH, int WAVES_PER_SIMD, int UNIT>
-__global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A H2G_GO_EXONS_PARAM)
+__global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A H2G_GO_EXONS_PARAM H2G_GO_XL_PARAM)
 {
 	extern __shared__ uint32_t s_mem[];
 	GoLds* Q = reinterpret_cast<GoLds*>(s_mem);
@@ -185,6 +193,9 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 #if H2G_EXT_OPTS
 	ctx_ext_opts(C, A.P);
 	C.exons = &X;
+#endif
+#if H2G_XL
+	C.xlp = &XP;
 #endif
 	C.alts = &A.alts; C.gws = A.gws_base ? (GraphWS*)(A.gws_base + tid * A.gws_stride) : nullptr; C.graph = GRAPH;
 	const size_t slot0 = (size_t)blockIdx.x * H2G_GO_SLOTS;
@@ -352,10 +363,10 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 	extern "C" void h2g_go_geometry_##NAME(uint32_t* g) { g[0] = H2G_GO_THREADS; g[1] = H2G_GO_SLOTS; \
 		g[2] = (uint32_t)((sizeof(GoLds) + 3) / 4 * 4); g[3] = H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; /* LDS: rings + one pack region per mate */ } \
 	extern "C" void h2g_go_caps_##NAME(uint32_t* c) { c[0] = AL_MAX_GHITS; c[1] = AL_MAX_RESULTS; c[2] = AL_MAX_SEARCHED; c[3] = AL_MAX_DEPTH; c[4] = AL_MAX_PARTIAL; } \
-	extern "C" int h2g_go_launch_##NAME(const GoArgs* a, const DExonTbl* x, unsigned grid, hipStream_t st) { \
+	extern "C" int h2g_go_launch_##NAME(const GoArgs* a, const DExonTbl* x, const XlPairs* xp, unsigned grid, hipStream_t st) { \
 		const unsigned lds = (unsigned)((sizeof(GoLds) + 3) / 4 * 4) + (a->paired ? 2u : 1u) * H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; \
 		static std::atomic<unsigned long long> lds_ok{0};   /* more than 64 KB of dynamic LDS is an opt-in, per device: a mask over device ids */ \
 		int dev_ = 0; (void)hipGetDevice(&dev_); const unsigned long long bit_ = 1ull << (dev_ & 63); \
 		if(!(lds_ok.load(std::memory_order_relaxed) & bit_)) { if(hipFuncSetAttribute((const void*)k_go<GRAPH, WAVES, UNIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit_, std::memory_order_relaxed); } \
-		(void)x; hipLaunchKernelGGL((k_go<GRAPH, WAVES, UNIT>), dim3(grid), dim3(H2G_GO_THREADS), lds, st, *a H2G_GO_EXONS_ARG(x)); \
+		(void)x; (void)xp; hipLaunchKernelGGL((k_go<GRAPH, WAVES, UNIT>), dim3(grid), dim3(H2G_GO_THREADS), lds, st, *a H2G_GO_EXONS_ARG(x) H2G_GO_XL_ARG(xp)); \
 		return (int)hipGetLastError(); }

@@ -188,6 +188,10 @@ struct h2g_stream {
 	h2g_edit* d_ledits = nullptr; uint32_t* d_ledits_cur = nullptr; size_t ledits_cap = 0; unsigned ledits_parts = 0;
 	unsigned ledits_touched = 0;   // parts a run has written to since the last h2g_set_reads (bit per machine stream): the span h2g_align_fetch_long_edits reports
 	h2g_alnres* d_paln_ovf = nullptr; size_t paln_ovf_cap = 0; unsigned paln_ovf_parts = 0;   // pairs with more records than pair_slots per mate (MachOut::ovf): one part of paln_ovf_cap records per machine stream
+	// the XL units' concordant lists that PairOut cannot carry (XlPairs): per read of the batch where its list starts, the lists (one part of xlp_cap words per
+	// machine stream) and one cursor per part.  xlp_pout: the result rows of the batch the last XL paired run wrote (nullptr: no list is current)
+	uint32_t* d_xlp_at = nullptr; size_t xlp_at_cap = 0; uint32_t* d_xlp = nullptr; size_t xlp_cap = 0; unsigned xlp_parts = 0; uint32_t* d_xlp_cur = nullptr;
+	const PairOut* xlp_pout = nullptr;
 	unsigned long long* d_counters = nullptr;   // [8]
 	void* d_tmp[4] = {nullptr, nullptr, nullptr, nullptr};
 	size_t tmp_sz[4] = {0, 0, 0, 0};
@@ -642,7 +646,7 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	for(int k = 0; k < 2; k++) (void)hipEventDestroy(s->ev_dr[k]);
 	(void)hipFree(s->d_fast_gws); (void)hipFree(s->d_fast_sc); (void)hipFree(s->d_sw_ws); (void)hipFree(s->d_sw_states); (void)hipFree(s->dbg_buf);
 	(void)hipFree(s->d_rout); (void)hipFree(s->d_aln); (void)hipFree(s->d_codes2); (void)hipFree(s->d_offs2); (void)hipFree(s->d_quals2);
-	(void)hipFree(s->d_names2); (void)hipFree(s->d_name_offs2); (void)hipFree(s->d_pout); (void)hipFree(s->d_paln[0]); (void)hipFree(s->d_paln[1]); (void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt);
+	(void)hipFree(s->d_names2); (void)hipFree(s->d_name_offs2); (void)hipFree(s->d_pout); (void)hipFree(s->d_paln[0]); (void)hipFree(s->d_paln[1]); (void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt);
 	for(unsigned b = 0; b < H2G_MAX_BATCHES; b++) if(b != s->cur_batch) {
 		BatchCtx& B = s->parked[b];
 		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
@@ -2002,22 +2006,19 @@ static int need_alignable(h2g_stream* s) {
 	return H2G_ERR_UNSUPPORTED;
 }
 
-// the go() units: [linear?][big?]
+// the go() units: [linear?][tier: default, big, extra-large]
 struct GoUnit {
-	size_t (*ws_bytes)(); size_t (*gws_bytes)(); int (*waves)(); void (*caps)(uint32_t*); int (*launch)(const GoArgs*, const DExonTbl*, unsigned, hipStream_t);
+	size_t (*ws_bytes)(); size_t (*gws_bytes)(); int (*waves)(); void (*caps)(uint32_t*); int (*launch)(const GoArgs*, const DExonTbl*, const XlPairs*, unsigned, hipStream_t);
 	size_t (*slot_off)(); size_t (*gsl_off)(); void (*geometry)(uint32_t*); size_t (*sw_bytes)(uint32_t, int);
 };
-static const GoUnit& go_unit(bool linear, bool big, bool spliced = false) {
+static const GoUnit& go_unit(bool linear, bool big, bool spliced = false, bool xl = false) {
 	// spliced alignment: the units whose machine carries the splice-site database joins
 #define H2G_UNIT_ROW(N) {h2g_go_ws_bytes_##N, h2g_go_gws_bytes_##N, h2g_go_waves_##N, h2g_go_caps_##N, h2g_go_launch_##N, h2g_go_slot_off_##N, h2g_go_gsl_off_##N, h2g_go_geometry_##N, h2g_go_sw_bytes_##N}
-	static const GoUnit spl[2][2] = {{H2G_UNIT_ROW(graph_spl), H2G_UNIT_ROW(graph_spl_big)}, {H2G_UNIT_ROW(linear_spl), H2G_UNIT_ROW(linear_spl_big)}};
-	if(spliced) return spl[linear ? 1 : 0][big ? 1 : 0];
-	static const GoUnit u[2][2] = {
-		{{h2g_go_ws_bytes_graph, h2g_go_gws_bytes_graph, h2g_go_waves_graph, h2g_go_caps_graph, h2g_go_launch_graph, h2g_go_slot_off_graph, h2g_go_gsl_off_graph, h2g_go_geometry_graph, h2g_go_sw_bytes_graph},
-		 {h2g_go_ws_bytes_graph_big, h2g_go_gws_bytes_graph_big, h2g_go_waves_graph_big, h2g_go_caps_graph_big, h2g_go_launch_graph_big, h2g_go_slot_off_graph_big, h2g_go_gsl_off_graph_big, h2g_go_geometry_graph_big, h2g_go_sw_bytes_graph_big}},
-		{{h2g_go_ws_bytes_linear, h2g_go_gws_bytes_linear, h2g_go_waves_linear, h2g_go_caps_linear, h2g_go_launch_linear, h2g_go_slot_off_linear, h2g_go_gsl_off_linear, h2g_go_geometry_linear, h2g_go_sw_bytes_linear},
-		 {h2g_go_ws_bytes_linear_big, h2g_go_gws_bytes_linear_big, h2g_go_waves_linear_big, h2g_go_caps_linear_big, h2g_go_launch_linear_big, h2g_go_slot_off_linear_big, h2g_go_gsl_off_linear_big, h2g_go_geometry_linear_big, h2g_go_sw_bytes_linear_big}}};
-	return u[linear ? 1 : 0][big ? 1 : 0];
+	const int tier = xl ? 2 : big ? 1 : 0;
+	static const GoUnit spl[2][3] = {{H2G_UNIT_ROW(graph_spl), H2G_UNIT_ROW(graph_spl_big), H2G_UNIT_ROW(graph_spl_xl)}, {H2G_UNIT_ROW(linear_spl), H2G_UNIT_ROW(linear_spl_big), H2G_UNIT_ROW(linear_spl_xl)}};
+	if(spliced) return spl[linear ? 1 : 0][tier];
+	static const GoUnit u[2][3] = {{H2G_UNIT_ROW(graph), H2G_UNIT_ROW(graph_big), H2G_UNIT_ROW(graph_xl)}, {H2G_UNIT_ROW(linear), H2G_UNIT_ROW(linear_big), H2G_UNIT_ROW(linear_xl)}};
+	return u[linear ? 1 : 0][tier];
 }
 
 // sizes the per-lane scratch of one pass and fills the pool fields of `a`
@@ -2099,8 +2100,11 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	const uint32_t maxsz = p->khits > p->kseeds ? p->khits : p->kseeds;
 	uint32_t caps[5], bcaps[5];
 	go_unit(linear, false, spl).caps(caps); go_unit(linear, true, spl).caps(bcaps);
-	if(p->khits == 0 || p->khits > H2G_SELECT_CAP || p->kseeds < p->khits || maxsz > bcaps[0]) {
-		snprintf(g_err, sizeof g_err, "align: -k %u / --max-seeds %u outside the built range (-k 1..%u, --max-seeds <= %u)", p->khits, p->kseeds, (unsigned)H2G_SELECT_CAP, bcaps[0]);
+	// a run beyond what the large units hold (more alignments selected than H2G_SELECT_CAP, or a list beyond their AL_MAX_GHITS) runs on the
+	// extra-large units (h2g_go_xl.h), whole: no fast pass, no second pass
+	const bool xl = p->khits > H2G_SELECT_CAP || maxsz > bcaps[0];
+	if(p->khits == 0 || p->khits > H2G_KHITS_MAX || p->kseeds < p->khits || p->kseeds > H2G_KSEEDS_MAX) {
+		snprintf(g_err, sizeof g_err, "align: -k %u / --max-seeds %u outside the built range (1 <= -k <= %u, -k <= --max-seeds <= %u)", p->khits, p->kseeds, (unsigned)H2G_KHITS_MAX, (unsigned)H2G_KSEEDS_MAX);
 		return H2G_ERR_ARG;
 	}
 	if(p->bowtie2_dp > 2 || p->pe_orientation > 2 || p->min_frag_len >= (1u << 24)) return H2G_ERR_ARG;
@@ -2118,8 +2122,8 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		s->st2_busy = false;
 	}
 	s->last_p = *p; s->last_paired = paired ? 1 : 0;
-	const bool big_main = maxsz > caps[0];
-	const GoUnit& U = go_unit(linear, big_main, spl);
+	const bool big_main = maxsz > caps[0];                  // (every XL run is one: khits > 32 or maxsz > 64 exceeds the default units' lists)
+	const GoUnit& U = go_unit(linear, big_main, spl, xl);
 	// (graph indexes: h2g_k_go_fast_graph.hip, the same pass over the graph form of the compact state; --haplotype and the pair-policy options are `spl`)
 	const bool fast = s->tune.fast && !spl && !big_main && p->no_spliced_alignment && !p->secondary && !p->bowtie2_dp;
 	// geometry of the unit: workgroups of geo[0] threads own geo[1] reads in flight; resident workgroups per CU = what the
@@ -2135,6 +2139,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	size_t want = (s->n_reads + geo[1] - 1) / geo[1];
 	size_t maxblocks = 256 * per_cu;
 	if(big_main && maxblocks > 32) maxblocks = 32;        // ~1.3 MB of workspace per read in flight
+	if(xl && maxblocks > 12) maxblocks = 12;              // XL: 18.7 MB per read in flight, 12 x 128 of them (h2g_go_xl.h)
 	const unsigned grid = (unsigned)(want < 1 ? 1 : (want > maxblocks ? maxblocks : want));
 	GoArgs A;
 	memset(&A, 0, sizeof A);
@@ -2226,6 +2231,26 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		}
 		A.O.ovf = s->d_paln_ovf;
 	}
+	XlPairs XP;
+	memset(&XP, 0, sizeof XP);
+	if(paired && xl) {
+		// the XL units' side area: a word per read, and per machine stream a part of lists with a cursor (an XL run is never behind a fast pass: it
+		// runs on the first stream and uses part 0, but the area is partitioned the way the overflow area is)
+		const size_t xcap = s->max_reads * 64 > ((size_t)1 << 20) ? s->max_reads * 64 : ((size_t)1 << 20);      // words per part
+		if(s->xlp_at_cap < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < M) {
+			HIPCHK(hipStreamSynchronize(s->st));
+			(void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); s->d_xlp_at = nullptr; s->d_xlp = nullptr; s->xlp_at_cap = 0; s->xlp_cap = 0; s->xlp_parts = 0;
+			HIPCHK(hipMalloc((void**)&s->d_xlp_at, s->max_reads * 4));
+			HIPCHK(hipMalloc((void**)&s->d_xlp, M * xcap * 4));
+			if(!s->d_xlp_cur) HIPCHK(hipMalloc((void**)&s->d_xlp_cur, H2G_MSTREAMS_MAX * 4));
+			s->xlp_at_cap = s->max_reads; s->xlp_cap = xcap; s->xlp_parts = M;
+		}
+		const unsigned part = 0;
+		HIPCHK(hipMemsetAsync(s->d_xlp_at, 0, s->n_reads * 4, s->st));
+		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_xlp_cur + part), (int)(part * s->xlp_cap), 1, s->st));
+		XP.at = s->d_xlp_at; XP.list = s->d_xlp; XP.cursor = s->d_xlp_cur + part; XP.cap = (uint32_t)((part + 1) * s->xlp_cap);
+	}
+	if(paired) s->xlp_pout = xl ? s->d_pout : (s->xlp_pout == s->d_pout ? nullptr : s->xlp_pout);
 	(void)hipGetLastError();
 	// the fast pass's hand-on list, the counters and its argument block are buffered H2G_NBUF deep: the general machine's pass over
 	// run k's hand-ons goes to machine stream k & 1 and may still be under way while the fast passes of runs k + 1 and k + 2 run
@@ -2477,19 +2502,19 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 			W1.list = s->d_ovf_list[m_]; W1.nlist = s->d_ovf_list[m_] + s->max_reads;                                       // a count of zero (memset on this stream above)
 			W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 124); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 126);
 			W1.defer_overflow = 0; W1.O.defer_list = nullptr; W1.O.defer_count = nullptr;
-			if(U.launch(&W1, &X, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+			if(U.launch(&W1, &X, nullptr, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 			if(second) {
 				GoArgs W2 = W1;
 				if((rc = go_pool_for(s, 2 * (int)m_ + 1, Bw, (size_t)wgeo[1], (size_t)wgeo[0], p->bowtie2_dp, &W2))) return rc;
 				W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 15);
-				if(Bw.launch(&W2, &X, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+				if(Bw.launch(&W2, &X, nullptr, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 			}
 		}
 		s->st2_busy = true;
 		s->mstreams_warm = true;
 	}
 	HIPCHK(hipEventRecord(s->ev[7], ms));
-	if(U.launch(&A, &X, mach_grid, ms) != 0) return set_err("go() launch", hipGetLastError());
+	if(U.launch(&A, &X, &XP, mach_grid, ms) != 0) return set_err("go() launch", hipGetLastError());
 	HIPCHK(hipEventRecord(s->ev[6], ms));
 	if(second) {
 		const GoUnit& B = go_unit(linear, true, spl);
@@ -2502,7 +2527,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		A2.work = reinterpret_cast<uint32_t*>(cblk + 15);
 		A2.list = ovl; A2.nlist = cnt;
 		A2.defer_overflow = 0; A2.O.defer_list = nullptr; A2.O.defer_count = nullptr;
-		if(B.launch(&A2, &X, bgrid, ms) != 0) return set_err("go() second pass launch", hipGetLastError());
+		if(B.launch(&A2, &X, nullptr, bgrid, ms) != 0) return set_err("go() second pass launch", hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(s->ev[8], ms));
 	if(fast) HIPCHK(hipEventRecord(s->ev_mach[gsel], ms));
@@ -2535,6 +2560,15 @@ extern "C" h2g_status h2g_align_fetch(h2g_stream* s, h2g_read_result* res, h2g_a
 }
 
 // ------------------------------------------------------------------------------------------ paired go(): fetch
+// An XL run's pair whose concordant list PairOut cannot carry (more than H2G_PAIR_CAP pairs, or an index past 255) only reaches a caller through the
+// compact fetch (its trailer): the slot and dense fetches flag it with H2G_OVF_PAIR_LIST instead
+static h2g_status xlp_flag(h2g_stream* s, h2g_pair_result* res, size_t first, size_t n) {
+	if(!s->xlp_pout || s->xlp_pout != s->d_pout || n == 0) return H2G_OK;
+	std::vector<uint32_t> at(n);
+	HIPCHK(hipMemcpy(at.data(), s->d_xlp_at + first, n * 4, hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < n; i++) if(at[i]) res[i].overflow |= H2G_OVF_PAIR_LIST;
+	return H2G_OK;
+}
 static h2g_status pairs_fetch_rows(h2g_stream* s, h2g_pair_result* res, h2g_alnres* aln1, h2g_alnres* aln2, size_t first, size_t n, bool callers_view) {
 	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
 	if(!s || !res || first + n > s->n_reads || !s->d_pout) return H2G_ERR_ARG;
@@ -2550,7 +2584,7 @@ static h2g_status pairs_fetch_rows(h2g_stream* s, h2g_pair_result* res, h2g_alnr
 	// a pair kept in the overflow area has more records than these fixed rows return: flagged in the returned copy (the dense variant
 	// returns every record)
 	if(callers_view) for(size_t i = 0; i < n; i++) if(res[i].pad) { res[i].overflow |= 4; res[i].pad = 0; }      // (the block offset itself is the device's business: allocation order, i.e. timing)
-	return H2G_OK;
+	return xlp_flag(s, res, first, n);
 }
 extern "C" h2g_status h2g_align_pairs_fetch(h2g_stream* s, h2g_pair_result* res, h2g_alnres* aln1, h2g_alnres* aln2, size_t first, size_t n) { return pairs_fetch_rows(s, res, aln1, aln2, first, n, true); }
 
@@ -2630,6 +2664,7 @@ extern "C" h2g_status h2g_align_pairs_fetch_dense(h2g_stream* s, h2g_pair_result
 	                 n, aln2, offs2, 2, s->d_pout + first, 1);
 	// `pad` is where the device kept the pair's records (a block offset in the overflow area: allocation order, i.e. timing) — nothing a caller may see
 	for(size_t i = 0; i < n; i++) res[i].pad = 0;
+	if(r == H2G_OK) r = xlp_flag(s, res, first, n);
 	return r;
 }
 
@@ -2645,8 +2680,11 @@ __device__ __forceinline__ const h2g_alnres* compact_src(const h2g_alnres* src, 
 	else if(*c > slots) *c = slots;
 	return a;
 }
+// The concordant list of an XL pair that PairOut cannot carry (XlPairs) travels as a trailer behind mate 1's records (include/h2g.h H2G_PAIR_TRAILER_TAG):
+// `xat` / `xlist` are passed for mate 1 of an XL run only, nullptr otherwise
+__device__ __forceinline__ uint32_t compact_trailer_bytes(uint32_t npairs) { return (40u + 4u * npairs + 7u) & ~7u; }
 __global__ __launch_bounds__(256) void k_compact_sizes(const h2g_alnres* src, uint32_t slots, const uint32_t* cnt, uint32_t cnt_stride, size_t n, unsigned long long* sizes,
-                                                       const PairOut* pout, const h2g_alnres* ovf, int mate)
+                                                       const PairOut* pout, const h2g_alnres* ovf, int mate, const uint32_t* xat = nullptr, const uint32_t* xlist = nullptr)
 {
 	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
 	if(i > n) return;
@@ -2655,6 +2693,7 @@ __global__ __launch_bounds__(256) void k_compact_sizes(const h2g_alnres* src, ui
 	const h2g_alnres* a = compact_src(src, slots, i, &c, pout, ovf, mate);
 	unsigned long long b = 0;
 	for(uint32_t k = 0; k < c; k++) b += compact_rec_bytes(a[k].nedits);
+	if(xat && xat[i]) b += compact_trailer_bytes(xlist[xat[i] - 1u]);
 	sizes[i] = b;
 }
 // exclusive prefix sum of v[0 .. n1) in place, three launches: tiles of 2048 entries scanned by a workgroup each (8 consecutive entries per thread), their sums scanned by
@@ -2700,7 +2739,7 @@ __global__ __launch_bounds__(256) void k_scan_add(unsigned long long* v, size_t 
 	if(i < n1) v[i] += tile_sum[i / H2G_SCAN_TILE];
 }
 __global__ __launch_bounds__(256) void k_compact_gather(const h2g_alnres* src, uint32_t slots, const uint32_t* cnt, uint32_t cnt_stride, const unsigned long long* offs, size_t n,
-                                                        uint8_t* dst, const PairOut* pout, const h2g_alnres* ovf, int mate)
+                                                        uint8_t* dst, const PairOut* pout, const h2g_alnres* ovf, int mate, const uint32_t* xat = nullptr, const uint32_t* xlist = nullptr)
 {
 	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
 	if(i >= n) return;
@@ -2718,14 +2757,26 @@ __global__ __launch_bounds__(256) void k_compact_gather(const h2g_alnres* src, u
 		if(e & 1u) de[3 * e] = 0;                                            // the alignment pad: never stale bytes
 		d += bytes;
 	}
+	if(xat && xat[i]) {      // the trailer: a record prefix whose nedits no record carries, npairs in tidx, then the pairs
+		const uint32_t* l = xlist + (xat[i] - 1u);
+		const uint32_t np = l[0];
+		uint32_t* dw = reinterpret_cast<uint32_t*>(d);
+		for(uint32_t w = 0; w < 10; w++) dw[w] = 0;
+		dw[1] = np; dw[6] = H2G_PAIR_TRAILER_TAG;                         // tidx, nedits
+		for(uint32_t k = 0; k < np; k++) dw[10 + k] = l[1 + k];
+		if(np & 1u) dw[10 + np] = 0;
+	}
 }
 static_assert(offsetof(h2g_alnres, edits) == 40 && sizeof(h2g_edit) == 12, "compact records are prefixes of h2g_alnres");
+static_assert(offsetof(h2g_alnres, tidx) == 4 && offsetof(h2g_alnres, nedits) == 24, "the pair trailer's fields");
 
 // sizes + scan for one mate into tmp slot `slot` (-> device offsets [n + 1], exclusive, in bytes)
-static int compact_offsets(h2g_stream* s, const h2g_alnres* d_src, uint32_t slots, const uint32_t* d_cnt, uint32_t cnt_stride, size_t n, int slot, const PairOut* d_pout, int mate, void** d_offs) {
+static int compact_offsets(h2g_stream* s, const h2g_alnres* d_src, uint32_t slots, const uint32_t* d_cnt, uint32_t cnt_stride, size_t n, int slot, const PairOut* d_pout, int mate, void** d_offs,
+                           const uint32_t* xat = nullptr) {
 	int rc;
 	if((rc = tmp_buf(s, slot, (n + 1) * 8 + ((n + 1) / H2G_SCAN_TILE + 2) * 8, d_offs))) return rc;      // offsets [n + 1], then the scan's tile sums
-	hipLaunchKernelGGL(k_compact_sizes, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, d_src, slots, d_cnt, cnt_stride, n, (unsigned long long*)*d_offs, d_pout, (const h2g_alnres*)s->d_paln_ovf, mate);
+	hipLaunchKernelGGL(k_compact_sizes, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, d_src, slots, d_cnt, cnt_stride, n, (unsigned long long*)*d_offs, d_pout, (const h2g_alnres*)s->d_paln_ovf, mate,
+	                   xat, xat ? (const uint32_t*)s->d_xlp : (const uint32_t*)nullptr);
 	{	// exclusive scan of the n + 1 sizes (the last one is 0: its slot becomes the total); the tile sums live behind the offsets
 		const size_t n1 = n + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
 		unsigned long long* v = (unsigned long long*)*d_offs;
@@ -2747,9 +2798,11 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 	HIPCHK(hipSetDevice(s->ix->device));
 	static_assert(offsetof(PairOut, nres) == 0 && sizeof(h2g_pair_result) == sizeof(PairOut), "PairOut layout");
 	const uint32_t* cnt = reinterpret_cast<const uint32_t*>(s->d_pout + first);
+	// the XL run's lists that PairOut cannot carry: a trailer behind mate 1's records (nullptr for every other run: the kernels take their former path)
+	const uint32_t* xat = s->xlp_pout && s->xlp_pout == s->d_pout ? s->d_xlp_at + first : nullptr;
 	void *d_o1 = nullptr, *d_o2 = nullptr, *d_b1 = nullptr, *d_b2 = nullptr;
 	int rc;
-	if((rc = compact_offsets(s, s->d_paln[0] + first * s->pair_slots, s->pair_slots, cnt, sizeof(PairOut) / 4, n, 0, s->d_pout + first, 0, &d_o1)) ||
+	if((rc = compact_offsets(s, s->d_paln[0] + first * s->pair_slots, s->pair_slots, cnt, sizeof(PairOut) / 4, n, 0, s->d_pout + first, 0, &d_o1, xat)) ||
 	   (rc = compact_offsets(s, s->d_paln[1] + first * s->pair_slots, s->pair_slots, cnt + 1, sizeof(PairOut) / 4, n, 2, s->d_pout + first, 1, &d_o2))) return (h2g_status)rc;
 	HIPCHK(hipMemcpyAsync(boffs1, d_o1, (n + 1) * 8, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipMemcpyAsync(boffs2, d_o2, (n + 1) * 8, hipMemcpyDeviceToHost, s->st));
@@ -2760,7 +2813,8 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 	if((rc = tmp_buf(s, 1, boffs1[n] + 8, &d_b1)) || (rc = tmp_buf(s, 3, boffs2[n] + 8, &d_b2))) return (h2g_status)rc;
 	const unsigned g = (unsigned)((n + 255) / 256);
 	if(boffs1[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->d_paln[0] + first * s->pair_slots, s->pair_slots, cnt, (uint32_t)(sizeof(PairOut) / 4),
-	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 0);
+	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 0,
+	                                 xat, xat ? (const uint32_t*)s->d_xlp : (const uint32_t*)nullptr);
 	if(boffs2[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->d_paln[1] + first * s->pair_slots, s->pair_slots, cnt + 1, (uint32_t)(sizeof(PairOut) / 4),
 	                                 (const unsigned long long*)d_o2, n, (uint8_t*)d_b2, s->d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 1);
 	HIPCHK(hipGetLastError());

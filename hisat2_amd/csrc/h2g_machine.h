@@ -1656,7 +1656,14 @@ H2G_MACH_FN void mach_finish(const AlnCtx& C, Mach& M) {
 		ReadOut o;
 		Rng rnd; rnd.last = gv.rnd;
 		o.nres = ws->m[0].nres; o.overflow = ws->overflow; o.nrank = ws->nrank; o.nsteps = ws->nsteps; o.depth = ws->nframes_max; o.nside = ws->nside;
+#if H2G_XL
+		o.nselect = al_select_xl(ws, &ws->m[0], *C.P, &rnd);          // (the selection stays in ws->sel_idx: past 32 entries and 255 rows)
+		for(uint32_t k = 0; k < H2G_SELECT_CAP; k++) o.select[k] = 0;
+		const uint16_t* const sel = ws->sel_idx;
+#else
 		o.nselect = al_select(&ws->m[0], *C.P, &rnd, o.select);
+		const uint8_t* const sel = o.select;
+#endif
 		// AlnSetSumm::init aligner_result.cpp:1209: best / second best by AlnScore (score, then hisat2_score)
 		int64_t b = INT64_MIN, sb = INT64_MIN, bh = 0, sbh = 0;
 		for(uint32_t k = 0; k < ws->m[0].nres; k++) {
@@ -1667,7 +1674,7 @@ H2G_MACH_FN void mach_finish(const AlnCtx& C, Mach& M) {
 		}
 		o.best = b == INT64_MIN ? INT32_MIN : (int32_t)b; o.secbest = sb == INT64_MIN ? INT32_MIN : (int32_t)sb;
 		o.best_h2 = (uint32_t)(uint64_t)bh; o.secbest_h2 = (uint32_t)(uint64_t)sbh;
-		if(O.aln) for(uint32_t k = 0; k < o.nselect && k < O.aln_slots; k++) if(!mach_copy_rec(O.aln[(size_t)i * O.aln_slots + k], ws->m[0].res[o.select[k]], O)) o.overflow |= 1;
+		if(O.aln) for(uint32_t k = 0; k < o.nselect && k < O.aln_slots; k++) if(!mach_copy_rec(O.aln[(size_t)i * O.aln_slots + k], ws->m[0].res[sel[k]], O)) o.overflow |= 1;
 		if(O.rout) O.rout[i] = o;
 		M.L.a0 = o.nselect > 0; M.L.a1 = o.overflow != 0;
 	} else {
@@ -1689,7 +1696,29 @@ H2G_MACH_FN void mach_finish(const AlnCtx& C, Mach& M) {
 			if(blk == H2G_MAX) o.overflow |= 4;
 		}
 		o.nrank = ws->nrank; o.nsteps = ws->nsteps; o.depth = ws->nframes_max; o.nside = ws->nside; o.rnd_state = gv.rnd; o.pad = blk == H2G_MAX ? 0u : blk + 1u;
-		for(uint32_t k = 0; k < AL_MAX_PAIRS; k++) { o.pair_i[k] = k < ws->npairs ? ws->pair_i[k] : 0; o.pair_j[k] = k < ws->npairs ? ws->pair_j[k] : 0; }
+		for(uint32_t k = 0; k < AL_MAX_PAIRS; k++) { o.pair_i[k] = k < ws->npairs ? (uint8_t)ws->pair_i[k] : 0; o.pair_j[k] = k < ws->npairs ? (uint8_t)ws->pair_j[k] : 0; }
+#if H2G_XL
+		{	// a list PairOut cannot carry (more than AL_MAX_PAIRS pairs, or an index past 255) goes whole to the side area; no room there: bit 128
+			bool whole = ws->npairs > AL_MAX_PAIRS;
+			for(uint32_t k = 0; k < ws->npairs && k < AL_MAX_PAIRS; k++) whole = whole || ws->pair_i[k] > 255 || ws->pair_j[k] > 255;
+			const XlPairs* X = C.xlp;
+			uint32_t at = 0;
+			if(whole && X && X->list) {
+#if defined(__HIP_DEVICE_COMPILE__)
+				const uint32_t b = atomicAdd(X->cursor, ws->npairs + 1u);
+#else
+				const uint32_t b = *X->cursor; *X->cursor += ws->npairs + 1u;
+#endif
+				if(b + ws->npairs + 1u <= X->cap) {
+					X->list[b] = ws->npairs;
+					for(uint32_t k = 0; k < ws->npairs; k++) X->list[(size_t)b + 1 + k] = (uint32_t)ws->pair_i[k] | ((uint32_t)ws->pair_j[k] << 16);
+					at = b + 1u;
+				}
+			}
+			if(whole && at == 0) o.overflow |= 128;
+			if(X && X->at) X->at[i] = at;
+		}
+#endif
 		for(int m = 0; m < 2; m++) {
 			if(!O.paln[m]) continue;
 			const uint32_t n = o.nres[m] < O.pair_slots ? o.nres[m] : O.pair_slots;

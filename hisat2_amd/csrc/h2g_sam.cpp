@@ -617,11 +617,17 @@ inline bool compact_table(const uint8_t* p, const uint8_t* end, size_t n, std::v
 	}
 	return true;
 }
-// walks every compact record in [p, end) into tab; returns their count (a truncated tail ends the walk)
-inline size_t compact_walk(const uint8_t* p, const uint8_t* end, std::vector<const h2g_alnres*>& tab) {
+// walks every compact record in [p, end) into tab; returns their count (a truncated tail ends the walk).  A pair trailer (include/h2g.h
+// H2G_PAIR_TRAILER_TAG) is no record: it ends the walk, and *trailer points at it when the caller asks
+inline size_t compact_walk(const uint8_t* p, const uint8_t* end, std::vector<const h2g_alnres*>& tab, const h2g_alnres** trailer = nullptr) {
 	tab.clear();
+	if(trailer) *trailer = nullptr;
 	while(p + 40 <= end) {
 		const h2g_alnres* r = reinterpret_cast<const h2g_alnres*>(p);
+		if(r->nedits == H2G_PAIR_TRAILER_TAG) {
+			if(trailer && p + H2G_PAIR_TRAILER_BYTES(r->tidx) <= end) *trailer = r;
+			break;
+		}
 		const size_t b = H2G_COMPACT_BYTES(r->nedits);
 		if(p + b > end) break;
 		tab.push_back(r);
@@ -736,7 +742,7 @@ inline bool long_record_ok(const h2g_sam* S, const h2g_alnres& r) {
 // the area — checked before a line is written, so that the formatter itself never meets a malformed buffer (ED() handed out a one-entry list, a failed
 // table dropped the read's lines silently)
 template <typename NEED>
-bool compact_ok(const h2g_sam* S, const uint8_t* rec, const uint64_t* boffs, size_t n, NEED&& need) {
+bool compact_ok(const h2g_sam* S, const uint8_t* rec, const uint64_t* boffs, size_t n, NEED&& need, bool trailers = false) {
 	for(size_t i = 0; i < n; i++) {
 		if(boffs[i + 1] < boffs[i]) return false;
 		const uint8_t* p = rec + boffs[i]; const uint8_t* const end = rec + boffs[i + 1];
@@ -744,6 +750,10 @@ bool compact_ok(const h2g_sam* S, const uint8_t* rec, const uint64_t* boffs, siz
 		while(p < end) {
 			if(p + 40 > end) return false;
 			const h2g_alnres* r = reinterpret_cast<const h2g_alnres*>(p);
+			if(r->nedits == H2G_PAIR_TRAILER_TAG) {        // a pair trailer: the last entry of the bytes, and only where a caller allows one
+				if(!trailers || p + H2G_PAIR_TRAILER_BYTES(r->tidx) != end) return false;
+				break;
+			}
 			const size_t b = H2G_COMPACT_BYTES(r->nedits);
 			if(p + b > end || !long_record_ok(S, *r)) return false;
 			p += b; k++;
@@ -954,7 +964,8 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 		const h2g_read_result& r = res[i];
 		if(r.best != INT32_MIN) { summ.best[0].valid = true; summ.best[0].score = r.best; summ.best[0].h2 = (int64_t)(((uint64_t)(int64_t)r.best << 32) | r.best_h2); }
 		if(r.secbest != INT32_MIN) { summ.secbest[0].valid = true; summ.secbest[0].score = r.secbest; summ.secbest[0].h2 = (int64_t)(((uint64_t)(int64_t)r.secbest << 32) | r.secbest_h2); }
-		const uint32_t nsel = r.nselect < H2G_ALN_CAP ? r.nselect : H2G_ALN_CAP;
+		// the slot layout holds H2G_ALN_CAP records per read; the dense and compact layouts every record selected (-k beyond H2G_ALN_CAP)
+		const uint32_t nsel = (compact || aln_offs) ? r.nselect : (r.nselect < H2G_ALN_CAP ? r.nselect : H2G_ALN_CAP);
 		met.nread++; met.nunpaired++;
 		if(nsel == 0) met.nunp_0++; else if(nsel == 1) met.nunp_uni1++; else met.nunp_uni2++;
 		if(nsel == 0) append_mate(*S, o, rd, nullptr, nullptr, nullptr, summ, fl, 0);
@@ -1005,9 +1016,10 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 		            {nb2 + noffs2[i], noffs2[i + 1] - noffs2[i], codes2 + offs2[i], offs2[i + 1] - offs2[i], quals2 ? quals2 + offs2[i] : nullptr}};
 		Recs r1, r2;
 		size_t n1, n2;
+		const h2g_alnres* trailer = nullptr;   // the whole concordant list of a pair beyond what h2g_pair_result carries (include/h2g.h)
 		if(compact1) {   // every record the device kept, found by walking the read's bytes
 			static thread_local std::vector<const h2g_alnres*> t1, t2;
-			n1 = compact_walk(compact1 + ao1[i], compact1 + ao1[i + 1], t1); n2 = compact_walk(compact2 + ao2[i], compact2 + ao2[i + 1], t2);
+			n1 = compact_walk(compact1 + ao1[i], compact1 + ao1[i + 1], t1, &trailer); n2 = compact_walk(compact2 + ao2[i], compact2 + ao2[i + 1], t2);
 			r1.tab = t1.data(); r2.tab = t2.data();
 		} else {
 			r1.base = ao1 ? aln1 + ao1[i] : aln1 + i * H2G_PAIR_RES_CAP;
@@ -1024,10 +1036,19 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 		// No — every concordant pair reported is kept (rs1_/rs2_); nconcord = their count
 		// pairs naming a record beyond the H2G_PAIR_RES_CAP returned per mate (such a pair carries an overflow flag) are dropped
 		// rather than indexed past the end of the fetched records
-		uint8_t pi[H2G_PAIR_CAP], pj[H2G_PAIR_CAP];
-		size_t np = 0;
-		for(size_t k = 0; k < std::min<size_t>(pr.npairs, H2G_PAIR_CAP); k++)
-			if(pr.pair_i[k] < n1 && pr.pair_j[k] < n2) { pi[np] = pr.pair_i[k]; pj[np] = pr.pair_j[k]; np++; }
+		static thread_local std::vector<uint32_t> pi, pj;
+		pi.clear(); pj.clear();
+		if(trailer) {
+			const uint32_t* l = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(trailer) + 40);
+			for(uint32_t k = 0; k < trailer->tidx; k++) {
+				const uint32_t a = l[k] & 0xffffu, b = l[k] >> 16;
+				if(a < n1 && b < n2) { pi.push_back(a); pj.push_back(b); }
+			}
+		} else {
+			for(size_t k = 0; k < std::min<size_t>(pr.npairs, H2G_PAIR_CAP); k++)
+				if(pr.pair_i[k] < n1 && pr.pair_j[k] < n2) { pi.push_back(pr.pair_i[k]); pj.push_back(pr.pair_j[k]); }
+		}
+		const size_t np = pi.size();
 		if(np > 0) {
 			Summ summ;
 			summ.paired = true;
@@ -1118,7 +1139,7 @@ extern "C" h2g_status h2g_sam_format_paired_compact(const h2g_sam* S, const uint
                                                     const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits, char* out, size_t cap, size_t* used)
 {
 	if(!boffs1 || !boffs2 || !S || !rec1 || !rec2 || !res) return H2G_ERR_ARG;
-	if(!compact_ok(S, rec1, boffs1, n, [](size_t) { return (size_t)0; }) || !compact_ok(S, rec2, boffs2, n, [](size_t) { return (size_t)0; })) return H2G_ERR_ARG;
+	if(!compact_ok(S, rec1, boffs1, n, [](size_t) { return (size_t)0; }, true) || !compact_ok(S, rec2, boffs2, n, [](size_t) { return (size_t)0; })) return H2G_ERR_ARG;
 	return format_paired(S, codes1, offs1, quals1, nb1, noffs1, codes2, offs2, quals2, nb2, noffs2, n, res, nullptr, boffs1, nullptr, boffs2, khits, out, cap, used, rec1, rec2);
 }
 extern "C" h2g_status h2g_sam_format_unpaired_compact(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals,
@@ -1126,7 +1147,7 @@ extern "C" h2g_status h2g_sam_format_unpaired_compact(const h2g_sam* S, const ui
                                                       const uint8_t* rec, const uint64_t* boffs, char* out, size_t cap, size_t* used)
 {
 	if(!boffs || !S || !rec || !res) return H2G_ERR_ARG;
-	if(!compact_ok(S, rec, boffs, n, [&](size_t i) { return (size_t)(res[i].nselect < H2G_ALN_CAP ? res[i].nselect : H2G_ALN_CAP); })) return H2G_ERR_ARG;
+	if(!compact_ok(S, rec, boffs, n, [&](size_t i) { return (size_t)res[i].nselect; })) return H2G_ERR_ARG;
 	return format_unpaired(S, codes, offs, quals, nb, noffs, n, res, nullptr, boffs, out, cap, used, rec);
 }
 extern "C" h2g_status h2g_sam_format_paired(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1,

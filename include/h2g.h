@@ -297,7 +297,7 @@ typedef struct {
 	                                * splice-score and trimmed-base fields — the AlnScore tie-break); best == INT32_MIN = none.  MAPQ, ZS:i */
 } h2g_read_result;
 typedef struct {
-	uint32_t khits, kseeds;        /* -k, --max-seeds */
+	uint32_t khits, kseeds;        /* -k, --max-seeds: 1 <= khits <= H2G_KHITS_MAX, khits <= kseeds <= H2G_KSEEDS_MAX */
 	uint32_t no_spliced_alignment; /* 1: --no-spliced-alignment; 0: introns are placed by combineWith (needs no_temp_splicesite, linear index) */
 	uint32_t secondary;
 	uint32_t bowtie2_dp;           /* --bowtie2-dp: 0 off (default), 1 SwAligner when no alignment reached minsc, 2 always
@@ -375,7 +375,19 @@ H2G_EXPORT h2g_status h2g_align_fetch_dense(h2g_stream*, h2g_read_result* res /*
 H2G_EXPORT h2g_status h2g_set_mates(h2g_stream*, const uint8_t* codes2, const uint32_t* offs2, const char* quals2,
                                     const char* name_bytes2, const uint32_t* name_offs2, size_t n_reads);
 #define H2G_PAIR_RES_CAP 16       /* unpaired alignments returned per mate */
-#define H2G_PAIR_CAP 32           /* concordant pairs returned per read pair */
+#define H2G_PAIR_CAP 32           /* concordant pairs returned per read pair (pair_i / pair_j); npairs is the true count */
+/* The range of -k / --max-seeds h2g_align_run and h2g_align_pairs_run accept.  A run with khits > 32 or max(khits, kseeds) > 64 runs on the
+ * extra-large units, whole (no fast pass, no second pass): a pair there may have more concordant pairings than H2G_PAIR_CAP, or name a record past
+ * index 255 of a mate's list.  Such a pair's whole list reaches a caller only through h2g_align_pairs_fetch_compact, as a trailer behind mate 1's
+ * records: a record prefix (40 bytes) with nedits == H2G_PAIR_TRAILER_TAG — no record carries it — and tidx = the number of pairs, then one uint32_t
+ * per pair in report order, mate-1 index | mate-2 index << 16, the whole rounded up to 8 bytes (H2G_PAIR_TRAILER_BYTES).  It is the last entry of
+ * the pair's mate-1 bytes; the list replaces npairs / pair_i / pair_j.  h2g_align_pairs_fetch and h2g_align_pairs_fetch_dense cannot carry such a
+ * pair: they return the first H2G_PAIR_CAP pairings truncated to 8 bits and set overflow bit H2G_OVF_PAIR_LIST. */
+#define H2G_KHITS_MAX 128
+#define H2G_KSEEDS_MAX 256
+#define H2G_PAIR_TRAILER_TAG 0x52494150u   /* "PAIR" */
+#define H2G_PAIR_TRAILER_BYTES(npairs) ((40u + 4u * (uint32_t)(npairs) + 7u) & ~7u)
+#define H2G_OVF_PAIR_LIST 4096u
 typedef struct {
 	uint32_t nres[2];              /* sink.report(mate) events per mate, in report order (rs1u_/rs2u_) */
 	uint32_t npairs;               /* sink.report(r1, r2) events, in report order (rs1_/rs2_) */
