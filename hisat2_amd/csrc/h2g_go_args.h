@@ -7,6 +7,30 @@
 #include "h2g_graph.h"
 #include "h2g_fast.h"
 
+// The counter block of one go_run generation (h2g_stream::d_counters holds H2G_NBUF of them), in 64-bit words.  Block 0 also serves the seed pipeline
+// (h2g_seed_extend_run: RANK .. EXT, read by h2g_get_counters before any go() run) and the rank benches' scratch words (BENCH_SUM, BENCH_CHECKSUM).
+enum : unsigned {
+	H2G_CNT_RANK = 0, H2G_CNT_SIDE = 1, H2G_CNT_STEPS = 2, H2G_CNT_EXT = 3,   // a machine pass (and the seed pipeline): rank calls, sides, SA steps, extensions
+	H2G_CNT_ALIGNED = 4, H2G_CNT_OVERFLOW = 5,                                 // ... reads aligned, reads still flagged
+	H2G_CNT_FAST_DONE = 6, H2G_CNT_FAST_BAILED = 7,                            // the fast pass: reads it completed, reads it handed on
+	H2G_CNT_BENCH_SUM = 6, H2G_CNT_BENCH_CHECKSUM = 7,                         // (the rank benches, block 0: never next to a go() run's)
+	H2G_CNT_WORK_FAST = 12, H2G_CNT_WORK_DRAIN = 13, H2G_CNT_WORK_MAIN = 14, H2G_CNT_WORK_SECOND = 15,   // work cursors (a uint32_t in the low half of the word)
+	H2G_CNT_PROF_GO = 16, H2G_CNT_PROF_GO_CTL = 80,                            // H2G_GO_PROF: a machine pass's time split (48 words), control by source ring (16)
+	H2G_CNT_NO_SECOND = 64,                                                    // [64, 72): written by nobody — the second pass h2g_get_counters reads before any go() run
+	H2G_CNT_FAST_BAIL_WHY = 96,                                                // the fast pass's hand-ons by reason (24 words)
+	H2G_CNT_FAST_RANK = 120, H2G_CNT_FAST_SIDE = 121, H2G_CNT_FAST_STEPS = 122, H2G_CNT_FAST_ALIGNED = 123,   // the fast launch's rank / side / step / aligned counters ...
+	H2G_CNT_DRAIN_OFF = 120,                                                   // ... and the drain launch's, at FastArgs::cnt_off = this behind them: [240, 244)
+	H2G_CNT_OVF_CURSOR = 124, H2G_CNT_LEDITS_CURSOR = 126,                     // cursors of the pair-overflow / long-edit areas (uint32_t)
+	H2G_CNT_PROF_FAST = 128, H2G_CNT_PROF_FAST_SITE = 176, H2G_CNT_PROF_FAST_TRIPS = 208,   // H2G_GO_PROF: the fast pass's time split (48), ticks (32) and trips (32) by site
+	H2G_CNT_SECOND = 256,                                                      // the second pass's own RANK .. OVERFLOW (+ its H2G_GO_PROF words): [256, 512)
+	H2G_CNT_PROF_FAST_BINS = 512,                                              // H2G_GO_PROF: the fast pass's time-resolved bins (h2g_fast_prof.h), [512, 768)
+#ifdef H2G_GO_PROF
+	H2G_CNT_BLOCK = 1024
+#else
+	H2G_CNT_BLOCK = 512
+#endif
+};
+
 __device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long v) {
 	for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
 	if((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
@@ -52,7 +76,7 @@ struct FastArgs {
 	const char* names2; const uint32_t* noffs2;
 	uint32_t* slots;                      // FG_SLOT_WORDS words per read in flight: packed state, hot words, packed reads, cold words
 	h2g::FastOut O;
-	unsigned long long* counters;         // [120] rank calls [121] sides [122] SA steps [123] aligned [6] completed [7] bailed, [96 + why] bails by reason
+	unsigned long long* counters;         // a counter block: H2G_CNT_FAST_* (+ cnt_off), completed, bailed, bails by reason
 	uint32_t* work;                       // next unclaimed read (zeroed before the launch)
 	uint32_t* bail_list; uint32_t* bail_count;
 	uint32_t total, paired;
@@ -66,7 +90,7 @@ struct FastArgs {
 	// when they could fetch no more and had thinned out to orphan_T reads; the drain launch (..._launch_drain) resumes the reads of `adopt_list` out of `adopt_slots`
 	uint32_t orphan_T; uint32_t* orphan_list; uint32_t* orphan_count;
 	const uint32_t* adopt_list; const uint32_t* adopt_count; const uint32_t* adopt_slots;
-	uint32_t cnt_off;                         // this launch's rank / side / step / aligned counters are counters[120 + cnt_off ..]
+	uint32_t cnt_off;                         // this launch's rank / side / step / aligned counters are counters[H2G_CNT_FAST_RANK + cnt_off ..]
 	uint32_t adopt_slot_words;                // words per slot of `adopt_slots` (the launch that left them may be another build of the pass: same layout, a shorter cold tail)
 	uint32_t mate_handover;                   // 1 (with orphan_T > 0, a build without alignMate): pairs that need alignMate are parked in their slots and listed for the drain launch — the alignMate build's
 };

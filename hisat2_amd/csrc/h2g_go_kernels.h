@@ -341,14 +341,14 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 #endif
 	}
 #ifdef H2G_GO_PROF
-	if(lane == 0) for(int k = 0; k < 48; k++) if(prof[k]) atomicAdd(A.counters + 16 + k, prof[k]);
-	if(lane == 0) for(int k = 0; k < 16; k++) if(prof_ctl[k]) atomicAdd(A.counters + 80 + k, prof_ctl[k]);
+	if(lane == 0) for(int k = 0; k < 48; k++) if(prof[k]) atomicAdd(A.counters + H2G_CNT_PROF_GO + k, prof[k]);
+	if(lane == 0) for(int k = 0; k < 16; k++) if(prof_ctl[k]) atomicAdd(A.counters + H2G_CNT_PROF_GO_CTL + k, prof_ctl[k]);
 #endif
-	wave_add(A.counters + 0, nrank);
-	wave_add(A.counters + 1, nside);
-	wave_add(A.counters + 2, nsteps);
-	wave_add(A.counters + 4, naln);
-	wave_add(A.counters + 5, novf);
+	wave_add(A.counters + H2G_CNT_RANK, nrank);
+	wave_add(A.counters + H2G_CNT_SIDE, nside);
+	wave_add(A.counters + H2G_CNT_STEPS, nsteps);
+	wave_add(A.counters + H2G_CNT_ALIGNED, naln);
+	wave_add(A.counters + H2G_CNT_OVERFLOW, novf);
 }
 
 // the extern "C" face of one translation unit (declared in h2g_go_args.h)

@@ -386,7 +386,7 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 				if(b) {
 					const uint32_t why = S.bail;
 					A->bail_list[base + (uint32_t)__popcll(bm & lt)] = S.read;
-					atomicAdd(A->counters + 96 + (why < FB_COUNT ? why : (uint32_t)FB_OTHER), 1ull);
+					atomicAdd(A->counters + H2G_CNT_FAST_BAIL_WHY + (why < FB_COUNT ? why : (uint32_t)FB_OTHER), 1ull);
 					nbail++;
 				}
 			}
@@ -407,12 +407,12 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 		}
 	}
 	FPROF_FLUSH(A->counters);
-	wave_add(cnt + 120, nrank);     // (slots of its own: the general machine's passes count in 0..5 / 64..69; the drain launch's cnt_off moves its four)
-	wave_add(cnt + 121, nside);
-	wave_add(cnt + 122, nsteps);
-	wave_add(cnt + 123, naln);
-	wave_add(A->counters + 6, ndone);
-	wave_add(A->counters + 7, nbail);
+	wave_add(cnt + H2G_CNT_FAST_RANK, nrank);     // (slots of its own: the general machine's passes count in 0..5 / 256..261; the drain launch's cnt_off moves its four)
+	wave_add(cnt + H2G_CNT_FAST_SIDE, nside);
+	wave_add(cnt + H2G_CNT_FAST_STEPS, nsteps);
+	wave_add(cnt + H2G_CNT_FAST_ALIGNED, naln);
+	wave_add(A->counters + H2G_CNT_FAST_DONE, ndone);
+	wave_add(A->counters + H2G_CNT_FAST_BAILED, nbail);
 }
 __global__ __launch_bounds__(H2G_FAST_THREADS) void FG_KERNEL(const FastArgs* __restrict__ A)
 {

@@ -85,26 +85,20 @@ struct h2g_index {
 #define H2G_DRAIN_GRID 64
 #define H2G_FAST_POOLS 3
 #define H2G_DEFAULT_ALIGN_MATE 0
-#ifdef H2G_GO_PROF
-#define H2G_CNT_BLOCK 1024u         // (+ the time-resolved bins of h2g_fast_prof.h at [512, 768))
-#else
-#define H2G_CNT_BLOCK 512u
-#endif
-//                            // counter words per go_run generation: [0, 256) the main / fast pass (+ their profiling slots), [256, 512) the second pass
+// (the counter words of one go_run generation, H2G_CNT_BLOCK of them: h2g_go_args.h)
 #define H2G_MACH_MAXGRID 48u       // workgroups of ONE machine pass behind a fast pass
 #define H2G_MACH_TOTAL 128u        // ... and of all machine passes in flight together ("mach_total": a pass gets at most mach_total / mstreams workgroups)
-// Resident batches (round 6): a stream holds up to H2G_MAX_BATCHES read sets WITH their result rows (h2g_stream_select_batch).  The named fields of h2g_stream are the
-// selected batch's; the others are parked in h2g_stream::parked.  A run captures its batch's pointers in its argument block when it is queued, so runs over different batches
+// Resident batches (round 6): a stream holds up to H2G_MAX_BATCHES read sets WITH their result rows (h2g_stream_select_batch): h2g_stream::batch, of which
+// h2g_stream::cur() is the selected one.  A run captures its batch's pointers in its argument block when it is queued, so runs over different batches
 // are in flight together — fast passes and up to eight machine passes — each writing its own rows (a streaming caller's steady state: SURVEY §8(d) configs[2] is 10 M pairs, not one
 // million ten times).
 #define H2G_MAX_BATCHES 16
-#define H2G_BATCH_FIELDS(X) X(n_reads) X(max_read_len) X(d_codes) X(d_offs) X(d_quals) X(has_quals) X(d_names) X(d_name_offs) X(names_cap) X(has_names) \
-	X(d_codes2) X(d_offs2) X(d_quals2) X(d_names2) X(d_name_offs2) X(has_mates) X(has_quals2) X(d_rout) X(d_aln) X(aln_alloc) X(aln_slots) X(d_pout) X(paln_alloc) X(pair_slots)
 struct BatchCtx {
 	size_t n_reads = 0; uint32_t max_read_len = 0;
 	uint8_t* d_codes = nullptr; uint32_t* d_offs = nullptr; char* d_quals = nullptr; bool has_quals = false;
 	char* d_names = nullptr; uint32_t* d_name_offs = nullptr; size_t names_cap = 0; bool has_names = false;
 	uint8_t* d_codes2 = nullptr; uint32_t* d_offs2 = nullptr; char* d_quals2 = nullptr; char* d_names2 = nullptr; uint32_t* d_name_offs2 = nullptr; bool has_mates = false, has_quals2 = false;
+	// result rows: aln_slots (>= -k) records per read in d_aln, pair_slots (>= H2G_PAIR_RES_CAP) per mate in d_paln; aln_alloc / paln_alloc records behind them
 	ReadOut* d_rout = nullptr; h2g_alnres* d_aln = nullptr; size_t aln_alloc = 0; uint32_t aln_slots = 0;
 	PairOut* d_pout = nullptr; h2g_alnres* d_paln[2] = {nullptr, nullptr}; size_t paln_alloc = 0; uint32_t pair_slots = 0;
 };
@@ -121,23 +115,18 @@ struct h2g_stream {
 	unsigned long long* cnt_cur = nullptr;   // the counter block of the last go_run
 	uint32_t last_bails = 0;
 	uint32_t* h_bails = nullptr;      // pinned: the hand-on count of the last two fast passes (sizes the machine's share of the CUs)
-	size_t max_reads = 0, max_bases = 0, n_reads = 0;
-	uint32_t max_read_len = 0;
-	uint8_t* d_codes = nullptr;
-	uint32_t* d_offs = nullptr;
-	char* d_quals = nullptr;
-	bool has_quals = false;
+	size_t max_reads = 0, max_bases = 0;
+	BatchCtx batch[H2G_MAX_BATCHES];  // the resident batches: read sets and their result rows
+	unsigned cur_batch = 0;
+	BatchCtx& cur() { return batch[cur_batch]; }   // the selected one
+	const BatchCtx& cur() const { return batch[cur_batch]; }
 	h2g_seed_result* d_seed = nullptr;
-	char* d_names = nullptr;
-	uint32_t* d_name_offs = nullptr;
-	size_t names_cap = 0;
-	bool has_names = false;
 	// per-lane scratch of the go() kernels: [0] the main pass, [1] the second pass over overflowed reads (large workspace)
 	struct GoPool {
 		uint8_t* ws = nullptr;  size_t ws_bytes = 0;      // AlignWS x lanes of the unit last run
 		uint8_t* gws = nullptr; size_t gws_bytes = 0;     // GraphWS x lanes (graph indexes only)
 		uint8_t* sw = nullptr;  size_t sw_stride = 0, sw_lanes = 0;   // Smith-Waterman scratch (only with bowtie2_dp != 0)
-		uint8_t* sc = nullptr;  size_t sc_lanes = 0;                  // combineWith temp_scores per lane
+		uint8_t* sc = nullptr;  size_t sc_bytes = 0;                  // combineWith temp_scores per lane
 	} pool[2 * H2G_MSTREAMS_MAX];     // [2 * m + 0] main pass, [2 * m + 1] second pass of machine stream m (m = 0 also: passes on the first stream)
 	uint32_t* dbg_buf = nullptr;      // development hook (H2G_GO_DBG_READ)
 	uint32_t* d_ovf_list[H2G_MSTREAMS_MAX] = {};   // per machine stream: read ids whose workspace overflowed in the main pass (+ their count behind the list)
@@ -166,24 +155,10 @@ struct h2g_stream {
 	struct Tune { int fast = 1, blocks_per_cu = 0, pair_slots = 0, no_second_pass = 0; unsigned mach_div = 0 /* auto */, mach_min = 4, mach_total = H2G_MACH_TOTAL; int mach_total_auto = 1; int fast_reserve = H2G_FAST_RESERVE_DEFAULT; long dbg_read = -1;
 	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */; } tune;
 	h2g_align_params last_p; int last_paired = -1;   // the option set of the last go_run (a different one waits for the machine streams)
-	uint32_t aln_slots = 0;           // alignment records kept per unpaired read in d_aln (>= -k of the last run)
-	uint32_t pair_slots = 0;          // report events kept per mate in d_paln (>= H2G_PAIR_RES_CAP; grows with -k)
-	size_t paln_alloc = 0;
-	size_t aln_alloc = 0;             // records allocated behind d_aln
 	uint8_t* d_sw_ws = nullptr;   // h2g_sw_align: H/E/F workspace of one batch of problems
 	size_t sw_ws_bytes = 0;
 	SwLaneState* d_sw_states = nullptr;
 	size_t sw_states = 0;
-	ReadOut* d_rout = nullptr;
-	h2g_alnres* d_aln = nullptr;
-	uint8_t* d_codes2 = nullptr;
-	uint32_t* d_offs2 = nullptr;
-	char* d_quals2 = nullptr;
-	char* d_names2 = nullptr;
-	uint32_t* d_name_offs2 = nullptr;
-	bool has_mates = false, has_quals2 = false;
-	PairOut* d_pout = nullptr;
-	h2g_alnres* d_paln[2] = {nullptr, nullptr};
 	// records with more than H2G_MAX_EDITS edits keep their lists here (MachOut::ledits): one part of ledits_cap edits and one cursor per machine stream
 	h2g_edit* d_ledits = nullptr; uint32_t* d_ledits_cur = nullptr; size_t ledits_cap = 0; unsigned ledits_parts = 0;
 	unsigned ledits_touched = 0;   // parts a run has written to since the last h2g_set_reads (bit per machine stream): the span h2g_align_fetch_long_edits reports
@@ -192,7 +167,7 @@ struct h2g_stream {
 	// machine stream) and one cursor per part.  xlp_pout: the result rows of the batch the last XL paired run wrote (nullptr: no list is current)
 	uint32_t* d_xlp_at = nullptr; size_t xlp_at_cap = 0; uint32_t* d_xlp = nullptr; size_t xlp_cap = 0; unsigned xlp_parts = 0; uint32_t* d_xlp_cur = nullptr;
 	const PairOut* xlp_pout = nullptr;
-	unsigned long long* d_counters = nullptr;   // [8]
+	unsigned long long* d_counters = nullptr;   // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
 	void* d_tmp[4] = {nullptr, nullptr, nullptr, nullptr};
 	size_t tmp_sz[4] = {0, 0, 0, 0};
 	hipEvent_t ev[12];
@@ -200,8 +175,6 @@ struct h2g_stream {
 	h2g_counters last;
 	bool mstreams_warm = false;          // every machine stream has run its two kernels once (go_run, large batches)
 	unsigned long long* d_warm_cnt = nullptr;   // counter block of those empty launches
-	BatchCtx parked[H2G_MAX_BATCHES];   // the batches that are not selected ([cur_batch] is unused: its fields are the stream's own)
-	unsigned cur_batch = 0;
 };
 
 // Large arrays travel through page-locked staging buffers filled by several threads: a pageable hipMemcpy of a human-size index (4.7 GB) was most of its 1.2 s load (round 6).
@@ -614,9 +587,10 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 	HIPCHK(hipMemset(s->d_counters, 0, H2G_NBUF * H2G_CNT_BLOCK * sizeof(unsigned long long)));
 	s->cnt_cur = s->d_counters;
 	if(max_reads) {
-		HIPCHK(hipMalloc((void**)&s->d_codes, max_bases + 64));
-		HIPCHK(hipMalloc((void**)&s->d_quals, max_bases + 64));
-		HIPCHK(hipMalloc((void**)&s->d_offs, (max_reads + 1) * 4));
+		BatchCtx& b0 = s->batch[0];
+		HIPCHK(hipMalloc((void**)&b0.d_codes, max_bases + 64));
+		HIPCHK(hipMalloc((void**)&b0.d_quals, max_bases + 64));
+		HIPCHK(hipMalloc((void**)&b0.d_offs, (max_reads + 1) * 4));
 		HIPCHK(hipMalloc((void**)&s->d_seed, max_reads * 2 * sizeof(h2g_seed_result)));
 	}
 	memset(&s->last, 0, sizeof s->last);
@@ -637,18 +611,16 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 extern "C" void h2g_stream_free(h2g_stream* s) {
 	if(!s) return;
 	(void)hipStreamSynchronize(s->st); (void)hipStreamSynchronize(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipStreamSynchronize(s->mst[k]);
-	(void)hipFree(s->d_codes); (void)hipFree(s->d_quals); (void)hipFree(s->d_offs); (void)hipFree(s->d_seed);
-	(void)hipFree(s->d_counters); (void)hipFree(s->d_names); (void)hipFree(s->d_name_offs); for(int k = 0; k < 2 * H2G_MSTREAMS_MAX; k++) { (void)hipFree(s->pool[k].ws); (void)hipFree(s->pool[k].gws); (void)hipFree(s->pool[k].sw); (void)hipFree(s->pool[k].sc); }
+	(void)hipFree(s->d_seed);
+	(void)hipFree(s->d_counters); for(int k = 0; k < 2 * H2G_MSTREAMS_MAX; k++) { (void)hipFree(s->pool[k].ws); (void)hipFree(s->pool[k].gws); (void)hipFree(s->pool[k].sw); (void)hipFree(s->pool[k].sc); }
 	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipFree(s->d_ovf_list[k]);
 	for(int k = 0; k < H2G_NBUF; k++) { (void)hipFree(s->d_bail_list[k]); (void)hipFree(s->d_fast_args[k]); (void)hipFree(s->d_fast_args[H2G_NBUF + k]); (void)hipFree(s->d_orphans[k]); (void)hipEventDestroy(s->ev_fast[k]); (void)hipEventDestroy(s->ev_mach[k]); (void)hipEventDestroy(s->ev_bails[k]); (void)hipEventDestroy(s->ev_drain[k]); }
 	for(int k = 0; k < H2G_FAST_POOLS; k++) { (void)hipFree(s->d_fast_slots[k]); (void)hipEventDestroy(s->ev_pool[k]); }
 	(void)hipFree(s->d_drain_slots); (void)hipFree(s->d_drain_sc);
 	for(int k = 0; k < 2; k++) (void)hipEventDestroy(s->ev_dr[k]);
 	(void)hipFree(s->d_fast_gws); (void)hipFree(s->d_fast_sc); (void)hipFree(s->d_sw_ws); (void)hipFree(s->d_sw_states); (void)hipFree(s->dbg_buf);
-	(void)hipFree(s->d_rout); (void)hipFree(s->d_aln); (void)hipFree(s->d_codes2); (void)hipFree(s->d_offs2); (void)hipFree(s->d_quals2);
-	(void)hipFree(s->d_names2); (void)hipFree(s->d_name_offs2); (void)hipFree(s->d_pout); (void)hipFree(s->d_paln[0]); (void)hipFree(s->d_paln[1]); (void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt);
-	for(unsigned b = 0; b < H2G_MAX_BATCHES; b++) if(b != s->cur_batch) {
-		BatchCtx& B = s->parked[b];
+	(void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt);
+	for(const BatchCtx& B : s->batch) {
 		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
 		(void)hipFree(B.d_quals2); (void)hipFree(B.d_names2); (void)hipFree(B.d_name_offs2); (void)hipFree(B.d_rout); (void)hipFree(B.d_aln); (void)hipFree(B.d_pout); (void)hipFree(B.d_paln[0]); (void)hipFree(B.d_paln[1]);
 	}
@@ -658,14 +630,18 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	delete s;
 }
 
-// both streams of a batch context (the second one only ever holds the machine pass behind a fast pass)
+// the machine streams, when one may hold work (st2_busy): waits for every one of them, then clears the flag
+static hipError_t sync_mach(h2g_stream* s) {
+	if(!s->st2_busy) return hipSuccess;
+	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { const hipError_t e = hipStreamSynchronize(s->mst[k]); if(e != hipSuccess) return e; }
+	s->st2_busy = false;
+	return hipSuccess;
+}
+// every stream of a batch context
 static hipError_t sync_all(h2g_stream* s) {
 	hipError_t e = hipStreamSynchronize(s->st);
 	if(e == hipSuccess && s->dst_busy) { e = hipStreamSynchronize(s->dst); s->dst_busy = false; }
-	if(e == hipSuccess && s->st2_busy) {
-		for(int k = 0; k < H2G_MSTREAMS_MAX && e == hipSuccess; k++) e = hipStreamSynchronize(s->mst[k]);
-		s->st2_busy = false;
-	}
+	if(e == hipSuccess && s->st2_busy) { e = sync_mach(s); s->st2_busy = false; }   // (the flag goes even when a wait fails)
 	return e;
 }
 extern "C" void* h2g_stream_hip(h2g_stream* s) { return s ? (void*)s->st : nullptr; }
@@ -681,22 +657,18 @@ extern "C" h2g_status h2g_stream_select_batch(h2g_stream* s, unsigned k) {
 	if(!s || k >= H2G_MAX_BATCHES) return H2G_ERR_ARG;
 	if(k == s->cur_batch) return H2G_OK;
 	HIPCHK(hipSetDevice(s->ix->device));
-	BatchCtx& out = s->parked[s->cur_batch];
-#define X(F) out.F = s->F;
-	H2G_BATCH_FIELDS(X)
-#undef X
-	out.d_paln[0] = s->d_paln[0]; out.d_paln[1] = s->d_paln[1];
-	BatchCtx& in = s->parked[k];
-	if(!in.d_codes && s->max_reads) {      // first use: the read buffers h2g_stream_create gives batch 0
-		HIPCHK(hipMalloc((void**)&in.d_codes, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&in.d_quals, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&in.d_offs, (s->max_reads + 1) * 4));
+	const BatchCtx& out = s->cur();
+	BatchCtx& in = s->batch[k];
+	if(s->max_reads) {      // first use: the read buffers h2g_stream_create gives batch 0
+		if(!in.d_codes) HIPCHK(hipMalloc((void**)&in.d_codes, s->max_bases + 64));
+		if(!in.d_quals) HIPCHK(hipMalloc((void**)&in.d_quals, s->max_bases + 64));
+		if(!in.d_offs) HIPCHK(hipMalloc((void**)&in.d_offs, (s->max_reads + 1) * 4));
 	}
 	// ... and result rows as large as the rows of the batch that is leaving (the option set a streaming caller runs every batch with): a batch's first run then
-	// allocates nothing — an allocation of gigabytes in the middle of a queue of runs waits for all of them
+	// allocates nothing — an allocation of gigabytes in the middle of a queue of runs waits for all of them.  (Their sizes are recorded once every allocation has succeeded.)
 	if(!in.d_pout && out.d_pout && out.paln_alloc) {
 		HIPCHK(hipMalloc((void**)&in.d_pout, s->max_reads * sizeof(PairOut)));
-		for(int m = 0; m < 2; m++) HIPCHK(hipMalloc((void**)&in.d_paln[m], out.paln_alloc * sizeof(h2g_alnres)));
+		for(int m = 0; m < 2; m++) if(!in.d_paln[m]) HIPCHK(hipMalloc((void**)&in.d_paln[m], out.paln_alloc * sizeof(h2g_alnres)));
 		in.paln_alloc = out.paln_alloc; in.pair_slots = out.pair_slots;
 		// (written once here: the first kernel to store into fresh device memory pays for its mapping — measured in bench.py's loop, lease F: 20 timed steps over 10 batches
 		// of which 5 had never been run took 18.5 ms each, 60 steps 12.1)
@@ -705,54 +677,56 @@ extern "C" h2g_status h2g_stream_select_batch(h2g_stream* s, unsigned k) {
 	}
 	if(!in.d_rout && out.d_rout && out.aln_alloc) {
 		HIPCHK(hipMalloc((void**)&in.d_rout, s->max_reads * sizeof(ReadOut)));
-		HIPCHK(hipMalloc((void**)&in.d_aln, out.aln_alloc * sizeof(h2g_alnres)));
+		if(!in.d_aln) HIPCHK(hipMalloc((void**)&in.d_aln, out.aln_alloc * sizeof(h2g_alnres)));
 		in.aln_alloc = out.aln_alloc; in.aln_slots = out.aln_slots;
 		HIPCHK(hipMemsetAsync(in.d_rout, 0, s->max_reads * sizeof(ReadOut), s->st));
 		HIPCHK(hipMemsetAsync(in.d_aln, 0, out.aln_alloc * sizeof(h2g_alnres), s->st));
 	}
-#define X(F) s->F = in.F;
-	H2G_BATCH_FIELDS(X)
-#undef X
-	s->d_paln[0] = in.d_paln[0]; s->d_paln[1] = in.d_paln[1];
-	in = BatchCtx();
 	s->cur_batch = k;
 	return H2G_OK;
 }
 
-static int tmp_buf(h2g_stream* s, int slot, size_t bytes, void** out) {
-	if(s->tmp_sz[slot] < bytes) {
-		(void)hipFree(s->d_tmp[slot]);
-		s->d_tmp[slot] = nullptr; s->tmp_sz[slot] = 0;
-		HIPCHK(hipMalloc(&s->d_tmp[slot], bytes + 256));
-		s->tmp_sz[slot] = bytes;
-	}
-	*out = s->d_tmp[slot];
+// Growth of a device buffer (or of n buffers of one size): when *have < want, frees them, allocates want x unit bytes each and records want.
+// A failed allocation leaves *have at 0, so the next call allocates again.
+static int grow(void** p, size_t* have, size_t want, size_t unit = 1, int n = 1) {
+	if(*have >= want) return H2G_OK;
+	for(int k = 0; k < n; k++) { (void)hipFree(p[k]); p[k] = nullptr; }
+	*have = 0;
+	for(int k = 0; k < n; k++) HIPCHK(hipMalloc(&p[k], want * unit));
+	*have = want;
 	return H2G_OK;
+}
+
+static int tmp_buf(h2g_stream* s, int slot, size_t bytes, void** out) {
+	const int rc = grow(&s->d_tmp[slot], &s->tmp_sz[slot], bytes + 256);     // (tmp_sz: the bytes allocated, 256 beyond the largest request)
+	*out = s->d_tmp[slot];
+	return rc;
 }
 
 extern "C" h2g_status h2g_set_reads(h2g_stream* s, const uint8_t* codes, const uint32_t* offs, const char* quals, size_t n) {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
 	if(!s || !codes || !offs || n > s->max_reads) return H2G_ERR_ARG;
+	BatchCtx& B = s->cur();
 	size_t nb = offs[n];
 	if(nb > s->max_bases) return H2G_ERR_ARG;
 	uint32_t mx = 0;
 	for(size_t i = 0; i < n; i++) { const uint32_t l = offs[i + 1] - offs[i]; if(l > mx) mx = l; }
-	s->max_read_len = mx;
-	HIPCHK(hipMemcpyAsync(s->d_codes, codes, nb, hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemcpyAsync(s->d_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
-	s->has_quals = quals != nullptr;
-	if(quals) HIPCHK(hipMemcpyAsync(s->d_quals, quals, nb, hipMemcpyHostToDevice, s->st));
+	B.max_read_len = mx;
+	HIPCHK(hipMemcpyAsync(B.d_codes, codes, nb, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
+	B.has_quals = quals != nullptr;
+	if(quals) HIPCHK(hipMemcpyAsync(B.d_quals, quals, nb, hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
-	s->n_reads = n;
-	s->has_names = false;
-	s->has_mates = false;
+	B.n_reads = n;
+	B.has_names = false;
+	B.has_mates = false;
 	s->ledits_touched = 0;            // (long-edit lists of the batch this one replaces are nobody's any more)
 	return H2G_OK;
 }
 
 static DReads dreads(const h2g_stream* s) {
 	DReads r;
-	r.codes = s->d_codes; r.offs = s->d_offs; r.quals = s->has_quals ? s->d_quals : nullptr; r.n = (uint32_t)s->n_reads;
+	r.codes = s->cur().d_codes; r.offs = s->cur().d_offs; r.quals = s->cur().has_quals ? s->cur().d_quals : nullptr; r.n = (uint32_t)s->cur().n_reads;
 	return r;
 }
 
@@ -1011,8 +985,8 @@ static int launch_rank(h2g_stream* s, const uint32_t* d_rows, const uint8_t* d_c
 		} else if(variant == 5 && synth) {
 			hipLaunchKernelGGL(k_rank_exp<5>, dim3(grid_for(n, 256)), dim3(256), 0, s->st, g, d_out, n, seed);
 		} else if(variant == 10 && synth) {
-			HIPCHK(hipMemsetAsync(s->d_counters + 6, 0, 8, s->st));
-			hipLaunchKernelGGL(k_rank_v0_sampled, dim3(grid_for(n, 256)), dim3(256), 0, s->st, g, d_out, n, seed, s->d_counters + 6);
+			HIPCHK(hipMemsetAsync(s->d_counters + H2G_CNT_BENCH_SUM, 0, 8, s->st));
+			hipLaunchKernelGGL(k_rank_v0_sampled, dim3(grid_for(n, 256)), dim3(256), 0, s->st, g, d_out, n, seed, s->d_counters + H2G_CNT_BENCH_SUM);
 		} else if(variant == 11 || variant == 12) {
 			// variant 0's loop in the chain kernel's geometry: ONE 512-thread workgroup per CU (11), two (12)
 			hipLaunchKernelGGL(k_rank_v0_512, dim3(variant == 11 ? 256u : 512u), dim3(512), 0, s->st, g, d_rows, d_cs, d_out, n, seed, synth);
@@ -1061,10 +1035,10 @@ extern "C" h2g_status h2g_rank_bench_synth(h2g_stream* s, size_t n, uint64_t see
 	rc = launch_rank(s, nullptr, nullptr, (uint32_t*)dout, n, seed, 1, variant, repeats, kernel_ms);
 	if(rc) return rc;
 	if(checksum) {
-		HIPCHK(hipMemsetAsync(s->d_counters + 7, 0, 8, s->st));
-		if(variant != 10) hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, s->st, (const uint32_t*)dout, n, s->d_counters + 7);
+		HIPCHK(hipMemsetAsync(s->d_counters + H2G_CNT_BENCH_CHECKSUM, 0, 8, s->st));
+		if(variant != 10) hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, s->st, (const uint32_t*)dout, n, s->d_counters + H2G_CNT_BENCH_CHECKSUM);
 		unsigned long long v = 0;
-		HIPCHK(hipMemcpyAsync(&v, s->d_counters + (variant == 10 ? 6 : 7), 8, hipMemcpyDeviceToHost, s->st));   // (variant 10 sums on the fly: the last repeat's)
+		HIPCHK(hipMemcpyAsync(&v, s->d_counters + (variant == 10 ? H2G_CNT_BENCH_SUM : H2G_CNT_BENCH_CHECKSUM), 8, hipMemcpyDeviceToHost, s->st));   // (variant 10 sums on the fly: the last repeat's)
 		HIPCHK(sync_all(s));
 		*checksum = v;
 	}
@@ -1146,7 +1120,7 @@ extern "C" H2G_EXPORT h2g_status h2g_rank_chain_bench(h2g_stream* s, size_t ncha
 	switch(chains_per_lane) { H2G_CHAIN_CASE(1) H2G_CHAIN_CASE(2) H2G_CHAIN_CASE(4) H2G_CHAIN_CASE(8) }
 #undef H2G_CHAIN_CASE
 	if(lds_bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) (void)hipGetLastError();
-	unsigned long long* dsum = s->d_counters + 7;
+	unsigned long long* dsum = s->d_counters + H2G_CNT_BENCH_CHECKSUM;
 	HIPCHK(hipEventRecord(s->ev[0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		HIPCHK(hipMemsetAsync(dsum, 0, 8, s->st));
@@ -1222,7 +1196,7 @@ extern "C" H2G_EXPORT h2g_status h2g_glf_chain_bench(h2g_stream* s, size_t nchai
 	if(repeats < 1) repeats = 1;
 	const void* fn = chains_per_lane == 1 ? (const void*)k_glf_chain<1> : chains_per_lane == 2 ? (const void*)k_glf_chain<2> : (const void*)k_glf_chain<4>;
 	if(lds_bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) (void)hipGetLastError();
-	unsigned long long* dsum = s->d_counters + 7;
+	unsigned long long* dsum = s->d_counters + H2G_CNT_BENCH_CHECKSUM;
 	HIPCHK(hipEventRecord(s->ev[0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		HIPCHK(hipMemsetAsync(dsum, 0, 8, s->st));
@@ -1415,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_sw_backtrace(DRef ref, DReads rd, SwPar
 }
 
 static int need_reads(h2g_stream* s) {
-	if(s->n_reads == 0) { snprintf(g_err, sizeof g_err, "no read batch set (h2g_set_reads)"); return H2G_ERR_ARG; }
+	if(s->cur().n_reads == 0) { snprintf(g_err, sizeof g_err, "no read batch set (h2g_set_reads)"); return H2G_ERR_ARG; }
 	return H2G_OK;
 }
 static int need_graph(h2g_stream* s) {
@@ -1455,7 +1429,7 @@ extern "C" h2g_status h2g_adjust_with_alt(h2g_stream* s, const h2g_adjust_query*
 	if(!s || !q || !hits || !nhits || n == 0 || cap == 0) return H2G_ERR_ARG;
 	int rc;
 	if((rc = need_reads(s)) || (rc = need_graph(s))) return rc;
-	for(size_t i = 0; i < n; i++) if(q[i].read >= s->n_reads || q[i].tidx >= s->ix->dr.nrefs) return H2G_ERR_ARG;
+	for(size_t i = 0; i < n; i++) if(q[i].read >= s->cur().n_reads || q[i].tidx >= s->ix->dr.nrefs) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
 	const unsigned grid = grid_for(n, 256) > 128 ? 128 : grid_for(n, 256);
 	void *dq, *dh, *dn, *dscr;
@@ -1507,7 +1481,7 @@ extern "C" h2g_status h2g_fm_search_graph(h2g_stream* s, const h2g_fm_query* q, 
 	int rc;
 	if((rc = need_reads(s)) || (rc = need_graph(s))) return rc;
 	for(size_t i = 0; i < n; i++) {
-		if(q[i].read >= s->n_reads) return H2G_ERR_ARG;
+		if(q[i].read >= s->cur().n_reads) return H2G_ERR_ARG;
 		if(q[i].mode != H2G_FM_PARTIAL) { snprintf(g_err, sizeof g_err, "fm_search: only H2G_FM_PARTIAL built"); return H2G_ERR_UNSUPPORTED; }
 	}
 	HIPCHK(hipSetDevice(s->ix->device));
@@ -1531,7 +1505,7 @@ extern "C" h2g_status h2g_fm_search(h2g_stream* s, const h2g_fm_query* q, size_t
 		return h2g_fm_search_graph(s, q, n, khits, khits * 2 > 5 ? khits * 2 : 5, out, nullptr);
 	if((rc = need_reads(s)) || (rc = need_linear(s))) return rc;
 	for(size_t i = 0; i < n; i++) {
-		if(q[i].read >= s->n_reads) return H2G_ERR_ARG;
+		if(q[i].read >= s->cur().n_reads) return H2G_ERR_ARG;
 		if(q[i].mode != H2G_FM_PARTIAL) { snprintf(g_err, sizeof g_err, "fm_search: only H2G_FM_PARTIAL built"); return H2G_ERR_UNSUPPORTED; }
 	}
 	HIPCHK(hipSetDevice(s->ix->device));
@@ -1625,7 +1599,7 @@ extern "C" h2g_status h2g_ext_search(h2g_stream* s, const h2g_ext_search_query* 
 	const bool graph = !s->ix->dg.linear;
 	const uint32_t nlocal = s->ix->dls.n;
 	for(size_t i = 0; i < n; i++) {
-		if(q[i].read >= s->n_reads) return H2G_ERR_ARG;
+		if(q[i].read >= s->cur().n_reads) return H2G_ERR_ARG;
 		if(q[i].lidx != H2G_MAX && (!s->ix->has_local || q[i].lidx >= nlocal)) return H2G_ERR_ARG;
 	}
 	HIPCHK(hipSetDevice(s->ix->device));
@@ -1702,8 +1676,8 @@ extern "C" h2g_status h2g_sw_align(h2g_stream* s, const h2g_sw_query* q, size_t 
 	int rc;
 	if((rc = need_reads(s))) return rc;
 	if(s->ix->synthetic) { snprintf(g_err, sizeof g_err, "synthetic index: rank only"); return H2G_ERR_ARG; }
-	for(size_t i = 0; i < n; i++) if(q[i].read >= s->n_reads || q[i].tidx >= s->ix->dr.nrefs) return H2G_ERR_ARG;
-	const uint32_t maxlen = s->max_read_len;   // longest read of the resident batch: sizes the per-problem workspace
+	for(size_t i = 0; i < n; i++) if(q[i].read >= s->cur().n_reads || q[i].tidx >= s->ix->dr.nrefs) return H2G_ERR_ARG;
+	const uint32_t maxlen = s->cur().max_read_len;   // longest read of the resident batch: sizes the per-problem workspace
 	if(maxlen == 0 || maxlen > H2G_SW_MAX_ROWS) { snprintf(g_err, sizeof g_err, "h2g_sw_align: read length %u outside 1..%d", maxlen, H2G_SW_MAX_ROWS); return H2G_ERR_ARG; }
 	HIPCHK(hipSetDevice(s->ix->device));
 	const size_t ncolmax = maxlen + 4 * H2G_SW_MAXGAP, ndmax = maxlen + ncolmax - 1;
@@ -1721,16 +1695,10 @@ extern "C" h2g_status h2g_sw_align(h2g_stream* s, const h2g_sw_query* q, size_t 
 	if(batch < 256) batch = 256;
 	if(batch > n) batch = n;
 	const size_t bt_threads = ((batch + 255) / 256) * 256;
-	if(s->sw_ws_bytes < batch * ws.stride) {
-		(void)hipFree(s->d_sw_ws); s->d_sw_ws = nullptr; s->sw_ws_bytes = 0;
-		HIPCHK(hipMalloc((void**)&s->d_sw_ws, batch * ws.stride));
-		s->sw_ws_bytes = batch * ws.stride;
-	}
+	if((rc = grow((void**)&s->d_sw_ws, &s->sw_ws_bytes, batch * ws.stride))) return rc;
 	if(s->sw_states < bt_threads) {
-		(void)hipFree(s->d_sw_states); s->d_sw_states = nullptr; s->sw_states = 0;
-		HIPCHK(hipMalloc((void**)&s->d_sw_states, bt_threads * sizeof(SwLaneState)));
+		if((rc = grow((void**)&s->d_sw_states, &s->sw_states, bt_threads, sizeof(SwLaneState)))) return rc;
 		HIPCHK(hipMemset(s->d_sw_states, 0, bt_threads * sizeof(SwLaneState)));   // mask-table generations start at 0
-		s->sw_states = bt_threads;
 	}
 	ws.base = s->d_sw_ws;
 	void *dq, *dout;
@@ -1786,7 +1754,7 @@ extern "C" h2g_status h2g_extend(h2g_stream* s, h2g_ghit* hits, const h2g_ext_ar
 	if(s->ix->synthetic) { snprintf(g_err, sizeof g_err, "synthetic index: rank only"); return H2G_ERR_ARG; }
 	const bool graph = !s->ix->dg.linear;
 	for(size_t i = 0; i < n; i++) {
-		if(hits[i].read >= s->n_reads || hits[i].tidx >= s->ix->dr.nrefs || hits[i].nedits > H2G_MAX_EDITS) return H2G_ERR_ARG;
+		if(hits[i].read >= s->cur().n_reads || hits[i].tidx >= s->ix->dr.nrefs || hits[i].nedits > H2G_MAX_EDITS) return H2G_ERR_ARG;
 	}
 	HIPCHK(hipSetDevice(s->ix->device));
 	void *dh, *da, *dres;
@@ -1826,8 +1794,8 @@ __global__ __launch_bounds__(256) void k_seed_search(DGfm g, DReads rd, h2g_seed
 		out[i].hit = h;
 		nrank += h.nrank; nside += h.nside;
 	}
-	wave_add(counters + 0, nrank);
-	wave_add(counters + 1, nside);
+	wave_add(counters + H2G_CNT_RANK, nrank);
+	wave_add(counters + H2G_CNT_SIDE, nside);
 }
 
 // K2: coordinates + 0-mismatch extension for every partial hit
@@ -1843,8 +1811,8 @@ __global__ __launch_bounds__(256) void k_seed_resolve_extend(DGfm g, DRef ref, D
 		resolve_extend_item(g, ref, sc, sv, &out[i], &scratch);
 		nsteps += out[i].nsteps; next += out[i].ncoords;
 	}
-	wave_add(counters + 2, nsteps);
-	wave_add(counters + 3, next);
+	wave_add(counters + H2G_CNT_STEPS, nsteps);
+	wave_add(counters + H2G_CNT_EXT, next);
 }
 
 extern "C" void h2g_seed_params_init(h2g_seed_params* p, const h2g_index* ix, int no_spliced) {
@@ -1860,7 +1828,7 @@ extern "C" h2g_status h2g_seed_extend_run(h2g_stream* s, const h2g_seed_params* 
 	int rc;
 	if((rc = need_reads(s)) || (rc = need_linear(s))) return rc;
 	HIPCHK(hipSetDevice(s->ix->device));
-	const size_t n = s->n_reads * 2;
+	const size_t n = s->cur().n_reads * 2;
 	HIPCHK(hipMemsetAsync(s->d_counters, 0, 4 * sizeof(unsigned long long), s->st));
 	DScoring sc;
 	HIPCHK(hipEventRecord(s->ev[2], s->st));
@@ -1874,7 +1842,7 @@ extern "C" h2g_status h2g_seed_extend_run(h2g_stream* s, const h2g_seed_params* 
 }
 
 extern "C" h2g_status h2g_seed_extend_fetch(h2g_stream* s, h2g_seed_result* out, size_t first_read, size_t n_reads) {
-	if(!s || !out || first_read + n_reads > s->n_reads) return H2G_ERR_ARG;
+	if(!s || !out || first_read + n_reads > s->cur().n_reads) return H2G_ERR_ARG;
 	HIPCHK(hipMemcpyAsync(out, s->d_seed + first_read * 2, n_reads * 2 * sizeof *out, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
 	return H2G_OK;
@@ -1917,20 +1885,21 @@ extern "C" void h2g_align_params_presets(h2g_align_params* p, const h2g_index* i
 
 extern "C" h2g_status h2g_set_read_names(h2g_stream* s, const char* bytes, const uint32_t* offs, size_t n) {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
-	if(!s || !bytes || !offs || n != s->n_reads || n == 0) return H2G_ERR_ARG;
+	if(!s || !bytes || !offs || n != s->cur().n_reads || n == 0) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
+	BatchCtx& B = s->cur();
 	size_t nb = offs[n];
-	if(s->names_cap < nb || !s->d_name_offs) {
-		(void)hipFree(s->d_names); (void)hipFree(s->d_name_offs);
-		s->d_names = nullptr; s->d_name_offs = nullptr;
-		HIPCHK(hipMalloc((void**)&s->d_names, nb + 64));
-		HIPCHK(hipMalloc((void**)&s->d_name_offs, (s->max_reads + 1) * 4));
-		s->names_cap = nb;
+	if(B.names_cap < nb || !B.d_name_offs) {
+		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
+		B.d_names = nullptr; B.d_name_offs = nullptr;
+		HIPCHK(hipMalloc((void**)&B.d_names, nb + 64));
+		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
+		B.names_cap = nb;
 	}
-	HIPCHK(hipMemcpyAsync(s->d_names, bytes, nb, hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemcpyAsync(s->d_name_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_names, bytes, nb, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_name_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
-	s->has_names = true;
+	B.has_names = true;
 	return H2G_OK;
 }
 
@@ -1938,26 +1907,27 @@ extern "C" h2g_status h2g_set_mates(h2g_stream* s, const uint8_t* codes2, const 
                                     const char* nb2, const uint32_t* noffs2, size_t n)
 {
 	if(s) HIPCHK(sync_all(s));
-	if(!s || !codes2 || !offs2 || !nb2 || !noffs2 || n != s->n_reads || n == 0) return H2G_ERR_ARG;
+	if(!s || !codes2 || !offs2 || !nb2 || !noffs2 || n != s->cur().n_reads || n == 0) return H2G_ERR_ARG;
 	if(offs2[n] > s->max_bases) return H2G_ERR_ARG;
-	for(size_t i = 0; i < n; i++) { const uint32_t l = offs2[i + 1] - offs2[i]; if(l > s->max_read_len) s->max_read_len = l; }
+	BatchCtx& B = s->cur();
+	for(size_t i = 0; i < n; i++) { const uint32_t l = offs2[i + 1] - offs2[i]; if(l > B.max_read_len) B.max_read_len = l; }
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(!s->d_codes2) {
-		HIPCHK(hipMalloc((void**)&s->d_codes2, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&s->d_quals2, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&s->d_offs2, (s->max_reads + 1) * 4));
-		HIPCHK(hipMalloc((void**)&s->d_name_offs2, (s->max_reads + 1) * 4));
+	if(!B.d_codes2) {
+		HIPCHK(hipMalloc((void**)&B.d_codes2, s->max_bases + 64));
+		HIPCHK(hipMalloc((void**)&B.d_quals2, s->max_bases + 64));
+		HIPCHK(hipMalloc((void**)&B.d_offs2, (s->max_reads + 1) * 4));
+		HIPCHK(hipMalloc((void**)&B.d_name_offs2, (s->max_reads + 1) * 4));
 	}
-	(void)hipFree(s->d_names2); s->d_names2 = nullptr;
-	HIPCHK(hipMalloc((void**)&s->d_names2, noffs2[n] + 64));
-	HIPCHK(hipMemcpyAsync(s->d_codes2, codes2, offs2[n], hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemcpyAsync(s->d_offs2, offs2, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
-	s->has_quals2 = quals2 != nullptr;
-	if(quals2) HIPCHK(hipMemcpyAsync(s->d_quals2, quals2, offs2[n], hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemcpyAsync(s->d_names2, nb2, noffs2[n], hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemcpyAsync(s->d_name_offs2, noffs2, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
+	(void)hipFree(B.d_names2); B.d_names2 = nullptr;
+	HIPCHK(hipMalloc((void**)&B.d_names2, noffs2[n] + 64));
+	HIPCHK(hipMemcpyAsync(B.d_codes2, codes2, offs2[n], hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_offs2, offs2, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
+	B.has_quals2 = quals2 != nullptr;
+	if(quals2) HIPCHK(hipMemcpyAsync(B.d_quals2, quals2, offs2[n], hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_names2, nb2, noffs2[n], hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(B.d_name_offs2, noffs2, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
-	s->has_mates = true;
+	B.has_mates = true;
 	return H2G_OK;
 }
 
@@ -1971,9 +1941,9 @@ extern "C" h2g_status h2g_combine_with(h2g_stream* s, const h2g_align_params* p,
 	if(s->ix->synthetic) { snprintf(g_err, sizeof g_err, "synthetic index: rank only"); return H2G_ERR_ARG; }
 	const bool linear = s->ix->dg.linear != 0;
 	for(size_t i = 0; i < n; i++) {
-		if(a[i].read >= s->n_reads || b[i].read != a[i].read || a[i].tidx >= s->ix->dr.nrefs || b[i].tidx >= s->ix->dr.nrefs || a[i].nedits > H2G_MAX_EDITS || b[i].nedits > H2G_MAX_EDITS) return H2G_ERR_ARG;
+		if(a[i].read >= s->cur().n_reads || b[i].read != a[i].read || a[i].tidx >= s->ix->dr.nrefs || b[i].tidx >= s->ix->dr.nrefs || a[i].nedits > H2G_MAX_EDITS || b[i].nedits > H2G_MAX_EDITS) return H2G_ERR_ARG;
 	}
-	if(s->max_read_len > H2G_COMBINE_MAXLEN) return H2G_ERR_ARG;      // (the joint's prefix / suffix score arrays)
+	if(s->cur().max_read_len > H2G_COMBINE_MAXLEN) return H2G_ERR_ARG;      // (the joint's prefix / suffix score arrays)
 	h2g_align_params hp;
 	if(p) hp = *p; else align_params_defaults(&hp, linear);
 	AlnParams P = aln_params_from(hp, hp.no_spliced_alignment != 0, linear);
@@ -2025,36 +1995,25 @@ static const GoUnit& go_unit(bool linear, bool big, bool spliced = false, bool x
 static int go_pool_for(h2g_stream* s, int which, const GoUnit& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
 	h2g_stream::GoPool& pl = s->pool[which];
 	const size_t wsb = u.ws_bytes(), gwb = u.gws_bytes();
-	if(pl.ws_bytes < slots * wsb) {
-		(void)hipFree(pl.ws); pl.ws = nullptr; pl.ws_bytes = 0;
-		HIPCHK(hipMalloc((void**)&pl.ws, slots * wsb));
-		pl.ws_bytes = slots * wsb;
-	}
+	int rc;
+	if((rc = grow((void**)&pl.ws, &pl.ws_bytes, slots * wsb))) return rc;
 	a->pool = pl.ws; a->ws_stride = wsb; a->slot_off = u.slot_off(); a->gsl_off = u.gsl_off();
 	a->gws_base = nullptr; a->gws_stride = gwb;
 	if(gwb) {
-		if(pl.gws_bytes < lanes * gwb) {
-			(void)hipFree(pl.gws); pl.gws = nullptr; pl.gws_bytes = 0;
-			HIPCHK(hipMalloc((void**)&pl.gws, lanes * gwb));
-			pl.gws_bytes = lanes * gwb;
-		}
+		if((rc = grow((void**)&pl.gws, &pl.gws_bytes, lanes * gwb))) return rc;
 		a->gws_base = pl.gws;
 	}
-	if(pl.sc_lanes < lanes) {
-		(void)hipFree(pl.sc); pl.sc = nullptr; pl.sc_lanes = 0;
-		HIPCHK(hipMalloc((void**)&pl.sc, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))));
-		pl.sc_lanes = lanes;
-	}
+	if((rc = grow((void**)&pl.sc, &pl.sc_bytes, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))))) return rc;
 	a->sc_base = pl.sc;
 	a->sw_base = nullptr; a->sw_stride = 0;
 	if(bowtie2_dp) {
-		const uint32_t swlen = s->max_read_len > H2G_SW_MAX_ROWS ? (uint32_t)H2G_SW_MAX_ROWS : s->max_read_len;
+		const uint32_t swlen = s->cur().max_read_len > H2G_SW_MAX_ROWS ? (uint32_t)H2G_SW_MAX_ROWS : s->cur().max_read_len;
 		bool wide = false;                                        // some read length of the batch may put minsc below -254: 16-bit cells
 		for(uint32_t l = 1; l <= swlen && !wide; l++) wide = sw_wide_for(min_score_for(a->P, l));
 		const size_t stride = (u.sw_bytes(swlen, wide ? 1 : 0) + 255) & ~(size_t)255;   // the unit's own SwLaneState (the large-workspace units hold 192-edit records)
-		if(pl.sw_stride < stride || pl.sw_lanes < lanes) {
-			(void)hipFree(pl.sw); pl.sw = nullptr; pl.sw_stride = 0; pl.sw_lanes = 0;
-			HIPCHK(hipMalloc((void**)&pl.sw, stride * lanes));
+		if(pl.sw_stride < stride || pl.sw_lanes < lanes) {      // (either one short: the pool is allocated again)
+			size_t had = 0; pl.sw_stride = 0; pl.sw_lanes = 0;
+			if((rc = grow((void**)&pl.sw, &had, stride * lanes))) return rc;
 			HIPCHK(hipMemset(pl.sw, 0, stride * lanes));   // SwLaneState: mask-table generations start at 0
 			pl.sw_stride = stride; pl.sw_lanes = lanes;
 		}
@@ -2065,21 +2024,12 @@ static int go_pool_for(h2g_stream* s, int which, const GoUnit& u, size_t slots, 
 
 // (the reads whose main-pass workspace overflowed are listed by the pass itself — MachOut::defer_list — and their rows left alone until the second pass writes them)
 
-// HI_Aligner::go for every read (pair) of the resident batch.  Two passes, both asynchronous on the stream: the main pass
-// with the default workspace, then the reads it flagged (a list overflowed) once more through the large-workspace unit,
-// whose results replace theirs.  Reads still flagged after that keep `overflow` set (n_overflow counts them).
-static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) {
-	if(!s || !p) return H2G_ERR_ARG;
+// ---- go_run, phase by phase.  The option checks: no device calls
+static int go_check(h2g_stream* s, const h2g_align_params* p, bool paired) {
 	int rc;
 	if((rc = need_reads(s)) || (rc = need_alignable(s))) return rc;
 	if(!s->ix->has_local) { snprintf(g_err, sizeof g_err, "align: index loaded without local (.5/.6) indexes"); return H2G_ERR_ARG; }
-	if(!s->has_names || (paired && !s->has_mates)) { snprintf(g_err, sizeof g_err, "align: read names (h2g_set_read_names)%s not set", paired ? " / mates (h2g_set_mates)" : ""); return H2G_ERR_ARG; }
-	const bool linear = s->ix->dg.linear != 0;
-	// --haplotype is compiled into the units that also carry the splice-site database (H2G_HAPLOTYPE, h2g_graph.h); they run either mode
-	// ... and so are -I, --rf / --ff, --nofw / --norc (H2G_EXT_OPTS, h2g_align.h)
-	// ... and --avoid-pseudogene / --tmo (al_report's transcriptome policy; --tmo also under --no-spliced-alignment)
-	const bool ext_opts = pe_flags_from(*p) != H2G_PE_DEFAULT || p->min_frag_len != 0 || p->transcriptome_mapping_only || (p->avoid_pseudogene && !p->no_spliced_alignment);
-	const bool spl = !p->no_spliced_alignment || (p->use_haplotype && !linear) || ext_opts;
+	if(!s->cur().has_names || (paired && !s->cur().has_mates)) { snprintf(g_err, sizeof g_err, "align: read names (h2g_set_read_names)%s not set", paired ? " / mates (h2g_set_mates)" : ""); return H2G_ERR_ARG; }
 	if(!p->no_spliced_alignment) {
 		// spliced alignment: combineWith places introns (hi_aligner.h:1588-1739) and every read is independent when novel splice
 		// sites are not shared (--no-temp-splicesite); the shared SpliceSiteDB of the default mode and graph indexes are not built
@@ -2097,12 +2047,6 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 			return H2G_ERR_UNSUPPORTED;
 		}
 	}
-	const uint32_t maxsz = p->khits > p->kseeds ? p->khits : p->kseeds;
-	uint32_t caps[5], bcaps[5];
-	go_unit(linear, false, spl).caps(caps); go_unit(linear, true, spl).caps(bcaps);
-	// a run beyond what the large units hold (more alignments selected than H2G_SELECT_CAP, or a list beyond their AL_MAX_GHITS) runs on the
-	// extra-large units (h2g_go_xl.h), whole: no fast pass, no second pass
-	const bool xl = p->khits > H2G_SELECT_CAP || maxsz > bcaps[0];
 	if(p->khits == 0 || p->khits > H2G_KHITS_MAX || p->kseeds < p->khits || p->kseeds > H2G_KSEEDS_MAX) {
 		snprintf(g_err, sizeof g_err, "align: -k %u / --max-seeds %u outside the built range (1 <= -k <= %u, -k <= --max-seeds <= %u)", p->khits, p->kseeds, (unsigned)H2G_KHITS_MAX, (unsigned)H2G_KSEEDS_MAX);
 		return H2G_ERR_ARG;
@@ -2110,159 +2054,200 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	if(p->bowtie2_dp > 2 || p->pe_orientation > 2 || p->min_frag_len >= (1u << 24)) return H2G_ERR_ARG;
 	if(p->pen_conflictsplice < 0) { snprintf(g_err, sizeof g_err, "align: --pen-conflictsplice arg must be at least 0"); return H2G_ERR_ARG; }
 	if(p->max_alts_tried && p->max_alts_tried < 8) { snprintf(g_err, sizeof g_err, "align: --max-altstried arg must be at least 8"); return H2G_ERR_ARG; }
-	if(p->bowtie2_dp) {
-		if(s->max_read_len == 0) return H2G_ERR_ARG;
-		// a read longer than H2G_SW_MAX_ROWS is flagged by the kernel (overflow bit 256) instead of run through the DP
-	}
-	HIPCHK(hipSetDevice(s->ix->device));
-	// Runs queued back to back share the result arrays (rows per read, record stride): a machine pass still in flight may only meet a
-	// run over the same reads with the same options.  Anything else waits for the machine streams first.
-	if(s->st2_busy && (s->last_paired != (paired ? 1 : 0) || memcmp(&s->last_p, p, sizeof *p) != 0)) {
-		for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));
-		s->st2_busy = false;
-	}
-	s->last_p = *p; s->last_paired = paired ? 1 : 0;
-	const bool big_main = maxsz > caps[0];                  // (every XL run is one: khits > 32 or maxsz > 64 exceeds the default units' lists)
-	const GoUnit& U = go_unit(linear, big_main, spl, xl);
+	// (a read longer than H2G_SW_MAX_ROWS is flagged by the kernel — overflow bit 256 — instead of run through the DP)
+	if(p->bowtie2_dp && s->cur().max_read_len == 0) return H2G_ERR_ARG;
+	return H2G_OK;
+}
+
+// what a run does, from its options, the batch and the stream's knobs: no device calls, no side effects
+struct GoPlan {
+	bool linear, spl, xl, big_main, fast, second;
+	const GoUnit *U, *L;           // the main pass's unit; the large-workspace unit (the second pass, the machine streams' warm-up)
+	uint32_t geo[4], lgeo[4];      // their geometries: [0] threads per workgroup, [1] reads in flight per workgroup
+	unsigned grid, M, bgrid;       // workgroups of the main pass; machine passes in flight (per-run buffers: M + 1 deep); workgroups of a second pass
+	unsigned mach_cap, pool_cap;   // workgroups of one machine pass behind a fast pass, and what its pools are sized for
+	size_t units;                  // batch units: pairs, or two unpaired reads
+};
+static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paired) {
+	GoPlan plan, *g = &plan;
+	const size_t n_reads = s->cur().n_reads;
+	g->linear = s->ix->dg.linear != 0;
+	// --haplotype is compiled into the units that also carry the splice-site database (H2G_HAPLOTYPE, h2g_graph.h); they run either mode
+	// ... and so are -I, --rf / --ff, --nofw / --norc (H2G_EXT_OPTS, h2g_align.h)
+	// ... and --avoid-pseudogene / --tmo (al_report's transcriptome policy; --tmo also under --no-spliced-alignment)
+	const bool ext_opts = pe_flags_from(*p) != H2G_PE_DEFAULT || p->min_frag_len != 0 || p->transcriptome_mapping_only || (p->avoid_pseudogene && !p->no_spliced_alignment);
+	g->spl = !p->no_spliced_alignment || (p->use_haplotype && !g->linear) || ext_opts;
+	const uint32_t maxsz = p->khits > p->kseeds ? p->khits : p->kseeds;
+	uint32_t caps[5], bcaps[5];
+	g->L = &go_unit(g->linear, true, g->spl);
+	go_unit(g->linear, false, g->spl).caps(caps); g->L->caps(bcaps);
+	// a run beyond what the large units hold (more alignments selected than H2G_SELECT_CAP, or a list beyond their AL_MAX_GHITS) runs on the
+	// extra-large units (h2g_go_xl.h), whole: no fast pass, no second pass
+	g->xl = p->khits > H2G_SELECT_CAP || maxsz > bcaps[0];
+	g->big_main = maxsz > caps[0];                  // (every XL run is one: khits > 32 or maxsz > 64 exceeds the default units' lists)
+	g->U = &go_unit(g->linear, g->big_main, g->spl, g->xl);
 	// (graph indexes: h2g_k_go_fast_graph.hip, the same pass over the graph form of the compact state; --haplotype and the pair-policy options are `spl`)
-	const bool fast = s->tune.fast && !spl && !big_main && p->no_spliced_alignment && !p->secondary && !p->bowtie2_dp;
+	g->fast = s->tune.fast && !g->spl && !g->big_main && p->no_spliced_alignment && !p->secondary && !p->bowtie2_dp;
+	g->second = !g->big_main && !s->tune.no_second_pass;     // (no_second_pass: a measurement / debugging knob)
 	// geometry of the unit: workgroups of geo[0] threads own geo[1] reads in flight; resident workgroups per CU = what the
 	// unit's waves per SIMD and the LDS (rings + one packed-read region per mate) allow
-	uint32_t geo[4];
-	U.geometry(geo);
-	const unsigned block = geo[0];
-	size_t per_cu = (size_t)U.waves() * 256 / block;
-	const size_t lds_blocks = (160u * 1024u) / (geo[2] + (paired ? 2u : 1u) * geo[3]);
+	g->U->geometry(g->geo); g->L->geometry(g->lgeo);
+	size_t per_cu = (size_t)g->U->waves() * 256 / g->geo[0];
+	const size_t lds_blocks = (160u * 1024u) / (g->geo[2] + (paired ? 2u : 1u) * g->geo[3]);
 	if(per_cu > lds_blocks) per_cu = lds_blocks;
 	if(per_cu < 1) per_cu = 1;
 	if(s->tune.blocks_per_cu > 0) per_cu = (size_t)s->tune.blocks_per_cu;
-	size_t want = (s->n_reads + geo[1] - 1) / geo[1];
+	const size_t want = (n_reads + g->geo[1] - 1) / g->geo[1];
 	size_t maxblocks = 256 * per_cu;
-	if(big_main && maxblocks > 32) maxblocks = 32;        // ~1.3 MB of workspace per read in flight
-	if(xl && maxblocks > 12) maxblocks = 12;              // XL: 18.7 MB per read in flight, 12 x 128 of them (h2g_go_xl.h)
-	const unsigned grid = (unsigned)(want < 1 ? 1 : (want > maxblocks ? maxblocks : want));
-	GoArgs A;
-	memset(&A, 0, sizeof A);
-	A.g = s->ix->dg; A.ref = s->ix->dr; A.ls = s->ix->dls; A.alts = s->ix->dalts;
-	if(p->max_alts_tried) A.alts.maxAltsTried = p->max_alts_tried;          // --max-altstried
-	if(p->use_haplotype && !linear && A.alts.n) A.alts.has_splice |= 2u;   // --haplotype: the table behind the ALTs is read (h2g_graph.h haps_of)
-	A.rd1 = dreads(s); A.rd2 = A.rd1;
-	if(paired) { A.rd2.codes = s->d_codes2; A.rd2.offs = s->d_offs2; A.rd2.quals = s->has_quals2 ? s->d_quals2 : nullptr; }
-	A.P = aln_params_from(*p, p->no_spliced_alignment != 0, linear);
-	if(!p->no_spliced_alignment) { A.ssdb = s->ix->dssdb; A.rdid_base = p->first_read_id; }
-	const DExonTbl X = p->no_spliced_alignment ? DExonTbl() : s->ix->dexons;   // (--avoid-pseudogene: the units that read it take it as an argument of its own)
-	if(!p->no_spliced_alignment) { A.P.sc.donor_sum = s->ix->d_spl[0]; A.P.sc.acc_sum1 = s->ix->d_spl[1]; A.P.sc.acc_sum2 = s->ix->d_spl[2]; }
-	A.names1 = s->d_names; A.noffs1 = s->d_name_offs; A.names2 = s->d_names2; A.noffs2 = s->d_name_offs2;
-	A.paired = paired ? 1u : 0u;
-	if(!fast && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (the machine streams' pools are about to be used on the first stream)
-	const unsigned M = s->mstreams, NB = M + 1;                    // machine passes in flight, and the depth of the per-run buffers
+	if(g->big_main && maxblocks > 32) maxblocks = 32;        // ~1.3 MB of workspace per read in flight
+	if(g->xl && maxblocks > 12) maxblocks = 12;              // XL: 18.7 MB per read in flight, 12 x 128 of them (h2g_go_xl.h)
+	g->grid = (unsigned)(want < 1 ? 1 : (want > maxblocks ? maxblocks : want));
+	g->M = s->mstreams;
 	// workgroups of one machine pass behind a fast pass: mach_total / M.  The default policy follows the batch: when the fast pass hands on more than 1.5 % of a linear index's
 	// batch (repeat-structured sequence: the machine's passes, not the fast pass, are the step) the passes get 192 workgroups in all instead of 128 — measured on the repeat-structured
 	// leg 44.7 -> 40.3 ms per step, while the fast-pass-bound legs (0.8 % handed on) lose 3 % with it (profiles/r05_NOTES.md §6).  The pools are sized for the larger share from the start.
-	const bool mt_auto = s->tune.mach_total_auto != 0 && linear;
-	const size_t units_ = paired ? s->n_reads : (s->n_reads + 1) / 2;
-	const unsigned mach_total_now = mt_auto && (size_t)s->last_bails * 1000 > units_ * 15 ? 192u : s->tune.mach_total;
-	unsigned mach_cap = mach_total_now / M;
-	if(mach_cap > H2G_MACH_MAXGRID) mach_cap = H2G_MACH_MAXGRID;
-	if(mach_cap < 1) mach_cap = 1;
-	unsigned pool_cap = (mt_auto ? 192u : s->tune.mach_total) / M;      // what the pools are sized for
-	if(pool_cap > H2G_MACH_MAXGRID) pool_cap = H2G_MACH_MAXGRID;
-	if(pool_cap < mach_cap) pool_cap = mach_cap;
-	const unsigned bgrid = fast ? 2u : 4u;                        // workgroups of a second pass (large workspace: ~5 MB per read in flight)
-	{	// behind a fast pass the machine works on stream gen % M with that stream's pools, on at most mach_cap workgroups
-		const size_t pgrid = fast && grid > pool_cap ? (size_t)pool_cap : (size_t)grid;
-		if(fast && s->n_reads >= 200000) {
-			// large batches (a streaming caller's): every machine stream's pools exist before the first pass that could need them — an allocation
-			// in the middle of a queue of runs (gigabytes, synchronous) would stall all of them.  The stream's SECOND run pays for it, once (round 6: a caller with one
-			// batch — a command line over a million pairs — never needs streams 1 .. M - 1: their 30 GB of pools were a second of its three).
-			// (Small batches keep allocating a machine stream's pools when it is first used.)
-			const GoUnit& Bp = go_unit(linear, true, spl);
-			uint32_t bgeo_[4];
-			Bp.geometry(bgeo_);
-			GoArgs scratch = A;
-			for(unsigned m_ = 0; m_ < M && s->gen >= 1; m_++) {
-				if((rc = go_pool_for(s, 2 * (int)m_, U, pgrid * geo[1], pgrid * block, p->bowtie2_dp, &scratch))) return rc;
-				if(!big_main && !s->tune.no_second_pass && (rc = go_pool_for(s, 2 * (int)m_ + 1, Bp, (size_t)bgrid * bgeo_[1], (size_t)bgrid * bgeo_[0], p->bowtie2_dp, &scratch))) return rc;
-				// ... and its overflow list, and the stream itself (a HIP stream gets its hardware queue when it is first used)
-				if(!s->d_ovf_list[m_]) { HIPCHK(hipMalloc((void**)&s->d_ovf_list[m_], (s->max_reads + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m_] + s->max_reads, 0, 16, s->mst[m_])); }
-			}
-			for(unsigned b_ = 0; b_ < M + 1; b_++) {      // the per-run buffers of every generation
-				if(!s->d_bail_list[b_]) HIPCHK(hipMalloc((void**)&s->d_bail_list[b_], (s->max_reads + 4) * 4));
-				if(!s->d_fast_args[b_]) HIPCHK(hipMalloc((void**)&s->d_fast_args[b_], sizeof(FastArgs)));
-				if(!s->d_fast_args[H2G_NBUF + b_]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b_], sizeof(FastArgs)));
-			}
+	const bool mt_auto = s->tune.mach_total_auto != 0 && g->linear;
+	g->units = paired ? n_reads : (n_reads + 1) / 2;
+	const unsigned mach_total_now = mt_auto && (size_t)s->last_bails * 1000 > g->units * 15 ? 192u : s->tune.mach_total;
+	g->mach_cap = mach_total_now / g->M;
+	if(g->mach_cap > H2G_MACH_MAXGRID) g->mach_cap = H2G_MACH_MAXGRID;
+	if(g->mach_cap < 1) g->mach_cap = 1;
+	g->pool_cap = (mt_auto ? 192u : s->tune.mach_total) / g->M;      // what the pools are sized for
+	if(g->pool_cap > H2G_MACH_MAXGRID) g->pool_cap = H2G_MACH_MAXGRID;
+	if(g->pool_cap < g->mach_cap) g->pool_cap = g->mach_cap;
+	g->bgrid = g->fast ? 2u : 4u;                                    // (large workspace: ~5 MB per read in flight)
+	return plan;
+}
+
+// the fast pass's share of a run (h2g_fast.h), decided by fast_policy
+struct FastPlan {
+	bool use_am, mate_ho;          // alignMate in the pass; pairs that need it parked for the drain launch (its alignMate build)
+	uint32_t fgeo[5], dgeo[5];     // geometry of the fast launch's build and of the drain launch's
+	unsigned fgrid, mgrid, dgrid;  // workgroups of the fast launch, of the machine pass behind it, of the drain launch
+	uint32_t orphan_T, psel;       // > 0: the end of the batch goes to a drain launch; the slot pool of the fast launch ...
+	size_t slot_bytes;             // ... and its size
+};
+// what a run queued now carries through to the end of go_run
+struct GoRun {
+	GoArgs A; DExonTbl X; XlPairs XP;   // the main pass's arguments (X: --avoid-pseudogene's exons, an argument of their own)
+	unsigned gsel, msel;           // the per-run buffer set (gen % (M + 1)) and the machine stream (gen % M)
+	unsigned long long* cblk;      // the run's counter block (h2g_go_args.h)
+	FastPlan f;
+	hipStream_t ms;                // the stream of the machine's passes ...
+	unsigned mach_grid, psel;      // ... the main pass's workgroups there, and its pools, overflow list and long-edit part
+	uint32_t* ovl;                 // the main pass's overflow list (+ its count behind it)
+};
+
+// the main pass's argument block, less its pools, result rows and counters
+static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired, const GoPlan& g, GoRun* r) {
+	const BatchCtx& b = s->cur();
+	GoArgs& A = r->A;
+	memset(&A, 0, sizeof A);
+	A.g = s->ix->dg; A.ref = s->ix->dr; A.ls = s->ix->dls; A.alts = s->ix->dalts;
+	if(p->max_alts_tried) A.alts.maxAltsTried = p->max_alts_tried;          // --max-altstried
+	if(p->use_haplotype && !g.linear && A.alts.n) A.alts.has_splice |= 2u;   // --haplotype: the table behind the ALTs is read (h2g_graph.h haps_of)
+	A.rd1 = dreads(s); A.rd2 = A.rd1;
+	if(paired) { A.rd2.codes = b.d_codes2; A.rd2.offs = b.d_offs2; A.rd2.quals = b.has_quals2 ? b.d_quals2 : nullptr; }
+	A.P = aln_params_from(*p, p->no_spliced_alignment != 0, g.linear);
+	if(!p->no_spliced_alignment) { A.ssdb = s->ix->dssdb; A.rdid_base = p->first_read_id; }
+	r->X = p->no_spliced_alignment ? DExonTbl() : s->ix->dexons;
+	if(!p->no_spliced_alignment) { A.P.sc.donor_sum = s->ix->d_spl[0]; A.P.sc.acc_sum1 = s->ix->d_spl[1]; A.P.sc.acc_sum2 = s->ix->d_spl[2]; }
+	A.names1 = b.d_names; A.noffs1 = b.d_name_offs; A.names2 = b.d_names2; A.noffs2 = b.d_name_offs2;
+	A.paired = paired ? 1u : 0u;
+}
+
+// the main pass's per-lane scratch: behind a fast pass the machine works on stream gen % M with that stream's pools, on at most mach_cap workgroups
+static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoArgs* A) {
+	const size_t pgrid = g.fast && g.grid > g.pool_cap ? (size_t)g.pool_cap : (size_t)g.grid;
+	int rc;
+	if(g.fast && s->cur().n_reads >= 200000) {
+		// large batches (a streaming caller's): every machine stream's pools exist before the first pass that could need them — an allocation
+		// in the middle of a queue of runs (gigabytes, synchronous) would stall all of them.  The stream's SECOND run pays for it, once (round 6: a caller with one
+		// batch — a command line over a million pairs — never needs streams 1 .. M - 1: their 30 GB of pools were a second of its three).
+		// (Small batches keep allocating a machine stream's pools when it is first used.)
+		GoArgs scratch = *A;
+		for(unsigned m = 0; m < g.M && s->gen >= 1; m++) {
+			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, &scratch))) return rc;
+			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &scratch))) return rc;
+			// ... and its overflow list, and the stream itself (a HIP stream gets its hardware queue when it is first used)
+			if(!s->d_ovf_list[m]) { HIPCHK(hipMalloc((void**)&s->d_ovf_list[m], (s->max_reads + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
 		}
-		if((rc = go_pool_for(s, fast ? 2 * (int)(s->gen % M) : 0, U, pgrid * geo[1], pgrid * block, p->bowtie2_dp, &A))) return rc;
+		for(unsigned b = 0; b < g.M + 1; b++) {      // the per-run buffers of every generation
+			if(!s->d_bail_list[b]) HIPCHK(hipMalloc((void**)&s->d_bail_list[b], (s->max_reads + 4) * 4));
+			if(!s->d_fast_args[b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[b], sizeof(FastArgs)));
+			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
+		}
 	}
+	return go_pool_for(s, g.fast ? 2 * (int)(s->gen % g.M) : 0, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, A);
+}
+
+// the batch's result rows (grown to this run's -k), the pairs' overflow area and the XL units' side area
+static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const GoPlan& g, GoRun* r) {
+	BatchCtx& b = s->cur();
+	GoArgs& A = r->A;
+	int rc;
 	memset(&A.O, 0, sizeof A.O);
 	if(!paired) {
-		if(!s->d_rout) HIPCHK(hipMalloc((void**)&s->d_rout, s->max_reads * sizeof(ReadOut)));
+		if(!b.d_rout) HIPCHK(hipMalloc((void**)&b.d_rout, s->max_reads * sizeof(ReadOut)));
 		const uint32_t slots = p->khits;
-		if(s->aln_alloc < s->max_reads * (size_t)slots) {
-			(void)hipFree(s->d_aln); s->d_aln = nullptr; s->aln_alloc = 0;
-			HIPCHK(hipMalloc((void**)&s->d_aln, s->max_reads * (size_t)slots * sizeof(h2g_alnres)));
-			s->aln_alloc = s->max_reads * (size_t)slots;
-		}
-		s->aln_slots = slots;
-		A.O.rout = s->d_rout; A.O.aln = s->d_aln; A.O.aln_slots = slots;
+		if((rc = grow((void**)&b.d_aln, &b.aln_alloc, s->max_reads * (size_t)slots, sizeof(h2g_alnres)))) return rc;
+		b.aln_slots = slots;
+		A.O.rout = b.d_rout; A.O.aln = b.d_aln; A.O.aln_slots = slots;
 	} else {
-		if(!s->d_pout) HIPCHK(hipMalloc((void**)&s->d_pout, s->max_reads * sizeof(PairOut)));
+		if(!b.d_pout) HIPCHK(hipMalloc((void**)&b.d_pout, s->max_reads * sizeof(PairOut)));
 		// a mate can report more alignments than -k before the pair is settled: 2 k + 4 slots, at least H2G_PAIR_RES_CAP
 		uint32_t pslots = p->khits * 2 + 4;
 		if(pslots < H2G_PAIR_RES_CAP) pslots = H2G_PAIR_RES_CAP;
 		if(s->tune.pair_slots > 0) pslots = (uint32_t)s->tune.pair_slots;   // test knob: tiny rows push pairs through the overflow area (dense fetch only)
-		if(s->paln_alloc < s->max_reads * (size_t)pslots) {
-			for(int m = 0; m < 2; m++) { (void)hipFree(s->d_paln[m]); s->d_paln[m] = nullptr; }
-			s->paln_alloc = 0;
-			for(int m = 0; m < 2; m++) HIPCHK(hipMalloc((void**)&s->d_paln[m], s->max_reads * (size_t)pslots * sizeof(h2g_alnres)));
-			s->paln_alloc = s->max_reads * (size_t)pslots;
-		}
-		s->pair_slots = pslots;
-		A.O.pout = s->d_pout; A.O.paln[0] = s->d_paln[0]; A.O.paln[1] = s->d_paln[1]; A.O.pair_slots = pslots;
+		if((rc = grow((void**)b.d_paln, &b.paln_alloc, s->max_reads * (size_t)pslots, sizeof(h2g_alnres), 2))) return rc;
+		b.pair_slots = pslots;
+		A.O.pout = b.d_pout; A.O.paln[0] = b.d_paln[0]; A.O.paln[1] = b.d_paln[1]; A.O.pair_slots = pslots;
 		// One part per machine stream: the machine passes of M queued runs may be in flight together and each takes its blocks
 		// from its own cursor.  Block offsets (PairOut::pad) are relative to the whole area, so whichever pass wrote a pair last, its block is found.
 		const size_t ovf_cap = s->max_reads / 4 > 65536 ? s->max_reads / 4 : 65536;   // records per part
-		if(s->paln_ovf_cap < ovf_cap || s->paln_ovf_parts < M) {
-			if(s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }
+		if(s->paln_ovf_cap < ovf_cap || s->paln_ovf_parts < g.M) {
+			HIPCHK(sync_mach(s));
 			HIPCHK(hipStreamSynchronize(s->st));
-			(void)hipFree(s->d_paln_ovf); s->d_paln_ovf = nullptr; s->paln_ovf_cap = 0; s->paln_ovf_parts = 0;
-			HIPCHK(hipMalloc((void**)&s->d_paln_ovf, M * ovf_cap * sizeof(h2g_alnres)));
-			s->paln_ovf_cap = ovf_cap; s->paln_ovf_parts = M;
+			size_t had = 0; s->paln_ovf_cap = 0; s->paln_ovf_parts = 0;
+			if((rc = grow((void**)&s->d_paln_ovf, &had, g.M * ovf_cap, sizeof(h2g_alnres)))) return rc;
+			s->paln_ovf_cap = ovf_cap; s->paln_ovf_parts = g.M;
 		}
 		A.O.ovf = s->d_paln_ovf;
 	}
-	XlPairs XP;
-	memset(&XP, 0, sizeof XP);
-	if(paired && xl) {
+	memset(&r->XP, 0, sizeof r->XP);
+	if(paired && g.xl) {
 		// the XL units' side area: a word per read, and per machine stream a part of lists with a cursor (an XL run is never behind a fast pass: it
 		// runs on the first stream and uses part 0, but the area is partitioned the way the overflow area is)
 		const size_t xcap = s->max_reads * 64 > ((size_t)1 << 20) ? s->max_reads * 64 : ((size_t)1 << 20);      // words per part
-		if(s->xlp_at_cap < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < M) {
+		if(s->xlp_at_cap < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < g.M) {
 			HIPCHK(hipStreamSynchronize(s->st));
-			(void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); s->d_xlp_at = nullptr; s->d_xlp = nullptr; s->xlp_at_cap = 0; s->xlp_cap = 0; s->xlp_parts = 0;
-			HIPCHK(hipMalloc((void**)&s->d_xlp_at, s->max_reads * 4));
-			HIPCHK(hipMalloc((void**)&s->d_xlp, M * xcap * 4));
+			size_t had = 0; s->xlp_at_cap = 0; s->xlp_cap = 0; s->xlp_parts = 0;
+			if((rc = grow((void**)&s->d_xlp_at, &s->xlp_at_cap, s->max_reads, 4)) || (rc = grow((void**)&s->d_xlp, &had, g.M * xcap, 4))) return rc;
 			if(!s->d_xlp_cur) HIPCHK(hipMalloc((void**)&s->d_xlp_cur, H2G_MSTREAMS_MAX * 4));
-			s->xlp_at_cap = s->max_reads; s->xlp_cap = xcap; s->xlp_parts = M;
+			s->xlp_cap = xcap; s->xlp_parts = g.M;
 		}
 		const unsigned part = 0;
-		HIPCHK(hipMemsetAsync(s->d_xlp_at, 0, s->n_reads * 4, s->st));
+		HIPCHK(hipMemsetAsync(s->d_xlp_at, 0, b.n_reads * 4, s->st));
 		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_xlp_cur + part), (int)(part * s->xlp_cap), 1, s->st));
-		XP.at = s->d_xlp_at; XP.list = s->d_xlp; XP.cursor = s->d_xlp_cur + part; XP.cap = (uint32_t)((part + 1) * s->xlp_cap);
+		r->XP.at = s->d_xlp_at; r->XP.list = s->d_xlp; r->XP.cursor = s->d_xlp_cur + part; r->XP.cap = (uint32_t)((part + 1) * s->xlp_cap);
 	}
-	if(paired) s->xlp_pout = xl ? s->d_pout : (s->xlp_pout == s->d_pout ? nullptr : s->xlp_pout);
-	(void)hipGetLastError();
-	// the fast pass's hand-on list, the counters and its argument block are buffered H2G_NBUF deep: the general machine's pass over
-	// run k's hand-ons goes to machine stream k & 1 and may still be under way while the fast passes of runs k + 1 and k + 2 run
-	const unsigned gsel = s->gen % NB, msel = s->gen % M;
-	unsigned long long* const cblk = s->d_counters + H2G_CNT_BLOCK * gsel;
-	HIPCHK(hipStreamWaitEvent(s->st, s->ev_mach[gsel], 0));          // run k - NB's machine pass: done with this set of buffers
-	HIPCHK(hipMemsetAsync(cblk, 0, H2G_CNT_BLOCK * sizeof(unsigned long long), s->st));
-	A.counters = cblk;
-	A.work = reinterpret_cast<uint32_t*>(cblk + 14);
-	if(paired) {   // the cursor starts at this machine stream's half of the area
-		const uint32_t half = fast ? msel : 0u;
-		A.O.ovf_cursor = reinterpret_cast<uint32_t*>(cblk + 124);
+	if(paired) s->xlp_pout = g.xl ? b.d_pout : (s->xlp_pout == b.d_pout ? nullptr : s->xlp_pout);
+	return H2G_OK;
+}
+
+// the run's counter block and cursors: the fast pass's hand-on list, the counters and its argument block are buffered H2G_NBUF deep — the general machine's
+// pass over run k's hand-ons goes to machine stream k % M and may still be under way while the fast passes of the following runs run
+static int go_counters(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
+	GoArgs& A = r->A;
+	r->gsel = s->gen % (g.M + 1); r->msel = s->gen % g.M;
+	r->cblk = s->d_counters + H2G_CNT_BLOCK * r->gsel;
+	HIPCHK(hipStreamWaitEvent(s->st, s->ev_mach[r->gsel], 0));          // run k - NB's machine pass: done with this set of buffers
+	HIPCHK(hipMemsetAsync(r->cblk, 0, H2G_CNT_BLOCK * sizeof(unsigned long long), s->st));
+	A.counters = r->cblk;
+	A.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_MAIN);
+	if(paired) {   // the cursor starts at this machine stream's part of the area
+		const uint32_t half = g.fast ? r->msel : 0u;
+		A.O.ovf_cursor = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_OVF_CURSOR);
 		A.O.ovf_cap = (uint32_t)((half + 1) * s->paln_ovf_cap);
 		if(half) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ovf_cursor, (int)(half * s->paln_ovf_cap), 1, s->st));
 	}
@@ -2272,266 +2257,311 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 		HIPCHK(hipMemsetAsync(s->dbg_buf, 0, (1u << 20) * 4, s->st));
 		A.dbg_buf = s->dbg_buf; A.dbg_read = (uint32_t)s->tune.dbg_read;
 	}
-	const int no_second = s->tune.no_second_pass;   // measurement / debugging knob
-	const bool second = !big_main && !no_second;
-	A.defer_overflow = second ? 1u : 0u;
-	HIPCHK(hipEventRecord(s->ev[5], s->st));
-	// ---- the fast pass (h2g_fast.h): the dominant traces with the per-read state on chip.  What it completes is final; the reads
-	// it hands on (a device-side list, no host sync) are the general machine's batch.  Built for unspliced alignment on a linear
-	// index with the default pair policy; every other option set goes to the machine whole.
-	s->ran_fast = fast;
-	unsigned fast_mgrid = 0, fast_orphan = 0, fast_dgrid = 0, fast_pool = 0; bool fast_mate_ho = false;
-	if(fast) {
-		uint32_t fgeo[5] = {0, 0, 0, 0, 0};
-		const bool use_am = linear && paired && s->tune.align_mate != 0;
-		if(!linear) h2g_go_fast_graph_geometry(fgeo); else if(use_am) h2g_go_fast_am_geometry(fgeo); else h2g_go_fast_geometry(fgeo);
-		// CUs: one persistent fast workgroup each (LDS-bound), minus the few the machine pass of the PREVIOUS run may still hold
-		// (the machine takes ~150 hand-ons per workgroup in half the time of a fast pass; the count is the last finished fast pass's)
-		for(unsigned back = 1; back < NB && back <= s->gen; back++) {                           // the latest fast pass that is over
-			const unsigned b = (s->gen - back) % NB;
-			if(hipEventQuery(s->ev_bails[b]) == hipSuccess) { s->last_bails = s->h_bails[b]; break; }
-		}
-		(void)hipGetLastError();
-		// hand-ons per machine workgroup (latency chains, two passes in flight).  Linear index: 400 — the fast pass is short and the machine's pass bounds the
-		// step.  Graph index: the fast pass bounds the step and every machine workgroup costs it two of its 256 (one per CU), while the machine's pass only
-		// has to end within two steps — so large batches give the machine less: 400 per workgroup up to 500 k batch units (pairs, or two unpaired reads), rising
-		// to 1600 at 1 M and beyond.  Measured steady steps, SNP graphs over 8-256 Mbp (profiles/r04_graph_scale.jsonl, r04_graph_scale2.jsonl):
-		//   500 k pairs: machine alone 55.3 ms | 400: 51.0 | 800: 55.2 | 1600: 70.6        1 M pairs (32 Mbp): alone 103.1 | 200: 110.0 | 400: 106.1 | 1600: 94.7 | 3200: 129.4
-		//   2 M pairs: alone 194.6 | 1600: 171.1 | 3200: 176.4                               1 M pairs, 128 / 256 Mbp: alone 110.6 / 119.6 | 400: 113.7 / 122.7 | 1600: 101.5 / 109.2
-		unsigned mach_div = s->tune.mach_div;
-		if(mach_div == 0) {
-			mach_div = 400;
-			if(!linear) {
-				const size_t units = paired ? (size_t)s->n_reads : (size_t)s->n_reads / 2;
-				if(units >= 1000000) mach_div = 1600;
-				else if(units > 500000) mach_div = 400 + (unsigned)((units - 500000) * 1200 / 500000);
-			}
-		}
-		const unsigned mach_min = s->tune.mach_min;
-		unsigned mgrid = (unsigned)((s->last_bails + mach_div - 1) / (mach_div ? mach_div : 1u));
-		if(mgrid < mach_min) mgrid = mach_min;
-		if(mgrid > mach_cap) mgrid = mach_cap;
-		// (Tried on repeat-rich sequence, 27 000 hand-ons: a share that follows the measured work of the two passes, m = 128 M / (F + M) — the machine's
-		// pass stayed a latency chain, 78 -> 66 ms on twice the workgroups, while the fast pass went 14.5 -> 49 ms on what was left; and the second pass
-		// on a stream of its own — the extra queues cost the common case 13 -> 20 ms per run.  Neither ships: profiles/r04_NOTES.md §6.)
-		size_t fwant = (s->n_reads + 127) / 128;                                                // small batches spread over the chip
-		unsigned reserve = s->tune.fast_reserve >= 0 ? (unsigned)s->tune.fast_reserve : M * mgrid;  // (M machine passes may be in flight)
-		if(reserve > 192) reserve = 192;
-		const unsigned fmax = 256 - reserve;
-		const unsigned fgrid = (unsigned)(fwant < 1 ? 1 : (fwant > fmax ? fmax : fwant));
-		const size_t slot_bytes = (size_t)256 * fgeo[2] * fgeo[3];
-		// the end of the batch goes to a drain launch (h2g_k_go_fast.hip) when the batch is large enough to have one
-		const size_t units_f = paired ? (size_t)s->n_reads : ((size_t)s->n_reads + 1) / 2;
-		uint32_t orphan_T = s->tune.orphan >= 0 ? (uint32_t)s->tune.orphan : (units_f >= H2G_ORPHAN_MIN_UNITS ? (uint32_t)H2G_ORPHAN_T : 0u);
-		if(orphan_T > fgeo[2]) orphan_T = fgeo[2];
-		if(!linear && fgeo[4] != 0) orphan_T = 0;                     // (a graph unit with GraphWS in global memory: its scratch is sized for one launch)
-		const unsigned dgrid = (unsigned)(s->tune.drain_grid < 1 ? 1 : s->tune.drain_grid);
-		// pairs that need alignMate (hi_aligner.h:5579): with a drain launch there, the fast launch parks them and the drain launch is the alignMate build of the pass (k_go_fast_am_drain)
-		// — the hot loop keeps the lighter build, the machine sees neither them nor the tail (h2g_stream_tune "mate_handover": -1 this policy, 0 off, 1 on)
-		const bool mate_ho = orphan_T != 0 && linear && paired && !use_am && s->tune.mate_handover != 0;
-		uint32_t dgeo[5] = {fgeo[0], fgeo[1], fgeo[2], fgeo[3], fgeo[4]};
-		if(mate_ho) h2g_go_fast_am_geometry(dgeo);
-		const unsigned psel_f = orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
-		{	// every buffer of the two launches exists (and has been written once: fresh device memory costs its first writer the mapping) before the first run that could need it
-			const size_t ocap = (size_t)256 * fgeo[2], dbytes = (size_t)dgrid * dgeo[2] * dgeo[3];
-			const size_t dsc = linear ? 0 : (size_t)dgrid * fgeo[0] * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
-			bool need = s->fast_slot_bytes[psel_f] < slot_bytes;
-			if(orphan_T) {
-				for(unsigned p_ = 0; p_ < H2G_FAST_POOLS; p_++) need = need || s->fast_slot_bytes[p_] < slot_bytes;
-				need = need || s->drain_slot_bytes < dbytes || s->drain_sc_bytes < dsc;
-				for(unsigned b_ = 0; b_ < NB; b_++) need = need || !s->d_orphans[b_] || !s->d_fast_args[H2G_NBUF + b_];
-				need = need || s->orphan_cap < ocap;
-			}
-			if(need) {
-				HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));
-				auto grow = [&](void** ptr, size_t* have, size_t want_) -> int {
-					if(*have >= want_) return H2G_OK;
-					(void)hipFree(*ptr); *ptr = nullptr; *have = 0;
-					if(want_) { HIPCHK(hipMalloc(ptr, want_)); HIPCHK(hipMemsetAsync(*ptr, 0, want_, s->st)); }
-					*have = want_;
-					return H2G_OK;
-				};
-				for(unsigned p_ = 0; p_ < (orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); p_++) if((rc = grow((void**)&s->d_fast_slots[orphan_T ? p_ : psel_f], &s->fast_slot_bytes[orphan_T ? p_ : psel_f], slot_bytes))) return rc;
-				if(orphan_T) {
-					if(s->orphan_cap < ocap) { for(int b_ = 0; b_ < H2G_NBUF; b_++) { (void)hipFree(s->d_orphans[b_]); s->d_orphans[b_] = nullptr; } s->orphan_cap = ocap; }
-					for(unsigned b_ = 0; b_ < NB; b_++) {
-						if(!s->d_orphans[b_]) { HIPCHK(hipMalloc((void**)&s->d_orphans[b_], (s->orphan_cap + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_orphans[b_], 0, (s->orphan_cap + 4) * 4, s->st)); }
-						if(!s->d_fast_args[H2G_NBUF + b_]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b_], sizeof(FastArgs)));
-					}
-					if((rc = grow((void**)&s->d_drain_slots, &s->drain_slot_bytes, dbytes))) return rc;
-					if((rc = grow((void**)&s->d_drain_sc, &s->drain_sc_bytes, dsc))) return rc;
-				}
-				HIPCHK(hipStreamSynchronize(s->st));
-			}
-		}
-		// run k - 3's drain launch is done with this pool — and a run WITHOUT a drain launch (a small resident batch queued behind a large one) uses pool 0, which the drain launch
-		// of an earlier run may still be reading: every fast launch waits for the last reader of its pool
-		HIPCHK(hipStreamWaitEvent(s->st, s->ev_pool[psel_f], 0));
-		if(!s->d_bail_list[gsel]) HIPCHK(hipMalloc((void**)&s->d_bail_list[gsel], (s->max_reads + 4) * 4));
-		uint32_t* const bl = s->d_bail_list[gsel];
-		HIPCHK(hipMemsetAsync(bl + s->max_reads, 0, 16, s->st));
-		FastArgs F;
-		memset(&F, 0, sizeof F);
-		F.g = A.g; F.ref = A.ref; F.ls = A.ls; F.rd1 = A.rd1; F.rd2 = A.rd2; F.P = A.P;
-		F.names1 = A.names1; F.noffs1 = A.noffs1; F.names2 = A.names2; F.noffs2 = A.noffs2;
-		F.slots = s->d_fast_slots[psel_f];
-		F.O.rout = A.O.rout; F.O.aln = A.O.aln; F.O.aln_slots = A.O.aln_slots; F.O.pout = A.O.pout; F.O.paln[0] = A.O.paln[0]; F.O.paln[1] = A.O.paln[1]; F.O.pair_slots = A.O.pair_slots;
-		F.counters = cblk; F.work = reinterpret_cast<uint32_t*>(cblk + 12);
-		F.bail_list = bl; F.bail_count = bl + s->max_reads;
-		F.total = (uint32_t)s->n_reads; F.paired = paired ? 1u : 0u;
-		F.alts = A.alts; F.gws_base = nullptr; F.gws_stride = 0; F.sc_base = nullptr;
-		F.dbg_read = A.dbg_read; F.dbg_buf = A.dbg_buf;
-		// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
-		F.tail = linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
-		if(!linear) {   // per-lane scratch of the graph primitives (every CU may hold a workgroup)
-			const size_t lanes = (size_t)256 * fgeo[0];
-			const size_t gws_bytes = lanes * fgeo[4], sc_bytes = lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
-			if(s->fast_gws_bytes < gws_bytes) {
-				(void)hipFree(s->d_fast_gws); s->d_fast_gws = nullptr; s->fast_gws_bytes = 0;
-				HIPCHK(hipMalloc((void**)&s->d_fast_gws, gws_bytes));
-				s->fast_gws_bytes = gws_bytes;
-			}
-			if(s->fast_sc_bytes < sc_bytes) {
-				(void)hipFree(s->d_fast_sc); s->d_fast_sc = nullptr; s->fast_sc_bytes = 0;
-				HIPCHK(hipMalloc((void**)&s->d_fast_sc, sc_bytes));
-				s->fast_sc_bytes = sc_bytes;
-			}
-			F.gws_base = s->d_fast_gws; F.gws_stride = fgeo[4]; F.sc_base = s->d_fast_sc;
-		}
-		if(!s->d_fast_args[gsel]) HIPCHK(hipMalloc((void**)&s->d_fast_args[gsel], sizeof(FastArgs)));
-		FastArgs D = F;
-		if(orphan_T) {
-			uint32_t* const ol = s->d_orphans[gsel];
-			HIPCHK(hipMemsetAsync(ol + s->orphan_cap, 0, 16, s->st));
-			F.orphan_T = orphan_T; F.orphan_list = ol; F.orphan_count = ol + s->orphan_cap; F.mate_handover = mate_ho ? 1u : 0u;
-			D.adopt_slot_words = fgeo[3] / 4;
-			// The drain launch's own tail (the last reads of each of its workgroups go to the machine).  With few hand-ons the machine's passes are short and the tail is a third of
-			// what they get: the drain launch finishes its reads itself (lease ZE, random genome: 11.48 -> 11.16 ms per step, hand-ons 2 830 -> 1 880); where the machine's passes are
-			// the step (more than 1.5 % handed on: the policy of mach_total) they absorb the tail for nothing and a drain launch that runs to its last read would be the longer one
-			// (repeat-structured: 37.8 -> 39.0 ms with it): the tail stays.  A caller's own setting (H2G_FAST_TAIL, "tail") is kept as it is.
-			if(s->tune.tail_auto) D.tail = linear && paired && (size_t)s->last_bails * 1000 > units_f * 15 ? (uint32_t)H2G_DEFAULT_TAIL : 0u;
-			D.slots = s->d_drain_slots;
-			D.adopt_list = ol; D.adopt_count = ol + s->orphan_cap; D.adopt_slots = F.slots;
-			D.work = reinterpret_cast<uint32_t*>(cblk + 13);
-			D.cnt_off = 120;                                             // its own rank / side / step / aligned counters: [240..243]
-			D.total = 0;
-			if(!linear) D.sc_base = s->d_drain_sc;
-			s->orph_cur = ol + s->orphan_cap;
-		}
-		// through pinned memory: a pageable source would make this call wait for everything queued on the stream (the previous run's fast
-		// pass), and the chip would idle while the host queues this run.  The staging block of this buffer set was last read by the upload
-		// of run k - H2G_NBUF, which is over once that run's fast pass is
-		if(s->gen >= NB && hipEventQuery(s->ev_fast[gsel]) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipEventSynchronize(s->ev_fast[gsel])); }
-		FastArgs* const hF = reinterpret_cast<FastArgs*>(s->h_fast_args) + gsel;
-		*hF = F;
-		HIPCHK(hipMemcpyAsync(s->d_fast_args[gsel], hF, sizeof F, hipMemcpyHostToDevice, s->st));
-		if(orphan_T) {
-			FastArgs* const hD = reinterpret_cast<FastArgs*>(s->h_fast_args) + H2G_NBUF + gsel;
-			*hD = D;
-			HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
-		}
-		if((!linear ? h2g_go_fast_graph_launch : use_am ? h2g_go_fast_am_launch : h2g_go_fast_launch)(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
-		A.list = bl; A.nlist = bl + s->max_reads;
-		fast_mgrid = mgrid;
-		fast_orphan = orphan_T; fast_dgrid = dgrid; fast_pool = psel_f; fast_mate_ho = mate_ho;
+	A.defer_overflow = g.second ? 1u : 0u;
+	return H2G_OK;
+}
+
+// ---- the fast pass (h2g_fast.h): the dominant traces with the per-read state on chip.  What it completes is final; the reads
+// it hands on (a device-side list, no host sync) are the general machine's batch.  Built for unspliced alignment on a linear
+// index with the default pair policy; every other option set goes to the machine whole.
+// Its policy: geometry, the CUs it takes, the machine pass's share, whether a drain launch finishes the batch
+static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f) {
+	const size_t n_reads = s->cur().n_reads;
+	const bool linear = g.linear;
+	*f = FastPlan();
+	f->use_am = linear && paired && s->tune.align_mate != 0;
+	if(!linear) h2g_go_fast_graph_geometry(f->fgeo); else if(f->use_am) h2g_go_fast_am_geometry(f->fgeo); else h2g_go_fast_geometry(f->fgeo);
+	// CUs: one persistent fast workgroup each (LDS-bound), minus the few the machine pass of the PREVIOUS run may still hold
+	// (the machine takes ~150 hand-ons per workgroup in half the time of a fast pass; the count is the last finished fast pass's)
+	const unsigned NB = g.M + 1;
+	for(unsigned back = 1; back < NB && back <= s->gen; back++) {                           // the latest fast pass that is over
+		const unsigned b = (s->gen - back) % NB;
+		if(hipEventQuery(s->ev_bails[b]) == hipSuccess) { s->last_bails = s->h_bails[b]; break; }
 	}
-	HIPCHK(hipEventRecord(s->ev[10], s->st));
-	// behind a fast pass the machine works on the second stream (a short list on few workgroups: the next run's fast pass does not wait for it)
-	hipStream_t ms = s->st;
-	unsigned mach_grid = grid;
-	s->ran_drain = false;
-	if(fast) {
-		HIPCHK(hipEventRecord(s->ev_fast[gsel], s->st));
-		ms = s->mst[msel]; s->st2_busy = true;
-		if(fast_mgrid < mach_grid) mach_grid = fast_mgrid;
-		if(fast_orphan) {
-			// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
-			const bool use_am = (linear && paired && s->tune.align_mate != 0) || fast_mate_ho;
-			HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
-			HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
-			if((!linear ? h2g_go_fast_graph_launch_drain : use_am ? h2g_go_fast_am_launch_drain : h2g_go_fast_launch_drain)(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), fast_dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
-			HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
-			HIPCHK(hipEventRecord(s->ev_pool[fast_pool], s->dst));
-			HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
-			HIPCHK(hipEventRecord(s->ev_drain[gsel], s->dst));
-			HIPCHK(hipEventRecord(s->ev_bails[gsel], s->dst));
-			HIPCHK(hipStreamWaitEvent(ms, s->ev_drain[gsel], 0));
-			s->ran_drain = true; s->dst_busy = true;
-		} else {
-			HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->st));
-			HIPCHK(hipEventRecord(s->ev_bails[gsel], s->st));
-			HIPCHK(hipStreamWaitEvent(ms, s->ev_fast[gsel], 0));
+	(void)hipGetLastError();
+	// hand-ons per machine workgroup (latency chains, two passes in flight).  Linear index: 400 — the fast pass is short and the machine's pass bounds the
+	// step.  Graph index: the fast pass bounds the step and every machine workgroup costs it two of its 256 (one per CU), while the machine's pass only
+	// has to end within two steps — so large batches give the machine less: 400 per workgroup up to 500 k batch units (pairs, or two unpaired reads), rising
+	// to 1600 at 1 M and beyond.  Measured steady steps, SNP graphs over 8-256 Mbp (profiles/r04_graph_scale.jsonl, r04_graph_scale2.jsonl):
+	//   500 k pairs: machine alone 55.3 ms | 400: 51.0 | 800: 55.2 | 1600: 70.6        1 M pairs (32 Mbp): alone 103.1 | 200: 110.0 | 400: 106.1 | 1600: 94.7 | 3200: 129.4
+	//   2 M pairs: alone 194.6 | 1600: 171.1 | 3200: 176.4                               1 M pairs, 128 / 256 Mbp: alone 110.6 / 119.6 | 400: 113.7 / 122.7 | 1600: 101.5 / 109.2
+	unsigned mach_div = s->tune.mach_div;
+	if(mach_div == 0) {
+		mach_div = 400;
+		if(!linear) {
+			const size_t units = paired ? n_reads : n_reads / 2;
+			if(units >= 1000000) mach_div = 1600;
+			else if(units > 500000) mach_div = 400 + (unsigned)((units - 500000) * 1200 / 500000);
 		}
 	}
-	const unsigned psel = fast ? msel : 0u;          // workspace pools and the overflow list of this machine stream
+	f->mgrid = (unsigned)((s->last_bails + mach_div - 1) / (mach_div ? mach_div : 1u));
+	if(f->mgrid < s->tune.mach_min) f->mgrid = s->tune.mach_min;
+	if(f->mgrid > g.mach_cap) f->mgrid = g.mach_cap;
+	// (Tried on repeat-rich sequence, 27 000 hand-ons: a share that follows the measured work of the two passes, m = 128 M / (F + M) — the machine's
+	// pass stayed a latency chain, 78 -> 66 ms on twice the workgroups, while the fast pass went 14.5 -> 49 ms on what was left; and the second pass
+	// on a stream of its own — the extra queues cost the common case 13 -> 20 ms per run.  Neither ships: profiles/r04_NOTES.md §6.)
+	const size_t fwant = (n_reads + 127) / 128;                                                // small batches spread over the chip
+	unsigned reserve = s->tune.fast_reserve >= 0 ? (unsigned)s->tune.fast_reserve : g.M * f->mgrid;  // (M machine passes may be in flight)
+	if(reserve > 192) reserve = 192;
+	const unsigned fmax = 256 - reserve;
+	f->fgrid = (unsigned)(fwant < 1 ? 1 : (fwant > fmax ? fmax : fwant));
+	f->slot_bytes = (size_t)256 * f->fgeo[2] * f->fgeo[3];
+	// the end of the batch goes to a drain launch (h2g_k_go_fast.hip) when the batch is large enough to have one
+	f->orphan_T = s->tune.orphan >= 0 ? (uint32_t)s->tune.orphan : (g.units >= H2G_ORPHAN_MIN_UNITS ? (uint32_t)H2G_ORPHAN_T : 0u);
+	if(f->orphan_T > f->fgeo[2]) f->orphan_T = f->fgeo[2];
+	if(!linear && f->fgeo[4] != 0) f->orphan_T = 0;                     // (a graph unit with GraphWS in global memory: its scratch is sized for one launch)
+	f->dgrid = (unsigned)(s->tune.drain_grid < 1 ? 1 : s->tune.drain_grid);
+	// pairs that need alignMate (hi_aligner.h:5579): with a drain launch there, the fast launch parks them and the drain launch is the alignMate build of the pass (k_go_fast_am_drain)
+	// — the hot loop keeps the lighter build, the machine sees neither them nor the tail (h2g_stream_tune "mate_handover": -1 this policy, 0 off, 1 on)
+	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && s->tune.mate_handover != 0;
+	for(int k = 0; k < 5; k++) f->dgeo[k] = f->fgeo[k];
+	if(f->mate_ho) h2g_go_fast_am_geometry(f->dgeo);
+	f->psel = f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
+}
+
+// every buffer of the two launches exists (and has been written once: fresh device memory costs its first writer the mapping) before the first run that could need it
+static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
+	const size_t ocap = (size_t)256 * f.fgeo[2], dbytes = (size_t)f.dgrid * f.dgeo[2] * f.dgeo[3];
+	const size_t dsc = g.linear ? 0 : (size_t)f.dgrid * f.fgeo[0] * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
+	bool need = s->fast_slot_bytes[f.psel] < f.slot_bytes;
+	if(f.orphan_T) {
+		for(unsigned q = 0; q < H2G_FAST_POOLS; q++) need = need || s->fast_slot_bytes[q] < f.slot_bytes;
+		need = need || s->drain_slot_bytes < dbytes || s->drain_sc_bytes < dsc;
+		for(unsigned b = 0; b < g.M + 1; b++) need = need || !s->d_orphans[b] || !s->d_fast_args[H2G_NBUF + b];
+		need = need || s->orphan_cap < ocap;
+	}
+	if(!need) return H2G_OK;
+	// (every stream, whatever st2_busy and dst_busy say: the pools about to be freed may be any launch's)
+	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
+	auto grow_zeroed = [s](void** ptr, size_t* have, size_t want) -> int {     // (fresh memory is written once, on the first stream)
+		if(*have >= want) return H2G_OK;
+		const int rc = grow(ptr, have, want);
+		if(rc == H2G_OK) HIPCHK(hipMemsetAsync(*ptr, 0, want, s->st));
+		return rc;
+	};
+	int rc;
+	for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) if((rc = grow_zeroed((void**)&s->d_fast_slots[f.orphan_T ? q : f.psel], &s->fast_slot_bytes[f.orphan_T ? q : f.psel], f.slot_bytes))) return rc;
+	if(f.orphan_T) {
+		if(s->orphan_cap < ocap) { for(int b = 0; b < H2G_NBUF; b++) { (void)hipFree(s->d_orphans[b]); s->d_orphans[b] = nullptr; } s->orphan_cap = ocap; }
+		for(unsigned b = 0; b < g.M + 1; b++) {
+			if(!s->d_orphans[b]) { HIPCHK(hipMalloc((void**)&s->d_orphans[b], (s->orphan_cap + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_orphans[b], 0, (s->orphan_cap + 4) * 4, s->st)); }
+			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
+		}
+		if((rc = grow_zeroed((void**)&s->d_drain_slots, &s->drain_slot_bytes, dbytes))) return rc;
+		if((rc = grow_zeroed((void**)&s->d_drain_sc, &s->drain_sc_bytes, dsc))) return rc;
+	}
+	HIPCHK(hipStreamSynchronize(s->st));
+	return H2G_OK;
+}
+
+// the fast launch (and the drain launch's argument block) on the first stream; the main pass then takes the hand-on list
+static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
+	const FastPlan& f = r->f;
+	const GoArgs& A = r->A;
+	const unsigned gsel = r->gsel;
+	int rc;
+	// run k - 3's drain launch is done with this pool — and a run WITHOUT a drain launch (a small resident batch queued behind a large one) uses pool 0, which the drain launch
+	// of an earlier run may still be reading: every fast launch waits for the last reader of its pool
+	HIPCHK(hipStreamWaitEvent(s->st, s->ev_pool[f.psel], 0));
+	if(!s->d_bail_list[gsel]) HIPCHK(hipMalloc((void**)&s->d_bail_list[gsel], (s->max_reads + 4) * 4));
+	uint32_t* const bl = s->d_bail_list[gsel];
+	HIPCHK(hipMemsetAsync(bl + s->max_reads, 0, 16, s->st));
+	FastArgs F;
+	memset(&F, 0, sizeof F);
+	F.g = A.g; F.ref = A.ref; F.ls = A.ls; F.rd1 = A.rd1; F.rd2 = A.rd2; F.P = A.P;
+	F.names1 = A.names1; F.noffs1 = A.noffs1; F.names2 = A.names2; F.noffs2 = A.noffs2;
+	F.slots = s->d_fast_slots[f.psel];
+	F.O.rout = A.O.rout; F.O.aln = A.O.aln; F.O.aln_slots = A.O.aln_slots; F.O.pout = A.O.pout; F.O.paln[0] = A.O.paln[0]; F.O.paln[1] = A.O.paln[1]; F.O.pair_slots = A.O.pair_slots;
+	F.counters = r->cblk; F.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_FAST);
+	F.bail_list = bl; F.bail_count = bl + s->max_reads;
+	F.total = (uint32_t)s->cur().n_reads; F.paired = paired ? 1u : 0u;
+	F.alts = A.alts; F.gws_base = nullptr; F.gws_stride = 0; F.sc_base = nullptr;
+	F.dbg_read = A.dbg_read; F.dbg_buf = A.dbg_buf;
+	// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
+	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
+	if(!g.linear) {   // per-lane scratch of the graph primitives (every CU may hold a workgroup)
+		const size_t lanes = (size_t)256 * f.fgeo[0];
+		if((rc = grow((void**)&s->d_fast_gws, &s->fast_gws_bytes, lanes * f.fgeo[4])) ||
+		   (rc = grow((void**)&s->d_fast_sc, &s->fast_sc_bytes, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))))) return rc;
+		F.gws_base = s->d_fast_gws; F.gws_stride = f.fgeo[4]; F.sc_base = s->d_fast_sc;
+	}
+	if(!s->d_fast_args[gsel]) HIPCHK(hipMalloc((void**)&s->d_fast_args[gsel], sizeof(FastArgs)));
+	FastArgs D = F;
+	if(f.orphan_T) {
+		uint32_t* const ol = s->d_orphans[gsel];
+		HIPCHK(hipMemsetAsync(ol + s->orphan_cap, 0, 16, s->st));
+		F.orphan_T = f.orphan_T; F.orphan_list = ol; F.orphan_count = ol + s->orphan_cap; F.mate_handover = f.mate_ho ? 1u : 0u;
+		D.adopt_slot_words = f.fgeo[3] / 4;
+		// The drain launch's own tail (the last reads of each of its workgroups go to the machine).  With few hand-ons the machine's passes are short and the tail is a third of
+		// what they get: the drain launch finishes its reads itself (lease ZE, random genome: 11.48 -> 11.16 ms per step, hand-ons 2 830 -> 1 880); where the machine's passes are
+		// the step (more than 1.5 % handed on: the policy of mach_total) they absorb the tail for nothing and a drain launch that runs to its last read would be the longer one
+		// (repeat-structured: 37.8 -> 39.0 ms with it): the tail stays.  A caller's own setting (H2G_FAST_TAIL, "tail") is kept as it is.
+		if(s->tune.tail_auto) D.tail = g.linear && paired && (size_t)s->last_bails * 1000 > g.units * 15 ? (uint32_t)H2G_DEFAULT_TAIL : 0u;
+		D.slots = s->d_drain_slots;
+		D.adopt_list = ol; D.adopt_count = ol + s->orphan_cap; D.adopt_slots = F.slots;
+		D.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_DRAIN);
+		D.cnt_off = H2G_CNT_DRAIN_OFF;                               // its own rank / side / step / aligned counters
+		D.total = 0;
+		if(!g.linear) D.sc_base = s->d_drain_sc;
+		s->orph_cur = ol + s->orphan_cap;
+	}
+	// through pinned memory: a pageable source would make this call wait for everything queued on the stream (the previous run's fast
+	// pass), and the chip would idle while the host queues this run.  The staging block of this buffer set was last read by the upload
+	// of run k - H2G_NBUF, which is over once that run's fast pass is
+	if(s->gen >= g.M + 1 && hipEventQuery(s->ev_fast[gsel]) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipEventSynchronize(s->ev_fast[gsel])); }
+	FastArgs* const hF = reinterpret_cast<FastArgs*>(s->h_fast_args) + gsel;
+	*hF = F;
+	HIPCHK(hipMemcpyAsync(s->d_fast_args[gsel], hF, sizeof F, hipMemcpyHostToDevice, s->st));
+	if(f.orphan_T) {
+		FastArgs* const hD = reinterpret_cast<FastArgs*>(s->h_fast_args) + H2G_NBUF + gsel;
+		*hD = D;
+		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
+	}
+	if((!g.linear ? h2g_go_fast_graph_launch : f.use_am ? h2g_go_fast_am_launch : h2g_go_fast_launch)(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
+	r->A.list = bl; r->A.nlist = bl + s->max_reads;
+	return H2G_OK;
+}
+
+// the stream hand-off behind a fast pass: the machine works on machine stream msel (a short list on few workgroups: the next run's fast pass does not wait for it),
+// after the drain launch when there is one
+static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
+	const FastPlan& f = r->f;
+	const unsigned gsel = r->gsel;
+	HIPCHK(hipEventRecord(s->ev_fast[gsel], s->st));
+	r->ms = s->mst[r->msel]; s->st2_busy = true;
+	if(f.mgrid < r->mach_grid) r->mach_grid = f.mgrid;
+	if(f.orphan_T) {
+		// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
+		const bool use_am = f.use_am || f.mate_ho;
+		HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
+		HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
+		if((!g.linear ? h2g_go_fast_graph_launch_drain : use_am ? h2g_go_fast_am_launch_drain : h2g_go_fast_launch_drain)(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
+		HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
+		HIPCHK(hipEventRecord(s->ev_pool[f.psel], s->dst));
+		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
+		HIPCHK(hipEventRecord(s->ev_drain[gsel], s->dst));
+		HIPCHK(hipEventRecord(s->ev_bails[gsel], s->dst));
+		HIPCHK(hipStreamWaitEvent(r->ms, s->ev_drain[gsel], 0));
+		s->ran_drain = true; s->dst_busy = true;
+	} else {
+		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->st));
+		HIPCHK(hipEventRecord(s->ev_bails[gsel], s->st));
+		HIPCHK(hipStreamWaitEvent(r->ms, s->ev_fast[gsel], 0));
+	}
+	return H2G_OK;
+}
+
+// the machine stream's overflow list and its part of the long-edit area
+static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
+	GoArgs& A = r->A;
+	const unsigned psel = r->psel;
 	s->ovf_cur = psel;
 	if(!s->d_ovf_list[psel]) HIPCHK(hipMalloc((void**)&s->d_ovf_list[psel], (s->max_reads + 4) * 4));
-	uint32_t* const ovl = s->d_ovf_list[psel];
-	HIPCHK(hipMemsetAsync(ovl + s->max_reads, 0, 16, ms));
-	{	// the long-edit area: part psel and its cursor belong to this machine stream (the pass that used them last is over: same stream)
-		const size_t lcap = s->max_reads > (1u << 20) ? s->max_reads : (size_t)(1u << 20);
-		if(s->ledits_cap < lcap || s->ledits_parts < M) {
-			if(s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); }
-			HIPCHK(hipStreamSynchronize(s->st));
-			(void)hipFree(s->d_ledits); s->d_ledits = nullptr; s->ledits_cap = 0; s->ledits_parts = 0;
-			HIPCHK(hipMalloc((void**)&s->d_ledits, M * lcap * sizeof(h2g_edit)));
-			if(!s->d_ledits_cur) HIPCHK(hipMalloc((void**)&s->d_ledits_cur, H2G_MSTREAMS_MAX * 4));
-			s->ledits_cap = lcap; s->ledits_parts = M;
-			for(unsigned m_ = 0; m_ < H2G_MSTREAMS_MAX; m_++) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_ledits_cur + m_), (int)(m_ < M ? m_ * lcap : 0), 1, s->st));
-			HIPCHK(hipStreamSynchronize(s->st));
-		}
-		A.O.ledits = s->d_ledits; A.O.ledits_cursor = s->d_ledits_cur + psel; A.O.ledits_cap = (uint32_t)((psel + 1) * s->ledits_cap);
-		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ledits_cursor, (int)(psel * s->ledits_cap), 1, ms));
-		s->ledits_touched |= 1u << psel;
+	r->ovl = s->d_ovf_list[psel];
+	HIPCHK(hipMemsetAsync(r->ovl + s->max_reads, 0, 16, r->ms));
+	// the long-edit area: part psel and its cursor belong to this machine stream (the pass that used them last is over: same stream)
+	const size_t lcap = s->max_reads > (1u << 20) ? s->max_reads : (size_t)(1u << 20);
+	if(s->ledits_cap < lcap || s->ledits_parts < g.M) {
+		// (the flag stays: this run's own fast pass, already queued, has set it)
+		if(s->st2_busy) for(int k = 0; k < H2G_MSTREAMS_MAX; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
+		HIPCHK(hipStreamSynchronize(s->st));
+		size_t had = 0; s->ledits_cap = 0; s->ledits_parts = 0;
+		int rc;
+		if((rc = grow((void**)&s->d_ledits, &had, g.M * lcap, sizeof(h2g_edit)))) return rc;
+		if(!s->d_ledits_cur) HIPCHK(hipMalloc((void**)&s->d_ledits_cur, H2G_MSTREAMS_MAX * 4));
+		s->ledits_cap = lcap; s->ledits_parts = g.M;
+		for(unsigned m = 0; m < H2G_MSTREAMS_MAX; m++) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_ledits_cur + m), (int)(m < g.M ? m * lcap : 0), 1, s->st));
+		HIPCHK(hipStreamSynchronize(s->st));
 	}
-	if(second) { A.O.defer_list = ovl; A.O.defer_count = ovl + s->max_reads; }     // overflowed reads: listed for the second pass, their rows untouched
-	if(fast && s->n_reads >= 200000 && s->gen >= 1 && !s->mstreams_warm) {
-		// A machine stream's FIRST kernels cost it ~64 ms on top of their own time (lease I of round 6, `profiles/r06_i_batches_first.jsonl`: runs 1-7 of a stream 94 ms, every
-		// later one 30; the kernels' own events read 10 + 20 ms throughout — the queue's scratch memory and code objects are set up when a queue first needs them).  A streaming
-		// caller's SECOND run therefore runs both machine kernels once on every other machine stream (the first run may be the only one), over an empty list: with the pools, lists and per-run buffers above this is
-		// everything a stream does for the first time (a bench that warms up for 5 steps then timed the first use of streams 5-7: 18.5 ms per step where the steady state is 12-13).
-		if(!s->d_warm_cnt) { HIPCHK(hipMalloc((void**)&s->d_warm_cnt, H2G_CNT_BLOCK * sizeof(unsigned long long))); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
-		const GoUnit& Bw = go_unit(linear, true, spl);
-		uint32_t wgeo[4];
-		Bw.geometry(wgeo);
-		for(unsigned m_ = 0; m_ < M; m_++) {
-			if(m_ == msel || !s->d_ovf_list[m_]) continue;
-			GoArgs W1 = A;
-			if((rc = go_pool_for(s, 2 * (int)m_, U, (size_t)geo[1], (size_t)block, p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
-			W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 14);
-			W1.list = s->d_ovf_list[m_]; W1.nlist = s->d_ovf_list[m_] + s->max_reads;                                       // a count of zero (memset on this stream above)
-			W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 124); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 126);
-			W1.defer_overflow = 0; W1.O.defer_list = nullptr; W1.O.defer_count = nullptr;
-			if(U.launch(&W1, &X, nullptr, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
-			if(second) {
-				GoArgs W2 = W1;
-				if((rc = go_pool_for(s, 2 * (int)m_ + 1, Bw, (size_t)wgeo[1], (size_t)wgeo[0], p->bowtie2_dp, &W2))) return rc;
-				W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + 15);
-				if(Bw.launch(&W2, &X, nullptr, 1, s->mst[m_]) != 0) return set_err("go() warm-up launch", hipGetLastError());
-			}
+	A.O.ledits = s->d_ledits; A.O.ledits_cursor = s->d_ledits_cur + psel; A.O.ledits_cap = (uint32_t)((psel + 1) * s->ledits_cap);
+	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ledits_cursor, (int)(psel * s->ledits_cap), 1, r->ms));
+	s->ledits_touched |= 1u << psel;
+	if(g.second) { A.O.defer_list = r->ovl; A.O.defer_count = r->ovl + s->max_reads; }     // overflowed reads: listed for the second pass, their rows untouched
+	return H2G_OK;
+}
+
+// A machine stream's FIRST kernels cost it ~64 ms on top of their own time (lease I of round 6, `profiles/r06_i_batches_first.jsonl`: runs 1-7 of a stream 94 ms, every
+// later one 30; the kernels' own events read 10 + 20 ms throughout — the queue's scratch memory and code objects are set up when a queue first needs them).  A streaming
+// caller's SECOND run therefore runs both machine kernels once on every other machine stream (the first run may be the only one), over an empty list: with the pools, lists and per-run buffers above this is
+// everything a stream does for the first time (a bench that warms up for 5 steps then timed the first use of streams 5-7: 18.5 ms per step where the steady state is 12-13).
+static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, const GoRun& r) {
+	int rc;
+	if(!s->d_warm_cnt) { HIPCHK(hipMalloc((void**)&s->d_warm_cnt, H2G_CNT_BLOCK * sizeof(unsigned long long))); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
+	for(unsigned m = 0; m < g.M; m++) {
+		if(m == r.msel || !s->d_ovf_list[m]) continue;
+		GoArgs W1 = r.A;
+		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.geo[1], (size_t)g.geo[0], p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
+		W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_MAIN);
+		W1.list = s->d_ovf_list[m]; W1.nlist = s->d_ovf_list[m] + s->max_reads;                                       // a count of zero (memset on this stream above)
+		W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_OVF_CURSOR); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_LEDITS_CURSOR);
+		W1.defer_overflow = 0; W1.O.defer_list = nullptr; W1.O.defer_count = nullptr;
+		if(g.U->launch(&W1, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+		if(g.second) {
+			GoArgs W2 = W1;
+			if((rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.lgeo[1], (size_t)g.lgeo[0], p->bowtie2_dp, &W2))) return rc;
+			W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_SECOND);
+			if(g.L->launch(&W2, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		}
-		s->st2_busy = true;
-		s->mstreams_warm = true;
 	}
-	HIPCHK(hipEventRecord(s->ev[7], ms));
-	if(U.launch(&A, &X, &XP, mach_grid, ms) != 0) return set_err("go() launch", hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[6], ms));
-	if(second) {
-		const GoUnit& B = go_unit(linear, true, spl);
-		uint32_t* cnt = ovl + s->max_reads;       // (filled by the main pass itself: MachOut::defer_list)
-		uint32_t bgeo[4];
-		B.geometry(bgeo);
-		GoArgs A2 = A;
-		if((rc = go_pool_for(s, 2 * psel + 1, B, (size_t)bgrid * bgeo[1], (size_t)bgrid * bgeo[0], p->bowtie2_dp, &A2))) return rc;
-		A2.counters = cblk + 256;           // (a region of its own: in H2G_GO_PROF builds a pass writes up to 96 words behind its counters)
-		A2.work = reinterpret_cast<uint32_t*>(cblk + 15);
-		A2.list = ovl; A2.nlist = cnt;
+	s->st2_busy = true;
+	s->mstreams_warm = true;
+	return H2G_OK;
+}
+
+// the main pass, then the second pass over the reads it flagged (large workspace), whose results replace theirs
+static int go_mach(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoRun* r) {
+	HIPCHK(hipEventRecord(s->ev[7], r->ms));
+	if(g.U->launch(&r->A, &r->X, &r->XP, r->mach_grid, r->ms) != 0) return set_err("go() launch", hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev[6], r->ms));
+	if(g.second) {
+		GoArgs A2 = r->A;
+		int rc;
+		if((rc = go_pool_for(s, 2 * r->psel + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &A2))) return rc;
+		A2.counters = r->cblk + H2G_CNT_SECOND;           // (a region of its own: in H2G_GO_PROF builds a pass writes up to 96 words behind its counters)
+		A2.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_SECOND);
+		A2.list = r->ovl; A2.nlist = r->ovl + s->max_reads;   // (the count is filled by the main pass itself: MachOut::defer_list)
 		A2.defer_overflow = 0; A2.O.defer_list = nullptr; A2.O.defer_count = nullptr;
-		if(B.launch(&A2, &X, nullptr, bgrid, ms) != 0) return set_err("go() second pass launch", hipGetLastError());
+		if(g.L->launch(&A2, &r->X, nullptr, g.bgrid, r->ms) != 0) return set_err("go() second pass launch", hipGetLastError());
 	}
-	HIPCHK(hipEventRecord(s->ev[8], ms));
-	if(fast) HIPCHK(hipEventRecord(s->ev_mach[gsel], ms));
-	s->cnt_cur = cblk; s->gen++;
+	HIPCHK(hipEventRecord(s->ev[8], r->ms));
+	if(g.fast) HIPCHK(hipEventRecord(s->ev_mach[r->gsel], r->ms));
+	return H2G_OK;
+}
+
+// HI_Aligner::go for every read (pair) of the resident batch.  Two passes, both asynchronous on the stream: the main pass
+// with the default workspace, then the reads it flagged (a list overflowed) once more through the large-workspace unit,
+// whose results replace theirs.  Reads still flagged after that keep `overflow` set (n_overflow counts them).
+static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) {
+	if(!s || !p) return H2G_ERR_ARG;
+	int rc;
+	if((rc = go_check(s, p, paired))) return rc;
+	const GoPlan g = go_plan(s, p, paired);
+	HIPCHK(hipSetDevice(s->ix->device));
+	// Runs queued back to back share the result arrays (rows per read, record stride): a machine pass still in flight may only meet a
+	// run over the same reads with the same options.  Anything else waits for the machine streams first.
+	if(s->st2_busy && (s->last_paired != (paired ? 1 : 0) || memcmp(&s->last_p, p, sizeof *p) != 0)) HIPCHK(sync_mach(s));
+	s->last_p = *p; s->last_paired = paired ? 1 : 0;
+	GoRun r = {};
+	go_args(s, p, paired, g, &r);
+	if(!g.fast) HIPCHK(sync_mach(s));   // (the machine streams' pools are about to be used on the first stream)
+	if((rc = go_pools(s, p, g, &r.A)) || (rc = go_rows(s, p, paired, g, &r))) return rc;
+	(void)hipGetLastError();
+	if((rc = go_counters(s, paired, g, &r))) return rc;
+	HIPCHK(hipEventRecord(s->ev[5], s->st));
+	s->ran_fast = g.fast;
+	if(g.fast) {
+		fast_policy(s, paired, g, &r.f);
+		if((rc = fast_buffers(s, g, r.f)) || (rc = fast_launch(s, paired, g, &r))) return rc;
+	}
+	HIPCHK(hipEventRecord(s->ev[10], s->st));
+	r.ms = s->st; r.mach_grid = g.grid;
+	s->ran_drain = false;
+	if(g.fast && (rc = fast_handoff(s, paired, g, &r))) return rc;
+	r.psel = g.fast ? r.msel : 0u;          // workspace pools and the overflow list of this machine stream
+	if((rc = go_mach_lists(s, g, &r))) return rc;
+	if(g.fast && s->cur().n_reads >= 200000 && s->gen >= 1 && !s->mstreams_warm && (rc = go_warmup(s, p, g, r))) return rc;
+	if((rc = go_mach(s, p, g, &r))) return rc;
+	s->cnt_cur = r.cblk; s->gen++;
 	HIPCHK(hipGetLastError());
 	s->ran_align = true;
 	return H2G_OK;
@@ -2541,13 +2571,13 @@ extern "C" h2g_status h2g_align_run(h2g_stream* s, const h2g_align_params* p) { 
 extern "C" h2g_status h2g_align_pairs_run(h2g_stream* s, const h2g_align_params* p) { return go_run(s, p, true); }
 
 extern "C" h2g_status h2g_align_fetch(h2g_stream* s, h2g_read_result* res, h2g_alnres* aln, size_t first, size_t n) {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
-	if(!s || !res || first + n > s->n_reads || !s->d_rout) return H2G_ERR_ARG;
+	if(s) HIPCHK(sync_mach(s));   // (results of the machine pass on the second stream)
+	if(!s || !res || first + n > s->cur().n_reads || !s->cur().d_rout) return H2G_ERR_ARG;
 	std::vector<ReadOut> tmp(n);
-	HIPCHK(hipMemcpyAsync(tmp.data(), s->d_rout + first, n * sizeof(ReadOut), hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipMemcpyAsync(tmp.data(), s->cur().d_rout + first, n * sizeof(ReadOut), hipMemcpyDeviceToHost, s->st));
 	if(aln && n) {   // device rows hold aln_slots (= -k of the run) records, the caller's rows H2G_ALN_CAP: copy what fits in both
-		const uint32_t w = s->aln_slots < H2G_ALN_CAP ? s->aln_slots : H2G_ALN_CAP;
-		HIPCHK(hipMemcpy2DAsync(aln, (size_t)H2G_ALN_CAP * sizeof(h2g_alnres), s->d_aln + first * s->aln_slots, (size_t)s->aln_slots * sizeof(h2g_alnres),
+		const uint32_t w = s->cur().aln_slots < H2G_ALN_CAP ? s->cur().aln_slots : H2G_ALN_CAP;
+		HIPCHK(hipMemcpy2DAsync(aln, (size_t)H2G_ALN_CAP * sizeof(h2g_alnres), s->cur().d_aln + first * s->cur().aln_slots, (size_t)s->cur().aln_slots * sizeof(h2g_alnres),
 		                        (size_t)w * sizeof(h2g_alnres), n, hipMemcpyDeviceToHost, s->st));
 	}
 	HIPCHK(sync_all(s));
@@ -2563,21 +2593,21 @@ extern "C" h2g_status h2g_align_fetch(h2g_stream* s, h2g_read_result* res, h2g_a
 // An XL run's pair whose concordant list PairOut cannot carry (more than H2G_PAIR_CAP pairs, or an index past 255) only reaches a caller through the
 // compact fetch (its trailer): the slot and dense fetches flag it with H2G_OVF_PAIR_LIST instead
 static h2g_status xlp_flag(h2g_stream* s, h2g_pair_result* res, size_t first, size_t n) {
-	if(!s->xlp_pout || s->xlp_pout != s->d_pout || n == 0) return H2G_OK;
+	if(!s->xlp_pout || s->xlp_pout != s->cur().d_pout || n == 0) return H2G_OK;
 	std::vector<uint32_t> at(n);
 	HIPCHK(hipMemcpy(at.data(), s->d_xlp_at + first, n * 4, hipMemcpyDeviceToHost));
 	for(size_t i = 0; i < n; i++) if(at[i]) res[i].overflow |= H2G_OVF_PAIR_LIST;
 	return H2G_OK;
 }
 static h2g_status pairs_fetch_rows(h2g_stream* s, h2g_pair_result* res, h2g_alnres* aln1, h2g_alnres* aln2, size_t first, size_t n, bool callers_view) {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
-	if(!s || !res || first + n > s->n_reads || !s->d_pout) return H2G_ERR_ARG;
-	if((aln1 || aln2) && s->pair_slots < H2G_PAIR_RES_CAP) return H2G_ERR_ARG;
-	HIPCHK(hipMemcpyAsync(res, s->d_pout + first, n * sizeof(PairOut), hipMemcpyDeviceToHost, s->st));
+	if(s) HIPCHK(sync_mach(s));   // (results of the machine pass on the second stream)
+	if(!s || !res || first + n > s->cur().n_reads || !s->cur().d_pout) return H2G_ERR_ARG;
+	if((aln1 || aln2) && s->cur().pair_slots < H2G_PAIR_RES_CAP) return H2G_ERR_ARG;
+	HIPCHK(hipMemcpyAsync(res, s->cur().d_pout + first, n * sizeof(PairOut), hipMemcpyDeviceToHost, s->st));
 	// device rows hold pair_slots records, the caller's rows H2G_PAIR_RES_CAP (the dense variant returns all of them)
 	for(int m = 0; m < 2 && n; m++) {
 		h2g_alnres* dst = m == 0 ? aln1 : aln2;
-		if(dst) HIPCHK(hipMemcpy2DAsync(dst, (size_t)H2G_PAIR_RES_CAP * sizeof(h2g_alnres), s->d_paln[m] + first * s->pair_slots, (size_t)s->pair_slots * sizeof(h2g_alnres),
+		if(dst) HIPCHK(hipMemcpy2DAsync(dst, (size_t)H2G_PAIR_RES_CAP * sizeof(h2g_alnres), s->cur().d_paln[m] + first * s->cur().pair_slots, (size_t)s->cur().pair_slots * sizeof(h2g_alnres),
 		                                (size_t)H2G_PAIR_RES_CAP * sizeof(h2g_alnres), n, hipMemcpyDeviceToHost, s->st));
 	}
 	HIPCHK(sync_all(s));
@@ -2634,34 +2664,34 @@ static int gather_dense(h2g_stream* s, const h2g_alnres* d_src, uint32_t slots, 
 }
 
 extern "C" h2g_status h2g_align_fetch_dense(h2g_stream* s, h2g_read_result* res, h2g_alnres* aln, size_t aln_cap, uint64_t* aln_offs, size_t first, size_t n) {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
-	if(!s || !res || !aln || !aln_offs || first + n > s->n_reads || !s->d_rout) return H2G_ERR_ARG;
+	if(s) HIPCHK(sync_mach(s));   // (results of the machine pass on the second stream)
+	if(!s || !res || !aln || !aln_offs || first + n > s->cur().n_reads || !s->cur().d_rout) return H2G_ERR_ARG;
 	const h2g_status rc = h2g_align_fetch(s, res, nullptr, first, n);
 	if(rc != H2G_OK) return rc;
 	static_assert(offsetof(ReadOut, nselect) == 4, "ReadOut layout");
-	if(dense_offsets(&res[0].nselect, sizeof(h2g_read_result) / 4, s->aln_slots, n, aln_offs) > aln_cap) return H2G_ERR_ARG;
-	return gather_dense(s, s->d_aln + first * s->aln_slots, s->aln_slots, reinterpret_cast<const uint32_t*>(s->d_rout + first) + 1, sizeof(ReadOut) / 4,
+	if(dense_offsets(&res[0].nselect, sizeof(h2g_read_result) / 4, s->cur().aln_slots, n, aln_offs) > aln_cap) return H2G_ERR_ARG;
+	return gather_dense(s, s->cur().d_aln + first * s->cur().aln_slots, s->cur().aln_slots, reinterpret_cast<const uint32_t*>(s->cur().d_rout + first) + 1, sizeof(ReadOut) / 4,
 	                    n, aln, aln_offs, 0);
 }
 
 extern "C" h2g_status h2g_align_pairs_fetch_dense(h2g_stream* s, h2g_pair_result* res, h2g_alnres* aln1, size_t cap1, uint64_t* offs1,
                                                   h2g_alnres* aln2, size_t cap2, uint64_t* offs2, size_t first, size_t n)
 {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
-	if(!s || !res || !aln1 || !aln2 || !offs1 || !offs2 || first + n > s->n_reads || !s->d_pout) return H2G_ERR_ARG;
+	if(s) HIPCHK(sync_mach(s));   // (results of the machine pass on the second stream)
+	if(!s || !res || !aln1 || !aln2 || !offs1 || !offs2 || first + n > s->cur().n_reads || !s->cur().d_pout) return H2G_ERR_ARG;
 	const h2g_status rc = pairs_fetch_rows(s, res, nullptr, nullptr, first, n, false);       // (the headers as the device holds them: `pad` says where a pair's records are)
 	if(rc != H2G_OK) return rc;
 	static_assert(offsetof(PairOut, nres) == 0, "PairOut layout");
 	// both totals are known before either capacity is judged, so a caller that has to grow its buffers learns both needs at once
 	static_assert(offsetof(h2g_pair_result, pad) == offsetof(PairOut, pad) && sizeof(h2g_pair_result) == sizeof(PairOut), "PairOut layout");
-	const uint64_t t1 = dense_offsets(&res[0].nres[0], sizeof(h2g_pair_result) / 4, s->pair_slots, n, offs1, &res[0].pad);
-	const uint64_t t2 = dense_offsets(&res[0].nres[1], sizeof(h2g_pair_result) / 4, s->pair_slots, n, offs2, &res[0].pad);
+	const uint64_t t1 = dense_offsets(&res[0].nres[0], sizeof(h2g_pair_result) / 4, s->cur().pair_slots, n, offs1, &res[0].pad);
+	const uint64_t t2 = dense_offsets(&res[0].nres[1], sizeof(h2g_pair_result) / 4, s->cur().pair_slots, n, offs2, &res[0].pad);
 	if(t1 > cap1 || t2 > cap2) return H2G_ERR_ARG;
 	int r;
-	if((r = gather_dense(s, s->d_paln[0] + first * s->pair_slots, s->pair_slots, reinterpret_cast<const uint32_t*>(s->d_pout + first), sizeof(PairOut) / 4,
-	                     n, aln1, offs1, 0, s->d_pout + first, 0))) return r;
-	r = gather_dense(s, s->d_paln[1] + first * s->pair_slots, s->pair_slots, reinterpret_cast<const uint32_t*>(s->d_pout + first) + 1, sizeof(PairOut) / 4,
-	                 n, aln2, offs2, 2, s->d_pout + first, 1);
+	if((r = gather_dense(s, s->cur().d_paln[0] + first * s->cur().pair_slots, s->cur().pair_slots, reinterpret_cast<const uint32_t*>(s->cur().d_pout + first), sizeof(PairOut) / 4,
+	                     n, aln1, offs1, 0, s->cur().d_pout + first, 0))) return r;
+	r = gather_dense(s, s->cur().d_paln[1] + first * s->cur().pair_slots, s->cur().pair_slots, reinterpret_cast<const uint32_t*>(s->cur().d_pout + first) + 1, sizeof(PairOut) / 4,
+	                 n, aln2, offs2, 2, s->cur().d_pout + first, 1);
 	// `pad` is where the device kept the pair's records (a block offset in the overflow area: allocation order, i.e. timing) — nothing a caller may see
 	for(size_t i = 0; i < n; i++) res[i].pad = 0;
 	if(r == H2G_OK) r = xlp_flag(s, res, first, n);
@@ -2792,31 +2822,31 @@ static int compact_offsets(h2g_stream* s, const h2g_alnres* d_src, uint32_t slot
 extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_result* res, uint8_t* rec1, size_t cap1, uint64_t* boffs1, uint8_t* rec2, size_t cap2, uint64_t* boffs2,
                                                     size_t first, size_t n)
 {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }
-	if(!s || !res || !rec1 || !rec2 || !boffs1 || !boffs2 || first + n > s->n_reads || !s->d_pout) return H2G_ERR_ARG;
+	if(s) HIPCHK(sync_mach(s));
+	if(!s || !res || !rec1 || !rec2 || !boffs1 || !boffs2 || first + n > s->cur().n_reads || !s->cur().d_pout) return H2G_ERR_ARG;
 	if(n == 0) { boffs1[0] = boffs2[0] = 0; return H2G_OK; }
 	HIPCHK(hipSetDevice(s->ix->device));
 	static_assert(offsetof(PairOut, nres) == 0 && sizeof(h2g_pair_result) == sizeof(PairOut), "PairOut layout");
-	const uint32_t* cnt = reinterpret_cast<const uint32_t*>(s->d_pout + first);
+	const uint32_t* cnt = reinterpret_cast<const uint32_t*>(s->cur().d_pout + first);
 	// the XL run's lists that PairOut cannot carry: a trailer behind mate 1's records (nullptr for every other run: the kernels take their former path)
-	const uint32_t* xat = s->xlp_pout && s->xlp_pout == s->d_pout ? s->d_xlp_at + first : nullptr;
+	const uint32_t* xat = s->xlp_pout && s->xlp_pout == s->cur().d_pout ? s->d_xlp_at + first : nullptr;
 	void *d_o1 = nullptr, *d_o2 = nullptr, *d_b1 = nullptr, *d_b2 = nullptr;
 	int rc;
-	if((rc = compact_offsets(s, s->d_paln[0] + first * s->pair_slots, s->pair_slots, cnt, sizeof(PairOut) / 4, n, 0, s->d_pout + first, 0, &d_o1, xat)) ||
-	   (rc = compact_offsets(s, s->d_paln[1] + first * s->pair_slots, s->pair_slots, cnt + 1, sizeof(PairOut) / 4, n, 2, s->d_pout + first, 1, &d_o2))) return (h2g_status)rc;
+	if((rc = compact_offsets(s, s->cur().d_paln[0] + first * s->cur().pair_slots, s->cur().pair_slots, cnt, sizeof(PairOut) / 4, n, 0, s->cur().d_pout + first, 0, &d_o1, xat)) ||
+	   (rc = compact_offsets(s, s->cur().d_paln[1] + first * s->cur().pair_slots, s->cur().pair_slots, cnt + 1, sizeof(PairOut) / 4, n, 2, s->cur().d_pout + first, 1, &d_o2))) return (h2g_status)rc;
 	HIPCHK(hipMemcpyAsync(boffs1, d_o1, (n + 1) * 8, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipMemcpyAsync(boffs2, d_o2, (n + 1) * 8, hipMemcpyDeviceToHost, s->st));
-	HIPCHK(hipMemcpyAsync(res, s->d_pout + first, n * sizeof(PairOut), hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipMemcpyAsync(res, s->cur().d_pout + first, n * sizeof(PairOut), hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipStreamSynchronize(s->st));
 	for(size_t i = 0; i < n; i++) if(res[i].pad) { res[i].overflow &= ~4u; res[i].pad = 0; }      // (every record is returned; the block offset is the device's business)
 	if(boffs1[n] > cap1 || boffs2[n] > cap2) return H2G_ERR_ARG;              // (boffs[n] = the bytes needed)
 	if((rc = tmp_buf(s, 1, boffs1[n] + 8, &d_b1)) || (rc = tmp_buf(s, 3, boffs2[n] + 8, &d_b2))) return (h2g_status)rc;
 	const unsigned g = (unsigned)((n + 255) / 256);
-	if(boffs1[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->d_paln[0] + first * s->pair_slots, s->pair_slots, cnt, (uint32_t)(sizeof(PairOut) / 4),
-	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 0,
+	if(boffs1[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->cur().d_paln[0] + first * s->cur().pair_slots, s->cur().pair_slots, cnt, (uint32_t)(sizeof(PairOut) / 4),
+	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->cur().d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 0,
 	                                 xat, xat ? (const uint32_t*)s->d_xlp : (const uint32_t*)nullptr);
-	if(boffs2[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->d_paln[1] + first * s->pair_slots, s->pair_slots, cnt + 1, (uint32_t)(sizeof(PairOut) / 4),
-	                                 (const unsigned long long*)d_o2, n, (uint8_t*)d_b2, s->d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 1);
+	if(boffs2[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->cur().d_paln[1] + first * s->cur().pair_slots, s->cur().pair_slots, cnt + 1, (uint32_t)(sizeof(PairOut) / 4),
+	                                 (const unsigned long long*)d_o2, n, (uint8_t*)d_b2, s->cur().d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 1);
 	HIPCHK(hipGetLastError());
 	if(boffs1[n]) HIPCHK(hipMemcpyAsync(rec1, d_b1, boffs1[n], hipMemcpyDeviceToHost, s->st));
 	if(boffs2[n]) HIPCHK(hipMemcpyAsync(rec2, d_b2, boffs2[n], hipMemcpyDeviceToHost, s->st));
@@ -2825,22 +2855,22 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 }
 
 extern "C" h2g_status h2g_align_fetch_compact(h2g_stream* s, h2g_read_result* res, uint8_t* rec, size_t cap, uint64_t* boffs, size_t first, size_t n) {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }
-	if(!s || !res || !rec || !boffs || first + n > s->n_reads || !s->d_rout) return H2G_ERR_ARG;
+	if(s) HIPCHK(sync_mach(s));
+	if(!s || !res || !rec || !boffs || first + n > s->cur().n_reads || !s->cur().d_rout) return H2G_ERR_ARG;
 	if(n == 0) { boffs[0] = 0; return H2G_OK; }
 	HIPCHK(hipSetDevice(s->ix->device));
 	static_assert(offsetof(ReadOut, nselect) == 4, "ReadOut layout");
-	const uint32_t* cnt = reinterpret_cast<const uint32_t*>(s->d_rout + first) + 1;
+	const uint32_t* cnt = reinterpret_cast<const uint32_t*>(s->cur().d_rout + first) + 1;
 	void *d_o = nullptr, *d_b = nullptr;
 	int rc;
-	if((rc = compact_offsets(s, s->d_aln + first * s->aln_slots, s->aln_slots, cnt, sizeof(ReadOut) / 4, n, 0, nullptr, 0, &d_o))) return (h2g_status)rc;
+	if((rc = compact_offsets(s, s->cur().d_aln + first * s->cur().aln_slots, s->cur().aln_slots, cnt, sizeof(ReadOut) / 4, n, 0, nullptr, 0, &d_o))) return (h2g_status)rc;
 	HIPCHK(hipMemcpyAsync(boffs, d_o, (n + 1) * 8, hipMemcpyDeviceToHost, s->st));
 	const h2g_status hr = h2g_align_fetch(s, res, nullptr, first, n);           // (the headers; syncs the stream)
 	if(hr != H2G_OK) return hr;
 	if(boffs[n] > cap) return H2G_ERR_ARG;
 	if(boffs[n] == 0) return H2G_OK;
 	if((rc = tmp_buf(s, 1, boffs[n] + 8, &d_b))) return (h2g_status)rc;
-	hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, s->d_aln + first * s->aln_slots, s->aln_slots, cnt, (uint32_t)(sizeof(ReadOut) / 4),
+	hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, s->cur().d_aln + first * s->cur().aln_slots, s->cur().aln_slots, cnt, (uint32_t)(sizeof(ReadOut) / 4),
 	                   (const unsigned long long*)d_o, n, (uint8_t*)d_b, (const PairOut*)nullptr, (const h2g_alnres*)nullptr, 0);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(rec, d_b, boffs[n], hipMemcpyDeviceToHost, s->st));
@@ -2859,7 +2889,7 @@ extern "C" h2g_status h2g_align_fetch_long_edits(h2g_stream* s, h2g_edit* out, s
 	*n = 0;
 	if(!s->ran_align || !s->d_ledits || !s->d_ledits_cur) return H2G_OK;
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }
+	HIPCHK(sync_mach(s));
 	HIPCHK(hipStreamSynchronize(s->st));
 	uint32_t cur[H2G_MSTREAMS_MAX];
 	HIPCHK(hipMemcpy(cur, s->d_ledits_cur, sizeof cur, hipMemcpyDeviceToHost));
@@ -2889,7 +2919,7 @@ extern "C" h2g_status h2g_align_fetch_long_edits(h2g_stream* s, h2g_edit* out, s
 extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream* s, const char* key, long v) {
 	if(!s || !key) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
-	for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));
+	for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));   // (whatever st2_busy says: a change never meets a queued run)
 	const std::string k(key);
 	if(k == "fast") s->tune.fast = (int)v; else if(k == "blocks_per_cu") s->tune.blocks_per_cu = (int)v; else if(k == "pair_slots") s->tune.pair_slots = (int)v;
 	else if(k == "no_second_pass") s->tune.no_second_pass = (int)v; else if(k == "mach_div") s->tune.mach_div = (unsigned)v; else if(k == "mach_min") s->tune.mach_min = (unsigned)v;
@@ -2905,7 +2935,7 @@ extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream
 
 // development hook (h2g_stream_tune "dbg_read" / env H2G_GO_DBG_READ=<read id>): the primitive requests of that read in the last go() launch, 8 words each
 extern "C" __attribute__((visibility("default"))) int h2g_go_debug_trace(h2g_stream* s, uint32_t* out, uint32_t cap_words) {
-	if(s && s->st2_busy) { for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_])); s->st2_busy = false; }   // (results of the machine pass on the second stream)
+	if(s) HIPCHK(sync_mach(s));   // (results of the machine pass on the second stream)
 	if(!s || !out || !s->dbg_buf) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
 	HIPCHK(hipMemcpy(out, s->dbg_buf, (size_t)cap_words * 4, hipMemcpyDeviceToHost));
@@ -2916,7 +2946,7 @@ extern "C" __attribute__((visibility("default"))) int h2g_go_debug_trace(h2g_str
 extern "C" __attribute__((visibility("default"))) int h2g_go_prof(h2g_stream* s, unsigned long long* out48) {
 	if(!s || !out48) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
-	HIPCHK(hipMemcpy(out48, s->cnt_cur + 16, 80 * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // [0..47] split, [64..79] control by source ring
+	HIPCHK(hipMemcpy(out48, s->cnt_cur + H2G_CNT_PROF_GO, 80 * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // [0..47] split, [64..79] control by source ring (H2G_CNT_PROF_GO_CTL)
 	return H2G_OK;
 }
 
@@ -2924,16 +2954,16 @@ extern "C" __attribute__((visibility("default"))) int h2g_go_prof(h2g_stream* s,
 extern "C" __attribute__((visibility("default"))) int h2g_go_fast_prof(h2g_stream* s, unsigned long long* out72 /* [136] */) {
 	if(!s || !out72) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
-	HIPCHK(hipMemcpy(out72, s->cnt_cur + 128, 48 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(out72 + 48, s->cnt_cur + 96, 24 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(out72 + 72, s->cnt_cur + 176, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // control time / trips by site
+	HIPCHK(hipMemcpy(out72, s->cnt_cur + H2G_CNT_PROF_FAST, 48 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out72 + 48, s->cnt_cur + H2G_CNT_FAST_BAIL_WHY, 24 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out72 + 72, s->cnt_cur + H2G_CNT_PROF_FAST_SITE, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // control time / trips by site
 	return H2G_OK;
 }
 #ifdef H2G_GO_PROF
 extern "C" __attribute__((visibility("default"))) int h2g_go_fast_prof_bins(h2g_stream* s, unsigned long long* out256) {
 	if(!s || !out256) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
-	HIPCHK(hipMemcpy(out256, s->cnt_cur + 512, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out256, s->cnt_cur + H2G_CNT_PROF_FAST_BINS, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	return H2G_OK;
 }
 #endif
@@ -2944,15 +2974,15 @@ extern "C" h2g_status h2g_get_counters(h2g_stream* s, h2g_counters* c) {
 	unsigned long long v[16];
 	unsigned long long* const cb = s->ran_align ? s->cnt_cur : s->d_counters;
 	HIPCHK(hipMemcpy(v, cb, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(v + 8, cb + (s->ran_align ? 256 : 64), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	// [0..7] the main pass, [8..15] <- slots 256..263: the second pass over its overflowed reads (go_run)
+	HIPCHK(hipMemcpy(v + 8, cb + (s->ran_align ? H2G_CNT_SECOND : H2G_CNT_NO_SECOND), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	// [0..7] the main pass, [8..15] <- H2G_CNT_SECOND: the second pass over its overflowed reads (go_run)
 	s->last.n_rank = v[0] + v[8]; s->last.n_side = v[1] + v[9]; s->last.n_sa_steps = v[2] + v[10]; s->last.n_ext = v[3];
 	s->last.n_aligned = v[4] + v[12];
 	uint32_t nsecond = 0;
 	if(s->d_ovf_list[s->ovf_cur] && s->ran_align) HIPCHK(hipMemcpy(&nsecond, s->d_ovf_list[s->ovf_cur] + s->max_reads, 4, hipMemcpyDeviceToHost));
 	s->last.n_second_pass = nsecond;
 	s->last.n_overflow = nsecond ? v[13] : v[5];   // reads still flagged after the last pass that saw them
-	s->last.n_queries = s->n_reads * 2;
+	s->last.n_queries = s->cur().n_reads * 2;
 	float t = 0;
 	if(s->ran_seed) {
 		if(hipEventElapsedTime(&t, s->ev[2], s->ev[3]) == hipSuccess) s->last.ms_search = t;
@@ -2964,8 +2994,8 @@ extern "C" h2g_status h2g_get_counters(h2g_stream* s, h2g_counters* c) {
 	s->last.ms_drain_kernel = 0; s->last.pad2_ = 0; s->last.n_drain_side = 0; s->last.n_drain_sa_steps = 0; s->last.n_adopted = 0;
 	if(s->ran_align && s->ran_fast) {
 		unsigned long long f[2], fc[4];
-		HIPCHK(hipMemcpy(f, s->cnt_cur + 6, sizeof f, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(fc, s->cnt_cur + 120, sizeof fc, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(f, s->cnt_cur + H2G_CNT_FAST_DONE, sizeof f, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(fc, s->cnt_cur + H2G_CNT_FAST_RANK, sizeof fc, hipMemcpyDeviceToHost));
 		s->last_bails = (uint32_t)f[1];
 		s->last.n_fast = f[0]; s->last.n_fast_bail = f[1];
 		s->last.n_fast_side = fc[1]; s->last.n_fast_sa_steps = fc[2];
@@ -2973,7 +3003,7 @@ extern "C" h2g_status h2g_get_counters(h2g_stream* s, h2g_counters* c) {
 		if(hipEventElapsedTime(&t, s->ev[5], s->ev[10]) == hipSuccess) s->last.ms_fast_kernel = t;
 		if(s->ran_drain) {
 			unsigned long long dc[4]; uint32_t nad = 0;
-			HIPCHK(hipMemcpy(dc, s->cnt_cur + 240, sizeof dc, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(dc, s->cnt_cur + H2G_CNT_FAST_RANK + H2G_CNT_DRAIN_OFF, sizeof dc, hipMemcpyDeviceToHost));
 			HIPCHK(hipMemcpy(&nad, s->orph_cur, 4, hipMemcpyDeviceToHost));
 			s->last.n_drain_side = dc[1]; s->last.n_drain_sa_steps = dc[2]; s->last.n_adopted = nad;
 			s->last.n_rank += dc[0]; s->last.n_side += dc[1]; s->last.n_sa_steps += dc[2]; s->last.n_aligned += dc[3];
