@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -180,6 +181,31 @@ class ReadResult(C.Structure):
                 ("best", C.c_int32), ("secbest", C.c_int32), ("best_h2", u32), ("secbest_h2", u32)]
 
 
+FUNC_TYPES = {"C": 1, "Constant": 1, "L": 2, "Linear": 2, "S": 3, "Sqrt": 3, "G": 4, "Log": 4}   # parseFuncType aligner_seed_policy.cpp:30-44
+
+
+def parse_n_ceil(arg, cur=(2, 0.0, float(np.float32(0.15)))):
+    """--n-ceil <arg> applied to the ceiling `cur` = (type, constant, coefficient), as the reference does: 1-3 comma-separated tokens
+    (empty ones dropped), one token x meaning C,x (hisat2.cpp:1525-1549), then PARSE_FUNC (aligner_seed_policy.cpp:47-70): a type, and
+    the constant and coefficient when given (fields not given keep their value).  ValueError carries the reference's message."""
+    toks = [t for t in arg.split(",") if t]
+    if len(toks) > 3:
+        raise ValueError(f"Error: expected 3 or fewer comma-separated arguments to --n-ceil option, got {len(toks)}")
+    if not toks:
+        raise ValueError("Error: expected at least one argument to --n-ceil option")
+    if len(toks) == 1:
+        toks = ["C"] + toks
+    if toks[0] not in FUNC_TYPES:
+        raise ValueError(f"Error: Bad function type '{toks[0]}'.  Should be C (constant), L (linear), S (square root) or G (natural log).")
+    t, c, l = FUNC_TYPES[toks[0]], cur[1], cur[2]
+    num = lambda x: float(re.match(r"\s*([+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?)?", x).group(1) or 0.0)   # istringstream >> double
+    if len(toks) > 1:
+        c = num(toks[1])
+    if len(toks) > 2:
+        l = num(toks[2])
+    return t, c, l
+
+
 class AlignParams(C.Structure):
     _fields_ = [("khits", u32), ("kseeds", u32), ("no_spliced_alignment", u32), ("secondary", u32), ("bowtie2_dp", u32),
                 ("mm_max", C.c_int32), ("mm_min", C.c_int32), ("n_pen", C.c_int32), ("rdg_const", C.c_int32), ("rdg_linear", C.c_int32),
@@ -190,7 +216,8 @@ class AlignParams(C.Structure):
                 ("pen_canintronlen_const", C.c_double), ("pen_canintronlen_coeff", C.c_double),
                 ("pen_noncanintronlen_const", C.c_double), ("pen_noncanintronlen_coeff", C.c_double),
                 ("min_anchor_len", u32), ("min_anchor_len_noncan", u32), ("xs_only", u32), ("use_haplotype", u32), ("max_alts_tried", u32), ("max_frag_len", u32), ("min_frag_len", u32), ("pe_orientation", u32), ("nofw", u32), ("norc", u32),
-                ("avoid_pseudogene", u32), ("transcriptome_mapping_only", u32), ("no_anchorstop", u32), ("pen_conflictsplice", C.c_int32)]
+                ("avoid_pseudogene", u32), ("transcriptome_mapping_only", u32), ("no_anchorstop", u32), ("pen_conflictsplice", C.c_int32),
+                ("seed", u32), ("n_ceil_type", u32), ("n_ceil_const", C.c_double), ("n_ceil_coeff", C.c_double)]
 
     def apply_options(self, opts, linear=None):
         """apply a list of reference command-line options (['-k', '3', '--mp', '4,2', ...]) to this block; returns leftovers.
@@ -299,6 +326,13 @@ class AlignParams(C.Structure):
                 if len(a) > 2:
                     setattr(self, w + "_coeff", float(a[2]))
                 i += 2
+            elif o == "--seed":
+                if int(v) < 0:
+                    raise ValueError("--seed arg must be at least 0")
+                self.seed = int(v); i += 2
+            elif o == "--n-ceil":
+                self.n_ceil_type, self.n_ceil_const, self.n_ceil_coeff = parse_n_ceil(v, (self.n_ceil_type, self.n_ceil_const, self.n_ceil_coeff))
+                i += 2
             elif o == "--score-min":
                 a = v.split(",")
                 self.score_min_type = {"C": 1, "L": 2, "S": 3, "G": 4}[a[0]]
@@ -367,7 +401,7 @@ EXPORTS = [
     "h2g_rank_bench", "h2g_rank_bench_synth", "h2g_rank_bench_synth_sample", "h2g_fm_search", "h2g_sa_resolve", "h2g_extend",
     "h2g_seed_params_init", "h2g_seed_extend_run", "h2g_seed_extend_fetch", "h2g_get_counters",
     "h2g_device_count", "h2g_ext_search", "h2g_local_index_of", "h2g_align_params_init", "h2g_align_params_presets", "h2g_set_read_names", "h2g_align_run", "h2g_align_fetch",
-    "h2g_set_mates", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
+    "h2g_set_mates", "h2g_set_read_seeds", "h2g_sam_set_n_ceil", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
 ]
@@ -434,6 +468,7 @@ def lib():
     L.h2g_align_run.argtypes = [vp, P(AlignParams)]
     L.h2g_align_fetch.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_set_mates.argtypes = [vp, vp, vp, vp, C.c_char_p, vp, C.c_size_t]
+    L.h2g_set_read_seeds.argtypes = [vp, vp, vp, C.c_size_t]
     L.h2g_align_pairs_run.argtypes = [vp, P(AlignParams)]
     L.h2g_align_pairs_fetch.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
@@ -669,6 +704,15 @@ class Stream:
         aln = (AlnRes * (n * ALN_CAP))() if with_alignments else None
         _chk(lib().h2g_align_fetch(self.h, res.ctypes.data, aln, first, n), "h2g_align_fetch")
         return res, aln
+
+    def set_read_seeds(self, seeds1, seeds2=None):
+        """explicit PRNG seeds of the resident batch's reads (mate 1, and mate 2 for pairs) in place of genRandSeed; None clears them"""
+        if seeds1 is None:
+            _chk(lib().h2g_set_read_seeds(self.h, None, None, 0), "h2g_set_read_seeds")
+            return
+        s1 = np.ascontiguousarray(seeds1, dtype=np.uint32)
+        s2 = None if seeds2 is None else np.ascontiguousarray(seeds2, dtype=np.uint32)
+        _chk(lib().h2g_set_read_seeds(self.h, s1.ctypes.data, None if s2 is None else s2.ctypes.data, len(s1)), "h2g_set_read_seeds")
 
     def set_mates(self, codes2, offs2, qnames2, quals2=None):
         codes2 = np.ascontiguousarray(codes2, dtype=np.uint8)

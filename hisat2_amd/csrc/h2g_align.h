@@ -12,6 +12,7 @@
 //   selectByScore aln_sink.h:2680   RandomSource random_source.h:33
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include "h2g_core.h"
 #include "h2g_sw.h"
 #include "h2g_graph.h"
@@ -345,9 +346,9 @@ struct Rng {   // RandomSource random_source.h:33-60
 	}
 };
 
-// genRandSeed pat.h:55-91 with global seed 0 (name bytes come from the host)
-H2G_HD uint32_t gen_rand_seed(const SeqView& fwseq, const char* name, uint32_t namelen, uint32_t seed) {
-	uint32_t rseed = (seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
+// genRandSeed pat.h:55-91 (name bytes come from the host).  `seed0` = rand_seed0(global seed), AlnParams::seed0
+H2G_HD uint32_t gen_rand_seed(const SeqView& fwseq, const char* name, uint32_t namelen, uint32_t seed0) {
+	uint32_t rseed = seed0;
 	for(uint32_t i = 0; i < fwseq.len; i++) rseed ^= ((uint32_t)fwseq.fwc[i] << ((i & 15) << 1));
 	for(uint32_t i = 0; i < fwseq.len; i++) rseed ^= ((uint32_t)(fwseq.q ? fwseq.q[i] : 'I') << ((i & 3) << 3));
 	for(uint32_t i = 0; i < namelen; i++) {
@@ -782,9 +783,14 @@ struct AlnParams {
 	uint32_t maxFragLen;     // PairedEndPolicy::maxFragLen = -X (hisat2.cpp:345)
 	uint32_t bowtie2_dp;     // ReportingParams::bowtie2_dp: 0 off, 1 conditional, 2 unconditional (hisat2.cpp:529, 1770)
 	uint32_t scoreMinType = 2;                                     // SimpleFunc scoreMin: 1 C, 2 L, 3 S, 4 G (simple_func.h:30-33)
+	uint32_t seed0 = rand_seed0(0);                                // genRandSeed's starting product for --seed (pat.h:59): fills what was padding
 	double   scoreMinConst = 0.0, scoreMinCoeff = (double)(-0.2f); // --score-min, default L,0,-0.2 (hisat2.cpp:440)
 	DScoring sc;
+	uint32_t nCeilType = 2;                                        // --n-ceil (nceil_value), default L,0,0.15
+	double   nCeilConst = 0.0, nCeilCoeff = (double)0.15f;
 };
+// seed0 took the 4 bytes of padding in front of scoreMinConst: every field up to sc keeps its offset
+static_assert(offsetof(AlnParams, seed0) == 60 && offsetof(AlnParams, scoreMinConst) == 64, "AlnParams: seed0 must sit in the padding before the doubles");
 // scoreMin.f<TAlScore>(len) (simple_func.h:88-110, hisat2.cpp:3380-3397: clamped to <= 0 in end-to-end mode)
 H2G_HD int64_t min_score_for(const AlnParams& P, uint32_t len) {
 	double X = 0.0;
@@ -807,6 +813,8 @@ inline AlnParams aln_params_from(const h2g_align_params& p, bool no_spliced, boo
 	P.pseudogeneStop = (linear && !no_spliced) ? 1 : 0; P.anchorStop = p.no_anchorstop ? 0 : 1; P.maxFragLen = p.max_frag_len ? p.max_frag_len : 1000;
 	P.bowtie2_dp = p.bowtie2_dp;
 	P.scoreMinType = p.score_min_type; P.scoreMinConst = p.score_min_const; P.scoreMinCoeff = p.score_min_coeff;
+	P.seed0 = rand_seed0(p.seed);
+	P.nCeilType = p.n_ceil_type; P.nCeilConst = p.n_ceil_const; P.nCeilCoeff = p.n_ceil_coeff;
 	P.sc.mmpMax = p.mm_max; P.sc.mmpMin = p.mm_min; P.sc.nPen = p.n_pen; P.sc.rdGapConst = p.rdg_const; P.sc.rdGapLinear = p.rdg_linear;
 	P.sc.rfGapConst = p.rfg_const; P.sc.rfGapLinear = p.rfg_linear; P.sc.scMax = p.sc_max; P.sc.scMin = p.sc_min;
 	P.sc.minAnchorLen = P.minAnchorLen; P.sc.minAnchorLen_noncan = P.minAnchorLen_noncan; P.sc.maxIntronLen = P.maxIntronLen;
@@ -827,6 +835,7 @@ inline void align_params_defaults(h2g_align_params* p, bool linear) {
 	p->pen_noncanintronlen_type = 4; p->pen_noncanintronlen_const = -8.0; p->pen_noncanintronlen_coeff = 1.0;
 	p->min_anchor_len = 7; p->min_anchor_len_noncan = 14; p->xs_only = 0; p->use_haplotype = 0; p->max_alts_tried = 16; p->max_frag_len = 1000; p->min_frag_len = 0; p->pe_orientation = 0; p->nofw = 0; p->norc = 0;
 	p->avoid_pseudogene = 0; p->transcriptome_mapping_only = 0; p->no_anchorstop = 0; p->pen_conflictsplice = 1000000;   // hisat2.cpp:495, :507-512
+	p->seed = 0; p->n_ceil_type = 2; p->n_ceil_const = 0.0; p->n_ceil_coeff = (double)0.15f;                             // hisat2.cpp:490; aligner_seed_policy.cpp:294
 }
 
 // One reported alignment = the arguments reportHit (hi_aligner.h:6064-6166) hands to AlnRes::init
@@ -1472,18 +1481,17 @@ struct ReadOut {
 	uint8_t  select[H2G_SELECT_CAP];   // fixed: the same layout in every translation unit whatever its AL_MAX_RESULTS
 };
 
-// Scoring::nFilter scoring.cpp:104 with the effective default nCeil = L,0,0.15 (SeedAlignmentPolicy::parseString
+// Scoring::nFilter scoring.cpp:104 with nCeil = --n-ceil (nceil_pass; default L,0,0.15: SeedAlignmentPolicy::parseString
 // aligner_seed_policy.cpp:294-296 overrides hisat2.cpp:443) + the length filter (hisat2.cpp:3413)
-H2G_HD bool read_passes_filters(const SeqView& v) {
+H2G_HD bool read_passes_filters(const SeqView& v, const AlnParams& P) {
 	if(v.len < 2) return false;
-	const uint32_t maxns = (uint32_t)(0.0 + (double)0.15f * (double)v.len);
 	uint32_t ns = 0;
 	if(v.pk) {                       // packed read: the N mask words (SeqView::at)
 		for(uint32_t w = 0; w < (v.len + 31) / 32; w++) ns += (uint32_t)__builtin_popcount(v.pk[(H2G_PK_WORDS + w) * v.pk_stride]);
-		return ns <= maxns;
+	} else {
+		for(uint32_t i = 0; i < v.len; i++) ns += v.fwc[i] == 4;
 	}
-	for(uint32_t i = 0; i < v.len; i++) if(v.fwc[i] == 4) { if(++ns > maxns) return false; }
-	return true;
+	return nceil_pass(P.nCeilType, P.nCeilConst, P.nCeilCoeff, v.len, ns);
 }
 // Paired read: rnd.init(seedA ^ seedB) (hisat2.cpp:3464-3466), go() with both mates.  The concordant /
 // discordant / unpaired classification and selection of finishRead stay on the host: the

@@ -18,6 +18,8 @@
 #include <deque>
 #include <chrono>
 #include <algorithm>
+#include <sstream>
+#include <time.h>
 #include <fcntl.h>
 #include <unistd.h>
 #include <sys/mman.h>
@@ -25,6 +27,7 @@
 #include <zlib.h>
 #include "../../include/h2g.h"
 #include "../../include/h2g_sam.h"
+#include "h2g_align.h"      // h2g::Rng (--non-deterministic)
 
 namespace {
 
@@ -272,6 +275,8 @@ int main(int argc, char** argv) {
 	std::vector<std::string> opts;                      // scoring / reporting options, applied once the index type is known
 	bool sensitive = false, very_sensitive = false, saw_k = false;
 	uint32_t k_arg = 0, max_seeds_arg = 0;
+	long seed_arg = 0;
+	bool arbitrary_random = false;
 	for(int i = 0; i < argc; i++) { if(i) cmdline.push_back(' '); cmdline += argv[i]; }
 	for(int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
@@ -327,6 +332,12 @@ int main(int argc, char** argv) {
 		else if(a == "--no-discordant") report_discordant = false;             // hisat2.cpp:1161
 		else if(a == "--haplotype") use_haplotype = true;                      // hisat2.cpp:1749 (ARG_HAPLOTYPE)
 		else if(a == "--bowtie2-dp") dp = (uint32_t)atoi(need("--bowtie2-dp"));
+		else if(a == "--seed") {                                                 // parseInt(0, ...) hisat2.cpp:1204, 1016-1032
+			seed_arg = strtol(need("--seed"), nullptr, 10);
+			if(seed_arg < 0 || seed_arg > INT32_MAX) { fprintf(stderr, "--seed arg must be at least 0\n"); return 1; }
+		}
+		else if(a == "--non-deterministic" || a == "--nondeterministic") arbitrary_random = true;   // hisat2.cpp:1207
+		else if(a == "--n-ceil") { opts.push_back(a); opts.push_back(need("--n-ceil")); }
 		else if(a == "-k" || a == "--max-seeds" || a == "--mp" || a == "--sp" || a == "--np" || a == "--rdg" || a == "--rfg" || a == "--score-min" ||
 		        a == "--min-intronlen" || a == "--max-intronlen" || a == "--pen-cansplice" || a == "--pen-noncansplice" || a == "--pen-conflictsplice" ||
 		        a == "--pen-canintronlen" || a == "--pen-intronlen" || a == "--pen-noncanintronlen") {
@@ -467,6 +478,21 @@ int main(int argc, char** argv) {
 			k_arg = (uint32_t)k; saw_k = true;
 		}
 		else if(o == "--max-seeds") max_seeds_arg = (uint32_t)atoi(opts[++i].c_str());
+		else if(o == "--n-ceil") {
+			// hisat2.cpp:1525-1549: 1-3 tokens, one token x is C,x; then PARSE_FUNC (aligner_seed_policy.cpp:47-70): type, constant and coefficient
+			// when given (istringstream >> double), the others keep their value
+			std::vector<std::string> t = split_commas(opts[++i].c_str());
+			if(t.size() > 3) { fprintf(stderr, "Error: expected 3 or fewer comma-separated arguments to --n-ceil option, got %zu\n", t.size()); return 1; }
+			if(t.empty()) { fprintf(stderr, "Error: expected at least one argument to --n-ceil option\n"); return 1; }
+			if(t.size() == 1) t.insert(t.begin(), "C");
+			const std::string& ty = t[0];
+			const uint32_t type = ty == "C" || ty == "Constant" ? 1 : ty == "L" || ty == "Linear" ? 2 : ty == "S" || ty == "Sqrt" ? 3 : ty == "G" || ty == "Log" ? 4 : 0;
+			if(!type) { fprintf(stderr, "Error: Bad function type '%s'.  Should be C (constant), L (linear), S (square root) or G (natural log).\n", ty.c_str()); return 1; }
+			auto num = [](const std::string& v) { double d = 0.0; std::istringstream ss(v); ss >> d; return d; };
+			P.n_ceil_type = type;
+			if(t.size() > 1) P.n_ceil_const = num(t[1]);
+			if(t.size() > 2) P.n_ceil_coeff = num(t[2]);
+		}
 		else if(o == "--secondary") P.secondary = 1;
 		else if(o == "--mp") two(&P.mm_max, &P.mm_min);
 		else if(o == "--sp") { int32_t unused = 0; two(&P.sc_max, &unused); P.sc_min = P.sc_max; }   // both read from the first number (aligner_seed_policy.cpp:438)
@@ -523,6 +549,7 @@ int main(int argc, char** argv) {
 	P.max_alts_tried = (uint32_t)max_alts_tried;
 	P.max_frag_len = (uint32_t)max_frag_len;
 	P.min_frag_len = (uint32_t)min_frag_len; P.pe_orientation = (uint32_t)pe_orientation; P.nofw = nofw ? 1 : 0; P.norc = norc ? 1 : 0;
+	P.seed = (uint32_t)seed_arg;
 	h2g_align_params_presets(&P, ix, saw_k ? 1 : 0, k_arg, max_seeds_arg, sensitive ? 1 : 0, very_sensitive ? 1 : 0);
 	if(!P.no_spliced_alignment && P.max_intronlen > 0xfffffu) {
 		fprintf(stderr, "hisat2-align-amd: --max-intronlen %u is beyond the 1048575 bases a splice edit holds here\n", P.max_intronlen);
@@ -586,6 +613,7 @@ int main(int argc, char** argv) {
 	h2g_sam_set_header_options(sam, no_sq, omit_sec_seq);
 	h2g_sam_set_new_summary(sam, new_summary);
 	h2g_sam_set_score_min(sam, P.score_min_type, P.score_min_const, P.score_min_coeff);
+	h2g_sam_set_n_ceil(sam, P.n_ceil_type, P.n_ceil_const, P.n_ceil_coeff);
 	h2g_sam_set_secondary(sam, (int)P.secondary);
 	h2g_sam_set_rna_strandness(sam, strandness);
 	FILE* out = outfn.empty() ? stdout : fopen(outfn.c_str(), "wb");
@@ -606,9 +634,18 @@ int main(int argc, char** argv) {
 	h2g_sam_set_no_unal(sam, no_unal ? 1 : 0);
 	Reader ra(paired ? m1 : u, fasta, threads, trim5, trim3), rb(m2, fasta, threads, trim5, trim3);
 	ra.phred64_ = rb.phred64_ = phred64;
+	// --non-deterministic: every read / pair takes two draws, mate 1's seed then mate 2's, from one RandomSource seeded with time(0) (hisat2.cpp:3273,
+	// :3311-3314; the reference keeps one per worker thread), in read order, before the -s test — skipped reads draw too.  H2G_ARB_SEED=<n> (test hook)
+	// replaces time(0).
+	h2g::Rng arb;
+	arb.init(getenv("H2G_ARB_SEED") ? (uint32_t)strtoul(getenv("H2G_ARB_SEED"), nullptr, 10) : (uint32_t)time(0));
+	std::vector<uint32_t> arb1, arb2;
 	if(skip) {   // -s: the skipped reads are parsed (their ids count) but not aligned
 		Batch junk;
-		for(uint64_t left = skip; left > 0;) { junk.clear(); const size_t g = ra.fill(junk, (size_t)std::min<uint64_t>(left, batch)); if(paired) { junk.clear(); rb.fill(junk, g); } if(!g) break; left -= g; }
+		for(uint64_t left = skip; left > 0;) {
+			junk.clear(); const size_t g = ra.fill(junk, (size_t)std::min<uint64_t>(left, batch)); if(paired) { junk.clear(); rb.fill(junk, g); } if(!g) break; left -= g;
+			if(arbitrary_random) for(size_t r = 0; r < 2 * g; r++) arb.nextU32();
+		}
 	}
 	uint64_t budget = upto;                               // -u counts the reads after the skipped ones (qUpto += skipReads, hisat2.cpp:1959-1963)
 	// Formatting on a thread of its own (round 6): the main thread fetches batch k + 1's records while batch k's text is written — what the device returns goes to one of two sets of page-locked
@@ -873,6 +910,13 @@ int main(int argc, char** argv) {
 			                "Use -p >= 2 or --ss-window W (output == hisat2 -p W/1000 --reorder), or --no-temp-splicesite, for throughput.\n");
 		if(paired) {
 			if(h2g_set_mates(sg.st, b.codes.data(), b.offs.data(), b.have_quals ? b.quals.data() : nullptr, b.names.data(), b.noffs.data(), n) != H2G_OK) die("h2g_set_mates");
+		}
+		if(arbitrary_random) {                         // this batch's draws, in read order (the batches are submitted in read order whatever the device)
+			arb1.resize(n); arb2.resize(n);
+			for(size_t r = 0; r < n; r++) { arb1[r] = arb.nextU32(); arb2[r] = arb.nextU32(); }
+			if(h2g_set_read_seeds(sg.st, arb1.data(), paired ? arb2.data() : nullptr, n) != H2G_OK) die("h2g_set_read_seeds");
+		}
+		if(paired) {
 			if(h2g_align_pairs_run(sg.st, &P) != H2G_OK) die("h2g_align_pairs_run");
 		} else if(h2g_align_run(sg.st, &P) != H2G_OK) die("h2g_align_run");
 		t_up += now() - tq0;

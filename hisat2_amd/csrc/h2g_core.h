@@ -24,6 +24,32 @@
 
 namespace h2g {
 
+// the starting product of genRandSeed (pat.h:59) for the global seed (--seed), in uint32 arithmetic
+H2G_HD constexpr uint32_t rand_seed0(uint32_t seed) { return (seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u; }
+
+// ------------------------------------------------------------------------------------------ N ceiling
+// nCeil.f<T>((double)len) (simple_func.h:86-108) as nCeil is initialised (aligner_seed_policy.cpp:294: min I = 0, max X = DMAX) and parsed
+// (PARSE_FUNC :47-70: type, then constant and coefficient as double).  std::min / std::max as written there: a NaN sum yields DMAX.  Never negative.
+H2G_HD double nceil_value(uint32_t type, double c, double l, uint32_t len) {
+	const double x = (double)len;
+	const double X = type == 2 ? x : type == 3 ? sqrt(x) : type == 4 ? log(x) : 0.0;
+	const double DMAX = 1.7976931348623157e308, v = c + l * X;
+	const double hi = v < DMAX ? v : DMAX;                  // std::min(X_, C + L * X)
+	return 0.0 < hi ? hi : 0.0;                             // std::max(I_, ...)
+}
+// Scoring::nFilter (scoring.cpp:104): a mate passes when its Ns are at most f<size_t>(len).  A value of len or more (DMAX included: f returns the
+// type's maximum) passes every count; below len the conversion is exact.
+H2G_HD bool nceil_pass(uint32_t type, double c, double l, uint32_t len, uint32_t ns) {
+	const double f = nceil_value(type, c, l, len);
+	return f >= (double)len || ns <= (uint32_t)f;
+}
+// the DP's ceiling (hisat2.cpp:3453-3459): min(f<int>(len), len).  (A value of 2^31 or more converts out of range there, which C++ leaves undefined;
+// here it is len, as every value from len up.)
+H2G_HD int nceil_dp(uint32_t type, double c, double l, uint32_t len) {
+	const double f = nceil_value(type, c, l, len);
+	return f >= (double)len ? (int)len : (int)f;
+}
+
 // ------------------------------------------------------------------------------------------ device views
 struct DGfm {   // one 32-bit GFM resident in HBM (sides exactly as on disk: 64 B linear / 128 B graph)
 	const uint8_t*  sides;
@@ -61,6 +87,7 @@ struct DReads {
 	// word k of this lane at pk[k * pk_stride] (lane-interleaved => conflict-free ds_read_b32)
 	const uint32_t* pk = nullptr;
 	uint32_t pk_stride = 0, pk_read = 0xffffffffu;
+	const uint32_t* seeds = nullptr;   // [n] explicit PRNG seeds of this read set (h2g_set_read_seeds, --non-deterministic); nullptr: genRandSeed
 };
 #define H2G_PK_WORDS 8           // 128 bases (longer reads are read from HBM base by base)
 #define H2G_PK_MAXLEN (H2G_PK_WORDS * 16)

@@ -783,7 +783,7 @@ H2G_HD uint32_t fg_res_hit(uint32_t m, uint32_t k) { return FW_RH + (m * FG_NRES
 // genRandSeed (pat.h:55-91, gen_rand_seed of h2g_align.h) of a read without N from its packed words: the 2-bit codes of 16 bases
 // XOR into the seed exactly as they lie in a packed word
 H2G_HD uint32_t fg_rand_seed(const FCtx& C, const FState& S, uint32_t set) {
-	uint32_t rseed = (0u + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
+	uint32_t rseed = C.P->seed0;
 	const uint32_t len = fs_rl(S, set);
 	const uint32_t* pk = set ? C.pk[1] : C.pk[0];
 	for(uint32_t w = 0; w < H2G_PK_WORDS; w++) rseed ^= pk[w * C.pk_stride];
@@ -827,10 +827,11 @@ H2G_HD void fast_begin(const FCtx& C, FState& S, uint32_t read, bool paired, boo
 	const uint32_t len0 = C.rd[0].offs[read + 1] - S.ro0, len1 = C.rd[1].offs[read + 1] - S.ro1;
 	if(!packed_ok || len0 < 32 || len0 > 128 || (paired && (len1 < 32 || len1 > 128))) { S.pc = FPC_BAIL; S.bail = FB_INPUT; return; }
 	S.rl0 = len0; S.rl1 = len1;
-	// no N, length >= 2: both filters pass (read_passes_filters)
+	// no N, length >= 2: both filters pass whatever --n-ceil says (read_passes_filters: nceil_value is never negative)
 	Rng rnd;
-	uint32_t seed = fg_rand_seed(C, S, 0);
-	if(paired) seed ^= fg_rand_seed(C, S, 1);                  // hisat2.cpp:3463-3468
+	const uint32_t* seeds0 = C.rd[0].seeds;                    // explicit seeds (--non-deterministic): both read sets carry them, or neither
+	uint32_t seed = seeds0 ? seeds0[read] : fg_rand_seed(C, S, 0);
+	if(paired) seed ^= seeds0 ? C.rd[1].seeds[read] : fg_rand_seed(C, S, 1);   // hisat2.cpp:3463-3468
 	rnd.init(seed);
 	S.rnd = rnd.last;
 	S.pc = FPC_GO_INIT;

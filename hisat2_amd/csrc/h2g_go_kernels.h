@@ -268,7 +268,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 					M.rd[1].pk_read = gs->pk_ok[1] ? i : 0xffffffffu;
 					M.name[1] = A.names2 + A.noffs2[i]; M.namelen[1] = A.noffs2[i + 1] - A.noffs2[i];
 				}
-				mach_begin(M, i, paired);
+				mach_begin(*C.P, M, i, paired);
 				gs->ro[0] = M.ro[0]; gs->ro[1] = M.ro[1]; gs->rl[0] = M.rl[0]; gs->rl[1] = M.rl[1];
 			}
 			PROF(0);

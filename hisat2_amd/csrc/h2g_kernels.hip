@@ -101,6 +101,8 @@ struct BatchCtx {
 	// result rows: aln_slots (>= -k) records per read in d_aln, pair_slots (>= H2G_PAIR_RES_CAP) per mate in d_paln; aln_alloc / paln_alloc records behind them
 	ReadOut* d_rout = nullptr; h2g_alnres* d_aln = nullptr; size_t aln_alloc = 0; uint32_t aln_slots = 0;
 	PairOut* d_pout = nullptr; h2g_alnres* d_paln[2] = {nullptr, nullptr}; size_t paln_alloc = 0; uint32_t pair_slots = 0;
+	// explicit PRNG seeds (h2g_set_read_seeds): mate 1's at [0, max_reads), mate 2's at [max_reads, 2 max_reads); a run reads them when has_seeds
+	uint32_t* d_seeds = nullptr; bool has_seeds = false, has_seeds2 = false;
 };
 struct h2g_stream {
 	h2g_index* ix = nullptr;
@@ -623,6 +625,7 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	for(const BatchCtx& B : s->batch) {
 		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
 		(void)hipFree(B.d_quals2); (void)hipFree(B.d_names2); (void)hipFree(B.d_name_offs2); (void)hipFree(B.d_rout); (void)hipFree(B.d_aln); (void)hipFree(B.d_pout); (void)hipFree(B.d_paln[0]); (void)hipFree(B.d_paln[1]);
+		(void)hipFree(B.d_seeds);
 	}
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
 	for(int i = 0; i < 12; i++) (void)hipEventDestroy(s->ev[i]);
@@ -720,6 +723,7 @@ extern "C" h2g_status h2g_set_reads(h2g_stream* s, const uint8_t* codes, const u
 	B.n_reads = n;
 	B.has_names = false;
 	B.has_mates = false;
+	B.has_seeds = B.has_seeds2 = false;
 	s->ledits_touched = 0;            // (long-edit lists of the batch this one replaces are nobody's any more)
 	return H2G_OK;
 }
@@ -1931,6 +1935,21 @@ extern "C" h2g_status h2g_set_mates(h2g_stream* s, const uint8_t* codes2, const 
 	return H2G_OK;
 }
 
+extern "C" h2g_status h2g_set_read_seeds(h2g_stream* s, const uint32_t* seeds1, const uint32_t* seeds2, size_t n) {
+	if(s) HIPCHK(sync_all(s));        // (a run of the previous seeds may still read the buffer)
+	if(!s) return H2G_ERR_ARG;
+	BatchCtx& B = s->cur();
+	if(!seeds1) { B.has_seeds = B.has_seeds2 = false; return H2G_OK; }
+	if(n != B.n_reads || n == 0) return H2G_ERR_ARG;
+	HIPCHK(hipSetDevice(s->ix->device));
+	if(!B.d_seeds) HIPCHK(hipMalloc((void**)&B.d_seeds, 2 * s->max_reads * sizeof(uint32_t)));
+	HIPCHK(hipMemcpyAsync(B.d_seeds, seeds1, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
+	if(seeds2) HIPCHK(hipMemcpyAsync(B.d_seeds + s->max_reads, seeds2, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
+	HIPCHK(sync_all(s));
+	B.has_seeds = true; B.has_seeds2 = seeds2 != nullptr;
+	return H2G_OK;
+}
+
 // go() on a graph index: the index must be a SNP graph (ALT database present)
 // GenomeHit::combineWith as a primitive of its own: a[i] becomes the combination of a[i] (the left hit) and b[i] on the resident reads, ok[i] the
 // function's return value.  Scoring and splice policy: `p` (nullptr: the defaults of the index).
@@ -2030,6 +2049,8 @@ static int go_check(h2g_stream* s, const h2g_align_params* p, bool paired) {
 	if((rc = need_reads(s)) || (rc = need_alignable(s))) return rc;
 	if(!s->ix->has_local) { snprintf(g_err, sizeof g_err, "align: index loaded without local (.5/.6) indexes"); return H2G_ERR_ARG; }
 	if(!s->cur().has_names || (paired && !s->cur().has_mates)) { snprintf(g_err, sizeof g_err, "align: read names (h2g_set_read_names)%s not set", paired ? " / mates (h2g_set_mates)" : ""); return H2G_ERR_ARG; }
+	if(paired && s->cur().has_seeds && !s->cur().has_seeds2) { snprintf(g_err, sizeof g_err, "align: explicit seeds without mate 2's (h2g_set_read_seeds seeds2)"); return H2G_ERR_ARG; }
+	if(p->n_ceil_type < 1 || p->n_ceil_type > 4) { snprintf(g_err, sizeof g_err, "align: n_ceil_type %u (1 C, 2 L, 3 S, 4 G)", p->n_ceil_type); return H2G_ERR_ARG; }
 	if(!p->no_spliced_alignment) {
 		// spliced alignment: combineWith places introns (hi_aligner.h:1588-1739) and every read is independent when novel splice
 		// sites are not shared (--no-temp-splicesite); the shared SpliceSiteDB of the default mode and graph indexes are not built
@@ -2148,6 +2169,7 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	if(p->use_haplotype && !g.linear && A.alts.n) A.alts.has_splice |= 2u;   // --haplotype: the table behind the ALTs is read (h2g_graph.h haps_of)
 	A.rd1 = dreads(s); A.rd2 = A.rd1;
 	if(paired) { A.rd2.codes = b.d_codes2; A.rd2.offs = b.d_offs2; A.rd2.quals = b.has_quals2 ? b.d_quals2 : nullptr; }
+	if(b.has_seeds) { A.rd1.seeds = b.d_seeds; A.rd2.seeds = paired ? b.d_seeds + s->max_reads : b.d_seeds; }   // every launch of the run copies rd1 / rd2
 	A.P = aln_params_from(*p, p->no_spliced_alignment != 0, g.linear);
 	if(!p->no_spliced_alignment) { A.ssdb = s->ix->dssdb; A.rdid_base = p->first_read_id; }
 	r->X = p->no_spliced_alignment ? DExonTbl() : s->ix->dexons;

@@ -176,8 +176,13 @@ H2G_HD void mach_cache_read(Mach& M, uint32_t read, bool paired_input) {
 	if(!paired_input) { M.ro[1] = M.ro[0]; M.rl[1] = M.rl[0]; }
 }
 
+// A mate's PRNG seed (Read::seed): the explicit one of its read set (--non-deterministic, hisat2.cpp:3311-3314) or genRandSeed
+H2G_HD uint32_t mach_read_seed(const Mach& M, const AlnParams& P, const SeqView& v, uint32_t set) {
+	const DReads& r = M.rd[set];
+	return r.seeds ? r.seeds[M.read] : gen_rand_seed(v, M.name[set], M.namelen[set], P.seed0);
+}
 // The prelude of the worker loop body for one read / pair (hisat2.cpp:3380-3530): filters, PRNG seed, which mates go() sees.
-H2G_MACH_FN void mach_begin(Mach& M, uint32_t read, bool paired_input) {
+H2G_MACH_FN void mach_begin(const AlnParams& P, Mach& M, uint32_t read, bool paired_input) {
 	AlignWS* ws = M.ws;
 	GoVars& gv = ws->gv;
 	M.read = read;
@@ -188,15 +193,15 @@ H2G_MACH_FN void mach_begin(Mach& M, uint32_t read, bool paired_input) {
 	SeqView v1 = mach_view(M, 0, true);
 	Rng rnd;
 	if(!paired_input) {
-		rnd.init(gen_rand_seed(v1, M.name[0], M.namelen[0], 0));       // rnd.init(ps->bufa().seed) hisat2.cpp:3468
+		rnd.init(mach_read_seed(M, P, v1, 0));                          // rnd.init(ps->bufa().seed) hisat2.cpp:3468
 		gv.rnd = rnd.last;
 		gv.paired = 0; gv.nm = 1; gv.slot0 = 0; gv.rd_sel[0] = 0; gv.rd_sel[1] = 0;
-		M.L.pc = read_passes_filters(v1) ? PC_GO_INIT : PC_FINISH;      // filt[0] false: go() is skipped (hisat2.cpp:3518)
+		M.L.pc = read_passes_filters(v1, P) ? PC_GO_INIT : PC_FINISH;   // filt[0] false: go() is skipped (hisat2.cpp:3518)
 		return;
 	}
 	SeqView v2 = mach_view(M, 1, true);
-	const bool f1 = read_passes_filters(v1), f2 = read_passes_filters(v2);
-	const uint32_t s1 = gen_rand_seed(v1, M.name[0], M.namelen[0], 0), s2 = gen_rand_seed(v2, M.name[1], M.namelen[1], 0);
+	const bool f1 = read_passes_filters(v1, P), f2 = read_passes_filters(v2, P);
+	const uint32_t s1 = mach_read_seed(M, P, v1, 0), s2 = mach_read_seed(M, P, v2, 1);
 	rnd.init((f1 && f2) ? (s1 ^ s2) : s1);                              // hisat2.cpp:3463-3468
 	gv.rnd = rnd.last;
 	gv.slot0 = 0; gv.rd_sel[0] = 0; gv.rd_sel[1] = 1;
@@ -205,6 +210,8 @@ H2G_MACH_FN void mach_begin(Mach& M, uint32_t read, bool paired_input) {
 	else if(f2)  { gv.paired = 0; gv.nm = 1; gv.slot0 = 1; gv.rd_sel[0] = 1; M.L.pc = PC_GO_INIT; }   // initRead(rds[1], rightendonly) :3524
 	else M.L.pc = PC_FINISH;
 }
+// (host instantiations that drive the machine step by step, tests/emul: the options' defaults, --seed 0 and --n-ceil L,0,0.15)
+inline void mach_begin(Mach& M, uint32_t read, bool paired_input) { mach_begin(AlnParams(), M, read, paired_input); }
 
 #define M_GOTO(NEXT) do { L.pc = (NEXT); goto again; } while(0)
 #define M_OP(OPC, NEXT) do { L.op = (OPC); L.pc = (NEXT); return; } while(0)
@@ -1590,6 +1597,7 @@ H2G_MACH_FN void mach_op_sw(const AlnCtx& C, Mach& M) {
 	const SeqView sv = mach_sv(M);
 	SwParams SP;
 	SP.sc = P.sc;
+	SP.nceil_type = P.nCeilType; SP.nceil_const = P.nCeilConst; SP.nceil_coeff = P.nCeilCoeff;
 	const uint32_t refoff = gh->toff > gh->rdoff ? gh->toff - gh->rdoff : 0;
 	SwOut* o = nullptr;
 	sw_align_single(*C.ref, SP, sv, gh->tidx, refoff, ws->m[gv.mw_slot].minsc, &gv.rnd, C.sw, &o);
@@ -1757,7 +1765,7 @@ H2G_HD void mach_run_single(const AlnCtx& C, Mach& M, uint32_t read, bool paired
 #else
 #define MP_PHASE(p)
 #endif
-	mach_begin(M, read, paired_input);
+	mach_begin(*C.P, M, read, paired_input);
 	while(M.L.pc != PC_FINISHED || M.L.op != OP_NONE) {
 		MP_PHASE(1)
 		mach_step(C, M);

@@ -40,6 +40,8 @@ struct h2g_sam {
 	bool secondary = false;                               // --secondary: selectByScore keeps lower-scoring alignments too
 	uint32_t smType = 2;                                  // --score-min (MAPQ's scMin), default L,0,-0.2
 	double smConst = 0.0, smCoeff = (double)(-0.2f);
+	uint32_t ncType = 2;                                  // --n-ceil (YF:Z:NS), default L,0,0.15
+	double ncConst = 0.0, ncCoeff = (double)0.15f;
 	std::vector<h2g_splice_site> alt_sites;               // the splice-site ALTs of a --ss index (SpliceSiteDB::read(gfm, alts)): always in the database
 	h2g::HostSpliceDB ssdb;                               // h2g_sam_set_splice_sites: TLEN of concordant pairs leaves known introns out
 	uint32_t ssdb_window = 0;
@@ -144,11 +146,11 @@ void put(std::string& o, int64_t v) {     // itoa10
 }
 
 // Scoring::nFilter / length filter as the worker applies them (hisat2.cpp:3404-3440): which YF:Z flag an unaligned read gets
-void read_filters(const Rd& r, bool* lenfilt, bool* nfilt) {
+void read_filters(const h2g_sam& S, const Rd& r, bool* lenfilt, bool* nfilt) {
 	*lenfilt = r.len >= 2;                     // rdlens <= multiseedMms(0) || < 2  => filtered
 	uint32_t ns = 0;
 	for(uint32_t i = 0; i < r.len; i++) ns += r.codes[i] > 3;
-	*nfilt = ns <= (uint32_t)(0.0 + (double)0.15f * (double)r.len);
+	*nfilt = h2g::nceil_pass(S.ncType, S.ncConst, S.ncCoeff, r.len, ns);   // the device's filter (h2g_core.h)
 }
 
 // BowtieMapq2::mapq unique.h:187-403 (end-to-end branch; canMax = false, exhausted = false)
@@ -949,6 +951,7 @@ extern "C" size_t h2g_sam_novel_splice_sites_text(const h2g_sam* S, char* out, s
 	return o.size();
 }
 extern "C" void h2g_sam_set_score_min(h2g_sam* S, uint32_t type, double c, double coeff) { if(S) { S->smType = type; S->smConst = c; S->smCoeff = coeff; } }
+extern "C" void h2g_sam_set_n_ceil(h2g_sam* S, uint32_t type, double c, double coeff) { if(S) { S->ncType = type; S->ncConst = c; S->ncCoeff = coeff; } }
 
 static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals,
                                   const char* nb, const uint32_t* noffs, size_t n, const h2g_read_result* res,
@@ -959,7 +962,7 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 	auto one = [&](size_t i, std::string& o, Met& met) {
 		Rd rd = {nb + noffs[i], noffs[i + 1] - noffs[i], codes + offs[i], offs[i + 1] - offs[i], quals ? quals + offs[i] : nullptr};
 		Flags fl;
-		read_filters(rd, &fl.lenfilt, &fl.nfilt);
+		read_filters(*S, rd, &fl.lenfilt, &fl.nfilt);
 		Summ summ;
 		const h2g_read_result& r = res[i];
 		if(r.best != INT32_MIN) { summ.best[0].valid = true; summ.best[0].score = r.best; summ.best[0].h2 = (int64_t)(((uint64_t)(int64_t)r.best << 32) | r.best_h2); }
@@ -1029,8 +1032,8 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 			n2 = ao2 ? (size_t)(ao2[i + 1] - ao2[i]) : std::min<size_t>(pr.nres[1], H2G_PAIR_RES_CAP);
 		}
 		Flags f1, f2;
-		read_filters(rd[0], &f1.lenfilt, &f1.nfilt);
-		read_filters(rd[1], &f2.lenfilt, &f2.nfilt);
+		read_filters(*S, rd[0], &f1.lenfilt, &f1.nfilt);
+		read_filters(*S, rd[1], &f2.lenfilt, &f2.nfilt);
 		Rng rnd = {pr.rnd_state};
 		// ReportingState::foundConcordant aln_sink.cpp:74-112: concordant pairs are kept while they tie the best pair score?
 		// No — every concordant pair reported is kept (rs1_/rs2_); nconcord = their count

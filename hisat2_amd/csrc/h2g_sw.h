@@ -39,7 +39,8 @@ namespace h2g {
 struct SwParams {   // Scoring (scoring.h) + the constants of the call site
 	DScoring sc;
 	int32_t gapbar = 4;          // gGapBarrier hisat2.cpp:419
-	uint32_t nceil_pct = 15;     // nCeil = L,0,0.15 (SeedAlignmentPolicy::parseString), evaluated per read length
+	uint32_t nceil_type = 2;     // --n-ceil, default L,0,0.15 (SeedAlignmentPolicy::parseString), evaluated per read length (nceil_dp)
+	double   nceil_const = 0.0, nceil_coeff = (double)0.15f;
 };
 
 struct SwFrame { uint16_t nedsz, celsz, row, col, gaps; int16_t ns; int32_t score; uint8_t ct; };
@@ -465,7 +466,7 @@ H2G_HD SwOut* sw_finish(const SwMats& m, const SwParams& P, const SeqView& sv, c
 	SwOut* o = &ls->out;
 	o->refl = rect.refl; o->refr = rect.refr;
 	const uint32_t rnd0 = *rnd;
-	const int nceil = nceil_given >= 0 ? nceil_given : (int)((double)P.nceil_pct * 0.01 * (double)m.nrow);
+	const int nceil = nceil_given >= 0 ? nceil_given : nceil_dp(P.nceil_type, P.nceil_const, P.nceil_coeff, m.nrow);
 	sw_gather_backtrace(m, P, sv, rect, minsc, nceil, rnd, mt, ls->stack, ls->cells, o);
 	if(mt.full && direct) {
 		const size_t n = (size_t)m.nrow * m.ncol;

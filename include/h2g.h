@@ -285,7 +285,7 @@ typedef struct {                   /* == the arguments reportHit (hi_aligner.h:6
 	 * the splice edits (2: every splice a database site, 1: spliced).  Read the strand as (fw & H2G_FW_STRAND). */
 	int64_t  score;                /* AS:i */
 	h2g_edit edits[H2G_MAX_EDITS]; /* as stored in the AlnRes (aligner_result.cpp:110-118): positions along the original read
-	                                * 5'->3', relative to its first aligned (non-soft-clipped) base */
+	                                * 5'->3', relative to its first aligned (non-soft-clipped) base; entries past nedits are unspecified */
 } h2g_alnres;
 typedef struct {
 	uint32_t nres;                 /* alignments reported to the sink (rs1u_) */
@@ -344,16 +344,33 @@ typedef struct {
 	 * default 1000000): Scoring::csp, the penalty of an alignment whose splices disagree in direction. */
 	uint32_t avoid_pseudogene, transcriptome_mapping_only, no_anchorstop;
 	int32_t  pen_conflictsplice;
+	/* --seed (hisat2.cpp:1204, default 0): the global seed of genRandSeed (pat.h:55-91), every read's PRNG seed.  h2g_set_read_seeds replaces the
+	 * hashed seeds with explicit ones (--non-deterministic) */
+	uint32_t seed;
+	/* --n-ceil (SimpleFunc nCeil: Scoring::nFilter scoring.cpp:104, the DP's nceil hisat2.cpp:3453-3459): type as score_min_type, default
+	 * L,0,0.15 with the coefficient (double)0.15f (aligner_seed_policy.cpp:294); clamped below at 0.  A mate with more Ns than
+	 * f(length) is filtered (YF:Z:NS); a mate without N always passes */
+	uint32_t n_ceil_type;
+	double   n_ceil_const, n_ceil_coeff;
 } h2g_align_params;
 /* number of visible HIP devices (0 without a GPU: the library has no CPU path) */
 H2G_EXPORT int        h2g_device_count(void);
 H2G_EXPORT void       h2g_align_params_init(h2g_align_params*, const h2g_index*);
+/* --n-ceil as given to the aligner (n_ceil_type / n_ceil_const / n_ceil_coeff) for a SAM handle of include/h2g_sam.h: which unaligned mates
+ * it flags YF:Z:NS (default L,0,(double)0.15f, as h2g_align_params_init) */
+struct h2g_sam;
+H2G_EXPORT void       h2g_sam_set_n_ceil(struct h2g_sam*, uint32_t type, double constant, double coeff);
 /* The reference applies its presets after ALL options were read (hisat2.cpp:1882-1909) and lets the index type decide the
  * default -k (:3903-3906): khits = saw_k ? k_arg : 10; --sensitive: bowtie2_dp 0 -> 1, khits < 10 -> 10 (counts as saw_k),
  * --score-min L,0,-0.5; --very-sensitive: bowtie2_dp 2, khits < 30 -> 30, L,0,-1; without saw_k khits = 5 (linear) / 10 (graph);
  * max_seeds_arg 0 -> max(5, 2 khits) (:3174).  Call it last, after every other field of *p was set from the options. */
 H2G_EXPORT void       h2g_align_params_presets(h2g_align_params* p, const h2g_index* ix, int saw_k, uint32_t k_arg, uint32_t max_seeds_arg,
                                                int sensitive, int very_sensitive);
+/* Explicit per-read PRNG seeds for the selected resident batch, in place of genRandSeed (hisat2.cpp:3311-3314, --non-deterministic: Read::seed of
+ * mate 1 and mate 2 drawn from a RandomSource).  seeds1 / seeds2: [n] (n = the batch's read count); seeds2 is read by paired runs only, and a paired run
+ * with seeds1 but no seeds2 is refused.  A pair's PRNG starts from seeds1[i] ^ seeds2[i] when both mates pass the filters (length, --n-ceil) and from
+ * seeds1[i] otherwise (hisat2.cpp:3463-3468); an unpaired read's from seeds1[i].  seeds1 == NULL clears them; h2g_set_reads clears them too. */
+H2G_EXPORT h2g_status h2g_set_read_seeds(h2g_stream*, const uint32_t* seeds1, const uint32_t* seeds2, size_t n);
 /* read names (needed by genRandSeed): name i = bytes[offs[i] .. offs[i+1]) */
 H2G_EXPORT h2g_status h2g_set_read_names(h2g_stream*, const char* bytes, const uint32_t* offs, size_t n_reads);
 /* GenomeHit::combineWith (hi_aligner.h:1420-2025) as a primitive of its own: a[i] (the left hit) absorbs b[i] — concatenation, the mismatch rescan of the joint,

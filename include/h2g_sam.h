@@ -73,6 +73,7 @@ H2G_EXPORT size_t     h2g_sam_take_novel_sites(h2g_sam*, h2g_splice_site* out, s
 H2G_EXPORT size_t     h2g_sam_novel_splice_sites_text(const h2g_sam*, char* out, size_t cap);
 /* --score-min as given to the aligner (h2g_align_params.score_min_*): MAPQ is relative to it (unique.h:214-222) */
 H2G_EXPORT void       h2g_sam_set_score_min(h2g_sam*, uint32_t type, double constant, double coeff);
+/* (--n-ceil: h2g_sam_set_n_ceil, declared in h2g.h next to h2g_align_params) */
 
 /* Records with more than H2G_MAX_EDITS edits (nedits > H2G_MAX_EDITS: a long deletion is one edit per base, edit.h) keep their edit list in the
  * long-edit area of their batch (h2g_align_fetch_long_edits, include/h2g.h).  Hand the area of the batch about to be formatted to the handle (not
