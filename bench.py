@@ -10,9 +10,12 @@ large-workspace pass over what overflowed that.  The machine's pass of step k ru
 the following steps (up to eight in flight); the K timed steps are bracketed by a full
 synchronisation of every stream, so the drain of the last machine passes is inside the timed region.
 
-Parity at the size that is timed: every record of the batch the timed steps ran on goes through the product's sink + SAM text and is
-compared with oracle/_ref/hisat2-align-s over the same reads, byte for byte (`parity_whole_batch`; a mismatch prints the line and fails
-the run) — the reference binary is the checker, never inside a timed region.
+A plain run does only what the headline needs: it obtains the index, makes the batches' reads (in worker processes, while the device and the
+index are set up), uploads them, warms up, times the steps and prints the line (roofline and counters from the last step's own counters).
+--full adds, on the batch of the last timed step, what is checked and measured beside it: parity at the size that is timed (every record of that
+batch goes through the product's sink + SAM text and is compared with oracle/_ref/hisat2-align-s over the same reads, byte for byte:
+`parity_whole_batch`; a mismatch prints the line and fails the run — the reference binary is the checker, never inside a timed region), the
+host-to-host figure `pcie_inclusive`, the command line's parity sample, the reference's CPU baseline and the command line end to end.
 
 Workload at N=1 = BASELINE.json configs[2]'s shape: a linear index in the GRCh38 contig profile, 101 bp paired-end reads,
 --no-spliced-alignment.  The index is the reference builder's (oracle/_ref/hisat2-build-s) over a seeded uniform-random genome in
@@ -20,7 +23,7 @@ Workload at N=1 = BASELINE.json configs[2]'s shape: a linear index in the GRCh38
 .bench_cache/ in a writable tree).  --genome (or H2G_BENCH_GENOME) sets its size: by default 256 Mbp (0.4 GB resident), which a fresh checkout
 builds in under two minutes; GRCh38 size is --genome 3.1e9 (4.7 GB resident; the build takes 17-40 min, so stage it with tools/build_bench_index.py
 first).  A staged grch38sim<len>_* index of exactly the wanted size, else of at least it, is used when present; the size actually used is named in
-config.workload.  --extras adds the other legs: configs[1] (E. coli-size, single-end) as "ecoli_se", the graph and spliced legs and the micro-benchmarks;
+config.workload.  --extras (which implies --full) adds the other legs: configs[1] (E. coli-size, single-end) as "ecoli_se", the graph and spliced legs and the micro-benchmarks;
 they are skipped when the run is past H2G_BENCH_DEADLINE seconds (default 1150), the two companion legs with an index build of their own
 (repeat_pe, graph256_pe) when they would end past H2G_BENCH_BIG_DEADLINE (1250): both are measured by `bench.py --only-legs` /
 tools/queued_steps.py in profiles/ whether or not a run reaches them.
@@ -99,22 +102,11 @@ def headline_index(cache, want_total):
     H2G_BENCH_FALLBACK_GENOME (default 256 Mbp, ~80 s to build) genome of the same contig profile and the line says so in metric and config.
     A build stopped at its budget leaves a marker in the cache: a later run with no larger budget goes straight to the fallback genome, so the
     runs that share a cache run on the same index (what --dump-outputs compares) and none of them spends the budget again."""
-    import glob
     import build_bench_index as BB
-    staged = []
-    for f in glob.glob(os.path.join(cache, "grch38sim*_s%d.1.ht2" % BB.SEED)):
-        tot = int(os.path.basename(f)[len("grch38sim"):].split("_")[0])
-        if BB.have(BB.index_base(tot, cache)):
-            staged.append(tot)
-    if staged and max(staged) >= want_total:
-        tot = want_total if want_total in staged else max(staged)
+    tot = _staged_total(cache, want_total)
+    if tot is not None:
         return BB.index_base(tot, cache), tot, "staged"
-    budget = float(os.environ.get("H2G_BENCH_BUILD_BUDGET", "1250"))
-    marker = BB.index_base(want_total, cache) + ".over_budget"
-    try:
-        tried = float(open(marker).read())
-    except (OSError, ValueError):
-        tried = -1.0
+    budget, marker, tried = _build_budget(cache, want_total)
     if tried >= budget:
         why = "an earlier run's %d bp build passed its %.0f s budget on this box and was stopped (%s)" % (want_total, tried, os.path.basename(marker))
     else:
@@ -132,6 +124,139 @@ def headline_index(cache, want_total):
     t1 = time.time()
     base = BB.build(small, cache=cache)
     return base, small, "FALLBACK: %s; this index built in %.0f s" % (why, time.time() - t1)
+
+
+def default_genome():
+    """bases of the headline index when --genome is not given: H2G_BENCH_GENOME, else 256 Mbp"""
+    return float(os.environ.get("H2G_BENCH_GENOME", "256e6"))
+
+
+def stage_headline_index():
+    """__graft_entry__.build()'s last step: the index a run with the default --genome uses, put into bench_cache_dir() by headline_index (the
+    reference's builder, CPU work only), so that the benchmark's runs find it built -> (base, how it was obtained)"""
+    base, _, how = headline_index(bench_cache_dir(), int(default_genome()))
+    return base, how
+
+
+def _staged_total(cache, want_total):
+    """the size of the staged GRCh38-scale index headline_index takes (exactly `want_total`, else the largest above it), or None"""
+    import glob
+    import build_bench_index as BB
+    staged = []
+    for f in glob.glob(os.path.join(cache, "grch38sim*_s%d.1.ht2" % BB.SEED)):
+        tot = int(os.path.basename(f)[len("grch38sim"):].split("_")[0])
+        if BB.have(BB.index_base(tot, cache)):
+            staged.append(tot)
+    if staged and max(staged) >= want_total:
+        return want_total if want_total in staged else max(staged)
+    return None
+
+
+def _build_budget(cache, want_total):
+    """(budget s, over-budget marker path, the budget an earlier stopped build had or -1)"""
+    import build_bench_index as BB
+    budget = float(os.environ.get("H2G_BENCH_BUILD_BUDGET", "1250"))
+    marker = BB.index_base(want_total, cache) + ".over_budget"
+    try:
+        tried = float(open(marker).read())
+    except (OSError, ValueError):
+        tried = -1.0
+    return budget, marker, tried
+
+
+def expected_headline_total(cache, want_total):
+    """the genome size headline_index will return, known before it runs (it differs only when a build passes its budget in this run), so that the
+    reads can be made while the index is built"""
+    tot = _staged_total(cache, want_total)
+    if tot is not None:
+        return tot
+    budget, _, tried = _build_budget(cache, want_total)
+    small = int(float(os.environ.get("H2G_BENCH_FALLBACK_GENOME", "256e6")))
+    return small if tried >= budget and small < want_total else want_total
+
+
+_READS = {}     # what the read workers inherit at the fork: the genome, the batch shape and one shared buffer per batch
+
+
+def _make_batch(b):
+    """batch b's read pairs, exactly synth.make_pairs with the seed the batch has always had, written into its shared buffer; -> (b, packed names)"""
+    from hisat2_amd import api, synth
+    R = _READS
+    m1, m2 = synth.make_pairs(R["contigs"], R["npairs"], 101, SEED + 7 + 1000 * R["rank"] + 100003 * b, sub_rate=0.005)
+    out = np.frombuffer(R["bufs"][b], dtype=np.uint8).reshape(2, R["npairs"], 101)
+    out[0] = m1
+    out[1] = m2
+    # FASTA names = decimal ids (they feed genRandSeed, pat.h:55), in the packed form the C ABI takes
+    return b, api.Stream.pack_names([str(b * R["n_global"] + R["lo"] + i) for i in range(R["npairs"])])
+
+
+def _batch_worker(w, nworkers, nbatch, conn):
+    """read worker w: batches w, w + nworkers, ... in order, each answered on its pipe as (b, packed names) or (None, the error)"""
+    os.nice(10)          # when the index is being built beside the workers, the builder's threads go first and the workers fill what they leave idle
+    try:
+        for b in range(w, nbatch, nworkers):
+            conn.send(_make_batch(b))
+    except Exception:    # noqa: BLE001
+        import traceback
+        conn.send((None, traceback.format_exc()))
+    conn.close()
+
+
+class ReadBatches:
+    """The resident batches' read pairs, made by forked worker processes while this process goes on with the device, the index and the upload of the
+    batches already made (worker w makes batches w, w + workers, ...).  Iterating yields (b, m1, m2, packed names) for b = 0, 1, ... in order; m1 / m2
+    are views of batch b's shared buffer, which lives as long as they do.  Every worker is forked here, before the device is opened (they only run
+    numpy), and none later: a worker that fails or dies makes the iteration raise; nothing waits for it and nothing replaces it."""
+
+    def __init__(self, contigs, npairs, nbatch, n_global, lo, rank, workers):
+        import mmap
+        import multiprocessing as mp
+        _READS.update(contigs=contigs, npairs=npairs, n_global=n_global, lo=lo, rank=rank,
+                      bufs=[mmap.mmap(-1, max(1, 2 * npairs * 101)) for _ in range(nbatch)])     # anonymous MAP_SHARED: the workers write, this process reads
+        self.n, self.nbatch = npairs, nbatch
+        self.procs, self.conns = [], []
+        if workers > 1 and nbatch > 1:
+            ctx = mp.get_context("fork")
+            for w in range(min(workers, nbatch)):
+                here, there = ctx.Pipe(duplex=False)
+                p = ctx.Process(target=_batch_worker, args=(w, min(workers, nbatch), nbatch, there), daemon=True)
+                p.start()
+                there.close()                            # (so that a worker's death reads as EOF here)
+                self.procs.append(p)
+                self.conns.append(here)
+
+    def _result(self, b):
+        if not self.conns:
+            return _make_batch(b)
+        try:
+            got, packed = self.conns[b % len(self.conns)].recv()
+        except EOFError:
+            raise RuntimeError("bench.py: the worker making read batch %d ended without it (exit code %s)" % (b, self.procs[b % len(self.procs)].exitcode)) from None
+        if got is None:
+            raise RuntimeError("bench.py: the worker making read batch %d failed:\n%s" % (b, packed))
+        return got, packed
+
+    def __iter__(self):
+        try:
+            for b in range(self.nbatch):
+                got, packed = self._result(b)
+                m = np.frombuffer(_READS["bufs"][got], dtype=np.uint8, count=2 * self.n * 101).reshape(2, self.n, 101)
+                _READS["bufs"][got] = None               # the views own the buffer from here on
+                yield got, m[0], m[1], packed
+        finally:
+            self.close()
+
+    def close(self):
+        """stops the workers still running (after a failure elsewhere) and frees what is not handed out"""
+        for p in self.procs:
+            if p.is_alive():
+                p.terminate()
+        for p in self.procs:
+            p.join()
+        for c in self.conns:
+            c.close()
+        self.procs, self.conns = [], []
+        _READS.clear()
 
 
 def reference_pairs(base, m1, m2, opts, threads, sam_path=None, upto=None):
@@ -460,12 +585,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pairs", type=int, default=1_000_000, help="read pairs per GPU per step")
     ap.add_argument("--batches", type=int, default=10, help="distinct resident batches of --pairs pairs the timed steps walk over (1..16)")
-    ap.add_argument("--genome", type=float, default=float(os.environ.get("H2G_BENCH_GENOME", "256e6")),
+    ap.add_argument("--genome", type=float, default=default_genome(),
                     help="bases of the headline index (default 256e6; GRCh38 size: 3.1e9, best staged beforehand with tools/build_bench_index.py)")
     ap.add_argument("--strong", action="store_true", help="one global batch of --pairs split over the ranks instead of --pairs per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-whole-parity", action="store_true", help="skip the whole-batch device-vs-reference SAM comparison of each leg (the 3 000 / 20 000-pair command-line samples stay)")
-    ap.add_argument("--extras", action="store_true", help="also run the extra legs (E. coli SE, graph index, spliced, companions, micro-benchmarks: up to ~25 min more)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's measurement, also check and measure the rest on the same batch: whole-batch parity against the reference binary, "
+                         "the host-to-host figure (pcie_inclusive), the command line's parity sample, the reference's CPU baseline and the command line end to end")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the parity checks, the CPU baseline and the command line end to end (pcie_inclusive stays)")
+    ap.add_argument("--no-whole-parity", action="store_true", help="with --full: skip the whole-batch device-vs-reference SAM comparison of each leg (the 3 000 / 20 000-pair command-line samples stay)")
+    ap.add_argument("--extras", action="store_true", help="--full, and also run the extra legs (E. coli SE, graph index, spliced, companions, micro-benchmarks: up to ~25 min more)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (the default; overrides --extras)")
     ap.add_argument("--rank-queries", type=int, default=1 << 28)
     ap.add_argument("--only-legs", default="", help="comma-separated big legs (repeat_pe, graph256_pe) to run INSTEAD of the headline: prints {leg: ...} and exits")
@@ -477,6 +605,8 @@ def main():
     a = ap.parse_args()
     if not a.extras:
         a.no_extras = True
+    if not a.no_extras:
+        a.full = True
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.warmup < 0:
@@ -500,10 +630,30 @@ def main():
         return dry_run(a, torch, shard, world, rank)
     from hisat2_amd import api, synth
     import build_bench_index as BB
+    cache = bench_cache_dir()
+    want_total = int(a.genome)
+    # the global read set is N x pairs (weak scaling: per-GPU work fixed) or `pairs` (--strong); rank r owns the id range
+    # shard_range(r) of it — exactly what `-s/--skip -u/--upto` restarts of the command line do.  No data-path collective.
+    n_global = a.pairs if a.strong else a.pairs * world
+    lo, hi = shard.shard_range(n_global, rank, world)
+    npairs = hi - lo
+    # configs[2] is 10 M pairs: the timed region walks over `--batches` DISTINCT batches of --pairs pairs (default 10), all resident in HBM before it starts
+    # (h2g_stream_select_batch: read sets with result rows of their own on one stream), step i on batch i mod B — not one batch K times.  Batch b holds the global
+    # ids [b x n_global + lo, b x n_global + hi) of a read set of B x n_global pairs.
+    nbatch = max(1, min(int(a.batches), 16))
+    batches = None
+    if not a.only_legs:
+        # the reads are made in worker processes while this one opens the device and builds or loads the index (forked before the device is opened)
+        planned = expected_headline_total(cache, want_total)
+        batches = ReadBatches(BB.genome(planned), npairs, nbatch, n_global, lo, rank, max(1, BB.usable_cpus() // world))
+    def refuse(msg):                       # (the workers' queued batches are dropped, not made before the process may exit)
+        if batches is not None:
+            batches.close()
+        raise SystemExit(msg)
     if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
+        refuse("bench.py needs an MI355X: the hot path has no CPU fallback")
     if torch.cuda.device_count() < world or local >= torch.cuda.device_count():
-        raise SystemExit("bench.py: %d GPUs requested (--gpus / WORLD_SIZE), %d visible: one rank per device, no sharing" % (world, torch.cuda.device_count()))
+        refuse("bench.py: %d GPUs requested (--gpus / WORLD_SIZE), %d visible: one rank per device, no sharing" % (world, torch.cuda.device_count()))
     torch.cuda.set_device(local)
     dist = None
     if world > 1:
@@ -518,7 +668,6 @@ def main():
         # single-GPU items (they run at N = 1: SURVEY §8(d)) and would only keep N - 1 ranks waiting at the last barrier
         a.no_extras = True
         a.no_cpu_baseline = True
-    cache = bench_cache_dir()
     if a.only_legs:
         out = {}
         for name in a.only_legs.split(","):
@@ -527,7 +676,6 @@ def main():
             out[name]["leg_seconds"] = time.time() - t0
         print(json.dumps(out))
         return
-    want_total = int(a.genome)
     how = None
     if rank == 0:
         base, total, how = headline_index(cache, want_total)
@@ -535,37 +683,28 @@ def main():
         dist.barrier()
     if rank != 0:
         base, total, how = headline_index(cache, want_total)
-    contigs = BB.genome(total)
+    if total != planned:                   # a build passed its budget in this run: the reads come from the fallback genome, made here
+        batches.close()
+        batches = ReadBatches(BB.genome(total), npairs, nbatch, n_global, lo, rank, 1)
 
-    # the global read set is N x pairs (weak scaling: per-GPU work fixed) or `pairs` (--strong); rank r owns the id range
-    # shard_range(r) of it — exactly what `-s/--skip -u/--upto` restarts of the command line do.  No data-path collective.
-    n_global = a.pairs if a.strong else a.pairs * world
-    lo, hi = shard.shard_range(n_global, rank, world)
-    npairs = hi - lo
-    # configs[2] is 10 M pairs: the timed region walks over `--batches` DISTINCT batches of --pairs pairs (default 10), all resident in HBM before it starts
-    # (h2g_stream_select_batch: read sets with result rows of their own on one stream), step i on batch i mod B — not one batch K times.  Batch b holds the global
-    # ids [b x n_global + lo, b x n_global + hi) of a read set of B x n_global pairs.
-    nbatch = max(1, min(int(a.batches), 16))
     ix = api.Index(base, device=local)
     st = api.Stream(ix, max_reads=npairs, max_bases=npairs * 101)
     last_b = (a.warmup + a.steps - 1) % nbatch                     # the batch of the last timed step: the one whose records the parity check reads
     t_upload = 0.0
-    for b in range(nbatch):
-        bm1, bm2 = synth.make_pairs(contigs, npairs, 101, SEED + 7 + 1000 * rank + 100003 * b, sub_rate=0.005)
+    for b, bm1, bm2, bnames in batches:
         bc1, bo1 = synth.flatten_reads(bm1)
         bc2, bo2 = synth.flatten_reads(bm2)
-        bnames = [str(b * n_global + lo + i) for i in range(npairs)]   # FASTA names = decimal ids (they feed genRandSeed, pat.h:55)
         st.select_batch(b)
         t_up0 = time.perf_counter()
         st.set_reads(bc1, bo1); st.set_read_names(bnames); st.set_mates(bc2, bo2, bnames)   # inputs resident in HBM before the timed region
         t_upload = time.perf_counter() - t_up0
         if b == last_b:
-            m1, m2, c1, o1, c2, o2, names, id0 = bm1, bm2, bc1, bo1, bc2, bo2, bnames, b * n_global + lo
+            m1, m2, c1, o1, c2, o2, id0 = bm1, bm2, bc1, bo1, bc2, bo2, b * n_global + lo
         if b == 0 and a.warmup > 0:
             # the first of the W warm-up steps runs here, on batch 0, before the other batches are selected: a stream's first run allocates its pools and this batch's
             # result rows, and a batch selected afterwards gets rows of the same size at selection (h2g_stream_select_batch) — nothing is allocated inside the timed region
             st.align_pairs_run(st.align_params()); st.sync()
-    del bm1, bm2, bc1, bc2, bnames
+    del bm1, bm2, bc1, bc2, bnames, batches
     params = st.align_params()
 
     def barrier():
@@ -650,97 +789,99 @@ def main():
         })
         if dumped is not None:
             out["dump_outputs"] = dumped
-        exe = os.path.join(REF, "hisat2-align-s")
-        cli = os.path.join(ROOT, "hisat2_amd", "hisat2-align-amd")
-        tmp = tempfile.mkdtemp(prefix="h2bench")
-        f1, f2 = os.path.join(tmp, "1.fa"), os.path.join(tmp, "2.fa")
         parity_failed = False
-        if os.path.exists(exe) and not a.no_cpu_baseline:
-            synth.write_reads_fasta(f1, m1, start_id=id0); synth.write_reads_fasta(f2, m2, start_id=id0)
-            if not a.no_whole_parity:
-                # every record of the batch the timed steps ran on (the stream still holds the last step's results) against the reference binary
-                out["parity_whole_batch"] = whole_batch_parity(api, base, st, c1, o1, c2, o2, names, int(params.khits), f1, f2, tmp=tmp)
-                parity_failed = not out["parity_whole_batch"].get("digest_equal", False)
-        if world > 1:
-            out["single_gpu_items"] = "cpu_baseline, parity_whole_batch, cli_end_to_end and the companion legs are measured by the N = 1 run"
-        # host buffers in, host buffers out: upload + both passes + compact fetch of the report events (never `value`)
-        pool = api.PinnedPool()
-        pc1 = pool.array("c1", c1.size); pc1[:] = c1
-        pc2 = pool.array("c2", c2.size); pc2[:] = c2
-        st.align_pairs_fetch_compact(pinned=pool)                  # (the page-locked result buffers exist before the timed pass, as a streaming caller's do)
-        packed = st.pack_names(names)                              # (name bytes + offsets, the form the C ABI takes: a parser's output, not part of the transfer)
-        reps = []
-        for _ in range(3):
-            t1 = time.perf_counter()
-            st.set_reads(pc1, o1); st.set_read_names(packed); st.set_mates(pc2, o2, packed)
-            t_up = time.perf_counter() - t1
-            st.align_pairs_run(params)
-            pres, pr1, pb1, pr2, pb2 = st.align_pairs_fetch_compact(pinned=pool)
-            reps.append((time.perf_counter() - t1, t_up))
-        t_e2e, t_up = sorted(reps)[1]
-        out["pcie_inclusive"] = {"pairs": npairs, "seconds": t_e2e, "reads_per_s": 2 * npairs / t_e2e, "upload_s": t_up, "upload_s_first_pageable": t_upload,
-                                 "compact_record_bytes": int(pb1[-1] + pb2[-1]),
-                                 "note": "h2g_set_reads + h2g_set_read_names + h2g_set_mates + h2g_align_pairs_run + h2g_align_pairs_fetch_compact (40 B + 12 B per edit held "
-                                         "per record instead of 424 B), base codes and results in page-locked host memory (h2g_host_alloc), one host thread, nothing overlapped: median of 3"}
-        del pres, pr1, pr2
-        pool.close()
-        if os.path.exists(exe) and not a.no_cpu_baseline:
-            ns = npairs
-            # parity on THIS config: the first pairs through the whole drop-in path (reads file -> hisat2-align-amd -> SAM) must be
-            # byte-identical to the reference's SAM
-            nv = min(3000, ns)
-            ref_sam, amd_sam = os.path.join(tmp, "ref.sam"), os.path.join(tmp, "amd.sam")
-            reference_pairs(base, f1, f2, [], 1, ref_sam, upto=nv)
-            r = subprocess.run([cli, "-f", "--no-spliced-alignment", "-p", "8", "-x", base, "-1", f1, "-2", f2, "-u", str(nv), "-S", amd_sam,
-                                "--h2g-stats", os.path.join(tmp, "stats.json")], capture_output=True, text=True)
-            if r.returncode != 0:
-                raise SystemExit("bench.py: hisat2-align-amd failed on the parity sample (rc %d): " % r.returncode + r.stderr[:1500] + " ... " + r.stderr[-300:])
-            wa, wb = body(amd_sam), body(ref_sam)
-            ndiff = sum(1 for x, y in zip(wa, wb) if x != y) + abs(len(wa) - len(wb))
-            out["parity"] = {"pairs_checked": nv, "sam_lines": len(wb), "sam_lines_differing": ndiff,
-                             "against": "oracle/_ref/hisat2-align-s -p 1 (complete SAM lines, byte for byte)", **json.load(open(os.path.join(tmp, "stats.json")))}
-            if ndiff:
-                raise SystemExit(f"bench.py: {ndiff} SAM lines of the parity sample differ from the reference")
-            # the reference on this box's host cores, same index, same reads: thread counts 1 .. nproc, each on as many pairs
-            # as ~6 s of work at that width; wall time minus the index load (a `-u 1` run at the same width); median of 3 at the best width
-            ncpu = os.cpu_count() or 1
-            widths = sorted({t for t in (1, 16, 64, 128, ncpu) if t <= ncpu})
-            last_rate = 12_000.0                         # pairs/s guess for sizing the first sample; then what the previous width measured
-            scan, best = {}, None
-            for pth in widths:
-                if time.time() - t_start > deadline:
-                    break
-                # ~5 s of work at the previous width's rate (the reference does not speed up beyond a few dozen threads on this input:
-                # its read-batch and output locks, pat.cpp:76-107 / outq.cpp — the scan shows it)
-                nsamp = int(min(ns, max(20_000, 5.0 * last_rate * (4 if pth == 16 else 1))))
-                t_load = reference_pairs(base, f1, f2, [], pth, upto=1)
-                t_run = max(reference_pairs(base, f1, f2, [], pth, upto=nsamp) - t_load, 1e-6)
-                rate = 2 * nsamp / t_run
-                scan[str(pth)] = {"reads_per_s": rate, "reads_per_s_per_core": rate / pth, "pairs": nsamp, "seconds": t_run, "index_load_s": t_load}
-                last_rate = max(2_000.0, nsamp / t_run)
-                if best is None or rate > best[0]:
-                    best = (rate, pth, t_run, t_load, nsamp)
-            reps = [best[0]]
-            for _ in range(2):
-                if time.time() - t_start > deadline:
-                    break
-                t_run = max(reference_pairs(base, f1, f2, [], best[1], upto=best[4]) - best[3], 1e-6)
-                reps.append(2 * best[4] / t_run)
-            med = sorted(reps)[len(reps) // 2]
-            out["cpu_baseline"] = {"value": med, "unit": "reads/s", "cores": best[1], "kind": "reference", "host_cpus": ncpu, "host_cpu_limits": host_cpu_limits(),
-                                   "reads_per_s_per_core_at_1_thread": scan.get("1", {}).get("reads_per_s_per_core"), "repeats_at_best_width": reps,
-                                   "threads_scan": scan,
-                                   "sample": f"first {best[4]} pairs of the bench batch, oracle/_ref/hisat2-align-s -p {best[1]} --no-spliced-alignment -S /dev/null on the same "
-                                             f"{total} bp index, {best[2]:.1f} s of alignment (index load {best[3]:.1f} s timed by a -u 1 run and subtracted); median of {len(reps)}; "
-                                             "every width's own sample is in threads_scan"}
-            # end to end on the same sample: reads files -> SAM file, both programs
-            t0c = time.perf_counter()
-            r = subprocess.run([cli, "-f", "--no-spliced-alignment", "-p", "32", "-x", base, "-1", f1, "-2", f2, "-S", os.path.join(tmp, "e2e.sam")],
-                               capture_output=True, text=True, env=dict(os.environ, H2G_CLI_TIMING="1"))
-            t_cli = time.perf_counter() - t0c
-            out["cli_end_to_end"] = {"pairs": ns, "wall_s": t_cli, "reads_per_s_wall": 2 * ns / t_cli, "host_threads": 32,
-                                     "timing": r.stderr.strip().splitlines()[-1] if r.returncode == 0 and r.stderr.strip() else r.stderr[-300:]}
-        shutil.rmtree(tmp, ignore_errors=True)
+        if a.full:                                 # the rest of the measurement and the checks against the reference, on the batch of the last timed step
+            exe = os.path.join(REF, "hisat2-align-s")
+            cli = os.path.join(ROOT, "hisat2_amd", "hisat2-align-amd")
+            tmp = tempfile.mkdtemp(prefix="h2bench")
+            f1, f2 = os.path.join(tmp, "1.fa"), os.path.join(tmp, "2.fa")
+            names = [str(id0 + i) for i in range(npairs)]
+            if os.path.exists(exe) and not a.no_cpu_baseline:
+                synth.write_reads_fasta(f1, m1, start_id=id0); synth.write_reads_fasta(f2, m2, start_id=id0)
+                if not a.no_whole_parity:
+                    # every record of the batch the timed steps ran on (the stream still holds the last step's results) against the reference binary
+                    out["parity_whole_batch"] = whole_batch_parity(api, base, st, c1, o1, c2, o2, names, int(params.khits), f1, f2, tmp=tmp)
+                    parity_failed = not out["parity_whole_batch"].get("digest_equal", False)
+            if world > 1:
+                out["single_gpu_items"] = "cpu_baseline, parity_whole_batch, cli_end_to_end and the companion legs are measured by the N = 1 run"
+            # host buffers in, host buffers out: upload + both passes + compact fetch of the report events (never `value`)
+            pool = api.PinnedPool()
+            pc1 = pool.array("c1", c1.size); pc1[:] = c1
+            pc2 = pool.array("c2", c2.size); pc2[:] = c2
+            st.align_pairs_fetch_compact(pinned=pool)                  # (the page-locked result buffers exist before the timed pass, as a streaming caller's do)
+            packed = st.pack_names(names)                              # (name bytes + offsets, the form the C ABI takes: a parser's output, not part of the transfer)
+            reps = []
+            for _ in range(3):
+                t1 = time.perf_counter()
+                st.set_reads(pc1, o1); st.set_read_names(packed); st.set_mates(pc2, o2, packed)
+                t_up = time.perf_counter() - t1
+                st.align_pairs_run(params)
+                pres, pr1, pb1, pr2, pb2 = st.align_pairs_fetch_compact(pinned=pool)
+                reps.append((time.perf_counter() - t1, t_up))
+            t_e2e, t_up = sorted(reps)[1]
+            out["pcie_inclusive"] = {"pairs": npairs, "seconds": t_e2e, "reads_per_s": 2 * npairs / t_e2e, "upload_s": t_up, "upload_s_first_pageable": t_upload,
+                                     "compact_record_bytes": int(pb1[-1] + pb2[-1]),
+                                     "note": "h2g_set_reads + h2g_set_read_names + h2g_set_mates + h2g_align_pairs_run + h2g_align_pairs_fetch_compact (40 B + 12 B per edit held "
+                                             "per record instead of 424 B), base codes and results in page-locked host memory (h2g_host_alloc), one host thread, nothing overlapped: median of 3"}
+            del pres, pr1, pr2
+            pool.close()
+            if os.path.exists(exe) and not a.no_cpu_baseline:
+                ns = npairs
+                # parity on THIS config: the first pairs through the whole drop-in path (reads file -> hisat2-align-amd -> SAM) must be
+                # byte-identical to the reference's SAM
+                nv = min(3000, ns)
+                ref_sam, amd_sam = os.path.join(tmp, "ref.sam"), os.path.join(tmp, "amd.sam")
+                reference_pairs(base, f1, f2, [], 1, ref_sam, upto=nv)
+                r = subprocess.run([cli, "-f", "--no-spliced-alignment", "-p", "8", "-x", base, "-1", f1, "-2", f2, "-u", str(nv), "-S", amd_sam,
+                                    "--h2g-stats", os.path.join(tmp, "stats.json")], capture_output=True, text=True)
+                if r.returncode != 0:
+                    raise SystemExit("bench.py: hisat2-align-amd failed on the parity sample (rc %d): " % r.returncode + r.stderr[:1500] + " ... " + r.stderr[-300:])
+                wa, wb = body(amd_sam), body(ref_sam)
+                ndiff = sum(1 for x, y in zip(wa, wb) if x != y) + abs(len(wa) - len(wb))
+                out["parity"] = {"pairs_checked": nv, "sam_lines": len(wb), "sam_lines_differing": ndiff,
+                                 "against": "oracle/_ref/hisat2-align-s -p 1 (complete SAM lines, byte for byte)", **json.load(open(os.path.join(tmp, "stats.json")))}
+                if ndiff:
+                    raise SystemExit(f"bench.py: {ndiff} SAM lines of the parity sample differ from the reference")
+                # the reference on this box's host cores, same index, same reads: thread counts 1 .. nproc, each on as many pairs
+                # as ~6 s of work at that width; wall time minus the index load (a `-u 1` run at the same width); median of 3 at the best width
+                ncpu = os.cpu_count() or 1
+                widths = sorted({t for t in (1, 16, 64, 128, ncpu) if t <= ncpu})
+                last_rate = 12_000.0                         # pairs/s guess for sizing the first sample; then what the previous width measured
+                scan, best = {}, None
+                for pth in widths:
+                    if time.time() - t_start > deadline:
+                        break
+                    # ~5 s of work at the previous width's rate (the reference does not speed up beyond a few dozen threads on this input:
+                    # its read-batch and output locks, pat.cpp:76-107 / outq.cpp — the scan shows it)
+                    nsamp = int(min(ns, max(20_000, 5.0 * last_rate * (4 if pth == 16 else 1))))
+                    t_load = reference_pairs(base, f1, f2, [], pth, upto=1)
+                    t_run = max(reference_pairs(base, f1, f2, [], pth, upto=nsamp) - t_load, 1e-6)
+                    rate = 2 * nsamp / t_run
+                    scan[str(pth)] = {"reads_per_s": rate, "reads_per_s_per_core": rate / pth, "pairs": nsamp, "seconds": t_run, "index_load_s": t_load}
+                    last_rate = max(2_000.0, nsamp / t_run)
+                    if best is None or rate > best[0]:
+                        best = (rate, pth, t_run, t_load, nsamp)
+                reps = [best[0]]
+                for _ in range(2):
+                    if time.time() - t_start > deadline:
+                        break
+                    t_run = max(reference_pairs(base, f1, f2, [], best[1], upto=best[4]) - best[3], 1e-6)
+                    reps.append(2 * best[4] / t_run)
+                med = sorted(reps)[len(reps) // 2]
+                out["cpu_baseline"] = {"value": med, "unit": "reads/s", "cores": best[1], "kind": "reference", "host_cpus": ncpu, "host_cpu_limits": host_cpu_limits(),
+                                       "reads_per_s_per_core_at_1_thread": scan.get("1", {}).get("reads_per_s_per_core"), "repeats_at_best_width": reps,
+                                       "threads_scan": scan,
+                                       "sample": f"first {best[4]} pairs of the bench batch, oracle/_ref/hisat2-align-s -p {best[1]} --no-spliced-alignment -S /dev/null on the same "
+                                                 f"{total} bp index, {best[2]:.1f} s of alignment (index load {best[3]:.1f} s timed by a -u 1 run and subtracted); median of {len(reps)}; "
+                                                 "every width's own sample is in threads_scan"}
+                # end to end on the same sample: reads files -> SAM file, both programs
+                t0c = time.perf_counter()
+                r = subprocess.run([cli, "-f", "--no-spliced-alignment", "-p", "32", "-x", base, "-1", f1, "-2", f2, "-S", os.path.join(tmp, "e2e.sam")],
+                                   capture_output=True, text=True, env=dict(os.environ, H2G_CLI_TIMING="1"))
+                t_cli = time.perf_counter() - t0c
+                out["cli_end_to_end"] = {"pairs": ns, "wall_s": t_cli, "reads_per_s_wall": 2 * ns / t_cli, "host_threads": 32,
+                                         "timing": r.stderr.strip().splitlines()[-1] if r.returncode == 0 and r.stderr.strip() else r.stderr[-300:]}
+            shutil.rmtree(tmp, ignore_errors=True)
         st.close()
         if not a.no_extras and time.time() - t_start > deadline:
             out["extras_skipped"] = "past H2G_BENCH_DEADLINE = %.0f s (index build included)" % deadline

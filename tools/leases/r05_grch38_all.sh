@@ -10,10 +10,10 @@ T0=$(date +%s)
 python tools/build_bench_index.py 3.1e9 > $OUT/build.log 2>&1; tail -1 $OUT/build.log | cut -c1-300
 echo "index after $(( $(date +%s) - T0 )) s" | tee $OUT/timeline.txt
 # (1)
-timeout 900 python bench.py --no-extras --steps 20 --warmup 5 > $OUT/bench_headline.json 2> $OUT/bench_headline.err; echo "bench rc $?"; head -c 2500 $OUT/bench_headline.json; echo
+timeout 900 python bench.py --full --no-extras --steps 20 --warmup 5 > $OUT/bench_headline.json 2> $OUT/bench_headline.err; echo "bench rc $?"; head -c 2500 $OUT/bench_headline.json; echo
 echo "headline after $(( $(date +%s) - T0 )) s" | tee -a $OUT/timeline.txt
 # (2)
-CMD="python bench.py --no-extras --no-cpu-baseline --steps 5 --warmup 2"
+CMD="python bench.py --full --no-extras --no-cpu-baseline --steps 5 --warmup 2"
 rm -rf /tmp/bp_trace
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/bp_trace -- $CMD > $OUT/bench_traced.json 2> /tmp/bp_trace.err
 python tools/rocpd_summary.py /tmp/bp_trace > $OUT/bench_trace.txt 2>&1; head -8 $OUT/bench_trace.txt | cut -c1-200
@@ -47,7 +47,7 @@ try:
            "calibration": "FETCH_SIZE counts fabric read requests x 64 B: exact for the scattered 64 B sides (k_rank_v0 at 2^28 queries: 17.51 GB reported for 17.18 GB of sides + 1.34 GB of query input), "
                           "half for 128 B requests (k_rank_g0: 18.43 GB reported for 34.36 + 1.34 GB) - profiles/r04_rank_pmc_*.txt.  traffic = FETCH_SIZE + WRITE_SIZE (every request at 64 B: a lower bound, "
                           "exact for the index lines); upper bound = 2 x FETCH_SIZE + WRITE_SIZE (every read request a 128 B one)",
-           "source": "profiles/r05_bench_pmc_FETCH_SIZE.txt + r05_bench_pmc_WRITE_SIZE.txt: rocprofv3 --pmc, separate passes of `python bench.py --no-extras --no-cpu-baseline --steps 5 --warmup 2`, mean per launch",
+           "source": "profiles/r05_bench_pmc_FETCH_SIZE.txt + r05_bench_pmc_WRITE_SIZE.txt: rocprofv3 --pmc, separate passes of `python bench.py --full --no-extras --no-cpu-baseline --steps 5 --warmup 2`, mean per launch",
            "note": "taken in the one GRCh38-size lease of round 5 (tools/r05_grch38_all.sh) on the kernel sources with this hash"}
     json.dump(rec, open(OUT + "/pmc_traffic.json", "w"), indent=1)
     print(json.dumps(rec)[:700])

@@ -8,12 +8,12 @@ export PYTHONPATH=$PWD:$PWD/tests:$PWD/tools
 OUT=gpurun_out/r06_grch38; mkdir -p $OUT
 T0=$(date +%s)
 # (0) bench.py's loop over 10 distinct batches on a fresh box, small genome: 20 / 5 must read the steady state now that a batch's rows are written at selection
-H2G_BENCH_GENOME=256e6 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_256_first.json 2> $OUT/bench_256_first.err
+H2G_BENCH_GENOME=256e6 timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_256_first.json 2> $OUT/bench_256_first.err
 python -c "
 import json; d = json.loads(open('$OUT/bench_256_first.json').read().strip().splitlines()[-1]); print('256 Mbp 20/5:', d['ms_per_step'], d['roofline']['kernel_ms'])"
 echo "check after $(( $(date +%s) - T0 )) s" | tee $OUT/timeline.txt
 # (1) the DRIVER's command: index build, headline, parity, cpu baseline, every extra leg, the repeat-structured companion at the metric's size while time lasts
-timeout 2400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc $?"; head -c 3000 $OUT/bench_driver.json; echo
+timeout 2400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc $?"; head -c 3000 $OUT/bench_driver.json; echo
 echo "driver command after $(( $(date +%s) - T0 )) s" | tee -a $OUT/timeline.txt
 python - <<'PY'
 import json
@@ -30,7 +30,7 @@ except Exception as e:
     print("driver line:", repr(e))
 PY
 # (2)
-CMD="python bench.py --no-extras --no-cpu-baseline --steps 5 --warmup 2"
+CMD="python bench.py --full --no-extras --no-cpu-baseline --steps 5 --warmup 2"
 rm -rf /tmp/bp_trace
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/bp_trace -- $CMD > $OUT/bench_traced.json 2> /tmp/bp_trace.err
 python tools/rocpd_summary.py /tmp/bp_trace > $OUT/bench_trace.txt 2>&1; head -8 $OUT/bench_trace.txt | cut -c1-200
@@ -64,7 +64,7 @@ try:
            "calibration": "FETCH_SIZE counts fabric read requests x 64 B: exact for the scattered 64 B sides (k_rank_v0 at 2^28 queries: 17.51 GB reported for 17.18 GB of sides + 1.34 GB of query input), "
                           "half for 128 B requests (k_rank_g0: 18.43 GB reported for 34.36 + 1.34 GB) - profiles/r04_rank_pmc_*.txt.  traffic = FETCH_SIZE + WRITE_SIZE (every request at 64 B: a lower bound, "
                           "exact for the index lines); upper bound = 2 x FETCH_SIZE + WRITE_SIZE (every read request a 128 B one)",
-           "source": "profiles/r06_bench_pmc_FETCH_SIZE.txt + r06_bench_pmc_WRITE_SIZE.txt: rocprofv3 --pmc, separate passes of `python bench.py --no-extras --no-cpu-baseline --steps 5 --warmup 2`, mean per launch",
+           "source": "profiles/r06_bench_pmc_FETCH_SIZE.txt + r06_bench_pmc_WRITE_SIZE.txt: rocprofv3 --pmc, separate passes of `python bench.py --full --no-extras --no-cpu-baseline --steps 5 --warmup 2`, mean per launch",
            "note": "taken in the one GRCh38-size lease of round 6 (tools/r06_grch38_all.sh) on the kernel sources with this hash"}
     json.dump(rec, open(OUT + "/pmc_traffic.json", "w"), indent=1)
     print(json.dumps(rec)[:700])

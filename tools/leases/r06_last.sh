@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 export PYTHONPATH=$PWD:$PWD/tests:$PWD/tools
 OUT=gpurun_out/r06_last; mkdir -p $OUT
 T0=$(date +%s)
-timeout 2400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc $? after $(( $(date +%s) - T0 )) s"
+timeout 2400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc $? after $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 try:

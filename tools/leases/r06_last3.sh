@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 export PYTHONPATH=$PWD:$PWD/tests:$PWD/tools
 OUT=gpurun_out/r06_last3; mkdir -p $OUT
 T0=$(date +%s)
-H2G_BENCH_GENOME=1.5e9 H2G_BENCH_HARD_LIMIT=${HARD:-1350} timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_1500Mbp.json 2> $OUT/bench_1500Mbp.err; echo "bench rc $? after $(( $(date +%s) - T0 )) s"
+H2G_BENCH_GENOME=1.5e9 H2G_BENCH_HARD_LIMIT=${HARD:-1350} timeout 1700 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_1500Mbp.json 2> $OUT/bench_1500Mbp.err; echo "bench rc $? after $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06_last3/bench_1500Mbp.json").read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for lib in new gnosink gos; do
 done
 unset H2G_LIB
 echo "graph after $(( $(date +%s) - T0 )) s"
-H2G_BENCH_GENOME=256e6 timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras > $OUT/bench_256Mbp.json 2> $OUT/bench_256Mbp.err; python - <<'PY'
+H2G_BENCH_GENOME=256e6 timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras > $OUT/bench_256Mbp.json 2> $OUT/bench_256Mbp.err; python - <<'PY'
 import json
 try:
     d = json.loads(open("gpurun_out/r06_d/bench_256Mbp.json").read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ T0=$(date +%s)
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1; tail -4 $OUT/gputests.log | cut -c1-300
 echo "tests after $(( $(date +%s) - T0 )) s"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-H2G_BENCH_GENOME=256e6 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_256.json 2> $OUT/bench_256.err
+H2G_BENCH_GENOME=256e6 timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_256.json 2> $OUT/bench_256.err
 python -c "
 import json; d = json.loads(open('$OUT/bench_256.json').read().strip().splitlines()[-1]); r = d['roofline']; print('256 Mbp 20/5:', d['ms_per_step'], d['value'], r['kernel_ms'], r['frac'], r.get('drain_launch'), r['pairs_handed_on'])"
 tail -3 $OUT/bench_256.err
