@@ -401,7 +401,7 @@ EXPORTS = [
     "h2g_rank_bench", "h2g_rank_bench_synth", "h2g_rank_bench_synth_sample", "h2g_fm_search", "h2g_sa_resolve", "h2g_extend",
     "h2g_seed_params_init", "h2g_seed_extend_run", "h2g_seed_extend_fetch", "h2g_get_counters",
     "h2g_device_count", "h2g_ext_search", "h2g_local_index_of", "h2g_align_params_init", "h2g_align_params_presets", "h2g_set_read_names", "h2g_align_run", "h2g_align_fetch",
-    "h2g_set_mates", "h2g_set_read_seeds", "h2g_sam_set_n_ceil", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
+    "h2g_set_mates", "h2g_set_read_seeds", "h2g_set_read_filter", "h2g_set_read_ids", "h2g_sam_set_read_ids", "h2g_sam_set_read_filter", "h2g_sam_set_record_ends", "h2g_sam_set_n_ceil", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
 ]
@@ -469,6 +469,8 @@ def lib():
     L.h2g_align_fetch.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_set_mates.argtypes = [vp, vp, vp, vp, C.c_char_p, vp, C.c_size_t]
     L.h2g_set_read_seeds.argtypes = [vp, vp, vp, C.c_size_t]
+    L.h2g_set_read_filter.argtypes = [vp, vp, vp]
+    L.h2g_set_read_ids.argtypes = [vp, vp]
     L.h2g_align_pairs_run.argtypes = [vp, P(AlignParams)]
     L.h2g_align_pairs_fetch.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
@@ -713,6 +715,22 @@ class Stream:
         s1 = np.ascontiguousarray(seeds1, dtype=np.uint32)
         s2 = None if seeds2 is None else np.ascontiguousarray(seeds2, dtype=np.uint32)
         _chk(lib().h2g_set_read_seeds(self.h, s1.ctypes.data, None if s2 is None else s2.ctypes.data, len(s1)), "h2g_set_read_seeds")
+
+    def set_read_ids(self, ids):
+        """explicit read ids (Read::rdid) of the resident batch's reads in place of first_read_id + index; None clears them"""
+        a = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+        if a is not None and len(a) != self.n_reads:
+            raise ValueError("one id per read of the resident batch")
+        _chk(lib().h2g_set_read_ids(self.h, None if a is None else a.ctypes.data), "h2g_set_read_ids")
+
+    def set_read_filter(self, pass1, pass2=None):
+        """--qc-filter bytes of the resident batch's reads (mate 1, and mate 2 for pairs): 0 = the read is not aligned; None = that set passes; both None clears them"""
+        p1 = None if pass1 is None else np.ascontiguousarray(pass1, dtype=np.uint8)
+        p2 = None if pass2 is None else np.ascontiguousarray(pass2, dtype=np.uint8)
+        for p in (p1, p2):
+            if p is not None and len(p) != self.n_reads:
+                raise ValueError("one filter byte per read of the resident batch")
+        _chk(lib().h2g_set_read_filter(self.h, None if p1 is None else p1.ctypes.data, None if p2 is None else p2.ctypes.data), "h2g_set_read_filter")
 
     def set_mates(self, codes2, offs2, qnames2, quals2=None):
         codes2 = np.ascontiguousarray(codes2, dtype=np.uint8)

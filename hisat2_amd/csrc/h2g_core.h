@@ -88,6 +88,8 @@ struct DReads {
 	const uint32_t* pk = nullptr;
 	uint32_t pk_stride = 0, pk_read = 0xffffffffu;
 	const uint32_t* seeds = nullptr;   // [n] explicit PRNG seeds of this read set (h2g_set_read_seeds, --non-deterministic); nullptr: genRandSeed
+	const uint32_t* ids = nullptr;     // [n] Read::rdid of every read (h2g_set_read_ids: a batch whose reads are not consecutive records); nullptr: rdid_base + index
+	const uint8_t*  qc = nullptr;      // [n] --qc-filter (h2g_set_read_filter): 0 = the read failed its QSEQ filter and is not aligned; nullptr: all pass
 };
 #define H2G_PK_WORDS 8           // 128 bases (longer reads are read from HBM base by base)
 #define H2G_PK_MAXLEN (H2G_PK_WORDS * 16)

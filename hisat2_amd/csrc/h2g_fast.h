@@ -826,6 +826,8 @@ H2G_HD void fast_begin(const FCtx& C, FState& S, uint32_t read, bool paired, boo
 	S.ro0 = C.rd[0].offs[read]; S.ro1 = C.rd[1].offs[read];                     // (unpaired: rd[1] is rd[0])
 	const uint32_t len0 = C.rd[0].offs[read + 1] - S.ro0, len1 = C.rd[1].offs[read + 1] - S.ro1;
 	if(!packed_ok || len0 < 32 || len0 > 128 || (paired && (len1 < 32 || len1 > 128))) { S.pc = FPC_BAIL; S.bail = FB_INPUT; return; }
+	// --qc-filter (h2g_set_read_filter: both read sets carry the bytes, or neither): a read or pair with a filtered mate is the general machine's
+	if(const uint8_t* qc0 = C.rd[0].qc) if(!qc0[read] || (paired && !C.rd[1].qc[read])) { S.pc = FPC_BAIL; S.bail = FB_INPUT; return; }
 	S.rl0 = len0; S.rl1 = len1;
 	// no N, length >= 2: both filters pass whatever --n-ceil says (read_passes_filters: nceil_value is never negative)
 	Rng rnd;

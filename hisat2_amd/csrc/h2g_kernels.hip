@@ -103,6 +103,9 @@ struct BatchCtx {
 	PairOut* d_pout = nullptr; h2g_alnres* d_paln[2] = {nullptr, nullptr}; size_t paln_alloc = 0; uint32_t pair_slots = 0;
 	// explicit PRNG seeds (h2g_set_read_seeds): mate 1's at [0, max_reads), mate 2's at [max_reads, 2 max_reads); a run reads them when has_seeds
 	uint32_t* d_seeds = nullptr; bool has_seeds = false, has_seeds2 = false;
+	// --qc-filter bytes (h2g_set_read_filter), laid out like the seeds: 1 = the read passes; a run reads them when has_qc
+	uint8_t* d_qc = nullptr; bool has_qc = false;
+	uint32_t* d_ids = nullptr; bool has_ids = false;      // explicit read ids (h2g_set_read_ids)
 };
 struct h2g_stream {
 	h2g_index* ix = nullptr;
@@ -626,6 +629,8 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
 		(void)hipFree(B.d_quals2); (void)hipFree(B.d_names2); (void)hipFree(B.d_name_offs2); (void)hipFree(B.d_rout); (void)hipFree(B.d_aln); (void)hipFree(B.d_pout); (void)hipFree(B.d_paln[0]); (void)hipFree(B.d_paln[1]);
 		(void)hipFree(B.d_seeds);
+		(void)hipFree(B.d_qc);
+		(void)hipFree(B.d_ids);
 	}
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
 	for(int i = 0; i < 12; i++) (void)hipEventDestroy(s->ev[i]);
@@ -724,6 +729,8 @@ extern "C" h2g_status h2g_set_reads(h2g_stream* s, const uint8_t* codes, const u
 	B.has_names = false;
 	B.has_mates = false;
 	B.has_seeds = B.has_seeds2 = false;
+	B.has_qc = false;
+	B.has_ids = false;
 	s->ledits_touched = 0;            // (long-edit lists of the batch this one replaces are nobody's any more)
 	return H2G_OK;
 }
@@ -1950,6 +1957,38 @@ extern "C" h2g_status h2g_set_read_seeds(h2g_stream* s, const uint32_t* seeds1, 
 	return H2G_OK;
 }
 
+extern "C" h2g_status h2g_set_read_ids(h2g_stream* s, const uint32_t* ids) {
+	if(s) HIPCHK(sync_all(s));        // (a run of the previous ids may still read the buffer)
+	if(!s) return H2G_ERR_ARG;
+	BatchCtx& B = s->cur();
+	if(!ids) { B.has_ids = false; return H2G_OK; }
+	const size_t n = B.n_reads;
+	if(n == 0 || n > s->max_reads) return H2G_ERR_ARG;
+	HIPCHK(hipSetDevice(s->ix->device));
+	if(!B.d_ids) HIPCHK(hipMalloc((void**)&B.d_ids, s->max_reads * sizeof(uint32_t)));
+	HIPCHK(hipMemcpyAsync(B.d_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
+	HIPCHK(sync_all(s));
+	B.has_ids = true;
+	return H2G_OK;
+}
+
+extern "C" h2g_status h2g_set_read_filter(h2g_stream* s, const uint8_t* pass1, const uint8_t* pass2) {
+	if(s) HIPCHK(sync_all(s));        // (a run of the previous bytes may still read the buffer)
+	if(!s) return H2G_ERR_ARG;
+	BatchCtx& B = s->cur();
+	if(!pass1 && !pass2) { B.has_qc = false; return H2G_OK; }
+	const size_t n = B.n_reads;
+	if(n == 0 || n > s->max_reads) return H2G_ERR_ARG;
+	HIPCHK(hipSetDevice(s->ix->device));
+	if(!B.d_qc) HIPCHK(hipMalloc((void**)&B.d_qc, 2 * s->max_reads));
+	// a set without bytes passes as a whole
+	if(pass1) HIPCHK(hipMemcpyAsync(B.d_qc, pass1, n, hipMemcpyHostToDevice, s->st)); else HIPCHK(hipMemsetAsync(B.d_qc, 1, n, s->st));
+	if(pass2) HIPCHK(hipMemcpyAsync(B.d_qc + s->max_reads, pass2, n, hipMemcpyHostToDevice, s->st)); else HIPCHK(hipMemsetAsync(B.d_qc + s->max_reads, 1, n, s->st));
+	HIPCHK(sync_all(s));
+	B.has_qc = true;
+	return H2G_OK;
+}
+
 // go() on a graph index: the index must be a SNP graph (ALT database present)
 // GenomeHit::combineWith as a primitive of its own: a[i] becomes the combination of a[i] (the left hit) and b[i] on the resident reads, ok[i] the
 // function's return value.  Scoring and splice policy: `p` (nullptr: the defaults of the index).
@@ -2170,6 +2209,8 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	A.rd1 = dreads(s); A.rd2 = A.rd1;
 	if(paired) { A.rd2.codes = b.d_codes2; A.rd2.offs = b.d_offs2; A.rd2.quals = b.has_quals2 ? b.d_quals2 : nullptr; }
 	if(b.has_seeds) { A.rd1.seeds = b.d_seeds; A.rd2.seeds = paired ? b.d_seeds + s->max_reads : b.d_seeds; }   // every launch of the run copies rd1 / rd2
+	if(b.has_ids) { A.rd1.ids = b.d_ids; A.rd2.ids = b.d_ids; }
+	if(b.has_qc) { A.rd1.qc = b.d_qc; A.rd2.qc = paired ? b.d_qc + s->max_reads : b.d_qc; }
 	A.P = aln_params_from(*p, p->no_spliced_alignment != 0, g.linear);
 	if(!p->no_spliced_alignment) { A.ssdb = s->ix->dssdb; A.rdid_base = p->first_read_id; }
 	r->X = p->no_spliced_alignment ? DExonTbl() : s->ix->dexons;

@@ -181,6 +181,13 @@ H2G_HD uint32_t mach_read_seed(const Mach& M, const AlnParams& P, const SeqView&
 	const DReads& r = M.rd[set];
 	return r.seeds ? r.seeds[M.read] : gen_rand_seed(v, M.name[set], M.namelen[set], P.seed0);
 }
+// Read::rdid of the machine's read, what the splice-site database's visibility window is measured against
+template <class Ctx> H2G_HD uint32_t mach_rdid(const Ctx& C, const Mach& M) { const uint32_t* ids = M.rd[0].ids; return ids ? ids[M.read] : C.rdid_base + M.read; }
+// --qc-filter (hisat2.cpp:3433-3439): a mate whose QSEQ filter field is '0' fails like one that fails the N filter
+H2G_HD bool mach_read_passes(const Mach& M, const AlnParams& P, const SeqView& v, uint32_t set) {
+	const uint8_t* qc = M.rd[set].qc;
+	return read_passes_filters(v, P) && (!qc || qc[M.read] != 0);
+}
 // The prelude of the worker loop body for one read / pair (hisat2.cpp:3380-3530): filters, PRNG seed, which mates go() sees.
 H2G_MACH_FN void mach_begin(const AlnParams& P, Mach& M, uint32_t read, bool paired_input) {
 	AlignWS* ws = M.ws;
@@ -196,11 +203,11 @@ H2G_MACH_FN void mach_begin(const AlnParams& P, Mach& M, uint32_t read, bool pai
 		rnd.init(mach_read_seed(M, P, v1, 0));                          // rnd.init(ps->bufa().seed) hisat2.cpp:3468
 		gv.rnd = rnd.last;
 		gv.paired = 0; gv.nm = 1; gv.slot0 = 0; gv.rd_sel[0] = 0; gv.rd_sel[1] = 0;
-		M.L.pc = read_passes_filters(v1, P) ? PC_GO_INIT : PC_FINISH;   // filt[0] false: go() is skipped (hisat2.cpp:3518)
+		M.L.pc = mach_read_passes(M, P, v1, 0) ? PC_GO_INIT : PC_FINISH;   // filt[0] false: go() is skipped (hisat2.cpp:3518)
 		return;
 	}
 	SeqView v2 = mach_view(M, 1, true);
-	const bool f1 = read_passes_filters(v1, P), f2 = read_passes_filters(v2, P);
+	const bool f1 = mach_read_passes(M, P, v1, 0), f2 = mach_read_passes(M, P, v2, 1);
 	const uint32_t s1 = mach_read_seed(M, P, v1, 0), s2 = mach_read_seed(M, P, v2, 1);
 	rnd.init((f1 && f2) ? (s1 ^ s2) : s1);                              // hisat2.cpp:3463-3468
 	gv.rnd = rnd.last;
@@ -731,7 +738,7 @@ again:
 					uint32_t fragoff, fraglen, left;
 					hit_get_left(&hit, nullptr, nullptr, &fragoff, &fraglen, &left, nullptr);
 					if(fraglen >= minK && left >= minK && hit.trim5 == 0 && !no_spliced) {
-						f.ncoords = ss_left_sites(*C.ssdb, hit.tidx, left + minK, minK, C.rdid_base + M.read, f.coords, AL_MAX_COORDS);
+						f.ncoords = ss_left_sites(*C.ssdb, hit.tidx, left + minK, minK, mach_rdid(C, M), f.coords, AL_MAX_COORDS);
 						if(f.ncoords > AL_MAX_COORDS) { ws->overflow |= 2048; f.ncoords = AL_MAX_COORDS; }
 					}
 					M_GOTO(PC_FS_L_LOOP);
@@ -749,7 +756,7 @@ again:
 				uint32_t fragoff, fraglen, left;
 				hit_get_left(&hit, nullptr, nullptr, &fragoff, &fraglen, &left, nullptr);
 				if(fraglen >= minK_local && left >= minK_local) {
-					f.ncoords = ss_left_sites(*C.ssdb, hit.tidx, left + minK_local, minK_local + (minK_local < fragoff ? minK_local : fragoff), C.rdid_base + M.read, f.coords, AL_MAX_COORDS);
+					f.ncoords = ss_left_sites(*C.ssdb, hit.tidx, left + minK_local, minK_local + (minK_local < fragoff ? minK_local : fragoff), mach_rdid(C, M), f.coords, AL_MAX_COORDS);
 					if(f.ncoords > AL_MAX_COORDS) { ws->overflow |= 2048; f.ncoords = AL_MAX_COORDS; }
 				}
 			}
@@ -766,7 +773,7 @@ again:
 				hit_get_right(&hit, &fragoff, &fraglen, &right);
 				if(fraglen >= minK_local) {
 					const uint32_t unmapped = rdlen - fragoff - fraglen;
-					f.ncoords = ss_right_sites(*C.ssdb, hit.tidx, right + fraglen - minK_local, minK_local + (minK_local < unmapped ? minK_local : unmapped), C.rdid_base + M.read, f.coords, AL_MAX_COORDS);
+					f.ncoords = ss_right_sites(*C.ssdb, hit.tidx, right + fraglen - minK_local, minK_local + (minK_local < unmapped ? minK_local : unmapped), mach_rdid(C, M), f.coords, AL_MAX_COORDS);
 					if(f.ncoords > AL_MAX_COORDS) { ws->overflow |= 2048; f.ncoords = AL_MAX_COORDS; }
 				}
 			}
@@ -838,7 +845,7 @@ again:
 			uint32_t fragoff, fraglen, right;
 			hit_get_right(&can, &fragoff, &fraglen, &right);
 			if(!(fraglen >= minK && can.trim3 == 0 && !no_spliced)) continue;
-			f.ncoords = ss_right_sites(*C.ssdb, can.tidx, right + fraglen - minK, minK, C.rdid_base + M.read, f.coords, AL_MAX_COORDS);
+			f.ncoords = ss_right_sites(*C.ssdb, can.tidx, right + fraglen - minK, minK, mach_rdid(C, M), f.coords, AL_MAX_COORDS);
 			if(f.ncoords > AL_MAX_COORDS) { ws->overflow |= 2048; f.ncoords = AL_MAX_COORDS; }
 			f.ri = 0;
 			M_GOTO(PC_FS_R_LOOP);

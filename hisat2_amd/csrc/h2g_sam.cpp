@@ -52,6 +52,9 @@ struct h2g_sam {
 	bool no_sq = false, omit_sec_seq = false;             // --no-sq (hisat2.cpp:4130), --omit-sec-seq (aln_sink.h:3190)
 	bool report_discordant = true, report_mixed = true;   // --no-discordant / --no-mixed clear them (ReportingParams::discord / mixed aln_sink.h:272)
 	bool tlen_adjust = true;                              // --no-templatelen-adjustment clears it (aln_sink.h:2070-2076)
+	const uint8_t* qc1 = nullptr; const uint8_t* qc2 = nullptr;   // h2g_sam_set_read_filter: the caller's bytes (not owned), of the batch being formatted
+	const uint64_t* read_ids = nullptr;                             // h2g_sam_set_read_ids: the caller's array (not owned)
+	uint64_t* record_ends = nullptr;                                // h2g_sam_set_record_ends: the caller's array (not owned)
 	const h2g_edit* long_edits = nullptr; size_t n_long_edits = 0;   // h2g_sam_set_long_edits: the caller's buffer (not owned), of the batch being formatted
 	// what SpliceSiteDB keeps per site for --novel-splicesite-outfile (splice_site.cpp:243-276): the number of lines written across it
 	// and the smallest edit distance among them; file / index sites enter with 0 / 0 (SpliceSite::init splice_site.h:237)
@@ -121,7 +124,7 @@ Score add(const Score& a, const Score& b) { Score s; s.valid = a.valid; s.score 
 
 struct Flags {        // AlnFlags (aligner_result.h:414-640); the filters are "passed" bits
 	int  pairing = PAIR_UNPAIRED;
-	bool primary = true, oppAligned = false, oppFw = true, nfilt = true, lenfilt = true;
+	bool primary = true, oppAligned = false, oppFw = true, nfilt = true, lenfilt = true, qcfilt = true;
 	bool partOfPair() const { return pairing < PAIR_UNPAIRED; }
 	bool concordant() const { return pairing == PAIR_CONCORD_M1 || pairing == PAIR_CONCORD_M2; }
 	bool discordant() const { return pairing == PAIR_DISCORD_M1 || pairing == PAIR_DISCORD_M2; }
@@ -463,7 +466,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	if(!rs) {                                                            // printEmptyOptFlags sam.h:1033-1100
 		o += "YT:Z:";
 		o += fl.concordant() ? "CP" : fl.discordant() ? "DP" : fl.unpairedMate() ? "UP" : "UU";
-		if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS";
+		if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS"; else if(!fl.qcfilt) o += "\tYF:Z:QC";
 		if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }   // sam.h:1102
 		o.push_back('\n');
 		return;
@@ -509,7 +512,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	if(summ.paired && rso) { o += "\tYS:i:"; put(o, rso->score); }
 	o += "\tYT:Z:";
 	o += fl.concordant() ? "CP" : fl.discordant() ? "DP" : fl.unpairedMate() ? "UP" : "UU";
-	if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS";
+	if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS"; else if(!fl.qcfilt) o += "\tYF:Z:QC";
 	if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }       // sam.h:780
 	if(S.rna_strandness != 0) {   // a stranded library: the tag follows from the mate and the strand it aligned to (sam.h:940-966)
 		char strand = '+';
@@ -700,7 +703,7 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 		o.reserve((e - b) * 760);                       // (two lines of a 101 bp pair; longer reads grow it)
 		tl_novel = &mets[t].novel;
 		tl_long_edits = S->long_edits; tl_long_edits_n = S->n_long_edits;
-		for(size_t i = b; i < e; i++) { tl_rdid = S->first_read_id + i; one(i, o, mets[t]); }
+		for(size_t i = b; i < e; i++) { tl_rdid = S->read_ids ? S->read_ids[i] : S->first_read_id + i; one(i, o, mets[t]); if(S->record_ends) S->record_ends[i] = o.size(); }
 		tl_novel = nullptr; tl_long_edits = nullptr; tl_long_edits_n = 0;
 	};
 	if(T == 1) work(0);
@@ -718,6 +721,7 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 	// the parts go to the caller's buffer side by side (hundreds of MB per batch: one thread would spend a third of the call here)
 	std::vector<size_t> at(T + 1, 0);
 	for(size_t t = 0; t < T; t++) at[t + 1] = at[t] + parts[t].size();
+	if(S->record_ends) for(size_t t = 1; t < T; t++) for(size_t i = n * t / T; i < n * (t + 1) / T; i++) S->record_ends[i] += at[t];
 	auto place = [&](size_t t) { memcpy(out + at[t], parts[t].data(), parts[t].size()); };
 	if(T == 1 || total < (1u << 20)) for(size_t t = 0; t < T; t++) place(t);
 	else {
@@ -730,6 +734,9 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 }
 }  // namespace
 
+extern "C" void h2g_sam_set_read_filter(h2g_sam* S, const uint8_t* pass1, const uint8_t* pass2) { if(S) { S->qc1 = pass1; S->qc2 = pass2; } }
+extern "C" void h2g_sam_set_read_ids(h2g_sam* S, const uint64_t* ids) { if(S) S->read_ids = ids; }
+extern "C" void h2g_sam_set_record_ends(h2g_sam* S, uint64_t* ends) { if(S) S->record_ends = ends; }
 extern "C" void h2g_sam_set_long_edits(h2g_sam* S, const h2g_edit* area, size_t n) { if(S) { S->long_edits = n ? area : nullptr; S->n_long_edits = area ? n : 0; } }
 namespace {
 // every long record of a batch must point inside the area the caller set: checked before a line is written (H2G_ERR_ARG otherwise)
@@ -963,6 +970,7 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 		Rd rd = {nb + noffs[i], noffs[i + 1] - noffs[i], codes + offs[i], offs[i + 1] - offs[i], quals ? quals + offs[i] : nullptr};
 		Flags fl;
 		read_filters(*S, rd, &fl.lenfilt, &fl.nfilt);
+		fl.qcfilt = !S->qc1 || S->qc1[i] != 0;
 		Summ summ;
 		const h2g_read_result& r = res[i];
 		if(r.best != INT32_MIN) { summ.best[0].valid = true; summ.best[0].score = r.best; summ.best[0].h2 = (int64_t)(((uint64_t)(int64_t)r.best << 32) | r.best_h2); }
@@ -1034,6 +1042,7 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 		Flags f1, f2;
 		read_filters(*S, rd[0], &f1.lenfilt, &f1.nfilt);
 		read_filters(*S, rd[1], &f2.lenfilt, &f2.nfilt);
+		f1.qcfilt = !S->qc1 || S->qc1[i] != 0; f2.qcfilt = !S->qc2 || S->qc2[i] != 0;
 		Rng rnd = {pr.rnd_state};
 		// ReportingState::foundConcordant aln_sink.cpp:74-112: concordant pairs are kept while they tie the best pair score?
 		// No — every concordant pair reported is kept (rs1_/rs2_); nconcord = their count

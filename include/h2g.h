@@ -371,6 +371,27 @@ H2G_EXPORT void       h2g_align_params_presets(h2g_align_params* p, const h2g_in
  * with seeds1 but no seeds2 is refused.  A pair's PRNG starts from seeds1[i] ^ seeds2[i] when both mates pass the filters (length, --n-ceil) and from
  * seeds1[i] otherwise (hisat2.cpp:3463-3468); an unpaired read's from seeds1[i].  seeds1 == NULL clears them; h2g_set_reads clears them too. */
 H2G_EXPORT h2g_status h2g_set_read_seeds(h2g_stream*, const uint32_t* seeds1, const uint32_t* seeds2, size_t n);
+/* --qc-filter (hisat2.cpp:3433-3439) for the selected resident batch: one byte per read, 0 = the read failed its QSEQ filter field and is not aligned
+ * (go() is skipped for it as for a read that fails the length or --n-ceil filter; its mate, if it passes, is aligned alone and the pair's PRNG starts
+ * from mate 1's seed alone).  pass1 / pass2: mate 1's / mate 2's bytes ([n], n = the batch's read count); NULL = that set passes as a whole; both NULL
+ * clears them; h2g_set_reads clears them too.  pass2 is read by paired runs only.  The sink prints YF:Z:QC for such a read (h2g_sam_set_read_filter). */
+H2G_EXPORT h2g_status h2g_set_read_filter(h2g_stream*, const uint8_t* pass1, const uint8_t* pass2);
+/* Explicit read ids (Read::rdid) for the selected resident batch, in place of first_read_id + index: for a batch whose reads are not consecutive records, such as
+ * the pairs of a stretch of records that mixes pairs and unpaired reads.  The splice-site database's visibility window is measured against them (temporary splice
+ * sites).  ids: [n]; NULL clears them; h2g_set_reads clears them too. */
+H2G_EXPORT h2g_status h2g_set_read_ids(h2g_stream*, const uint32_t* ids);
+/* ... and for a SAM handle of include/h2g_sam.h (the list of declarations of that header is pinned by tests/test_abi.py, so they stand here, as h2g_sam_set_n_ceil does).
+ * The ids the format calls tag collected junctions with (h2g_sam_collect_novel_sites) and test the database's window against, in place of first_read_id + index
+ * (ids: [n_reads] of the caller, not copied; NULL switches back): */
+H2G_EXPORT void       h2g_sam_set_read_ids(struct h2g_sam*, const uint64_t* ids);
+/* --qc-filter: the bytes given to h2g_set_read_filter for the batch about to be formatted (not copied: they must stay valid through the format call;
+ * NULL = that set passes as a whole).  A read with a zero byte is printed unaligned with YF:Z:QC, after YF:Z:LN and YF:Z:NS in precedence
+ * (aligner_result.cpp:1266-1279); the summary counts it as aligned 0 times.  pass2 is read by the paired format calls only. */
+H2G_EXPORT void       h2g_sam_set_read_filter(struct h2g_sam*, const uint8_t* pass1, const uint8_t* pass2);
+/* Where each read's / pair's text ends: the format calls that deliver their text also write, for read (pair) i of the call, the offset in `out` just
+ * past its last line into ends[i] (ends: [n_reads] of the caller, not copied: the array is written during the format call, by its threads; NULL switches it off).  A read without a line (--no-unal) ends where
+ * the one before it does.  For callers that interleave the text of several calls or sort reads by the flags of their lines. */
+H2G_EXPORT void       h2g_sam_set_record_ends(struct h2g_sam*, uint64_t* ends);
 /* read names (needed by genRandSeed): name i = bytes[offs[i] .. offs[i+1]) */
 H2G_EXPORT h2g_status h2g_set_read_names(h2g_stream*, const char* bytes, const uint32_t* offs, size_t n_reads);
 /* GenomeHit::combineWith (hi_aligner.h:1420-2025) as a primitive of its own: a[i] (the left hit) absorbs b[i] — concatenation, the mismatch rescan of the joint,

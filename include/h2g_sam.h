@@ -79,6 +79,7 @@ H2G_EXPORT void       h2g_sam_set_score_min(h2g_sam*, uint32_t type, double cons
  * long-edit area of their batch (h2g_align_fetch_long_edits, include/h2g.h).  Hand the area of the batch about to be formatted to the handle (not
  * copied: it must stay valid through the format call; n = 0 clears it).  A dense format call over such a record without its area is H2G_ERR_ARG. */
 H2G_EXPORT void       h2g_sam_set_long_edits(h2g_sam*, const h2g_edit* area, size_t n);
+/* (--qc-filter and the record ends: h2g_sam_set_read_filter and h2g_sam_set_record_ends, declared in h2g.h next to h2g_set_read_filter) */
 
 /* "@HD / @SQ / @PG" header as the reference prints it (sam.h printHeader: VN:1.0 SO:unsorted, one @SQ per reference,
  * @PG ID:hisat2 PN:hisat2 VN:<version> CL:"<cmdline>").  Returns bytes needed; writes at most cap. */

@@ -30,10 +30,13 @@ def body_md5(path):
 
 
 variants = [(os.path.basename(e), e, {}, True) for e in exes]
-for name, exe, env, check in variants:
-    for dest in (os.path.join(tmp, "o.sam"), "/dev/null"):
+for vi, (name, exe, env, check) in enumerate(variants):
+    # (a file of its own per executable: overwriting the 6 GB file of the one before cost the later one a second and more, whichever it was — profiles/r07_readsets_cli_perf.md)
+    for dest in (os.path.join(tmp, "o%d.sam" % vi), "/dev/null"):
         t0 = time.perf_counter()
         r = subprocess.run([exe, "-f", "--no-spliced-alignment", "-p", "32", "-x", base, "-1", f1, "-2", f2, "-S", dest], env=dict(os.environ, H2G_CLI_TIMING="1", **env), capture_output=True, text=True)
         dt = time.perf_counter() - t0
         h = body_md5(dest) if (check and dest != "/dev/null") else ""
+        if dest != "/dev/null":
+            os.remove(dest)
         print("%-22s -> %-9s rc %d wall %.2f s = %.2f M reads/s %s | %s" % (name, "file" if dest != "/dev/null" else dest, r.returncode, dt, 2 * n / dt / 1e6, h, [l for l in r.stderr.splitlines() if l.startswith("time:") or l.startswith("index load:")]), flush=True)
