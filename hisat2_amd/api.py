@@ -404,6 +404,7 @@ EXPORTS = [
     "h2g_set_mates", "h2g_set_read_seeds", "h2g_set_read_filter", "h2g_set_read_ids", "h2g_sam_set_read_ids", "h2g_sam_set_read_filter", "h2g_sam_set_record_ends", "h2g_sam_set_n_ceil", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
+    "h2g_index_dense_sa_check",
 ]
 
 
@@ -432,6 +433,7 @@ def lib():
     L.h2g_index_synth_sides.argtypes = [u64, u64, C.c_int, P(vp)]
     L.h2g_index_free.argtypes = [vp]
     L.h2g_index_free.restype = None
+    L.h2g_index_dense_sa_check.argtypes = [vp, P(u32), P(u64)]
     L.h2g_stream_create.argtypes = [vp, C.c_size_t, C.c_size_t, P(vp)]
     L.h2g_stream_free.argtypes = [vp]
     L.h2g_stream_free.restype = None
@@ -499,6 +501,12 @@ class Index:
             _chk(L.h2g_index_load(base.encode(), C.byref(o), C.byref(self.h)), "h2g_index_load")
         self.info = IndexInfo()
         _chk(L.h2g_index_get_info(self.h, C.byref(self.info)), "h2g_index_get_info")
+
+    def dense_sa(self, verify=False):
+        """Waits for the dense SA table's build (H2G_DENSE_SA).  -> (has_table, rows that differ from the canonical walk or None)"""
+        st, nd = u32(0), u64(0)
+        _chk(lib().h2g_index_dense_sa_check(self.h, C.byref(st), C.byref(nd) if verify else None), "h2g_index_dense_sa_check")
+        return bool(st.value), (int(nd.value) if verify else None)
 
     def close(self):
         if self.h:

@@ -834,6 +834,10 @@ int main(int argc, char** argv) {
 		const int per = e && !temp_ss ? atoi(e) : 1;
 		if(per > 1) gpus *= per;
 	}
+	// The dense SA table (include/h2g.h, H2G_DENSE_SA) is for a process whose index serves batch after batch: its build is 80 ms of device time at 256 Mbp, about a second
+	// at GRCh38 size, for 1.3 ms less device time per million pairs — and this program is bound by its host side (parsing, SAM text), not by the device.  Measured on
+	// 1 M pairs it cost 0.05 s of 0.6 s (profiles/r07_dense_sa.md), so the command line leaves it out unless the variable says otherwise.
+	setenv("H2G_DENSE_SA", "0", 0);
 	std::vector<h2g_index*> ixs((size_t)gpus, nullptr);
 	for(int g = 0; g < gpus; g++) {
 		const int dev = (device + g % ndevs_asked) % ndev;

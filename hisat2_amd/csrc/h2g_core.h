@@ -66,6 +66,9 @@ struct DGfm {   // one 32-bit GFM resident in HBM (sides exactly as on disk: 64 
 	// M bits at 78, u32 {F_loc, M_occ, occ[4]} at 104
 	static constexpr uint32_t SYMS = 208, NCW = 7, F_OFF = 52, M_OFF = 78, HDR = 104, WSZ = 4;
 	H2G_HD uint32_t offs_at(uint32_t i) const { return offs[i]; }
+	// the dense SA table of a linear global index (sa_resolve_row below), [gbwtLen] each; nullptr: every row walks
+	const uint32_t* sa_dense = nullptr;   // what sa_walk returns for the row
+	const uint8_t*  sa_dist = nullptr;    // the LF steps that walk takes; H2G_SA_DIST_SAT: not in the table
 };
 
 struct DRef {   // BitPairReference: records sorted by (text, offset); buf 2 bit/base
@@ -495,6 +498,48 @@ H2G_HD uint32_t sa_walk(const DGfm& g, uint32_t row, uint32_t* steps) {
 	return jumps;
 }
 
+// ---- the dense SA table.  SA[row] and the length of the walk from `row` are properties of the index alone, so a linear global index
+// may carry both for every row (5 bytes per row, built once on the device when the index is loaded): a resolution is then two
+// independent loads instead of a chain of about 15 dependent LF steps.  The step count is kept because it is part of the results
+// (PairOut::nsteps, h2g_counters::n_sa_steps).  A walk of H2G_SA_DIST_SAT steps or more is not in the table: that row walks.
+#ifndef H2G_SA_DIST_SAT
+#define H2G_SA_DIST_SAT 255u
+#endif
+// sa_walk through the table when the index has one
+H2G_HD uint32_t sa_resolve_row(const DGfm& g, uint32_t row, uint32_t* steps) {
+	if(g.sa_dist) {
+		const uint32_t d = g.sa_dist[row], v = g.sa_dense[row];
+		if(d != H2G_SA_DIST_SAT) { *steps += d; return v; }
+	}
+	return sa_walk(g, row, steps);
+}
+// Builds the table for rows first, first + stride, ... below `end`: sa_walk's loop with the walks of ONE caller laid end to end, so that a
+// lane of a wave starts its next row when its own walk ends, not when the longest of the wave's 64 does.
+H2G_HD void sa_dense_build_rows(const DGfm& g, uint64_t first, uint32_t stride, uint64_t end, uint32_t* sa_dense, uint8_t* sa_dist) {
+	uint64_t cur = first;
+	uint32_t row = (uint32_t)first, jumps = 0;
+	while(cur < end) {
+		uint32_t val = 0;
+		bool done = false;
+		if(g.nZ && row == g.zoff) { val = jumps; done = true; }
+		else if((row & g.offMask) == row) {
+			const uint32_t off = g.offs[row >> g.offRate];
+			if(off != H2G_MAX) { val = off + jumps; done = true; }
+		}
+		if(!done && jumps >= H2G_SA_DIST_SAT) { jumps = H2G_SA_DIST_SAT; done = true; }
+		if(done) {
+			sa_dense[cur] = val; sa_dist[cur] = (uint8_t)jumps;
+			cur += stride; row = (uint32_t)cur; jumps = 0;
+			continue;
+		}
+		const uint32_t s0 = row / 192u, c0 = row - s0 * 192u;
+		const Side64 sd = load_side64(g.sides + (size_t)s0 * 64);
+		const int c = rowL_in_side64(sd, c0);
+		row = rank_in_side64(g, sd, s0, c0, c);
+		jumps++;
+	}
+}
+
 // GFM::joinedToTextOff gfm.h:5527-5600 (forward index)
 H2G_HD bool joined_to_text(const DGfm& g, uint32_t qlen, uint32_t off, uint32_t* tidx, uint32_t* textoff,
                            bool rejectStraddle, bool* straddled)
@@ -559,7 +604,7 @@ H2G_HD bool genome_coords_item(const DGfm& g, uint32_t top, uint32_t bot, uint32
 	if(nelt > cap) nelt = cap;
 	res->ok = 1; res->ncoords = 0; res->straddled = 0; res->nsteps = 0;
 	for(uint32_t e = 0; e < nelt; e++) {
-		uint32_t joff = sa_walk(g, top + e, &res->nsteps);
+		uint32_t joff = sa_resolve_row(g, top + e, &res->nsteps);
 		uint32_t tidx = 0, toff = 0;
 		bool st2 = false;
 		joined_to_text(g, len, joff, &tidx, &toff, rejectStraddle, &st2);

@@ -2123,13 +2123,26 @@ H2G_HD bool fast_op_gcoords(const FCtx& C, FState& S, const FWords& W) {
 		if(nelt > FG_NCO) nelt = FG_NCO;
 	}
 	uint32_t budget = FG_WALK_STEPS, nsteps = 0;
+	// the dense SA table (sa_resolve_row, h2g_core.h): the rows of ALL elements are fetched before any is used — they are independent, where the walk
+	// was a chain — and an element the table does not hold (no table, a walk of H2G_SA_DIST_SAT steps or more) walks as before
+	uint32_t tv[FG_NCO], td[FG_NCO];
+#pragma unroll
+	for(uint32_t k = 0; k < FG_NCO; k++) {
+		const bool in = g.sa_dist != nullptr && k < nelt;
+		td[k] = in ? (uint32_t)g.sa_dist[S.a0 + k] : H2G_SA_DIST_SAT;
+		tv[k] = in ? g.sa_dense[S.a0 + k] : 0u;
+	}
 	for(; e < nelt; e++) {
+		uint32_t d = H2G_SA_DIST_SAT, v = 0;
+#pragma unroll
+		for(uint32_t k = 0; k < FG_NCO; k++) if(k == e) { d = td[k]; v = tv[k]; }
 		if(!resume) { row = S.a0 + e; jumps = 0; }
-		resume = false;
 		// sa_walk (h2g_core.h) with a step budget
 		uint32_t joff = 0;
 		bool found = false;
-		while(true) {
+		if(!resume && d != H2G_SA_DIST_SAT) { joff = v; nsteps += d; found = true; }
+		resume = false;
+		while(!found) {
 			if(g.nZ && row == g.zoff) { joff = jumps; found = true; break; }
 			if((row & g.offMask) == row) {
 				const uint32_t off = g.offs[row >> g.offRate];

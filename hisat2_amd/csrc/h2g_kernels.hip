@@ -10,6 +10,7 @@
 #include <vector>
 #include <thread>
 #include <atomic>
+#include <memory>
 #include <chrono>
 #include <algorithm>
 #define H2G_EXT_OPTS 0      // likewise -I / --fr --rf --ff / --nofw --norc (h2g_align.h): go() units only
@@ -59,7 +60,24 @@ struct h2g_index {
 	std::vector<DLocalDesc> h_ldesc;   // host copy of the local-index descriptors (bucketing of h2g_ext_search)
 	std::vector<void*> allocs;
 	uint64_t device_bytes = 0;
+	// the dense SA table of a linear index (h2g_core.h sa_resolve_row): built by k_sa_dense_build on a stream of the index's own behind the uploads.
+	// `dg` never carries its pointers: a run takes them through dg_now(), which hands them out once the build is over (dense_ready)
+	uint32_t* d_sa_dense = nullptr; uint8_t* d_sa_dist = nullptr;
+	hipStream_t dense_st = nullptr; hipEvent_t dense_ev = nullptr;
+	std::atomic<bool> dense_ready{false};
+	double dense_ms = 0.0;                                 // (H2G_DENSE_SA=2: the build, timed on the host)
 };
+// the index's DGfm as a run queued now may use it: with the dense SA table from the moment its build is over (polled, never waited for)
+static DGfm dg_now(h2g_index* ix) {
+	DGfm g = ix->dg;
+	if(!ix->d_sa_dist) return g;
+	if(!ix->dense_ready.load(std::memory_order_acquire)) {
+		if(hipEventQuery(ix->dense_ev) != hipSuccess) { (void)hipGetLastError(); return g; }
+		ix->dense_ready.store(true, std::memory_order_release);
+	}
+	g.sa_dense = ix->d_sa_dense; g.sa_dist = ix->d_sa_dist;
+	return g;
+}
 
 // The general machine's pass over run k's hand-ons is a LATENCY CHAIN: its length is its longest reads' (hundreds of dependent trips of
 // 60-100 us on a 115 KB workspace), not their number — 30 ms behind a 14.5 ms fast pass on the random GRCh38-size genome, 118 ms behind a 25 ms
@@ -250,6 +268,73 @@ static int upload(h2g_index* ix, const std::vector<T>& v, const T** out, size_t 
 
 extern "C" void h2g_load_opts_init(h2g_load_opts* o) { o->device = 0; o->load_local = 1; }
 
+// ------------------------------------------------------------------------------------------ the dense SA table
+// Row-parallel: every row runs the canonical walk (sa_dense_build_rows, h2g_core.h).  A wave owns H2G_DENSE_CHUNK consecutive rows, lane l the rows
+// l, l + 64, ... of them: its stores stay within the chunk's 20 KB while its walks follow one another without waiting for the wave's longest.
+#define H2G_DENSE_CHUNK 4096u
+__global__ __launch_bounds__(256) void k_sa_dense_build(DGfm g, uint32_t* sa_dense, uint8_t* sa_dist) {
+	const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / 64u;
+	const uint64_t base = wave * H2G_DENSE_CHUNK;
+	if(base >= g.gbwtLen) return;
+	const uint64_t lim = base + H2G_DENSE_CHUNK < g.gbwtLen ? base + H2G_DENSE_CHUNK : g.gbwtLen;
+	sa_dense_build_rows(g, base + (threadIdx.x & 63u), 64u, lim, sa_dense, sa_dist);
+}
+// rows whose table entry is not what the canonical walk gives (h2g_index_dense_sa_check)
+__global__ __launch_bounds__(256) void k_sa_dense_check(DGfm g, const uint32_t* sa_dense, const uint8_t* sa_dist, unsigned long long* ndiff) {
+	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+	unsigned long long bad = 0;
+	for(uint64_t row = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; row < g.gbwtLen; row += stride) {
+		uint32_t steps = 0;
+		const uint32_t off = sa_walk(g, (uint32_t)row, &steps);
+		const uint32_t d = steps < H2G_SA_DIST_SAT ? steps : H2G_SA_DIST_SAT;
+		if(sa_dist[row] != d || (d != H2G_SA_DIST_SAT && sa_dense[row] != off)) bad++;
+	}
+	if(bad) atomicAdd(ndiff, bad);
+}
+// H2G_DENSE_SA: 0 never, 1 (default) build asynchronously when the table fits, 2 build and wait.  Nothing here fails a load: no table = every row walks.
+static void dense_sa_start(h2g_index* ix) {
+	const char* ev = getenv("H2G_DENSE_SA");
+	const int mode = ev && *ev ? atoi(ev) : 1;
+	const DGfm& g = ix->dg;
+	if(mode <= 0 || !g.linear || g.lineRate != 6 || g.gbwtLen == 0) return;
+	const size_t rows = g.gbwtLen, b_dense = rows * 4 + 64, b_dist = rows + 64;
+	size_t free_b = 0, total_b = 0;
+	// it fits when it takes at most a quarter of the memory that is free now, with the index uploaded: a caller's own pools are not squeezed
+	if(hipMemGetInfo(&free_b, &total_b) != hipSuccess || b_dense + b_dist > free_b / 4) { (void)hipGetLastError(); return; }
+	void *pd = nullptr, *pt = nullptr;
+	hipStream_t st = nullptr; hipEvent_t e = nullptr;
+	bool ok = hipMalloc(&pd, b_dense) == hipSuccess && hipMalloc(&pt, b_dist) == hipSuccess &&
+	          hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+	if(ok) {   // at the lowest priority: runs queued while it is under way get their workgroups placed first
+		int least = 0, greatest = 0;
+		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess;
+	}
+	ok = ok && hipDeviceSynchronize() == hipSuccess;                  // the uploads (their padding is set on the null stream) are over
+	const auto t0 = std::chrono::steady_clock::now();
+	if(ok) {
+		const uint64_t waves = ((uint64_t)rows + H2G_DENSE_CHUNK - 1) / H2G_DENSE_CHUNK;
+		hipLaunchKernelGGL(k_sa_dense_build, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, g, (uint32_t*)pd, (uint8_t*)pt);
+		ok = hipGetLastError() == hipSuccess && hipEventRecord(e, st) == hipSuccess;
+		if(!ok && st) (void)hipStreamSynchronize(st);
+	}
+	if(!ok) {
+		(void)hipGetLastError();
+		if(pd) (void)hipFree(pd);
+		if(pt) (void)hipFree(pt);
+		if(e) (void)hipEventDestroy(e);
+		if(st) (void)hipStreamDestroy(st);
+		return;
+	}
+	ix->allocs.push_back(pd); ix->allocs.push_back(pt);
+	ix->device_bytes += b_dense + b_dist;
+	ix->d_sa_dense = (uint32_t*)pd; ix->d_sa_dist = (uint8_t*)pt; ix->dense_st = st; ix->dense_ev = e;
+	if(mode >= 2) {
+		if(hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }       // (the table stays unused: dense_ready is never set by a failed event)
+		ix->dense_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		ix->dense_ready.store(true, std::memory_order_release);
+	}
+}
+
 static void fill_dgfm(const HostGfm& g, uint32_t minK, DGfm* d) {
 	for(int i = 0; i < 5; i++) d->fchr[i] = g.fchr[i];
 	d->len = g.p.len; d->gbwtLen = g.p.gbwtLen; d->ftabLim = g.p.linear ? g.p.len : g.p.gbwtLen;
@@ -285,7 +370,8 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto lsec = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count(); };
 	BigViews bv;                                             // sides, SA sample and reference bases stay in the mapped files until they are on the device
-	Stager sg;
+	std::unique_ptr<Stager> sgp(new Stager());               // (freed before the dense SA table's build is queued: freeing page-locked memory waits for the device)
+	Stager& sg = *sgp;
 	sg.init(o.device);
 	try { rc = load_host_index(base, false, ix->host, false, &bv); } catch(...) { rc = -2; }
 	const double t_parse = lsec();   // a length read from a corrupt file: an allocation failure is a format error, not std::terminate across the C ABI
@@ -375,7 +461,11 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 		if((s = upload(ix, d, &ix->d_spl[0])) || (s = upload(ix, a1, &ix->d_spl[1])) || (s = upload(ix, a2, &ix->d_spl[2]))) { h2g_index_free(ix); return s; }
 	}
 	if(!ix->alt_sites.empty()) { h2g_index* tmp_ = ix; const h2g_status rs_ = h2g_index_set_splice_sites(tmp_, nullptr, 0, 0); if(rs_ != H2G_OK) { h2g_index_free(ix); return rs_; } }
-	if(ltime) fprintf(stderr, "index load: parse %.3f s, global arrays on the device %.3f s, local pack joined %.3f s, all %.3f s (%.2f GB)\n", t_parse, t_global, t_join, lsec(), ix->device_bytes / 1e9);
+	sgp.reset();
+	const double t_up = lsec();
+	dense_sa_start(ix);
+	if(ltime) fprintf(stderr, "index load: parse %.3f s, global arrays on the device %.3f s, local pack joined %.3f s, dense SA table %s (%.3f s here, build %.1f ms), all %.3f s (%.2f GB)\n", t_parse, t_global, t_join,
+	                  !ix->d_sa_dist ? "none" : ix->dense_ready.load() ? "built" : "queued", lsec() - t_up, ix->dense_ms, lsec(), ix->device_bytes / 1e9);
 	*out = ix;
 	return H2G_OK;
 }
@@ -455,8 +545,38 @@ extern "C" h2g_status h2g_index_add_splice_sites(h2g_index* ix, const h2g_splice
 	return upload_splice_db(ix);
 }
 
+// The dense SA table of the index: *state = 0 none (not a linear index, H2G_DENSE_SA=0, or it did not fit), 1 complete.  Waits for the build, then walks
+// every row on the device and counts in *rows_differ the rows whose entry is not what the walk gives (tests; either pointer may be NULL).
+extern "C" h2g_status h2g_index_dense_sa_check(h2g_index* ix, uint32_t* state, uint64_t* rows_differ) {
+	if(!ix) return H2G_ERR_ARG;
+	if(state) *state = 0;
+	if(rows_differ) *rows_differ = 0;
+	if(!ix->d_sa_dist) return H2G_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	HIPCHK(hipStreamSynchronize(ix->dense_st));
+	const DGfm g = dg_now(ix);
+	if(!g.sa_dist) return H2G_OK;
+	if(state) *state = 1;
+	if(!rows_differ) return H2G_OK;
+	unsigned long long* dn = nullptr;
+	HIPCHK(hipMalloc(&dn, sizeof *dn));
+	unsigned long long hn = 0;
+	hipError_t e = hipMemsetAsync(dn, 0, sizeof *dn, ix->dense_st);
+	if(e == hipSuccess) {
+		hipLaunchKernelGGL(k_sa_dense_check, dim3(8192), dim3(256), 0, ix->dense_st, ix->dg, (const uint32_t*)g.sa_dense, (const uint8_t*)g.sa_dist, dn);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipMemcpyAsync(&hn, dn, sizeof hn, hipMemcpyDeviceToHost, ix->dense_st);
+	if(e == hipSuccess) e = hipStreamSynchronize(ix->dense_st);
+	(void)hipFree(dn);
+	if(e != hipSuccess) return (h2g_status)set_err("h2g_index_dense_sa_check", e);
+	*rows_differ = hn;
+	return H2G_OK;
+}
+
 extern "C" void h2g_index_free(h2g_index* ix) {
 	if(!ix) return;
+	if(ix->dense_st) { (void)hipSetDevice(ix->device); (void)hipStreamSynchronize(ix->dense_st); (void)hipEventDestroy(ix->dense_ev); (void)hipStreamDestroy(ix->dense_st); }
 	for(void* p : ix->d_ssdb) if(p) (void)hipFree(p);
 	for(void* p : ix->allocs) (void)hipFree(p);
 	delete ix;
@@ -1750,7 +1870,7 @@ extern "C" h2g_status h2g_sa_resolve(h2g_stream* s, const h2g_sa_query* q, size_
 	   (rc = tmp_buf(s, 2, n * sizeof *res, &dres))) return rc;
 	HIPCHK(hipMemcpyAsync(dq, q, n * sizeof *q, hipMemcpyHostToDevice, s->st));
 	HIPCHK(hipMemsetAsync(dco, 0xff, n * cap * sizeof *coords, s->st));
-	hipLaunchKernelGGL(k_sa_resolve, dim3(grid_for(n, 256)), dim3(256), 0, s->st, s->ix->dg, (const h2g_sa_query*)dq, n, cap, (h2g_coord*)dco, (h2g_sa_result*)dres);
+	hipLaunchKernelGGL(k_sa_resolve, dim3(grid_for(n, 256)), dim3(256), 0, s->st, dg_now(s->ix), (const h2g_sa_query*)dq, n, cap, (h2g_coord*)dco, (h2g_sa_result*)dres);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(coords, dco, n * cap * sizeof *coords, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipMemcpyAsync(res, dres, n * sizeof *res, hipMemcpyDeviceToHost, s->st));
@@ -1845,7 +1965,7 @@ extern "C" h2g_status h2g_seed_extend_run(h2g_stream* s, const h2g_seed_params* 
 	HIPCHK(hipEventRecord(s->ev[2], s->st));
 	hipLaunchKernelGGL(k_seed_search, dim3(grid_for(n, 256)), dim3(256), 0, s->st, s->ix->dg, dreads(s), *p, s->d_seed, s->d_counters);
 	HIPCHK(hipEventRecord(s->ev[3], s->st));
-	hipLaunchKernelGGL(k_seed_resolve_extend, dim3(grid_for(n, 256)), dim3(256), 0, s->st, s->ix->dg, s->ix->dr, dreads(s), sc, s->d_seed, s->d_counters);
+	hipLaunchKernelGGL(k_seed_resolve_extend, dim3(grid_for(n, 256)), dim3(256), 0, s->st, dg_now(s->ix), s->ix->dr, dreads(s), sc, s->d_seed, s->d_counters);
 	HIPCHK(hipEventRecord(s->ev[4], s->st));
 	HIPCHK(hipGetLastError());
 	s->ran_seed = true;
@@ -2203,7 +2323,7 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	const BatchCtx& b = s->cur();
 	GoArgs& A = r->A;
 	memset(&A, 0, sizeof A);
-	A.g = s->ix->dg; A.ref = s->ix->dr; A.ls = s->ix->dls; A.alts = s->ix->dalts;
+	A.g = dg_now(s->ix); A.ref = s->ix->dr; A.ls = s->ix->dls; A.alts = s->ix->dalts;
 	if(p->max_alts_tried) A.alts.maxAltsTried = p->max_alts_tried;          // --max-altstried
 	if(p->use_haplotype && !g.linear && A.alts.n) A.alts.has_splice |= 2u;   // --haplotype: the table behind the ALTs is read (h2g_graph.h haps_of)
 	A.rd1 = dreads(s); A.rd2 = A.rd1;

@@ -64,6 +64,14 @@ H2G_EXPORT h2g_status h2g_index_get_info(const h2g_index*, h2g_index_info* out);
  * consistent Occ checkpoints (GRCh38 scale = 15.3 M sides ~ 0.98 GB); only rank queries are valid. */
 H2G_EXPORT h2g_status h2g_index_synth_sides(uint64_t num_sides, uint64_t seed, int device, h2g_index** out);
 H2G_EXPORT void       h2g_index_free(h2g_index*);
+/* The dense SA table of a linear index: SA[row] and the LF steps of the walk from `row` for every row of the BWT (5 bytes per row; 1.3 GB
+ * for 256 Mbp, 15.5 GB at GRCh38 size), built on the device by h2g_index_load on a stream of its own.  A run queued once the table is complete
+ * resolves a row with two loads; a run queued earlier, or an index without a table, walks — the results, work counters included, are the same.
+ * Environment H2G_DENSE_SA, read by h2g_index_load: 0 no table; 1 (default) build it behind the load when it takes at most a quarter of the
+ * device memory that is free once the index is uploaded; 2 the same, and the load returns when the table is complete.
+ * h2g_index_dense_sa_check waits for the build; *state = 1 when the index has a complete table (else 0), and with rows_differ != NULL every
+ * row is walked on the device and the rows whose entry differs from the walk are counted (0 = the table is right). */
+H2G_EXPORT h2g_status h2g_index_dense_sa_check(h2g_index*, uint32_t* state, uint64_t* rows_differ);
 /* Splice sites for spliced alignment (SpliceSiteDB, splice_site.h:470): what --known-splicesite-infile / --novel-splicesite-infile
  * hand the reference (SpliceSiteDB::read splice_site.cpp:727: text name, left = last base of the upstream exon, right = first
  * base of the downstream exon, both 0-based, strand).  go() joins reads through them (spliced_aligner.h:409-676, 685-811,
