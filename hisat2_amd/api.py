@@ -6,7 +6,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
@@ -181,31 +180,6 @@ class ReadResult(C.Structure):
                 ("best", C.c_int32), ("secbest", C.c_int32), ("best_h2", u32), ("secbest_h2", u32)]
 
 
-FUNC_TYPES = {"C": 1, "Constant": 1, "L": 2, "Linear": 2, "S": 3, "Sqrt": 3, "G": 4, "Log": 4}   # parseFuncType aligner_seed_policy.cpp:30-44
-
-
-def parse_n_ceil(arg, cur=(2, 0.0, float(np.float32(0.15)))):
-    """--n-ceil <arg> applied to the ceiling `cur` = (type, constant, coefficient), as the reference does: 1-3 comma-separated tokens
-    (empty ones dropped), one token x meaning C,x (hisat2.cpp:1525-1549), then PARSE_FUNC (aligner_seed_policy.cpp:47-70): a type, and
-    the constant and coefficient when given (fields not given keep their value).  ValueError carries the reference's message."""
-    toks = [t for t in arg.split(",") if t]
-    if len(toks) > 3:
-        raise ValueError(f"Error: expected 3 or fewer comma-separated arguments to --n-ceil option, got {len(toks)}")
-    if not toks:
-        raise ValueError("Error: expected at least one argument to --n-ceil option")
-    if len(toks) == 1:
-        toks = ["C"] + toks
-    if toks[0] not in FUNC_TYPES:
-        raise ValueError(f"Error: Bad function type '{toks[0]}'.  Should be C (constant), L (linear), S (square root) or G (natural log).")
-    t, c, l = FUNC_TYPES[toks[0]], cur[1], cur[2]
-    num = lambda x: float(re.match(r"\s*([+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?)?", x).group(1) or 0.0)   # istringstream >> double
-    if len(toks) > 1:
-        c = num(toks[1])
-    if len(toks) > 2:
-        l = num(toks[2])
-    return t, c, l
-
-
 class AlignParams(C.Structure):
     _fields_ = [("khits", u32), ("kseeds", u32), ("no_spliced_alignment", u32), ("secondary", u32), ("bowtie2_dp", u32),
                 ("mm_max", C.c_int32), ("mm_min", C.c_int32), ("n_pen", C.c_int32), ("rdg_const", C.c_int32), ("rdg_linear", C.c_int32),
@@ -221,153 +195,47 @@ class AlignParams(C.Structure):
 
     def apply_options(self, opts, linear=None):
         """apply a list of reference command-line options (['-k', '3', '--mp', '4,2', ...]) to this block; returns leftovers.
-        Presets are resolved AFTER all options were read, as hisat2.cpp:1882-1909 / 3174-3176 / 3903-3906 does (the same
-        rules as h2g_align_params_presets): --sensitive alone keeps -k 5 on a linear index, and a preset's --score-min wins.
-        `linear` defaults to what the block's default -k says about the index (5 = linear, 10 = graph)."""
+        Every rule is the library's (h2g_align_params_apply_options, then h2g_align_params_presets: the command line's parser);
+        a faulty option raises ValueError with the library's message.  `linear` defaults to what the block's default -k says about
+        the index (5 = linear, 10 = graph)."""
         if linear is None:
             linear = self.khits == 5
-        rest, i = [], 0
-        saw_k, k_arg, max_seeds, sensitive, very = False, 0, 0, False, False
-        ignore_quals = False
-        dta = False
+        L = lib()
+        rest, mine, i = [], [], 0
         while i < len(opts):
             o = opts[i]
-            v = opts[i + 1] if i + 1 < len(opts) else None
-            if o == "-k":
-                k_arg = int(v); saw_k = True; i += 2
-            elif o == "--max-seeds":
-                max_seeds = int(v); i += 2
-            elif o == "--secondary":
-                self.secondary = 1; i += 1
-            elif o == "--no-temp-splicesite":
-                self.no_temp_splicesite = 1; i += 1
-            elif o == "--no-spliced-alignment":
-                self.no_spliced_alignment = 1; i += 1
+            arity = L.h2g_align_option_arity(o.encode())
+            if arity >= 0:
+                mine += opts[i:i + 1 + arity]
             elif o == "--spliced":          # test shorthand: the reference's default mode
-                self.no_spliced_alignment = 0; i += 1
-            elif o == "--sensitive":
-                sensitive = True; i += 1
-            elif o == "--very-sensitive":
-                very = True; i += 1
-            elif o == "--bowtie2-dp":
-                self.bowtie2_dp = int(v); i += 2
-            elif o == "--mp":
-                a = v.split(","); self.mm_max = int(a[0]); self.mm_min = int(a[1]) if len(a) > 1 else self.mm_min; i += 2
-            elif o == "--sp":
-                a = v.split(",")   # the reference reads BOTH max and min from the first number (aligner_seed_policy.cpp:438-441)
-                self.sc_max = self.sc_min = int(a[0]); i += 2
-            elif o == "--no-softclip":
-                self.sc_max = self.sc_min = 2 ** 31 - 1; i += 1
-            elif o == "--np":
-                self.n_pen = int(v); i += 2
-            elif o == "--rdg":
-                a = v.split(","); self.rdg_const = int(a[0]); self.rdg_linear = int(a[1]) if len(a) > 1 else self.rdg_linear; i += 2
-            elif o == "--rfg":
-                a = v.split(","); self.rfg_const = int(a[0]); self.rfg_linear = int(a[1]) if len(a) > 1 else self.rfg_linear; i += 2
-            elif o in ("--dta", "--downstream-transcriptome-assembly", "--dta-cufflinks"):
-                dta = True
-                if o == "--dta-cufflinks":
-                    self.xs_only = 1
-                i += 1
-            elif o in ("--rna-strandness", "--novel-splicesite-outfile"):   # output only: h2g_sam_set_rna_strandness / h2g_sam_novel_splice_sites_text
-                i += 2
-            elif o in ("-I", "--minins"):
-                self.min_frag_len = int(v); i += 2
-            elif o in ("--fr", "--rf", "--ff"):
-                self.pe_orientation = {"--fr": 0, "--rf": 1, "--ff": 2}[o]; i += 1
-            elif o == "--nofw":
-                self.nofw = 1; i += 1
-            elif o == "--norc":
-                self.norc = 1; i += 1
-            elif o == "--avoid-pseudogene":
-                self.avoid_pseudogene = 1; i += 1
-            elif o in ("--tmo", "--transcriptome-mapping-only"):
-                self.transcriptome_mapping_only = 1; i += 1
-            elif o == "--no-anchorstop":
-                self.no_anchorstop = 1; i += 1
-            elif o == "--splicesite-db-only":   # accepted and read nowhere by the reference (hisat2.cpp:1706-1708)
-                i += 1
-            elif o == "--pen-conflictsplice":
-                if int(v) < 0:
-                    raise ValueError("--pen-conflictsplice arg must be at least 0")
-                self.pen_conflictsplice = int(v); i += 2
-            elif o in ("-X", "--maxins"):
-                self.max_frag_len = int(v); i += 2
-            elif o == "--max-altstried":
-                self.max_alts_tried = int(v); i += 2
-            elif o == "--haplotype":
-                self.use_haplotype = 1; i += 1
-            elif o in ("--rg-id", "--rg"):                                   # output only: h2g_sam_add_read_group
-                i += 2
-            elif o == "--ignore-quals":
-                ignore_quals = True; i += 1
-            elif o == "--summary-file":
-                i += 2
-            elif o in ("--no-sq", "--omit-sec-seq", "--new-summary", "--add-chrname", "--remove-chrname"):                         # output only: h2g_sam_set_header_options
-                i += 1
-            elif o in ("--no-mixed", "--no-discordant"):                      # output only: h2g_sam_set_report_policy
-                i += 1
-            elif o == "--no-templatelen-adjustment":                       # output only (TLEN): h2g_sam_set_templatelen_adjustment
-                i += 1
-            elif o == "--min-intronlen":
-                self.min_intronlen = int(v); i += 2
-            elif o == "--max-intronlen":
-                self.max_intronlen = int(v); i += 2
-            elif o == "--pen-cansplice":
-                self.pen_cansplice = int(v); i += 2
-            elif o == "--pen-noncansplice":
-                self.pen_noncansplice = int(v); i += 2
-            elif o in ("--pen-canintronlen", "--pen-intronlen", "--pen-noncanintronlen"):
-                a = v.split(",")            # PARSE_FUNC aligner_seed_policy.cpp:47: only the fields given are changed
-                w = "pen_noncanintronlen" if o == "--pen-noncanintronlen" else "pen_canintronlen"
-                setattr(self, w + "_type", {"C": 1, "L": 2, "S": 3, "G": 4}[a[0]])
-                if len(a) > 1:
-                    setattr(self, w + "_const", float(a[1]))
-                if len(a) > 2:
-                    setattr(self, w + "_coeff", float(a[2]))
-                i += 2
-            elif o == "--seed":
-                if int(v) < 0:
-                    raise ValueError("--seed arg must be at least 0")
-                self.seed = int(v); i += 2
-            elif o == "--n-ceil":
-                self.n_ceil_type, self.n_ceil_const, self.n_ceil_coeff = parse_n_ceil(v, (self.n_ceil_type, self.n_ceil_const, self.n_ceil_coeff))
-                i += 2
-            elif o == "--score-min":
-                a = v.split(",")
-                self.score_min_type = {"C": 1, "L": 2, "S": 3, "G": 4}[a[0]]
-                self.score_min_const = float(a[1]) if len(a) > 1 else 0.0
-                self.score_min_coeff = float(a[2]) if len(a) > 2 else 0.0
-                i += 2
-            else:
-                rest.append(o); i += 1
-        if dta:                              # hisat2.cpp:3920, 4078: applied after every option was read
-            self.min_anchor_len, self.min_anchor_len_noncan = 15, 20
-            self.pen_noncanintronlen_type, self.pen_noncanintronlen_const, self.pen_noncanintronlen_coeff = 4, -8.0, 2.0
-        if ignore_quals and "--mp" not in opts:   # COST_MODEL_CONSTANT: every mismatch costs the maximum (aligner_seed_policy.cpp:279); --mp sets the quality model again (:418)
-            self.mm_min = self.mm_max
-        self.presets(linear, saw_k, k_arg, max_seeds, sensitive, very)
+                self.no_spliced_alignment = 0
+            elif o not in OUTPUT_OPTIONS:
+                rest.append(o)
+            i += 1 + max(arity, OUTPUT_OPTIONS.get(o, 0))
+        pre, err = AlignPresets(), C.create_string_buffer(512)
+        argv = (C.c_char_p * max(1, len(mine)))(*[m.encode() for m in mine])
+        if L.h2g_align_params_apply_options(C.byref(self), C.byref(pre), argv, len(mine), err, len(err)) != 0:
+            raise ValueError(err.value.decode())
+        L.h2g_align_params_presets(C.byref(self), int(bool(linear)), C.byref(pre))
         return rest
 
-    def presets(self, linear, saw_k, k_arg, max_seeds, sensitive, very_sensitive):
-        """Python mirror of h2g_align_params_presets (tests/test_abi.py checks the two against each other)"""
-        import numpy as np
-        khits = k_arg if saw_k else 10
-        if sensitive:
-            if self.bowtie2_dp == 0:
-                self.bowtie2_dp = 1
-            if khits < 10:
-                khits, saw_k = 10, True
-            self.score_min_type, self.score_min_const, self.score_min_coeff = 2, 0.0, float(np.float32(-0.5))
-        elif very_sensitive:
-            self.bowtie2_dp = 2
-            if khits < 30:
-                khits, saw_k = 30, True
-            self.score_min_type, self.score_min_const, self.score_min_coeff = 2, 0.0, float(np.float32(-1.0))
-        if not saw_k:
-            khits = 5 if linear else 10
-        self.khits = khits
-        self.kseeds = max_seeds if max_seeds else max(5, 2 * khits)
+
+class AlignPresets(C.Structure):     # h2g_align_presets
+    _fields_ = [(n, u32) for n in ("saw_k", "k_arg", "max_seeds_arg", "sensitive", "very_sensitive")]
+
+
+# options of the command line that change the SAM text only (include/h2g_sam.h), never h2g_align_params: name -> arity
+OUTPUT_OPTIONS = {"--rg-id": 1, "--rg": 1, "--rna-strandness": 1, "--novel-splicesite-outfile": 1, "--summary-file": 1, "--no-sq": 0, "--omit-sec-seq": 0,
+                  "--new-summary": 0, "--add-chrname": 0, "--remove-chrname": 0, "--no-mixed": 0, "--no-discordant": 0, "--no-templatelen-adjustment": 0}
+
+
+def parse_n_ceil(arg, cur=(2, 0.0, float(np.float32(0.15)))):
+    """--n-ceil <arg> applied to the ceiling `cur` = (type, constant, coefficient) by the library's parser (fields not given keep
+    their value).  ValueError carries the reference's message."""
+    p = AlignParams()
+    p.n_ceil_type, p.n_ceil_const, p.n_ceil_coeff = cur
+    p.apply_options(["--n-ceil", arg], linear=True)
+    return p.n_ceil_type, p.n_ceil_const, p.n_ceil_coeff
 
 
 PAIR_RES_CAP = 16
@@ -400,7 +268,7 @@ EXPORTS = [
     "h2g_last_error", "h2g_stream_create", "h2g_stream_free", "h2g_stream_hip", "h2g_stream_sync", "h2g_stream_select_batch", "h2g_set_reads",
     "h2g_rank_bench", "h2g_rank_bench_synth", "h2g_rank_bench_synth_sample", "h2g_fm_search", "h2g_sa_resolve", "h2g_extend",
     "h2g_seed_params_init", "h2g_seed_extend_run", "h2g_seed_extend_fetch", "h2g_get_counters",
-    "h2g_device_count", "h2g_ext_search", "h2g_local_index_of", "h2g_align_params_init", "h2g_align_params_presets", "h2g_set_read_names", "h2g_align_run", "h2g_align_fetch",
+    "h2g_device_count", "h2g_ext_search", "h2g_local_index_of", "h2g_align_params_init", "h2g_align_option_arity", "h2g_align_params_apply_options", "h2g_align_params_presets", "h2g_set_read_names", "h2g_align_run", "h2g_align_fetch",
     "h2g_set_mates", "h2g_set_read_seeds", "h2g_set_read_filter", "h2g_set_read_ids", "h2g_sam_set_read_ids", "h2g_sam_set_read_filter", "h2g_sam_set_record_ends", "h2g_sam_set_n_ceil", "h2g_combine_with", "h2g_align_pairs_run", "h2g_align_pairs_fetch", "h2g_align_fetch_dense", "h2g_align_pairs_fetch_dense", "h2g_align_fetch_long_edits",
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
@@ -461,7 +329,9 @@ def lib():
     L.h2g_get_counters.argtypes = [vp, P(Counters)]
     L.h2g_align_params_init.argtypes = [P(AlignParams), vp]
     L.h2g_align_params_init.restype = None
-    L.h2g_align_params_presets.argtypes = [P(AlignParams), vp, C.c_int, u32, u32, C.c_int, C.c_int]
+    L.h2g_align_option_arity.argtypes = [C.c_char_p]
+    L.h2g_align_params_apply_options.argtypes = [P(AlignParams), P(AlignPresets), P(C.c_char_p), C.c_size_t, C.c_char_p, C.c_size_t]
+    L.h2g_align_params_presets.argtypes = [P(AlignParams), C.c_int, P(AlignPresets)]
     L.h2g_align_params_presets.restype = None
     L.h2g_ext_search.argtypes = [vp, vp, C.c_size_t, u32, vp, vp]
     L.h2g_local_index_of.argtypes = [vp, u32, u32]

@@ -20,7 +20,6 @@
 #include <deque>
 #include <chrono>
 #include <algorithm>
-#include <sstream>
 #include <time.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -590,32 +589,25 @@ int main(int argc, char** argv) {
 	QualCoding qcoding;
 	std::string rs_arg[RS_KINDS];
 	bool rs_gz[RS_KINDS] = {false, false, false, false, false};
-	bool fasta = false, nospliced = false, notempss = false, nohead = false, parse_only = false, no_unal = false;
+	bool fasta = false, nohead = false, parse_only = false, no_unal = false;
 	std::string known_ss, novel_ss, novel_out;
-	bool tlen_adjust = true, use_haplotype = false;
-	int max_alts_tried = 16, max_frag_len = 1000, min_frag_len = 0, pe_orientation = 0;
-	bool nofw = false, norc = false, no_sq = false, omit_sec_seq = false;
+	bool tlen_adjust = true;
+	bool no_sq = false, omit_sec_seq = false;
 	std::vector<std::pair<bool, std::string> > rg_args;
 	bool new_summary = false;
 	std::string summary_file;
 	int chrname_mode = 0;
-	bool ignore_quals = false, quiet = false, raw_input = false, cmdline_input = false;
+	bool quiet = false, raw_input = false, cmdline_input = false;
 	bool report_mixed = true, report_discordant = true;
-	bool dta = false, xs_only = false;
-	bool avoid_pseudogene = false, tmo = false, no_anchorstop = false;
 	int strandness = 0;
 	uint64_t skip = 0, upto = ~0ull;
 	uint32_t trim5 = 0, trim3 = 0;
-	uint32_t dp = 0;
 	size_t batch = 1u << 20;
 	bool saw_batch = false;
 	int device = 0, threads = 1, gpus = 1;
 	uint32_t ss_window_opt = 0;
 	std::string cmdline;
-	std::vector<std::string> opts;                      // scoring / reporting options, applied once the index type is known
-	bool sensitive = false, very_sensitive = false, saw_k = false;
-	uint32_t k_arg = 0, max_seeds_arg = 0;
-	long seed_arg = 0;
+	std::vector<const char*> opts;                        // the alignment options and their arguments, in order: parsed by the library (h2g_align_params_apply_options)
 	bool arbitrary_random = false;
 	for(int i = 0; i < argc; i++) { if(i) cmdline.push_back(' '); cmdline += argv[i]; }
 	for(int i = 1; i < argc; i++) {
@@ -643,61 +635,29 @@ int main(int argc, char** argv) {
 		else if(a == "-f") fasta = true;
 		else if(a == "-q") fasta = false;
 		else if(a == "-p" || a == "--threads") threads = atoi(need("-p"));        // host threads for parsing and SAM formatting
-		else if(a == "--no-spliced-alignment") nospliced = true;
-		else if(a == "--no-temp-splicesite") notempss = true;
 		else if(a == "--ss-window") ss_window_opt = (uint32_t)strtoul(need("--ss-window"), nullptr, 10);   // reads a temporary splice site stays invisible for: 1000 x <-p> of the reference (hisat2.cpp:3687), decoupled from this program's host threads
-		else if(a == "--dta" || a == "--downstream-transcriptome-assembly") dta = true;
-		else if(a == "--dta-cufflinks") { dta = true; xs_only = true; }
 		else if(a == "--rna-strandness") {
 			const std::string v = need("--rna-strandness");
 			strandness = v == "F" ? 1 : v == "R" ? 2 : v == "FR" ? 3 : v == "RF" ? 4 : 0;
 			if(!strandness) { fprintf(stderr, "Error: should be one of F, R, FR, or RF \n"); return 1; }
 		}
-		else if(a == "--avoid-pseudogene") avoid_pseudogene = true;               // TranscriptomePolicy (tp.h), reportHit hi_aligner.h:6105-6127
-		else if(a == "--tmo" || a == "--transcriptome-mapping-only") tmo = true;
-		else if(a == "--no-anchorstop") no_anchorstop = true;                     // hisat2.cpp:1710-1712
-		else if(a == "--splicesite-db-only") {}                                   // accepted and read nowhere by the reference (hisat2.cpp:1706-1708)
 		else if(a == "--known-splicesite-infile") known_ss = need("--known-splicesite-infile");
 		else if(a == "--novel-splicesite-infile") novel_ss = need("--novel-splicesite-infile");
 		else if(a == "--novel-splicesite-outfile") novel_out = need("--novel-splicesite-outfile");
 		else if(a == "--no-templatelen-adjustment") tlen_adjust = false;
-		else if(a == "--max-altstried") { max_alts_tried = atoi(need("--max-altstried")); if(max_alts_tried < 8) { fprintf(stderr, "--max-altstried arg must be at least 8\n"); return 1; } }
-		else if(a == "-X" || a == "--maxins") { max_frag_len = atoi(need("-X")); if(max_frag_len < 1) { fprintf(stderr, "-X arg must be at least 1\n"); return 1; } }
-		else if(a == "-I" || a == "--minins") { min_frag_len = atoi(need("-I")); if(min_frag_len < 0) { fprintf(stderr, "-I arg must be positive\n"); return 1; } }
-		else if(a == "--fr") pe_orientation = 0;                               // hisat2.cpp:1166-1168
-		else if(a == "--rf") pe_orientation = 1;
-		else if(a == "--ff") pe_orientation = 2;
-		else if(a == "--nofw") nofw = true;                                    // hisat2.cpp:1337-1338
-		else if(a == "--norc") norc = true;
 		else if(a == "--rg-id") rg_args.push_back({true, need("--rg-id")});    // hisat2.cpp:1389-1407, in command-line order
 		else if(a == "--rg") rg_args.push_back({false, need("--rg")});
 		else if(a == "--no-sq" || a == "--sam-no-sq" || a == "--sam-nosq" || a == "--sam-noSQ") no_sq = true;
 		else if(a == "--omit-sec-seq" || a == "--sam-omit-sec-seq") omit_sec_seq = true;
 		else if(a == "--phred64" || a == "--phred64-quals" || a == "--solexa1.3-quals") qcoding.phred64 = true;   // hisat2.cpp ARG_PHRED64
 		else if(a == "--phred33" || a == "--phred33-quals") qcoding.phred64 = false;
-		else if(a == "--ignore-quals") ignore_quals = true;                    // hisat2.cpp:1434
 		else if(a == "--remove-chrname") chrname_mode |= 1;
 		else if(a == "--add-chrname") chrname_mode |= 2;
 		else if(a == "--new-summary") new_summary = true;
 		else if(a == "--summary-file") summary_file = need("--summary-file");
 		else if(a == "--no-mixed") report_mixed = false;                       // hisat2.cpp:1162
 		else if(a == "--no-discordant") report_discordant = false;             // hisat2.cpp:1161
-		else if(a == "--haplotype") use_haplotype = true;                      // hisat2.cpp:1749 (ARG_HAPLOTYPE)
-		else if(a == "--bowtie2-dp") dp = (uint32_t)atoi(need("--bowtie2-dp"));
-		else if(a == "--seed") {                                                 // parseInt(0, ...) hisat2.cpp:1204, 1016-1032
-			seed_arg = strtol(need("--seed"), nullptr, 10);
-			if(seed_arg < 0 || seed_arg > INT32_MAX) { fprintf(stderr, "--seed arg must be at least 0\n"); return 1; }
-		}
 		else if(a == "--non-deterministic" || a == "--nondeterministic") arbitrary_random = true;   // hisat2.cpp:1207
-		else if(a == "--n-ceil") { opts.push_back(a); opts.push_back(need("--n-ceil")); }
-		else if(a == "-k" || a == "--max-seeds" || a == "--mp" || a == "--sp" || a == "--np" || a == "--rdg" || a == "--rfg" || a == "--score-min" ||
-		        a == "--min-intronlen" || a == "--max-intronlen" || a == "--pen-cansplice" || a == "--pen-noncansplice" || a == "--pen-conflictsplice" ||
-		        a == "--pen-canintronlen" || a == "--pen-intronlen" || a == "--pen-noncanintronlen") {
-			opts.push_back(a); opts.push_back(need(a.c_str()));
-		}
-		else if(a == "--secondary" || a == "--no-softclip") opts.push_back(a);
-		else if(a == "--sensitive") sensitive = true;
-		else if(a == "--very-sensitive") very_sensitive = true;
 		else if(a == "--no-hd" || a == "--no-head") nohead = true;
 		else if(a == "--batch") { batch = (size_t)atoll(need("--batch")); saw_batch = true; }
 		else if(a == "--device") device = atoi(need("--device"));
@@ -712,11 +672,20 @@ int main(int argc, char** argv) {
 		else if(a == "--reorder" || a == "-t" || a == "--time" || a == "--mm") {}   // output is always in read order; --mm (index mapping) has nothing to act on here
 		else if(a == "--h2g-stats") stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow} as JSON (tests, bench)
 		else if(a == "--parse-only") parse_only = true;                           // test hook: ingest the reads, print counts + checksums
+		else if(const int arity = h2g_align_option_arity(argv[i]); arity >= 0) { opts.push_back(argv[i]); if(arity) opts.push_back(need(argv[i])); }   // every option that ends in a field of h2g_align_params
 		else { fprintf(stderr, "hisat2-align-amd: option %s is not built (see DESIGN.md, scope)\n", a.c_str()); return 1; }
 	}
 	if(base.empty() || (m12.empty() && u.empty() && (m1.empty() || m2.empty()))) {
 		fprintf(stderr, "usage: hisat2-align-amd -x <ht2-base> {-U <r.fq> | -1 <m1.fq> -2 <m2.fq> | --tab5 <r.tab5> | --tab6 <r.tab6>} [-f|-q|--qseq] --no-spliced-alignment [--bowtie2-dp 0|1|2] [-S out.sam]\n");
 		return 1;
+	}
+	// the alignment options: the library's one parser (h2g_options.cpp), before anything touches a device; -k and the presets follow with the index type
+	h2g_align_params P; h2g_align_params_init(&P, nullptr);
+	P.no_spliced_alignment = 0;                           // the command line's default is the reference's: spliced alignment
+	h2g_align_presets presets;
+	{
+		char err[512];
+		if(h2g_align_params_apply_options(&P, &presets, opts.data(), opts.size(), err, sizeof err) != H2G_OK) { fprintf(stderr, "%s\n", err); return 1; }
 	}
 	bool sorting = false;
 	for(int k = 0; k < RS_KINDS; k++) sorting = sorting || !rs_arg[k].empty();
@@ -792,7 +761,7 @@ int main(int argc, char** argv) {
 	}
 	// Temporary splice sites (the reference's default): a read sees the junctions of reads at least W = 1000 * p ids before it
 	// (hisat2.cpp:3687; -p 1 means W = 0, every read after the other).  The batches are waves of <= W reads run one after the other.
-	const bool temp_ss = !nospliced && !notempss;
+	const bool temp_ss = !P.no_spliced_alignment && !P.no_temp_splicesite;
 	uint32_t ss_window = 0, ss_wave = 0;      // the reference's visibility window, and the reads of one wave here (the window, or ONE read when it is 0)
 	if(temp_ss) {
 		// -p 1 (and no --ss-window): the reference's window is 0 (hisat2.cpp:3687) — a read sees the junctions of EVERY read before it, a strict
@@ -851,91 +820,11 @@ int main(int argc, char** argv) {
 	if(h2g_sam_open(base.c_str(), &sam) != H2G_OK) die("cannot read reference names");
 	if(chrname_mode == 3) { fprintf(stderr, "Error: --remove-chrname and --add-chrname cannot be used at the same time\n"); return 1; }   // hisat2.cpp:3958
 	if(chrname_mode) h2g_sam_set_chrname_mode(sam, chrname_mode);
-	h2g_align_params P; h2g_align_params_init(&P, ix);
-	P.bowtie2_dp = dp;
-	P.no_spliced_alignment = nospliced ? 1 : 0; P.no_temp_splicesite = notempss ? 1 : 0;
-	for(size_t i = 0; i < opts.size(); i++) {             // same parse rules as hisat2.cpp:1500-1620 / aligner_seed_policy.cpp
-		const std::string& o = opts[i];
-		auto two = [&](int32_t* x, int32_t* y) { const std::string& v = opts[++i]; *x = atoi(v.c_str()); const size_t c = v.find(','); if(c != std::string::npos) *y = atoi(v.c_str() + c + 1); };
-		if(o == "-k") {
-			const int k = atoi(opts[++i].c_str());
-			if(k < 1) { fprintf(stderr, "-k arg must be at least 1\n"); return 1; }
-			k_arg = (uint32_t)k; saw_k = true;
-		}
-		else if(o == "--max-seeds") max_seeds_arg = (uint32_t)atoi(opts[++i].c_str());
-		else if(o == "--n-ceil") {
-			// hisat2.cpp:1525-1549: 1-3 tokens, one token x is C,x; then PARSE_FUNC (aligner_seed_policy.cpp:47-70): type, constant and coefficient
-			// when given (istringstream >> double), the others keep their value
-			std::vector<std::string> t = split_commas(opts[++i].c_str());
-			if(t.size() > 3) { fprintf(stderr, "Error: expected 3 or fewer comma-separated arguments to --n-ceil option, got %zu\n", t.size()); return 1; }
-			if(t.empty()) { fprintf(stderr, "Error: expected at least one argument to --n-ceil option\n"); return 1; }
-			if(t.size() == 1) t.insert(t.begin(), "C");
-			const std::string& ty = t[0];
-			const uint32_t type = ty == "C" || ty == "Constant" ? 1 : ty == "L" || ty == "Linear" ? 2 : ty == "S" || ty == "Sqrt" ? 3 : ty == "G" || ty == "Log" ? 4 : 0;
-			if(!type) { fprintf(stderr, "Error: Bad function type '%s'.  Should be C (constant), L (linear), S (square root) or G (natural log).\n", ty.c_str()); return 1; }
-			auto num = [](const std::string& v) { double d = 0.0; std::istringstream ss(v); ss >> d; return d; };
-			P.n_ceil_type = type;
-			if(t.size() > 1) P.n_ceil_const = num(t[1]);
-			if(t.size() > 2) P.n_ceil_coeff = num(t[2]);
-		}
-		else if(o == "--secondary") P.secondary = 1;
-		else if(o == "--mp") two(&P.mm_max, &P.mm_min);
-		else if(o == "--sp") { int32_t unused = 0; two(&P.sc_max, &unused); P.sc_min = P.sc_max; }   // both read from the first number (aligner_seed_policy.cpp:438)
-		else if(o == "--no-softclip") P.sc_max = P.sc_min = INT32_MAX;
-		else if(o == "--np") P.n_pen = atoi(opts[++i].c_str());
-		else if(o == "--rdg") two(&P.rdg_const, &P.rdg_linear);
-		else if(o == "--rfg") two(&P.rfg_const, &P.rfg_linear);
-		else if(o == "--score-min") {
-			const std::string& v = opts[++i];
-			P.score_min_type = v[0] == 'C' ? 1 : v[0] == 'L' ? 2 : v[0] == 'S' ? 3 : v[0] == 'G' ? 4 : 0;
-			if(!P.score_min_type) { fprintf(stderr, "Error: bad function type in --score-min %s\n", v.c_str()); return 1; }
-			P.score_min_const = P.score_min_coeff = 0.0;
-			const size_t c1 = v.find(',');
-			if(c1 != std::string::npos) { P.score_min_const = atof(v.c_str() + c1 + 1); const size_t c2 = v.find(',', c1 + 1); if(c2 != std::string::npos) P.score_min_coeff = atof(v.c_str() + c2 + 1); }
-		}
-		// splice scoring hisat2.cpp:1631-1688
-		else if(o == "--min-intronlen" || o == "--max-intronlen") {
-			const int v = atoi(opts[++i].c_str());
-			if(v < 20) { fprintf(stderr, "%s arg must be at least 20\n", o.c_str()); return 1; }
-			(o == "--min-intronlen" ? P.min_intronlen : P.max_intronlen) = (uint32_t)v;
-		}
-		else if(o == "--pen-cansplice" || o == "--pen-noncansplice" || o == "--pen-conflictsplice") {
-			const int v = atoi(opts[++i].c_str());
-			if(v < 0) { fprintf(stderr, "%s arg must be at least 0\n", o.c_str()); return 1; }
-			(o == "--pen-cansplice" ? P.pen_cansplice : o == "--pen-noncansplice" ? P.pen_noncansplice : P.pen_conflictsplice) = v;
-		}
-		else if(o == "--pen-canintronlen" || o == "--pen-intronlen" || o == "--pen-noncanintronlen") {   // PARSE_FUNC: only the given fields change
-			const bool nc = o == "--pen-noncanintronlen";
-			const std::string& v = opts[++i];
-			const uint32_t t = v[0] == 'C' ? 1 : v[0] == 'L' ? 2 : v[0] == 'S' ? 3 : v[0] == 'G' ? 4 : 0;
-			if(!t) { fprintf(stderr, "Error: bad function type in %s %s\n", o.c_str(), v.c_str()); return 1; }
-			(nc ? P.pen_noncanintronlen_type : P.pen_canintronlen_type) = t;
-			const size_t c1 = v.find(',');
-			if(c1 != std::string::npos) {
-				(nc ? P.pen_noncanintronlen_const : P.pen_canintronlen_const) = atof(v.c_str() + c1 + 1);
-				const size_t c2 = v.find(',', c1 + 1);
-				if(c2 != std::string::npos) (nc ? P.pen_noncanintronlen_coeff : P.pen_canintronlen_coeff) = atof(v.c_str() + c2 + 1);
-			}
-		}
+	{   // -k / --max-seeds and the presets wait for the index type (hisat2.cpp:1882-1909, 3903)
+		h2g_index_info info;
+		if(h2g_index_get_info(ix, &info) != H2G_OK) die("h2g_index_get_info");
+		h2g_align_params_presets(&P, (int)info.linear, &presets);
 	}
-	// presets and the -k / --max-seeds defaults are resolved after every option was read, whatever their order (hisat2.cpp:1882-1909, 3903)
-	if(dta) {   // hisat2.cpp:3920, 4078-4079: after every option was read
-		P.min_anchor_len = 15; P.min_anchor_len_noncan = 20;
-		P.pen_noncanintronlen_type = 4; P.pen_noncanintronlen_const = -8.0; P.pen_noncanintronlen_coeff = 2.0;
-	}
-	{   // COST_MODEL_CONSTANT: every mismatch costs the maximum (aligner_seed_policy.cpp:279, scoring.h:129); a --mp sets the quality model again (:418)
-		bool saw_mp = false;
-		for(const std::string& o : opts) if(o == "--mp") saw_mp = true;
-		if(ignore_quals && !saw_mp) P.mm_min = P.mm_max;
-	}
-	P.xs_only = xs_only ? 1 : 0;
-	P.avoid_pseudogene = avoid_pseudogene ? 1 : 0; P.transcriptome_mapping_only = tmo ? 1 : 0; P.no_anchorstop = no_anchorstop ? 1 : 0;
-	P.use_haplotype = use_haplotype ? 1 : 0;
-	P.max_alts_tried = (uint32_t)max_alts_tried;
-	P.max_frag_len = (uint32_t)max_frag_len;
-	P.min_frag_len = (uint32_t)min_frag_len; P.pe_orientation = (uint32_t)pe_orientation; P.nofw = nofw ? 1 : 0; P.norc = norc ? 1 : 0;
-	P.seed = (uint32_t)seed_arg;
-	h2g_align_params_presets(&P, ix, saw_k ? 1 : 0, k_arg, max_seeds_arg, sensitive ? 1 : 0, very_sensitive ? 1 : 0);
 	if(!P.no_spliced_alignment && P.max_intronlen > 0xfffffu) {
 		fprintf(stderr, "hisat2-align-amd: --max-intronlen %u is beyond the 1048575 bases a splice edit holds here\n", P.max_intronlen);
 		return 1;
@@ -964,7 +853,7 @@ int main(int argc, char** argv) {
 		}
 		h2g_sam_set_splice_sites(sam, sites.data(), sites.size(), ss_window);
 	};
-	if(!nospliced && (!known_ss.empty() || !novel_ss.empty())) {
+	if(!P.no_spliced_alignment && (!known_ss.empty() || !novel_ss.empty())) {
 		for(int pass = 0; pass < 2; pass++) {
 			const std::string& fn = pass == 0 ? known_ss : novel_ss;
 			if(fn.empty()) continue;
@@ -984,14 +873,14 @@ int main(int argc, char** argv) {
 		}
 		publish_sites();
 	} else if(temp_ss) publish_sites();                    // (the window of the wave scheme; the sites arrive wave after wave)
-	if(!temp_ss && !nospliced && !novel_out.empty() && h2g_sam_novel_splice_sites_text(sam, nullptr, 0) > 0) {
+	if(!temp_ss && !P.no_spliced_alignment && !novel_out.empty() && h2g_sam_novel_splice_sites_text(sam, nullptr, 0) > 0) {
 		// write (the outfile) + read (a file's or the index's sites) without the temporary-site window: the reference then lets every read see
 		// the junctions of whichever reads its threads happened to finish first (window 0, hisat2.cpp:3687, :4092-4093) — not a function of the input
 		fprintf(stderr, "hisat2-align-amd: --novel-splicesite-outfile with --no-temp-splicesite and a splice-site database (file or --ss index) "
 		        "makes the reference's output depend on thread timing; drop --no-temp-splicesite (output == hisat2 -p <int> --reorder)\n");
 		return 1;
 	}
-	if(temp_ss || (!nospliced && !novel_out.empty())) h2g_sam_collect_novel_sites(sam, 1);   // SpliceSiteDB's `write` (hisat2.cpp:4092)
+	if(temp_ss || (!P.no_spliced_alignment && !novel_out.empty())) h2g_sam_collect_novel_sites(sam, 1);   // SpliceSiteDB's `write` (hisat2.cpp:4092)
 	h2g_sam_set_templatelen_adjustment(sam, tlen_adjust);
 	h2g_sam_set_report_policy(sam, report_discordant, report_mixed);
 	for(const auto& r : rg_args) h2g_sam_add_read_group(sam, r.first ? r.second.c_str() : nullptr, r.first ? nullptr : r.second.c_str());

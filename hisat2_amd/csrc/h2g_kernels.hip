@@ -1989,31 +1989,6 @@ extern "C" int h2g_device_count(void) { int n = 0; if(hipGetDeviceCount(&n) != h
 
 extern "C" void h2g_align_params_init(h2g_align_params* p, const h2g_index* ix) { align_params_defaults(p, !ix || ix->dg.linear); }
 
-// hisat2.cpp applies its presets AFTER every option was read, and the index type decides the default -k:
-//   khits starts at 10 (:336); -k sets it and saw_k (:1316-1322); --sensitive: bowtie2_dp 0 -> 1, khits < 10 -> 10 (+ saw_k),
-//   --score-min L,0,-0.5 (:1892-1901); --very-sensitive: bowtie2_dp 2, khits < 30 -> 30 (+ saw_k), L,0,-1 (:1902-1909);
-//   without saw_k khits = 5 on a linear index, 10 on a graph (:3903-3906); --max-seeds 0 -> max(5, 2 khits) (:3174-3176).
-// So `--sensitive` alone keeps -k 5 on a linear index, and a preset's --score-min wins over an explicit one.
-extern "C" void h2g_align_params_presets(h2g_align_params* p, const h2g_index* ix, int saw_k, uint32_t k_arg, uint32_t max_seeds_arg,
-                                         int sensitive, int very_sensitive)
-{
-	if(!p) return;
-	uint32_t khits = saw_k ? k_arg : 10u;
-	bool sawk = saw_k != 0;
-	if(sensitive) {
-		if(p->bowtie2_dp == 0) p->bowtie2_dp = 1;
-		if(khits < 10) { khits = 10; sawk = true; }
-		p->score_min_type = 2; p->score_min_const = 0.0; p->score_min_coeff = (double)(-0.5f);
-	} else if(very_sensitive) {
-		p->bowtie2_dp = 2;
-		if(khits < 30) { khits = 30; sawk = true; }
-		p->score_min_type = 2; p->score_min_const = 0.0; p->score_min_coeff = (double)(-1.0f);
-	}
-	if(!sawk) khits = (!ix || ix->dg.linear) ? 5u : 10u;
-	p->khits = khits;
-	p->kseeds = max_seeds_arg ? max_seeds_arg : (khits * 2 > 5 ? khits * 2 : 5);
-}
-
 extern "C" h2g_status h2g_set_read_names(h2g_stream* s, const char* bytes, const uint32_t* offs, size_t n) {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
 	if(!s || !bytes || !offs || n != s->cur().n_reads || n == 0) return H2G_ERR_ARG;

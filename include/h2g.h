@@ -368,12 +368,24 @@ H2G_EXPORT void       h2g_align_params_init(h2g_align_params*, const h2g_index*)
  * it flags YF:Z:NS (default L,0,(double)0.15f, as h2g_align_params_init) */
 struct h2g_sam;
 H2G_EXPORT void       h2g_sam_set_n_ceil(struct h2g_sam*, uint32_t type, double constant, double coeff);
+/* The reference's alignment options (csrc/h2g_options.cpp: host only, needs no device and no index): every rule by which an option changes
+ * a field of h2g_align_params.  The command line and the Python binding both parse through these three calls.
+ * h2g_align_option_arity: -1 = not an alignment option, 0 = a flag, 1 = takes one argument (aliases such as --minins, --maxins, --tmo,
+ * --pen-intronlen included). */
+H2G_EXPORT int        h2g_align_option_arity(const char* name);
+/* what the options leave for h2g_align_params_presets, which needs the index type */
+typedef struct { uint32_t saw_k, k_arg, max_seeds_arg, sensitive, very_sensitive; } h2g_align_presets;
+/* Applies opts[0..n) (names known to h2g_align_option_arity, each followed by its argument when its arity is 1) to *p in command-line order,
+ * then what the reference applies after every option was read and that does not depend on the index: --dta's anchor minima and
+ * --pen-noncanintronlen G,-8,2; --ignore-quals without --mp.  Fills *pre.  On a faulty option returns H2G_ERR_ARG with the message (the
+ * reference's wording, no newline) in err[0..err_cap); *p and *pre are then unspecified. */
+H2G_EXPORT h2g_status h2g_align_params_apply_options(h2g_align_params* p, h2g_align_presets* pre, const char* const* opts, size_t n,
+                                                     char* err, size_t err_cap);
 /* The reference applies its presets after ALL options were read (hisat2.cpp:1882-1909) and lets the index type decide the
  * default -k (:3903-3906): khits = saw_k ? k_arg : 10; --sensitive: bowtie2_dp 0 -> 1, khits < 10 -> 10 (counts as saw_k),
  * --score-min L,0,-0.5; --very-sensitive: bowtie2_dp 2, khits < 30 -> 30, L,0,-1; without saw_k khits = 5 (linear) / 10 (graph);
- * max_seeds_arg 0 -> max(5, 2 khits) (:3174).  Call it last, after every other field of *p was set from the options. */
-H2G_EXPORT void       h2g_align_params_presets(h2g_align_params* p, const h2g_index* ix, int saw_k, uint32_t k_arg, uint32_t max_seeds_arg,
-                                               int sensitive, int very_sensitive);
+ * max_seeds_arg 0 -> max(5, 2 khits) (:3174).  linear: h2g_index_info.linear.  Call it last, after h2g_align_params_apply_options. */
+H2G_EXPORT void       h2g_align_params_presets(h2g_align_params* p, int linear, const h2g_align_presets* pre);
 /* Explicit per-read PRNG seeds for the selected resident batch, in place of genRandSeed (hisat2.cpp:3311-3314, --non-deterministic: Read::seed of
  * mate 1 and mate 2 drawn from a RandomSource).  seeds1 / seeds2: [n] (n = the batch's read count); seeds2 is read by paired runs only, and a paired run
  * with seeds1 but no seeds2 is refused.  A pair's PRNG starts from seeds1[i] ^ seeds2[i] when both mates pass the filters (length, --n-ceil) and from
