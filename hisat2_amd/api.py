@@ -357,6 +357,15 @@ def _chk(rc, what):
         raise H2GError(f"{what} failed: status {rc} ({msg.decode() if msg else ''})")
 
 
+def mstreams_policy(units, last_bails, linear, pinned=0, light=2):
+    """development hook (h2g_mstreams_policy, a pure host function): the machine streams a run keeps in rotation for a batch of `units` pairs whose
+    latest finished fast pass handed on `last_bails`; pinned = H2G_MSTREAMS (0: not set), light = H2G_MSTREAMS_LIGHT"""
+    f = lib().h2g_mstreams_policy
+    f.argtypes = [C.c_ulonglong, C.c_uint, C.c_int, C.c_uint, C.c_uint]
+    f.restype = C.c_uint
+    return int(f(int(units), int(last_bails), int(bool(linear)), int(pinned), int(light)))
+
+
 class Index:
     def __init__(self, base=None, device=0, synth_sides=None, seed=20260925, graph=False):
         L = lib()
@@ -653,6 +662,17 @@ class Stream:
         f = lib().h2g_stream_tune
         f.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         _chk(f(self.h, key.encode(), int(value)), "h2g_stream_tune " + key)
+
+    def probe(self, key):
+        """development hook, read-only (h2g_stream_probe): "mstreams_rotation" (machine streams in rotation for the last run behind a fast pass),
+        "mstreams_used" (those that ever entered it), "mstreams_created", "pools" (workspace pools allocated), "lanes" """
+        f = lib().h2g_stream_probe
+        f.argtypes = [C.c_void_p, C.c_char_p]
+        f.restype = C.c_long
+        v = int(f(self.h, key.encode()))
+        if v < 0:
+            raise H2GError("h2g_stream_probe: no such name: " + key)
+        return v
 
     def align_pairs_fetch_compact(self, first=0, n=None, pinned=None):
         """-> (res, rec1, boffs1, rec2, boffs2): compact records (40 bytes + 12 per edit held, 8-aligned) as uint8 arrays, byte offsets [n + 1] per mate.

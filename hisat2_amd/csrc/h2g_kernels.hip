@@ -81,12 +81,19 @@ static DGfm dg_now(h2g_index* ix) {
 
 // The general machine's pass over run k's hand-ons is a LATENCY CHAIN: its length is its longest reads' (hundreds of dependent trips of
 // 60-100 us on a 115 KB workspace), not their number — 30 ms behind a 14.5 ms fast pass on the random GRCh38-size genome, 118 ms behind a 25 ms
-// fast pass on repeat-structured sequence (profiles/r04_NOTES.md §4-§6).  The stream therefore keeps up to H2G_MSTREAMS_MAX such passes in flight,
-// one per machine stream, next to the fast passes of the following runs: run k's pass goes to machine stream k % M and the hand-on list, the
-// counters and the argument block are buffered M + 1 deep.  M is a property of the stream (h2g_stream_tune "mstreams", H2G_MSTREAMS; default
-// H2G_MSTREAMS_DEFAULT).  A caller sees no difference: results are complete when a fetch / sync returns.
+// fast pass on repeat-structured sequence (profiles/r04_NOTES.md §4-§6).  The stream therefore keeps such passes in flight next to the fast passes of
+// the following runs.  Two numbers describe that, and they are not the same thing (profiles/r08_mstreams.md):
+//   LANES (M, H2G_MSTREAMS_MAX unless pinned): run k is lane k % M.  Everything that OUTLIVES a pass rotates by lane — the parts of the pair-overflow,
+//     long-edit and XL areas and their cursors, ledits_touched, ev_mach, and the hand-on list, counters and argument block, buffered M + 1 deep.  This is
+//     the caller's contract (fetch a batch before M further runs are queued) and does not follow the load.
+//   MACHINE STREAMS IN ROTATION (S <= M): lane m's pass runs on HIP stream mst[m % S] with that stream's workspace pools and overflow list, which a pass
+//     only needs while it runs (passes on one HIP stream are in order).  HIP streams share the few hardware queues of a process and serialise there, so S
+//     follows the load (mstreams_policy): H2G_MSTREAMS_LIGHT_DEFAULT while a linear index's fast pass hands on little — the passes are short and two in
+//     flight cover them — and H2G_MSTREAMS_MAX once it hands on more than 1.5 % of the batch, or on a graph index.
+// H2G_MSTREAMS / h2g_stream_tune "mstreams" pins both to one value (M = S); H2G_MSTREAMS_LIGHT / "mstreams_light" sets the light S.  A caller sees no
+// difference: results are complete when a fetch / sync returns.
 #define H2G_MSTREAMS_MAX 8
-#define H2G_MSTREAMS_DEFAULT 8
+#define H2G_MSTREAMS_LIGHT_DEFAULT 2
 #define H2G_NBUF (H2G_MSTREAMS_MAX + 1)
 // CUs the fast pass's persistent grid leaves free for the machine passes: -1 = as many as M passes may hold; 0 = none — the fast pass asks for every
 // CU and the hardware dispatcher places machine workgroups as CUs come free (the fast pass draws its reads from one counter, so a late workgroup costs nothing)
@@ -130,8 +137,13 @@ struct h2g_stream {
 	hipStream_t st = nullptr;
 	// the general machine's pass over a fast pass's hand-ons runs on one of these, next to the fast passes of the FOLLOWING two batches:
 	// its few reads are long latency chains (about a fast pass's duration whatever their number), so two such passes are kept in flight
-	hipStream_t mst[H2G_MSTREAMS_MAX] = {};
-	unsigned mstreams = H2G_MSTREAMS_DEFAULT;   // machine passes kept in flight (1 .. H2G_MSTREAMS_MAX)
+	hipStream_t mst[H2G_MSTREAMS_MAX] = {};     // all created with the context (h2g_stream_create: their order matters); mst[0 .. n_mst) have entered the rotation, only those ever held work
+	hipEvent_t ev_rot[H2G_MSTREAMS_MAX] = {};   // what a machine stream holds when the rotation changes
+	unsigned n_mst = 0;
+	unsigned mstreams = 0;                      // pinned (1 .. H2G_MSTREAMS_MAX): lanes = machine streams in rotation = this; 0: S follows the load
+	unsigned mstreams_light = H2G_MSTREAMS_LIGHT_DEFAULT;   // S of the light regime
+	unsigned rot = 0;                           // machine streams in rotation for the last run behind a fast pass (0: there was none yet)
+	unsigned warm_mask = 0;                     // bit j: mst[j] has run both machine kernels once
 	bool st2_busy = false;            // a machine stream may hold work
 	hipEvent_t ev_fast[H2G_NBUF], ev_mach[H2G_NBUF];
 	unsigned gen = 0;                 // go_run generation: bail list, counters and argument block are buffered H2G_NBUF deep by gen % H2G_NBUF
@@ -196,8 +208,8 @@ struct h2g_stream {
 	hipEvent_t ev[12];
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
-	bool mstreams_warm = false;          // every machine stream has run its two kernels once (go_run, large batches)
-	unsigned long long* d_warm_cnt = nullptr;   // counter block of those empty launches
+	unsigned long long* d_warm_cnt = nullptr;   // counter block of the machine streams' empty first launches (go_warmup); word H2G_CNT_NO_SECOND, which nobody writes, is their list's count
+	uint8_t* d_warm_rows = nullptr;             // ... and the result rows they are given: never the current batch's
 };
 
 // Large arrays travel through page-locked staging buffers filled by several threads: a pageable hipMemcpy of a human-size index (4.7 GB) was most of its 1.2 s load (round 6).
@@ -689,9 +701,10 @@ extern "C" h2g_status h2g_index_synth_graph_sides(uint64_t num_sides, uint64_t s
 }
 
 // ------------------------------------------------------------------------------------------ stream
-// A stream of this library is 2 + H2G_MSTREAMS_MAX HIP streams (the fast launches', the drain launches', one per machine pass in flight) whose kernels must be able to run side by side.  ROCclr maps HIP streams onto
+// A stream of this library USES 2 + S HIP streams (the fast launches', the drain launches', and the S <= H2G_MSTREAMS_MAX machine streams in rotation: 2 while the fast pass hands on little) whose kernels must be able to run side by side.  ROCclr maps HIP streams onto
 // GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue serialise — measured: four machine passes "in flight" on the
-// default 4 queues ran one after the other (repeat-structured leg: 127 ms per step against 78 ms with 16 queues; profiles/r05_NOTES.md).  The library
+// default 4 queues ran one after the other (repeat-structured leg: 127 ms per step against 78 ms with 16 queues; profiles/r05_NOTES.md), and a machine pass or a drain launch in
+// front of a fast launch on a shared queue is idle CUs (profiles/r08_mstreams.md): a context opens no more machine streams than its load needs.  The library
 // does not set the variable: the number of hardware queues a process opens is the host's and the caller's choice, and results do not depend on it.
 
 extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t max_bases, h2g_stream** out) {
@@ -699,8 +712,11 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 	HIPCHK(hipSetDevice(ix->device));
 	h2g_stream* s = new h2g_stream();
 	s->ix = ix; s->max_reads = max_reads; s->max_bases = max_bases;
+	// Every HIP stream of the context is created here, in this order, whatever the rotation will be: the runtime places a stream on a hardware queue by its place among the
+	// process's streams, and the place decides which launches serialise (profiles/r08_mstreams.md §2: the same two machine streams in rotation, created on first use
+	// behind the drain stream, 18.4 ms per step; created here, 10.8).  A stream that never enters the rotation never runs a kernel, holds no pools and costs nothing.
 	HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) HIPCHK(hipStreamCreateWithFlags(&s->mst[k], hipStreamNonBlocking));
+	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { HIPCHK(hipStreamCreateWithFlags(&s->mst[k], hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&s->ev_rot[k], hipEventDisableTiming)); }
 	HIPCHK(hipStreamCreateWithFlags(&s->dst, hipStreamNonBlocking));
 	HIPCHK(hipHostMalloc((void**)&s->h_fast_args, sizeof(FastArgs) * 2 * H2G_NBUF));
 	HIPCHK(hipHostMalloc((void**)&s->h_bails, 4 * H2G_NBUF)); for(int k = 0; k < H2G_NBUF; k++) s->h_bails[k] = 0;
@@ -727,7 +743,9 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		s->tune.tail = (int)env("H2G_FAST_TAIL", H2G_DEFAULT_TAIL); s->tune.tail_auto = getenv("H2G_FAST_TAIL") ? 0 : 1; s->tune.align_mate = (int)env("H2G_FAST_AM", H2G_DEFAULT_ALIGN_MATE);
 		s->tune.orphan = (int)env("H2G_FAST_ORPHAN", -1); s->tune.drain_grid = (int)env("H2G_DRAIN_GRID", H2G_DRAIN_GRID); s->tune.mate_handover = (int)env("H2G_FAST_MATE_HANDOVER", -1);
 		s->tune.mach_total = (unsigned)env("H2G_MACH_TOTAL", H2G_MACH_TOTAL); s->tune.mach_total_auto = getenv("H2G_MACH_TOTAL") ? 0 : 1; s->tune.fast_reserve = (int)env("H2G_FAST_RESERVE", H2G_FAST_RESERVE_DEFAULT);
-		{ const long m = env("H2G_MSTREAMS", H2G_MSTREAMS_DEFAULT); s->mstreams = (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); }
+		auto clampm = [](long m) { return (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); };
+		if(getenv("H2G_MSTREAMS")) s->mstreams = clampm(env("H2G_MSTREAMS", 0));   // pinned
+		s->mstreams_light = clampm(env("H2G_MSTREAMS_LIGHT", H2G_MSTREAMS_LIGHT_DEFAULT));
 	}
 	*out = s;
 	return H2G_OK;
@@ -735,7 +753,7 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 
 extern "C" void h2g_stream_free(h2g_stream* s) {
 	if(!s) return;
-	(void)hipStreamSynchronize(s->st); (void)hipStreamSynchronize(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipStreamSynchronize(s->mst[k]);
+	(void)hipStreamSynchronize(s->st); (void)hipStreamSynchronize(s->dst); for(unsigned k = 0; k < s->n_mst; k++) (void)hipStreamSynchronize(s->mst[k]);
 	(void)hipFree(s->d_seed);
 	(void)hipFree(s->d_counters); for(int k = 0; k < 2 * H2G_MSTREAMS_MAX; k++) { (void)hipFree(s->pool[k].ws); (void)hipFree(s->pool[k].gws); (void)hipFree(s->pool[k].sw); (void)hipFree(s->pool[k].sc); }
 	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipFree(s->d_ovf_list[k]);
@@ -744,7 +762,7 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	(void)hipFree(s->d_drain_slots); (void)hipFree(s->d_drain_sc);
 	for(int k = 0; k < 2; k++) (void)hipEventDestroy(s->ev_dr[k]);
 	(void)hipFree(s->d_fast_gws); (void)hipFree(s->d_fast_sc); (void)hipFree(s->d_sw_ws); (void)hipFree(s->d_sw_states); (void)hipFree(s->dbg_buf);
-	(void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt);
+	(void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt); (void)hipFree(s->d_warm_rows);
 	for(const BatchCtx& B : s->batch) {
 		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
 		(void)hipFree(B.d_quals2); (void)hipFree(B.d_names2); (void)hipFree(B.d_name_offs2); (void)hipFree(B.d_rout); (void)hipFree(B.d_aln); (void)hipFree(B.d_pout); (void)hipFree(B.d_paln[0]); (void)hipFree(B.d_paln[1]);
@@ -754,14 +772,14 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	}
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
 	for(int i = 0; i < 12; i++) (void)hipEventDestroy(s->ev[i]);
-	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipStreamDestroy(s->mst[k]); (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
+	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { (void)hipStreamDestroy(s->mst[k]); (void)hipEventDestroy(s->ev_rot[k]); } (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
 	delete s;
 }
 
 // the machine streams, when one may hold work (st2_busy): waits for every one of them, then clears the flag
 static hipError_t sync_mach(h2g_stream* s) {
 	if(!s->st2_busy) return hipSuccess;
-	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { const hipError_t e = hipStreamSynchronize(s->mst[k]); if(e != hipSuccess) return e; }
+	for(unsigned k = 0; k < s->n_mst; k++) { const hipError_t e = hipStreamSynchronize(s->mst[k]); if(e != hipSuccess) return e; }
 	s->st2_busy = false;
 	return hipSuccess;
 }
@@ -2219,10 +2237,22 @@ struct GoPlan {
 	bool linear, spl, xl, big_main, fast, second;
 	const GoUnit *U, *L;           // the main pass's unit; the large-workspace unit (the second pass, the machine streams' warm-up)
 	uint32_t geo[4], lgeo[4];      // their geometries: [0] threads per workgroup, [1] reads in flight per workgroup
-	unsigned grid, M, bgrid;       // workgroups of the main pass; machine passes in flight (per-run buffers: M + 1 deep); workgroups of a second pass
+	unsigned grid, M, bgrid;       // workgroups of the main pass; lanes (per-run buffers: M + 1 deep; area parts: M); workgroups of a second pass
+	unsigned S;                    // machine streams in rotation: lane m's pass runs on mst[m % S]
 	unsigned mach_cap, pool_cap;   // workgroups of one machine pass behind a fast pass, and what its pools are sized for
 	size_t units;                  // batch units: pairs, or two unpaired reads
 };
+// Machine streams in rotation, from the load (no device calls, no state): a pinned value as it is; a graph index, and a linear one whose latest finished
+// fast pass handed on more than 1.5 % of the batch (the regime of mach_total below: the machine's passes are the step), every lane its own stream; otherwise `light`.
+static unsigned mstreams_policy(size_t units, uint32_t last_bails, bool linear, unsigned pinned, unsigned light) {
+	if(pinned) return pinned > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : pinned;
+	if(!linear || (size_t)last_bails * 1000 > units * 15) return H2G_MSTREAMS_MAX;
+	return light < 1 ? 1u : light > H2G_MSTREAMS_MAX ? (unsigned)H2G_MSTREAMS_MAX : light;
+}
+// development hook (tests): the policy above, as it is
+extern "C" __attribute__((visibility("default"))) unsigned h2g_mstreams_policy(unsigned long long units, unsigned last_bails, int linear, unsigned pinned, unsigned light) {
+	return mstreams_policy((size_t)units, last_bails, linear != 0, pinned, light);
+}
 static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paired) {
 	GoPlan plan, *g = &plan;
 	const size_t n_reads = s->cur().n_reads;
@@ -2257,13 +2287,14 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 	if(g->big_main && maxblocks > 32) maxblocks = 32;        // ~1.3 MB of workspace per read in flight
 	if(g->xl && maxblocks > 12) maxblocks = 12;              // XL: 18.7 MB per read in flight, 12 x 128 of them (h2g_go_xl.h)
 	g->grid = (unsigned)(want < 1 ? 1 : (want > maxblocks ? maxblocks : want));
-	g->M = s->mstreams;
-	// workgroups of one machine pass behind a fast pass: mach_total / M.  The default policy follows the batch: when the fast pass hands on more than 1.5 % of a linear index's
+	g->M = s->mstreams ? s->mstreams : H2G_MSTREAMS_MAX;
+	// workgroups of one machine pass behind a fast pass: mach_total / M (the lanes, whatever S: a pass is the same pass on any stream).  The default policy follows the batch: when the fast pass hands on more than 1.5 % of a linear index's
 	// batch (repeat-structured sequence: the machine's passes, not the fast pass, are the step) the passes get 192 workgroups in all instead of 128 — measured on the repeat-structured
 	// leg 44.7 -> 40.3 ms per step, while the fast-pass-bound legs (0.8 % handed on) lose 3 % with it (profiles/r05_NOTES.md §6).  The pools are sized for the larger share from the start.
 	const bool mt_auto = s->tune.mach_total_auto != 0 && g->linear;
 	g->units = paired ? n_reads : (n_reads + 1) / 2;
 	const unsigned mach_total_now = mt_auto && (size_t)s->last_bails * 1000 > g->units * 15 ? 192u : s->tune.mach_total;
+	g->S = mstreams_policy(g->units, s->last_bails, g->linear, s->mstreams, s->mstreams_light);
 	g->mach_cap = mach_total_now / g->M;
 	if(g->mach_cap > H2G_MACH_MAXGRID) g->mach_cap = H2G_MACH_MAXGRID;
 	if(g->mach_cap < 1) g->mach_cap = 1;
@@ -2285,11 +2316,11 @@ struct FastPlan {
 // what a run queued now carries through to the end of go_run
 struct GoRun {
 	GoArgs A; DExonTbl X; XlPairs XP;   // the main pass's arguments (X: --avoid-pseudogene's exons, an argument of their own)
-	unsigned gsel, msel;           // the per-run buffer set (gen % (M + 1)) and the machine stream (gen % M)
+	unsigned gsel, msel, ssel;     // the per-run buffer set (gen % (M + 1)), the lane (gen % M) and its machine stream (lane % S)
 	unsigned long long* cblk;      // the run's counter block (h2g_go_args.h)
 	FastPlan f;
 	hipStream_t ms;                // the stream of the machine's passes ...
-	unsigned mach_grid, psel;      // ... the main pass's workgroups there, and its pools, overflow list and long-edit part
+	unsigned mach_grid, psel, qsel;   // ... the main pass's workgroups there, its long-edit part (the lane's), and its pools and overflow list (the stream's)
 	uint32_t* ovl;                 // the main pass's overflow list (+ its count behind it)
 };
 
@@ -2314,20 +2345,34 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	A.paired = paired ? 1u : 0u;
 }
 
-// the main pass's per-lane scratch: behind a fast pass the machine works on stream gen % M with that stream's pools, on at most mach_cap workgroups
+// The machine streams in rotation for a run behind a fast pass: mst[0 .. S); n_mst counts those that ever entered (the others hold nothing to wait for).  When S changes, lane m moves from stream
+// m % S' to m % S: what it shares with its earlier passes (its parts' cursors, the rows of a batch) was ordered by the stream, so every stream of the new
+// rotation waits for everything queued on the streams in use — on the device: the host never waits here.
+static int go_rotation(h2g_stream* s, const GoPlan& g) {
+	if(s->n_mst < g.S) s->n_mst = g.S;
+	if(s->rot && s->rot != g.S && s->st2_busy) {
+		for(unsigned j = 0; j < s->rot; j++) HIPCHK(hipEventRecord(s->ev_rot[j], s->mst[j]));
+		for(unsigned k = 0; k < g.S; k++) for(unsigned j = 0; j < s->rot; j++) if(j != k) HIPCHK(hipStreamWaitEvent(s->mst[k], s->ev_rot[j], 0));
+	}
+	s->rot = g.S;
+	return H2G_OK;
+}
+
+// the main pass's per-lane scratch: behind a fast pass the machine works on stream (gen % M) % S with that stream's pools, on at most mach_cap workgroups
 static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoArgs* A) {
 	const size_t pgrid = g.fast && g.grid > g.pool_cap ? (size_t)g.pool_cap : (size_t)g.grid;
 	int rc;
 	if(g.fast && s->cur().n_reads >= 200000) {
-		// large batches (a streaming caller's): every machine stream's pools exist before the first pass that could need them — an allocation
+		// large batches (a streaming caller's): the pools of every machine stream in rotation exist before the first pass that could need them — an allocation
 		// in the middle of a queue of runs (gigabytes, synchronous) would stall all of them.  The stream's SECOND run pays for it, once (round 6: a caller with one
-		// batch — a command line over a million pairs — never needs streams 1 .. M - 1: their 30 GB of pools were a second of its three).
+		// batch — a command line over a million pairs — never needs streams 1 .. S - 1: their 30 GB of pools were a second of its three); a stream that enters the
+		// rotation later (the regime turns heavy) gets its pools then.
 		// (Small batches keep allocating a machine stream's pools when it is first used.)
 		GoArgs scratch = *A;
-		for(unsigned m = 0; m < g.M && s->gen >= 1; m++) {
+		for(unsigned m = 0; m < g.S && s->gen >= 1; m++) {
 			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, &scratch))) return rc;
 			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &scratch))) return rc;
-			// ... and its overflow list, and the stream itself (a HIP stream gets its hardware queue when it is first used)
+			// ... and its overflow list
 			if(!s->d_ovf_list[m]) { HIPCHK(hipMalloc((void**)&s->d_ovf_list[m], (s->max_reads + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
 		}
 		for(unsigned b = 0; b < g.M + 1; b++) {      // the per-run buffers of every generation
@@ -2336,7 +2381,7 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
 		}
 	}
-	return go_pool_for(s, g.fast ? 2 * (int)(s->gen % g.M) : 0, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, A);
+	return go_pool_for(s, g.fast ? 2 * (int)((s->gen % g.M) % g.S) : 0, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, A);
 }
 
 // the batch's result rows (grown to this run's -k), the pairs' overflow area and the XL units' side area
@@ -2360,7 +2405,7 @@ static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const 
 		if((rc = grow((void**)b.d_paln, &b.paln_alloc, s->max_reads * (size_t)pslots, sizeof(h2g_alnres), 2))) return rc;
 		b.pair_slots = pslots;
 		A.O.pout = b.d_pout; A.O.paln[0] = b.d_paln[0]; A.O.paln[1] = b.d_paln[1]; A.O.pair_slots = pslots;
-		// One part per machine stream: the machine passes of M queued runs may be in flight together and each takes its blocks
+		// One part per lane: the machine passes of M queued runs may be in flight together and each takes its blocks
 		// from its own cursor.  Block offsets (PairOut::pad) are relative to the whole area, so whichever pass wrote a pair last, its block is found.
 		const size_t ovf_cap = s->max_reads / 4 > 65536 ? s->max_reads / 4 : 65536;   // records per part
 		if(s->paln_ovf_cap < ovf_cap || s->paln_ovf_parts < g.M) {
@@ -2394,16 +2439,16 @@ static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const 
 }
 
 // the run's counter block and cursors: the fast pass's hand-on list, the counters and its argument block are buffered H2G_NBUF deep — the general machine's
-// pass over run k's hand-ons goes to machine stream k % M and may still be under way while the fast passes of the following runs run
+// pass over run k's hand-ons (lane k % M, on machine stream lane % S) may still be under way while the fast passes of the following runs run
 static int go_counters(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	GoArgs& A = r->A;
-	r->gsel = s->gen % (g.M + 1); r->msel = s->gen % g.M;
+	r->gsel = s->gen % (g.M + 1); r->msel = s->gen % g.M; r->ssel = r->msel % g.S;
 	r->cblk = s->d_counters + H2G_CNT_BLOCK * r->gsel;
 	HIPCHK(hipStreamWaitEvent(s->st, s->ev_mach[r->gsel], 0));          // run k - NB's machine pass: done with this set of buffers
 	HIPCHK(hipMemsetAsync(r->cblk, 0, H2G_CNT_BLOCK * sizeof(unsigned long long), s->st));
 	A.counters = r->cblk;
 	A.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_MAIN);
-	if(paired) {   // the cursor starts at this machine stream's part of the area
+	if(paired) {   // the cursor starts at this lane's part of the area
 		const uint32_t half = g.fast ? r->msel : 0u;
 		A.O.ovf_cursor = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_OVF_CURSOR);
 		A.O.ovf_cap = (uint32_t)((half + 1) * s->paln_ovf_cap);
@@ -2459,7 +2504,7 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	// pass stayed a latency chain, 78 -> 66 ms on twice the workgroups, while the fast pass went 14.5 -> 49 ms on what was left; and the second pass
 	// on a stream of its own — the extra queues cost the common case 13 -> 20 ms per run.  Neither ships: profiles/r04_NOTES.md §6.)
 	const size_t fwant = (n_reads + 127) / 128;                                                // small batches spread over the chip
-	unsigned reserve = s->tune.fast_reserve >= 0 ? (unsigned)s->tune.fast_reserve : g.M * f->mgrid;  // (M machine passes may be in flight)
+	unsigned reserve = s->tune.fast_reserve >= 0 ? (unsigned)s->tune.fast_reserve : g.S * f->mgrid;  // (S machine passes may run side by side)
 	if(reserve > 192) reserve = 192;
 	const unsigned fmax = 256 - reserve;
 	f->fgrid = (unsigned)(fwant < 1 ? 1 : (fwant > fmax ? fmax : fwant));
@@ -2490,7 +2535,7 @@ static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 	}
 	if(!need) return H2G_OK;
 	// (every stream, whatever st2_busy and dst_busy say: the pools about to be freed may be any launch's)
-	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
+	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
 	auto grow_zeroed = [s](void** ptr, size_t* have, size_t want) -> int {     // (fresh memory is written once, on the first stream)
 		if(*have >= want) return H2G_OK;
 		const int rc = grow(ptr, have, want);
@@ -2580,13 +2625,13 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	return H2G_OK;
 }
 
-// the stream hand-off behind a fast pass: the machine works on machine stream msel (a short list on few workgroups: the next run's fast pass does not wait for it),
+// the stream hand-off behind a fast pass: the machine works on machine stream ssel (a short list on few workgroups: the next run's fast pass does not wait for it),
 // after the drain launch when there is one
 static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	const FastPlan& f = r->f;
 	const unsigned gsel = r->gsel;
 	HIPCHK(hipEventRecord(s->ev_fast[gsel], s->st));
-	r->ms = s->mst[r->msel]; s->st2_busy = true;
+	r->ms = s->mst[r->ssel]; s->st2_busy = true;
 	if(f.mgrid < r->mach_grid) r->mach_grid = f.mgrid;
 	if(f.orphan_T) {
 		// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
@@ -2609,19 +2654,19 @@ static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	return H2G_OK;
 }
 
-// the machine stream's overflow list and its part of the long-edit area
+// the machine stream's overflow list and the lane's part of the long-edit area
 static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 	GoArgs& A = r->A;
-	const unsigned psel = r->psel;
-	s->ovf_cur = psel;
-	if(!s->d_ovf_list[psel]) HIPCHK(hipMalloc((void**)&s->d_ovf_list[psel], (s->max_reads + 4) * 4));
-	r->ovl = s->d_ovf_list[psel];
+	const unsigned psel = r->psel, qsel = r->qsel;
+	s->ovf_cur = qsel;
+	if(!s->d_ovf_list[qsel]) HIPCHK(hipMalloc((void**)&s->d_ovf_list[qsel], (s->max_reads + 4) * 4));
+	r->ovl = s->d_ovf_list[qsel];
 	HIPCHK(hipMemsetAsync(r->ovl + s->max_reads, 0, 16, r->ms));
-	// the long-edit area: part psel and its cursor belong to this machine stream (the pass that used them last is over: same stream)
+	// the long-edit area: part psel and its cursor belong to this lane (the pass that used them last is over: it ran on the same stream, or go_rotation made this stream wait for it)
 	const size_t lcap = s->max_reads > (1u << 20) ? s->max_reads : (size_t)(1u << 20);
 	if(s->ledits_cap < lcap || s->ledits_parts < g.M) {
 		// (the flag stays: this run's own fast pass, already queued, has set it)
-		if(s->st2_busy) for(int k = 0; k < H2G_MSTREAMS_MAX; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
+		if(s->st2_busy) for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
 		HIPCHK(hipStreamSynchronize(s->st));
 		size_t had = 0; s->ledits_cap = 0; s->ledits_parts = 0;
 		int rc;
@@ -2640,19 +2685,28 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 
 // A machine stream's FIRST kernels cost it ~64 ms on top of their own time (lease I of round 6, `profiles/r06_i_batches_first.jsonl`: runs 1-7 of a stream 94 ms, every
 // later one 30; the kernels' own events read 10 + 20 ms throughout — the queue's scratch memory and code objects are set up when a queue first needs them).  A streaming
-// caller's SECOND run therefore runs both machine kernels once on every other machine stream (the first run may be the only one), over an empty list: with the pools, lists and per-run buffers above this is
-// everything a stream does for the first time (a bench that warms up for 5 steps then timed the first use of streams 5-7: 18.5 ms per step where the steady state is 12-13).
+// caller's SECOND run therefore runs both machine kernels once on every other machine stream in rotation that has not run them yet (the first run may be the only one), over an
+// empty list: with the pools, lists and per-run buffers above this is everything a stream does for the first time (a bench that warms up for 5 steps then timed the first use
+// of streams 5-7: 18.5 ms per step where the steady state is 12-13).  A stream that enters the rotation later is warmed by the run that brings it in.
+// The launches own everything they could write: a list whose count is a word nobody writes (zero by construction — a machine stream's overflow list may hold the deferred
+// count of an earlier run), rows and cursors of their own.
 static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, const GoRun& r) {
 	int rc;
+	const size_t warm_rows = (size_t)1 << 16;
 	if(!s->d_warm_cnt) { HIPCHK(hipMalloc((void**)&s->d_warm_cnt, H2G_CNT_BLOCK * sizeof(unsigned long long))); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
-	for(unsigned m = 0; m < g.M; m++) {
-		if(m == r.msel || !s->d_ovf_list[m]) continue;
+	if(!s->d_warm_rows) { HIPCHK(hipMalloc((void**)&s->d_warm_rows, warm_rows)); HIPCHK(hipMemset(s->d_warm_rows, 0, warm_rows)); }
+	for(unsigned m = 0; m < g.S; m++) {
+		if(m == r.ssel || ((s->warm_mask >> m) & 1u) || !s->d_ovf_list[m]) continue;
 		GoArgs W1 = r.A;
 		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.geo[1], (size_t)g.geo[0], p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
 		W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_MAIN);
-		W1.list = s->d_ovf_list[m]; W1.nlist = s->d_ovf_list[m] + s->max_reads;                                       // a count of zero (memset on this stream above)
+		W1.list = reinterpret_cast<uint32_t*>(s->d_warm_rows); W1.nlist = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_NO_SECOND);   // a count of zero
+		memset(&W1.O, 0, sizeof W1.O);
+		W1.O.rout = reinterpret_cast<ReadOut*>(s->d_warm_rows); W1.O.aln = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.aln_slots = r.A.O.aln_slots;
+		W1.O.pout = reinterpret_cast<PairOut*>(s->d_warm_rows); W1.O.paln[0] = W1.O.paln[1] = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.pair_slots = r.A.O.pair_slots;
+		W1.O.ovf = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.ledits = reinterpret_cast<h2g_edit*>(s->d_warm_rows);      // (both areas with a capacity of zero)
 		W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_OVF_CURSOR); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_LEDITS_CURSOR);
-		W1.defer_overflow = 0; W1.O.defer_list = nullptr; W1.O.defer_count = nullptr;
+		W1.defer_overflow = 0;
 		if(g.U->launch(&W1, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		if(g.second) {
 			GoArgs W2 = W1;
@@ -2660,9 +2714,9 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 			W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_SECOND);
 			if(g.L->launch(&W2, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		}
+		s->warm_mask |= 1u << m;
 	}
 	s->st2_busy = true;
-	s->mstreams_warm = true;
 	return H2G_OK;
 }
 
@@ -2674,7 +2728,7 @@ static int go_mach(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, Go
 	if(g.second) {
 		GoArgs A2 = r->A;
 		int rc;
-		if((rc = go_pool_for(s, 2 * r->psel + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &A2))) return rc;
+		if((rc = go_pool_for(s, 2 * r->qsel + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &A2))) return rc;
 		A2.counters = r->cblk + H2G_CNT_SECOND;           // (a region of its own: in H2G_GO_PROF builds a pass writes up to 96 words behind its counters)
 		A2.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_SECOND);
 		A2.list = r->ovl; A2.nlist = r->ovl + s->max_reads;   // (the count is filled by the main pass itself: MachOut::defer_list)
@@ -2682,7 +2736,7 @@ static int go_mach(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, Go
 		if(g.L->launch(&A2, &r->X, nullptr, g.bgrid, r->ms) != 0) return set_err("go() second pass launch", hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(s->ev[8], r->ms));
-	if(g.fast) HIPCHK(hipEventRecord(s->ev_mach[r->gsel], r->ms));
+	if(g.fast) { HIPCHK(hipEventRecord(s->ev_mach[r->gsel], r->ms)); s->warm_mask |= 1u << r->ssel; }
 	return H2G_OK;
 }
 
@@ -2702,6 +2756,7 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	GoRun r = {};
 	go_args(s, p, paired, g, &r);
 	if(!g.fast) HIPCHK(sync_mach(s));   // (the machine streams' pools are about to be used on the first stream)
+	else if((rc = go_rotation(s, g))) return rc;
 	if((rc = go_pools(s, p, g, &r.A)) || (rc = go_rows(s, p, paired, g, &r))) return rc;
 	(void)hipGetLastError();
 	if((rc = go_counters(s, paired, g, &r))) return rc;
@@ -2715,9 +2770,10 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	r.ms = s->st; r.mach_grid = g.grid;
 	s->ran_drain = false;
 	if(g.fast && (rc = fast_handoff(s, paired, g, &r))) return rc;
-	r.psel = g.fast ? r.msel : 0u;          // workspace pools and the overflow list of this machine stream
+	r.psel = g.fast ? r.msel : 0u;          // the lane's part of the long-edit area
+	r.qsel = g.fast ? r.ssel : 0u;          // workspace pools and the overflow list of this machine stream
 	if((rc = go_mach_lists(s, g, &r))) return rc;
-	if(g.fast && s->cur().n_reads >= 200000 && s->gen >= 1 && !s->mstreams_warm && (rc = go_warmup(s, p, g, r))) return rc;
+	if(g.fast && s->cur().n_reads >= 200000 && s->gen >= 1 && (~s->warm_mask & ((1u << g.S) - 1u) & ~(1u << r.ssel)) && (rc = go_warmup(s, p, g, r))) return rc;
 	if((rc = go_mach(s, p, g, &r))) return rc;
 	s->cnt_cur = r.cblk; s->gen++;
 	HIPCHK(hipGetLastError());
@@ -3072,12 +3128,12 @@ extern "C" h2g_status h2g_align_fetch_long_edits(h2g_stream* s, h2g_edit* out, s
 
 // development hook: measurement / debugging knobs of go_run by name.  Everything in flight is waited for first, so a change never meets a
 // queued run.  "fast" 0/1, "blocks_per_cu", "pair_slots", "no_second_pass", "mach_div", "mach_min", "dbg_read" (-1 = off), "tail", "align_mate",
-// "mstreams" (machine passes kept in flight, 1..H2G_MSTREAMS_MAX), "mach_total" (workgroups of all of them together), "fast_reserve" (CUs the fast pass leaves
+// "mstreams" (pins lanes = machine streams in rotation, 1..H2G_MSTREAMS_MAX), "mstreams_light" (machine streams in rotation while the fast pass hands on little), "mach_total" (workgroups of all of them together), "fast_reserve" (CUs the fast pass leaves
 // free: -1 = as many as the machine passes in flight may hold)
 extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream* s, const char* key, long v) {
 	if(!s || !key) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
-	for(int k_ = 0; k_ < H2G_MSTREAMS_MAX; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));   // (whatever st2_busy says: a change never meets a queued run)
+	for(unsigned k_ = 0; k_ < s->n_mst; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));   // (whatever st2_busy says: a change never meets a queued run)
 	const std::string k(key);
 	if(k == "fast") s->tune.fast = (int)v; else if(k == "blocks_per_cu") s->tune.blocks_per_cu = (int)v; else if(k == "pair_slots") s->tune.pair_slots = (int)v;
 	else if(k == "no_second_pass") s->tune.no_second_pass = (int)v; else if(k == "mach_div") s->tune.mach_div = (unsigned)v; else if(k == "mach_min") s->tune.mach_min = (unsigned)v;
@@ -3086,9 +3142,23 @@ extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream
 	else if(k == "fast_reserve") s->tune.fast_reserve = (int)v;
 	else if(k == "mate_handover") s->tune.mate_handover = (int)v;
 	else if(k == "orphan") s->tune.orphan = (int)v; else if(k == "drain_grid") s->tune.drain_grid = (int)(v < 1 ? 1 : v > 128 ? 128 : v);
-	else if(k == "mstreams") { s->mstreams = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v); s->gen = 0; }   // (nothing is in flight: every buffer set is free)
+	else if(k == "mstreams") { s->mstreams = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v); s->gen = 0; }   // pins lanes = machine streams (nothing is in flight: every buffer set is free)
+	else if(k == "mstreams_light") s->mstreams_light = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v);   // S of the light regime (mstreams_policy)
 	else return H2G_ERR_ARG;
 	return H2G_OK;
+}
+
+// development hook (tests): what a stream holds for the machine's passes, by name — "mstreams_rotation" (machine streams in rotation for the last run behind a
+// fast pass), "mstreams_used" (machine streams that ever entered the rotation), "mstreams_created" (HIP streams that exist), "pools" (workspace pools allocated), "lanes".  Read-only: nothing is waited for.  -1: no such name
+extern "C" __attribute__((visibility("default"))) long h2g_stream_probe(const h2g_stream* s, const char* key) {
+	if(!s || !key) return -1;
+	const std::string k(key);
+	if(k == "mstreams_rotation") return (long)s->rot;
+	if(k == "mstreams_used") return (long)s->n_mst;
+	if(k == "mstreams_created") { long n = 0; for(hipStream_t m : s->mst) n += m != nullptr; return n; }
+	if(k == "lanes") return (long)(s->mstreams ? s->mstreams : H2G_MSTREAMS_MAX);
+	if(k == "pools") { long n = 0; for(const h2g_stream::GoPool& pl : s->pool) n += pl.ws != nullptr; return n; }
+	return -1;
 }
 
 // development hook (h2g_stream_tune "dbg_read" / env H2G_GO_DBG_READ=<read id>): the primitive requests of that read in the last go() launch, 8 words each
