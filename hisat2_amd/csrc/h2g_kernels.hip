@@ -2688,8 +2688,8 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 // caller's SECOND run therefore runs both machine kernels once on every other machine stream in rotation that has not run them yet (the first run may be the only one), over an
 // empty list: with the pools, lists and per-run buffers above this is everything a stream does for the first time (a bench that warms up for 5 steps then timed the first use
 // of streams 5-7: 18.5 ms per step where the steady state is 12-13).  A stream that enters the rotation later is warmed by the run that brings it in.
-// The launches own everything they could write: a list whose count is a word nobody writes (zero by construction — a machine stream's overflow list may hold the deferred
-// count of an earlier run), rows and cursors of their own.
+// The launches own everything they could write: a list whose count is a word no kernel writes (a machine stream's overflow list may hold the deferred count of an
+// earlier run) and which every warmed stream zeroes itself in front of its launches, rows and cursors of their own.
 static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, const GoRun& r) {
 	int rc;
 	const size_t warm_rows = (size_t)1 << 16;
@@ -2707,6 +2707,9 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 		W1.O.ovf = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.ledits = reinterpret_cast<h2g_edit*>(s->d_warm_rows);      // (both areas with a capacity of zero)
 		W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_OVF_CURSOR); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_LEDITS_CURSOR);
 		W1.defer_overflow = 0;
+		// The count is zero ON THIS STREAM before its kernels read it: the hipMemset above runs on the null stream, which the (non-blocking) machine streams do not wait
+		// for, and the host does not have to either — a launch that went out first read whatever the fresh block held as its count and the row block as read ids.
+		HIPCHK(hipMemsetAsync(s->d_warm_cnt + H2G_CNT_NO_SECOND, 0, 8 * sizeof(unsigned long long), s->mst[m]));
 		if(g.U->launch(&W1, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		if(g.second) {
 			GoArgs W2 = W1;

@@ -97,11 +97,25 @@ static Scoring* makeScoring(SimpleFunc& scoreMin, SimpleFunc& nCeil,
 		DEFAULT_REF_GAP_LINEAR, 4, 0, 12, 1000000, &canIL, &noncanIL);
 }
 
-/** Parse a FASTA file of reads into Read objects (names = text after '>'). */
+/** Parse a FASTA file of reads into Read objects (names = text after '>'); a file that starts with '@' is four-line FASTQ (phred+33). */
 static void loadReads(const char* fn, vector<Read*>& rds) {
 	ifstream in(fn);
 	string line, name, seq;
 	uint64_t id = 0;
+	if(in.peek() == '@') {
+		string plus, q;
+		while(getline(in, name) && getline(in, seq) && getline(in, plus) && getline(in, q)) {
+			Read* r = new Read();
+			r->name.install(name.c_str() + 1);
+			r->patFw.installChars(seq.c_str(), seq.size());
+			r->qual.install(q.c_str(), q.size());
+			r->rdid = id++;
+			r->mate = 0;
+			r->finalize();
+			rds.push_back(r);
+		}
+		return;
+	}
 	while(true) {
 		bool ok = (bool)getline(in, line);
 		if(!ok || (!line.empty() && line[0] == '>')) {
@@ -158,6 +172,23 @@ int main(int argc, char** argv) {
 		       gh._len, gh._gbwtLen, gh._numNodes, gh._lineRate, gh._offRate, gh._ftabChars,
 		       gh._eftabLen, (int)gh.linearFM(), gh._sideSz, gh._sideGbwtSz, gh._sideGbwtLen,
 		       gh._numSides, gh._offsLen, (unsigned)gfm.nPat(), (unsigned)gfm.nFrag());
+		return 0;
+	}
+	if(cmd == "localof") {
+		// localof <base>: HGFM::getLocalGFM (hgfm.h:1713) for every text at offset 0, at its last offset, its length and one past it, and at every
+		// multiple of the local index interval (and the offset before it) up to two intervals past the text's end -> tidx toff present localOffset
+		for(index_t t = 0; t < gfm.nPat(); t++) {
+			index_t tlen = gfm.plen()[t];
+			vector<index_t> offs;
+			offs.push_back(0);
+			for(index_t o = local_index_interval; o <= tlen + 2 * local_index_interval; o += local_index_interval) { offs.push_back(o - 1); offs.push_back(o); }
+			if(tlen > 0) offs.push_back(tlen - 1);
+			offs.push_back(tlen); offs.push_back(tlen + 1);
+			for(size_t i = 0; i < offs.size(); i++) {
+				const LocalGFM<local_index_t, index_t>* l = p.gfm->getLocalGFM(t, offs[i]);
+				printf("%u %u %d %u\n", t, offs[i], l != NULL, l != NULL ? (unsigned)l->_localOffset : 0u);
+			}
+		}
 		return 0;
 	}
 	if(cmd == "rank") {
@@ -471,10 +502,14 @@ int main(int argc, char** argv) {
 				EList<Coord> coords;
 				bool straddled = false;
 				index_t rdoff = hit._len - ph._bwoff - ph._len;
-				al.getGenomeCoords(gfm, *p.altdb, *p.ref, rnd, ph._top, ph._bot, ph._node_top,
+				// coords <base> <reads> <nospliced> <rejectStraddle>: with the fourth argument every line starts with "rejectStraddle returnValue"
+				const bool coordsRej = cmd == "coords" && argc > 5;
+				const bool rejectStraddle = coordsRej && atoi(argv[5]) != 0;
+				bool cok = al.getGenomeCoords(gfm, *p.altdb, *p.ref, rnd, ph._top, ph._bot, ph._node_top,
 				                   ph._node_bot, ph._node_iedge_count, fw, ph._bot - ph._top,
-				                   rdoff, ph._len, coords, wlm, prm, him, false, straddled);
+				                   rdoff, ph._len, coords, wlm, prm, him, rejectStraddle, straddled);
 				if(cmd == "coords") {
+					if(coordsRej) printf("%d %d ", (int)rejectStraddle, (int)cok);
 					printf("%llu %d %u %u %u %u %d %u", (unsigned long long)rd.rdid, (int)fw,
 					       ph._top, ph._bot, rdoff, ph._len, (int)straddled, (unsigned)coords.size());
 					for(size_t k = 0; k < coords.size(); k++)
@@ -562,19 +597,25 @@ int main(int argc, char** argv) {
 					continue;
 				}
 				// extend: for each coordinate, a GenomeHit extended with mm = 0, 1, 2, 3
+				// extend <base> <reads> <nospliced> bounds: every hit is also extended with max_leftext = max_rightext = 0, 1, 7, 33; the bound is
+				// then a ninth field before the arrow (4294967295 = unbounded)
+				static const index_t boundsAll[5] = {(index_t)INDEX_MAX, 0, 1, 7, 33};
+				const int nbounds = argc > 5 ? 5 : 1;
 				for(size_t k = 0; k < coords.size(); k++) {
 					if(coords[k].ref() == (TRefId)std::numeric_limits<index_t>::max()) continue;
-					for(index_t mm = 0; mm < 4; mm++) {
+					for(index_t mm = 0; mm < 4; mm++) for(int bi = 0; bi < nbounds; bi++) {
 						GenomeHit<index_t> gh_;
 						gh_.init(fw, rdoff, ph._len, 0, 0, (index_t)coords[k].ref(),
 						         (index_t)coords[k].off(), (index_t)coords[k].joinedOff(), sharedVars);
-						index_t leftext = (index_t)INDEX_MAX, rightext = (index_t)INDEX_MAX;
+						index_t leftext = boundsAll[bi], rightext = boundsAll[bi];
 						bool ext = gh_.extend(rd, gfm, *p.ref, *p.altdb, *p.repeatdb, ssdb, swa, swm, prm,
 						                      *sc, minsc, rnd, (index_t)8, tpol, gpol, leftext, rightext, mm);
-						printf("%llu %d %u %u %u %u %u %u -> %d %u %u %u %u %u %u %lld %u",
+						printf("%llu %d %u %u %u %u %u %u",
 						       (unsigned long long)rd.rdid, (int)fw, rdoff, ph._len,
 						       (unsigned)coords[k].ref(), (unsigned)coords[k].off(),
-						       (unsigned)coords[k].joinedOff(), mm,
+						       (unsigned)coords[k].joinedOff(), mm);
+						if(nbounds > 1) printf(" %u", boundsAll[bi]);
+						printf(" -> %d %u %u %u %u %u %u %lld %u",
 						       (int)ext, gh_.rdoff(), gh_.len(), gh_.refoff(), gh_._joinedOff,
 						       leftext, rightext, (long long)gh_.score(), (unsigned)gh_.edits().size());
 						for(size_t e = 0; e < gh_.edits().size(); e++) {

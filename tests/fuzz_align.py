@@ -17,7 +17,14 @@ from hisat2_amd import synth  # noqa: E402
 REF = os.path.join(ROOT, "oracle", "_ref")
 
 
-def run_case(seed, nreads, rdlen, sub, indel, nrate, lens=(300000, 120000, 60000), repeats=6, gaps=2, verbose=8, extra=(), backend=None, bowtie2_dp=0, snps=0, fastq=False):
+def run_case(seed, nreads=0, rdlen=0, sub=0.0, indel=0.0, nrate=0.0, lens=(300000, 120000, 60000), repeats=6, gaps=2, verbose=8, extra=(), backend=None, bowtie2_dp=0, snps=0, fastq=False,
+             genome=None, reads=None, variants=None, info=None, spliced=False):
+    """genome = (records, names) with reads = a list of read arrays (any lengths): a prepared case instead of lens= / nreads= / rdlen=; variants = a
+    synth.write_snps list for a graph index of the prepared genome.  info: a dict that receives the reference's records ("want"), the @SQ names
+    ("refnames") and the counts ("bad", "overflow", "aligned") of the run.  spliced (prepared cases): spliced alignment, every read on its own
+    (--no-temp-splicesite), instead of --no-spliced-alignment."""
+    if genome is not None:
+        return _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced)
     tmp = tempfile.mkdtemp(prefix="h2fuzz")
     contigs = synth.make_genome(list(lens), seed, n_gaps=gaps, gap_len=300, repeats=repeats, repeat_len=500)
     fa = os.path.join(tmp, "g.fa")
@@ -45,14 +52,46 @@ def run_case(seed, nreads, rdlen, sub, indel, nrate, lens=(300000, 120000, 60000
             txt = synth._ALPHA[reads]
             for i in range(nreads):
                 f.write(b"@%d\n" % i + txt[i].tobytes() + b"\n+\n" + quals[i].tobytes() + b"\n")
+    return _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, f"n {nreads} len {rdlen} sub {sub} indel {indel} N {nrate}")
+
+
+def _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced):
+    import numpy as np
+    tmp = tempfile.mkdtemp(prefix="h2fuzz")
+    records, names = genome
+    fa = os.path.join(tmp, "g.fa")
+    synth.write_fasta(fa, records, names=names)
+    base = os.path.join(tmp, "g")
+    snp = []
+    if variants:
+        synth.write_snps(os.path.join(tmp, "g.snp"), variants)
+        snp = ["--snp", os.path.join(tmp, "g.snp")]
+    subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q"] + snp + [fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+    quals = None
+    if fastq:
+        rng = np.random.default_rng(seed + 9)
+        quals = (33 + rng.choice(np.array([2, 8, 15, 20, 25, 30, 37, 40], dtype=np.uint8), size=sum(len(r) for r in reads))).astype(np.uint8)
+    rfa = os.path.join(tmp, "r.fq" if fastq else "r.fa")
+    with open(rfa, "wb") as f:
+        off = 0
+        for i, r in enumerate(reads):
+            s = synth._ALPHA[r].tobytes()
+            f.write((b"@%d\n" % i + s + b"\n+\n" + quals[off:off + len(r)].tobytes() + b"\n") if fastq else (b">%d\n" % i + s + b"\n"))
+            off += len(r)
+    return _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, f"prepared n {len(reads)}", spliced)
+
+
+def _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, what, spliced=False):
+    nreads = len(reads)
     sam = os.path.join(tmp, "ref.sam")
-    subprocess.run([os.path.join(REF, "hisat2-align-s"), "-q" if fastq else "-f", "-p", "1", "--no-spliced-alignment", "-x", base, "-U", rfa, "-S", sam] + list(extra),
+    subprocess.run([os.path.join(REF, "hisat2-align-s"), "-q" if fastq else "-f", "-p", "1", "--no-temp-splicesite" if spliced else "--no-spliced-alignment", "-x", base, "-U", rfa, "-S", sam] + list(extra),
                    check=True, stdout=subprocess.DEVNULL, stderr=open(os.path.join(tmp, "ref.err"), "w"))
     refnames, want = SU.parse_sam(sam)
     qnames = [str(i) for i in range(nreads)]
     if backend is None:
-        outs, recs = emu_align(base, [reads[i] for i in range(nreads)], qnames, bowtie2_dp=bowtie2_dp, quals=None if quals is None else quals.reshape(-1),
-                               options=list(extra))
+        outs, recs = emu_align(base, [reads[i] for i in range(nreads)], qnames, no_spliced=0 if spliced else 1, bowtie2_dp=bowtie2_dp,
+                               quals=None if quals is None else quals.reshape(-1), options=list(extra))
         got = SU.render(outs, recs, refnames, [reads[i] for i in range(nreads)], qnames)
     else:   # backend(base, reads, qnames) -> (outs with .overflow/.depth, rendered dict)
         kw = {}
@@ -61,6 +100,8 @@ def run_case(seed, nreads, rdlen, sub, indel, nrate, lens=(300000, 120000, 60000
         opts = list(extra)
         if opts:
             kw["options"] = opts
+        if spliced:
+            kw["spliced"] = True
         outs, got = backend(base, reads, qnames, refnames, **kw)
     bad = ovf = setbad = 0
     maxdep = 0
@@ -75,7 +116,9 @@ def run_case(seed, nreads, rdlen, sub, indel, nrate, lens=(300000, 120000, 60000
             if bad <= verbose:
                 print(" read", q, ("ovf%d" % outs[i].overflow) if outs[i].overflow else "", "\n   GOT ", got[q], "\n   WANT", want[q])
     naln = sum(1 for q in qnames if want[q][0][0] != 4)
-    print(f"seed {seed} n {nreads} len {rdlen} sub {sub} indel {indel} N {nrate}: aligned(ref) {naln}  mismatching {bad} (set-level {setbad})  overflow {ovf}  max depth {maxdep}  tmp {tmp}")
+    print(f"seed {seed} {what}: aligned(ref) {naln}  mismatching {bad} (set-level {setbad})  overflow {ovf}  max depth {maxdep}  tmp {tmp}")
+    if info is not None:
+        info.update(want=want, got=got, refnames=refnames, bad=bad, overflow=ovf, aligned=naln, base=base, tmp=tmp)
     return bad, tmp
 
 

@@ -25,6 +25,20 @@ OPTS = ()   # extra reference command-line options (scoring / reporting), applie
 SNPS = int(os.environ.get("H2G_FUZZ_SNPS", "0"))   # > 0: graph index with a seeded variant every ~SNPS bp, pairs from the alt haplotype
 
 
+def flatten(m):
+    """(codes, offsets) of an (n, L) array or of a list of read arrays of any lengths"""
+    if isinstance(m, np.ndarray) and m.ndim == 2:
+        return synth.flatten_reads(m)
+    lst = [np.ascontiguousarray(r, dtype=np.uint8) for r in m]
+    return np.concatenate(lst), np.concatenate([[0], np.cumsum([len(r) for r in lst])]).astype(np.uint32)
+
+
+def write_fasta_reads(path, m):
+    with open(path, "wb") as f:
+        for i in range(len(m)):
+            f.write(b">%d\n" % i + synth._ALPHA[np.asarray(m[i])].tobytes() + b"\n")
+
+
 def emu_pairs(base, m1, m2, q1, q2):
     e = Emu(base)
     e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
@@ -32,9 +46,9 @@ def emu_pairs(base, m1, m2, q1, q2):
     if OPTS:
         from h2gemu_align import set_options
         set_options(e, DP, OPTS)
-    n, L = m1.shape
-    c1, o1 = synth.flatten_reads(m1)
-    c2, o2 = synth.flatten_reads(m2)
+    n = len(m1)
+    c1, o1 = flatten(m1)
+    c2, o2 = flatten(m2)
     e.set_reads(c1, o1)
     nb1 = "".join(q1).encode(); no1 = np.concatenate([[0], np.cumsum([len(q) for q in q1])]).astype(np.uint32)
     nb2 = "".join(q2).encode(); no2 = np.concatenate([[0], np.cumsum([len(q) for q in q2])]).astype(np.uint32)
@@ -80,9 +94,19 @@ def _nmask(m1, m2):     # N-filtered mates: the other mate goes through initRead
 MUTATORS = {"flip": _flip, "nmask": _nmask}
 
 
-def run_case(seed, npairs, rdlen, sub, lens=(300000, 120000, 60000), repeats=6, gaps=2, frag_mean=300, frag_sd=30, verbose=6,
-             backend=None, stride=16, mutate=None):
+def run_case(seed, npairs=0, rdlen=0, sub=0.0, lens=(300000, 120000, 60000), repeats=6, gaps=2, frag_mean=300, frag_sd=30, verbose=6,
+             backend=None, stride=16, mutate=None, genome=None, pairs=None, info=None):
+    """genome = (records, names) with pairs = (mate 1 list, mate 2 list): a prepared case instead of lens= / npairs= / rdlen=.  info: a dict that
+    receives the reference's records ("want") and the counts ("bad", "overflow", "concordant") of the run."""
     tmp = tempfile.mkdtemp(prefix="h2pe")
+    if genome is not None:
+        fa = os.path.join(tmp, "g.fa")
+        synth.write_fasta(fa, genome[0], names=genome[1])
+        base = os.path.join(tmp, "g")
+        subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q", fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        m1, m2 = pairs
+        npairs = len(m1)
+        return _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, f"prepared n {npairs}")
     contigs = synth.make_genome(list(lens), seed, n_gaps=gaps, gap_len=300, repeats=repeats, repeat_len=500)
     fa = os.path.join(tmp, "g.fa")
     synth.write_fasta(fa, contigs)
@@ -99,9 +123,13 @@ def run_case(seed, npairs, rdlen, sub, lens=(300000, 120000, 60000), repeats=6, 
     m1, m2 = synth.make_pairs(src, npairs, rdlen, seed + 1, frag_mean=frag_mean, frag_sd=frag_sd, sub_rate=sub)
     if mutate is not None:   # a name in MUTATORS or a callable (m1, m2) -> (m1, m2)
         m1, m2 = (MUTATORS[mutate] if isinstance(mutate, str) else mutate)(m1, m2)
+    return _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, f"n {npairs} len {rdlen} sub {sub}")
+
+
+def _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, what):
     f1, f2 = os.path.join(tmp, "r1.fa"), os.path.join(tmp, "r2.fa")
-    synth.write_reads_fasta(f1, m1)
-    synth.write_reads_fasta(f2, m2)
+    write_fasta_reads(f1, m1)
+    write_fasta_reads(f2, m2)
     sam = os.path.join(tmp, "ref.sam")
     subprocess.run([os.path.join(REF, "hisat2-align-s"), "-f", "-p", "1", "--no-spliced-alignment", "-x", base, "-1", f1, "-2", f2, "-S", sam] + (["--bowtie2-dp", str(DP)] if DP else []) + list(OPTS),
                    check=True, stdout=subprocess.DEVNULL, stderr=open(os.path.join(tmp, "ref.err"), "w"))
@@ -131,7 +159,9 @@ def run_case(seed, npairs, rdlen, sub, lens=(300000, 120000, 60000), repeats=6, 
                 setbad += 1
             if bad <= verbose:
                 print(" pair", i, ("ovf%d" % outs[i].overflow) if outs[i].overflow else "", "\n   GOT ", got, "\n   WANT", w)
-    print(f"PE seed {seed} n {npairs} len {rdlen} sub {sub}: concordant(ref) {ncon}  mismatching {bad} (set-level {setbad})  overflow {ovf}  tmp {tmp}")
+    print(f"PE seed {seed} {what}: concordant(ref) {ncon}  mismatching {bad} (set-level {setbad})  overflow {ovf}  tmp {tmp}")
+    if info is not None:
+        info.update(want=want, refnames=refnames, bad=bad, overflow=ovf, concordant=ncon, base=base, tmp=tmp)
     return bad, tmp
 
 

@@ -14,6 +14,11 @@ for a small seeded genome ("g1"):
   g1s.snp.gz, g1s.{1..8}.ht2.gz   ~500 seeded variants of g1 and the hisat2-build-s --snp graph index
   reads_snp.fa.gz                 300 reads drawn from the alternate haplotype (all variants applied)
   probe_g1s_{params,rank,glf,glf1,psearch,psearch_spliced,coords,coords_short,extend,adjust,adjust_short,lglf}.txt.gz   reference GFM graph-LF / group-walk outputs
+`gen_golden.py frag` adds the FRAGMENTED assembly fixture (tests/frag_cases.py: ~217 texts, ~330 fragments, all-N records, N runs at record ends):
+  gfrag.fa.gz, gfrag.{1..8}.ht2.gz, reads_gfrag.fa.gz (1500 reads, classes A-G, 36-150 bases)
+  probe_gfrag_{params,offset,stretch,psearch,coords,extend,extend_fq,extsearch,localof}.txt.gz
+                                  coords: getGenomeCoords with rejectStraddle 0 and 1; extend: max_leftext / max_rightext unbounded, 0, 1, 7, 33
+                                  (_fq: the same reads as FASTQ with seeded qualities); localof: HGFM::getLocalGFM at and past every text's end
 Everything is deterministic (seeds below); the fixtures are committed.
 """
 import gzip
@@ -269,8 +274,76 @@ def main_combine():
     shutil.rmtree(tmp)
 
 
+def main_frag():
+    sys.path.insert(0, HERE)
+    import frag_cases as FC
+    tmp = tempfile.mkdtemp(prefix="h2goldf")
+    g = FC.make_frag_genome(FC.GFRAG_SEED, FC.GFRAG_TOTAL)
+    base = FC.build_index(g, tmp, REF)
+    os.rename(os.path.join(tmp, "g.fa"), os.path.join(tmp, "gfrag.fa"))
+    gz_write(os.path.join(GOLD, "gfrag.fa.gz"), open(os.path.join(tmp, "gfrag.fa"), "rb").read())
+    for k in range(1, 9):
+        gz_write(os.path.join(GOLD, f"gfrag.{k}.ht2.gz"), open(f"{base}.{k}.ht2", "rb").read())
+    reads, labels, origin = FC.make_frag_reads(g, FC.GFRAG_SEED + 1, FC.GFRAG_NREADS, with_origin=True)
+    rfa, rfq = os.path.join(tmp, "reads_gfrag.fa"), os.path.join(tmp, "reads_gfrag.fq")
+    FC.write_reads(rfa, reads)
+    FC.write_reads(rfq, reads, FC.seeded_quals(reads, FC.GFRAG_SEED + 2))
+    gz_write(os.path.join(GOLD, "reads_gfrag.fa.gz"), open(rfa, "rb").read())
+    # the extension vectors: the classes whose exact-match cores end at a contig end / an N run / a repeat copy (B, D, F, G)
+    keep = [i for i, c in enumerate(labels) if c in "BDFG"]
+    xfa, xfq = os.path.join(tmp, "x.fa"), os.path.join(tmp, "x.fq")
+    xr = [reads[i] for i in keep]
+    FC.write_reads(xfa, xr)
+    q = FC.seeded_quals(reads, FC.GFRAG_SEED + 2)
+    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads])])
+    FC.write_reads(xfq, xr, np.concatenate([q[offs[i]:offs[i + 1]] for i in keep]))
+    probe = os.path.join(REF, "ref_probe")
+    for name, cmd, args in [("params", "params", []), ("offset", "offset", ["3000", "13"]), ("stretch", "stretch", ["3000", "14"]),
+                            ("psearch", "psearch", [rfa, "1"]), ("localof", "localof", [])]:
+        out = run([probe, cmd, base] + args).stdout
+        gz_write(os.path.join(GOLD, f"probe_gfrag_{name}.txt.gz"), out)
+        print(name, len(out.splitlines()), "lines")
+    out = run([probe, "coords", base, rfa, "1", "0"]).stdout + run([probe, "coords", base, rfa, "1", "1"]).stdout
+    gz_write(os.path.join(GOLD, "probe_gfrag_coords.txt.gz"), out)
+    print("coords", len(out.splitlines()), "lines")
+    for name, f in (("extend", xfa), ("extend_fq", xfq)):
+        lines = run([probe, "extend", base, f, "1", "bounds"]).stdout.splitlines(True)
+        # read ids of the subset -> ids of reads_gfrag; the FASTQ run keeps every third hit (the qualities only change scores)
+        lines = [b"%d " % keep[int(l.split(b" ", 1)[0])] + l.split(b" ", 1)[1] for l in lines]
+        if name == "extend_fq":
+            lines = lines[::3]
+        gz_write(os.path.join(GOLD, f"probe_gfrag_{name}.txt.gz"), b"".join(lines))
+        print(name, len(lines), "lines")
+    # extsearch: the local index under every read's origin (most texts here have ONE local index of a few dozen to a few hundred bases) and the
+    # global index; offsets at and past the text's end go through localof
+    text_of = {r: t for t, r in enumerate(g.texts)}
+    rng = np.random.default_rng(FC.GFRAG_SEED + 77)
+    qs = []
+    for i, (rec, pos, fw) in enumerate(origin):
+        n = len(reads[i])
+        t = text_of[rec]
+        tl = len(g.records[rec])
+        qs.append((i, int(fw), n - 1, 0, 0, 0, 0xffffffff, 1))
+        for _ in range(2):
+            rdoff = int(rng.integers(8, n))
+            toff = min(max(0, pos + int(rng.integers(0, n))), tl - 1)
+            qs.append((i, int(fw) if rng.integers(0, 8) else 1 - int(fw), rdoff, 1, t, toff, 0xffff if rng.integers(0, 2) else int(rng.integers(8, 40)), int(rng.integers(0, 2))))
+    qf = os.path.join(tmp, "q.txt")
+    open(qf, "w").write("".join(" ".join(map(str, x)) + "\n" for x in qs))
+    out = run([probe, "extsearch", base, rfa, qf]).stdout.decode().splitlines()
+    assert len(out) == len(qs), (len(out), len(qs))
+    gz_write(os.path.join(GOLD, "probe_gfrag_extsearch.txt.gz"), "".join(" ".join(map(str, x)) + " " + o + "\n" for x, o in zip(qs, out)).encode())
+    print("extsearch", len(out), "lines,", sum(1 for o in out if not o.startswith("0 ")), "with elements")
+    shutil.rmtree(tmp)
+    for f in sorted(os.listdir(GOLD)):
+        if "gfrag" in f:
+            print(f, os.path.getsize(os.path.join(GOLD, f)))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "combine":
+    if len(sys.argv) > 1 and sys.argv[1] == "frag":
+        main_frag()
+    elif len(sys.argv) > 1 and sys.argv[1] == "combine":
         sys.path.insert(0, HERE)
         main_combine()
     elif len(sys.argv) > 1 and sys.argv[1] == "extsearch":

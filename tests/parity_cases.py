@@ -380,3 +380,193 @@ def check_ext_search(search, local_index_of, golden_dir, fn):
             nel += 1
             assert (g.hitlen, g.top, g.bot) == (w[1], w[2], w[3]), (q.read, q.fw, q.rdoff, q.lidx, g.hitlen, g.top, g.bot, w)
     return len(qs), nel
+
+
+# ---------------------------------------------------------------- fragmented assembly (gfrag: tests/frag_cases.py, gen_golden.py frag)
+def unpack_index(golden_dir, name, dst):
+    """the committed index `name` unpacked under dst -> basename"""
+    import shutil
+    for k in range(1, 9):
+        with gzip.open(os.path.join(golden_dir, f"{name}.{k}.ht2.gz"), "rb") as f, open(os.path.join(str(dst), f"{name}.{k}.ht2"), "wb") as o:
+            shutil.copyfileobj(f, o)
+    return os.path.join(str(dst), name)
+
+
+def load_frag_reads(golden_dir):
+    """-> (list of read arrays, flat codes, offsets)"""
+    _, seqs = H.read_fasta_reads(os.path.join(golden_dir, "reads_gfrag.fa.gz"))
+    codes = np.concatenate(seqs).astype(np.uint8)
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint32)
+    return seqs, codes, offs
+
+
+def frag_texts(golden_dir):
+    """the texts of the gfrag index: the FASTA's records without the all-N ones (the builder drops them)"""
+    return [c for c in load_contigs(golden_dir, "gfrag.fa.gz") if (c < 4).any()]
+
+
+def check_frag_info(info, golden_dir):
+    kv = H.glines(golden_dir, "probe_gfrag_params.txt.gz")[0].split()
+    d = dict(zip(kv[0::2], map(int, kv[1::2])))
+    for k in ("len", "gbwtLen", "numNodes", "lineRate", "offRate", "ftabChars", "eftabLen", "linear", "sideSz", "sideGbwtSz", "sideGbwtLen", "numSides", "offsLen",
+              "nPat", "nFrag"):
+        assert getattr(info, k) == d[k], k
+    texts = frag_texts(golden_dir)
+    assert info.nPat == len(texts) and info.nFrag >= 300
+    return d
+
+
+def _sa_array(rows):
+    """(n, 5) uint32 rows {top, bot, maxelt, len, rejectStraddle} -> ctypes array of api.SaQuery"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    arr = (api.SaQuery * len(rows))()
+    np.frombuffer(arr, dtype=np.uint32).reshape(len(rows), 5)[:] = rows
+    return arr
+
+
+def check_frag_coords(be, golden_dir):
+    """getGenomeCoords with rejectStraddle 0 and 1 (first two fields of a line: rejectStraddle, the reference's return value).  A rejected range returns
+    false with the coordinates resolved before the straddler.  -> (lines, lines with straddled = 1, rejected lines)"""
+    rows, want = [], []
+    for l in H.glines(golden_dir, "probe_gfrag_coords.txt.gz"):
+        f = l.split()
+        rej, ok = int(f[0]), int(f[1])
+        top, bot, rdoff, hlen, strad, n = map(int, f[4:10])
+        rows.append((top, bot, bot - top, hlen, rej))
+        want.append((ok, strad, [tuple(int(x) & 0xFFFFFFFF for x in f[10 + k].split(":")) for k in range(n)]))
+    cap = 16
+    co, res = be.sa_resolve(_sa_array(rows), cap=cap)
+    nstrad = nrej = 0
+    for i, (ok, strad, cs) in enumerate(want):
+        assert (res[i].ok, res[i].ncoords, res[i].straddled) == (ok, len(cs), strad), (rows[i], res[i].ok, res[i].ncoords, res[i].straddled, ok, cs, strad)
+        for k, c in enumerate(cs):
+            g = co[i * cap + k]
+            assert (g.tidx, g.toff, g.joinedOff) == c, (rows[i], k)
+        nstrad += strad
+        nrej += not ok
+    return len(rows), nstrad, nrej
+
+
+def frag_sa_queries(gbwtLen, seed=4242, nranges=5000):
+    """every row of the index as a one-row query + `nranges` seeded ranges 2-5 wide; len in {1, 20, 101} and rejectStraddle in {0, 1} cycle with the query
+    index; every third range asks for fewer elements than it is wide"""
+    rng = np.random.default_rng(seed)
+    rows = np.arange(gbwtLen, dtype=np.int64)
+    one = np.stack([rows, rows + 1, np.ones_like(rows), np.array([1, 20, 101])[rows % 3], (rows // 3) % 2], axis=1)
+    top = rng.integers(0, gbwtLen - 5, size=nranges)
+    wid = rng.integers(2, 6, size=nranges)
+    k = np.arange(nranges)
+    maxelt = np.where(k % 3 == 0, wid - 1, wid)
+    rngs = np.stack([top, top + wid, maxelt, np.array([1, 20, 101])[k % 3], (k // 3) % 2], axis=1)
+    return np.concatenate([one, rngs]).astype(np.uint32)
+
+
+def check_frag_sa_resolve_vs_oracle(be, olib, oix, gbwtLen):
+    """h2g_sa_resolve against h2o_genome_coords on frag_sa_queries: ok, ncoords, straddled, nsteps and every coordinate"""
+    q = frag_sa_queries(gbwtLen)
+    n, cap = len(q), 5
+    co, res = be.sa_resolve(_sa_array(q), cap=cap)
+    got_co = np.frombuffer(co, dtype=np.uint32).reshape(n, cap, 3)
+    got_res = np.frombuffer(res, dtype=np.uint32).reshape(n, 4)
+    want_co = np.zeros((n, cap, 3), dtype=np.uint32)
+    want_res = np.zeros((n, 4), dtype=np.uint32)
+    f = olib.h2o_genome_coords
+    saved = f.argtypes
+    f.argtypes = [saved[0], C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    try:
+        cb, rb = want_co.ctypes.data, want_res.ctypes.data
+        ql = q.tolist()
+        for i, (top, bot, maxelt, ln, rej) in enumerate(ql):
+            r = rb + 16 * i
+            want_res[i, 0] = f(oix, top, bot, maxelt, ln, rej, cb + 12 * cap * i, r + 4, r + 8, r + 12)
+    finally:
+        f.argtypes = saved
+    assert np.array_equal(got_res, want_res), np.nonzero((got_res != want_res).any(axis=1))[0][:10]
+    valid = np.arange(cap)[None, :] < want_res[:, 1][:, None]
+    assert np.array_equal(got_co[valid], want_co[valid])
+    return n, int(want_res[:, 2].sum()), int((want_res[:, 0] == 0).sum())
+
+
+def parse_frag_extend(golden_dir, fn):
+    """-> [(rid, fw, rdoff, len, tidx, toff, joff, mm, bound, result fields)]"""
+    out = []
+    for l in H.glines(golden_dir, fn):
+        lhs, rhs = l.split(" -> ")
+        out.append(tuple(map(int, lhs.split())) + (rhs.split(),))
+    return out
+
+
+def check_frag_extend(be, golden_dir, fn, seqs):
+    """GenomeHit::extend with max_leftext = max_rightext unbounded / 0 / 1 / 7 / 33, mm 0-3.  -> (vectors, unbounded vectors whose extension stopped at
+    the end of a stretch of unambiguous bases — a contig end or an N — with read bases left over on that side)"""
+    texts = frag_texts(golden_dir)
+    cases = parse_frag_extend(golden_dir, fn)
+    hits, args = (api.GHit * len(cases))(), (api.ExtArgs * len(cases))()
+    for h, a, c in zip(hits, args, cases):
+        h.read, h.fw, h.rdoff, h.len, h.tidx, h.toff, h.joinedOff = c[:7]
+        a.mm, a.max_leftext, a.max_rightext = c[7], c[8], c[8]
+    out, res = be.extend(hits, args)
+    nstop = 0
+    for h, r, c in zip(out, res, cases):
+        w = c[9]
+        got = [r.extended, h.rdoff, h.len, h.toff, h.joinedOff, r.leftext, r.rightext, h.score, h.nedits]
+        assert got == list(map(int, w[:9])), (c[:9], got, w)
+        eds = [f"{h.edits[k].pos}:{chr(h.edits[k].chr)}>{chr(h.edits[k].qchr)}" for k in range(h.nedits)]
+        assert eds == w[9:] and h.overflow == 0, (c[:9], eds, w)
+        if c[8] == api.MAX:
+            t = texts[c[4]]
+            rdoff, ln, toff = int(w[1]), int(w[2]), int(w[3])
+            left = rdoff > 0 and (toff == 0 or t[toff - 1] > 3)
+            right = rdoff + ln < len(seqs[c[0]]) and (toff + ln >= len(t) or t[toff + ln] > 3)
+            nstop += left or right
+    return len(cases), nstop
+
+
+def check_frag_fm_search(be, golden_dir, olib, oix, seqs):
+    """partialSearch from offset 0 against the vectors, and from offsets > 0 (the continuation after a first hit) against the C oracle"""
+    qs, want = [], []
+    for l in H.glines(golden_dir, "probe_gfrag_psearch.txt.gz"):
+        v = list(map(int, l.split()))
+        qs.append(api.FmQuery(v[0], 0, v[1], 0, 0, 1))
+        want.append(v[2:])
+    out = be.fm_search(qs, khits=5)
+    cont = []
+    for o, w, q in zip(out, want, qs):
+        got = [getattr(o, f) for f in api.FM_HIT_FIELDS[:13]]
+        assert got == w, (q.read, q.fw, got, w)
+        if not o.done and 0 < o.cur < len(seqs[q.read]):
+            cont.append(api.FmQuery(q.read, o.cur, q.fw, 0, 0, 1))
+    out = be.fm_search(cont, khits=5)
+    for o, q in zip(out, cont):
+        s = np.ascontiguousarray(seqs[q.read] if q.fw else H.revcomp(seqs[q.read]))
+        w = H.BwtHit()
+        olib.h2o_partial_search(oix, s.ctypes.data, len(s), q.offset, 0, 1, 5, C.byref(w))
+        assert [getattr(o, f) for f in api.FM_HIT_FIELDS] == [getattr(w, f) for f in api.FM_HIT_FIELDS], (q.read, q.fw, q.offset)
+    return len(qs), len(cont)
+
+
+def oracle_seed_extend_ragged(olib, oix, seqs, pseudo, khits=5, cap=api.SEED_CAP):
+    """oracle_seed_extend for reads of different lengths"""
+    out = np.zeros(len(seqs) * 2, dtype=api.SEED_RESULT_DTYPE)
+    for L in sorted({len(s) for s in seqs}):
+        idx = [i for i, s in enumerate(seqs) if len(s) == L]
+        part = oracle_seed_extend(olib, oix, np.stack([seqs[i] for i in idx]), pseudo, khits, cap)
+        for k, i in enumerate(idx):
+            out[2 * i], out[2 * i + 1] = part[2 * k], part[2 * k + 1]
+    return out
+
+
+def check_frag_local_index_of(local_index_of, golden_dir):
+    """HGFM::getLocalGFM at offset 0, at and past every text's end and around every multiple of the interval: the same offsets have a local index, and the
+    indexes are numbered in (text, local offset) order"""
+    want = [tuple(map(int, l.split())) for l in H.glines(golden_dir, "probe_gfrag_localof.txt.gz")]
+    ids = {}
+    for t, off, present, lo in want:
+        if present:
+            ids.setdefault((t, lo), len(ids))
+    nabsent = 0
+    for t, off, present, lo in want:
+        got = local_index_of(t, off)
+        assert got == (ids[(t, lo)] if present else 0xffffffff), (t, off, present, lo, got)
+        nabsent += not present
+    return len(want), nabsent

@@ -164,3 +164,26 @@ def test_reads_same_bytes_with_and_without_the_table(libs, genome, monkeypatch, 
     r = _same(_run_both(monkeypatch, libs[sat], base, reads, None))
     if case["rdlen"] <= 128:
         assert r["completed"] > 0.4 * r["n"], r
+
+
+# ---------------------------------------------------------------- fragmented assembly (tests/frag_cases.py)
+@pytest.mark.parametrize("sat", [255, 8])
+def test_table_equals_the_walk_on_every_row_gfrag(libs, golden_dir, tmp_path, monkeypatch, sat):
+    import parity_cases as PC
+    e = _emu(monkeypatch, libs[sat], PC.unpack_index(golden_dir, "gfrag", tmp_path))
+    saturated, longest = _check_every_row(e, sat)
+    assert (saturated > 0) == (longest >= sat)
+
+
+@needs_builder
+@pytest.mark.parametrize("sat", [255, 8])
+def test_fragmented_assembly_same_bytes_with_and_without_the_table(libs, monkeypatch, sat):
+    """the fast pass resolves rows from the dense table and then tests every element for a straddle itself: reads and pairs that straddle two texts or two
+    fragments, hang off contig ends or abut N runs give the same bytes with the table as with the walk"""
+    import frag_cases as FR
+    g, reads, _, m1, m2, _ = FR.live_case()
+    base = FR.build_index(g, tempfile.mkdtemp(prefix="h2densefrag"), os.path.dirname(BUILD))
+    r = _same(_run_both(monkeypatch, libs[sat], base, reads, None))
+    assert r["completed"] > 0, r
+    r = _same(_run_both(monkeypatch, libs[sat], base, m1, m2))
+    assert r["completed"] > 0, r

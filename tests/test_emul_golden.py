@@ -326,3 +326,86 @@ def test_combine_with_golden(g1_index, golden_dir, spliced):
                 assert (ed.pos, chr(ed.chr), chr(ed.qchr), ed.type) == (int(f[0]), chr_, qchr, int(f[2])), (i, l, k)
             kinds.add(ed.type)
     assert ncomb > 700 and kinds >= ({1, 2, 3, 5} if spliced else {1, 2, 3})
+
+
+# ---------------------------------------------------------------- fragmented assembly (gfrag: tests/frag_cases.py): ~190 texts, 300+ fragments
+@pytest.fixture(scope="module")
+def gfrag_index(tmp_path_factory, golden_dir):
+    return PC.unpack_index(golden_dir, "gfrag", tmp_path_factory.mktemp("gfrag"))
+
+
+@pytest.fixture(scope="module")
+def femu(gfrag_index, golden_dir):
+    e = Emu(gfrag_index)
+    seqs, codes, offs = PC.load_frag_reads(golden_dir)
+    e.set_reads(codes, offs)
+    e.seqs = seqs
+    return e
+
+
+def test_frag_reads_are_the_generators(golden_dir):
+    """the committed reads are make_frag_reads' (the class labels the tests use come from regenerating them)"""
+    import frag_cases as FC
+    g = FC.make_frag_genome(FC.GFRAG_SEED, FC.GFRAG_TOTAL)
+    reads, labels = FC.make_frag_reads(g, FC.GFRAG_SEED + 1, FC.GFRAG_NREADS)
+    seqs, _, _ = PC.load_frag_reads(golden_dir)
+    assert len(seqs) == len(reads) and all(np.array_equal(a, b) for a, b in zip(seqs, reads))
+    assert [len(t) for t in PC.frag_texts(golden_dir)] == [len(t) for t in g.text_seqs()]
+    assert set(labels) == set(FC.READ_CLASSES)
+
+
+def test_frag_coords(femu, golden_dir):
+    import frag_cases as FC
+    n, nstrad, nrej = PC.check_frag_coords(femu, golden_dir)
+    assert n > 2000 and nstrad >= FC.MINIMA["coords_straddled"] and nrej >= FC.MINIMA["coords_rejected"]
+
+
+def test_frag_sa_resolve_every_row_vs_oracle(femu, oracle_lib, gfrag_index):
+    oix = H.load_index(oracle_lib, gfrag_index)
+    n, nstrad, nrej = PC.check_frag_sa_resolve_vs_oracle(femu, oracle_lib, oix, oix.contents.g.p.gbwtLen)
+    import frag_cases as FC
+    assert n == oix.contents.g.p.gbwtLen + 5000 and nstrad >= FC.MINIMA["sa_straddled"] and nrej >= FC.MINIMA["sa_rejected"]
+
+
+@pytest.mark.parametrize("fn", ["probe_gfrag_extend.txt.gz", "probe_gfrag_extend_fq.txt.gz"])
+def test_frag_extend(femu, gfrag_index, golden_dir, fn):
+    import frag_cases as FC
+    e = femu
+    if fn.endswith("_fq.txt.gz"):
+        e = Emu(gfrag_index)
+        seqs, codes, offs = PC.load_frag_reads(golden_dir)
+        e.set_reads(codes, offs, quals=FC.seeded_quals(seqs, FC.GFRAG_SEED + 2))
+    n, nstop = PC.check_frag_extend(e, golden_dir, fn, femu.seqs)
+    assert n > 10000 and nstop >= FC.MINIMA["extend_stop_at_stretch_end" + ("_fq" if e is not femu else "")]
+
+
+def test_frag_fm_search_and_seed_stage(femu, oracle_lib, gfrag_index, golden_dir):
+    oix = H.load_index(oracle_lib, gfrag_index)
+    n, ncont = PC.check_frag_fm_search(femu, golden_dir, oracle_lib, oix, femu.seqs)
+    import frag_cases as FC
+    assert n == 3000 and ncont >= FC.MINIMA["psearch_continued"]
+    got = femu.seed_extend(pseudogeneStop=0)
+    want = PC.oracle_seed_extend_ragged(oracle_lib, oix, femu.seqs, 0)
+    PC.assert_seed_equal(got, want)
+    assert (want["ncoords"] > 0).sum() >= FC.MINIMA["seed_anchored"] and (want["straddled"] > 0).sum() >= FC.MINIMA["seed_straddled"]
+
+
+def test_frag_ext_search_and_local_index_of(femu, golden_dir):
+    """most texts of gfrag have ONE local index, of 25 to 2000 bases"""
+    import ctypes as C
+    from hisat2_amd import api
+    femu.L.h2gemu_local_index_of.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    femu.L.h2gemu_local_index_of.restype = C.c_uint32
+    femu.L.h2gemu_ext_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lof = lambda t, o: femu.L.h2gemu_local_index_of(femu.h, t, o)   # noqa: E731
+    n, nabsent = PC.check_frag_local_index_of(lof, golden_dir)
+    import frag_cases as FC
+    assert n > 1000 and nabsent >= FC.MINIMA["localof_absent"]
+
+    def search(qs):
+        arr = (api.ExtSearchQuery * len(qs))(*qs)
+        out = (api.ExtSearchHit * len(qs))()
+        femu.L.h2gemu_ext_search(femu.h, arr, len(qs), out)
+        return out
+    n, nel = PC.check_ext_search(search, lof, golden_dir, "probe_gfrag_extsearch.txt.gz")
+    assert n == 4500 and nel >= FC.MINIMA["extsearch_with_elements"]

@@ -233,3 +233,21 @@ def test_bail_reason_names_cover_the_fb_enum():
     names = [m.lower() for m in re.findall(r"FB_([A-Z]+)", body)]
     assert names == FC.BAIL_REASONS
     assert names == bench.BAIL_REASONS
+
+
+def test_fragmented_assembly_equals_the_machine():
+    """the fast pass on a fragmented assembly (tests/frag_cases.py): its own restatement of the straddle test (dense-table loads + joined_to_text per element), its
+    word-wise comparison next to stretch ends (RefCursor::covers / chunk32) and its pairing, on reads that hang off contig ends, straddle two texts, abut N runs, and on
+    pairs whose mates lie on neighbouring texts.  Reads of 150 bases are handed on (longer than the packed form)."""
+    import frag_cases as FR
+    g, reads, labels, m1, m2, plabels = FR.live_case()
+    tmp = tempfile.mkdtemp(prefix="h2fastfrag")
+    base = FR.build_index(g, tmp, os.path.dirname(BUILD))
+    r = FC.fast_check(base, reads)
+    assert r["mismatching"] == 0, r
+    short = sum(1 for x in reads if len(x) <= 128)
+    assert r["bails"].get("input", 0) == len(reads) - short and r["completed"] > 0, r
+    print("reads:", r)
+    r = FC.fast_check(base, m1, m2)
+    assert r["mismatching"] == 0 and r["completed"] > 0, r
+    print("pairs:", r)

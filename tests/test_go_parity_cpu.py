@@ -142,3 +142,45 @@ def test_live_reference_ignore_quals(extra):
     import fuzz_align as F
     bad, _ = F.run_case(8001, 3000, 101, 0.02, 0.001, 0.0, extra=extra, verbose=2, fastq=True)
     assert bad == 0
+
+
+# ---------------------------------------------------------------- fragmented assembly (tests/frag_cases.py)
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "hisat2-align-s")), reason="needs oracle/_ref")
+@pytest.mark.parametrize("case", [
+    dict(),
+    dict(fastq=True, extra=("--mp", "4,2")),
+    dict(spliced=True),                   # --no-temp-splicesite: a read whose halves lie either side of an N run becomes a spliced alignment over it
+    dict(snps=True),                      # SNP-graph index, variants 0-4 bases from contig ends and N runs, reads from the alternate haplotype
+], ids=["plain", "fastq-mp", "spliced", "snp-graph"])
+def test_live_reference_fragmented_assembly(case):
+    """~1100 texts of 25 to 12 000 bases with N runs of every small length and two all-N records the builder drops; 3000 reads of 36-150 bases in
+    one batch: interior, hanging off contig ends, straddling two texts / two fragments in the joined string, across N runs, whole short contigs,
+    zero overhang, a repeat whose copies sit at contig ends.  No read is left out; the classes must have exercised their edges (teeth)."""
+    import frag_cases as FC
+    import fuzz_align as F
+    case = dict(case)
+    g, reads, labels, _, _, _ = FC.live_case()
+    variants = None
+    if case.pop("snps", False):
+        g = FC.make_frag_genome(FC.LIVE_SEED, FC.GRAPH_TOTAL)
+        variants, alt = FC.make_frag_snps(g, FC.LIVE_SEED + 5)
+        reads, labels = FC.make_frag_reads(alt, FC.LIVE_SEED + 6, 3000)
+    info = {}
+    bad, _ = F.run_case(FC.LIVE_SEED, genome=(g.records, g.names), reads=reads, variants=variants, info=info, verbose=5, **case)
+    assert bad == 0 and info["overflow"] == 0
+    assert info["refnames"] == g.text_names()          # the all-N records are not texts: ids shift against record order
+    if not case and not variants:
+        FC.assert_teeth(FC.read_teeth(info["want"], labels), FC.LIVE_READ_MINIMA)
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "hisat2-align-s")), reason="needs oracle/_ref")
+def test_live_reference_fragmented_assembly_pairs():
+    """pairs inside one short contig (overlapping, one mate inside the other, fragment == contig), a mate hanging off the contig end, mates on two
+    texts that are neighbours in the joined string (concordant in joined coordinates: must not pair), mates either side of a 300-N run"""
+    import frag_cases as FC
+    import fuzz_pairs as F
+    g, _, _, m1, m2, plabels = FC.live_case()
+    info = {}
+    bad, _ = F.run_case(FC.LIVE_SEED, genome=(g.records, g.names), pairs=(m1, m2), info=info, verbose=5)
+    assert bad == 0 and info["overflow"] == 0
+    FC.assert_teeth(FC.pair_teeth(info["want"], plabels), FC.LIVE_PAIR_MINIMA)

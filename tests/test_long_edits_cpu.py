@@ -113,3 +113,58 @@ def test_records_beyond_32_edits_equal_the_reference(case):
     rc = L.h2g_sam_format_unpaired_dense(h, codes.ctypes.data, offs.ctypes.data, None, nb, noffs.ctypes.data, n, C.addressof(res), C.addressof(dense), offs64.ctypes.data, buf, 1 << 22, C.byref(u))
     assert rc == 0 and buf.raw[:u.value].decode().splitlines() == want
     L.h2g_sam_close(h)
+
+
+NWHOLE_MIN = 100      # the reference aligns all 200 reads of the case below end to end across the run (measured from its SAM): half of that
+
+
+def _align_long(base, reads, opts):
+    """the large-workspace configuration on the host over a list of reads -> SAM body lines, number of records beyond 32 edits, reads still flagged"""
+    n = len(reads)
+    e = Emu(base, "long")
+    set_options(e, 0, opts)
+    codes, offs = SL.flat(reads)
+    e.set_reads(codes, offs, None)
+    names = [str(i) for i in range(n)]
+    nb, noffs = SL.flat_names(names)
+    outs = (SU.ReadOut * n)()
+    rows = (api.AlnRes * (n * api.ALN_CAP))()
+    cap = 1 << 18
+    led = (api.Edit * cap)()
+    used = C.c_uint32(0)
+    vp = C.c_void_p
+    e.L.h2gemu_align_abi.argtypes = [vp, C.c_uint32, C.c_char_p, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    e.L.h2gemu_align_abi(e.h, 1, nb, noffs.ctypes.data, outs, rows, api.ALN_CAP, led, cap, C.byref(used))
+    res = (api.ReadResult * n)()
+    nlong = flagged = 0
+    for i in range(n):
+        o, r = outs[i], res[i]
+        flagged += o.overflow != 0
+        r.nres, r.nselect, r.overflow, r.nrank, r.nsteps, r.depth = o.nres, o.nselect, o.overflow, o.nrank, o.nsteps, o.depth
+        r.best, r.secbest, r.best_h2, r.secbest_h2 = o.best, o.secbest, o.best_h2, o.secbest_h2
+        nlong += sum(1 for k in range(min(o.nselect, api.ALN_CAP)) if rows[i * api.ALN_CAP + k].nedits > api.MAX_EDITS)
+    got = SL.format_unpaired(SL.load_sam_lib(), base, reads, names, res, rows, options=opts, long_edits=(led, used.value))
+    return got, nlong, flagged
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "hisat2-align-s")), reason="needs oracle/_ref")
+def test_reads_across_a_50_base_N_run_equal_the_reference():
+    """a read with real bases where the assembly has a run of 50 Ns: GenomeHit::extend charges nothing for a reference N, so the reference aligns the read end to end
+    with 50+ mismatch edits in one record (found with tests/frag_cases.py: the default units flag such a read, overflow bit 1, and the large workspace takes it)"""
+    import frag_cases as FR
+    g = FR.live_case()[0]
+    reads = FR.make_nrun_reads(g, 2850, 200)
+    tmp = tempfile.mkdtemp(prefix="h2longn")
+    base = FR.build_index(g, tmp, REF)
+    rfa, sam = os.path.join(tmp, "r.fa"), os.path.join(tmp, "ref.sam")
+    FR.write_reads(rfa, reads)
+    subprocess.run([os.path.join(REF, "hisat2-align-s"), "-f", "-p", "1", "--no-spliced-alignment", "-x", base, "-U", rfa, "-S", sam], check=True,
+                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    want = SL.body_lines(sam)
+    nwhole = sum(1 for l in want if "NM:i:" in l and int(l.split("NM:i:")[1].split("\t")[0]) >= 50)
+    print("lines with 50+ edits in the reference's SAM:", nwhole)
+    assert nwhole >= NWHOLE_MIN
+    got, nlong, flagged = _align_long(base, reads, [])
+    assert flagged == 0 and nlong >= nwhole
+    bad = [i for i, (x, y) in enumerate(zip(got, want)) if x != y]
+    assert len(got) == len(want) and not bad, (len(bad), got[bad[0]], want[bad[0]])

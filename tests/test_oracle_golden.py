@@ -389,3 +389,88 @@ def test_sw_reference_known_answer_cases(oracle_lib, golden_dir):
         nfound += o.found
         nwide += case["minsc"] < -254
     assert len(cases) == 105 and nfound > 60 and nwide == 1
+
+
+# ---------------------------------------------------------------- fragmented assembly (gfrag): the oracle itself against the new vectors
+@pytest.fixture(scope="module")
+def gfrag_index(tmp_path_factory, golden_dir):
+    import parity_cases as PC
+    return PC.unpack_index(golden_dir, "gfrag", tmp_path_factory.mktemp("gfrag"))
+
+
+def test_frag_params_offset_stretch(oracle_lib, gfrag_index, golden_dir):
+    ix = H.load_index(oracle_lib, gfrag_index)
+    kv = H.glines(golden_dir, "probe_gfrag_params.txt.gz")[0].split()
+    d = dict(zip(kv[0::2], map(int, kv[1::2])))
+    p = ix.contents.g.p
+    for k in ("len", "gbwtLen", "numNodes", "lineRate", "offRate", "ftabChars", "eftabLen", "linear", "sideSz", "sideGbwtSz", "sideGbwtLen", "numSides", "offsLen"):
+        assert getattr(p, k) == d[k], k
+    assert ix.contents.g.nPat == d["nPat"] and ix.contents.g.nFrag == d["nFrag"] and d["nFrag"] >= 300
+    g = C.byref(ix.contents.g)
+    for l in H.glines(golden_dir, "probe_gfrag_offset.txt.gz"):
+        row, off, qlen, ok, tidx, toff, tlen, strad = map(int, l.split())
+        st = C.c_uint32(0)
+        assert oracle_lib.h2o_get_offset(g, row, C.byref(st)) == off
+        if off < p.len:
+            a, b, c_, s = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+            got = oracle_lib.h2o_joined_to_text(g, qlen, off, C.byref(a), C.byref(b), C.byref(c_), 0, C.byref(s))
+            assert (got, a.value, b.value, c_.value, s.value) == (ok, tidx, toff, tlen, strad)
+    r = C.byref(ix.contents.r)
+    for l in H.glines(golden_dir, "probe_gfrag_stretch.txt.gz"):
+        tidx, toff, cnt, s = l.split()
+        buf = np.zeros(int(cnt), dtype=np.uint8)
+        oracle_lib.h2o_get_stretch(r, int(tidx), int(toff), int(cnt), buf.ctypes.data)
+        assert bytes(b"ACGTN"[x] for x in buf) == s.encode(), l
+
+
+def test_frag_partial_search_and_coords(oracle_lib, gfrag_index, golden_dir):
+    import parity_cases as PC
+    ix = H.load_index(oracle_lib, gfrag_index)
+    seqs, _, _ = PC.load_frag_reads(golden_dir)
+    for l in H.glines(golden_dir, "probe_gfrag_psearch.txt.gz"):
+        v = list(map(int, l.split()))
+        seq = np.ascontiguousarray(seqs[v[0]] if v[1] else H.revcomp(seqs[v[0]]))
+        o = H.BwtHit()
+        oracle_lib.h2o_partial_search(ix, seq.ctypes.data, len(seq), 0, 0, 1, 5, C.byref(o))
+        got = [o.top, o.bot, o.node_top, o.node_bot, o.bwoff, o.len, o.hit_type, o.cur, o.done, o.numPartialSearch, o.numUniqueSearch, o.pseudogeneStop, o.anchorStop]
+        assert got == v[2:], (v[0], v[1], got, v[2:])
+    nrej = 0
+    for l in H.glines(golden_dir, "probe_gfrag_coords.txt.gz"):
+        f = l.split()
+        rej, ok = int(f[0]), int(f[1])
+        top, bot, rdoff, hlen, strad, n = map(int, f[4:10])
+        co = (H.Coord * 32)()
+        nco, st, steps = C.c_uint32(0), C.c_int(0), C.c_uint32(0)
+        got = oracle_lib.h2o_genome_coords(ix, top, bot, bot - top, hlen, rej, co, C.byref(nco), C.byref(st), C.byref(steps))
+        assert (got, nco.value, st.value) == (ok, n, strad), l
+        for k in range(n):
+            t, o_, j = map(int, f[10 + k].split(":"))
+            assert (co[k].tidx, co[k].toff, co[k].joinedOff) == (t & 0xFFFFFFFF, o_, j)
+        nrej += not ok
+    import frag_cases as FC
+    assert nrej >= FC.MINIMA["coords_rejected"]
+
+
+@pytest.mark.parametrize("fn", ["probe_gfrag_extend.txt.gz", "probe_gfrag_extend_fq.txt.gz"])
+def test_frag_extend(oracle_lib, gfrag_index, golden_dir, fn):
+    import frag_cases as FC
+    import parity_cases as PC
+    ix = H.load_index(oracle_lib, gfrag_index)
+    seqs, _, offs = PC.load_frag_reads(golden_dir)
+    quals = FC.seeded_quals(seqs, FC.GFRAG_SEED + 2) if fn.endswith("_fq.txt.gz") else None
+    sc = H.Scoring()
+    oracle_lib.h2o_scoring_default(C.byref(sc))
+    cache = {}
+    for c in PC.parse_frag_extend(golden_dir, fn):
+        rid, fw, rdoff, hlen, tidx, toff, joff, mm, bound, r = c
+        if (rid, fw) not in cache:
+            q = b"I" * len(seqs[rid]) if quals is None else quals[offs[rid]:offs[rid + 1]].tobytes()
+            cache[(rid, fw)] = (np.ascontiguousarray(seqs[rid] if fw else H.revcomp(seqs[rid])), q if fw else q[::-1])
+        seq, qual = cache[(rid, fw)]
+        h = H.GHit()
+        h.fw, h.rdoff, h.len, h.tidx, h.toff, h.joinedOff = fw, rdoff, hlen, tidx, toff, joff
+        le, re = C.c_uint32(bound), C.c_uint32(bound)
+        ext = oracle_lib.h2o_extend(ix, C.byref(sc), seq.ctypes.data, qual, len(seq), C.byref(h), C.byref(le), C.byref(re), mm)
+        got = [ext, h.rdoff, h.len, h.toff, h.joinedOff, le.value, re.value, h.score, h.nedits]
+        assert got == list(map(int, r[:9])), (c[:9], got, r)
+        assert [f"{h.edits[k].pos}:{chr(h.edits[k].chr)}>{chr(h.edits[k].qchr)}" for k in range(h.nedits)] == r[9:], (c[:9], r)
