@@ -257,8 +257,28 @@ private:
 	inline static std::vector<std::string> paths_;   // (static: the exit handler outlives main's frame)
 };
 
+// The reference's two warnings for every read or mate the length filter drops (printMmsSkipMsg / printLenSkipMsg, hisat2.cpp:3017-3052; the worker at :3417-3432:
+// length <= the seed mismatches, which are 0, or < 2), in its order: the first message for mate 1 and mate 2, then the second for both.  The length is the trimmed
+// one, the name the record's as it was read.  `b`: the second mates when record i is a pair.  --quiet (gQuiet) takes them with the summary.
+void warn_length_filtered(const Batch& a, const Batch* b, size_t i) {
+	if(a.offs[i + 1] - a.offs[i] >= 2 && (!b || b->offs[i + 1] - b->offs[i] >= 2)) return;   // the common case: nothing to say
+	const Batch* m[2] = {&a, b};
+	for(int msg = 0; msg < 2; msg++) for(int k = 0; k < (b ? 2 : 1); k++) {
+		const Batch& s = *m[k];
+		const uint32_t len = s.offs[i + 1] - s.offs[i];
+		if(len >= 2) continue;
+		std::string w = "Warning: skipping ";
+		if(b) { w += "mate #"; w += (char)('1' + k); w += " of "; }
+		w += "read '"; w.append(s.names, s.noffs[i], s.noffs[i + 1] - s.noffs[i]);
+		if(msg == 0) w += "' because length (" + std::to_string(len) + ") <= # seed mismatches (0)\n";
+		else w += "' because it was < 2 characters long\n";
+		fwrite(w.data(), 1, w.size(), stderr);
+	}
+}
+
 // --parse-only (test hook): records, bases and a checksum over every window of <--batch> records (codes, names, qualities and lengths of the unpaired reads and first
-// mates, then those of the second mates), then the number of pairs and of unpaired reads; one line per --un / --al option with the file name(s) it would write
+// mates, then those of the second mates), then the number of pairs and of unpaired reads; one line per --un / --al option with the file name(s) it would write.
+// On stderr: the length-filter warnings of the records, as a run writes them.
 int parse_only(const Options& o) {
 	Source src(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, false, o.skip, o.upto);
 	Win w;
@@ -266,6 +286,7 @@ int parse_only(const Options& o) {
 	auto mix = [&](const void* p, size_t len) { const uint8_t* c = (const uint8_t*)p; for(size_t i = 0; i < len; i++) { h ^= c[i]; h *= 1099511628211ull; } };
 	while(src.next(w, o.batch)) {
 		n += w.n; npairs += w.npairs;
+		if(!o.quiet) for(size_t i = 0; i < w.n; i++) warn_length_filtered(w.a, (w.kinds.empty() ? w.paired : w.kinds[i] != 0) ? &w.b : nullptr, i);
 		for(int m = 0; m < (w.npairs ? 2 : 1); m++) {
 			const Batch& b = m ? w.b : w.a;
 			bases += b.codes.size();
@@ -635,7 +656,7 @@ struct FmtJob { long batch; size_t n; uint64_t first_id; int set; bool paired; i
 // before the next wave starts, and submit() formats on the caller's thread.  Either way one thread formats: everything below the queue is that thread's.
 class FormatStage {
 public:
-	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites; uint32_t khits; };
+	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites, warn_short; uint32_t khits; };
 	FormatStage(const Config& c, h2g_sam* sam, ParseStage& parse, TextWriter& writer, ReadSorter& sorter, SpliceSites& sites, const Replicas& ix)
 		: c_(c), sam_(sam), parse_(parse), writer_(writer), sorter_(sorter), sites_(sites), ix_(ix) { if(c_.async) thread_ = std::thread(&FormatStage::run, this); }
 	~FormatStage() { finish(); }
@@ -720,6 +741,7 @@ private:
 			size_t& i = k ? ip : is;
 			const uint64_t t0 = i ? mends_[m][i - 1] : 0, t1 = mends_[m][i];
 			memcpy(buf.data() + at, mtext_[m].data() + t0, (size_t)(t1 - t0));
+			if(c_.warn_short) warn_length_filtered(k ? pa : a, k ? &pb : nullptr, i);   // (one thread formats, in record order: each warning once, ahead of the summary)
 			if(sorter_.on) sort_record(k ? pa : a, k ? &pb : nullptr, i, buf.data() + at, buf.data() + at + (t1 - t0));
 			at += (size_t)(t1 - t0);
 			i++;
@@ -755,6 +777,7 @@ private:
 			std::vector<uint64_t>& ends = mends_[0];
 			format_item(job, buf, used, sorter_.on ? &ends : nullptr);
 			Batch& a = parse_.a(job.batch); Batch& b = parse_.b(job.batch);
+			if(c_.warn_short) for(size_t i = 0; i < n; i++) warn_length_filtered(a, job.paired ? &b : nullptr, i);
 			if(sorter_.on) for(size_t i = 0; i < n; i++) sort_record(a, job.paired ? &b : nullptr, i, buf.data() + (i ? ends[i - 1] : 0), buf.data() + ends[i]);
 		}
 		if(c_.drop_unal) used = drop_unaligned(buf, used);
@@ -986,7 +1009,7 @@ int main(int argc, char** argv) {
 	// the stages; their destructors join in the reverse order, whatever way out is taken
 	TextWriter writer(out);
 	ParseStage parse(src, H, batch, wv, ix.streams());
-	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, P.khits}, sam, parse, writer, sorter, sites, ix);
+	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits}, sam, parse, writer, sorter, sites, ix);
 	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch}, P, wv, ix, parse, fmt);
 	double t_parse = 0;                                   // what the main thread waited for the parser
 	bool short_mates = false;

@@ -461,7 +461,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	if(rs && rso && summ.paired && (rs->tidx == rso->tidx || fl.concordant())) put(o, fragment_length(*rs, *rso, fl.readMate1(), fl.concordant() && S.tlen_adjust ? &S : nullptr, tl_rdid));
 	else o.push_back('0');
 	o.push_back('\t');
-	if(!fl.primary && S.omit_sec_seq) o += "*\t*\t";                     // aln_sink.h:3190, :3206
+	if((!fl.primary && S.omit_sec_seq) || rd.len == 0) o += "*\t*\t";    // aln_sink.h:3190, :3206; a read without bases: '*' too (:3194, :3209)
 	else { o += seq; o.push_back('\t'); o += qual; o.push_back('\t'); }
 	if(!rs) {                                                            // printEmptyOptFlags sam.h:1033-1100
 		o += "YT:Z:";

@@ -32,6 +32,7 @@ struct Emu {
 	std::vector<uint32_t> offs;
 	std::vector<char> quals;
 	bool has_quals = false;
+	std::vector<char> quals2;                             // second mates (h2gemu_set_mate_quals): FASTQ pairs; empty = 'I'
 	LocalPack lp;
 	DLocalSet dls;
 	DAlts dalts;
@@ -100,7 +101,10 @@ void h2gemu_set_reads(Emu* e, const uint8_t* codes, const uint32_t* offs, const 
 	e->offs.assign(offs, offs + n + 1);
 	e->has_quals = quals != nullptr;
 	if(quals) e->quals.assign(quals, quals + offs[n]);
+	e->quals2.clear();
 }
+// qualities of the second mates handed to h2gemu_align_pairs / h2gemu_fast_check (phred+33, over their offsets); they go with the reads set last
+void h2gemu_set_mate_quals(Emu* e, const char* quals, size_t nbytes) { e->quals2.assign(quals, quals + nbytes); e->quals2.resize(nbytes + 8, 'I'); }
 
 void h2gemu_rank(Emu* e, const uint32_t* rows, const uint8_t* cs, size_t n, uint32_t* out) {
 	const bool graph = !e->dg.linear;
@@ -380,7 +384,7 @@ void h2gemu_align_pairs(Emu* e, uint32_t no_spliced, const uint8_t* codes2, cons
 	AlignWS* ws = new AlignWS();
 	Mach M;
 	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = nullptr;
+	M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = e->quals2.empty() ? nullptr : e->quals2.data();
 	MachOut O; O.rout = nullptr; O.aln = nullptr; O.pout = outs; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = EMU_REC_STRIDE;
 	for(uint32_t i = 0; i < M.rd[0].n; i++) {
 		M.name[0] = names1 + noffs1[i]; M.namelen[0] = noffs1[i + 1] - noffs1[i];
@@ -454,7 +458,7 @@ void h2gemu_fast_check(Emu* e, const uint8_t* codes2, const uint32_t* offs2, con
 	AlignWS* ws = new AlignWS();
 	Mach M;
 	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	if(paired) { M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = nullptr; }
+	if(paired) { M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = e->quals2.empty() ? nullptr : e->quals2.data(); }
 	const uint32_t n = M.rd[0].n, slots = 16;
 	std::vector<PairOut> mp(1), fp(n);
 	std::vector<ReadOut> mr(1), fr(n);

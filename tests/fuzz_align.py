@@ -21,7 +21,7 @@ def run_case(seed, nreads=0, rdlen=0, sub=0.0, indel=0.0, nrate=0.0, lens=(30000
              genome=None, reads=None, variants=None, info=None, spliced=False):
     """genome = (records, names) with reads = a list of read arrays (any lengths): a prepared case instead of lens= / nreads= / rdlen=; variants = a
     synth.write_snps list for a graph index of the prepared genome.  info: a dict that receives the reference's records ("want"), the @SQ names
-    ("refnames") and the counts ("bad", "overflow", "aligned") of the run.  spliced (prepared cases): spliced alignment, every read on its own
+    ("refnames"), the counts ("bad", "overflow", "aligned") of the run and the ids of the reads with an overflow bit ("flagged").  spliced (prepared cases): spliced alignment, every read on its own
     (--no-temp-splicesite), instead of --no-spliced-alignment."""
     if genome is not None:
         return _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced)
@@ -118,7 +118,7 @@ def _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie
     naln = sum(1 for q in qnames if want[q][0][0] != 4)
     print(f"seed {seed} {what}: aligned(ref) {naln}  mismatching {bad} (set-level {setbad})  overflow {ovf}  max depth {maxdep}  tmp {tmp}")
     if info is not None:
-        info.update(want=want, got=got, refnames=refnames, bad=bad, overflow=ovf, aligned=naln, base=base, tmp=tmp)
+        info.update(want=want, got=got, refnames=refnames, bad=bad, overflow=ovf, aligned=naln, base=base, tmp=tmp, flagged=[i for i in range(nreads) if outs[i].overflow])
     return bad, tmp
 
 

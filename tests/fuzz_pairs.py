@@ -39,7 +39,8 @@ def write_fasta_reads(path, m):
             f.write(b">%d\n" % i + synth._ALPHA[np.asarray(m[i])].tobytes() + b"\n")
 
 
-def emu_pairs(base, m1, m2, q1, q2):
+def emu_pairs(base, m1, m2, q1, q2, quals=None):
+    """quals = (flat phred+33 bytes of the first mates, of the second mates): FASTQ pairs"""
     e = Emu(base)
     e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
     e.L.h2gemu_set_bowtie2_dp(e.h, DP)
@@ -49,7 +50,12 @@ def emu_pairs(base, m1, m2, q1, q2):
     n = len(m1)
     c1, o1 = flatten(m1)
     c2, o2 = flatten(m2)
-    e.set_reads(c1, o1)
+    e.set_reads(c1, o1, None if quals is None else quals[0])
+    if quals is not None:
+        q2b = np.ascontiguousarray(quals[1], dtype=np.uint8)
+        assert q2b.size == c2.size
+        e.L.h2gemu_set_mate_quals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        e.L.h2gemu_set_mate_quals(e.h, q2b.ctypes.data, q2b.size)
     nb1 = "".join(q1).encode(); no1 = np.concatenate([[0], np.cumsum([len(q) for q in q1])]).astype(np.uint32)
     nb2 = "".join(q2).encode(); no2 = np.concatenate([[0], np.cumsum([len(q) for q in q2])]).astype(np.uint32)
     outs = (PS.PairOut * n)()
@@ -95,18 +101,23 @@ MUTATORS = {"flip": _flip, "nmask": _nmask}
 
 
 def run_case(seed, npairs=0, rdlen=0, sub=0.0, lens=(300000, 120000, 60000), repeats=6, gaps=2, frag_mean=300, frag_sd=30, verbose=6,
-             backend=None, stride=16, mutate=None, genome=None, pairs=None, info=None):
-    """genome = (records, names) with pairs = (mate 1 list, mate 2 list): a prepared case instead of lens= / npairs= / rdlen=.  info: a dict that
-    receives the reference's records ("want") and the counts ("bad", "overflow", "concordant") of the run."""
+             backend=None, stride=16, mutate=None, genome=None, pairs=None, info=None, variants=None):
+    """genome = (records, names) with pairs = (mate 1 list, mate 2 list): a prepared case instead of lens= / npairs= / rdlen=; variants = a
+    synth.write_snps list for a graph index of the prepared genome.  info: a dict that receives the reference's records ("want") and the counts
+    ("bad", "overflow", "concordant") of the run."""
     tmp = tempfile.mkdtemp(prefix="h2pe")
     if genome is not None:
         fa = os.path.join(tmp, "g.fa")
         synth.write_fasta(fa, genome[0], names=genome[1])
         base = os.path.join(tmp, "g")
-        subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q", fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        snp = []
+        if variants:
+            synth.write_snps(os.path.join(tmp, "g.snp"), variants)
+            snp = ["--snp", os.path.join(tmp, "g.snp")]
+        subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q"] + snp + [fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         m1, m2 = pairs
         npairs = len(m1)
-        return _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, f"prepared n {npairs}")
+        return _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, f"prepared n {npairs}", graph=bool(variants))
     contigs = synth.make_genome(list(lens), seed, n_gaps=gaps, gap_len=300, repeats=repeats, repeat_len=500)
     fa = os.path.join(tmp, "g.fa")
     synth.write_fasta(fa, contigs)
@@ -126,7 +137,7 @@ def run_case(seed, npairs=0, rdlen=0, sub=0.0, lens=(300000, 120000, 60000), rep
     return _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, f"n {npairs} len {rdlen} sub {sub}")
 
 
-def _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, what):
+def _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, what, graph=False):
     f1, f2 = os.path.join(tmp, "r1.fa"), os.path.join(tmp, "r2.fa")
     write_fasta_reads(f1, m1)
     write_fasta_reads(f2, m2)
@@ -142,7 +153,7 @@ def _compare(seed, tmp, base, m1, m2, npairs, verbose, backend, stride, info, wh
     elif "--very-sensitive" in OPTS and "--sensitive" not in OPTS and khits < 30:
         khits, saw_k = 30, True
     if not saw_k:
-        khits = 10 if SNPS else 5
+        khits = 10 if SNPS or graph else 5
     secondary = "--secondary" in OPTS
     q = [str(i) for i in range(npairs)]
     outs, r1, r2 = (backend or emu_pairs)(base, m1, m2, q, q)

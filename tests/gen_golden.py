@@ -19,6 +19,9 @@ for a small seeded genome ("g1"):
   probe_gfrag_{params,offset,stretch,psearch,coords,extend,extend_fq,extsearch,localof}.txt.gz
                                   coords: getGenomeCoords with rejectStraddle 0 and 1; extend: max_leftext / max_rightext unbounded, 0, 1, 7, 33
                                   (_fq: the same reads as FASTQ with seeded qualities); localof: HGFM::getLocalGFM at and past every text's end
+`gen_golden.py ragged` adds the TRIMMED read sets (tests/ragged_cases.py) on the index g1, without touching the above:
+  ragged_se.fq.gz, ragged_pe_{1,2}.fq.gz   2000 reads / 1500 pairs of 0-300 bases, mates of different lengths, empty records
+  ragged_{se,pe}.sam.gz, ragged_{se,pe}.err.gz   hisat2-align-s -q -p 1 --no-spliced-alignment: the SAM body, and stderr (length-filter warnings + summary)
 Everything is deterministic (seeds below); the fixtures are committed.
 """
 import gzip
@@ -340,9 +343,48 @@ def main_frag():
             print(f, os.path.getsize(os.path.join(GOLD, f)))
 
 
+def main_ragged():
+    """tests/ragged_cases.py on the committed index g1: 2000 ragged reads and 1500 ragged pairs as FASTQ, the reference's SAM body and its stderr (the
+    length-filter warnings, then the summary)"""
+    sys.path.insert(0, HERE)
+    import ragged_cases as RC
+    tmp = tempfile.mkdtemp(prefix="h2goldr")
+    for k in range(1, 9):
+        open(os.path.join(tmp, f"g1.{k}.ht2"), "wb").write(gzip.open(os.path.join(GOLD, f"g1.{k}.ht2.gz")).read())
+    base = os.path.join(tmp, "g1")
+    contigs = synth.make_genome([60000, 45000, 30000], SEED, n_gaps=1, gap_len=500, repeats=2, repeat_len=400)
+    minK, ftab = RC.index_params(base)
+    reads, labels = RC.make_ragged_reads(contigs, RC.GOLDEN_SEED, RC.GOLDEN_NREADS, minK, ftab)
+    m1, m2, plabels = RC.make_ragged_pairs(contigs, RC.GOLDEN_SEED + 1, RC.GOLDEN_NPAIRS, minK, ftab)
+    files = {}
+    for tag, rs, seed, pre in (("se", reads, 2, "r"), ("pe_1", m1, 3, "p"), ("pe_2", m2, 4, "p")):
+        files[tag] = os.path.join(tmp, f"ragged_{tag}.fq")
+        RC.write_reads(files[tag], rs, RC.seeded_quals(rs, RC.GOLDEN_SEED + seed), [f"{pre}{i}" for i in range(len(rs))])
+        gz_write(os.path.join(GOLD, f"ragged_{tag}.fq.gz"), open(files[tag], "rb").read())
+    for tag, inputs in (("se", ["-U", files["se"]]), ("pe", ["-1", files["pe_1"], "-2", files["pe_2"]])):
+        sam = os.path.join(tmp, tag + ".sam")
+        err = run([os.path.join(REF, "hisat2-align-s"), "-q", "-p", "1", "--no-spliced-alignment", "-x", base, "-S", sam] + inputs).stderr
+        body = [l for l in open(sam, "rb") if not l.startswith(b"@")]
+        gz_write(os.path.join(GOLD, f"ragged_{tag}.sam.gz"), b"".join(body))
+        gz_write(os.path.join(GOLD, f"ragged_{tag}.err.gz"), err)
+        ln = sum(1 for l in body if l.rstrip().endswith(b"YF:Z:LN"))
+        if tag == "se":
+            print("reads:", len(reads), "aligned", sum(1 for l in body if l.split(b"\t")[1] != b"4"), "YF:Z:LN lines", ln,
+                  {c: sum(1 for x in labels if x == c) for c in RC.READ_CLASSES})
+        else:
+            print("pairs:", len(m1), "concordant", sum(1 for l in body if int(l.split(b"\t")[1]) & 2) // 2, "YF:Z:LN lines", ln,
+                  {c: sum(1 for x in plabels if x == c) for c in RC.PAIR_CLASSES})
+    shutil.rmtree(tmp)
+    for f in sorted(os.listdir(GOLD)):
+        if f.startswith("ragged_"):
+            print(f, os.path.getsize(os.path.join(GOLD, f)))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "frag":
         main_frag()
+    elif len(sys.argv) > 1 and sys.argv[1] == "ragged":
+        main_ragged()
     elif len(sys.argv) > 1 and sys.argv[1] == "combine":
         sys.path.insert(0, HERE)
         main_combine()

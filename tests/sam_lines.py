@@ -181,8 +181,8 @@ def format_unpaired(L, base, reads, names, res, aln, quals=None, options=(), lon
     return buf.raw[:used.value].decode().splitlines()
 
 
-def format_paired(L, base, m1, m2, n1, n2, res, a1, a2, khits, options=(), dense=None):
-    """dense = (offs1, offs2): a1 / a2 hold every pair's records back to back (h2g_align_pairs_fetch_dense's layout), uint64 offsets [n + 1]"""
+def format_paired(L, base, m1, m2, n1, n2, res, a1, a2, khits, options=(), dense=None, quals=None):
+    """quals = (flat phred+33 bytes of the first mates, of the second mates): FASTQ pairs.  dense = (offs1, offs2): a1 / a2 hold every pair's records back to back (h2g_align_pairs_fetch_dense's layout), uint64 offsets [n + 1]"""
     h = C.c_void_p()
     assert L.h2g_sam_open(base.encode(), C.byref(h)) == 0
     _score_min(L, h, options)
@@ -195,11 +195,16 @@ def format_paired(L, base, m1, m2, n1, n2, res, a1, a2, khits, options=(), dense
     buf = C.create_string_buffer(cap)
     used = C.c_size_t(0)
     ptr = lambda x: x.ctypes.data if isinstance(x, np.ndarray) else C.addressof(x)
+    qp1 = qp2 = None
+    if quals is not None:
+        quals = [np.ascontiguousarray(q, dtype=np.uint8) for q in quals]
+        assert quals[0].size == c1.size and quals[1].size == c2.size
+        qp1, qp2 = quals[0].ctypes.data, quals[1].ctypes.data
     if dense is not None:
-        rc = L.h2g_sam_format_paired_dense(h, c1.ctypes.data, o1.ctypes.data, None, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, None, nb2,
+        rc = L.h2g_sam_format_paired_dense(h, c1.ctypes.data, o1.ctypes.data, qp1, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, qp2, nb2,
                                            no2.ctypes.data, n, ptr(res), ptr(a1), dense[0].ctypes.data, ptr(a2), dense[1].ctypes.data, khits, buf, cap, C.byref(used))
     else:
-        rc = L.h2g_sam_format_paired(h, c1.ctypes.data, o1.ctypes.data, None, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, None, nb2,
+        rc = L.h2g_sam_format_paired(h, c1.ctypes.data, o1.ctypes.data, qp1, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, qp2, nb2,
                                      no2.ctypes.data, n, ptr(res), ptr(a1), ptr(a2), khits, buf, cap, C.byref(used))
     if rc == 0 and not (options and ("--novel-splicesite-outfile" in options or "--new-summary" in options)) and n <= 20000:
         # the compact formatter over a host-compacted copy of the same records must write the same text
@@ -217,7 +222,7 @@ def format_paired(L, base, m1, m2, n1, n2, res, a1, a2, khits, options=(), dense
                                                      C.POINTER(C.c_size_t)]
         buf2 = C.create_string_buffer(used.value + 64)
         u2 = C.c_size_t(0)
-        rc2 = L.h2g_sam_format_paired_compact(h2, c1.ctypes.data, o1.ctypes.data, None, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, None, nb2, no2.ctypes.data, n, ptr(res),
+        rc2 = L.h2g_sam_format_paired_compact(h2, c1.ctypes.data, o1.ctypes.data, qp1, nb1, no1.ctypes.data, c2.ctypes.data, o2.ctypes.data, qp2, nb2, no2.ctypes.data, n, ptr(res),
                                               rec1, bo1.ctypes.data, rec2, bo2.ctypes.data, khits, buf2, used.value + 64, C.byref(u2))
         L.h2g_sam_close(h2)
         assert rc2 == 0 and buf2.raw[:u2.value] == buf.raw[:used.value], "compact formatter differs from the row formatter"

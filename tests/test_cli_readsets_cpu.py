@@ -1,6 +1,7 @@
 """The record stream of hisat2-align-amd, host side (no GPU, no index: `--parse-only` prints records, bases, a checksum over every window of <--batch>
 records, and the numbers of pairs and of unpaired reads): --tab5 / --tab6 / --12 / --qseq, -1/-2 together with -U, --solexa-quals / --int-quals, the
-reference's quality-count errors, and the file names of --un-conc and its kin (which `--parse-only` prints, one line per option)."""
+reference's quality-count errors, records of 0 and 1 bases with the length-filter warnings they bring (which `--parse-only` writes to stderr as a run does), and the
+file names of --un-conc and its kin (which `--parse-only` prints, one line per option)."""
 import gzip
 import math
 import os
@@ -132,6 +133,165 @@ def test_every_format_parses_to_the_same_records(tmp_path):
     want = expected(trecs, 700)
     for fmt, path in files.items():
         assert run(FLAG[fmt] + [path, "-p", 2, "--batch", 700, "-5", t5, "-3", t3, "-s", skip, "-u", upto]) == want, (fmt, "trim")
+
+
+def short_record_set(rng, n=600, short=(0, 1, 2, 8, 9)):
+    """names, sequences and qualities with records of 0, 1, 2, 8 and 9 bases among ordinary ones (-5 3 -3 5 cuts those of 2, 3, 4 and 8 to 0 and those of 9 to 1);
+    the shortest kind comes first, twice in a row, and last"""
+    names = [f"M{i % 5}_7_{i % 8}_{1100 + i % 90}_{int(rng.integers(0, 20000))}_{i}_0/1" for i in range(n)]
+    lens = [int(rng.choice(short)) if rng.random() < 0.4 else int(rng.integers(30, 160)) for _ in range(n)]
+    lens[0] = lens[7] = lens[8] = lens[-1] = min(short)
+    seqs = ["".join(rng.choice(list("ACGTNacgtRY"), size=k)) for k in lens]
+    quals = [rand_qual(rng, k) for k in lens]
+    return names, seqs, quals
+
+
+TRIM5, TRIM3 = 3, 5
+TAB_SHORT = (3, 4, 8, 9)      # under -5 3 the reference's tabbed parser aborts on a record of fewer than 3 bases: see test_records_of_zero_and_one_bases
+
+
+def mixed_short_lines(rng, fmt, n=600, short=(0, 1, 2, 8, 9)):
+    """a tabbed file of pairs and unpaired reads whose mates are empty, one base long or ordinary, each on its own -> (lines, records as expected() takes them)"""
+    draw = lambda: "".join(rng.choice(list("ACGT"), size=int(rng.choice(short)) if rng.random() < 0.4 else int(rng.integers(30, 160))))   # noqa: E731
+    recs, lines = [], []
+    for i in range(n):
+        nm = "r%d" % i
+        s1, s2 = draw(), draw()
+        q1, q2 = rand_qual(rng, len(s1)), rand_qual(rng, len(s2))
+        if rng.integers(0, 2):
+            lines.append(f"{nm}\t{s1}\t{q1}\t{s2}\t{q2}" if fmt == "tab5" else f"{nm}\t{s1}\t{q1}\tm{i}\t{s2}\t{q2}")
+            recs.append((nm, s1, q1, (nm if fmt == "tab5" else "m%d" % i, s2, q2)))
+        else:
+            lines.append(f"{nm}\t{s1}\t{q1}")
+            recs.append((nm, s1, q1, None))
+    return lines, recs
+
+
+def length_warnings(recs):
+    """the reference's two warnings per read or mate of fewer than 2 bases (hisat2.cpp:3017-3052, :3417-3432), for records as expected() takes them"""
+    from ragged_cases import length_warnings as model
+    return model([[(r[0], len(codes_of(r[1])))] + ([(r[3][0], len(codes_of(r[3][1])))] if r[3] is not None else []) for r in recs])
+
+
+def skip_warnings(stderr):
+    return [l for l in stderr.split("\n") if l.startswith("Warning: skipping read '") or l.startswith("Warning: skipping mate #")]
+
+
+def run_warnings(args):
+    """the length-filter warnings `--parse-only` writes to stderr: those of a run over the same records"""
+    return skip_warnings(subprocess.run([CLI, "--parse-only", "-x", "unused"] + [str(a) for a in args], check=True, capture_output=True, text=True).stderr)
+
+
+def trim_all(recs):
+    t = lambda r: (r[0],) + trimmed(r[1], r[2], TRIM5, TRIM3)      # noqa: E731
+    return [t(r) + (None if r[3] is None else t(r[3]),) for r in recs]
+
+
+def test_records_of_zero_and_one_bases(tmp_path):
+    """records without bases and with one base, and -5 / -3 values that cut reads down to 0 or 1 bases, in FASTQ, tab5, tab6, --12 and QSEQ, as mates of tabbed
+    pairs and of -1/-2 files, for several thread counts and batch sizes: every record stays a record (none is dropped or merged with its neighbour), with its name
+    and an empty sequence.  That this is what the reference does with each of these files is test_the_reference_keeps_records_of_zero_and_one_bases's to show.
+    One record kind is left out for the tabbed formats (--tab5, --tab6, --12), and only under -5: a record with fewer bases than -5 takes away.  The reference ends
+    such a run with "Error: Read ... has more read characters than quality values." (its tabbed parser trims the sequence while it reads it and then counts the
+    qualities against the untrimmed length); the trimmed tabbed runs use records of 3 bases and more (TAB_SHORT), which -5 3 -3 5 still cuts to 0 and 1, and
+    the refusal itself is asserted."""
+    rng = np.random.default_rng(21)
+    names, seqs, quals = short_record_set(rng)
+    files = write_formats(tmp_path, names, seqs, quals)
+    assert set(files) == {"fastq", "tab5", "tab6", "qseq"}
+    recs = [(nm, s, q, None) for nm, s, q in zip(names, seqs, quals)]
+    assert sum(1 for s in seqs if len(s) == 0) > 40 and sum(1 for s in seqs if len(s) == 1) > 20
+    tn, ts, tq = short_record_set(rng, short=TAB_SHORT)
+    tfiles = write_formats(tmp_path, tn, ts, tq, tag="_t")
+    trecs = {"fastq": trim_all(recs), "qseq": trim_all(recs)}
+    trecs["tab5"] = trecs["tab6"] = trim_all([(nm, s, q, None) for nm, s, q in zip(tn, ts, tq)])
+    for t in trecs.values():
+        assert sum(1 for x in t if len(x[1]) == 0) > 40 and sum(1 for x in t if len(x[1]) == 1) > 20
+    trim = ["-5", TRIM5, "-3", TRIM3]
+    for threads, batch in COMBOS:
+        for fmt, path in files.items():
+            assert run(FLAG[fmt] + [path, "-p", threads, "--batch", batch]) == expected(recs, batch), (fmt, threads, batch)
+            tpath = tfiles[fmt] if fmt.startswith("tab") else path
+            assert run(FLAG[fmt] + [tpath, "-p", threads, "--batch", batch] + trim) == expected(trecs[fmt], batch), (fmt, threads, batch, "trim")
+    assert run(["--12", files["tab5"]]) == expected(recs, 1 << 20)
+    assert run(["--12", tfiles["tab5"]] + trim) == expected(trecs["tab5"], 1 << 20)
+    # the length-filter warnings: two per read of fewer than 2 bases after trimming, in record order, once each whatever the windows and threads; none with --quiet
+    for fmt, path in files.items():
+        tpath = tfiles[fmt] if fmt.startswith("tab") else path
+        assert run_warnings(FLAG[fmt] + [path, "-p", 3, "--batch", 70]) == length_warnings(recs) != [], fmt
+        assert run_warnings(FLAG[fmt] + [tpath, "-p", 3, "--batch", 70] + trim) == length_warnings(trecs[fmt]), (fmt, "trim")
+        assert run_warnings(FLAG[fmt] + [path, "--quiet"]) == [], fmt
+    assert run(FLAG["fastq"] + [gz(files["fastq"]), "-p", 4]) == expected(recs, 1 << 20)
+    for flag in (["--tab5", files["tab5"]], ["--tab6", files["tab6"]], ["--12", files["tab5"]]):     # the reference's refusal, word for word
+        p = subprocess.run([CLI, "--parse-only", "-x", "unused"] + [str(a) for a in flag + trim], capture_output=True, text=True)
+        assert p.returncode == 1 and f"Error: Read {names[0]} has more read characters than quality values." in p.stderr.split("\n"), p
+    for fmt in ("tab5", "tab6"):
+        for short, tr in (((0, 1, 2, 8, 9), []), (TAB_SHORT, trim)):
+            lines, mrecs = mixed_short_lines(rng, fmt, short=short)
+            path = tmp_path / f"mixed_short{len(tr)}.{fmt}"
+            path.write_text("\n".join(lines) + "\n")
+            want = trim_all(mrecs) if tr else mrecs
+            for threads, batch in COMBOS:
+                assert run([f"--{fmt}", path, "-p", threads, "--batch", batch] + tr) == expected(want, batch), (fmt, threads, batch, tr)
+            assert run_warnings([f"--{fmt}", path, "-p", 2, "--batch", 50] + tr) == length_warnings(want), (fmt, tr)       # "mate #1 of read" / "mate #2 of read" for a pair's
+    # -1/-2 with -U: mates and unpaired reads of 0, 1, 2, 8, 9 and more bases as three FASTQ files, plain and trimmed
+    _, mrecs = mixed_short_lines(rng, "tab6")
+    pairs = [r for r in mrecs if r[3] is not None]
+    singles = [r for r in mrecs if r[3] is None]
+    for fn, rs in (("s_1.fq", [r[:3] for r in pairs]), ("s_2.fq", [r[3] for r in pairs]), ("s_u.fq", [r[:3] for r in singles])):
+        (tmp_path / fn).write_text("".join(f"@{nm}\n{s}\n+\n{q}\n" for nm, s, q in rs))
+    args = ["-q", "-1", tmp_path / "s_1.fq", "-2", tmp_path / "s_2.fq", "-U", tmp_path / "s_u.fq"]
+    for threads, batch in COMBOS:
+        wins = [range(b0, min(len(pairs), b0 + batch)) for b0 in range(0, len(pairs), batch)] + [range(len(pairs) + b0, len(pairs) + min(len(singles), b0 + batch)) for b0 in range(0, len(singles), batch)]
+        assert run(args + ["-p", threads, "--batch", batch]) == expected(pairs + singles, batch, wins), (threads, batch)
+        assert run(args + ["-p", threads, "--batch", batch] + trim) == expected(trim_all(pairs + singles), batch, wins), (threads, batch, "trim")
+    assert run_warnings(args + ["-p", 4, "--batch", 64]) == length_warnings(pairs + singles)
+    assert run_warnings(args + ["-p", 4, "--batch", 64] + trim) == length_warnings(trim_all(pairs + singles))
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "hisat2-align-s")), reason="needs oracle/_ref")
+def test_the_reference_keeps_records_of_zero_and_one_bases(tmp_path, g1_index):
+    """what test_records_of_zero_and_one_bases expects is what the reference does: one run of hisat2-align-s per format, and one with -5 3 -3 5, over the same
+    files; its SAM has one line per read or mate, in record order, under the record's name, with the sequence length the test computes ('*' for none).  The
+    reference takes an empty record in every one of these formats, also as the first and as the last record of a file (only its FASTA parser drops an empty last
+    record; there is no FASTA file here).  What it refuses is a tabbed record of fewer bases than -5 takes away: that run ends with an error, here as there."""
+    ref = os.path.join(ROOT, "oracle", "_ref", "hisat2-align-s")
+    rng = np.random.default_rng(21)
+    names, seqs, quals = short_record_set(rng)
+    files = write_formats(tmp_path, names, seqs, quals)
+    tn, ts, tq = short_record_set(rng, short=TAB_SHORT)
+    tfiles = write_formats(tmp_path, tn, ts, tq, tag="_t")
+    trim = ["-5", TRIM5, "-3", TRIM3]
+
+    def ref_run(args):
+        return subprocess.run([ref, "-p", "1", "--no-spliced-alignment", "-x", g1_index] + [str(a) for a in args], capture_output=True, text=True)
+
+    def ref_records(args):
+        p = ref_run(args)
+        assert p.returncode == 0, p.stderr[-500:]
+        assert skip_warnings(p.stderr) == run_warnings(args)              # the warnings on stderr: the reference's own, line for line
+        return [(t[0], 0 if t[9] == "*" else len(t[9])) for t in (l.split("\t") for l in p.stdout.splitlines() if not l.startswith("@")) if not int(t[1]) & 256]
+
+    def lengths(ns, ss, qs, tr):
+        return [(nm, len(codes_of(trimmed(s, q, TRIM5, TRIM3)[0] if tr else s))) for nm, s, q in zip(ns, ss, qs)]
+
+    for fmt, path in list(files.items()) + [("--12", files["tab5"])]:
+        flag = ["--12"] if fmt == "--12" else FLAG[fmt]
+        tabbed = fmt in ("tab5", "tab6", "--12")
+        assert ref_records(flag + [path]) == lengths(names, seqs, quals, False), fmt
+        if tabbed:
+            p = ref_run(flag + [path] + trim)
+            assert p.returncode != 0 and f"Error: Read {names[0]} has more read characters than quality values." in p.stderr.split("\n"), (fmt, p.stderr[-300:])
+            assert ref_records(flag + [tfiles["tab5" if fmt == "--12" else fmt]] + trim) == lengths(tn, ts, tq, True), (fmt, "trim")
+        else:
+            assert ref_records(flag + [path] + trim) == lengths(names, seqs, quals, True), (fmt, "trim")
+    strip = lambda nm: nm[:-2] if nm.endswith(("/1", "/2")) else nm      # noqa: E731
+    for fmt in ("tab5", "tab6"):
+        lines, mrecs = mixed_short_lines(rng, fmt)
+        path = tmp_path / f"mixed_short.{fmt}"
+        path.write_text("\n".join(lines) + "\n")
+        flat = sum(([(r[0], len(r[1]))] + ([(r[3][0], len(r[3][1]))] if r[3] is not None else []) for r in mrecs), [])
+        assert [(strip(nm), k) for nm, k in ref_records([f"--{fmt}", path])] == flat, fmt
 
 
 def test_tabbed_file_mixes_pairs_and_unpaired_reads(tmp_path):

@@ -13,10 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _backend(base, m1, m2, q1, q2):
-    c1, o1 = synth.flatten_reads(m1)
-    c2, o2 = synth.flatten_reads(m2)
+    c1, o1 = F.flatten(m1)               # (n, L) arrays or lists of mates of any lengths
+    c2, o2 = F.flatten(m2)
     ix = api.Index(base, device=0)
-    st = api.Stream(ix, max_reads=len(m1), max_bases=c1.size)
+    st = api.Stream(ix, max_reads=len(m1), max_bases=max(c1.size, c2.size))      # the second mates may be the longer set
     st.set_reads(c1, o1)
     st.set_read_names(q1)
     st.set_mates(c2, o2, q2)

@@ -190,8 +190,10 @@ def test_command_line_ragged_and_odd_reads():
     want = SL.body_lines(os.path.join(tmp, "ref3.sam"))
     assert len(want) >= 3000
     assert diff_lines(SL.body_lines(os.path.join(tmp, "amd3.sam")), want) == 0
-    ref_err = [l for l in open(os.path.join(tmp, "ref3.err")) if not l.startswith("Warning")]
-    assert open(os.path.join(tmp, "amd3.err")).read() == "".join(ref_err)
+    # stderr whole: the two length-filter warnings of every read of 1 base (in record order, across --batch 700 and -p 3), then the summary
+    ref_err = open(os.path.join(tmp, "ref3.err")).read()
+    assert ref_err.count("Warning: skipping read ") >= 2 * 100 and ref_err.count("Warning") == ref_err.count("Warning: skipping read ")
+    assert open(os.path.join(tmp, "amd3.err")).read() == ref_err
 
 
 @needs_ref

@@ -118,14 +118,16 @@ def test_records_beyond_32_edits_equal_the_reference(case):
 NWHOLE_MIN = 100      # the reference aligns all 200 reads of the case below end to end across the run (measured from its SAM): half of that
 
 
-def _align_long(base, reads, opts):
+def _align_long(base, reads, opts, bowtie2_dp=0, names=None):
     """the large-workspace configuration on the host over a list of reads -> SAM body lines, number of records beyond 32 edits, reads still flagged"""
     n = len(reads)
     e = Emu(base, "long")
-    set_options(e, 0, opts)
+    set_options(e, bowtie2_dp, opts)
+    e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
+    e.L.h2gemu_set_bowtie2_dp(e.h, bowtie2_dp)
     codes, offs = SL.flat(reads)
     e.set_reads(codes, offs, None)
-    names = [str(i) for i in range(n)]
+    names = names or [str(i) for i in range(n)]
     nb, noffs = SL.flat_names(names)
     outs = (SU.ReadOut * n)()
     rows = (api.AlnRes * (n * api.ALN_CAP))()

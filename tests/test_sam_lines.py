@@ -68,6 +68,25 @@ def test_unpaired_lines_identical(case):
     assert SL.LAST_SUMMARY == open(os.path.join(tmp, "ref.err")).read()      # the alignment summary on stderr
 
 
+def paired_lines(base, m1, m2, n1, n2, opts=(), graph=False, quals=None):
+    """the host instantiation's paired go() (fuzz_pairs.emu_pairs, options = fuzz_pairs.OPTS) through the C++ sink -> SAM body lines.  m1 / m2: lists of
+    read arrays of any lengths (mates of different lengths, empty mates); quals = (flat phred+33 bytes of the first mates, of the second mates)"""
+    import fuzz_pairs as F
+    outs, r1, r2 = F.emu_pairs(base, m1, m2, n1, n2, quals=quals)
+    n = len(m1)
+    res = (api.PairResult * n)()
+    a1 = (api.AlnRes * (n * api.PAIR_RES_CAP))()
+    a2 = (api.AlnRes * (n * api.PAIR_RES_CAP))()
+    assert C.sizeof(api.PairResult) == C.sizeof(outs[0])
+    C.memmove(res, outs, C.sizeof(res))
+    for i in range(n):
+        for m, (src, dst) in enumerate(((r1, a1), (r2, a2))):
+            for k in range(min(outs[i].nres[m], api.PAIR_RES_CAP)):
+                C.memmove(C.byref(dst[i * api.PAIR_RES_CAP + k]), C.byref(src[i * SU.AL_MAX_RESULTS + k]), C.sizeof(api.AlnRes))
+    khits = int(opts[opts.index("-k") + 1]) if "-k" in opts else (10 if graph else 5)
+    return SL.format_paired(SL.load_sam_lib(), base, m1, m2, n1, n2, res, a1, a2, khits, options=opts, quals=quals)
+
+
 @needs_ref
 @pytest.mark.parametrize("snps,case", [
     (0, dict(seed=311, npairs=2500, rdlen=101, sub=0.02)),
@@ -88,19 +107,7 @@ def test_paired_lines_identical(monkeypatch, snps, case):
     assert bad == 0
     n1, m1 = read_fa(os.path.join(tmp, "r1.fa"))
     n2, m2 = read_fa(os.path.join(tmp, "r2.fa"))
-    outs, r1, r2 = F.emu_pairs(os.path.join(tmp, "g"), np.stack(m1), np.stack(m2), n1, n2)
-    n = len(m1)
-    res = (api.PairResult * n)()
-    a1 = (api.AlnRes * (n * api.PAIR_RES_CAP))()
-    a2 = (api.AlnRes * (n * api.PAIR_RES_CAP))()
-    assert C.sizeof(api.PairResult) == C.sizeof(outs[0])
-    C.memmove(res, outs, C.sizeof(res))
-    for i in range(n):
-        for m, (src, dst) in enumerate(((r1, a1), (r2, a2))):
-            for k in range(min(outs[i].nres[m], api.PAIR_RES_CAP)):
-                C.memmove(C.byref(dst[i * api.PAIR_RES_CAP + k]), C.byref(src[i * SU.AL_MAX_RESULTS + k]), C.sizeof(api.AlnRes))
-    khits = int(opts[opts.index("-k") + 1]) if "-k" in opts else (10 if snps else 5)
-    got = SL.format_paired(SL.load_sam_lib(), os.path.join(tmp, "g"), m1, m2, n1, n2, res, a1, a2, khits, options=opts)
+    got = paired_lines(os.path.join(tmp, "g"), m1, m2, n1, n2, opts, graph=bool(snps))
     want = SL.body_lines(os.path.join(tmp, "ref.sam"))
     assert diff_lines(got, want) == 0
     assert SL.LAST_SUMMARY == open(os.path.join(tmp, "ref.err")).read()
