@@ -263,6 +263,25 @@ SEED_RESULT_DTYPE = np.dtype([("hit", FM_HIT_DTYPE), ("ncoords", np.uint32), ("s
                               ("nsteps", np.uint32), ("pad", np.uint32), ("ext", SEED_EXT_DTYPE, (SEED_CAP,))])
 assert SEED_RESULT_DTYPE.itemsize == C.sizeof(SeedResult)
 
+class WindowSeg(C.Structure):        # h2g_window_seg
+    _fields_ = [("text_start", C.c_uint64), ("name_off0", C.c_uint64), ("rdid0", C.c_uint64), ("n_windows", C.c_uint32), ("prefix_start", C.c_uint32),
+                ("prefix_len", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class WindowPlanInfo(C.Structure):   # h2g_window_plan_info
+    _fields_ = [("n_reads", C.c_uint64), ("n_text", C.c_uint64), ("n_segs", C.c_uint64), ("n_prefix_bytes", C.c_uint64), ("next_rdid", C.c_uint64),
+                ("len", C.c_uint32), ("step", C.c_uint32)]
+
+
+class WindowsStats(C.Structure):     # h2g_windows_stats
+    _fields_ = [("bytes_uploaded", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float), ("pad", C.c_float)]
+
+
+WINDOW_SEG_DTYPE = np.dtype([("text_start", np.uint64), ("name_off0", np.uint64), ("rdid0", np.uint64), ("n_windows", np.uint32), ("prefix_start", np.uint32),
+                             ("prefix_len", np.uint32), ("pad", np.uint32)])
+assert WINDOW_SEG_DTYPE.itemsize == C.sizeof(WindowSeg)
+
+
 EXPORTS = [
     "h2g_load_opts_init", "h2g_index_load", "h2g_index_get_info", "h2g_index_synth_sides", "h2g_index_free", "h2g_index_set_splice_sites", "h2g_index_add_splice_sites",
     "h2g_last_error", "h2g_stream_create", "h2g_stream_free", "h2g_stream_hip", "h2g_stream_sync", "h2g_stream_select_batch", "h2g_set_reads",
@@ -273,6 +292,8 @@ EXPORTS = [
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
     "h2g_index_dense_sa_check",
+    "h2g_window_plan_create", "h2g_window_plan_add_file", "h2g_window_plan_get_info", "h2g_window_plan_text", "h2g_window_plan_prefixes", "h2g_window_plan_segments",
+    "h2g_window_plan_select", "h2g_window_plan_free", "h2g_set_reads_windows", "h2g_get_windows_stats", "h2g_fetch_reads",
 ]
 
 
@@ -343,6 +364,22 @@ def lib():
     L.h2g_set_read_seeds.argtypes = [vp, vp, vp, C.c_size_t]
     L.h2g_set_read_filter.argtypes = [vp, vp, vp]
     L.h2g_set_read_ids.argtypes = [vp, vp]
+    L.h2g_window_plan_create.argtypes = [u32, u32, u64, P(vp)]
+    L.h2g_window_plan_add_file.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.h2g_window_plan_get_info.argtypes = [vp, P(WindowPlanInfo)]
+    L.h2g_window_plan_text.argtypes = [vp]
+    L.h2g_window_plan_text.restype = vp
+    L.h2g_window_plan_prefixes.argtypes = [vp]
+    L.h2g_window_plan_prefixes.restype = vp
+    L.h2g_window_plan_segments.argtypes = [vp, u64, u64, vp, C.c_size_t]
+    L.h2g_window_plan_segments.restype = C.c_size_t
+    L.h2g_window_plan_select.argtypes = [vp, u64, u64, P(u64), P(u64)]
+    L.h2g_window_plan_select.restype = None
+    L.h2g_window_plan_free.argtypes = [vp]
+    L.h2g_window_plan_free.restype = None
+    L.h2g_set_reads_windows.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, u32, u32, vp, C.c_size_t]
+    L.h2g_get_windows_stats.argtypes = [vp, P(WindowsStats)]
+    L.h2g_fetch_reads.argtypes = [vp, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(C.c_int), vp, vp, vp, vp, vp]
     L.h2g_align_pairs_run.argtypes = [vp, P(AlignParams)]
     L.h2g_align_pairs_fetch.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
@@ -364,6 +401,72 @@ def mstreams_policy(units, last_bails, linear, pinned=0, light=2):
     f.argtypes = [C.c_ulonglong, C.c_uint, C.c_int, C.c_uint, C.c_uint]
     f.restype = C.c_uint
     return int(f(int(units), int(last_bails), int(bool(linear)), int(pinned), int(light)))
+
+
+class WindowPlan:
+    """-F <len>,<step>: the planner of include/h2g.h (h2g_window_plan_*; host only).  add_file() takes the bytes of one FASTA file; the id counter
+    carries over from file to file.  text / prefixes are copies; segments(first, n) is a WINDOW_SEG_DTYPE array."""
+    def __init__(self, length, step, first_rdid=0):
+        self.h = C.c_void_p()
+        _chk(lib().h2g_window_plan_create(length, step, first_rdid, C.byref(self.h)), "h2g_window_plan_create")
+        self.len, self.step = length, step
+
+    def add_file(self, data: bytes):
+        _chk(lib().h2g_window_plan_add_file(self.h, data, len(data)), "h2g_window_plan_add_file")
+
+    def info(self):
+        i = WindowPlanInfo()
+        _chk(lib().h2g_window_plan_get_info(self.h, C.byref(i)), "h2g_window_plan_get_info")
+        return i
+
+    @property
+    def n_reads(self):
+        return int(self.info().n_reads)
+
+    def text(self):
+        n = int(self.info().n_text)
+        return np.frombuffer(C.string_at(lib().h2g_window_plan_text(self.h), n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+
+    def prefixes(self):
+        n = int(self.info().n_prefix_bytes)
+        return C.string_at(lib().h2g_window_plan_prefixes(self.h), n) if n else b""
+
+    def segments(self, first=0, n=None):
+        n = self.n_reads - first if n is None else n
+        cnt = lib().h2g_window_plan_segments(self.h, first, n, None, 0)
+        out = np.zeros(cnt, dtype=WINDOW_SEG_DTYPE)
+        if cnt:
+            lib().h2g_window_plan_segments(self.h, first, n, out.ctypes.data, cnt)
+        return out
+
+    def select(self, rdid_lo, rdid_hi):
+        """-> (first_read, n): the reads with rdid_lo <= rdid < rdid_hi (-s / -u)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().h2g_window_plan_select(self.h, rdid_lo, rdid_hi, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def close(self):
+        if self.h:
+            lib().h2g_window_plan_free(self.h)
+            self.h = C.c_void_p()
+
+
+def expand_windows(text, segs, length, step, prefixes):
+    """The arrays h2g_set_reads_windows leaves on the device, computed on the host with numpy: (codes, offs, name bytes, name offs, ids)."""
+    text = np.asarray(text, dtype=np.uint8)
+    starts, names, ids = [], [], []
+    for s in segs:
+        j = np.arange(int(s["n_windows"]), dtype=np.uint64)
+        starts.append(np.uint64(s["text_start"]) + j * np.uint64(step))
+        pre = prefixes[int(s["prefix_start"]):int(s["prefix_start"]) + int(s["prefix_len"])]
+        names += [pre + str(int(s["name_off0"]) + int(k) * step).encode() for k in j]
+        ids.append(((np.uint64(s["rdid0"]) + j * np.uint64(step)) & np.uint64(0xffffffff)).astype(np.uint32))
+    starts = np.concatenate(starts) if starts else np.zeros(0, np.uint64)
+    n = len(starts)
+    codes = text[(starts[:, None] + np.arange(length, dtype=np.uint64)[None, :]).astype(np.int64)].reshape(-1)
+    offs = (np.arange(n + 1, dtype=np.uint64) * np.uint64(length)).astype(np.uint32)
+    noffs = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.uint32)
+    return codes, offs, b"".join(names), noffs, (np.concatenate(ids) if ids else np.zeros(0, np.uint32))
 
 
 class Index:
@@ -451,6 +554,32 @@ class Stream:
             q = np.ascontiguousarray(quals, dtype=np.uint8).ctypes.data
         _chk(lib().h2g_set_reads(self.h, codes.ctypes.data, offs.ctypes.data, q, n), "h2g_set_reads")
         self.n_reads = n
+
+    def set_reads_windows(self, text, segs, length, step, prefixes=b""):
+        """-F windows expanded on the device (h2g_set_reads_windows): for the selected batch what set_reads + set_read_names + set_read_ids do with the
+        expanded arrays.  text: codes 0..4; segs: WINDOW_SEG_DTYPE (WindowPlan.segments)"""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        segs = np.ascontiguousarray(segs, dtype=WINDOW_SEG_DTYPE)
+        pre = np.frombuffer(bytes(prefixes), dtype=np.uint8)
+        _chk(lib().h2g_set_reads_windows(self.h, text.ctypes.data, len(text), segs.ctypes.data, len(segs), length, step, pre.ctypes.data if len(pre) else None, len(pre)),
+             "h2g_set_reads_windows")
+        self.n_reads = int(segs["n_windows"].sum())
+
+    def windows_stats(self):
+        st = WindowsStats()
+        _chk(lib().h2g_get_windows_stats(self.h, C.byref(st)), "h2g_get_windows_stats")
+        return st
+
+    def fetch_reads(self):
+        """the selected batch as the device holds it (h2g_fetch_reads): dict(codes, offs, names (bytes), name_offs, ids (None without explicit ids))"""
+        n, nb, nn, hi = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int()
+        _chk(lib().h2g_fetch_reads(self.h, C.byref(n), C.byref(nb), C.byref(nn), C.byref(hi), None, None, None, None, None), "h2g_fetch_reads")
+        codes = np.zeros(nb.value, np.uint8); offs = np.zeros(n.value + 1, np.uint32)
+        names = np.zeros(nn.value, np.uint8); noffs = np.zeros(n.value + 1, np.uint32)
+        ids = np.zeros(n.value, np.uint32) if hi.value else None
+        _chk(lib().h2g_fetch_reads(self.h, C.byref(n), C.byref(nb), C.byref(nn), C.byref(hi), codes.ctypes.data, offs.ctypes.data, names.ctypes.data if nn.value else None,
+                                   noffs.ctypes.data if nn.value else None, None if ids is None else ids.ctypes.data), "h2g_fetch_reads")
+        return {"codes": codes, "offs": offs, "names": names.tobytes(), "name_offs": noffs, "ids": ids}
 
     def rank(self, rows, cs, variant=0, repeats=1):
         rows = np.ascontiguousarray(rows, dtype=np.uint32)

@@ -6,6 +6,7 @@
 // main() is the table of contents.  What it runs, each a type or function of its own that owns its state, its synchronisation and its thread:
 //   Options / parse_options   the command line; Options::check() holds the refusals that need no device
 //   TempInputs                -c / -r: the reads as temporary FASTA files, unlinked on every way out
+//   WindowPlan                -F: the window plan over the -U files (the library's planner)
 //   parse_only                the test hook --parse-only
 //   plan_waves                temporary splice sites: the visibility window and the waves of reads it makes
 //   Replicas                  one index per device, shared where streams share a device
@@ -29,6 +30,7 @@
 #include <deque>
 #include <chrono>
 #include <algorithm>
+#include <memory>
 #include <time.h>
 #include <unistd.h>
 #include "../../include/h2g.h"
@@ -89,6 +91,8 @@ struct Options {
 	QualCoding qcoding;
 	std::string rs_arg[RS_KINDS];
 	bool rs_gz[RS_KINDS] = {false, false, false, false, false};
+	bool windows = false;                                 // -F <len>,<step>: every <len>-base window, <step> apart, of the -U FASTA records is a read
+	uint32_t win_len = 0, win_step = 0;
 	bool fasta = false, nohead = false, parse_only = false, no_unal = false;
 	std::string known_ss, novel_ss, novel_out;
 	bool tlen_adjust = true;
@@ -145,8 +149,21 @@ Options parse_options(int argc, char** argv) {
 		else if(a == "-S") o.outfn = need("-S");
 		else if(a == "-r") o.raw_input = true;                                   // one sequence per line (RawPatternSource pat.h)
 		else if(a == "-c") o.cmdline_input = true;                               // -U / -1 / -2 are comma-separated sequences (VectorPatternSource)
-		else if(a == "-f") o.fasta = true;
-		else if(a == "-q") o.fasta = false;
+		else if(a == "-f") { o.fasta = true; o.windows = false; }                // the last of -f / -q / -F decides (hisat2.cpp:1120-1132)
+		else if(a == "-q") { o.fasta = false; o.windows = false; }
+		else if(a == "-F") {
+			// <len>,<step> as the reference's binary reads it, and the manual's k:<len>,i:<step> (which the binary reads as 0,0: DESIGN.md §8)
+			const char* v = need("-F");
+			unsigned long L = 0, S = 0;
+			char* e = nullptr;
+			const char* q = strncmp(v, "k:", 2) == 0 ? v + 2 : v;
+			bool ok = *q >= '0' && *q <= '9';
+			if(ok) { L = strtoul(q, &e, 10); ok = *e == ','; }
+			if(ok) { q = e + 1; if(strncmp(q, "i:", 2) == 0) q += 2; ok = *q >= '0' && *q <= '9'; }
+			if(ok) { S = strtoul(q, &e, 10); ok = *e == 0 && S <= 0xffffffffull; }
+			if(!ok) { fprintf(stderr, "hisat2-align-amd: -F takes <len>,<step> (or k:<len>,i:<step>), not '%s'\n", v); exit(1); }
+			o.windows = true; o.win_len = (uint32_t)std::min<unsigned long>(L, 0xffffffffu); o.win_step = (uint32_t)S;
+		}
 		else if(a == "-p" || a == "--threads") o.threads = atoi(need("-p"));        // host threads for parsing and SAM formatting
 		else if(a == "--ss-window") o.ss_window_opt = (uint32_t)strtoul(need("--ss-window"), nullptr, 10);   // reads a temporary splice site stays invisible for: 1000 x <-p> of the reference (hisat2.cpp:3687), decoupled from this program's host threads
 		else if(a == "--rna-strandness") {
@@ -205,6 +222,25 @@ int Options::check() {
 		if(h2g_align_params_apply_options(&P, &presets, opts.data(), opts.size(), err, sizeof err) != H2G_OK) { fprintf(stderr, "%s\n", err); return 1; }
 	}
 	for(int k = 0; k < RS_KINDS; k++) sorting = sorting || !rs_arg[k].empty();
+	if(windows) {
+		// -F cuts its reads out of the -U files and nothing else: what would need another reader or a second mate is refused by name
+		const char* with = !m1.empty() || !m2.empty() ? "-1/-2" : !m12.empty() ? "--tab5/--tab6/--12" : qseq ? "--qseq" : cmdline_input ? "-c" : raw_input ? "-r" : nullptr;
+		if(with) { fprintf(stderr, "hisat2-align-amd: -F is not built together with %s: it takes -U FASTA files only (see DESIGN.md, scope)\n", with); return 1; }
+		if(sorting) { fprintf(stderr, "hisat2-align-amd: -F is not built together with --un / --al and their kin (see DESIGN.md, scope)\n"); return 1; }
+		if(win_len == 0) { fprintf(stderr, "hisat2-align-amd: -F %u,%u: a window length of 0 yields no reads\n", win_len, win_step); return 1; }
+		if(win_len > 1024) { fprintf(stderr, "hisat2-align-amd: -F %u,%u: windows longer than 1024 bases are beyond the reference's ring (pat.h:1346)\n", win_len, win_step); return 1; }
+		if(u.empty()) { fprintf(stderr, "hisat2-align-amd: -F needs -U <fasta>[,<fasta>...]\n"); return 1; }
+		// temporary splice sites with a window (-p >= 2 / --ss-window): the window is measured in read ids, and with a step other than 1 the ids have gaps — the
+		// reference's own --reorder output stalls there, so there is nothing to equal
+		const bool temp_ss = !P.no_spliced_alignment && !P.no_temp_splicesite;
+		if(temp_ss && win_step != 1 && (ss_window_opt || threads >= 2)) {
+			fprintf(stderr, "hisat2-align-amd: -F %u,%u with -p %d is not built for the temporary-splice-site mode (read ids with gaps: the reference's --reorder output stalls): "
+			                "use -p 1, a step of 1, --no-temp-splicesite or --no-spliced-alignment\n", win_len, win_step, threads);
+			return 1;
+		}
+		trim5 = trim3 = 0;                                    // (not applied by this source, as in the reference)
+		fasta = true;
+	}
 	if(sorting && !from_front_end) {
 		// as in the reference, where these are options of the `hisat2` script and hisat2-align-s refuses them
 		for(int k = 0; k < RS_KINDS; k++) if(!rs_arg[k].empty()) {
@@ -276,16 +312,43 @@ void warn_length_filtered(const Batch& a, const Batch* b, size_t i) {
 	}
 }
 
+// -F: the plan over the -U files (h2g_window_plan_*, the library's planner) and the reads -s / -u leave of it
+struct WindowPlan {
+	h2g_window_plan* plan = nullptr;
+	uint64_t first = 0, n = 0;
+	h2g_window_plan_info info{};
+	WindowPlan() = default;
+	WindowPlan(const WindowPlan&) = delete;
+	~WindowPlan() { h2g_window_plan_free(plan); }
+	// 0, or the exit status
+	int load(const Options& o) {
+		// H2G_WINDOW_FIRST_ID=<n> (test hook): the id counter's start, as if records with n windows at step 1 had gone before
+		const uint64_t id0 = getenv("H2G_WINDOW_FIRST_ID") ? strtoull(getenv("H2G_WINDOW_FIRST_ID"), nullptr, 10) : 0;
+		if(h2g_window_plan_create(o.win_len, o.win_step, id0, &plan) != H2G_OK) { fprintf(stderr, "hisat2-align-amd: -F %u,%u: cannot plan\n", o.win_len, o.win_step); return 1; }
+		std::vector<char> bytes;
+		for(const std::string& fn : o.u) {
+			if(!read_whole_file(fn, bytes)) { fprintf(stderr, "Error: could not open %s\n", fn.c_str()); return 1; }
+			if(h2g_window_plan_add_file(plan, bytes.data(), bytes.size()) != H2G_OK) { fprintf(stderr, "hisat2-align-amd: -F: %s holds a record of more than 2^32 windows, or the record names exceed 4 GB\n", fn.c_str()); return 1; }
+		}
+		h2g_window_plan_get_info(plan, &info);
+		const uint64_t hi = o.upto > ~0ull - o.skip ? ~0ull : o.upto + o.skip;      // -u counts from the skipped ids on (hisat2.cpp:1959-1963)
+		h2g_window_plan_select(plan, o.skip, hi, &first, &n);
+		return 0;
+	}
+};
+
 // --parse-only (test hook): records, bases and a checksum over every window of <--batch> records (codes, names, qualities and lengths of the unpaired reads and first
 // mates, then those of the second mates), then the number of pairs and of unpaired reads; one line per --un / --al option with the file name(s) it would write.
 // On stderr: the length-filter warnings of the records, as a run writes them.
-int parse_only(const Options& o) {
-	Source src(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, false, o.skip, o.upto);
+// Under -F: after that line, the first and the last read id of every window of <--batch> reads.
+int parse_only(const Options& o, Source& src) {
 	Win w;
+	std::string id_lines;
 	uint64_t n = 0, bases = 0, npairs = 0, h = 1469598103934665603ull;
 	auto mix = [&](const void* p, size_t len) { const uint8_t* c = (const uint8_t*)p; for(size_t i = 0; i < len; i++) { h ^= c[i]; h *= 1099511628211ull; } };
 	while(src.next(w, o.batch)) {
 		n += w.n; npairs += w.npairs;
+		if(!w.ids64.empty()) id_lines += std::to_string(w.ids64.front()) + " " + std::to_string(w.ids64.back()) + "\n";
 		if(!o.quiet) for(size_t i = 0; i < w.n; i++) warn_length_filtered(w.a, (w.kinds.empty() ? w.paired : w.kinds[i] != 0) ? &w.b : nullptr, i);
 		for(int m = 0; m < (w.npairs ? 2 : 1); m++) {
 			const Batch& b = m ? w.b : w.a;
@@ -299,6 +362,7 @@ int parse_only(const Options& o) {
 	}
 	if(src.short_mates()) { fprintf(stderr, "Error, fewer reads in file specified with -2 than in file specified with -1\n"); return 1; }
 	printf("%llu %llu %016llx %llu %llu\n", (unsigned long long)n, (unsigned long long)bases, (unsigned long long)h, (unsigned long long)npairs, (unsigned long long)(n - npairs));
+	fputs(id_lines.c_str(), stdout);
 	for(int k = 0; k < RS_KINDS; k++) if(!o.rs_arg[k].empty()) {
 		std::string f1, f2;
 		read_sink_names(k, o.rs_arg[k], &f1, &f2);
@@ -549,7 +613,7 @@ private:
 // What one device run takes: a run of records of one kind.  A window that mixes pairs and unpaired reads (a tabbed file) becomes two items, its pairs (merge 1) and then
 // its unpaired reads (merge 2), whose text is put back into record order (`order`: 1 = pair) before it is written: N records in windows of B make at most
 // 2 ceil(N / B) device runs however the kinds alternate.  With temporary splice sites the read ids must be exact: the two items carry their records' ids (h2g_set_read_ids), both see the wave's one snapshot of the database and their junctions are merged after the second.
-struct Item { size_t n = 0; bool paired = false; uint64_t first_id = 0, skipped = 0; int merge = 0; std::vector<uint8_t> order; std::vector<uint32_t> ids; std::vector<uint64_t> ids64; };   // ids: Read::rdid per read, for the two items of a mixed window
+struct Item { std::vector<h2g_window_seg> wsegs; /* -F: the segments of the item's reads; with them ids / ids64 */ size_t n = 0; bool paired = false; uint64_t first_id = 0, skipped = 0; int merge = 0; std::vector<uint8_t> order; std::vector<uint32_t> ids; std::vector<uint64_t> ids64; };   // ids: Read::rdid per read, for the two items of a mixed window
 
 // ---- the parser: item j is read into host buffer pair j mod H as soon as that pair is free (item j - H is formatted), ahead of the main thread.
 // H = streams + 2 (+ 1 with a formatter thread): item k + 1 is parsed while item k is uploaded and up to G earlier ones are on the GPUs / being formatted.
@@ -619,6 +683,7 @@ private:
 			if(!w.kinds.empty()) { if(!emit_mixed(w, sa, tp)) return; continue; }
 			busy_ += now() - tp;
 			Item it; it.n = w.n; it.paired = w.paired; it.first_id = w.first_id; it.skipped = w.skipped;
+			if(!w.wsegs.empty()) { it.wsegs.swap(w.wsegs); it.ids.assign(w.ids64.begin(), w.ids64.end()); it.ids64.swap(w.ids64); }
 			if(!emit(w.a, w.paired ? &w.b : nullptr, std::move(it), false)) return;
 		}
 	}
@@ -813,7 +878,7 @@ private:
 // device) before the next wave starts (the exchange between two waves is the junction list, tens of bytes per site).
 class DeviceStage {
 public:
-	struct Config { bool qc_filter, arbitrary_random; size_t batch; };
+	struct Config { bool qc_filter, arbitrary_random; size_t batch; const h2g_window_plan* plan; /* -F, or null */ };
 	DeviceStage(const Config& c, const h2g_align_params& P, const Waves& wv, const Replicas& ix, ParseStage& parse, FormatStage& fmt)
 		: c_(c), P_(P), wv_(wv), ix_(ix), parse_(parse), fmt_(fmt), G_(ix.streams()), S_((size_t)ix.streams()), wave_left_(wv.wave) {
 		// --non-deterministic: every read / pair takes two draws, mate 1's seed then mate 2's, from one RandomSource seeded with time(0) (hisat2.cpp:3273,
@@ -845,10 +910,18 @@ public:
 			t_stream += now() - ts;
 		}
 		const double tq0 = now();
-		if(h2g_set_reads(sg.st, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, n) != H2G_OK) die("h2g_set_reads");
-		if(h2g_set_read_names(sg.st, a.names.data(), a.noffs.data(), n) != H2G_OK) die("h2g_set_read_names");
-		// read ids are 32 bits in the splice-site window test (DSpliceSite::readid): past that the temporary sites' visibility would wrap silently
-		if(!it.ids.empty() && h2g_set_read_ids(sg.st, it.ids.data()) != H2G_OK) die("h2g_set_read_ids");
+		if(!it.wsegs.empty()) {
+			// -F: the device cuts the windows out of the text itself (codes, names and ids; the host's copies are for the SAM text)
+			h2g_window_plan_info pi;
+			h2g_window_plan_get_info(c_.plan, &pi);
+			if(h2g_set_reads_windows(sg.st, h2g_window_plan_text(c_.plan), pi.n_text, it.wsegs.data(), it.wsegs.size(), pi.len, pi.step, h2g_window_plan_prefixes(c_.plan),
+			                         pi.n_prefix_bytes) != H2G_OK) die("h2g_set_reads_windows");
+		} else {
+			if(h2g_set_reads(sg.st, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, n) != H2G_OK) die("h2g_set_reads");
+			if(h2g_set_read_names(sg.st, a.names.data(), a.noffs.data(), n) != H2G_OK) die("h2g_set_read_names");
+			// read ids are 32 bits in the splice-site window test (DSpliceSite::readid): past that the temporary sites' visibility would wrap silently
+			if(!it.ids.empty() && h2g_set_read_ids(sg.st, it.ids.data()) != H2G_OK) die("h2g_set_read_ids");
+		}
 		if(wv_.temp_ss && (it.ids.empty() ? it.first_id + n : it.ids64.back() + 1) > 0xffffffffull) die("read ids beyond 2^32 with temporary splice sites (use --no-temp-splicesite or split the input)");
 		h2g_align_params P = P_;                       // (this run's: nothing another thread may read is changed)
 		P.first_read_id = (uint32_t)it.first_id;
@@ -978,10 +1051,20 @@ int main(int argc, char** argv) {
 	Options o = parse_options(argc, argv);
 	if(const int rc = o.check()) return rc;
 	TempInputs tmp_inputs(o);
-	if(o.parse_only) return parse_only(o);
+	WindowPlan wp;
+	if(o.windows) if(const int rc = wp.load(o)) return rc;
+	if(o.parse_only) {
+		if(o.windows) { Source src(wp.plan, wp.first, wp.n); return parse_only(o, src); }
+		Source src(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, false, o.skip, o.upto);
+		return parse_only(o, src);
+	}
 	Waves wv;
 	size_t batch = o.batch;
 	if(const int rc = plan_waves(o, &wv, &batch)) return rc;
+	if(o.windows && wv.temp_ss && wp.info.next_rdid > 0x100000000ull) {
+		fprintf(stderr, "hisat2-align-amd: -F %u,%u: the read ids pass 2^32 - 1, beyond what the temporary-splice-site mode compares (use --no-temp-splicesite or split the input)\n", o.win_len, o.win_step);
+		return 1;
+	}
 	const double t0 = now();
 	Replicas ix;
 	if(const int rc = ix.load(o, wv.temp_ss)) return rc;
@@ -1000,7 +1083,9 @@ int main(int argc, char** argv) {
 	const bool drop_unal = o.sorting && o.no_unal;
 	h2g_sam_set_no_unal(sam, o.no_unal && !drop_unal ? 1 : 0);
 	// (-s / -u: the record stream skips and counts, Source::next; -u counts the reads after the skipped ones, qUpto += skipReads hisat2.cpp:1959-1963)
-	Source src(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, o.sorting, o.skip, o.upto);
+	std::unique_ptr<Source> src_owner(o.windows ? new Source(wp.plan, wp.first, wp.n)
+	                                            : new Source(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, o.sorting, o.skip, o.upto));
+	Source& src = *src_owner;
 	ReadSorter sorter;
 	for(int k = 0; k < RS_KINDS; k++) if(!o.rs_arg[k].empty()) sorter.open(k, o.rs_arg[k], o.rs_gz[k]);
 	const bool merge_sites = wv.temp_ss || !o.novel_out.empty();
@@ -1010,7 +1095,7 @@ int main(int argc, char** argv) {
 	TextWriter writer(out);
 	ParseStage parse(src, H, batch, wv, ix.streams());
 	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits}, sam, parse, writer, sorter, sites, ix);
-	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch}, P, wv, ix, parse, fmt);
+	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch, wp.plan}, P, wv, ix, parse, fmt);
 	double t_parse = 0;                                   // what the main thread waited for the parser
 	bool short_mates = false;
 	for(long k = 0;; k++) {

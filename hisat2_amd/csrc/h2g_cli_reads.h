@@ -17,6 +17,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <zlib.h>
+#include "../../include/h2g.h"
 
 namespace h2g_cli {
 
@@ -107,6 +108,19 @@ inline void append_bases(std::vector<uint8_t>& codes, const char* q, const char*
 	uint8_t* o = codes.data() + at;
 	for(; q < e; q++) { const uint8_t v = tb[(unsigned char)*q]; *o = v; o += v != 0xff; }
 	codes.resize((size_t)(o - codes.data()));
+}
+
+// the bytes of a file, inflated when its name ends in .gz (-F plans over whole files); false: it could not be opened
+inline bool read_whole_file(const std::string& fn, std::vector<char>& out) {
+	out.clear();
+	gzFile g = gzopen(fn.c_str(), "rb");      // (zlib hands a file that is not gzipped through as it is)
+	if(!g) return false;
+	gzbuffer(g, 1 << 20);
+	std::vector<char> chunk(8 << 20);
+	int got;
+	while((got = gzread(g, chunk.data(), (unsigned)chunk.size())) > 0) out.insert(out.end(), chunk.begin(), chunk.begin() + got);
+	gzclose(g);
+	return got == 0;
 }
 
 // Sequential stream of reads over a list of files of one format, parsed in parallel: a file is mapped, the record starts are found by all
@@ -410,6 +424,8 @@ private:
 // which records are pairs.
 struct Win {
 	Batch a, b;
+	std::vector<h2g_window_seg> wsegs;   // -F: the segments the window's reads are cut from (the device expands them itself), and the reads' ids
+	std::vector<uint64_t> ids64;
 	std::vector<uint8_t> kinds;       // filled only when the window mixes pairs and unpaired reads (1 = pair)
 	bool paired = false;              // (when it does not mix) every record is a pair
 	size_t n = 0, npairs = 0;
@@ -431,11 +447,15 @@ public:
 			if(!u.empty()) segs_.push_back(Seg{mk(u), nullptr, false});
 		}
 	}
+	// -F <len>,<step>: the reads are the windows [first, first + n) of a plan (include/h2g.h; the -s / -u selection is the caller's, h2g_window_plan_select)
+	Source(const h2g_window_plan* plan, uint64_t first, uint64_t n) : plan_(plan), wcur_(first), wleft_(n), skip_(0), upto_(0) {}
 	~Source() { for(Seg& s : segs_) { delete s.a; delete s.b; } }
 	Source(const Source&) = delete;
 	bool short_mates() const { return short_mates_; }         // the -2 files ran out before the -1 files
 	bool next(Win& w, size_t max) {
 		w.a.clear(); w.b.clear(); w.kinds.clear(); w.n = w.npairs = 0; w.skipped = 0; w.paired = false;
+		w.wsegs.clear(); w.ids64.clear();
+		if(plan_) return next_windows(w, max);
 		while(si_ < segs_.size()) {
 			Seg& s = segs_[si_];
 			Batch ja, jb;
@@ -468,6 +488,35 @@ public:
 		return false;
 	}
 private:
+	// the next up to `max` windows, expanded on the host for the SAM text: codes, names (the record's prefix and the decimal offset) and ids
+	bool next_windows(Win& w, size_t max) {
+		if(wleft_ == 0 || max == 0) return false;
+		const uint64_t g = std::min<uint64_t>(max, wleft_);
+		h2g_window_plan_info pi;
+		h2g_window_plan_get_info(plan_, &pi);
+		w.wsegs.resize(h2g_window_plan_segments(plan_, wcur_, g, nullptr, 0));
+		h2g_window_plan_segments(plan_, wcur_, g, w.wsegs.data(), w.wsegs.size());
+		const uint8_t* text = h2g_window_plan_text(plan_);
+		const char* pre = h2g_window_plan_prefixes(plan_);
+		w.a.codes.reserve((size_t)g * pi.len);
+		char num[24];
+		for(const h2g_window_seg& s : w.wsegs) for(uint64_t j = 0; j < s.n_windows; j++) {
+			const uint8_t* t = text + s.text_start + j * pi.step;
+			w.a.codes.insert(w.a.codes.end(), t, t + pi.len);
+			w.a.offs.push_back((uint32_t)w.a.codes.size());
+			w.a.names.append(pre + s.prefix_start, s.prefix_len);
+			w.a.names.append(num, (size_t)snprintf(num, sizeof num, "%llu", (unsigned long long)(s.name_off0 + j * pi.step)));
+			w.a.noffs.push_back((uint32_t)w.a.names.size());
+			w.ids64.push_back(s.rdid0 + j * pi.step);
+		}
+		w.n = (size_t)g; w.first_id = w.ids64.front();
+		if(!wstarted_) { w.skipped = wcur_; wstarted_ = true; }
+		wcur_ += g; wleft_ -= g;
+		return true;
+	}
+	const h2g_window_plan* plan_ = nullptr;
+	uint64_t wcur_ = 0, wleft_ = 0;
+	bool wstarted_ = false;
 	struct Seg { Reader* a; Reader* b; bool tabbed; uint64_t id = 0, budget = 0; bool started = false; };
 	size_t fill(Seg& s, Batch& a, Batch& b, std::vector<uint8_t>& kinds, size_t w) {
 		if(s.tabbed) return s.a->fill(a, w, &b, &kinds);

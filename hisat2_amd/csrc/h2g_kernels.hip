@@ -24,6 +24,7 @@
 #include "h2g_local_pack.h"
 #include "h2g_splice_host.h"
 #include "h2g_splice_db_host.h"
+#include "h2g_windows.h"   // the -F window expansion's per-read arithmetic
 #include "h2g_go_args.h"   // GoArgs + the extern "C" face of the go() units (their AlignWS layouts are opaque on this side)
 
 using namespace h2g;
@@ -205,9 +206,10 @@ struct h2g_stream {
 	unsigned long long* d_counters = nullptr;   // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
 	void* d_tmp[4] = {nullptr, nullptr, nullptr, nullptr};
 	size_t tmp_sz[4] = {0, 0, 0, 0};
-	hipEvent_t ev[12];
+	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows)
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
+	h2g_windows_stats win_stats = {};           // of the last h2g_set_reads_windows
 	unsigned long long* d_warm_cnt = nullptr;   // counter block of the machine streams' empty first launches (go_warmup); word H2G_CNT_NO_SECOND, which nobody writes, is their list's count
 	uint8_t* d_warm_rows = nullptr;             // ... and the result rows they are given: never the current batch's
 };
@@ -723,7 +725,7 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 	for(int k = 0; k < H2G_NBUF; k++) { HIPCHK(hipEventCreateWithFlags(&s->ev_fast[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_mach[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_bails[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_drain[k], hipEventDisableTiming)); }
 	for(int k = 0; k < H2G_FAST_POOLS; k++) HIPCHK(hipEventCreateWithFlags(&s->ev_pool[k], hipEventDisableTiming));
 	for(int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&s->ev_dr[k]));
-	for(int i = 0; i < 12; i++) HIPCHK(hipEventCreate(&s->ev[i]));
+	for(int i = 0; i < 14; i++) HIPCHK(hipEventCreate(&s->ev[i]));
 	HIPCHK(hipMalloc((void**)&s->d_counters, H2G_NBUF * H2G_CNT_BLOCK * sizeof(unsigned long long)));
 	HIPCHK(hipMemset(s->d_counters, 0, H2G_NBUF * H2G_CNT_BLOCK * sizeof(unsigned long long)));
 	s->cnt_cur = s->d_counters;
@@ -771,7 +773,7 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 		(void)hipFree(B.d_ids);
 	}
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
-	for(int i = 0; i < 12; i++) (void)hipEventDestroy(s->ev[i]);
+	for(int i = 0; i < 14; i++) (void)hipEventDestroy(s->ev[i]);
 	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { (void)hipStreamDestroy(s->mst[k]); (void)hipEventDestroy(s->ev_rot[k]); } (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
 	delete s;
 }
@@ -2082,6 +2084,137 @@ extern "C" h2g_status h2g_set_read_ids(h2g_stream* s, const uint32_t* ids) {
 	HIPCHK(hipMemcpyAsync(B.d_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
 	B.has_ids = true;
+	return H2G_OK;
+}
+
+// ------------------------------------------------------------------------------------------ -F windows: the read set expanded on the device
+// The code array of a window batch is one run of n * len bytes.  A lane owns 16 consecutive OUTPUT bytes and stores them as one dwordx4: a wave writes 1 KB
+// contiguous whatever len and step are.  The sources are gathered byte by byte from the text; neighbouring windows overlap (len / step fold), so the text is read
+// from L2 and the kernel's traffic is its stores.  The per-read arithmetic is h2g_windows.h's.
+__global__ __launch_bounds__(256) void k_win_codes(const uint8_t* __restrict__ text, const h2g_win::DSeg* __restrict__ segs, uint32_t n_segs, uint32_t len, uint32_t step,
+                                                   uint64_t n_bytes, uint8_t* __restrict__ codes)
+{
+	const uint64_t chunks = (n_bytes + 15) / 16;
+	for(uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t b0 = c * 16;
+		const uint32_t m = n_bytes - b0 < 16 ? (uint32_t)(n_bytes - b0) : 16u;      // (the bytes past the end of the last chunk are written as 0: the buffer has 64 spare)
+		h2g_win::CodeCursor cur;
+		cur.seek(segs, n_segs, len, step, b0);
+		uint32_t w[4] = {0, 0, 0, 0};
+		for(uint32_t k = 0; k < m; k++) w[k >> 2] |= (uint32_t)text[cur.next()] << (8 * (k & 3));
+		*(uint4*)(codes + b0) = make_uint4(w[0], w[1], w[2], w[3]);
+	}
+}
+// one lane per read: its offset, id, name offset and the bytes of its name; lane n the closing offsets
+__global__ __launch_bounds__(256) void k_win_meta(const h2g_win::DSeg* __restrict__ segs, uint32_t n_segs, uint32_t len, uint32_t step, uint32_t n, const char* __restrict__ prefixes,
+                                                  uint32_t* __restrict__ offs, uint32_t* __restrict__ ids, uint32_t* __restrict__ name_offs, char* __restrict__ names)
+{
+	for(uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += gridDim.x * blockDim.x) {
+		offs[r] = r * len;
+		if(r == n) { name_offs[r] = segs[n_segs].name_first; break; }
+		const h2g_win::DSeg s = segs[h2g_win::seg_of(segs, n_segs, r)];
+		const uint32_t j = r - s.first_read;
+		ids[r] = s.rdid0 + j * step;
+		const uint32_t at = h2g_win::name_start(s, step, j);
+		name_offs[r] = at;
+		h2g_win::write_name(s, step, j, prefixes, names + at);
+	}
+}
+
+extern "C" h2g_status h2g_set_reads_windows(h2g_stream* s, const uint8_t* text, size_t n_text, const h2g_window_seg* segs, size_t n_segs, uint32_t len, uint32_t step,
+                                            const char* prefixes, size_t n_prefix_bytes)
+{
+	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
+	if(!s || !text || !segs || n_segs == 0 || n_segs >= 0xffffffffull || len == 0 || (!prefixes && n_prefix_bytes)) return H2G_ERR_ARG;
+	BatchCtx& B = s->cur();
+	// the kernels' table: the per-segment first read and first name byte, the text range the segments touch
+	std::vector<h2g_win::DSeg> ds(n_segs + 1);
+	uint64_t n = 0, nb = 0, lo = UINT64_MAX, hi = 0;
+	for(size_t k = 0; k < n_segs; k++) {
+		const h2g_window_seg& x = segs[k];
+		const uint64_t last = x.text_start + (uint64_t)(x.n_windows ? x.n_windows - 1 : 0) * step;
+		if(x.n_windows == 0 || last + len > n_text || last < x.text_start || (uint64_t)x.prefix_start + x.prefix_len > n_prefix_bytes) {
+			snprintf(g_err, sizeof g_err, "h2g_set_reads_windows: segment %zu names text or prefix bytes that were not given", k); return H2G_ERR_ARG;
+		}
+		if(x.text_start < lo) lo = x.text_start;
+		if(last + len > hi) hi = last + len;
+		h2g_win::DSeg& d = ds[k];
+		d.name_off0 = x.name_off0; d.rdid0 = (uint32_t)x.rdid0; d.first_read = (uint32_t)n; d.name_first = (uint32_t)nb;
+		d.prefix_start = x.prefix_start; d.prefix_len = x.prefix_len;
+		n += x.n_windows;
+		nb += (uint64_t)x.n_windows * x.prefix_len + h2g_win::width_sum(x.name_off0, step, x.n_windows);
+		if(n > s->max_reads || n * len > s->max_bases || n * len > 0xffffffffull || nb > 0xffffffffull) {      // (read and name offsets are 32 bits)
+			snprintf(g_err, sizeof g_err, "h2g_set_reads_windows: the windows exceed the stream's %zu reads / %zu bases, or their names 4 GB", s->max_reads, s->max_bases); return H2G_ERR_ARG;
+		}
+	}
+	if(hi - lo > 0xffffffffull) { snprintf(g_err, sizeof g_err, "h2g_set_reads_windows: the segments span more than 4 G bases of text"); return H2G_ERR_ARG; }
+	for(size_t k = 0; k < n_segs; k++) ds[k].text_start = (uint32_t)(segs[k].text_start - lo);
+	memset(&ds[n_segs], 0, sizeof ds[n_segs]);
+	ds[n_segs].first_read = (uint32_t)n; ds[n_segs].name_first = (uint32_t)nb;
+	HIPCHK(hipSetDevice(s->ix->device));
+	if(B.names_cap < nb || !B.d_name_offs) {      // (grows as h2g_set_read_names does)
+		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
+		B.d_names = nullptr; B.d_name_offs = nullptr; B.names_cap = 0;
+		HIPCHK(hipMalloc((void**)&B.d_names, nb + 64));
+		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
+		B.names_cap = nb;
+	}
+	if(!B.d_ids) HIPCHK(hipMalloc((void**)&B.d_ids, s->max_reads * sizeof(uint32_t)));
+	void *d_text, *d_segs, *d_pre;
+	int rc;
+	if((rc = tmp_buf(s, 0, hi - lo, &d_text)) || (rc = tmp_buf(s, 1, ds.size() * sizeof(h2g_win::DSeg), &d_segs)) || (rc = tmp_buf(s, 2, n_prefix_bytes, &d_pre))) return (h2g_status)rc;
+	HIPCHK(hipMemcpyAsync(d_text, text + lo, hi - lo, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(d_segs, ds.data(), ds.size() * sizeof(h2g_win::DSeg), hipMemcpyHostToDevice, s->st));
+	if(n_prefix_bytes) HIPCHK(hipMemcpyAsync(d_pre, prefixes, n_prefix_bytes, hipMemcpyHostToDevice, s->st));
+	const uint64_t n_bytes = n * len;
+	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	k_win_codes<<<grid_for((n_bytes + 15) / 16, 256), 256, 0, s->st>>>((const uint8_t*)d_text, (const h2g_win::DSeg*)d_segs, (uint32_t)n_segs, len, step, n_bytes, B.d_codes);
+	k_win_meta<<<grid_for(n + 1, 256), 256, 0, s->st>>>((const h2g_win::DSeg*)d_segs, (uint32_t)n_segs, len, step, (uint32_t)n, (const char*)d_pre, B.d_offs, B.d_ids, B.d_name_offs, B.d_names);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(sync_all(s));
+	s->win_stats.bytes_uploaded = (hi - lo) + ds.size() * sizeof(h2g_win::DSeg) + n_prefix_bytes;
+	s->win_stats.bytes_written = n_bytes + (n + 1) * 8 + n * 4 + nb;
+	HIPCHK(hipEventElapsedTime(&s->win_stats.kernel_ms, s->ev[12], s->ev[13]));
+	B.n_reads = n;
+	B.max_read_len = len;
+	B.has_quals = false;
+	B.has_names = true;
+	B.has_mates = false;
+	B.has_seeds = B.has_seeds2 = false;
+	B.has_qc = false;
+	B.has_ids = true;
+	s->ledits_touched = 0;
+	return H2G_OK;
+}
+extern "C" h2g_status h2g_get_windows_stats(h2g_stream* s, h2g_windows_stats* out) {
+	if(!s || !out) return H2G_ERR_ARG;
+	*out = s->win_stats;
+	return H2G_OK;
+}
+
+extern "C" h2g_status h2g_fetch_reads(h2g_stream* s, size_t* n_reads, size_t* n_bases, size_t* n_name_bytes, int* has_ids, uint8_t* codes, uint32_t* offs, char* names,
+                                      uint32_t* name_offs, uint32_t* ids)
+{
+	if(!s) return H2G_ERR_ARG;
+	HIPCHK(sync_all(s));
+	const BatchCtx& B = s->cur();
+	const size_t n = B.n_reads;
+	uint32_t nb = 0, nn = 0;
+	HIPCHK(hipSetDevice(s->ix->device));
+	if(n) HIPCHK(hipMemcpy(&nb, B.d_offs + n, 4, hipMemcpyDeviceToHost));
+	if(n && B.has_names) HIPCHK(hipMemcpy(&nn, B.d_name_offs + n, 4, hipMemcpyDeviceToHost));
+	if(n_reads) *n_reads = n;
+	if(n_bases) *n_bases = nb;
+	if(n_name_bytes) *n_name_bytes = nn;
+	if(has_ids) *has_ids = B.has_ids ? 1 : 0;
+	if(n == 0) return H2G_OK;
+	if((ids && !B.has_ids) || ((names || name_offs) && !B.has_names)) return H2G_ERR_ARG;
+	if(codes && nb) HIPCHK(hipMemcpy(codes, B.d_codes, nb, hipMemcpyDeviceToHost));
+	if(offs) HIPCHK(hipMemcpy(offs, B.d_offs, (n + 1) * 4, hipMemcpyDeviceToHost));
+	if(names && nn) HIPCHK(hipMemcpy(names, B.d_names, nn, hipMemcpyDeviceToHost));
+	if(name_offs) HIPCHK(hipMemcpy(name_offs, B.d_name_offs, (n + 1) * 4, hipMemcpyDeviceToHost));
+	if(ids) HIPCHK(hipMemcpy(ids, B.d_ids, n * 4, hipMemcpyDeviceToHost));
 	return H2G_OK;
 }
 

@@ -414,6 +414,53 @@ H2G_EXPORT void       h2g_sam_set_read_filter(struct h2g_sam*, const uint8_t* pa
 H2G_EXPORT void       h2g_sam_set_record_ends(struct h2g_sam*, uint64_t* ends);
 /* read names (needed by genRandSeed): name i = bytes[offs[i] .. offs[i+1]) */
 H2G_EXPORT h2g_status h2g_set_read_names(h2g_stream*, const char* bytes, const uint32_t* offs, size_t n_reads);
+/* ---- -F <len>,<step>: reads sampled from long FASTA sequences (FastaContinuousPatternSource, pat.h:1214-1354) ------------------------------
+ * Every <len>-base window, <step> bases apart, of a FASTA record is a read; its name is the record's name up to the first blank, '_', and the
+ * decimal offset of the window's first base (bases only are counted); qualities are 'I'.  A window set is len / step times larger than the text
+ * it is cut from, so it travels as that text plus a list of segments and is expanded on the device (h2g_set_reads_windows).
+ * A segment is a run of windows of one record: window j of it starts at text[text_start + j * step], prints the offset name_off0 + j * step behind
+ * the prefix prefixes[prefix_start .. prefix_start + prefix_len) (the record's name and '_'; empty for text before the first '>') and has
+ * Read::rdid = rdid0 + j * step. */
+typedef struct {
+	uint64_t text_start;       /* index of window 0's first base in the text */
+	uint64_t name_off0;        /* the offset window 0 prints */
+	uint64_t rdid0;            /* Read::rdid of window 0 (the device keeps 32 bits, as h2g_set_read_ids) */
+	uint32_t n_windows;
+	uint32_t prefix_start, prefix_len;
+	uint32_t pad;
+} h2g_window_seg;
+/* The planner (csrc/h2g_windows.cpp: host only, needs no device): the bytes of FASTA files, in order -> the text (one code 0..4 per counted base:
+ * asc2dnacat != 0, IUPAC letters become N = 4, every other character is skipped without advancing the offset), the prefix pool and the
+ * segments.  The window state restarts at every '>' and at every file; the id counter (rdid of a record's window 0: it grows by L - len + 1
+ * after a record of L >= len bases; a shorter record yields no read) is carried across files, starting at first_rdid (0 for a run).  step == 0:
+ * one window per record, at offset 0.  len: 1 .. 1024 (the reference's ring). */
+typedef struct h2g_window_plan h2g_window_plan;
+typedef struct { uint64_t n_reads, n_text, n_segs, n_prefix_bytes, next_rdid; uint32_t len, step; } h2g_window_plan_info;
+H2G_EXPORT h2g_status h2g_window_plan_create(uint32_t len, uint32_t step, uint64_t first_rdid, h2g_window_plan** out);
+H2G_EXPORT h2g_status h2g_window_plan_add_file(h2g_window_plan*, const char* bytes, size_t n);
+H2G_EXPORT h2g_status h2g_window_plan_get_info(const h2g_window_plan*, h2g_window_plan_info* out);
+H2G_EXPORT const uint8_t* h2g_window_plan_text(const h2g_window_plan*);        /* [n_text], valid until the next add_file / free */
+H2G_EXPORT const char*    h2g_window_plan_prefixes(const h2g_window_plan*);    /* [n_prefix_bytes] */
+/* The segments of the reads [first_read, first_read + n) (read = window, in input order; the range may begin and end inside a record) into
+ * out[0..cap): returns how many there are (nothing is written past cap; out may be NULL to count). */
+H2G_EXPORT size_t     h2g_window_plan_segments(const h2g_window_plan*, uint64_t first_read, uint64_t n, h2g_window_seg* out, size_t cap);
+/* -s / -u act on Read::rdid (hisat2.cpp:3319, :3634): the reads with rdid_lo <= rdid < rdid_hi, up to the first read at or past rdid_hi. */
+H2G_EXPORT void       h2g_window_plan_select(const h2g_window_plan*, uint64_t rdid_lo, uint64_t rdid_hi, uint64_t* first_read, uint64_t* n);
+H2G_EXPORT void       h2g_window_plan_free(h2g_window_plan*);
+/* For the selected resident batch, what h2g_set_reads + h2g_set_read_names + h2g_set_read_ids do with the expanded arrays and no qualities:
+ * the reads are the windows of segs[0..n_segs) in order, each `len` bases.  Uploads text[lo, hi) (the range the segments touch), the segment
+ * table and the prefixes; kernels write the batch's codes, offsets, names, name offsets and ids.  n_text / n_prefix_bytes bound what the
+ * segments may name.  The reads must fit the stream's max_reads / max_bases; the names must fit 32-bit offsets. */
+H2G_EXPORT h2g_status h2g_set_reads_windows(h2g_stream*, const uint8_t* text, size_t n_text, const h2g_window_seg* segs, size_t n_segs,
+                                            uint32_t len, uint32_t step, const char* prefixes, size_t n_prefix_bytes);
+/* bytes uploaded / HIP-event time of the expansion kernels of this stream's last h2g_set_reads_windows (measurement) */
+typedef struct { uint64_t bytes_uploaded, bytes_written; float kernel_ms, pad; } h2g_windows_stats;
+H2G_EXPORT h2g_status h2g_get_windows_stats(h2g_stream*, h2g_windows_stats* out);
+/* Debug read-back of the selected resident batch as the device holds it: codes [offs[n]], offs [n + 1], names [name_offs[n]], name_offs [n + 1],
+ * ids [n] (a batch without explicit ids: H2G_ERR_ARG when ids != NULL).  The four counts are always set, so a first call with NULL arrays
+ * sizes the second; any pointer may be NULL. */
+H2G_EXPORT h2g_status h2g_fetch_reads(h2g_stream*, size_t* n_reads, size_t* n_bases, size_t* n_name_bytes, int* has_ids,
+                                      uint8_t* codes, uint32_t* offs, char* names, uint32_t* name_offs, uint32_t* ids);
 /* GenomeHit::combineWith (hi_aligner.h:1420-2025) as a primitive of its own: a[i] (the left hit) absorbs b[i] — concatenation, the mismatch rescan of the joint,
  * an insertion or deletion, or (spliced alignment) an intron placed by the donor / acceptor scan — over the resident reads; ok[i] = the function's return value.  `p` carries
  * scoring and splice policy (NULL: h2g_align_params_init's defaults for this index).  Inside go() the same device function runs as OP_COMBINE. */
