@@ -787,7 +787,8 @@ class Stream:
             c1, c2 = max(c1, int(o1[n])), max(c2, int(o2[n]))
 
     def tune(self, key, value):
-        """development / measurement knobs of go_run by name (h2g_stream_tune: "mstreams", "mach_total", "fast_reserve", "pair_slots", "fast", ...)"""
+        """development / measurement knobs of go_run by name (h2g_stream_tune: "mstreams", "mach_total", "fast_reserve", "pair_slots", "fast",
+        "fast_spliced" — 0 (the default): a spliced run on a linear index goes to the general machine whole, 1: through the fast pass's spliced build first —, ...)"""
         f = lib().h2g_stream_tune
         f.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         _chk(f(self.h, key.encode(), int(value)), "h2g_stream_tune " + key)

@@ -200,7 +200,7 @@ Options parse_options(int argc, char** argv) {
 		else if(a == "--quiet") o.quiet = true;                                      // gQuiet: no alignment summary on stderr (hisat2.cpp:4165)
 		else if(a == "--version") { printf("hisat2-align-amd (h2g) — output format of HISAT2 2.2.3\n"); exit(0); }
 		else if(a == "--reorder" || a == "-t" || a == "--time" || a == "--mm") {}   // output is always in read order; --mm (index mapping) has nothing to act on here
-		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow} as JSON (tests, bench)
+		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on} as JSON (tests, bench)
 		else if(a == "--parse-only") o.parse_only = true;                           // test hook: ingest the reads, print counts + checksums
 		else if(const int arity = h2g_align_option_arity(argv[i]); arity >= 0) { o.opts.push_back(argv[i]); if(arity) o.opts.push_back(need(argv[i])); }   // every option that ends in a field of h2g_align_params
 		else { fprintf(stderr, "hisat2-align-amd: option %s is not built (see DESIGN.md, scope)\n", a.c_str()); exit(1); }
@@ -961,6 +961,7 @@ public:
 	}
 	void free_streams() { for(Str& sg : S_) if(sg.st) { h2g_stream_free(sg.st); sg.st = nullptr; } }
 	uint64_t nsecond = 0, nruns = 0;          // reads that took the second pass; device runs
+	uint64_t nfast = 0, nhanded = 0;          // reads / pairs the fast pass completed; handed on to the general machine (summed over the runs)
 	double t_gpu = 0, t_up = 0, t_fetch = 0, t_stream = 0;
 private:
 	struct Str { h2g_stream* st = nullptr; size_t reads = 0, bases = 0; long batch = -1; size_t n = 0; uint64_t first_id = 0; bool paired = false; int merge = 0; };
@@ -999,7 +1000,7 @@ private:
 				[&] { return h2g_align_fetch_compact(st, res, ps.rec1.p, ps.rec1.cap, ao1, 0, n); },
 				[&] { if(ao1[n] <= ps.rec1.cap) return false; ps.rec1.need(ao1[n] + 8); return true; });
 		}
-		{ h2g_counters hc; if(h2g_get_counters(st, &hc) == H2G_OK) nsecond += hc.n_second_pass; }
+		{ h2g_counters hc; if(h2g_get_counters(st, &hc) == H2G_OK) { nsecond += hc.n_second_pass; nfast += hc.n_fast; nhanded += hc.n_fast_bail; } }
 		t_fetch += now() - tq0;
 		const FmtJob job{sg.batch, n, sg.first_id, set, sg.paired, sg.merge};
 		sg.batch = -1;                                  // (the stream's rows are copied: it can take the next batch)
@@ -1127,7 +1128,8 @@ int main(int argc, char** argv) {
 	        t_parse, parse.busy(), tot.t_fmt, t2 - t0, dev.t_stream, dev.t_up, dev.t_fetch);
 	if(!o.stats_fn.empty()) {
 		FILE* sf = fopen(o.stats_fn.c_str(), "w");
-		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns); fclose(sf); }
+		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
+		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded); fclose(sf); }
 	}
 	// (Measured and not shipped, round 6: ending the process here without the frees below saves this run 0.1 s and costs the NEXT process 1.7 s — the driver reclaims 40 GB of
 	// device memory of a process that did not return it while the next one is already allocating: profiles/r06_zc_ab.log.)

@@ -13,8 +13,15 @@
 // kernel (h2g_k_go_fast.hip) is the slot-queue scheme: a workgroup owns 1024 slots and one queue of slot ids per primitive; a wave pops <= 64 slots
 // of the longest queue, loads them in one go, runs THAT primitive at one code site, lets each lane run its control flow to the next request.
 //
-// Built for: --no-spliced-alignment, no --secondary, --bowtie2-dp 0, default pair policy (--fr, -I 0), reads of 32..128 bases without N.
-// Everything else never enters (go_run) or bails at the first state.
+// Built for: no --secondary, --bowtie2-dp 0, default pair policy (--fr, -I 0), reads of 32..128 bases without N; --no-spliced-alignment on either
+// kind of index, or — FG_SPLICED = 1, linear indexes — spliced alignment on.  Everything else never enters (go_run) or bails at the first state.
+//
+// FG_SPLICED = 1 (h2g_k_go_fast_spl.hip, tests/emul_spl) is the same state machine under the SPLICED rules, for the reads of a spliced run whose whole
+// trace stays unspliced (in an RNA-seq run: most reads, they lie inside one exon).  What spliced alignment changes in an unspliced trace is restated:
+// nextBWT's pseudogeneStop, getAnchorHits' overlap window and compatibleWith's bound of maxIntronLen, pairReads without the fragment-length test, and the
+// splice-site database's lookups in hybridSearch_recur (the pass goes on only when they return no site).  The moment a splice would enter the state — a
+// join whose reference gap is an intron, a database site next to a hit — the read bails: an edit here is 16 bits and holds no intron.  Pairs that need
+// alignMate bail as well (its cushion and window differ in spliced mode).  The machine behind this build is go_unit(linear, big, spl = true).
 //
 // FG_GRAPH = 1 (round 4) is the same state machine over a GRAPH index (SNP / indel ALTs): a partial hit carries its node range and in-edge
 // list, a coordinate is re-seated by adjustWithALT before it becomes a hit, and a hit's edits carry ALT ids.  The graph primitives are the
@@ -28,6 +35,12 @@
 #endif
 #if FG_GRAPH
 #include "h2g_graph.h"
+#endif
+#ifndef FG_SPLICED
+#define FG_SPLICED 0                    // 1: the pass under the SPLICED rules on a linear index (h2g_k_go_fast_spl.hip): reads whose whole trace stays unspliced; a splice is a bail
+#endif
+#if FG_SPLICED && (FG_GRAPH || FG_ALIGN_MATE)
+#error "FG_SPLICED is built for linear indexes, without alignMate in the pass"
 #endif
 
 namespace h2g {
@@ -212,6 +225,10 @@ struct FCtx {
 	const DAlts* alts;                             // the ALT database
 	GraphWS* gws;                                  // this LANE's scratch of one primitive (group walk, ALT-aware extension): nothing in it outlives a trip
 #endif
+#if FG_SPLICED
+	const DSpliceDB* ssdb = nullptr;               // the splice-site database (nullptr / empty: no lookups) and the id of read 0 of the batch (its visibility window)
+	uint32_t rdid_base = 0;
+#endif
 };
 #if FG_GRAPH
 // BWTHit::_node_iedge_count in one word: n (2 bits), then (node index, extra in-edges) 7 + 7 bits each, at most two entries; a list that does
@@ -364,8 +381,17 @@ H2G_HD void fh_get_left(const FHit& h, uint32_t* rdoff, uint32_t* len, uint32_t*
 #pragma unroll
 	for(uint32_t i = 0; i < FG_FE; i++) if(i < h.nedits && !stop && FH_STOP(h, i)) { *len = FE_POS(FE_GET(h, i)); stop = true; }
 }
-// compatibleWith :1375-1413 (hit_compatible) without spliced alignment
-H2G_HD bool fh_compatible(const FHit& a, const FHit& b) {
+// compatibleWith :1375-1413 (hit_compatible) without spliced alignment; FG_SPLICED: with the intron bound (:1409, h2g_align.h hit_compatible)
+#if FG_SPLICED
+#define FG_MIL , P.maxIntronLen
+#else
+#define FG_MIL
+#endif
+H2G_HD bool fh_compatible(const FHit& a, const FHit& b
+#if FG_SPLICED
+                          , uint32_t maxIntronLen
+#endif
+                          ) {
 	if(a.fw != b.fw || a.tidx != b.tidx) return false;
 	if(a.rdoff > b.rdoff) return false;
 	if(a.rdoff + a.len > b.rdoff + b.len) return false;
@@ -376,6 +402,9 @@ H2G_HD bool fh_compatible(const FHit& a, const FHit& b) {
 	if(ar > br) return false;
 	if(ar + al > br + bl) return false;
 	if(at > bt) return false;
+#if FG_SPLICED
+	if(bt - at > (br - ar) + maxIntronLen) return false;
+#endif
 	return true;
 }
 // calculateScore :3711-3891 (calculate_score) for mismatch / gap edits and soft trims
@@ -610,7 +639,11 @@ H2G_HD int64_t fh_part_score(const DScoring& sc, const SeqView& seq, const FHit&
 	}
 	return score;
 }
-H2G_HD bool fh_combine(const DRef& ref, const DScoring& sc, const SeqView& seq, FHit& a, const FHit& b, int64_t minsc, bool* indel) {
+H2G_HD bool fh_combine(const DRef& ref, const DScoring& sc, const SeqView& seq, FHit& a, const FHit& b, int64_t minsc, bool* indel
+#if FG_SPLICED
+                       , uint32_t minIntronLen
+#endif
+                       ) {
 	*indel = false;
 	uint32_t this_rdoff, this_len, this_toff, other_rdoff, other_len, other_toff;
 	fh_get_right(a, &this_rdoff, &this_len, &this_toff);
@@ -621,6 +654,15 @@ H2G_HD bool fh_combine(const DRef& ref, const DScoring& sc, const SeqView& seq, 
 	if(this_toff + len > reflen) return false;
 	const uint32_t refdif = other_toff - this_toff, rddif = other_rdoff - this_rdoff;
 	if(refdif != rddif) {
+#if FG_SPLICED
+		// spliced alignment on: a reference gap of minIntronLen or more is an intron (:1488, h2g_align.h hit_combine) — refused there without the
+		// probability tables or beyond the edit's length field, else the general machine's: an edit of this file cannot hold one
+		if(refdif > rddif && refdif - rddif >= minIntronLen) {
+			if(sc.donor_sum == nullptr || refdif - rddif > H2G_SPL_MAXLEN) return false;
+			*indel = true;
+			return false;
+		}
+#endif
 		// an insertion or a deletion: the gap budget decides first (:1539-1560); a join that survives it is the general machine's
 		int64_t remainsc = minsc - ((int64_t)a.score - fh_part_score(sc, seq, a, true)) - ((int64_t)b.score - fh_part_score(sc, seq, b, false));
 		if(remainsc > 0) remainsc = 0;
@@ -925,6 +967,10 @@ H2G_HD int64_t fg_hisat2_key(int64_t score, uint32_t trim) {      // hisat2_scor
 	return (int64_t)((uint64_t)score << 32) | ((int64_t)255 << 16) | t;
 }
 
+#if FG_SPLICED
+// Read::rdid of this read (mach_rdid of h2g_machine.h): what the database's visibility window is measured against
+H2G_HD uint32_t fg_rdid(const FCtx& C, const FState& S) { const uint32_t* ids = C.rd[0].ids; return ids ? ids[S.read] : C.rdid_base + S.read; }
+#endif
 // Runs the control flow of this lane until it needs a primitive (S.op != FOP_NONE), completes (FPC_DONE) or gives up (FPC_BAIL).
 H2G_HD void fast_step(const FCtx& C, FState& S, const FWords& W)
 {
@@ -1019,7 +1065,10 @@ again:
 		}
 		S.rb_np = fs_b4_set(S.rb_np, x, np + 1);
 		if(done) { S.rb_done |= 1u << x; S.sel_r = rdi; S.sel_f = fwi; F_GOTO(FPC_ALIGN); }
-		{ const uint32_t cur = fs_b4(S.rb_cur, x); if(cur + 1 < fs_rl(S, rdi)) S.rb_cur = fs_b4_set(S.rb_cur, x, cur + 1); }   // !pseudogeneStop (never set without spliced alignment)
+#if FG_SPLICED
+		if(type != H2G_PSEUDOGENE_HIT)                      // !pseudogeneStop (:4741; a search that stopped for it — and not as an anchor — is of that type: partial_search_item)
+#endif
+		{ const uint32_t cur = fs_b4(S.rb_cur, x); if(cur + 1 < fs_rl(S, rdi)) S.rb_cur = fs_b4_set(S.rb_cur, x, cur + 1); }   // (FG_SPLICED 0: unconditional — pseudogeneStop is never set without spliced alignment)
 		if(anchor) { S.rb_done |= 1u << x; S.sel_r = rdi; S.sel_f = fwi; F_GOTO(FPC_ALIGN); }
 		F_GOTO(FPC_NB_PICK);
 	}
@@ -1070,8 +1119,12 @@ again:
 				if(r > rr2) continue;
 				if(r + (int64_t)P.maxIntronLen < l2) continue;
 				bool pass;
+#if FG_SPLICED
+				pass = true;                                        // (the fragment-length test belongs to --no-spliced-alignment: :6013)
+#else
 				if(o1 < o2) pass = pe_concordant(o1, e1, fw1, o2, e2, fw2, P.maxFragLen);
 				else        pass = pe_concordant(o2, e2, fw2, o1, e1, fw1, P.maxFragLen);
+#endif
 				if(pass) {
 					int64_t threshold = S.bestPair == F_SMIN ? INT64_MIN : (int64_t)S.bestPair;
 					if(S.bestUnp0 != F_SMIN16 && S.bestUnp1 != F_SMIN16 && S.bestUnp0 >= S.minsc0 && S.bestUnp1 >= S.minsc1) {
@@ -1367,7 +1420,13 @@ again:
 				if(W.ld(gb) != tidx || ((w5 & 1u) != 0) != (S.sv_fw != 0)) continue;
 				const uint32_t g_rdoff = W.ld(gb + 4) & 0xffu;
 				const uint32_t hitoff = W.ld(gb + 1) + rl - g_rdoff, hitoff2 = toff + rl - S.gh_rdoff;
+#if FG_SPLICED
+				int64_t d_ = (int64_t)hitoff - (int64_t)hitoff2;    // within maxIntronLen of each other (:5160)
+				if(d_ < 0) d_ = -d_;
+				if(d_ <= (int64_t)P.maxIntronLen) { overlapped = true; W.st(gb + 5, w5 + (1u << 8)); break; }
+#else
 				if(hitoff == hitoff2) { overlapped = true; W.st(gb + 5, w5 + (1u << 8)); break; }   // _hitcount++
+#endif
 			}
 			if(!overlapped) {
 				if(S.nghits >= FG_NGH) F_BAIL(FB_NGHITS);
@@ -1448,6 +1507,19 @@ again:
 				const uint32_t rb = fg_res_base(S.sv_rdi, i), m = W.ld(rb + 2);
 				if(W.ld(rb) == hit.tidx && W.ld(rb + 1) == hit.toff && (m & 1u) == (hit.fw ? 1u : 0u) && ((m >> 1) & 7u) == hit.nedits) F_BAIL(FB_REDUNDANT);
 			}
+#if FG_SPLICED
+			// a full alignment with a database there: the same read joined through database sites near its ends (spliced_aligner.h:409-676) — the
+			// lookups the general machine performs (PC_RC_ENTRY / PC_FS_R_I of h2g_machine.h); with no site in either window the candidate list
+			// is the hit alone and it is reported as below, with one the joins are the machine's
+			if(C.ssdb != nullptr && C.ssdb->n != 0) {
+				const uint32_t rdid = fg_rdid(C, S);
+				uint32_t fo, fl, ft;
+				fh_get_left(hit, &fo, &fl, &ft);
+				if(fl >= minK && ft >= minK && hit.trim5 == 0 && ss_left_sites(*C.ssdb, hit.tidx, ft + minK, minK, rdid, nullptr, 0) != 0) F_BAIL(FB_OTHER);
+				fh_get_right(hit, &fo, &fl, &ft);
+				if(fl >= minK && hit.trim3 == 0 && ss_right_sites(*C.ssdb, hit.tidx, ft + fl - minK, minK, rdid, nullptr, 0) != 0) F_BAIL(FB_OTHER);
+			}
+#endif
 			// reportHit :6064 (al_report)
 			if(!(hit.rdoff - hit.trim5 > 0 || hit.len + hit.trim5 + hit.trim3 < rdlen) && hit.score >= minsc) {
 				if(nr >= FG_NRES) F_BAIL(FB_NRES);
@@ -1472,6 +1544,25 @@ again:
 			F_RC_RET(S.f_maxsc);
 		}
 		if(S.sp >= FG_NFRAME - 1) F_BAIL(FB_DEPTH);          // the deepest frame holds no lists: it may only report
+#if FG_SPLICED
+		// a partial alignment: database sites next to the end about to be extended come first (:685-811 left, :1365-1496 right) — the machine's
+		// lookups (PC_RC_ENTRY); a site there is a join through it, which is the machine's
+		if(C.ssdb != nullptr && C.ssdb->n != 0) {
+			const uint32_t rdid = fg_rdid(C, S);
+			uint32_t fo, fl, ft;
+			if(hitoff > 0 && (hitoff + hitlen == rdlen || hitoff + hitoff < rdlen - hitlen)) {
+				fh_get_left(hit, &fo, &fl, &ft);
+				if(fl >= minK_local && ft >= minK_local &&
+				   ss_left_sites(*C.ssdb, hit.tidx, ft + minK_local, minK_local + (minK_local < fo ? minK_local : fo), rdid, nullptr, 0) != 0) F_BAIL(FB_OTHER);
+			} else {
+				fh_get_right(hit, &fo, &fl, &ft);
+				if(fl >= minK_local) {
+					const uint32_t unmapped = rdlen - fo - fl;
+					if(ss_right_sites(*C.ssdb, hit.tidx, ft + fl - minK_local, minK_local + (minK_local < unmapped ? minK_local : unmapped), rdid, nullptr, 0) != 0) F_BAIL(FB_OTHER);
+				}
+			}
+		}
+#endif
 		if(hitoff > 0 && (hitoff + hitlen == rdlen || hitoff + hitoff < rdlen - hitlen)) F_GOTO(FPC_RC_ENTRY_LX);
 		F_GOTO(FPC_RC_ENTRY_RX);
 	}
@@ -1587,7 +1678,7 @@ again:
 		if(!S.a0) { S.f_ri--; F_GOTO(FPC_L_FOR_RI); }
 		const uint32_t hb = fg_frame_hit(S.sp);
 #endif
-		if(!fh_compatible(fh_load(W, FW_T1), fh_load(W, hb))) {
+		if(!fh_compatible(fh_load(W, FW_T1), fh_load(W, hb) FG_MIL)) {
 			if(S.f_count == 1) { S.f_ri--; F_GOTO(FPC_L_FOR_RI); }
 			F_GOTO(FPC_L_AFTER_FOR);
 		}
@@ -1683,7 +1774,7 @@ again:
 		if(!S.a0) F_GOTO(FPC_L_FOR_G);
 		const uint32_t hb = fg_frame_hit(S.sp);
 #endif
-		if(!fh_compatible(fh_load(W, FW_T1), fh_load(W, hb))) F_GOTO(FPC_L_FOR_G);
+		if(!fh_compatible(fh_load(W, FW_T1), fh_load(W, hb) FG_MIL)) F_GOTO(FPC_L_FOR_G);
 		if(S.f_unique) { S.a0 = 0; S.a1 = H2G_MAX; S.a2 = 0; S.a3 = FW_T1; F_OP(FOP_EXTEND, FPC_L_G_B); }
 		F_GOTO(FPC_L_G_B);
 	}
@@ -1820,7 +1911,7 @@ again:
 		if(!S.a0) { S.f_ri++; F_GOTO(FPC_R_FOR_RI); }
 		const uint32_t hb = fg_frame_hit(S.sp);
 #endif
-		if(!fh_compatible(fh_load(W, hb), fh_load(W, FW_T1))) {
+		if(!fh_compatible(fh_load(W, hb), fh_load(W, FW_T1) FG_MIL)) {
 			if(S.f_count == 1) { S.f_ri++; F_GOTO(FPC_R_FOR_RI); }
 			F_GOTO(FPC_R_AFTER_FOR);
 		}
@@ -1895,7 +1986,7 @@ again:
 		if(!S.a0) F_GOTO(FPC_R_FOR_G);
 		const uint32_t hb = fg_frame_hit(S.sp);
 #endif
-		if(!fh_compatible(fh_load(W, hb), fh_load(W, FW_T1))) F_GOTO(FPC_R_FOR_G);
+		if(!fh_compatible(fh_load(W, hb), fh_load(W, FW_T1) FG_MIL)) F_GOTO(FPC_R_FOR_G);
 		S.a0 = 0; S.a1 = 0; S.a2 = H2G_MAX; S.a3 = FW_T1;
 		F_OP(FOP_EXTEND, FPC_R_G_B);
 	}
@@ -2410,7 +2501,11 @@ H2G_HD void fast_op_combine(const FCtx& C, FState& S, const FWords& W) {
 	FHit a = fh_load(W, S.a3);
 	const FHit b = fh_load(W, S.a4);
 	bool indel = false;
-	const bool ok = fh_combine(*C.ref, C.P->sc, fg_sv(C, S), a, b, (int64_t)S.rc_minsc, &indel);
+	const bool ok = fh_combine(*C.ref, C.P->sc, fg_sv(C, S), a, b, (int64_t)S.rc_minsc, &indel
+#if FG_SPLICED
+	                           , C.P->minIntronLen
+#endif
+	                           );
 	if(indel) { S.pc = FPC_BAIL; S.bail = FB_INDEL; }
 	else if(!fh_store(W, S.a3, a)) { S.pc = FPC_BAIL; S.bail = FB_EDITS; }
 	S.a0 = ok ? 1u : 0u;

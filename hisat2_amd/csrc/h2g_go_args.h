@@ -93,6 +93,9 @@ struct FastArgs {
 	uint32_t cnt_off;                         // this launch's rank / side / step / aligned counters are counters[H2G_CNT_FAST_RANK + cnt_off ..]
 	uint32_t adopt_slot_words;                // words per slot of `adopt_slots` (the launch that left them may be another build of the pass: same layout, a shorter cold tail)
 	uint32_t mate_handover;                   // 1 (with orphan_T > 0, a build without alignMate): pairs that need alignMate are parked in their slots and listed for the drain launch — the alignMate build's
+	// spliced runs only (h2g_k_go_fast_spl.hip; at the end: the other builds' fields keep their offsets): the splice-site database and Read::rdid of read 0 of the batch (rd1.ids: per-read ids)
+	h2g::DSpliceDB ssdb;
+	uint32_t rdid_base;
 };
 extern "C" int h2g_go_fast_launch(const FastArgs*, unsigned grid, hipStream_t);
 extern "C" int h2g_go_fast_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
@@ -103,3 +106,6 @@ extern "C" int h2g_go_fast_am_launch(const FastArgs*, unsigned grid, hipStream_t
 extern "C" void h2g_go_fast_am_geometry(uint32_t* g);
 extern "C" int h2g_go_fast_graph_launch(const FastArgs*, unsigned grid, hipStream_t);
 extern "C" void h2g_go_fast_graph_geometry(uint32_t* g);   // ... [4] bytes of GraphWS per lane
+extern "C" int h2g_go_fast_spl_launch(const FastArgs*, unsigned grid, hipStream_t);        // h2g_k_go_fast_spl.hip: the pass under the spliced rules (FG_SPLICED = 1)
+extern "C" int h2g_go_fast_spl_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
+extern "C" void h2g_go_fast_spl_geometry(uint32_t* g);

@@ -114,6 +114,9 @@ __device__ __forceinline__ void fk_ctx(const FastArgs* A, uint32_t* stage, uint3
 		C.sc = reinterpret_cast<int64_t*>(A->sc_base + (tid >> 6) * (size_t)(64 * 2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))) + (threadIdx.x & 63); C.sc_stride = 64;
 	}
 #endif
+#if FG_SPLICED
+	C.ssdb = &A->ssdb; C.rdid_base = A->rdid_base;
+#endif
 	C.O = A->O;
 	C.mate_handover = FG_ALIGN_MATE ? 0u : A->mate_handover;
 	C.defer_slow = FG_GRAPH ? 1u : 0u;

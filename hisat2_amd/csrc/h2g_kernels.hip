@@ -111,6 +111,10 @@ static DGfm dg_now(h2g_index* ix) {
 #define H2G_DRAIN_GRID 64
 #define H2G_FAST_POOLS 3
 #define H2G_DEFAULT_ALIGN_MATE 0
+// the fast pass of SPLICED runs on a linear index (h2g_k_go_fast_spl.hip; env H2G_FAST_SPLICED, h2g_stream_tune "fast_spliced").  OFF by default: 1 M pairs drawn from a spliced transcript
+// model (36 % with a junction) take 225 ms per run with it and 70 ms with the machine alone — version 1 hands 44 % of the pairs on, and a machine pass behind a fast pass has at most
+// H2G_MACH_MAXGRID workgroups where the machine alone has the chip (profiles/r09_spliced_fast.md §4)
+#define H2G_DEFAULT_FAST_SPLICED 0
 // (the counter words of one go_run generation, H2G_CNT_BLOCK of them: h2g_go_args.h)
 #define H2G_MACH_MAXGRID 48u       // workgroups of ONE machine pass behind a fast pass
 #define H2G_MACH_TOTAL 128u        // ... and of all machine passes in flight together ("mach_total": a pass gets at most mach_total / mstreams workgroups)
@@ -189,7 +193,8 @@ struct h2g_stream {
 	bool ran_fast = false;
 	// development / measurement knobs (h2g_stream_tune; their H2G_* environment names are read ONCE, when the stream is created)
 	struct Tune { int fast = 1, blocks_per_cu = 0, pair_slots = 0, no_second_pass = 0; unsigned mach_div = 0 /* auto */, mach_min = 4, mach_total = H2G_MACH_TOTAL; int mach_total_auto = 1; int fast_reserve = H2G_FAST_RESERVE_DEFAULT; long dbg_read = -1;
-	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */; } tune;
+	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */;
+	              int fast_spliced = H2G_DEFAULT_FAST_SPLICED; /* the fast pass of spliced runs on a linear index (h2g_k_go_fast_spl.hip) */ } tune;
 	h2g_align_params last_p; int last_paired = -1;   // the option set of the last go_run (a different one waits for the machine streams)
 	uint8_t* d_sw_ws = nullptr;   // h2g_sw_align: H/E/F workspace of one batch of problems
 	size_t sw_ws_bytes = 0;
@@ -744,6 +749,7 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		s->tune.dbg_read = env("H2G_GO_DBG_READ", -1);
 		s->tune.tail = (int)env("H2G_FAST_TAIL", H2G_DEFAULT_TAIL); s->tune.tail_auto = getenv("H2G_FAST_TAIL") ? 0 : 1; s->tune.align_mate = (int)env("H2G_FAST_AM", H2G_DEFAULT_ALIGN_MATE);
 		s->tune.orphan = (int)env("H2G_FAST_ORPHAN", -1); s->tune.drain_grid = (int)env("H2G_DRAIN_GRID", H2G_DRAIN_GRID); s->tune.mate_handover = (int)env("H2G_FAST_MATE_HANDOVER", -1);
+		s->tune.fast_spliced = (int)env("H2G_FAST_SPLICED", H2G_DEFAULT_FAST_SPLICED);
 		s->tune.mach_total = (unsigned)env("H2G_MACH_TOTAL", H2G_MACH_TOTAL); s->tune.mach_total_auto = getenv("H2G_MACH_TOTAL") ? 0 : 1; s->tune.fast_reserve = (int)env("H2G_FAST_RESERVE", H2G_FAST_RESERVE_DEFAULT);
 		auto clampm = [](long m) { return (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); };
 		if(getenv("H2G_MSTREAMS")) s->mstreams = clampm(env("H2G_MSTREAMS", 0));   // pinned
@@ -2368,6 +2374,7 @@ static int go_check(h2g_stream* s, const h2g_align_params* p, bool paired) {
 // what a run does, from its options, the batch and the stream's knobs: no device calls, no side effects
 struct GoPlan {
 	bool linear, spl, xl, big_main, fast, second;
+	bool fast_spl;                 // the fast pass is the build for spliced runs (h2g_k_go_fast_spl.hip): its hand-ons go to the spliced machine units
 	const GoUnit *U, *L;           // the main pass's unit; the large-workspace unit (the second pass, the machine streams' warm-up)
 	uint32_t geo[4], lgeo[4];      // their geometries: [0] threads per workgroup, [1] reads in flight per workgroup
 	unsigned grid, M, bgrid;       // workgroups of the main pass; lanes (per-run buffers: M + 1 deep; area parts: M); workgroups of a second pass
@@ -2406,6 +2413,10 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 	g->U = &go_unit(g->linear, g->big_main, g->spl, g->xl);
 	// (graph indexes: h2g_k_go_fast_graph.hip, the same pass over the graph form of the compact state; --haplotype and the pair-policy options are `spl`)
 	g->fast = s->tune.fast && !g->spl && !g->big_main && p->no_spliced_alignment && !p->secondary && !p->bowtie2_dp;
+	// spliced alignment on a linear index (the reference's default run): the build of the pass under the spliced rules takes the reads whose whole trace stays
+	// unspliced and hands every other read on to the spliced units (h2g_stream_tune "fast_spliced")
+	g->fast_spl = s->tune.fast && s->tune.fast_spliced && g->linear && !p->no_spliced_alignment && !ext_opts && !g->big_main && !p->secondary && !p->bowtie2_dp;
+	if(g->fast_spl) g->fast = true;
 	g->second = !g->big_main && !s->tune.no_second_pass;     // (no_second_pass: a measurement / debugging knob)
 	// geometry of the unit: workgroups of geo[0] threads own geo[1] reads in flight; resident workgroups per CU = what the
 	// unit's waves per SIMD and the LDS (rings + one packed-read region per mate) allow
@@ -2598,15 +2609,15 @@ static int go_counters(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 }
 
 // ---- the fast pass (h2g_fast.h): the dominant traces with the per-read state on chip.  What it completes is final; the reads
-// it hands on (a device-side list, no host sync) are the general machine's batch.  Built for unspliced alignment on a linear
-// index with the default pair policy; every other option set goes to the machine whole.
+// it hands on (a device-side list, no host sync) are the general machine's batch.  Built for unspliced alignment (linear and graph
+// indexes) and for spliced alignment on a linear index (GoPlan::fast_spl), with the default pair policy; every other option set goes to the machine whole.
 // Its policy: geometry, the CUs it takes, the machine pass's share, whether a drain launch finishes the batch
 static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f) {
 	const size_t n_reads = s->cur().n_reads;
 	const bool linear = g.linear;
 	*f = FastPlan();
-	f->use_am = linear && paired && s->tune.align_mate != 0;
-	if(!linear) h2g_go_fast_graph_geometry(f->fgeo); else if(f->use_am) h2g_go_fast_am_geometry(f->fgeo); else h2g_go_fast_geometry(f->fgeo);
+	f->use_am = linear && paired && s->tune.align_mate != 0 && !g.fast_spl;      // (alignMate differs in spliced mode: such pairs are the machine's)
+	if(!linear) h2g_go_fast_graph_geometry(f->fgeo); else if(g.fast_spl) h2g_go_fast_spl_geometry(f->fgeo); else if(f->use_am) h2g_go_fast_am_geometry(f->fgeo); else h2g_go_fast_geometry(f->fgeo);
 	// CUs: one persistent fast workgroup each (LDS-bound), minus the few the machine pass of the PREVIOUS run may still hold
 	// (the machine takes ~150 hand-ons per workgroup in half the time of a fast pass; the count is the last finished fast pass's)
 	const unsigned NB = g.M + 1;
@@ -2649,7 +2660,7 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	f->dgrid = (unsigned)(s->tune.drain_grid < 1 ? 1 : s->tune.drain_grid);
 	// pairs that need alignMate (hi_aligner.h:5579): with a drain launch there, the fast launch parks them and the drain launch is the alignMate build of the pass (k_go_fast_am_drain)
 	// — the hot loop keeps the lighter build, the machine sees neither them nor the tail (h2g_stream_tune "mate_handover": -1 this policy, 0 off, 1 on)
-	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && s->tune.mate_handover != 0;
+	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && !g.fast_spl && s->tune.mate_handover != 0;
 	for(int k = 0; k < 5; k++) f->dgeo[k] = f->fgeo[k];
 	if(f->mate_ho) h2g_go_fast_am_geometry(f->dgeo);
 	f->psel = f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
@@ -2713,6 +2724,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	F.total = (uint32_t)s->cur().n_reads; F.paired = paired ? 1u : 0u;
 	F.alts = A.alts; F.gws_base = nullptr; F.gws_stride = 0; F.sc_base = nullptr;
 	F.dbg_read = A.dbg_read; F.dbg_buf = A.dbg_buf;
+	F.ssdb = A.ssdb; F.rdid_base = A.rdid_base;                          // (spliced runs: the database of this run — a wave of the temporary-splice-site mode brings its own)
 	// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
 	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
 	if(!g.linear) {   // per-lane scratch of the graph primitives (every CU may hold a workgroup)
@@ -2753,7 +2765,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		*hD = D;
 		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
 	}
-	if((!g.linear ? h2g_go_fast_graph_launch : f.use_am ? h2g_go_fast_am_launch : h2g_go_fast_launch)(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
+	if((!g.linear ? h2g_go_fast_graph_launch : g.fast_spl ? h2g_go_fast_spl_launch : f.use_am ? h2g_go_fast_am_launch : h2g_go_fast_launch)(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
 	r->A.list = bl; r->A.nlist = bl + s->max_reads;
 	return H2G_OK;
 }
@@ -2771,7 +2783,7 @@ static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		const bool use_am = f.use_am || f.mate_ho;
 		HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
 		HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
-		if((!g.linear ? h2g_go_fast_graph_launch_drain : use_am ? h2g_go_fast_am_launch_drain : h2g_go_fast_launch_drain)(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
+		if((!g.linear ? h2g_go_fast_graph_launch_drain : g.fast_spl ? h2g_go_fast_spl_launch_drain : use_am ? h2g_go_fast_am_launch_drain : h2g_go_fast_launch_drain)(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
 		HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
 		HIPCHK(hipEventRecord(s->ev_pool[f.psel], s->dst));
 		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
@@ -3263,7 +3275,7 @@ extern "C" h2g_status h2g_align_fetch_long_edits(h2g_stream* s, h2g_edit* out, s
 }
 
 // development hook: measurement / debugging knobs of go_run by name.  Everything in flight is waited for first, so a change never meets a
-// queued run.  "fast" 0/1, "blocks_per_cu", "pair_slots", "no_second_pass", "mach_div", "mach_min", "dbg_read" (-1 = off), "tail", "align_mate",
+// queued run.  "fast" 0/1, "blocks_per_cu", "pair_slots", "no_second_pass", "mach_div", "mach_min", "dbg_read" (-1 = off), "tail", "align_mate", "fast_spliced" (0: spliced runs go to the machine whole),
 // "mstreams" (pins lanes = machine streams in rotation, 1..H2G_MSTREAMS_MAX), "mstreams_light" (machine streams in rotation while the fast pass hands on little), "mach_total" (workgroups of all of them together), "fast_reserve" (CUs the fast pass leaves
 // free: -1 = as many as the machine passes in flight may hold)
 extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream* s, const char* key, long v) {
@@ -3277,6 +3289,7 @@ extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream
 	else if(k == "mach_total") { s->tune.mach_total_auto = v <= 0; s->tune.mach_total = v <= 0 ? H2G_MACH_TOTAL : (unsigned)v; }      // (0 = the default policy)
 	else if(k == "fast_reserve") s->tune.fast_reserve = (int)v;
 	else if(k == "mate_handover") s->tune.mate_handover = (int)v;
+	else if(k == "fast_spliced") s->tune.fast_spliced = (int)v;
 	else if(k == "orphan") s->tune.orphan = (int)v; else if(k == "drain_grid") s->tune.drain_grid = (int)(v < 1 ? 1 : v > 128 ? 128 : v);
 	else if(k == "mstreams") { s->mstreams = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v); s->gen = 0; }   // pins lanes = machine streams (nothing is in flight: every buffer set is free)
 	else if(k == "mstreams_light") s->mstreams_light = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v);   // S of the light regime (mstreams_policy)
