@@ -292,6 +292,7 @@ EXPORTS = [
     "h2g_align_fetch_compact", "h2g_align_pairs_fetch_compact", "h2g_host_alloc", "h2g_host_free",
     "h2g_graph_lf", "h2g_fm_search_graph", "h2g_index_synth_graph_sides", "h2g_sw_align", "h2g_sa_resolve_graph", "h2g_adjust_with_alt",
     "h2g_index_dense_sa_check",
+    "h2g_index_dense_lsa_check",
     "h2g_window_plan_create", "h2g_window_plan_add_file", "h2g_window_plan_get_info", "h2g_window_plan_text", "h2g_window_plan_prefixes", "h2g_window_plan_segments",
     "h2g_window_plan_select", "h2g_window_plan_free", "h2g_set_reads_windows", "h2g_get_windows_stats", "h2g_fetch_reads",
 ]
@@ -323,6 +324,7 @@ def lib():
     L.h2g_index_free.argtypes = [vp]
     L.h2g_index_free.restype = None
     L.h2g_index_dense_sa_check.argtypes = [vp, P(u32), P(u64)]
+    L.h2g_index_dense_lsa_check.argtypes = [vp, P(u32), P(u64)]
     L.h2g_stream_create.argtypes = [vp, C.c_size_t, C.c_size_t, P(vp)]
     L.h2g_stream_free.argtypes = [vp]
     L.h2g_stream_free.restype = None
@@ -488,6 +490,12 @@ class Index:
         """Waits for the dense SA table's build (H2G_DENSE_SA).  -> (has_table, rows that differ from the canonical walk or None)"""
         st, nd = u32(0), u64(0)
         _chk(lib().h2g_index_dense_sa_check(self.h, C.byref(st), C.byref(nd) if verify else None), "h2g_index_dense_sa_check")
+        return bool(st.value), (int(nd.value) if verify else None)
+
+    def dense_lsa(self, verify=False):
+        """Waits for the build of the dense table of local rows (H2G_DENSE_LSA).  -> (has_table, entries that differ from the canonical walk or None)"""
+        st, nd = u32(0), u64(0)
+        _chk(lib().h2g_index_dense_lsa_check(self.h, C.byref(st), C.byref(nd) if verify else None), "h2g_index_dense_lsa_check")
         return bool(st.value), (int(nd.value) if verify else None)
 
     def close(self):

@@ -60,6 +60,9 @@ struct DLocalSet {
 	const uint32_t*   first;   // [nPat+1] first local index of each text (HGFM::_localGFMs[tidx])
 	const uint32_t*   zoffs;   // all '$' rows, DLocalDesc::zoffs_off
 	uint32_t n, ftabChars, offRate;
+	// the dense table of the local rows of a linear index (lsa_resolve_row below): row r of local index i at lsa[lsa_base[i] + r]; nullptr: every row walks
+	const uint32_t*   lsa = nullptr;        // what sa_walk_idx returns for the row | the LF steps that walk takes << 16; H2G_LSA_DIST_SAT steps: not in the table
+	const uint64_t*   lsa_base = nullptr;   // [n + 1] prefix sum of the indexes' row counts (len + 1): beyond 32 bits on a human-size genome
 };
 #define H2G_LOCAL_INTERVAL 56320u   // local_index_interval hier_idx_common.h:24-31
 
@@ -287,6 +290,48 @@ H2G_HD uint32_t sa_walk_idx(const IDX& ix, uint32_t row, uint32_t offMask, uint3
 	return jumps;
 }
 
+// ---- the dense table of local rows.  Like the global table (h2g_core.h sa_resolve_row): a local row's joined offset and the length of its walk are
+// properties of the index alone, so a linear index may carry both for every row of every local index — 4 bytes per row, one scattered request where the
+// walk was a chain of about 7 dependent sides (one local row in 8 is sampled).  The step count is kept because it is part of the results.  A walk of
+// H2G_LSA_DIST_SAT steps or more is not in the table: that row walks (and, in the fast pass, still bails at 500 steps as it did: the threshold stays below that).
+#ifndef H2G_LSA_DIST_SAT
+#define H2G_LSA_DIST_SAT 255u
+#endif
+static_assert(H2G_LSA_DIST_SAT <= 500u && H2G_LSA_DIST_SAT > 0u, "rows the fast pass bails on (more than 500 steps) must stay out of the table");
+#define H2G_LSA_MISS (H2G_LSA_DIST_SAT << 16)
+// sa_walk_idx of row `row` of local index `lidx` (ix is that index) through the table when the set has one
+template <typename IDX>
+H2G_HD uint32_t lsa_resolve_row(const IDX& ix, const DLocalSet& ls, uint32_t lidx, uint32_t row, uint32_t* steps) {
+	if(ls.lsa) {
+		const uint32_t v = ls.lsa[ls.lsa_base[lidx] + row];
+		if((v >> 16) != H2G_LSA_DIST_SAT) { *steps += v >> 16; return v & 0xffffu; }
+	}
+	return sa_walk_idx(ix, row, (0xffffu << ls.offRate) & 0xffffu, ls.offRate, ls.words + ls.desc[lidx].offs_off, true, steps);
+}
+// Builds the entries of rows first, first + stride, ... below `end` of one local index into tab[row]: sa_walk_idx's loop with the walks of ONE caller laid
+// end to end (as sa_dense_build_rows), one side load per step
+template <typename IDX>
+H2G_HD void lsa_build_rows(const IDX& ix, uint32_t offMask, uint32_t offRate, const uint16_t* offs, uint32_t first, uint32_t stride, uint32_t end, uint32_t* tab) {
+	uint32_t cur = first, row = first, jumps = 0;
+	while(cur < end) {
+		uint32_t val = 0;
+		bool done = false;
+		if(ix.is_zoff(row)) { val = jumps; done = true; }
+		else if((row & offMask) == row) {
+			const uint32_t off = offs[row >> offRate];
+			if(off != 0xffffu) { val = off + jumps; done = true; }
+		}
+		if(jumps >= H2G_LSA_DIST_SAT || val > 0xffffu) { jumps = H2G_LSA_DIST_SAT; val = 0; done = true; }
+		if(done) {
+			tab[cur] = val | (jumps << 16);
+			cur += stride; row = cur; jumps = 0;
+			continue;
+		}
+		row = ix.lf(row);
+		jumps++;
+	}
+}
+
 // LocalGFM::joinedToTextOff (gfm.h:5527, 16-bit rstarts, rejectStraddle = true) + the local -> global shift of
 // getGenomeCoords_local (hi_aligner.h:5925-5934).  false = skip this element.
 H2G_HD bool local_joff_to_coord(const DLocalSet& ls, const DLocalDesc* d, uint32_t joff, uint32_t rdoff, uint32_t rdlen, h2g_coord* out) {
@@ -322,10 +367,10 @@ H2G_HD bool genome_coords_local(const LX& ix, uint32_t top, uint32_t bot, uint32
                                 uint32_t cap, uint32_t* ncoords, uint32_t* nsteps)
 {
 	const DLocalDesc* d = ix.d;
-	const uint32_t offMask = (0xffffu << ix.ls->offRate) & 0xffffu;
+	const uint32_t lidx = (uint32_t)(d - ix.ls->desc);
 	uint32_t n = 0;
 	for(uint32_t e = 0; e < bot - top; e++) {
-		uint32_t joff = sa_walk_idx(ix, top + e, offMask, ix.ls->offRate, ix.ls->words + d->offs_off, true, nsteps);
+		uint32_t joff = lsa_resolve_row(ix, *ix.ls, lidx, top + e, nsteps);
 		h2g_coord c;
 		if(!local_joff_to_coord(*ix.ls, d, joff, rdoff, rdlen, &c)) continue;
 		if(n < cap) coords[n++] = c;

@@ -2381,21 +2381,26 @@ H2G_HD void fast_op_lsearch(const FCtx& C, FState& S) {
 #endif
 // getGenomeCoords_local :5861 (genome_coords_local), chunked like fast_op_gcoords.  a0 lidx a1 top a2 bot a3 rdoff a4 rdlen a5 dst; under way:
 // a2 bits 16.. = 1 | element << 1 | coordinates written << 4 | jumps << 7, a4 bits 8.. = the row (16 bits)
+// `tab`: the rows of this local index in the dense table (lsa_resolve_row, h2g_align.h), nullptr without one: an element that is not under way (prog & 1: it
+// goes on walking, the launch that stored it may have run without the table) takes its entry from there, and walks as before when the table does not hold
+// the row.  A fresh request starts at element e0 with n0 coordinates written (fast_op_lcoords).
 template <typename LX>
-H2G_HD bool fast_op_lcoords_walk(const FCtx& C, FState& S, const FWords& W, const LX& lx) {
+H2G_HD bool fast_op_lcoords_walk(const FCtx& C, FState& S, const FWords& W, const LX& lx, const uint32_t* tab, uint32_t e0, uint32_t n0) {
 	const uint32_t offMask = (0xffffu << C.ls->offRate) & 0xffffu, offRate = C.ls->offRate;
 	const uint16_t* offs = C.ls->words + lx.d->offs_off;
 	const uint32_t top = S.a1, bot = S.a2 & 0xffffu, rdlen = S.a4 & 0xffu;
-	uint32_t prog = S.a2 >> 16, e = 0, n = 0, jumps = 0, row = 0;
+	uint32_t prog = S.a2 >> 16, e = e0, n = n0, jumps = 0, row = 0;
 	bool resume = false;
 	if(prog & 1u) { e = (prog >> 1) & 7u; n = (prog >> 4) & 7u; jumps = prog >> 7; row = S.a4 >> 8; resume = true; }
 	uint32_t budget = FG_LWALK_STEPS, steps = 0;
 	for(; e < bot - top; e++) {
+		const uint32_t ent = tab != nullptr && !resume ? tab[top + e] : H2G_LSA_MISS;
 		if(!resume) { row = top + e; jumps = 0; }
 		resume = false;
 		uint32_t joff = 0;
 		bool found = false;
-		while(true) {                                            // sa_walk_idx (h2g_align.h) with a step budget
+		if((ent >> 16) != H2G_LSA_DIST_SAT) { joff = ent & 0xffffu; steps += ent >> 16; found = true; }
+		while(!found) {                                          // sa_walk_idx (h2g_align.h) with a step budget
 			if(lx.is_zoff(row)) { joff = jumps; found = true; break; }
 			if((row & offMask) == row) {
 				const uint32_t off = offs[row >> offRate];
@@ -2425,7 +2430,7 @@ H2G_HD bool fast_op_lcoords_walk(const FCtx& C, FState& S, const FWords& W, cons
 // linear index (chunked), a graph one through the group walk.  a6 / a7 node range, a8 in-edges of the search that found the rows
 H2G_HD bool fast_op_lcoords(const FCtx& C, FState& S, const FWords& W) {
 	const DLocalDesc* d = &C.ls->desc[S.a0];
-	if(local_is_linear(*d)) { LIdxW lw; lw.ls = C.ls; lw.d = d; return fast_op_lcoords_walk(C, S, W, lw); }
+	if(local_is_linear(*d)) { LIdxW lw; lw.ls = C.ls; lw.d = d; return fast_op_lcoords_walk(C, S, W, lw, nullptr, 0u, 0u); }
 	const LGfm x = lgfm_of(*C.ls, *d);
 	const uint32_t rdlen = S.a4 & 0xffu;
 	// one node through one row: the row walk, chunked (under way: a2 bit 31 set, a1 = the row, a6 = the node, a7 = steps so far)
@@ -2494,8 +2499,36 @@ H2G_HD void fast_op_gsearch(const FCtx& C, FState& S) {       // globalGFMSearch
 // (LIdxR needs the descriptor pointer for local_joff_to_coord and the offs array: fast_op_lcoords_walk reads lx.d)
 struct LIdxRD : LIdxR { const DLocalDesc* d; };
 H2G_HD bool fast_op_lcoords(const FCtx& C, FState& S, const FWords& W) {
-	LIdxRD lx; lx.d = &C.ls->desc[S.a0]; lx.init(C.ls, lx.d);
-	return fast_op_lcoords_walk(C, S, W, lx);
+	const DLocalDesc* d = &C.ls->desc[S.a0];
+	const uint32_t* tab = C.ls->lsa ? C.ls->lsa + C.ls->lsa_base[S.a0] : nullptr;
+	uint32_t e0 = 0, n0 = 0;
+	// The dense table of local rows: the entries of the first FG_NCO elements of a fresh request are fetched before any is used — independent loads where
+	// the walk was a chain — and the request is over here, the index's descriptor never read into registers, unless the table does not hold one of its rows
+	// (a walk of H2G_LSA_DIST_SAT steps or more): from that element on it goes the old way.  Elements beyond FG_NCO (some were skipped by
+	// local_joff_to_coord) fetch their entry one by one.
+	if(tab != nullptr && !((S.a2 >> 16) & 1u)) {
+		const uint32_t top = S.a1, nelt = (S.a2 & 0xffffu) - top, rdlen = S.a4 & 0xffu;
+		uint32_t tv[FG_NCO], steps = 0;
+#pragma unroll
+		for(uint32_t k = 0; k < FG_NCO; k++) tv[k] = k < nelt ? tab[top + k] : H2G_LSA_MISS;
+		for(; e0 < nelt; e0++) {
+			uint32_t ent = H2G_LSA_MISS;
+			if(e0 >= FG_NCO) ent = tab[top + e0];
+			else {
+#pragma unroll
+				for(uint32_t k = 0; k < FG_NCO; k++) if(k == e0) ent = tv[k];
+			}
+			if((ent >> 16) == H2G_LSA_DIST_SAT) break;
+			steps += ent >> 16;
+			h2g_coord c;
+			if(!local_joff_to_coord(*C.ls, d, ent & 0xffffu, S.a3, rdlen, &c)) continue;
+			if(n0 < FG_NCO) { const uint32_t co3[3] = {c.tidx, c.toff, c.joinedOff}; W.stv<3>(S.a5 + 3 * n0, co3); n0++; }
+		}
+		S.nsteps += steps;
+		if(e0 == nelt) { S.a0 = n0; return false; }
+	}
+	LIdxRD lx; lx.d = d; lx.init(C.ls, d);
+	return fast_op_lcoords_walk(C, S, W, lx, nullptr, e0, n0);
 }
 H2G_HD void fast_op_combine(const FCtx& C, FState& S, const FWords& W) {
 	FHit a = fh_load(W, S.a3);

@@ -67,6 +67,14 @@ struct h2g_index {
 	hipStream_t dense_st = nullptr; hipEvent_t dense_ev = nullptr;
 	std::atomic<bool> dense_ready{false};
 	double dense_ms = 0.0;                                 // (H2G_DENSE_SA=2: the build, timed on the host)
+	bool dense_synced = false;                             // the uploads are known to be over (one device-wide wait, before the first build is queued)
+	// the dense table of the local rows (h2g_align.h lsa_resolve_row): built by k_lsa_dense_build behind the global table's build on dense_st, with an
+	// event of its own.  `dls` never carries its pointers: dls_now()
+	uint32_t* d_lsa = nullptr; uint64_t* d_lsa_base = nullptr;
+	uint64_t lsa_rows = 0;
+	hipEvent_t lsa_ev = nullptr;
+	std::atomic<bool> lsa_ready{false};
+	double lsa_ms = 0.0;                                   // (H2G_DENSE_LSA=2: the build, timed on the host)
 };
 // the index's DGfm as a run queued now may use it: with the dense SA table from the moment its build is over (polled, never waited for)
 static DGfm dg_now(h2g_index* ix) {
@@ -78,6 +86,18 @@ static DGfm dg_now(h2g_index* ix) {
 	}
 	g.sa_dense = ix->d_sa_dense; g.sa_dist = ix->d_sa_dist;
 	return g;
+}
+
+// ... and its DLocalSet: with the dense table of the local rows from the moment that table's own build is over
+static DLocalSet dls_now(h2g_index* ix) {
+	DLocalSet l = ix->dls;
+	if(!ix->d_lsa) return l;
+	if(!ix->lsa_ready.load(std::memory_order_acquire)) {
+		if(hipEventQuery(ix->lsa_ev) != hipSuccess) { (void)hipGetLastError(); return l; }
+		ix->lsa_ready.store(true, std::memory_order_release);
+	}
+	l.lsa = ix->d_lsa; l.lsa_base = ix->d_lsa_base;
+	return l;
 }
 
 // The general machine's pass over run k's hand-ons is a LATENCY CHAIN: its length is its longest reads' (hundreds of dependent trips of
@@ -329,6 +349,7 @@ static void dense_sa_start(h2g_index* ix) {
 		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess;
 	}
 	ok = ok && hipDeviceSynchronize() == hipSuccess;                  // the uploads (their padding is set on the null stream) are over
+	ix->dense_synced = ok;
 	const auto t0 = std::chrono::steady_clock::now();
 	if(ok) {
 		const uint64_t waves = ((uint64_t)rows + H2G_DENSE_CHUNK - 1) / H2G_DENSE_CHUNK;
@@ -351,6 +372,86 @@ static void dense_sa_start(h2g_index* ix) {
 		if(hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }       // (the table stays unused: dense_ready is never set by a failed event)
 		ix->dense_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		ix->dense_ready.store(true, std::memory_order_release);
+	}
+}
+
+// ------------------------------------------------------------------------------------------ the dense table of local rows
+// One workgroup per local index, a quarter of its rows per wave, lane l the rows l, l + 64, ... of that quarter (lsa_build_rows, h2g_align.h): the index's
+// 16 KB of sides stay in cache under the workgroup and a wave's stores stay within its quarter.  An empty local index (never searched) keeps one unused entry.
+__global__ __launch_bounds__(256) void k_lsa_dense_build(DLocalSet ls, const uint64_t* lsa_base, uint32_t* lsa) {
+	const uint32_t li = blockIdx.x;
+	if(li >= ls.n) return;
+	const DLocalDesc* d = &ls.desc[li];
+	uint32_t* tab = lsa + lsa_base[li];
+	if(d->len == 0) { if(threadIdx.x == 0) tab[0] = H2G_LSA_MISS; return; }
+	const uint32_t rows = d->len + 1, per = (rows + 3) / 4, lo = (threadIdx.x >> 6) * per, hi = lo + per < rows ? lo + per : rows;
+	LIdxR lx; lx.init(&ls, d);
+	lsa_build_rows(lx, (0xffffu << ls.offRate) & 0xffffu, ls.offRate, ls.words + d->offs_off, lo + (threadIdx.x & 63u), 64u, hi, tab);
+}
+// entries that are not what the canonical walk gives (h2g_index_dense_lsa_check)
+__global__ __launch_bounds__(256) void k_lsa_dense_check(DLocalSet ls, const uint64_t* lsa_base, const uint32_t* lsa, unsigned long long* ndiff) {
+	unsigned long long bad = 0;
+	for(uint32_t li = blockIdx.x; li < ls.n; li += gridDim.x) {
+		const DLocalDesc* d = &ls.desc[li];
+		const uint32_t* tab = lsa + lsa_base[li];
+		if(d->len == 0) { if(threadIdx.x == 0 && tab[0] != H2G_LSA_MISS) bad++; continue; }
+		LIdxR lx; lx.init(&ls, d);
+		for(uint32_t row = threadIdx.x; row <= d->len; row += blockDim.x) {
+			uint32_t steps = 0;
+			const uint32_t off = sa_walk_idx(lx, row, (0xffffu << ls.offRate) & 0xffffu, ls.offRate, ls.words + d->offs_off, true, &steps);
+			const uint32_t want = steps >= H2G_LSA_DIST_SAT || off > 0xffffu ? H2G_LSA_MISS : off | (steps << 16);
+			if(tab[row] != want) bad++;
+		}
+	}
+	if(bad) atomicAdd(ndiff, bad);
+}
+// H2G_DENSE_LSA: 0 never, 1 build asynchronously when the table fits, 2 build and wait; unset: what H2G_DENSE_SA resolves to.  Queued behind the global
+// table's build on the same low-priority stream; the fit rule is that table's, applied to the memory free once it is allocated.  Nothing here fails a load.
+static void dense_lsa_start(h2g_index* ix) {
+	const char* ev = getenv("H2G_DENSE_LSA");
+	if(!ev || !*ev) ev = getenv("H2G_DENSE_SA");
+	const int mode = ev && *ev ? atoi(ev) : 1;
+	if(mode <= 0 || !ix->dg.linear || !ix->has_local || ix->h_ldesc.empty()) return;
+	const size_t n = ix->h_ldesc.size();
+	std::vector<uint64_t> base(n + 1, 0);
+	for(size_t i = 0; i < n; i++) {
+		if(!local_is_linear(ix->h_ldesc[i])) return;
+		base[i + 1] = base[i] + (uint64_t)ix->h_ldesc[i].len + 1;
+	}
+	const size_t rows = base[n], b_tab = rows * 4 + 64, b_base = (n + 1) * 8;
+	size_t free_b = 0, total_b = 0;
+	if(hipMemGetInfo(&free_b, &total_b) != hipSuccess || b_tab + b_base > free_b / 4) { (void)hipGetLastError(); return; }
+	void *pt = nullptr, *pb = nullptr;
+	hipStream_t st = ix->dense_st; hipEvent_t e = nullptr;
+	bool ok = hipMalloc(&pt, b_tab) == hipSuccess && hipMalloc(&pb, b_base) == hipSuccess &&
+	          hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+	if(ok && !st) {
+		int least = 0, greatest = 0;
+		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess;
+	}
+	if(ok && !ix->dense_synced) { ok = hipDeviceSynchronize() == hipSuccess; ix->dense_synced = ok; }
+	ok = ok && hipMemcpy(pb, base.data(), b_base, hipMemcpyHostToDevice) == hipSuccess;
+	const auto t0 = std::chrono::steady_clock::now();
+	if(ok) {
+		hipLaunchKernelGGL(k_lsa_dense_build, dim3((unsigned)n), dim3(256), 0, st, ix->dls, (const uint64_t*)pb, (uint32_t*)pt);
+		ok = hipGetLastError() == hipSuccess && hipEventRecord(e, st) == hipSuccess;
+		if(!ok && st) (void)hipStreamSynchronize(st);
+	}
+	if(!ok) {
+		(void)hipGetLastError();
+		if(pt) (void)hipFree(pt);
+		if(pb) (void)hipFree(pb);
+		if(e) (void)hipEventDestroy(e);
+		if(st && !ix->dense_st) (void)hipStreamDestroy(st);
+		return;
+	}
+	ix->allocs.push_back(pt); ix->allocs.push_back(pb);
+	ix->device_bytes += b_tab + b_base;
+	ix->d_lsa = (uint32_t*)pt; ix->d_lsa_base = (uint64_t*)pb; ix->lsa_rows = rows; ix->dense_st = st; ix->lsa_ev = e;
+	if(mode >= 2) {
+		if(hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }
+		ix->lsa_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		ix->lsa_ready.store(true, std::memory_order_release);
 	}
 }
 
@@ -483,8 +584,13 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	sgp.reset();
 	const double t_up = lsec();
 	dense_sa_start(ix);
-	if(ltime) fprintf(stderr, "index load: parse %.3f s, global arrays on the device %.3f s, local pack joined %.3f s, dense SA table %s (%.3f s here, build %.1f ms), all %.3f s (%.2f GB)\n", t_parse, t_global, t_join,
-	                  !ix->d_sa_dist ? "none" : ix->dense_ready.load() ? "built" : "queued", lsec() - t_up, ix->dense_ms, lsec(), ix->device_bytes / 1e9);
+	const double t_sa = lsec();
+	dense_lsa_start(ix);
+	if(ltime) fprintf(stderr, "index load: parse %.3f s, global arrays on the device %.3f s, local pack joined %.3f s, dense SA table %s (%.3f s here, build %.1f ms), "
+	                  "dense local table %s (%.3f s here, build %.1f ms, %.2f GB), all %.3f s (%.2f GB)\n", t_parse, t_global, t_join,
+	                  !ix->d_sa_dist ? "none" : ix->dense_ready.load() ? "built" : "queued", t_sa - t_up, ix->dense_ms,
+	                  !ix->d_lsa ? "none" : ix->lsa_ready.load() ? "built" : "queued", lsec() - t_sa, ix->lsa_ms, ix->d_lsa ? (ix->lsa_rows * 4 + 64 + (ix->h_ldesc.size() + 1) * 8) / 1e9 : 0.0,
+	                  lsec(), ix->device_bytes / 1e9);
 	*out = ix;
 	return H2G_OK;
 }
@@ -593,9 +699,43 @@ extern "C" h2g_status h2g_index_dense_sa_check(h2g_index* ix, uint32_t* state, u
 	return H2G_OK;
 }
 
+// The dense table of the local rows, as h2g_index_dense_sa_check: *state = 0 none (not a linear index, no local indexes, H2G_DENSE_LSA=0, or it did not fit),
+// 1 complete; *rows_differ = entries that are not what the walk gives.
+extern "C" h2g_status h2g_index_dense_lsa_check(h2g_index* ix, uint32_t* state, uint64_t* rows_differ) {
+	if(!ix) return H2G_ERR_ARG;
+	if(state) *state = 0;
+	if(rows_differ) *rows_differ = 0;
+	if(!ix->d_lsa) return H2G_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	HIPCHK(hipStreamSynchronize(ix->dense_st));
+	const DLocalSet l = dls_now(ix);
+	if(!l.lsa) return H2G_OK;
+	if(state) *state = 1;
+	if(!rows_differ) return H2G_OK;
+	unsigned long long* dn = nullptr;
+	HIPCHK(hipMalloc(&dn, sizeof *dn));
+	unsigned long long hn = 0;
+	hipError_t e = hipMemsetAsync(dn, 0, sizeof *dn, ix->dense_st);
+	if(e == hipSuccess) {
+		hipLaunchKernelGGL(k_lsa_dense_check, dim3(l.n < 8192u ? l.n : 8192u), dim3(256), 0, ix->dense_st, ix->dls, l.lsa_base, l.lsa, dn);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipMemcpyAsync(&hn, dn, sizeof hn, hipMemcpyDeviceToHost, ix->dense_st);
+	if(e == hipSuccess) e = hipStreamSynchronize(ix->dense_st);
+	(void)hipFree(dn);
+	if(e != hipSuccess) return (h2g_status)set_err("h2g_index_dense_lsa_check", e);
+	*rows_differ = hn;
+	return H2G_OK;
+}
+
 extern "C" void h2g_index_free(h2g_index* ix) {
 	if(!ix) return;
-	if(ix->dense_st) { (void)hipSetDevice(ix->device); (void)hipStreamSynchronize(ix->dense_st); (void)hipEventDestroy(ix->dense_ev); (void)hipStreamDestroy(ix->dense_st); }
+	if(ix->dense_st) {
+		(void)hipSetDevice(ix->device); (void)hipStreamSynchronize(ix->dense_st);
+		if(ix->dense_ev) (void)hipEventDestroy(ix->dense_ev);
+		if(ix->lsa_ev) (void)hipEventDestroy(ix->lsa_ev);
+		(void)hipStreamDestroy(ix->dense_st);
+	}
 	for(void* p : ix->d_ssdb) if(p) (void)hipFree(p);
 	for(void* p : ix->allocs) (void)hipFree(p);
 	delete ix;
@@ -1807,14 +1947,14 @@ extern "C" h2g_status h2g_ext_search(h2g_stream* s, const h2g_ext_search_query* 
 	HIPCHK(hipEventRecord(s->ev[0], s->st));
 	if(!buckets.empty()) {
 		const unsigned grid = (unsigned)(buckets.size() < 256 * 8 ? buckets.size() : 256 * 8);
-		hipLaunchKernelGGL(k_ext_search_lds, dim3(grid), dim3(256), max_stage, s->st, s->ix->dg, s->ix->dls, dreads(s), (const h2g_ext_search_query*)dq, d_olds,
+		hipLaunchKernelGGL(k_ext_search_lds, dim3(grid), dim3(256), max_stage, s->st, s->ix->dg, dls_now(s->ix), dreads(s), (const h2g_ext_search_query*)dq, d_olds,
 		                   (const uint2*)dbk, (uint32_t)buckets.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
 	}
 	HIPCHK(hipEventRecord(s->ev[1], s->st));
 	if(!o_hbm.empty()) {
-		if(graph) hipLaunchKernelGGL((k_ext_search_hbm<true>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, s->ix->dls, dreads(s),
+		if(graph) hipLaunchKernelGGL((k_ext_search_hbm<true>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, dls_now(s->ix), dreads(s),
 		                             (const h2g_ext_search_query*)dq, d_ohbm, o_hbm.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
-		else hipLaunchKernelGGL((k_ext_search_hbm<false>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, s->ix->dls, dreads(s),
+		else hipLaunchKernelGGL((k_ext_search_hbm<false>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, dls_now(s->ix), dreads(s),
 		                        (const h2g_ext_search_query*)dq, d_ohbm, o_hbm.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
 	}
 	HIPCHK(hipEventRecord(s->ev[9], s->st));
@@ -2473,7 +2613,7 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	const BatchCtx& b = s->cur();
 	GoArgs& A = r->A;
 	memset(&A, 0, sizeof A);
-	A.g = dg_now(s->ix); A.ref = s->ix->dr; A.ls = s->ix->dls; A.alts = s->ix->dalts;
+	A.g = dg_now(s->ix); A.ref = s->ix->dr; A.ls = dls_now(s->ix); A.alts = s->ix->dalts;
 	if(p->max_alts_tried) A.alts.maxAltsTried = p->max_alts_tried;          // --max-altstried
 	if(p->use_haplotype && !g.linear && A.alts.n) A.alts.has_splice |= 2u;   // --haplotype: the table behind the ALTs is read (h2g_graph.h haps_of)
 	A.rd1 = dreads(s); A.rd2 = A.rd1;

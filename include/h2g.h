@@ -72,6 +72,13 @@ H2G_EXPORT void       h2g_index_free(h2g_index*);
  * h2g_index_dense_sa_check waits for the build; *state = 1 when the index has a complete table (else 0), and with rows_differ != NULL every
  * row is walked on the device and the rows whose entry differs from the walk are counted (0 = the table is right). */
 H2G_EXPORT h2g_status h2g_index_dense_sa_check(h2g_index*, uint32_t* state, uint64_t* rows_differ);
+/* The dense table of LOCAL rows of a linear index: the joined offset (low 16 bits) and the LF steps of the walk (high 16 bits) for every row of every
+ * local index, 4 bytes per row (about 1.02 rows per base: 1.05 GB for 256 Mbp, 12.6 GB at GRCh38 size), built behind the global table's build on the
+ * same stream.  Either table is used from the moment its own build is over; results and work counters are the same with and without it.
+ * Environment H2G_DENSE_LSA, read by h2g_index_load: 0 no table; 1 build it behind the load when it takes at most a quarter of the device memory
+ * that is free once the global table is allocated; 2 the same, and the load returns when it is complete; unset: whatever H2G_DENSE_SA resolves to.
+ * h2g_index_dense_lsa_check is h2g_index_dense_sa_check for this table. */
+H2G_EXPORT h2g_status h2g_index_dense_lsa_check(h2g_index*, uint32_t* state, uint64_t* rows_differ);
 /* Splice sites for spliced alignment (SpliceSiteDB, splice_site.h:470): what --known-splicesite-infile / --novel-splicesite-infile
  * hand the reference (SpliceSiteDB::read splice_site.cpp:727: text name, left = last base of the upstream exon, right = first
  * base of the downstream exon, both 0-based, strand).  go() joins reads through them (spliced_aligner.h:409-676, 685-811,
