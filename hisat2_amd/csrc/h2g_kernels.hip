@@ -2482,6 +2482,12 @@ static int go_check(h2g_stream* s, const h2g_align_params* p, bool paired) {
 	if(!s->cur().has_names || (paired && !s->cur().has_mates)) { snprintf(g_err, sizeof g_err, "align: read names (h2g_set_read_names)%s not set", paired ? " / mates (h2g_set_mates)" : ""); return H2G_ERR_ARG; }
 	if(paired && s->cur().has_seeds && !s->cur().has_seeds2) { snprintf(g_err, sizeof g_err, "align: explicit seeds without mate 2's (h2g_set_read_seeds seeds2)"); return H2G_ERR_ARG; }
 	if(p->n_ceil_type < 1 || p->n_ceil_type > 4) { snprintf(g_err, sizeof g_err, "align: n_ceil_type %u (1 C, 2 L, 3 S, 4 G)", p->n_ceil_type); return H2G_ERR_ARG; }
+	// the scoring fields go() divides by (sc_min: the trimming bound; mm_max: maxmm and the pair bound) or counts down with (max_gaps: a gap
+	// extension below 1 never ends it).  A division by zero does not trap on the device: the run would go on with an undefined quotient
+	if(p->sc_min < 1) { snprintf(g_err, sizeof g_err, "align: sc_min %d (--sp): the soft-clipping penalty must be at least 1", p->sc_min); return H2G_ERR_ARG; }
+	if(p->mm_max < 1) { snprintf(g_err, sizeof g_err, "align: mm_max %d (--mp): the maximum mismatch penalty must be at least 1", p->mm_max); return H2G_ERR_ARG; }
+	if(p->mm_max < p->mm_min) { snprintf(g_err, sizeof g_err, "align: mm_max %d is less than mm_min %d (--mp)", p->mm_max, p->mm_min); return H2G_ERR_ARG; }
+	if(p->rdg_linear < 1 || p->rfg_linear < 1) { snprintf(g_err, sizeof g_err, "align: rdg_linear %d / rfg_linear %d (--rdg, --rfg): a gap extension penalty must be at least 1", p->rdg_linear, p->rfg_linear); return H2G_ERR_ARG; }
 	if(!p->no_spliced_alignment) {
 		// spliced alignment: combineWith places introns (hi_aligner.h:1588-1739) and every read is independent when novel splice
 		// sites are not shared (--no-temp-splicesite); the shared SpliceSiteDB of the default mode and graph indexes are not built

@@ -92,12 +92,27 @@ extern "C" h2g_status h2g_align_params_apply_options(h2g_align_params* p, h2g_al
 			break;
 		}
 		case O_SECONDARY: P.secondary = 1; break;
-		case O_MP: two(v, &P.mm_max, &P.mm_min); saw_mp = true; break;
-		case O_SP: { int32_t unused = 0; two(v, &P.sc_max, &unused); P.sc_min = P.sc_max; break; }   // both read from the first number (aligner_seed_policy.cpp:438)
+		case O_MP:
+			// refused where the option is read, whatever --ignore-quals does later (aligner_seed_policy.cpp:411-416; the message ends without its bracket).
+			// The maximum is a divisor of go() (maxmm, the pair bound): below 1 the reference itself dies of SIGFPE (--mp 0,0), so that refusal is ours
+			two(v, &P.mm_max, &P.mm_min); saw_mp = true;
+			if(P.mm_min > P.mm_max) return fail(err, err_cap, "Error: Maximum mismatch penalty (%d) is less than minimum penalty (%d", P.mm_max, P.mm_min);
+			if(P.mm_max < 1) return fail(err, err_cap, "--mp: the maximum mismatch penalty must be at least 1 (got %d)", P.mm_max);
+			break;
+		case O_SP: {   // both read from the first number (aligner_seed_policy.cpp:438); the minimum is a divisor of the trimming bound (:446-449)
+			int32_t unused = 0; two(v, &P.sc_max, &unused); P.sc_min = P.sc_max;
+			if(P.sc_min < 1) return fail(err, err_cap, "min (%d) should be greater than 0", P.sc_min);
+			break;
+		}
 		case O_NO_SOFTCLIP: P.sc_max = P.sc_min = INT32_MAX; break;
 		case O_NP: P.n_pen = atoi(v); break;
-		case O_RDG: two(v, &P.rdg_const, &P.rdg_linear); break;
-		case O_RFG: two(v, &P.rfg_const, &P.rfg_linear); break;
+		// a gap extension below 1 never ends Scoring::maxReadGaps / maxRefGaps (scoring.cpp:53, :84: the reference hangs; max_gaps here would): refused by name
+		case O_RDG: case O_RFG: {
+			const bool rd = opt->op == O_RDG;
+			two(v, rd ? &P.rdg_const : &P.rfg_const, rd ? &P.rdg_linear : &P.rfg_linear);
+			if((rd ? P.rdg_linear : P.rfg_linear) < 1) return fail(err, err_cap, "%s: the gap extension penalty must be at least 1 (got %d)", o, rd ? P.rdg_linear : P.rfg_linear);
+			break;
+		}
 		case O_SCORE_MIN: {
 			P.score_min_type = func_letter(v);
 			if(!P.score_min_type) return fail(err, err_cap, "Error: bad function type in --score-min %s", v);

@@ -11,8 +11,8 @@ BAIL_REASONS = ["none", "input", "longpool", "subsample", "coords", "nghits", "e
                 "redundant", "mate", "npairs", "partial", "straddle", "other", "indel", "tail", "iedges", "gwalk"]    # == h2g_fast.h FB_* (FB_COUNT entries: tests/test_fast_path_cpu.py checks it)
 
 
-def fast_check(base, reads1, reads2=None, names=None, quals=None, options=(), variant=""):
-    """-> dict(completed, mismatching, bails {reason: n}, bad [read ids], done flags)"""
+def fast_check(base, reads1, reads2=None, names=None, quals=None, options=(), variant="", quals2=None):
+    """-> dict(completed, mismatching, bails {reason: n}, bad [read ids], done flags); quals / quals2: flat phred+33 bytes of reads1 / reads2 (FASTQ)"""
     e = Emu(base, variant)
     if options:
         from h2gemu_align import set_options
@@ -32,6 +32,11 @@ def fast_check(base, reads1, reads2=None, names=None, quals=None, options=(), va
     if reads2 is not None:
         c2 = np.concatenate([np.concatenate(reads2).astype(np.uint8), np.zeros(8, np.uint8)])
         o2 = np.concatenate([[0], np.cumsum([len(r) for r in reads2])]).astype(np.uint32)
+        if quals2 is not None:
+            q2b = np.ascontiguousarray(quals2, dtype=np.uint8)
+            assert q2b.size == c2.size - 8
+            e.L.h2gemu_set_mate_quals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            e.L.h2gemu_set_mate_quals(e.h, q2b.ctypes.data, q2b.size)
         e.L.h2gemu_fast_check(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data)
     else:
         e.L.h2gemu_fast_check(e.h, None, None, nb, noffs.ctypes.data, None, None, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data)

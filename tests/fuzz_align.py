@@ -18,13 +18,14 @@ REF = os.path.join(ROOT, "oracle", "_ref")
 
 
 def run_case(seed, nreads=0, rdlen=0, sub=0.0, indel=0.0, nrate=0.0, lens=(300000, 120000, 60000), repeats=6, gaps=2, verbose=8, extra=(), backend=None, bowtie2_dp=0, snps=0, fastq=False,
-             genome=None, reads=None, variants=None, info=None, spliced=False):
+             genome=None, reads=None, variants=None, info=None, spliced=False, quals=None, ref_timeout=None, base=None):
     """genome = (records, names) with reads = a list of read arrays (any lengths): a prepared case instead of lens= / nreads= / rdlen=; variants = a
     synth.write_snps list for a graph index of the prepared genome.  info: a dict that receives the reference's records ("want"), the @SQ names
     ("refnames"), the counts ("bad", "overflow", "aligned") of the run and the ids of the reads with an overflow bit ("flagged").  spliced (prepared cases): spliced alignment, every read on its own
-    (--no-temp-splicesite), instead of --no-spliced-alignment."""
+    (--no-temp-splicesite), instead of --no-spliced-alignment.  quals (prepared cases): flat phred+33 bytes over the reads' offsets in place of the seeded ones of fastq=True;
+    ref_timeout: seconds the reference process may take (subprocess.TimeoutExpired beyond them); base (prepared cases): the genome's index, already built."""
     if genome is not None:
-        return _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced)
+        return _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq or quals is not None, info, spliced, quals, ref_timeout, base)
     tmp = tempfile.mkdtemp(prefix="h2fuzz")
     contigs = synth.make_genome(list(lens), seed, n_gaps=gaps, gap_len=300, repeats=repeats, repeat_len=500)
     fa = os.path.join(tmp, "g.fa")
@@ -55,21 +56,21 @@ def run_case(seed, nreads=0, rdlen=0, sub=0.0, indel=0.0, nrate=0.0, lens=(30000
     return _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, f"n {nreads} len {rdlen} sub {sub} indel {indel} N {nrate}")
 
 
-def _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced):
+def _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie2_dp, fastq, info, spliced, quals=None, ref_timeout=None, base=None):
     import numpy as np
     tmp = tempfile.mkdtemp(prefix="h2fuzz")
     records, names = genome
     fa = os.path.join(tmp, "g.fa")
     synth.write_fasta(fa, records, names=names)
-    base = os.path.join(tmp, "g")
     snp = []
     if variants:
         synth.write_snps(os.path.join(tmp, "g.snp"), variants)
         snp = ["--snp", os.path.join(tmp, "g.snp")]
-    subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q"] + snp + [fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    if base is None:                    # (base: the index of this genome, built by the caller once for many cases)
+        base = os.path.join(tmp, "g")
+        subprocess.run([os.path.join(REF, "hisat2-build-s"), "-q"] + snp + [fa, base], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
-    quals = None
-    if fastq:
+    if fastq and quals is None:
         rng = np.random.default_rng(seed + 9)
         quals = (33 + rng.choice(np.array([2, 8, 15, 20, 25, 30, 37, 40], dtype=np.uint8), size=sum(len(r) for r in reads))).astype(np.uint8)
     rfa = os.path.join(tmp, "r.fq" if fastq else "r.fa")
@@ -79,14 +80,14 @@ def _run_prepared(seed, genome, reads, variants, verbose, extra, backend, bowtie
             s = synth._ALPHA[r].tobytes()
             f.write((b"@%d\n" % i + s + b"\n+\n" + quals[off:off + len(r)].tobytes() + b"\n") if fastq else (b">%d\n" % i + s + b"\n"))
             off += len(r)
-    return _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, f"prepared n {len(reads)}", spliced)
+    return _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, f"prepared n {len(reads)}", spliced, ref_timeout)
 
 
-def _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, what, spliced=False):
+def _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie2_dp, fastq, info, what, spliced=False, ref_timeout=None):
     nreads = len(reads)
     sam = os.path.join(tmp, "ref.sam")
     subprocess.run([os.path.join(REF, "hisat2-align-s"), "-q" if fastq else "-f", "-p", "1", "--no-temp-splicesite" if spliced else "--no-spliced-alignment", "-x", base, "-U", rfa, "-S", sam] + list(extra),
-                   check=True, stdout=subprocess.DEVNULL, stderr=open(os.path.join(tmp, "ref.err"), "w"))
+                   check=True, stdout=subprocess.DEVNULL, stderr=open(os.path.join(tmp, "ref.err"), "w"), timeout=ref_timeout)
     refnames, want = SU.parse_sam(sam)
     qnames = [str(i) for i in range(nreads)]
     if backend is None:
@@ -118,7 +119,8 @@ def _compare(seed, tmp, base, rfa, reads, quals, verbose, extra, backend, bowtie
     naln = sum(1 for q in qnames if want[q][0][0] != 4)
     print(f"seed {seed} {what}: aligned(ref) {naln}  mismatching {bad} (set-level {setbad})  overflow {ovf}  max depth {maxdep}  tmp {tmp}")
     if info is not None:
-        info.update(want=want, got=got, refnames=refnames, bad=bad, overflow=ovf, aligned=naln, base=base, tmp=tmp, flagged=[i for i in range(nreads) if outs[i].overflow])
+        info.update(want=want, got=got, refnames=refnames, bad=bad, overflow=ovf, aligned=naln, base=base, tmp=tmp, flagged=[i for i in range(nreads) if outs[i].overflow],
+                    ref_err=open(os.path.join(tmp, "ref.err")).read())
     return bad, tmp
 
 

@@ -133,6 +133,29 @@ REFUSALS = [
     ("--pen-canintronlen x,1", "Error: bad function type in --pen-canintronlen x,1"),
     ("--pen-noncanintronlen 3", "Error: bad function type in --pen-noncanintronlen 3"),
 ]
+SCORING_REFUSALS = [
+    # penalties go() divides by: the soft-clipping minimum (aligner_seed_policy.cpp:446) and the mismatch maximum (:411, checked where --mp is read: the
+    # reference's line ends without its bracket)
+    ("--sp 0", "min (0) should be greater than 0"),
+    ("--sp 0,0", "min (0) should be greater than 0"),
+    ("--sp -2,5", "min (-2) should be greater than 0"),
+    ("--mp 0", "Error: Maximum mismatch penalty (0) is less than minimum penalty (2"),
+    ("--mp 1", "Error: Maximum mismatch penalty (1) is less than minimum penalty (2"),
+    ("--mp 1,3", "Error: Maximum mismatch penalty (1) is less than minimum penalty (3"),
+    ("--ignore-quals --mp 1,3", "Error: Maximum mismatch penalty (1) is less than minimum penalty (3"),
+    ("--mp 1,3 --ignore-quals", "Error: Maximum mismatch penalty (1) is less than minimum penalty (3"),
+    # values the reference itself dies of (--mp 0,0: SIGFPE) or hangs on (a gap extension of 0 never ends Scoring::maxReadGaps): refusals of our own
+    ("--mp 0,0", "--mp: the maximum mismatch penalty must be at least 1 (got 0)"),
+    ("--mp -1,-3", "--mp: the maximum mismatch penalty must be at least 1 (got -1)"),
+    ("--rdg 0,0", "--rdg: the gap extension penalty must be at least 1 (got 0)"),
+    ("--rdg 5,0", "--rdg: the gap extension penalty must be at least 1 (got 0)"),
+    ("--rfg 5,0", "--rfg: the gap extension penalty must be at least 1 (got 0)"),
+    ("--rfg 2,-1", "--rfg: the gap extension penalty must be at least 1 (got -1)"),
+]
+REFUSALS += SCORING_REFUSALS
+# the rows above whose text is our own: the reference gives no first line to equal (it crashes or hangs)
+OWN_REFUSALS = {"--mp 0,0", "--mp -1,-3", "--rdg 0,0", "--rdg 5,0", "--rfg 5,0", "--rfg 2,-1"}
+REF_ALIGN = os.path.join(ROOT, "oracle", "_ref", "hisat2-align-s")
 
 ARITY = {"-k": 1, "--max-seeds": 1, "--secondary": 0, "--mp": 1, "--sp": 1, "--no-softclip": 0, "--np": 1, "--rdg": 1, "--rfg": 1, "--score-min": 1,
          "--n-ceil": 1, "--min-intronlen": 1, "--max-intronlen": 1, "--pen-cansplice": 1, "--pen-noncansplice": 1, "--pen-conflictsplice": 1,
@@ -225,3 +248,27 @@ def test_command_line_refuses_before_it_needs_a_device(tmp_path, line, msg):
                        capture_output=True, text=True)
     assert p.returncode == 1
     assert p.stderr.splitlines()[0] == msg
+
+
+@pytest.mark.skipif(not os.path.exists(REF_ALIGN), reason="needs oracle/_ref")
+@pytest.mark.parametrize("line,msg", [r for r in SCORING_REFUSALS if r[0] not in OWN_REFUSALS], ids=[r[0] for r in SCORING_REFUSALS if r[0] not in OWN_REFUSALS])
+def test_scoring_refusals_are_the_reference_binarys(tmp_path, line, msg):
+    """the text of the scoring refusals is the live reference's first stderr line, and it exits with 1 as well (it reads its options before it looks for the index)"""
+    r = tmp_path / "r.fa"
+    r.write_text(">0\nACGTACGTACGTACGTACGTACGTACGTACGTACGT\n")
+    p = subprocess.run([REF_ALIGN, "-f", "-x", str(tmp_path / "no_such_index"), "-U", str(r)] + line.split() + ["-S", str(tmp_path / "o.sam")],
+                       capture_output=True, text=True, timeout=60)
+    assert p.returncode == 1
+    assert p.stderr.splitlines()[0] == msg
+
+
+def test_a_block_that_cannot_run_is_not_mended_by_the_parser():
+    """the refusals look at what an option leaves behind: --ignore-quals alone sets mm_min = mm_max and passes; a --mp that leaves the block's minimum above its maximum does not"""
+    p = command_line_block()
+    p.mm_min = 5
+    with pytest.raises(ValueError) as e:
+        p.apply_options(["--mp", "4"], linear=True)
+    assert str(e.value) == "Error: Maximum mismatch penalty (4) is less than minimum penalty (5"
+    p = command_line_block()
+    assert p.apply_options(["--ignore-quals", "--mp", "1,1", "--sp", "1", "--rdg", "0,1", "--rfg", "0,1"], linear=True) == []
+    assert (p.mm_max, p.mm_min, p.sc_min, p.sc_max, p.rdg_linear, p.rfg_linear) == (1, 1, 1, 1, 1, 1)
