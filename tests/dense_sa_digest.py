@@ -1,14 +1,13 @@
 """Digests of go() over a batch around the moment the dense SA table of the index becomes usable, one JSON line (tests/test_gpu_dense_sa.py; H2G_DENSE_SA is
 read when the index is loaded).  Runs are queued straight after the load — on whichever side of the switch each falls — fetched, then the build is
 waited for (h2g_stream_sync, h2g_index_dense_sa_check) and the runs are repeated.  usage: dense_sa_digest.py index_base reads.npz"""
-import hashlib
 import json
 import sys
 
 import numpy as np
 
 from hisat2_amd import api, synth
-from fast_digest import aln_bytes
+from fast_digest import pairs_digest, run_counters
 
 
 def main():
@@ -26,11 +25,9 @@ def main():
     out = {"sha": [], "fast": [], "aligned": [], "device_bytes": int(ix.info.device_bytes)}
 
     def fetch():
-        res, a1, f1, a2, f2 = st.align_pairs_fetch_dense()
-        h = hashlib.sha256()
-        h.update(bytes(res)); h.update(f1.tobytes()); h.update(f2.tobytes()); h.update(aln_bytes(a1, int(f1[n]))); h.update(aln_bytes(a2, int(f2[n])))
-        c = st.counters()
-        out["sha"].append(h.hexdigest()); out["fast"].append(int(c.n_fast)); out["aligned"].append(int(c.n_aligned))
+        out["sha"].append(pairs_digest(st, n)[0])
+        c = run_counters(st)
+        out["fast"].append(c["fast"]); out["aligned"].append(c["aligned"])
 
     for rep in range(4):                                          # each run fetched on its own: any of them may be the first with the table
         st.align_pairs_run(p)

@@ -4,6 +4,7 @@
 // also compiled here with g++ and driven item-by-item, to check the kernel logic against the golden vectors in
 // `-m "not gpu"` runs.  This library lives under tests/, is never shipped with or loaded by hisat2_amd, and
 // is not a fallback: libh2g.so has no host execution path.
+#include <memory>
 #include <vector>
 #include <stdlib.h>
 #include <string.h>
@@ -336,111 +337,80 @@ void h2gemu_set_splice_sites(Emu* e, const h2g_splice_site* sites, size_t n, uin
 	e->dssdb.n = (uint32_t)e->hssdb.fw.size(); e->dssdb.window = window;
 }
 
-void h2gemu_align(Emu* e, uint32_t no_spliced, const char* names, const uint32_t* name_offs, ReadOut* outs, AlnRec* recs) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, no_spliced, &P, &C);
-	AlignWS* ws = new AlignWS();
+}  // extern "C"
+
+// ---- One host lane of the general machine and one of the fast pass, for read i of the batch: what the entry points below drive, and the harnesses
+// that #include this file (tests/emul_spl, tests/dense_sa, tests/dense_lsa).
+static const char* mate_quals(Emu* e) { return e->quals2.empty() ? nullptr : e->quals2.data(); }      // h2gemu_set_mate_quals; nullptr = 'I'
+
+struct MachLane {
+	AlnParams P; AlnCtx C;                                    // (C points at P: a lane is not copied)
+	std::unique_ptr<AlignWS> ws;
 	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	MachOut O; O.rout = outs; O.aln = nullptr; O.aln_slots = 0; O.pout = nullptr; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = 0;
-	for(uint32_t i = 0; i < M.rd[0].n; i++) {
-		M.name[0] = names + name_offs[i]; M.namelen[0] = name_offs[i + 1] - name_offs[i];
-		M.name[1] = nullptr; M.namelen[1] = 0;
-		if(getenv("H2GEMU_POISON")) memset((void*)ws, atoi(getenv("H2GEMU_POISON")), sizeof *ws);   // stale-state hunting: nothing may be read before it is written
-		mach_run_single(C, M, i, false, O);
-		for(uint32_t k = 0; k < ws->m[0].nres; k++) if(k < EMU_REC_STRIDE) recs[(size_t)i * EMU_REC_STRIDE + k] = ws->m[0].res[k];
+	// codes2 == nullptr: unpaired (both read sets are the emulator's); quals2: the second mates' qualities or nullptr
+	MachLane(Emu* e, uint32_t no_spliced, const uint8_t* codes2 = nullptr, const uint32_t* offs2 = nullptr, const char* quals2 = nullptr) : ws(new AlignWS()) {
+		emu_ctx(e, no_spliced, &P, &C);
+		M.ws = ws.get(); M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
+		if(codes2) { M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = quals2; }
 	}
-	delete ws;
-}
-
-
-// go() with the result rows of the C ABI (h2g_align_fetch's layout: `slots` h2g_alnres per read, the selected alignments in order) and the long-edit
-// area (MachOut::ledits): the path a record with more than H2G_MAX_EDITS edits takes out of the large-workspace units.  *ledits_used = edits written.
-void h2gemu_align_abi(Emu* e, uint32_t no_spliced, const char* names, const uint32_t* name_offs, ReadOut* outs, h2g_alnres* rows, uint32_t slots,
-                      h2g_edit* ledits, uint32_t ledits_cap, uint32_t* ledits_used) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, no_spliced, &P, &C);
-	AlignWS* ws = new AlignWS();
-	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	uint32_t cursor = 0;
-	MachOut O; O.rout = outs; O.aln = rows; O.aln_slots = slots; O.pout = nullptr; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = 0;
-	O.ledits = ledits; O.ledits_cursor = &cursor; O.ledits_cap = ledits_cap;
-	for(uint32_t i = 0; i < M.rd[0].n; i++) {
-		M.name[0] = names + name_offs[i]; M.namelen[0] = name_offs[i + 1] - name_offs[i];
-		M.name[1] = nullptr; M.namelen[1] = 0;
-		mach_run_single(C, M, i, false, O);
-	}
-	*ledits_used = cursor;
-	delete ws;
-}
-uint32_t h2gemu_ghit_edits() { return H2G_GHIT_EDITS; }
-
-// paired go(): mate 2 passed separately; names1/names2 as in the FASTA files
-void h2gemu_align_pairs(Emu* e, uint32_t no_spliced, const uint8_t* codes2, const uint32_t* offs2, const char* names1,
-                        const uint32_t* noffs1, const char* names2, const uint32_t* noffs2, PairOut* outs, AlnRec* recs1, AlnRec* recs2) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, no_spliced, &P, &C);
-	AlignWS* ws = new AlignWS();
-	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = e->quals2.empty() ? nullptr : e->quals2.data();
-	MachOut O; O.rout = nullptr; O.aln = nullptr; O.pout = outs; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = EMU_REC_STRIDE;
-	for(uint32_t i = 0; i < M.rd[0].n; i++) {
+	MachLane(const MachLane&) = delete;
+	uint32_t n() const { return M.rd[0].n; }
+	void name(uint32_t i, const char* names1, const uint32_t* noffs1, const char* names2 = nullptr, const uint32_t* noffs2 = nullptr) {
 		M.name[0] = names1 + noffs1[i]; M.namelen[0] = noffs1[i + 1] - noffs1[i];
-		M.name[1] = names2 + noffs2[i]; M.namelen[1] = noffs2[i + 1] - noffs2[i];
-		if(getenv("H2GEMU_POISON")) memset((void*)ws, atoi(getenv("H2GEMU_POISON")), sizeof *ws);
-		mach_run_single(C, M, i, true, O);
-		for(uint32_t k = 0; k < ws->m[0].nres; k++) if(k < EMU_REC_STRIDE) recs1[(size_t)i * EMU_REC_STRIDE + k] = ws->m[0].res[k];
-		for(uint32_t k = 0; k < ws->m[1].nres; k++) if(k < EMU_REC_STRIDE) recs2[(size_t)i * EMU_REC_STRIDE + k] = ws->m[1].res[k];
+		M.name[1] = names2 ? names2 + noffs2[i] : nullptr; M.namelen[1] = names2 ? noffs2[i + 1] - noffs2[i] : 0;
 	}
-	delete ws;
-}
-
-
-static bool rec_equal(const h2g_alnres& a, const AlnRec& b);
-// paired go() with `slots` record rows per mate and an overflow area of `ovf_cap` records (MachOut::ovf): every pair's records, read the way
-// the dense fetch reads them (PairOut::pad -> its block, mate 2 behind mate 1; else its rows), must equal the workspace's lists.
-// stats[0] pairs kept in the area, [1] pairs with a wrong record, [2] pairs flagged (area full), [3] records the area holds at the end
-void h2gemu_pairs_overflow_check(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1,
-                                 const char* names2, const uint32_t* noffs2, uint32_t slots, uint32_t ovf_cap, uint64_t* stats) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, 1, &P, &C);
-	AlignWS* ws = new AlignWS();
-	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = nullptr;
-	const uint32_t n = M.rd[0].n;
-	std::vector<PairOut> outs(n);
-	std::vector<h2g_alnres> r1((size_t)n * slots), r2((size_t)n * slots), area(ovf_cap ? ovf_cap : 1);
-	uint32_t cursor = 0;
-	MachOut O; O.rout = nullptr; O.aln = nullptr; O.aln_slots = 0; O.pout = outs.data(); O.paln[0] = r1.data(); O.paln[1] = r2.data(); O.pair_slots = slots;
-	O.ovf = area.data(); O.ovf_cursor = &cursor; O.ovf_cap = ovf_cap;
-	stats[0] = stats[1] = stats[2] = stats[3] = 0;
-	for(uint32_t i = 0; i < n; i++) {
-		M.name[0] = names1 + noffs1[i]; M.namelen[0] = noffs1[i + 1] - noffs1[i];
-		M.name[1] = names2 + noffs2[i]; M.namelen[1] = noffs2[i + 1] - noffs2[i];
-		mach_run_single(C, M, i, true, O);
-		const PairOut& o = outs[i];
-		const bool big = o.nres[0] > slots || o.nres[1] > slots;
-		bool bad = (o.pad != 0 || (o.overflow & 4)) != big || (o.pad != 0 && (o.overflow & 4));
-		stats[0] += o.pad != 0; stats[2] += (o.overflow & 4) != 0;
-		for(int m = 0; m < 2 && !bad; m++) {
-			const h2g_alnres* a = o.pad ? area.data() + (o.pad - 1) + (m ? o.nres[0] : 0) : (m ? r2.data() : r1.data()) + (size_t)i * slots;
-			const uint32_t c = o.pad ? o.nres[m] : (o.nres[m] < slots ? o.nres[m] : slots);
-			if(o.nres[m] != ws->m[m].nres) bad = true;
-			for(uint32_t k = 0; k < c && !bad; k++) bad = !rec_equal(a[k], ws->m[m].res[k]);
-		}
-		stats[1] += bad;
+	// The machine writes read i's result to pout[i] / rout[i] and to the rows from i * slots on: the device's layout, arrays over the whole batch.  A harness that
+	// wants it in ONE local record hands over arrays that start i elements before that record; the machine touches no other element of them.
+	static MachOut single(uint32_t i, uint32_t slots, bool paired, PairOut& po, ReadOut& ro, h2g_alnres* rows1, h2g_alnres* rows2) {
+		MachOut O{};
+		if(paired) { O.pout = &po - i; O.paln[0] = rows1 - (size_t)i * slots; O.paln[1] = rows2 - (size_t)i * slots; O.pair_slots = slots; }
+		else { O.rout = &ro - i; O.aln = rows1 - (size_t)i * slots; O.aln_slots = slots; }
+		return O;
 	}
-	stats[3] = cursor;
-	delete ws;
-}
+	void poison() { if(const char* v = getenv("H2GEMU_POISON")) memset((void*)ws.get(), atoi(v), sizeof(AlignWS)); }   // stale-state hunting: nothing may be read before it is written
+	void run(uint32_t i, bool paired, const MachOut& O) { mach_run_single(C, M, i, paired, O); }
+	// mate m's records of the read just run, into the caller's array of EMU_REC_STRIDE records per read
+	void copy_recs(int m, AlnRec* dst) const { for(uint32_t k = 0; k < ws->m[m].nres && k < EMU_REC_STRIDE; k++) dst[k] = ws->m[m].res[k]; }
+};
 
+struct FastLane {                                             // shares the machine lane's reads, names and parameters
+	MachLane& ML;
+	FCtx F{};
+	FState S;
+	uint32_t pk[2][H2G_PK_WORDS], words[FW_TOTAL];
+	FWords W;
+	std::vector<int64_t> sc;
+#if FG_GRAPH
+	std::unique_ptr<GraphWS> gws;
+#endif
+	FastLane(Emu* e, MachLane& ml) : ML(ml), sc(2 * H2G_COMBINE_MAXLEN) {
+		F.g = &e->dg; F.ref = &e->dr; F.ls = &e->dls; F.P = &ML.P;
+		F.rd[0] = ML.M.rd[0]; F.rd[1] = ML.M.rd[1];
+		F.pk[0] = pk[0]; F.pk[1] = pk[1]; F.pk_stride = 1;
+		F.sc = sc.data(); F.sc_stride = 1;
+		W.hot = words; W.hot_stride = 1; W.cold = words + FW_HOT;
+#if FG_GRAPH
+		gws.reset(new GraphWS());
+		F.alts = &e->dalts; F.gws = gws.get();
+#endif
+#if FG_SPLICED
+		if(ML.C.ssdb) { F.ssdb = ML.C.ssdb; F.rdid_base = ML.C.rdid_base; }      // a spliced machine lane: the pass looks its sites up in the same database
+#endif
+	}
+	FastLane(const FastLane&) = delete;
+	void out(const MachOut& O) { F.O.rout = O.rout; F.O.aln = O.aln; F.O.aln_slots = O.aln_slots; F.O.pout = O.pout; F.O.paln[0] = O.paln[0]; F.O.paln[1] = O.paln[1]; F.O.pair_slots = O.pair_slots; }
+	// read i (named on the machine lane) packed, the word store and the state poisoned -> fg_pack_read's verdict, fast_begin's packed_ok
+	bool begin(uint32_t i, bool paired) {
+		for(int m = 0; m < 2; m++) { F.name[m] = ML.M.name[m]; F.namelen[m] = ML.M.namelen[m]; }
+		memset(words, 0xa5, sizeof words);
+		memset((void*)&S, 0xa5, sizeof S);
+		bool ok = fg_pack_read(F.rd[0], i, pk[0], 1);
+		if(paired) ok = fg_pack_read(F.rd[1], i, pk[1], 1) && ok;
+		return ok;
+	}
+	bool run(uint32_t i, bool paired) { return fast_run_single(F, S, W, i, paired, begin(i, paired)); }      // true = completed; else S.bail says why
+};
 
-// ---- the fast path (h2g_fast.h) against the general machine: every read / pair of the batch through both; for the ones the
-// fast path completes, its PairOut / ReadOut and records must equal the machine's.  stats[0] completed, [1] mismatching,
-// [2 + why] bails by reason; bad_ids (cap entries) = the first mismatching read ids.  codes2 == nullptr: unpaired.
 static bool rec_equal(const h2g_alnres& a, const AlnRec& b) {
 	if(a.fw != b.fw || a.tidx != b.tidx || a.toff != b.toff || a.len != b.len || a.trim5 != b.trim5 || a.trim3 != b.trim3 || a.nedits != b.nedits ||
 	   a.splicescore != b.splicescore || a.score != b.score) return false;
@@ -450,128 +420,237 @@ static bool rec_equal(const h2g_alnres& a, const AlnRec& b) {
 	}
 	return true;
 }
-void h2gemu_fast_check(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1, const char* names2,
-                       const uint32_t* noffs2, uint64_t* stats, uint32_t* bad_ids, uint32_t cap, uint8_t* done_flags) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, 1, &P, &C);
+static bool rows_equal(const h2g_alnres* a, const AlnRec* b, uint32_t n) {
+	for(uint32_t k = 0; k < n; k++) if(!rec_equal(a[k], b[k])) return false;
+	return true;
+}
+// rows of the C ABI on both sides (what an unpaired run selected): the fields and the first nedits edits
+static bool abi_rows_equal(const h2g_alnres* x, const h2g_alnres* y, uint32_t n) {
+	for(uint32_t k = 0; k < n; k++) {
+		const h2g_alnres &a = x[k], &b = y[k];
+		if(!(a.fw == b.fw && a.tidx == b.tidx && a.toff == b.toff && a.len == b.len && a.trim5 == b.trim5 && a.trim3 == b.trim3 && a.nedits == b.nedits &&
+		     a.splicescore == b.splicescore && a.score == b.score && memcmp(a.edits, b.edits, a.nedits * sizeof(h2g_edit)) == 0)) return false;
+	}
+	return true;
+}
+static bool pairout_equal(const PairOut& a, const PairOut& b) {
+	return a.nres[0] == b.nres[0] && a.nres[1] == b.nres[1] && a.npairs == b.npairs && a.overflow == b.overflow && a.nrank == b.nrank &&
+	       a.nsteps == b.nsteps && a.depth == b.depth && a.nside == b.nside && a.rnd_state == b.rnd_state &&
+	       memcmp(a.pair_i, b.pair_i, sizeof a.pair_i) == 0 && memcmp(a.pair_j, b.pair_j, sizeof a.pair_j) == 0;
+}
+static bool readout_equal(const ReadOut& a, const ReadOut& b) {
+	if(!(a.nres == b.nres && a.nselect == b.nselect && a.overflow == b.overflow && a.nrank == b.nrank && a.nsteps == b.nsteps &&
+	     a.depth == b.depth && a.nside == b.nside && a.best == b.best && a.secbest == b.secbest && a.best_h2 == b.best_h2 &&
+	     a.secbest_h2 == b.secbest_h2)) return false;
+	for(uint32_t k = 0; k < a.nselect; k++) if(a.select[k] != b.select[k]) return false;
+	return true;
+}
+
+static uint64_t fnv(uint64_t h, const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for(size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } return h; }
+// one read's PairOut / ReadOut and both record rows, whole (`slots` records each, written or not).  select[] past nselect is not part of a ReadOut: the
+// machine and the pass both store a local whose tail they never set, so those bytes are whatever their stack held
+static uint64_t row_digest(uint64_t h, bool paired, const PairOut& po, const ReadOut& ro, const h2g_alnres* r1, const h2g_alnres* r2, uint32_t slots) {
+	ReadOut r = ro;
+	for(uint32_t k = r.nselect; k < H2G_SELECT_CAP; k++) r.select[k] = 0;
+	h = paired ? fnv(h, &po, sizeof po) : fnv(h, &r, sizeof r);
+	h = fnv(h, r1, slots * sizeof(h2g_alnres));
+	return fnv(h, r2, slots * sizeof(h2g_alnres));
+}
+// Every read / pair of the batch through the general machine and through the fast pass, one lane at a time, each into zeroed rows: out[0] = hash of the
+// machine's PairOut / ReadOut and record rows, [1] = the same of what the pass completed (and the bail code of what it did not), [2] = reads it completed,
+// [3] = the machine's nsteps summed.  codes2 == nullptr: unpaired; the second mates carry no qualities.  fast(FL, i, paired) -> completed: the harness's own
+// way of running the pass over read i (h2gemu_dense_digest, h2gemu_lsa_digest).
+template <class Fast> static void lanes_digest(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1, const char* names2,
+                                                const uint32_t* noffs2, uint64_t* out, Fast fast) {
 	const bool paired = codes2 != nullptr;
-	AlignWS* ws = new AlignWS();
-	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	if(paired) { M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = e->quals2.empty() ? nullptr : e->quals2.data(); }
-	const uint32_t n = M.rd[0].n, slots = 16;
-	std::vector<PairOut> mp(1), fp(n);
-	std::vector<ReadOut> mr(1), fr(n);
+	MachLane ML(e, 1, codes2, offs2, nullptr);
+	FastLane FL(e, ML);
+	const uint32_t n = ML.n(), slots = 16;
+	std::vector<h2g_alnres> r1(slots), r2(slots);
+	uint64_t hm = 1469598103934665603ull, hf = hm;
+	out[2] = out[3] = 0;
+	for(uint32_t i = 0; i < n; i++) {
+		ML.name(i, names1, noffs1, paired ? names2 : nullptr, noffs2);
+		PairOut po; ReadOut ro;
+		const MachOut O = MachLane::single(i, slots, paired, po, ro, r1.data(), r2.data());
+		auto zero = [&]() {
+			memset((void*)&po, 0, sizeof po); memset((void*)&ro, 0, sizeof ro);
+			memset((void*)r1.data(), 0, slots * sizeof(h2g_alnres)); memset((void*)r2.data(), 0, slots * sizeof(h2g_alnres));
+		};
+		zero();
+		ML.run(i, paired, O);
+		out[3] += paired ? po.nsteps : ro.nsteps;
+		hm = row_digest(hm, paired, po, ro, r1.data(), r2.data(), slots);
+		zero();
+		FL.out(O);
+		if(!fast(FL, i, paired)) { const uint32_t why = FL.S.bail; hf = fnv(hf, &why, sizeof why); continue; }
+		out[2]++;
+		hf = row_digest(hf, paired, po, ro, r1.data(), r2.data(), slots);
+	}
+	out[0] = hm; out[1] = hf;
+}
+
+// ---- the fast pass (h2g_fast.h) against the general machine: every read / pair of the batch through both; for the ones the pass completes, its PairOut /
+// ReadOut and records must equal the machine's.  stats[0] completed, [1] mismatching, [2 + why] bails by reason; bad_ids (cap entries) = the first mismatching
+// read ids; done_flags[i] (may be null) = 1: completed.  codes2 == nullptr: unpaired.
+// wrong_index: this library's pass is built for another kind of index than e's (stats[1] = ~0, nothing is run).  every_read: the machine also runs on what the
+// pass did not complete, and spl_flags[i] (may be null) = 1: the MACHINE's result of read / pair i holds a record with a splice edit.
+static void fast_check_lanes(Emu* e, uint32_t no_spliced, bool wrong_index, bool every_read, const uint8_t* codes2, const uint32_t* offs2, const char* names1,
+                             const uint32_t* noffs1, const char* names2, const uint32_t* noffs2, uint64_t* stats, uint32_t* bad_ids, uint32_t cap,
+                             uint8_t* done_flags, uint8_t* spl_flags) {
+	const bool paired = codes2 != nullptr;
+	MachLane ML(e, no_spliced, codes2, offs2, mate_quals(e));
+	for(int k = 0; k < 2 + (int)FB_COUNT; k++) stats[k] = 0;
+	if(wrong_index) { stats[1] = ~0ull; return; }
+	const uint32_t n = ML.n(), slots = 16;
+	std::vector<PairOut> fp(n);
+	std::vector<ReadOut> fr(n);
 	std::vector<h2g_alnres> f1((size_t)n * slots), f2((size_t)n * slots), m1(slots), m2(slots);
-	FCtx F;
-	F.g = &e->dg; F.ref = &e->dr; F.ls = &e->dls; F.P = &P;
-	F.rd[0] = M.rd[0]; F.rd[1] = M.rd[1];
-	uint32_t pk[2][H2G_PK_WORDS];
-	F.pk[0] = pk[0]; F.pk[1] = pk[1]; F.pk_stride = 1;
-	static int64_t sc_[2 * H2G_COMBINE_MAXLEN];
-	F.sc = sc_; F.sc_stride = 1;
-	for(int k = 0; k < 2 + (int)FB_COUNT; k++) stats[k] = 0;
-	if((e->dg.linear != 0) == (FG_GRAPH != 0)) { stats[1] = ~0ull; delete ws; return; }      // this library's fast path is built for the other kind of index
-#if FG_GRAPH
-	static GraphWS fgws_;
-	F.alts = &e->dalts; F.gws = &fgws_;
-#endif
-	F.O.rout = fr.data(); F.O.aln = f1.data(); F.O.aln_slots = slots; F.O.pout = fp.data(); F.O.paln[0] = f1.data(); F.O.paln[1] = f2.data(); F.O.pair_slots = slots;
-	uint32_t words[FW_TOTAL];
-	FWords W; W.hot = words; W.hot_stride = 1; W.cold = words + FW_HOT;
-	for(int k = 0; k < 2 + (int)FB_COUNT; k++) stats[k] = 0;
+	FastLane FL(e, ML);
+	MachOut FO{};                                              // the pass writes into arrays over the batch, paired and unpaired rows in the same one
+	FO.rout = fr.data(); FO.aln = f1.data(); FO.aln_slots = slots; FO.pout = fp.data(); FO.paln[0] = f1.data(); FO.paln[1] = f2.data(); FO.pair_slots = slots;
+	FL.out(FO);
+	const AlignWS& ws = *ML.ws;
+	auto has_splice = [](const AlnRec& r) { for(uint32_t k = 0; k < r.nedits && k < H2G_GHIT_EDITS; k++) if(r.edits[k].type == H2G_EDIT_SPL) return true; return false; };
 	uint32_t nbad = 0;
 	for(uint32_t i = 0; i < n; i++) {
-		F.name[0] = names1 + noffs1[i]; F.namelen[0] = noffs1[i + 1] - noffs1[i];
-		F.name[1] = paired ? names2 + noffs2[i] : nullptr; F.namelen[1] = paired ? noffs2[i + 1] - noffs2[i] : 0;
-		memset(words, 0xa5, sizeof words);
-		bool ok = fg_pack_read(F.rd[0], i, pk[0], 1);
-		if(paired) ok = fg_pack_read(F.rd[1], i, pk[1], 1) && ok;
-		FState S;
-		memset(&S, 0xa5, sizeof S);
-		const bool done = fast_run_single(F, S, W, i, paired, ok);
+		ML.name(i, names1, noffs1, paired ? names2 : nullptr, noffs2);
+		const bool done = FL.run(i, paired);
 		if(done_flags) done_flags[i] = done ? 1 : 0;
-		if(!done) { stats[2 + (S.bail < FB_COUNT ? S.bail : FB_OTHER)]++; continue; }
-		stats[0]++;
+		if(done) stats[0]++; else stats[2 + (FL.S.bail < FB_COUNT ? FL.S.bail : FB_OTHER)]++;
+		if(!done && !every_read) continue;
 		// the machine on the same read
-		M.name[0] = F.name[0]; M.namelen[0] = F.namelen[0]; M.name[1] = F.name[1]; M.namelen[1] = F.namelen[1];
-		MachOut O; O.rout = nullptr; O.aln = nullptr; O.aln_slots = 0; O.pout = nullptr; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = 0;
-		bool same = true;
-		if(paired) {
-			std::vector<PairOut> tmp(n ? 1 : 1);
-			// the machine writes pout[i]: give it a window that starts at -i
-			PairOut one; O.pout = &one - i; O.paln[0] = m1.data() - (size_t)i * slots; O.paln[1] = m2.data() - (size_t)i * slots; O.pair_slots = slots;
-			mach_run_single(C, M, i, true, O);
-			const PairOut& f = fp[i];
-			same = one.nres[0] == f.nres[0] && one.nres[1] == f.nres[1] && one.npairs == f.npairs && one.overflow == f.overflow && one.nrank == f.nrank &&
-			       one.nsteps == f.nsteps && one.depth == f.depth && one.nside == f.nside && one.rnd_state == f.rnd_state &&
-			       memcmp(one.pair_i, f.pair_i, sizeof one.pair_i) == 0 && memcmp(one.pair_j, f.pair_j, sizeof one.pair_j) == 0;
-			for(uint32_t k = 0; same && k < f.nres[0]; k++) same = rec_equal(f1[(size_t)i * slots + k], ws->m[0].res[k]);
-			for(uint32_t k = 0; same && k < f.nres[1]; k++) same = rec_equal(f2[(size_t)i * slots + k], ws->m[1].res[k]);
-		} else {
-			ReadOut one; O.rout = &one - i; O.aln = m1.data() - (size_t)i * slots; O.aln_slots = slots;
-			mach_run_single(C, M, i, false, O);
-			const ReadOut& f = fr[i];
-			same = one.nres == f.nres && one.nselect == f.nselect && one.overflow == f.overflow && one.nrank == f.nrank && one.nsteps == f.nsteps &&
-			       one.depth == f.depth && one.nside == f.nside && one.best == f.best && one.secbest == f.secbest && one.best_h2 == f.best_h2 &&
-			       one.secbest_h2 == f.secbest_h2;
-			for(uint32_t k = 0; same && k < f.nselect; k++) same = one.select[k] == f.select[k];
-			for(uint32_t k = 0; same && k < f.nselect; k++) {
-				const h2g_alnres &a = f1[(size_t)i * slots + k], &b = m1[k];
-				same = a.fw == b.fw && a.tidx == b.tidx && a.toff == b.toff && a.len == b.len && a.trim5 == b.trim5 && a.trim3 == b.trim3 && a.nedits == b.nedits &&
-				       a.splicescore == b.splicescore && a.score == b.score && memcmp(a.edits, b.edits, a.nedits * sizeof(h2g_edit)) == 0;
-			}
+		PairOut onep; ReadOut oner;
+		ML.run(i, paired, MachLane::single(i, slots, paired, onep, oner, m1.data(), m2.data()));
+		if(spl_flags) {
+			bool spl = false;
+			for(int m = 0; m < (paired ? 2 : 1); m++) for(uint32_t k = 0; k < ws.m[m].nres; k++) spl = spl || has_splice(ws.m[m].res[k]);
+			spl_flags[i] = spl ? 1 : 0;
 		}
-		if(!same) {
-			stats[1]++; if(nbad < cap) bad_ids[nbad++] = i;
-			if(getenv("H2GEMU_FAST_VERBOSE") && paired) {
-				const PairOut& f = fp[i];
-				PairOut one; MachOut O2; O2.rout = nullptr; O2.aln = nullptr; O2.aln_slots = 0; O2.pout = &one - i; O2.paln[0] = m1.data() - (size_t)i * slots; O2.paln[1] = m2.data() - (size_t)i * slots; O2.pair_slots = slots;
-				mach_run_single(C, M, i, true, O2);
-				fprintf(stderr, "pair %u: fast nres %u/%u npairs %u nrank %u nsteps %u depth %u nside %u rnd %08x | machine nres %u/%u npairs %u nrank %u nsteps %u depth %u nside %u rnd %08x\n", i,
-				        f.nres[0], f.nres[1], f.npairs, f.nrank, f.nsteps, f.depth, f.nside, f.rnd_state, one.nres[0], one.nres[1], one.npairs, one.nrank, one.nsteps, one.depth, one.nside, one.rnd_state);
-				for(int m = 0; m < 2; m++) {
-					for(uint32_t k = 0; k < f.nres[m]; k++) { const h2g_alnres& a = (m ? f2 : f1)[(size_t)i * slots + k]; fprintf(stderr, "   fast m%d r%u fw %u toff %u len %u trim %u/%u ned %u score %lld\n", m, k, a.fw, a.toff, a.len, a.trim5, a.trim3, a.nedits, (long long)a.score); }
-					for(uint32_t k = 0; k < one.nres[m]; k++) { const AlnRec& a = ws->m[m].res[k]; fprintf(stderr, "   mach m%d r%u fw %u toff %u len %u trim %u/%u ned %u score %lld\n", m, k, a.fw, a.toff, a.len, a.trim5, a.trim3, a.nedits, (long long)a.score); }
-				}
+		if(!done) continue;
+		const PairOut& f = fp[i];
+		const h2g_alnres *a1 = &f1[(size_t)i * slots], *a2 = &f2[(size_t)i * slots];
+		const bool same = paired ? pairout_equal(onep, f) && rows_equal(a1, ws.m[0].res, f.nres[0]) && rows_equal(a2, ws.m[1].res, f.nres[1])
+		                         : readout_equal(oner, fr[i]) && abi_rows_equal(a1, m1.data(), fr[i].nselect);
+		if(same) continue;
+		stats[1]++; if(nbad < cap) bad_ids[nbad++] = i;
+		if(getenv("H2GEMU_FAST_VERBOSE") && paired) {
+			const PairOut& one = onep;
+			fprintf(stderr, "pair %u: fast nres %u/%u npairs %u nrank %u nsteps %u depth %u nside %u rnd %08x | machine nres %u/%u npairs %u nrank %u nsteps %u depth %u nside %u rnd %08x\n", i,
+			        f.nres[0], f.nres[1], f.npairs, f.nrank, f.nsteps, f.depth, f.nside, f.rnd_state, one.nres[0], one.nres[1], one.npairs, one.nrank, one.nsteps, one.depth, one.nside, one.rnd_state);
+			for(int m = 0; m < 2; m++) {
+				for(uint32_t k = 0; k < f.nres[m]; k++) { const h2g_alnres& a = (m ? a2 : a1)[k]; fprintf(stderr, "   fast m%d r%u fw %u toff %u len %u trim %u/%u ned %u score %lld\n", m, k, a.fw, a.toff, a.len, a.trim5, a.trim3, a.nedits, (long long)a.score); }
+				for(uint32_t k = 0; k < one.nres[m]; k++) { const AlnRec& a = ws.m[m].res[k]; fprintf(stderr, "   mach m%d r%u fw %u toff %u len %u trim %u/%u ned %u score %lld\n", m, k, a.fw, a.toff, a.len, a.trim5, a.trim3, a.nedits, (long long)a.score); }
 			}
 		}
 	}
-	delete ws;
+}
+
+extern "C" {
+
+// HI_Aligner::go + selection for every read of the batch (names: '\0'-free bytes + offsets), one lane of the machine at a time; record k of read i at
+// recs[i * EMU_REC_STRIDE + k], straight from the workspace
+void h2gemu_align(Emu* e, uint32_t no_spliced, const char* names, const uint32_t* name_offs, ReadOut* outs, AlnRec* recs) {
+	MachLane ML(e, no_spliced);
+	MachOut O{}; O.rout = outs;
+	for(uint32_t i = 0; i < ML.n(); i++) {
+		ML.name(i, names, name_offs);
+		ML.poison();
+		ML.run(i, false, O);
+		ML.copy_recs(0, recs + (size_t)i * EMU_REC_STRIDE);
+	}
+}
+
+// go() with the result rows of the C ABI (h2g_align_fetch's layout: `slots` h2g_alnres per read, the selected alignments in order) and the long-edit
+// area (MachOut::ledits): the path a record with more than H2G_MAX_EDITS edits takes out of the large-workspace units.  *ledits_used = edits written.
+void h2gemu_align_abi(Emu* e, uint32_t no_spliced, const char* names, const uint32_t* name_offs, ReadOut* outs, h2g_alnres* rows, uint32_t slots,
+                      h2g_edit* ledits, uint32_t ledits_cap, uint32_t* ledits_used) {
+	MachLane ML(e, no_spliced);
+	uint32_t cursor = 0;
+	MachOut O{}; O.rout = outs; O.aln = rows; O.aln_slots = slots;
+	O.ledits = ledits; O.ledits_cursor = &cursor; O.ledits_cap = ledits_cap;
+	for(uint32_t i = 0; i < ML.n(); i++) {
+		ML.name(i, names, name_offs);
+		ML.run(i, false, O);
+	}
+	*ledits_used = cursor;
+}
+uint32_t h2gemu_ghit_edits() { return H2G_GHIT_EDITS; }
+
+// paired go(): mate 2 passed separately; names1/names2 as in the FASTA files; records as h2gemu_align's, per mate
+void h2gemu_align_pairs(Emu* e, uint32_t no_spliced, const uint8_t* codes2, const uint32_t* offs2, const char* names1,
+                        const uint32_t* noffs1, const char* names2, const uint32_t* noffs2, PairOut* outs, AlnRec* recs1, AlnRec* recs2) {
+	MachLane ML(e, no_spliced, codes2, offs2, mate_quals(e));
+	MachOut O{}; O.pout = outs; O.pair_slots = EMU_REC_STRIDE;
+	for(uint32_t i = 0; i < ML.n(); i++) {
+		ML.name(i, names1, noffs1, names2, noffs2);
+		ML.poison();
+		ML.run(i, true, O);
+		ML.copy_recs(0, recs1 + (size_t)i * EMU_REC_STRIDE);
+		ML.copy_recs(1, recs2 + (size_t)i * EMU_REC_STRIDE);
+	}
+}
+
+// paired go() with `slots` record rows per mate and an overflow area of `ovf_cap` records (MachOut::ovf): every pair's records, read the way
+// the dense fetch reads them (PairOut::pad -> its block, mate 2 behind mate 1; else its rows), must equal the workspace's lists.
+// stats[0] pairs kept in the area, [1] pairs with a wrong record, [2] pairs flagged (area full), [3] records the area holds at the end
+void h2gemu_pairs_overflow_check(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1,
+                                 const char* names2, const uint32_t* noffs2, uint32_t slots, uint32_t ovf_cap, uint64_t* stats) {
+	MachLane ML(e, 1, codes2, offs2, nullptr);
+	const uint32_t n = ML.n();
+	std::vector<PairOut> outs(n);
+	std::vector<h2g_alnres> r1((size_t)n * slots), r2((size_t)n * slots), area(ovf_cap ? ovf_cap : 1);
+	uint32_t cursor = 0;
+	MachOut O{}; O.pout = outs.data(); O.paln[0] = r1.data(); O.paln[1] = r2.data(); O.pair_slots = slots;
+	O.ovf = area.data(); O.ovf_cursor = &cursor; O.ovf_cap = ovf_cap;
+	stats[0] = stats[1] = stats[2] = stats[3] = 0;
+	for(uint32_t i = 0; i < n; i++) {
+		ML.name(i, names1, noffs1, names2, noffs2);
+		ML.run(i, true, O);
+		const PairOut& o = outs[i];
+		const bool big = o.nres[0] > slots || o.nres[1] > slots;
+		bool bad = (o.pad != 0 || (o.overflow & 4)) != big || (o.pad != 0 && (o.overflow & 4));
+		stats[0] += o.pad != 0; stats[2] += (o.overflow & 4) != 0;
+		for(int m = 0; m < 2 && !bad; m++) {
+			const h2g_alnres* a = o.pad ? area.data() + (o.pad - 1) + (m ? o.nres[0] : 0) : (m ? r2.data() : r1.data()) + (size_t)i * slots;
+			const uint32_t c = o.pad ? o.nres[m] : (o.nres[m] < slots ? o.nres[m] : slots);
+			bad = o.nres[m] != ML.ws->m[m].nres || !rows_equal(a, ML.ws->m[m].res, c);
+		}
+		stats[1] += bad;
+	}
+	stats[3] = cursor;
+}
+
+// the fast pass of this library (FG_GRAPH: over a graph index, else over a linear one) against the unspliced machine: fast_check_lanes
+void h2gemu_fast_check(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1, const char* names2,
+                       const uint32_t* noffs2, uint64_t* stats, uint32_t* bad_ids, uint32_t cap, uint8_t* done_flags) {
+	fast_check_lanes(e, 1, (e->dg.linear != 0) == (FG_GRAPH != 0), false, codes2, offs2, names1, noffs1, names2, noffs2, stats, bad_ids, cap, done_flags, nullptr);
 }
 
 // development: trips (primitive requests) of the general machine per read, by primitive — the length of a hard read's latency chain.
 // out[nids * 16]: [op] = requests of that primitive, [15] = control phases (mach_step calls)
 void h2gemu_pair_trips(Emu* e, const uint8_t* codes2, const uint32_t* offs2, const char* names1, const uint32_t* noffs1, const char* names2,
                        const uint32_t* noffs2, const uint32_t* ids, size_t nids, uint32_t* out) {
-	AlnParams P; AlnCtx C;
-	emu_ctx(e, 1, &P, &C);
 	const bool paired = codes2 != nullptr;
-	AlignWS* ws = new AlignWS();
-	Mach M;
-	M.ws = ws; M.rd[0] = e->reads(); M.rd[1] = M.rd[0];
-	if(paired) { M.rd[1].codes = codes2; M.rd[1].offs = offs2; M.rd[1].quals = nullptr; }
+	MachLane ML(e, 1, codes2, offs2, nullptr);
+	Mach& M = ML.M;
 	std::vector<h2g_alnres> m1(64), m2(64);
 	for(size_t k = 0; k < nids; k++) {
 		const uint32_t i = ids[k];
 		uint32_t* o = out + k * 16;
 		for(int j = 0; j < 16; j++) o[j] = 0;
-		M.name[0] = names1 + noffs1[i]; M.namelen[0] = noffs1[i + 1] - noffs1[i];
-		M.name[1] = paired ? names2 + noffs2[i] : nullptr; M.namelen[1] = paired ? noffs2[i + 1] - noffs2[i] : 0;
-		MachOut O; O.rout = nullptr; O.aln = nullptr; O.aln_slots = 0; O.pout = nullptr; O.paln[0] = O.paln[1] = nullptr; O.pair_slots = 0;
+		ML.name(i, names1, noffs1, paired ? names2 : nullptr, noffs2);
 		PairOut onep; ReadOut oner;
-		if(paired) { O.pout = &onep - i; O.paln[0] = m1.data() - (size_t)i * 64; O.paln[1] = m2.data() - (size_t)i * 64; O.pair_slots = 64; }
-		else { O.rout = &oner - i; O.aln = m1.data() - (size_t)i * 64; O.aln_slots = 64; }
+		const MachOut O = MachLane::single(i, 64, paired, onep, oner, m1.data(), m2.data());
 		M.out = &O; M.paired_input = paired;
 		mach_begin(M, i, paired);
 		while(M.L.pc != PC_FINISHED || M.L.op != OP_NONE) {
-			mach_step(C, M);
+			mach_step(ML.C, M);
 			o[15]++;
-			if(M.L.op != OP_NONE) { if(M.L.op < 15) o[M.L.op]++; mach_exec(C, M, M.L.op); }
+			if(M.L.op != OP_NONE) { if(M.L.op < 15) o[M.L.op]++; mach_exec(ML.C, M, M.L.op); }
 		}
 		M.L.pc = PC_IDLE;
 	}
-	delete ws;
 }
 
 // glf1_top_fused (one LF step of one row from sides held in registers) against map_glf1_nochar, and gw_walk_single against gw_resolve,

@@ -1,6 +1,5 @@
 """The fast path of go() (hisat2_amd/csrc/h2g_fast.h) against the general machine, both instantiated on the host (tests/emul):
 every read / pair runs through both; what the fast path completes must equal the machine's result bit for bit."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,58 +10,35 @@ BAIL_REASONS = ["none", "input", "longpool", "subsample", "coords", "nghits", "e
                 "redundant", "mate", "npairs", "partial", "straddle", "other", "indel", "tail", "iedges", "gwalk"]    # == h2g_fast.h FB_* (FB_COUNT entries: tests/test_fast_path_cpu.py checks it)
 
 
-def fast_check(base, reads1, reads2=None, names=None, quals=None, options=(), variant="", quals2=None):
-    """-> dict(completed, mismatching, bails {reason: n}, bad [read ids], done flags); quals / quals2: flat phred+33 bytes of reads1 / reads2 (FASTQ)"""
-    e = Emu(base, variant)
+def fast_check(base, reads1, reads2=None, names=None, quals=None, options=(), variant="", quals2=None, emu=None, spliced=False):
+    """-> dict(completed, mismatching, bails {reason: n}, bad [read ids], done flags); quals / quals2: flat phred+33 bytes of reads1 / reads2 (FASTQ).
+    emu: an emulator to run on (default: a fresh one of `variant` over `base`).  spliced: h2gemu_fast_check_spl (tests/emul_spl), which adds "spl": per read,
+    the machine's result holds a splice edit"""
+    e = Emu(base, variant) if emu is None else emu
     if options:
         from h2gemu_align import set_options
         set_options(e, 0, options)
     n = len(reads1)
-    codes = np.concatenate(reads1).astype(np.uint8)
-    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads1])]).astype(np.uint32)
-    e.set_reads(codes, offs, quals)
-    names = names or [str(i) for i in range(n)]
-    nb = "".join(names).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-    stats = np.zeros(2 + len(BAIL_REASONS) + 2, dtype=np.uint64)
-    bad = np.zeros(64, dtype=np.uint32)
-    done = np.zeros(n, dtype=np.uint8)
-    vp = C.c_void_p
-    e.L.h2gemu_fast_check.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, vp, C.c_uint32, vp]
-    if reads2 is not None:
-        c2 = np.concatenate([np.concatenate(reads2).astype(np.uint8), np.zeros(8, np.uint8)])
-        o2 = np.concatenate([[0], np.cumsum([len(r) for r in reads2])]).astype(np.uint32)
-        if quals2 is not None:
-            q2b = np.ascontiguousarray(quals2, dtype=np.uint8)
-            assert q2b.size == c2.size - 8
-            e.L.h2gemu_set_mate_quals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-            e.L.h2gemu_set_mate_quals(e.h, q2b.ctypes.data, q2b.size)
-        e.L.h2gemu_fast_check(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data)
-    else:
-        e.L.h2gemu_fast_check(e.h, None, None, nb, noffs.ctypes.data, None, None, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data)
+    e.load_reads(reads1, quals)
+    if reads2 is not None and quals2 is not None:
+        assert np.size(quals2) == sum(len(r) for r in reads2)
+        e.set_mate_quals(quals2)
+    stats, bad, done, *spl = e.fast_check(reads2, names, spliced=spliced)
     nbad = int(stats[1])
-    return {"n": n, "completed": int(stats[0]), "mismatching": nbad, "bails": {BAIL_REASONS[k]: int(stats[2 + k]) for k in range(len(BAIL_REASONS)) if stats[2 + k]},
-            "bad": [int(x) for x in bad[:min(nbad, 64)]], "done": done}
+    r = {"n": n, "completed": int(stats[0]), "mismatching": nbad, "bails": {BAIL_REASONS[k]: int(stats[2 + k]) for k in range(len(BAIL_REASONS)) if stats[2 + k]},
+         "bad": [int(x) for x in bad[:min(nbad, 64)]], "done": done}
+    if spliced:
+        r["spl"] = spl[0]
+    return r
 
 
 def pairs_overflow_check(base, reads1, reads2, slots, ovf_cap):
     """paired go() on the host machine with `slots` record rows per mate and an overflow area of ovf_cap records (MachOut::ovf)
     -> dict(in_area, mismatching, flagged, area_records)"""
     e = Emu(base)
-    n = len(reads1)
-    codes = np.concatenate(reads1).astype(np.uint8)
-    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads1])]).astype(np.uint32)
-    e.set_reads(codes, offs, None)
-    names = [str(i) for i in range(n)]
-    nb = "".join(names).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-    c2 = np.concatenate([np.concatenate(reads2).astype(np.uint8), np.zeros(8, np.uint8)])
-    o2 = np.concatenate([[0], np.cumsum([len(r) for r in reads2])]).astype(np.uint32)
-    stats = np.zeros(4, dtype=np.uint64)
-    vp = C.c_void_p
-    e.L.h2gemu_pairs_overflow_check.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, C.c_uint32, C.c_uint32, vp]
-    e.L.h2gemu_pairs_overflow_check(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, slots, ovf_cap, stats.ctypes.data)
-    return {"n": n, "in_area": int(stats[0]), "mismatching": int(stats[1]), "flagged": int(stats[2]), "area_records": int(stats[3])}
+    e.load_reads(reads1)
+    stats = e.pairs_overflow_check(reads2, slots, ovf_cap)
+    return {"n": len(reads1), "in_area": int(stats[0]), "mismatching": int(stats[1]), "flagged": int(stats[2]), "area_records": int(stats[3])}
 
 
 if __name__ == "__main__":

@@ -45,6 +45,32 @@ def aln_bytes(arr, n, st=None, count=None):
     return a.tobytes() + b"".join(lists)
 
 
+def pairs_digest(st, n, long_edits=None):
+    """the paired run's dense results of st's n pairs -> (SHA-256 of headers, both offset arrays, both record arrays; mate-1 records, their number, mate-2
+    records, their number).  long_edits: a one-element list — records beyond 32 edits are hashed with their lists fetched from the stream, and their number is
+    added to it (aln_bytes); None: as their slots stand"""
+    res, a1, f1, a2, f2 = st.align_pairs_fetch_dense()
+    n1, n2 = int(f1[n]), int(f2[n])
+    lst = st if long_edits is not None else None
+    h = hashlib.sha256()
+    h.update(bytes(res)); h.update(f1.tobytes()); h.update(f2.tobytes()); h.update(aln_bytes(a1, n1, lst, long_edits)); h.update(aln_bytes(a2, n2, lst, long_edits))
+    return h.hexdigest(), a1, n1, a2, n2
+
+
+def reads_digest(st, n, long_edits=None):
+    """the unpaired run's dense results of st's n reads -> (SHA-256 of headers, offsets, records; the records, their number); long_edits as pairs_digest's"""
+    res, aln, offs = st.align_fetch_dense()
+    nrec = int(offs[n])
+    h = hashlib.sha256()
+    h.update(res.tobytes()); h.update(offs.tobytes()); h.update(aln_bytes(aln, nrec, st if long_edits is not None else None, long_edits))
+    return h.hexdigest(), aln, nrec
+
+
+def run_counters(st):
+    c = st.counters()
+    return {"fast": int(c.n_fast), "handed_on": int(c.n_fast_bail), "aligned": int(c.n_aligned), "overflow": int(c.n_overflow), "adopted": int(c.n_adopted)}
+
+
 def flat_of(d, key):
     """(codes, offsets) of read set `key` of the npz, stacked or flat"""
     if key in d.files:
@@ -79,23 +105,15 @@ def main():
     assert not rest, rest
     for rep in range(3):                                         # back-to-back runs: the machine passes of earlier runs overlap the later fast passes
         st.align_pairs_run(p)
-    res, a1, f1, a2, f2 = st.align_pairs_fetch_dense()
-    h = hashlib.sha256()
     nlong = [0]
-    h.update(bytes(res)); h.update(f1.tobytes()); h.update(f2.tobytes()); h.update(aln_bytes(a1, int(f1[n]), st, nlong)); h.update(aln_bytes(a2, int(f2[n]), st, nlong))
-    c = st.counters()
-    out["pairs"] = {"sha": h.hexdigest(), "fast": int(c.n_fast), "handed_on": int(c.n_fast_bail), "aligned": int(c.n_aligned), "overflow": int(c.n_overflow), "adopted": int(c.n_adopted)}
+    out["pairs"] = {"sha": pairs_digest(st, n, nlong)[0], **run_counters(st)}
     if extended:
         out["pairs"]["long_edits"] = nlong[0]
     st.set_reads(rc, ro, quals["reads"]); st.set_read_names([str(i) for i in range(nrd)])
     for rep in range(3):
         st.align_run(p)
-    res, aln, offs = st.align_fetch_dense()
-    h = hashlib.sha256()
     nlong = [0]
-    h.update(res.tobytes()); h.update(offs.tobytes()); h.update(aln_bytes(aln, int(offs[nrd]), st, nlong))
-    c = st.counters()
-    out["reads"] = {"sha": h.hexdigest(), "fast": int(c.n_fast), "handed_on": int(c.n_fast_bail), "aligned": int(c.n_aligned), "overflow": int(c.n_overflow), "adopted": int(c.n_adopted)}
+    out["reads"] = {"sha": reads_digest(st, nrd, nlong)[0], **run_counters(st)}
     if extended:
         out["reads"]["long_edits"] = nlong[0]
     st.close(); ix.close()

@@ -1,7 +1,6 @@
 """Campaign behind tests/test_long_edits_cpu.py: random genomes, reads of 60-250 bases with substitutions, short indels AND a long deletion in a third of them,
 --score-min L,0,-1 ... L,0,-3, single-end — the host instantiation of the large-workspace configuration (libh2gemu_long.so: 192 edits per working hit, records through the
 long-edit area) against oracle/_ref/hisat2-align-s, every SAM line; counts the reads still flagged.   usage: fuzz_long_edits.py [cases] [seed0]"""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -13,7 +12,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
 import sam_lines as SL
-import sam_util as SU
 from h2gemu_py import Emu
 from h2gemu_align import set_options
 from hisat2_amd import api, synth
@@ -45,18 +43,9 @@ def run_case(seed, verbose=True):
     want = SL.body_lines(sam)
     e = Emu(base, "long")
     set_options(e, 0, opts)
-    codes, offs = SL.flat([reads[i] for i in range(n)])
-    e.set_reads(codes, offs, None)
+    e.load_reads(reads)
     names = [str(i) for i in range(n)]
-    nb, noffs = SL.flat_names(names)
-    outs = (SU.ReadOut * n)()
-    rows = (api.AlnRes * (n * api.ALN_CAP))()
-    cap = 1 << 19
-    led = (api.Edit * cap)()
-    used = C.c_uint32(0)
-    vp = C.c_void_p
-    e.L.h2gemu_align_abi.argtypes = [vp, C.c_uint32, C.c_char_p, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
-    e.L.h2gemu_align_abi(e.h, 1, nb, noffs.ctypes.data, outs, rows, api.ALN_CAP, led, cap, C.byref(used))
+    outs, rows, led, used = e.align_abi(names, ledits_cap=1 << 19)
     res = (api.ReadResult * n)()
     flagged = nlong = 0
     for i in range(n):
@@ -65,7 +54,7 @@ def run_case(seed, verbose=True):
         r.nres, r.nselect, r.overflow, r.nrank, r.nsteps, r.depth = o.nres, o.nselect, o.overflow, o.nrank, o.nsteps, o.depth
         r.best, r.secbest, r.best_h2, r.secbest_h2 = o.best, o.secbest, o.best_h2, o.secbest_h2
         nlong += sum(1 for k in range(min(o.nselect, api.ALN_CAP)) if rows[i * api.ALN_CAP + k].nedits > api.MAX_EDITS)
-    got = SL.format_unpaired(SL.load_sam_lib(), base, [reads[i] for i in range(n)], names, res, rows, options=opts, long_edits=(led, used.value))
+    got = SL.format_unpaired(SL.load_sam_lib(), base, [reads[i] for i in range(n)], names, res, rows, options=opts, long_edits=(led, used))
     bad = sum(1 for x, y in zip(got, want) if x != y) + abs(len(got) - len(want))
     if verbose:
         print("seed %d len %d %s: lines %d differing %d, flagged reads %d, records beyond 32 edits %d" % (seed, rdlen, " ".join(opts), len(want), bad, flagged, nlong), flush=True)

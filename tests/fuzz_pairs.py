@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
 """Development fuzzer for the paired go() (host instantiation) vs the real reference binary."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -14,7 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 import pe_sink as PS  # noqa: E402
 import sam_util as SU  # noqa: E402
-from h2gemu_py import Emu  # noqa: E402
+from h2gemu_py import Emu, flat_reads  # noqa: E402
 from hisat2_amd import synth  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref")
@@ -29,8 +28,7 @@ def flatten(m):
     """(codes, offsets) of an (n, L) array or of a list of read arrays of any lengths"""
     if isinstance(m, np.ndarray) and m.ndim == 2:
         return synth.flatten_reads(m)
-    lst = [np.ascontiguousarray(r, dtype=np.uint8) for r in m]
-    return np.concatenate(lst), np.concatenate([[0], np.cumsum([len(r) for r in lst])]).astype(np.uint32)
+    return flat_reads(m)
 
 
 def write_fasta_reads(path, m, quals=None):
@@ -47,29 +45,15 @@ def emu_pairs(base, m1, m2, q1, q2, quals=None, options=None):
     """quals = (flat phred+33 bytes of the first mates, of the second mates): FASTQ pairs; options: the reference's options of the case (default: OPTS)"""
     options = OPTS if options is None else options
     e = Emu(base)
-    e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
     e.L.h2gemu_set_bowtie2_dp(e.h, DP)
     if options:
         from h2gemu_align import set_options
         set_options(e, DP, options)
-    n = len(m1)
-    c1, o1 = flatten(m1)
-    c2, o2 = flatten(m2)
-    e.set_reads(c1, o1, None if quals is None else quals[0])
+    e.load_reads(m1, None if quals is None else quals[0])
     if quals is not None:
-        q2b = np.ascontiguousarray(quals[1], dtype=np.uint8)
-        assert q2b.size == c2.size
-        e.L.h2gemu_set_mate_quals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        e.L.h2gemu_set_mate_quals(e.h, q2b.ctypes.data, q2b.size)
-    nb1 = "".join(q1).encode(); no1 = np.concatenate([[0], np.cumsum([len(q) for q in q1])]).astype(np.uint32)
-    nb2 = "".join(q2).encode(); no2 = np.concatenate([[0], np.cumsum([len(q) for q in q2])]).astype(np.uint32)
-    outs = (PS.PairOut * n)()
-    r1 = (SU.AlnRec * (n * SU.AL_MAX_RESULTS))()
-    r2 = (SU.AlnRec * (n * SU.AL_MAX_RESULTS))()
-    vp = C.c_void_p
-    e.L.h2gemu_align_pairs.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, vp, vp]
-    e.L.h2gemu_align_pairs(e.h, 1, c2.ctypes.data, o2.ctypes.data, nb1, no1.ctypes.data, nb2, no2.ctypes.data, outs, r1, r2)
-    return outs, r1, r2
+        assert np.size(quals[1]) == sum(len(r) for r in m2)
+        e.set_mate_quals(quals[1])
+    return e.align_pairs(m2, q1, q2)
 
 
 def parse_pe_sam(path):

@@ -16,7 +16,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 import sam_lines as SL  # noqa: E402
 import sam_util as SU  # noqa: E402
-import pe_sink as PS  # noqa: E402
 from h2gemu_py import Emu  # noqa: E402
 from hisat2_amd import api, synth  # noqa: E402
 
@@ -73,19 +72,8 @@ def emu_pairs(base, m1, m2, q1, q2, options=(), splice_sites=None):
     set_options(e, 0, list(options))
     if splice_sites:
         set_splice_sites(e, splice_sites)
-    n, L = m1.shape
-    c1, o1 = synth.flatten_reads(m1)
-    c2, o2 = synth.flatten_reads(m2)
-    e.set_reads(c1, o1)
-    nb1 = "".join(q1).encode(); no1 = np.concatenate([[0], np.cumsum([len(q) for q in q1])]).astype(np.uint32)
-    nb2 = "".join(q2).encode(); no2 = np.concatenate([[0], np.cumsum([len(q) for q in q2])]).astype(np.uint32)
-    outs = (PS.PairOut * n)()
-    r1 = (SU.AlnRec * (n * SU.AL_MAX_RESULTS))()
-    r2 = (SU.AlnRec * (n * SU.AL_MAX_RESULTS))()
-    vp = C.c_void_p
-    e.L.h2gemu_align_pairs.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, vp, vp]
-    e.L.h2gemu_align_pairs(e.h, 0, c2.ctypes.data, o2.ctypes.data, nb1, no1.ctypes.data, nb2, no2.ctypes.data, outs, r1, r2)
-    return outs, r1, r2
+    e.load_reads(m1)
+    return e.align_pairs(m2, q1, q2, no_spliced=0)
 
 
 def run_case(seed, npairs, sub=0.005, extra=(), show=6, known=0.0, novel_out=False):

@@ -1,9 +1,6 @@
 """Driver for the host instantiation of the go() state machine (tests only)."""
 import ctypes as C
 
-import numpy as np
-
-import sam_util as SU
 from h2gemu_py import Emu
 
 
@@ -40,16 +37,6 @@ def emu_align(base, reads_list, qnames, no_spliced=1, bowtie2_dp=0, quals=None, 
         set_splice_sites(e, splice_sites, window=window, rdid_base=rdid_base)
     if options:
         set_options(e, bowtie2_dp, options)
-    e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
     e.L.h2gemu_set_bowtie2_dp(e.h, bowtie2_dp)
-    codes = np.concatenate(reads_list).astype(np.uint8)
-    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads_list])]).astype(np.uint32)
-    e.set_reads(codes, offs, quals)   # quals: flat phred+33 bytes, same offsets (FASTQ input); None = FASTA ('I')
-    nb = "".join(qnames).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in qnames])]).astype(np.uint32)
-    n = len(reads_list)
-    outs = (SU.ReadOut * n)()
-    recs = (SU.AlnRec * (n * SU.AL_MAX_RESULTS))()
-    e.L.h2gemu_align.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    e.L.h2gemu_align(e.h, no_spliced, nb, noffs.ctypes.data, outs, recs)
-    return outs, recs
+    e.load_reads(reads_list, quals)   # quals: flat phred+33 bytes, same offsets (FASTQ input); None = FASTA ('I')
+    return e.align(qnames, no_spliced)

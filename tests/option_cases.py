@@ -167,23 +167,18 @@ def _long_rec_type():
 
 
 def _long_emu(base, options):
-    import ctypes as C
     from h2gemu_align import set_options
     from h2gemu_py import Emu
     e = Emu(base, "long")
-    e.L.h2gemu_ghit_edits.restype = C.c_uint32
-    assert e.L.h2gemu_ghit_edits() == LONG_EDITS
+    assert e.ghit_edits() == LONG_EDITS
     if options:
         set_options(e, 0, options)
     return e
 
 
 def _flat(lst):
-    return np.concatenate([np.asarray(r, dtype=np.uint8) for r in lst]), np.concatenate([[0], np.cumsum([len(r) for r in lst])]).astype(np.uint32)
-
-
-def _names(q):
-    return "".join(q).encode(), np.concatenate([[0], np.cumsum([len(x) for x in q])]).astype(np.uint32)
+    from h2gemu_py import flat_reads
+    return flat_reads(lst)
 
 
 def _sub_quals(quals, offs, ids):
@@ -203,7 +198,6 @@ class _Rows:
 
 def host_reads_backend(base, reads, qnames, refnames, quals=None, options=()):
     """a fuzz_align backend -> (outs, rendered records); outs[i].overflow is what is left after the second pass"""
-    import ctypes as C
     import sam_util as SU
     from h2gemu_align import emu_align
     reads = [np.asarray(r, dtype=np.uint8) for r in reads]
@@ -214,14 +208,8 @@ def host_reads_backend(base, reads, qnames, refnames, quals=None, options=()):
     host_reads_backend.left = lambda: sorted({o.overflow for o in outs})
     if ids:
         e = _long_emu(base, options)
-        codes, offs = _flat([reads[i] for i in ids])
-        _, offs_all = _flat(reads)
-        e.set_reads(codes, offs, _sub_quals(quals, offs_all, ids))
-        nb, noffs = _names([qnames[i] for i in ids])
-        o2 = (SU.ReadOut * len(ids))()
-        r2 = (_long_rec_type() * (len(ids) * SU.AL_MAX_RESULTS))()
-        e.L.h2gemu_align.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        e.L.h2gemu_align(e.h, 1, nb, noffs.ctypes.data, o2, r2)
+        e.load_reads([reads[i] for i in ids], _sub_quals(quals, _flat(reads)[1], ids))
+        o2, r2 = e.align([qnames[i] for i in ids], rec_type=_long_rec_type())
         for k, i in enumerate(ids):
             outs[i] = o2[k]
             rows.over[i] = (r2, k)
@@ -230,9 +218,7 @@ def host_reads_backend(base, reads, qnames, refnames, quals=None, options=()):
 
 def host_pairs_backend(base, m1, m2, q1, q2, quals=None, options=()):
     """a fuzz_pairs backend -> (outs, rows of the first mates, of the second mates), stride sam_util.AL_MAX_RESULTS"""
-    import ctypes as C
     import fuzz_pairs as FP
-    import pe_sink as PS
     import sam_util as SU
     outs, r1, r2 = FP.emu_pairs(base, m1, m2, q1, q2, quals=quals, options=tuple(options))
     outs, r1, r2 = list(outs), _Rows(r1, SU.AL_MAX_RESULTS), _Rows(r2, SU.AL_MAX_RESULTS)
@@ -241,21 +227,10 @@ def host_pairs_backend(base, m1, m2, q1, q2, quals=None, options=()):
     host_pairs_backend.left = lambda: sorted({o.overflow for o in outs})
     if ids:
         e = _long_emu(base, options)
-        (c1, o1), (c2, o2) = _flat([m1[i] for i in ids]), _flat([m2[i] for i in ids])
-        (_, a1), (_, a2) = _flat(m1), _flat(m2)
-        e.set_reads(c1, o1, None if quals is None else _sub_quals(quals[0], a1, ids))
+        e.load_reads([m1[i] for i in ids], None if quals is None else _sub_quals(quals[0], _flat(m1)[1], ids))
         if quals is not None:
-            qb = np.ascontiguousarray(_sub_quals(quals[1], a2, ids), dtype=np.uint8)
-            e.L.h2gemu_set_mate_quals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-            e.L.h2gemu_set_mate_quals(e.h, qb.ctypes.data, qb.size)
-        c2 = np.concatenate([c2, np.zeros(8, np.uint8)])
-        (nb1, no1), (nb2, no2) = _names([q1[i] for i in ids]), _names([q2[i] for i in ids])
-        po = (PS.PairOut * len(ids))()
-        T = _long_rec_type()
-        l1, l2 = (T * (len(ids) * SU.AL_MAX_RESULTS))(), (T * (len(ids) * SU.AL_MAX_RESULTS))()
-        vp = C.c_void_p
-        e.L.h2gemu_align_pairs.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, vp, vp]
-        e.L.h2gemu_align_pairs(e.h, 1, c2.ctypes.data, o2.ctypes.data, nb1, no1.ctypes.data, nb2, no2.ctypes.data, po, l1, l2)
+            e.set_mate_quals(_sub_quals(quals[1], _flat(m2)[1], ids))
+        po, l1, l2 = e.align_pairs([m2[i] for i in ids], [q1[i] for i in ids], [q2[i] for i in ids], rec_type=_long_rec_type())
         for k, i in enumerate(ids):
             outs[i] = po[k]
             r1.over[i], r2.over[i] = (l1, k), (l2, k)

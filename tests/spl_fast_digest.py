@@ -3,13 +3,12 @@ H2G_GO_FAST=0: the switch is read once per process).  fast_digest.py's three bac
 of the others (no_temp_splicesite = 1), optionally a splice-site file loaded into the index's database, and the number of records that hold a splice edit.
 usage: spl_fast_digest.py index_base reads.npz [--sites file] [reference options, e.g. --dta]"""
 import ctypes as C
-import hashlib
 import json
 import sys
 
 import numpy as np
 
-from fast_digest import ALN_DT, aln_bytes, flat_of
+from fast_digest import ALN_DT, flat_of, pairs_digest, reads_digest, run_counters
 from hisat2_amd import api
 
 EDIT_SPL = 5
@@ -44,21 +43,13 @@ def main():
     p.no_spliced_alignment = 0; p.no_temp_splicesite = 1
     for rep in range(3):                                         # back-to-back runs: the machine passes of earlier runs overlap the later fast passes
         st.align_pairs_run(p)
-    res, a1, f1, a2, f2 = st.align_pairs_fetch_dense()
-    h = hashlib.sha256()
-    h.update(bytes(res)); h.update(f1.tobytes()); h.update(f2.tobytes()); h.update(aln_bytes(a1, int(f1[n]))); h.update(aln_bytes(a2, int(f2[n])))
-    c = st.counters()
-    out["pairs"] = {"sha": h.hexdigest(), "fast": int(c.n_fast), "handed_on": int(c.n_fast_bail), "aligned": int(c.n_aligned), "overflow": int(c.n_overflow), "adopted": int(c.n_adopted),
-                    "spliced_records": spliced_records(a1, int(f1[n])) + spliced_records(a2, int(f2[n]))}
+    sha, a1, n1, a2, n2 = pairs_digest(st, n)
+    out["pairs"] = {"sha": sha, **run_counters(st), "spliced_records": spliced_records(a1, n1) + spliced_records(a2, n2)}
     st.set_reads(rc, ro); st.set_read_names([str(i) for i in range(nrd)])
     for rep in range(3):
         st.align_run(p)
-    res, aln, offs = st.align_fetch_dense()
-    h = hashlib.sha256()
-    h.update(res.tobytes()); h.update(offs.tobytes()); h.update(aln_bytes(aln, int(offs[nrd])))
-    c = st.counters()
-    out["reads"] = {"sha": h.hexdigest(), "fast": int(c.n_fast), "handed_on": int(c.n_fast_bail), "aligned": int(c.n_aligned), "overflow": int(c.n_overflow), "adopted": int(c.n_adopted),
-                    "spliced_records": spliced_records(aln, int(offs[nrd]))}
+    sha, aln, nrec = reads_digest(st, nrd)
+    out["reads"] = {"sha": sha, **run_counters(st), "spliced_records": spliced_records(aln, nrec)}
     st.close(); ix.close()
     print(json.dumps(out))
 

@@ -2,12 +2,10 @@
 built by the code the device runs equals the canonical walk for EVERY row of every local index ('$' rows included), the fast path and the general machine
 give the same bytes with the table attached as without it (work counters included), and a walk stored half way by a run without the table is finished
 correctly by a run with it.  With the saturation threshold lowered to 4 most rows miss the table and take the fallback (one local row in eight is sampled)."""
-import ctypes as C
 import os
 import subprocess
 import tempfile
 
-import numpy as np
 import pytest
 
 from hisat2_amd import synth
@@ -50,21 +48,13 @@ def genome():
 def _emu(monkeypatch, lib, base):
     from h2gemu_py import Emu
     monkeypatch.setenv("H2GEMU_LIB", lib)
-    e = Emu(base)
-    vp = C.c_void_p
-    e.L.h2gemu_lsa_build.argtypes = [vp]
-    e.L.h2gemu_lsa_attach.argtypes = [vp, C.c_uint32]
-    e.L.h2gemu_lsa_check.argtypes = [vp, vp]
-    e.L.h2gemu_lsa_sat.restype = C.c_uint32
-    e.L.h2gemu_lsa_digest.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, C.c_uint32, vp]
-    return e
+    return Emu(base)
 
 
 def _check_every_row(e, sat):
-    assert e.L.h2gemu_lsa_sat() == sat
-    e.L.h2gemu_lsa_build(e.h)
-    out = np.zeros(10, dtype=np.uint64)
-    e.L.h2gemu_lsa_check(e.h, out.ctypes.data)
+    assert e.lsa_sat() == sat
+    e.lsa_build()
+    out = e.table_check("lsa", 10)
     r = dict(zip(("wrong", "resolved_wrong", "saturated", "longest", "rows", "dollar", "multi_frag", "short", "empty", "n"), (int(x) for x in out)))
     print(f"sat {sat}: {r}")
     assert r["wrong"] == 0 and r["resolved_wrong"] == 0
@@ -91,20 +81,8 @@ def test_table_equals_the_walk_on_every_local_row(libs, genome, monkeypatch, sat
 
 
 def _digest(e, reads1, reads2, midwalk=0):
-    n = len(reads1)
-    names = [str(i) for i in range(n)]
-    nb = "".join(names).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-    codes = np.concatenate(reads1).astype(np.uint8)
-    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads1])]).astype(np.uint32)
-    e.set_reads(codes, offs, None)
-    out = np.zeros(5, dtype=np.uint64)
-    if reads2 is not None:
-        c2 = np.concatenate([np.concatenate(reads2).astype(np.uint8), np.zeros(8, np.uint8)])
-        o2 = np.concatenate([[0], np.cumsum([len(r) for r in reads2])]).astype(np.uint32)
-        e.L.h2gemu_lsa_digest(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, midwalk, out.ctypes.data)
-    else:
-        e.L.h2gemu_lsa_digest(e.h, None, None, nb, noffs.ctypes.data, None, None, midwalk, out.ctypes.data)
+    e.load_reads(reads1)
+    out = e.table_digest("lsa", reads2, midwalk)
     return dict(machine=int(out[0]), fast=int(out[1]), completed=int(out[2]), nsteps=int(out[3])), int(out[4])
 
 
@@ -114,13 +92,12 @@ def _run_both(monkeypatch, lib, base, reads1, reads2):
     res = []
     for on in (0, 1):
         e = _emu(monkeypatch, lib, base)
-        e.L.h2gemu_lsa_build(e.h)
-        e.L.h2gemu_lsa_attach(e.h, on)
-        monkeypatch.setattr(FC, "Emu", lambda b, v="", _e=e: _e)                 # (FC.fast_check makes its own Emu: give it this one)
-        r = FC.fast_check(base, list(reads1), None if reads2 is None else list(reads2))
+        e.lsa_build()
+        e.lsa_attach(on)
+        r = FC.fast_check(base, list(reads1), None if reads2 is None else list(reads2), emu=e)
         res.append((r, _digest(e, reads1, reads2)[0]))
     e = _emu(monkeypatch, lib, base)                                             # (a fresh instance, as the two above: the digests are compared across instances)
-    e.L.h2gemu_lsa_build(e.h)
+    e.lsa_build()
     mid, switched = _digest(e, reads1, reads2, midwalk=1)
     return res, mid, switched
 

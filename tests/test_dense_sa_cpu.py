@@ -1,12 +1,10 @@
 """The dense SA table (hisat2_amd/csrc/h2g_core.h: sa_dense_build_rows, sa_resolve_row; h2g_fast.h fast_op_gcoords) on the host: the table built by the
 same code the device runs equals the canonical walk for EVERY row, and the fast path and the general machine give the same bytes with the table
 attached as without it (work counters included).  With the saturation threshold lowered to 8 most rows miss the table and take the fallback."""
-import ctypes as C
 import os
 import subprocess
 import tempfile
 
-import numpy as np
 import pytest
 
 from hisat2_amd import synth
@@ -47,21 +45,13 @@ def genome():
 def _emu(monkeypatch, lib, base):
     from h2gemu_py import Emu
     monkeypatch.setenv("H2GEMU_LIB", lib)
-    e = Emu(base)
-    vp = C.c_void_p
-    e.L.h2gemu_dense_build.argtypes = [vp]
-    e.L.h2gemu_dense_attach.argtypes = [vp, C.c_uint32]
-    e.L.h2gemu_dense_check.argtypes = [vp, vp]
-    e.L.h2gemu_dense_sat.restype = C.c_uint32
-    return e
+    return Emu(base)
 
 
 def _check_every_row(e, sat):
-    assert e.L.h2gemu_dense_sat() == sat
-    e.L.h2gemu_dense_build(e.h)
-    out = np.zeros(4, dtype=np.uint64)
-    e.L.h2gemu_dense_check(e.h, out.ctypes.data)
-    wrong, resolved_wrong, saturated, longest = (int(x) for x in out)
+    assert e.dense_sat() == sat
+    e.dense_build()
+    wrong, resolved_wrong, saturated, longest = (int(x) for x in e.table_check("dense", 4))
     print(f"sat {sat}: {wrong} wrong entries, {resolved_wrong} rows resolved differently, {saturated} rows not in the table, longest walk {longest}")
     assert wrong == 0 and resolved_wrong == 0
     return saturated, longest
@@ -91,31 +81,16 @@ def _run_both(monkeypatch, lib, base, reads1, reads2):
     res = []
     for on in (0, 1):
         e = _emu(monkeypatch, lib, base)
-        e.L.h2gemu_dense_build(e.h)
-        e.L.h2gemu_dense_attach(e.h, on)
-        monkeypatch.setattr(FC, "Emu", lambda b, v="", _e=e: _e)                 # (FC.fast_check makes its own Emu: give it this one)
-        r = FC.fast_check(base, list(reads1), None if reads2 is None else list(reads2))
+        e.dense_build()
+        e.dense_attach(on)
+        r = FC.fast_check(base, list(reads1), None if reads2 is None else list(reads2), emu=e)
         res.append((r, _digest(e, reads1, reads2)))
     return res
 
 
 def _digest(e, reads1, reads2):
-    n = len(reads1)
-    names = [str(i) for i in range(n)]
-    nb = "".join(names).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-    codes = np.concatenate(reads1).astype(np.uint8)
-    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads1])]).astype(np.uint32)
-    e.set_reads(codes, offs, None)
-    vp = C.c_void_p
-    out = np.zeros(4, dtype=np.uint64)
-    e.L.h2gemu_dense_digest.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp]
-    if reads2 is not None:
-        c2 = np.concatenate([np.concatenate(reads2).astype(np.uint8), np.zeros(8, np.uint8)])
-        o2 = np.concatenate([[0], np.cumsum([len(r) for r in reads2])]).astype(np.uint32)
-        e.L.h2gemu_dense_digest(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, out.ctypes.data)
-    else:
-        e.L.h2gemu_dense_digest(e.h, None, None, nb, noffs.ctypes.data, None, None, out.ctypes.data)
+    e.load_reads(reads1)
+    out = e.table_digest("dense", reads2)
     return dict(machine=int(out[0]), fast=int(out[1]), completed=int(out[2]), nsteps=int(out[3]))
 
 

@@ -11,7 +11,6 @@ import numpy as np
 import pytest
 
 import sam_lines as SL
-import sam_util as SU
 from h2gemu_py import Emu
 from h2gemu_align import set_options
 from hisat2_amd import api, synth
@@ -59,21 +58,14 @@ def test_records_beyond_32_edits_equal_the_reference(case):
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     want = SL.body_lines(sam)
     e = Emu(base, "long")
-    e.L.h2gemu_ghit_edits.restype = C.c_uint32
-    assert e.L.h2gemu_ghit_edits() == 192                          # the *_big units' own configuration
+    assert e.ghit_edits() == 192                                   # the *_big units' own configuration
     p = set_options(e, 0, opts)
     codes, offs = SL.flat([reads[i] for i in range(n)])
     e.set_reads(codes, offs, None)
     names = [str(i) for i in range(n)]
     nb, noffs = SL.flat_names(names)
-    outs = (SU.ReadOut * n)()
-    rows = (api.AlnRes * (n * api.ALN_CAP))()
-    cap = 1 << 18
-    led = (api.Edit * cap)()
-    used = C.c_uint32(0)
+    outs, rows, led, used = e.align_abi(names)
     vp = C.c_void_p
-    e.L.h2gemu_align_abi.argtypes = [vp, C.c_uint32, C.c_char_p, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
-    e.L.h2gemu_align_abi(e.h, 1, nb, noffs.ctypes.data, outs, rows, api.ALN_CAP, led, cap, C.byref(used))
     res = (api.ReadResult * n)()
     nlong = 0
     for i in range(n):
@@ -85,10 +77,10 @@ def test_records_beyond_32_edits_equal_the_reference(case):
             rec = rows[i * api.ALN_CAP + k]
             if rec.nedits > api.MAX_EDITS:
                 nlong += 1
-                assert rec.edits[0].snp == 0x4c4f4e47 and rec.edits[0].pos + rec.nedits <= used.value
+                assert rec.edits[0].snp == 0x4c4f4e47 and rec.edits[0].pos + rec.nedits <= used
     assert nlong >= 20, nlong                                      # the long path is what this test is about (most such reads end soft-clipped)
     L = SL.load_sam_lib()
-    got = SL.format_unpaired(L, base, [reads[i] for i in range(n)], names, res, rows, options=opts, long_edits=(led, used.value))
+    got = SL.format_unpaired(L, base, [reads[i] for i in range(n)], names, res, rows, options=opts, long_edits=(led, used))
     assert len(got) == len(want)
     bad = [i for i, (x, y) in enumerate(zip(got, want)) if x != y]
     assert not bad, (len(bad), got[bad[0]], want[bad[0]])
@@ -109,7 +101,7 @@ def test_records_beyond_32_edits_equal_the_reference(case):
     rc = L.h2g_sam_format_unpaired_dense(h, codes.ctypes.data, offs.ctypes.data, None, nb, noffs.ctypes.data, n, C.addressof(res), C.addressof(dense), offs64.ctypes.data, buf, 1 << 22, C.byref(u))
     assert rc != 0
     L.h2g_sam_set_long_edits.argtypes = [vp, vp, C.c_size_t]
-    L.h2g_sam_set_long_edits(h, led, used.value)
+    L.h2g_sam_set_long_edits(h, led, used)
     rc = L.h2g_sam_format_unpaired_dense(h, codes.ctypes.data, offs.ctypes.data, None, nb, noffs.ctypes.data, n, C.addressof(res), C.addressof(dense), offs64.ctypes.data, buf, 1 << 22, C.byref(u))
     assert rc == 0 and buf.raw[:u.value].decode().splitlines() == want
     L.h2g_sam_close(h)
@@ -123,20 +115,10 @@ def _align_long(base, reads, opts, bowtie2_dp=0, names=None):
     n = len(reads)
     e = Emu(base, "long")
     set_options(e, bowtie2_dp, opts)
-    e.L.h2gemu_set_bowtie2_dp.argtypes = [C.c_void_p, C.c_uint32]
     e.L.h2gemu_set_bowtie2_dp(e.h, bowtie2_dp)
-    codes, offs = SL.flat(reads)
-    e.set_reads(codes, offs, None)
+    e.load_reads(reads)
     names = names or [str(i) for i in range(n)]
-    nb, noffs = SL.flat_names(names)
-    outs = (SU.ReadOut * n)()
-    rows = (api.AlnRes * (n * api.ALN_CAP))()
-    cap = 1 << 18
-    led = (api.Edit * cap)()
-    used = C.c_uint32(0)
-    vp = C.c_void_p
-    e.L.h2gemu_align_abi.argtypes = [vp, C.c_uint32, C.c_char_p, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
-    e.L.h2gemu_align_abi(e.h, 1, nb, noffs.ctypes.data, outs, rows, api.ALN_CAP, led, cap, C.byref(used))
+    outs, rows, led, used = e.align_abi(names)
     res = (api.ReadResult * n)()
     nlong = flagged = 0
     for i in range(n):
@@ -145,7 +127,7 @@ def _align_long(base, reads, opts, bowtie2_dp=0, names=None):
         r.nres, r.nselect, r.overflow, r.nrank, r.nsteps, r.depth = o.nres, o.nselect, o.overflow, o.nrank, o.nsteps, o.depth
         r.best, r.secbest, r.best_h2, r.secbest_h2 = o.best, o.secbest, o.best_h2, o.secbest_h2
         nlong += sum(1 for k in range(min(o.nselect, api.ALN_CAP)) if rows[i * api.ALN_CAP + k].nedits > api.MAX_EDITS)
-    got = SL.format_unpaired(SL.load_sam_lib(), base, reads, names, res, rows, options=opts, long_edits=(led, used.value))
+    got = SL.format_unpaired(SL.load_sam_lib(), base, reads, names, res, rows, options=opts, long_edits=(led, used))
     return got, nlong, flagged
 
 

@@ -3,7 +3,6 @@ machine, both instantiated on the host (tests/emul_spl/h2g_emul_spl.cpp over tes
 the pass completes must equal the machine's result bit for bit (PairOut / ReadOut incl. the PRNG state and the work counters, every record); a read the
 machine aligns with a splice edit is never completed; with the known-sites file loaded every read inside a decoy exon is handed on.  The share of class
 (a) — reads wholly inside an exon — that completes is printed per case: tests/test_gpu_spl_fast.py takes its floor from the `gpu_layout` case."""
-import ctypes as C
 import os
 import subprocess
 
@@ -11,7 +10,7 @@ import numpy as np
 import pytest
 
 import spl_fast_cases as SC
-from fast_check import BAIL_REASONS
+from fast_check import fast_check
 from hisat2_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,29 +57,9 @@ def spl_check(lib, base, reads1, reads2=None, options=(), sites=None):
     set_options(e, 0, list(options))
     if sites:
         set_splice_sites(e, sites)
-    n = len(reads1)
-    c1, o1 = synth.flatten_reads(reads1)
-    e.set_reads(c1, o1, None)
-    names = [str(i) for i in range(n)]
-    nb = "".join(names).encode()
-    noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-    stats = np.zeros(2 + len(BAIL_REASONS) + 2, dtype=np.uint64)
-    bad = np.zeros(64, dtype=np.uint32)
-    done = np.zeros(n, dtype=np.uint8)
-    spl = np.zeros(n, dtype=np.uint8)
-    vp = C.c_void_p
-    f = e.L.h2gemu_fast_check_spl
-    f.restype = None
-    f.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, vp, C.c_uint32, vp, vp]
-    if reads2 is not None:
-        c2, o2 = synth.flatten_reads(reads2)
-        c2 = np.concatenate([c2, np.zeros(8, np.uint8)])
-        f(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data, spl.ctypes.data)
-    else:
-        f(e.h, None, None, nb, noffs.ctypes.data, None, None, stats.ctypes.data, bad.ctypes.data, 64, done.ctypes.data, spl.ctypes.data)
-    nbad = int(stats[1])
-    return {"n": n, "completed": int(stats[0]), "mismatching": nbad, "bails": {BAIL_REASONS[k]: int(stats[2 + k]) for k in range(len(BAIL_REASONS)) if stats[2 + k]},
-            "bad": [int(x) for x in bad[:min(nbad, 64)]], "done": done.astype(bool), "spl": spl.astype(bool)}
+    r = fast_check(base, reads1, reads2, emu=e, spliced=True)
+    r["done"], r["spl"] = r["done"].astype(bool), r["spl"].astype(bool)
+    return r
 
 
 def share_a(r, labels):

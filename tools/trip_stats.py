@@ -2,7 +2,7 @@
 """Development: how long are the latency chains of the reads the fast pass hands on?  Host instantiation (tests/emul): the batch through
 the fast path, then the general machine over every handed-on pair with its primitive requests (trips) counted per pair.
 usage: trip_stats.py [pairs] [genome bases] [rep|rnd]"""
-import ctypes as C, os, sys, subprocess, time
+import os, sys, subprocess, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
@@ -33,18 +33,8 @@ r = FC.fast_check(base, m1, m2)
 print("fast_check %.1f s: completed %d mismatching %d bails %s" % (time.time() - t0, r["completed"], r["mismatching"], r["bails"]))
 ids = np.nonzero(r["done"] == 0)[0].astype(np.uint32)
 e = Emu(base)
-codes = np.concatenate(m1).astype(np.uint8)
-offs = np.concatenate([[0], np.cumsum([len(x) for x in m1])]).astype(np.uint32)
-e.set_reads(codes, offs, None)
-names = [str(i) for i in range(n)]
-nb = "".join(names).encode()
-noffs = np.concatenate([[0], np.cumsum([len(q) for q in names])]).astype(np.uint32)
-c2 = np.concatenate([np.concatenate(m2).astype(np.uint8), np.zeros(8, np.uint8)])
-o2 = np.concatenate([[0], np.cumsum([len(x) for x in m2])]).astype(np.uint32)
-out = np.zeros((len(ids), 16), dtype=np.uint32)
-vp = C.c_void_p
-e.L.h2gemu_pair_trips.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, vp, vp, C.c_size_t, vp]
-e.L.h2gemu_pair_trips(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, ids.ctypes.data, len(ids), out.ctypes.data)
+e.load_reads(m1)
+out = e.pair_trips(m2, ids)
 trips = out[:, 1:12].sum(axis=1)
 print("handed on: %d of %d pairs; trips per handed-on pair: mean %.1f median %d p90 %d p99 %d max %d" % (len(ids), n, trips.mean(), np.median(trips), np.percentile(trips, 90), np.percentile(trips, 99), trips.max()))
 print("by primitive (mean per handed-on pair): " + ", ".join("%s %.1f" % (OPS[k], out[:, k].mean()) for k in range(1, 12) if out[:, k].any()))
@@ -55,7 +45,6 @@ hist = np.bincount(np.minimum(trips // 50, 40))
 print("histogram (bins of 50 trips):", hist.tolist())
 # all pairs (incl. completed ones) for scale
 allids = np.arange(min(n, 20000), dtype=np.uint32)
-out2 = np.zeros((len(allids), 16), dtype=np.uint32)
-e.L.h2gemu_pair_trips(e.h, c2.ctypes.data, o2.ctypes.data, nb, noffs.ctypes.data, nb, noffs.ctypes.data, allids.ctypes.data, len(allids), out2.ctypes.data)
+out2 = e.pair_trips(m2, allids)
 t2 = out2[:, 1:12].sum(axis=1)
 print("every pair (first %d): machine trips mean %.1f median %d p99 %d max %d" % (len(allids), t2.mean(), np.median(t2), np.percentile(t2, 99), t2.max()))
