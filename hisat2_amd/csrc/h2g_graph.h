@@ -727,7 +727,8 @@ H2G_HDN void gw_advance(const X& g, GwCtx* x, uint32_t range) {
 				GRange r;
 				IEdges tie;
 				map_glf(g, curtop, curbot, c, cur_node_bot - cur_node_top, &r, &tie);
-				if(tie.n > H2G_GW_MAXELT) { GW_OVF(x); return; }
+				// tie is an IEdges: n is the true count, only H2G_IEDGE_CAP entries exist.  A longer list is a capacity hit before any entry is read
+				if(tie.n > H2G_GW_MAXELT || tie.n > H2G_IEDGE_CAP) { GW_OVF(x); return; }
 				if(first) {
 					first = false;
 					newtop = r.top; newbot = r.bot; new_node_top = r.node_top; new_node_bot = r.node_bot;
@@ -796,7 +797,7 @@ H2G_HDN bool gw_resolve(const X& g, GwCtx* x, uint32_t top, uint32_t bot, uint32
 	uint32_t nelt = node_bot - node_top;
 	if(nelt > maxelt) nelt = maxelt;
 	*nelt_out = nelt;
-	if(nelt > H2G_GW_MAXELT || (ie && ie->n > H2G_GW_MAXELT)) return false;
+	if(nelt > H2G_GW_MAXELT || (ie && (ie->n > H2G_GW_MAXELT || ie->n > H2G_IEDGE_CAP))) return false;   // (the caller's list stores H2G_IEDGE_CAP entries)
 	x->nelt = nelt; x->nst = 0; x->nsteps = 0; x->overflow = 0;
 	for(uint32_t i = 0; i < nelt; i++) { x->offs[i] = H2G_MAX; x->fmap[i] = H2G_MAX; }
 	GwState* s = gw_new_state(x);                             // GroupWalk2S::init :1430-1470

@@ -1653,9 +1653,9 @@ static int sw_rect(const h2o_scoring* sc, const uint8_t* seq, const char* qual, 
  * merged when several rows lead into one node — the merged-away duplicates are "resolved" with their own element index
  * as the offset (group_walk.h:1171, 1246), which is reproduced here because it reaches the alignment through
  * joinedToTextOff.  tryOffset (gfm.h:2719) samples by NODE: (node & offMask) == node -> offs[node >> offRate]. */
-#define GW_MAXELT 64
-#define GW_MAXST 96
-#define GW_MAXIE 64
+#define GW_MAXELT 128
+#define GW_MAXST 256
+#define GW_MAXIE 128
 typedef struct { uint32_t first, second; } gw_pair;
 typedef struct {
 	uint32_t top, bot, node_top, node_bot, step, mapi, nmap, nie;
@@ -1671,7 +1671,9 @@ typedef struct {
 	uint32_t nst;
 	uint32_t nsteps;
 	int overflow;
+	uint32_t max_ie;                                       /* read-out: the longest in-edge list this walk met (initial list, every tie, every split-off state's) */
 } gw_ctx;
+#define GW_SEE_IE(X, N) do { if((N) > (X)->max_ie) (X)->max_ie = (N); } while(0)
 
 static uint32_t gw_try_offset(const h2o_gfm* g, uint32_t row, uint32_t node) {
 	for(uint32_t i = 0; i < g->nZ; i++) if(row == g->zOffs[i]) return 0;
@@ -1768,6 +1770,7 @@ static void gw_init(gw_ctx* x, uint32_t range) {
 			}
 			n++;
 		}
+		if(x->overflow) return;
 		for(uint32_t i = 0; i < nz; i++) {
 			s = &x->st[range];
 			uint32_t new_top = zin[i] + 1;
@@ -1788,9 +1791,12 @@ static void gw_init(gw_ctx* x, uint32_t range) {
 				if(j + 1 < j2 && ntie < GW_MAXIE) { tie[ntie].first = nn - (new_node_top - s->node_top); tie[ntie].second = j2 - j - 1; ntie++; }
 				j = j2;
 			}
+			GW_SEE_IE(x, ntie);
 			gw_state* ns = gw_new_state(x);
+			if(x->overflow) return;
 			s = &x->st[range];
 			ns->nmap = new_node_bot - new_node_top; ns->mapi = 0;
+			if(ns->nmap > GW_MAXELT) { x->overflow = 1; return; }
 			for(uint32_t j = new_node_top; j < new_node_bot; j++) ns->map[j - new_node_top] = s->map[j - s->node_top + s->mapi];
 			ns->top = new_top; ns->bot = new_bot; ns->node_top = new_node_top; ns->node_bot = new_node_bot;
 			ns->nie = ntie; memcpy(ns->ie, tie, sizeof(gw_pair) * ntie);
@@ -1806,7 +1812,7 @@ static void gw_init(gw_ctx* x, uint32_t range) {
 			if(s->ie[k].first >= s->node_bot - s->node_top) { s->nie = k; break; }
 			width += s->ie[k].second;
 		}
-		if(width != s->bot - s->top) {
+		if(width != s->bot - s->top && s->nie > 0) {
 			s->ie[s->nie - 1].second -= 1;
 			if(s->ie[s->nie - 1].second == 0) s->nie--;
 		}
@@ -1868,19 +1874,21 @@ static void gw_advance(gw_ctx* x, uint32_t range) {
 				uint32_t t, b, nt, nb;
 				gw_pair tie[GW_MAXIE]; uint32_t ntie = 0, tmpie[2 * GW_MAXIE];
 				h2o_map_glf(g, curtop, curbot, c, cur_node_bot - cur_node_top, &t, &b, &nt, &nb, tmpie, GW_MAXIE, &ntie);
+				GW_SEE_IE(x, ntie);
 				if(ntie > GW_MAXIE) { ntie = GW_MAXIE; x->overflow = 1; }
 				for(uint32_t k = 0; k < ntie; k++) { tie[k].first = tmpie[2 * k]; tie[k].second = tmpie[2 * k + 1]; }
 				if(first) {
 					first = 0;
 					newtop = t; newbot = b; new_node_top = nt; new_node_bot = nb;
 					nbackup = ntie; memcpy(backup, tie, sizeof(gw_pair) * ntie);
-					for(uint32_t j = 0; j < n; j++) if(mask[c][j]) gmap[ngmap++] = s->map[j + s->mapi + (cur_node_top - s->node_top)];
+					for(uint32_t j = 0; j < n; j++) if(mask[c][j]) { if(ngmap < GW_MAXELT) gmap[ngmap++] = s->map[j + s->mapi + (cur_node_top - s->node_top)]; else x->overflow = 1; }
 					if(new_node_bot - new_node_top < ngmap) gw_merge_dups(x, curtop, mask[c], n, c, gmap, &ngmap);
 				} else {
 					gw_state* ns = gw_new_state(x);
+					if(x->overflow) return;
 					s = &x->st[range];
 					ns->mapi = 0; ns->nmap = 0;
-					for(uint32_t j = 0; j < n; j++) if(mask[c][j]) ns->map[ns->nmap++] = s->map[j + s->mapi + (cur_node_top - s->node_top)];
+					for(uint32_t j = 0; j < n; j++) if(mask[c][j]) { if(ns->nmap < GW_MAXELT) ns->map[ns->nmap++] = s->map[j + s->mapi + (cur_node_top - s->node_top)]; else x->overflow = 1; }
 					if(nb - nt < ns->nmap) gw_merge_dups(x, curtop, mask[c], n, c, ns->map, &ns->nmap);
 					ns->top = t; ns->bot = b; ns->node_top = nt; ns->node_bot = nb;
 					ns->nie = ntie; memcpy(ns->ie, tie, sizeof(gw_pair) * ntie);
@@ -1906,16 +1914,21 @@ static void gw_advance(gw_ctx* x, uint32_t range) {
 	gw_init(x, range);
 }
 
+static gw_ctx gw_last;                                     /* ~60 KB; the oracle is single-threaded test code */
+/* read-outs of the last h2o_genome_coords_graph call: the longest in-edge list the group walk met (the caller's list, every list a step mapped
+   to, every list of a split-off state: true counts), the states it created and its elements.  Which capacities a case needs. */
+void h2o_gw_readout(uint32_t* max_iedges, uint32_t* nstates, uint32_t* nelt) { *max_iedges = gw_last.max_ie; *nstates = gw_last.nst; *nelt = gw_last.nelt; }
+
 int h2o_genome_coords_graph(const h2o_index* ix, uint32_t top, uint32_t bot, uint32_t node_top, uint32_t node_bot,
                             const uint32_t* iedges, uint32_t niedges, uint32_t maxelt, uint32_t rdlen, int rejectStraddle,
                             h2o_coord* coords, uint32_t* ncoords, int* straddled, uint32_t* nsteps)
 {
-	static gw_ctx ctx;                                      /* ~60 KB; the oracle is single-threaded test code */
-	gw_ctx* x = &ctx;
+	gw_ctx* x = &gw_last;
 	const h2o_gfm* g = &ix->g;
 	*straddled = 0;
 	uint32_t nelt = node_bot - node_top;
 	if(nelt > maxelt) nelt = maxelt;
+	x->max_ie = niedges; x->nst = 0; x->nelt = nelt;
 	if(nelt > GW_MAXELT) return -1;
 	x->g = g; x->topf = top; x->botf = bot; x->sa_node_top = node_top; x->nelt = nelt; x->nst = 0; x->nsteps = 0; x->overflow = 0;
 	for(uint32_t i = 0; i < nelt; i++) { x->offs[i] = H2O_MAX; x->fmap[i].first = x->fmap[i].second = H2O_MAX; }
@@ -1923,7 +1936,8 @@ int h2o_genome_coords_graph(const h2o_index* ix, uint32_t top, uint32_t bot, uin
 	s->nmap = nelt; s->mapi = 0;
 	for(uint32_t i = 0; i < nelt; i++) s->map[i] = i;
 	s->top = top; s->bot = bot; s->node_top = node_top; s->node_bot = node_top + nelt;
-	s->nie = niedges < GW_MAXIE ? niedges : GW_MAXIE;
+	if(niedges > GW_MAXIE) return -1;
+	s->nie = niedges;
 	for(uint32_t k = 0; k < s->nie; k++) { s->ie[k].first = iedges[2 * k]; s->ie[k].second = iedges[2 * k + 1]; }
 	s->step = 0;
 	gw_init(x, 0);

@@ -141,6 +141,8 @@ int  h2o_genome_coords(const h2o_index*, uint32_t top, uint32_t bot, uint32_t ma
 int  h2o_genome_coords_graph(const h2o_index*, uint32_t top, uint32_t bot, uint32_t node_top, uint32_t node_bot,
                              const uint32_t* iedges, uint32_t niedges, uint32_t maxelt, uint32_t rdlen, int rejectStraddle,
                              h2o_coord* coords, uint32_t* ncoords, int* straddled, uint32_t* nsteps);
+/* what the last h2o_genome_coords_graph call needed: its longest in-edge list (true count), its states, its elements */
+void h2o_gw_readout(uint32_t* max_iedges, uint32_t* nstates, uint32_t* nelt);
 /* GenomeHit::extend hi_aligner.h:2031 (+alignWithALTs :683, _recur :2763 without ALTs,
  * calculateScore :3711).  seq/qual in the hit's orientation. */
 int  h2o_extend(const h2o_index*, const h2o_scoring*, const uint8_t* seq, const char* qual, uint32_t rdlen,

@@ -422,7 +422,10 @@ int main(int argc, char** argv) {
 		return 0;
 	}
 	if(cmd == "psearch" || cmd == "lsearch" || cmd == "coords" || cmd == "extend" || cmd == "sw" || cmd == "adjust") {
-		// <cmd> <base> <reads.fa> <nospliced:0|1>
+		// <cmd> <base> <reads.fa> <nospliced:0|1> [...] [maxrows=N]: the trailing "maxrows=N" lifts the 16-row limit on the ranges that coords / extend /
+		// adjust resolve (dense graphs: long in-edge lists need wide ranges)
+		index_t maxrows = 16;
+		if(argc > 4 && strncmp(argv[argc - 1], "maxrows=", 8) == 0) { maxrows = (index_t)atoi(argv[argc - 1] + 8); argc--; }
 		vector<Read*> rds;
 		loadReads(argv[3], rds);
 		bool nospliced = (argc > 4) ? atoi(argv[4]) != 0 : true;
@@ -498,7 +501,7 @@ int main(int argc, char** argv) {
 					putchar('\n');
 					continue;
 				}
-				if(ph.empty() || ph._bot - ph._top > 16) continue;
+				if(ph.empty() || ph._bot - ph._top > maxrows) continue;
 				EList<Coord> coords;
 				bool straddled = false;
 				index_t rdoff = hit._len - ph._bwoff - ph._len;

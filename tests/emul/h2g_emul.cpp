@@ -8,8 +8,15 @@
 #include <vector>
 #include <stdlib.h>
 #include <string.h>
-// the host instantiation runs with the large-workspace capacities (one workspace, no second pass on the host)
-#ifndef H2G_MEMPROF   // tools/memprof profiles the default device workspace layout
+// the host instantiation runs with the large-workspace capacities (one workspace, no second pass on the host) unless the compile line names another of the
+// shipped capacity sets: -DH2GEMU_CAPS=1 the DEFAULT units' (no capacity header), -DH2GEMU_CAPS=2 the graph fast pass's (h2g_go_fast_graph_caps.h, the
+// header h2g_k_go_fast_graph.hip itself includes)
+#ifndef H2GEMU_CAPS
+#define H2GEMU_CAPS 0
+#endif
+#if H2GEMU_CAPS == 2
+#include "../../hisat2_amd/csrc/h2g_go_fast_graph_caps.h"
+#elif H2GEMU_CAPS == 0 && !defined(H2G_MEMPROF)   // tools/memprof profiles the default device workspace layout
 #include "../../hisat2_amd/csrc/h2g_go_big.h"
 #endif
 #include "../../hisat2_amd/csrc/h2g_core.h"

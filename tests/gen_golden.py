@@ -22,6 +22,10 @@ for a small seeded genome ("g1"):
 `gen_golden.py ragged` adds the TRIMMED read sets (tests/ragged_cases.py) on the index g1, without touching the above:
   ragged_se.fq.gz, ragged_pe_{1,2}.fq.gz   2000 reads / 1500 pairs of 0-300 bases, mates of different lengths, empty records
   ragged_{se,pe}.sam.gz, ragged_{se,pe}.err.gz   hisat2-align-s -q -p 1 --no-spliced-alignment: the SAM body, and stderr (length-filter warnings + summary)
+`gen_golden.py dense` adds the IN-EDGE-RICH graph fixture (tests/dense_cases.py: families of repeat copies with SNPs at the same element offsets):
+  gdense.fa.gz, gdense.snp.gz, gdense.{1..8}.ht2.gz, reads_gdense_kmers.fa.gz (3000 k-mers of 10-24 bases from the alternate haplotype)
+  probe_gdense_{psearch,coords,extend,adjust}.txt.gz   ranges of up to 64 rows (ref_probe ... maxrows=64): in-edge lists and node ranges of up to 64
+  reads_gdense_{se,pe_1,pe_2}.fa.gz, ref_gdense_{se,pe}.sam.gz   2000 reads / 1000 pairs of 101 bases and their --no-spliced-alignment SAM bodies
 Everything is deterministic (seeds below); the fixtures are committed.
 """
 import gzip
@@ -380,9 +384,55 @@ def main_ragged():
             print(f, os.path.getsize(os.path.join(GOLD, f)))
 
 
+def main_dense():
+    """tests/dense_cases.py: the in-edge-rich graph fixture gdense (families of diverged repeat copies that carry SNPs at the same element offsets), its k-mers of
+    10-24 bases from the alternate haplotype, the reference's vectors over them (ranges of up to DC.MAXROWS rows: `maxrows=`), the 2000 reads and 1000 pairs of
+    101 bases from the alternate haplotype and the reference's SAM for them"""
+    sys.path.insert(0, HERE)
+    import dense_cases as DC
+    tmp = tempfile.mkdtemp(prefix="h2goldd")
+    g, where = DC.make_dense_genome()
+    snps = DC.make_dense_snps(g, where)
+    fa, snpf, base = os.path.join(tmp, "gdense.fa"), os.path.join(tmp, "gdense.snp"), os.path.join(tmp, "gdense")
+    synth.write_fasta(fa, [g], names=[DC.NAME])
+    synth.write_snps(snpf, snps)
+    run([os.path.join(REF, "hisat2-build-s"), "-q", "--snp", snpf, fa, base])
+    gz_write(os.path.join(GOLD, "gdense.fa.gz"), open(fa, "rb").read())
+    gz_write(os.path.join(GOLD, "gdense.snp.gz"), open(snpf, "rb").read())
+    for k in range(1, 9):
+        gz_write(os.path.join(GOLD, f"gdense.{k}.ht2.gz"), open(f"{base}.{k}.ht2", "rb").read())
+    kfa = os.path.join(tmp, "kmers.fa")
+    DC.write_ragged_fasta(kfa, DC.make_kmers(g, where, snps))
+    gz_write(os.path.join(GOLD, "reads_gdense_kmers.fa.gz"), open(kfa, "rb").read())
+    probe = os.path.join(REF, "ref_probe")
+    for name in ("psearch", "coords", "extend", "adjust"):
+        out = run([probe, name, base, kfa, "1", f"maxrows={DC.MAXROWS}"]).stdout
+        if name in ("extend", "adjust"):                       # one line per coordinate (and mismatch budget): every DC.THIN-th keeps the files small
+            out = b"".join(out.splitlines(True)[::DC.THIN])
+        gz_write(os.path.join(GOLD, f"probe_gdense_{name}.txt.gz"), out)
+        print(name, len(out.splitlines()), "lines")
+    reads, m1, m2 = DC.make_reads(g, snps)
+    files = {}
+    for tag, rs in (("se", reads), ("pe_1", m1), ("pe_2", m2)):
+        files[tag] = os.path.join(tmp, f"reads_gdense_{tag}.fa")
+        synth.write_reads_fasta(files[tag], rs)
+        gz_write(os.path.join(GOLD, f"reads_gdense_{tag}.fa.gz"), open(files[tag], "rb").read())
+    for tag, inputs in (("se", ["-U", files["se"]]), ("pe", ["-1", files["pe_1"], "-2", files["pe_2"]])):
+        sam = os.path.join(tmp, tag + ".sam")
+        run([os.path.join(REF, "hisat2-align-s"), "-f", "-p", "1", "--no-spliced-alignment", "-x", base, "-S", sam] + inputs)
+        body = [l for l in open(sam, "rb") if not l.startswith(b"@")]
+        gz_write(os.path.join(GOLD, f"ref_gdense_{tag}.sam.gz"), b"".join(body))
+    shutil.rmtree(tmp)
+    for f in sorted(os.listdir(GOLD)):
+        if "gdense" in f:
+            print(f, os.path.getsize(os.path.join(GOLD, f)))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "frag":
         main_frag()
+    elif len(sys.argv) > 1 and sys.argv[1] == "dense":
+        main_dense()
     elif len(sys.argv) > 1 and sys.argv[1] == "ragged":
         main_ragged()
     elif len(sys.argv) > 1 and sys.argv[1] == "combine":

@@ -145,7 +145,7 @@ def graph_genome():
     dict(n=2000, rdlen=125, sub=0.01, alt=True),
 ])
 def test_graph_pairs_equal_the_machine(graph_genome, case):
-    """the fast path over a graph index (FG_GRAPH = 1, tests/emul/libh2gemu_g.so = the configuration of h2g_k_go_fast_graph.hip): node ranges and
+    """the fast path over a graph index (FG_GRAPH = 1, tests/emul/libh2gemu_g.so = the PASS's configuration of h2g_k_go_fast_graph.hip at the *_big CAPACITIES; that unit's own capacities: h2g_caps_check_gfast, tests/test_graph_caps_cpu.py): node ranges and
     in-edge lists of the partial hits, adjustWithALT of every coordinate, ALT-aware extension and joins, ALT ids in the reported edits"""
     base, ref, alt = graph_genome
     m1, m2 = synth.make_pairs(alt if case["alt"] else ref, case["n"], case["rdlen"], 177 + case["n"], frag_mean=case.get("frag_mean", 300), frag_sd=case.get("frag_sd", 30), sub_rate=case["sub"])

@@ -239,6 +239,41 @@ def test_graph_adjust_with_alt_golden(ggpu, golden_dir):
     assert PC.check_graph_adjust(ggpu, golden_dir, "probe_g1s_adjust.txt.gz") > 250
 
 
+# ---- the in-edge-rich graph gdense (tests/dense_cases.py) through the C-ABI primitives: the DEFAULT capacities (in-edge lists of 24, 24 nodes, 40 states), so
+# a result is the reference's or flagged, and only a case that, by the oracle's walk of it, does not fit those capacities may be flagged
+@pytest.fixture(scope="module")
+def dgpu(tmp_path_factory, golden_dir):
+    import dense_cases as DC
+    base = PC.unpack_index(golden_dir, "gdense", tmp_path_factory.mktemp("gdense"))
+    ix = api.Index(base, device=0)
+    codes, offs = DC.load_kmers(golden_dir)
+    st = api.Stream(ix, max_reads=len(offs) - 1, max_bases=int(codes.size))
+    st.set_reads(codes, offs)
+    st.base = base
+    yield st
+    st.close()
+    ix.close()
+
+
+def test_dense_genome_coords_equal_or_flagged(dgpu, oracle_lib, golden_dir):
+    import dense_cases as DC
+    cases = PC.parse_graph_coords(golden_dir, "probe_gdense_coords.txt.gz")
+    needs = DC.coords_needs(oracle_lib, H.load_index(oracle_lib, dgpu.base), cases)
+    n, nflag = DC.check_coords_abi(dgpu, cases, needs, DC.CAPS["gdef"])
+    print("gdense coordinates on the device:", n, "cases,", nflag, "flagged")
+    assert n > 1500 and 0 < nflag == sum(1 for x in needs if not DC.fits(x, DC.CAPS["gdef"]))
+
+
+def test_dense_partial_search_extend_adjust(dgpu, golden_dir):
+    import dense_cases as DC
+    n, nlong = DC.check_psearch_abi(dgpu, golden_dir)
+    assert n == 6000
+    n, nflag = DC.check_extend_abi(dgpu, golden_dir)
+    assert n > 10000 and nflag == 0          # (no extension of a k-mer comes near 24 new edits)
+    n, nflag = DC.check_adjust_abi(dgpu, golden_dir)
+    assert n > 2500 and nflag == 0
+
+
 def test_graph_lf_vs_oracle_random(ggpu, oracle_lib, g1s_index):
     oix = H.load_index(oracle_lib, g1s_index)
     g = C.byref(oix.contents.g)

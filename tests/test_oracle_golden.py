@@ -474,3 +474,91 @@ def test_frag_extend(oracle_lib, gfrag_index, golden_dir, fn):
         got = [ext, h.rdoff, h.len, h.toff, h.joinedOff, le.value, re.value, h.score, h.nedits]
         assert got == list(map(int, r[:9])), (c[:9], got, r)
         assert [f"{h.edits[k].pos}:{chr(h.edits[k].chr)}>{chr(h.edits[k].qchr)}" for k in range(h.nedits)] == r[9:], (c[:9], r)
+
+
+# ---------------------------------------------------------------- the in-edge-rich graph (gdense, tests/dense_cases.py): the oracle itself against the new vectors
+@pytest.fixture(scope="module")
+def gdense_index(tmp_path_factory, golden_dir):
+    import parity_cases as PC
+    return PC.unpack_index(golden_dir, "gdense", tmp_path_factory.mktemp("gdense"))
+
+
+def test_dense_partial_search(oracle_lib, gdense_index, golden_dir):
+    """partial searches of 10-24 base k-mers of repeat copies: in-edge lists of up to a few dozen entries"""
+    ix = H.load_index(oracle_lib, gdense_index)
+    _, seqs = H.read_fasta_reads(os.path.join(golden_dir, "reads_gdense_kmers.fa.gz"))
+    u32 = C.c_uint32
+    n = nlong = 0
+    for l in H.glines(golden_dir, "probe_gdense_psearch.txt.gz"):
+        f = l.split()
+        v = list(map(int, f[:15]))
+        ie = [tuple(map(int, x.split(":"))) for x in f[16:]]
+        seq = np.ascontiguousarray(seqs[v[0]] if v[1] else H.revcomp(seqs[v[0]]))
+        o = H.BwtHit()
+        buf = (u32 * 256)()
+        nie = u32()
+        oracle_lib.h2o_partial_search_graph(ix, seq.ctypes.data, len(seq), 0, 0, 1, 10, 20, C.byref(o), buf, 128, nie)
+        got = [o.top, o.bot, o.node_top, o.node_bot, o.bwoff, o.len, o.hit_type, o.cur, o.done, o.numPartialSearch, o.numUniqueSearch, o.pseudogeneStop, o.anchorStop]
+        assert got == v[2:], (l, got)
+        assert [(buf[2 * i], buf[2 * i + 1]) for i in range(nie.value)] == ie, l
+        n += 1
+        nlong += len(ie) > 4
+    assert n == 6000 and nlong > 0
+
+
+def test_dense_genome_coords_and_walk_readout(oracle_lib, gdense_index, golden_dir):
+    """the group walk over ranges of up to 64 rows (every case: dense_cases.coords_needs asserts the reference's coordinates) and its read-out: the longest
+    in-edge list a walk met is at least the list it was called with, and the fixture fills every window between the shipped capacity sets"""
+    import dense_cases as DC
+    import parity_cases as PC
+    ix = H.load_index(oracle_lib, gdense_index)
+    cases = PC.parse_graph_coords(golden_dir, "probe_gdense_coords.txt.gz")
+    needs = DC.coords_needs(oracle_lib, ix, cases)
+    assert all(n[0] >= len(c[4]) and n[1] >= 1 and n[2] == c[3] - c[2] for c, n in zip(cases, needs))
+    assert any(n[0] > len(c[4]) for c, n in zip(cases, needs))          # a walk meets longer lists than it starts with
+    w = DC.windows(cases, needs)
+    assert w["ie3_4"] >= 50 and w["ie5_8"] >= 50 and w["ie9_24"] >= 20 and w["nodes5_8"] >= 50 and w["nodes9_24"] >= 50, w
+
+
+def test_dense_extend_with_alts(oracle_lib, gdense_index, golden_dir):
+    ix = H.load_index(oracle_lib, gdense_index)
+    _, seqs = H.read_fasta_reads(os.path.join(golden_dir, "reads_gdense_kmers.fa.gz"))
+    sc = H.Scoring()
+    oracle_lib.h2o_scoring_default(C.byref(sc))
+    n = nsnp = 0
+    for l in H.glines(golden_dir, "probe_gdense_extend.txt.gz"):
+        lhs, rhs = l.split(" -> ")
+        rid, fw, rdoff, hlen, tidx, toff, joff, mm = map(int, lhs.split())
+        r = rhs.split()
+        seq = np.ascontiguousarray(seqs[rid] if fw else H.revcomp(seqs[rid]))
+        h = H.GHit()
+        h.fw, h.rdoff, h.len, h.tidx, h.toff, h.joinedOff = fw, rdoff, hlen, tidx, toff, joff
+        le, re = C.c_uint32(H.MAX), C.c_uint32(H.MAX)
+        ext = oracle_lib.h2o_extend(ix, C.byref(sc), seq.ctypes.data, b"I" * len(seq), len(seq), C.byref(h), C.byref(le), C.byref(re), mm)
+        got = [ext, h.rdoff, h.len, h.toff, h.joinedOff, le.value, re.value, h.score, h.nedits]
+        assert got == list(map(int, r[:9])), (l, got)
+        eds = [f"{h.edits[k].pos}:{chr(h.edits[k].chr)}>{chr(h.edits[k].qchr)}:{h.edits[k].type}:{-1 if h.edits[k].snp == H.MAX else h.edits[k].snp}"
+               for k in range(h.nedits)]
+        assert eds == r[9:], (l, eds)
+        n += 1
+        nsnp += any(not e.endswith(":-1") for e in eds)
+    assert n > 10000 and nsnp > 0          # (a k-mer is mostly one exact hit: little is left to extend; the ALT-rich extensions are the g1s vectors)
+
+
+def test_dense_adjust_with_alt(oracle_lib, gdense_index, golden_dir):
+    import parity_cases as PC
+    ix = H.load_index(oracle_lib, gdense_index)
+    _, seqs = H.read_fasta_reads(os.path.join(golden_dir, "reads_gdense_kmers.fa.gz"))
+    u32 = C.c_uint32
+    n = nsnp = 0
+    for rid, fw, rdoff, ln, tidx, toff, joff, found, want in PC.parse_adjust(golden_dir, "probe_gdense_adjust.txt.gz"):
+        seq = np.ascontiguousarray(seqs[rid] if fw else H.revcomp(seqs[rid]))
+        hits = (H.GHit * 8)()
+        nh = u32(0)
+        r = oracle_lib.h2o_adjust_with_alt(ix, seq.ctypes.data, fw, rdoff, ln, tidx, toff, joff, hits, C.byref(nh), 8)
+        got = [([hits[k].rdoff, hits[k].len, hits[k].toff, hits[k].joinedOff, hits[k].nedits], PC.edit_strings_snp(hits[k].edits, hits[k].nedits))
+               for k in range(nh.value)]
+        assert r == found and got == want, (rid, fw, got, want)
+        n += 1
+        nsnp += any(w[0][4] > 0 for w in want)
+    assert n > 2500 and nsnp > 100
