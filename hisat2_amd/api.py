@@ -282,6 +282,25 @@ WINDOW_SEG_DTYPE = np.dtype([("text_start", np.uint64), ("name_off0", np.uint64)
 assert WINDOW_SEG_DTYPE.itemsize == C.sizeof(WindowSeg)
 
 
+class SamLine(C.Structure):
+    """h2g_sam_line (include/h2g.h): one SAM line as the planner decides it, 64 bytes"""
+    _fields_ = [("read", C.c_uint32), ("nh", C.c_uint32), ("rec_off", C.c_uint64), ("orec_off", C.c_uint64), ("tlen", C.c_int64), ("zs", C.c_int32), ("oref_tidx", C.c_int32),
+                ("oref_toff", C.c_uint32), ("aux_off", C.c_uint32), ("aux_len", C.c_uint32), ("flag", C.c_uint16), ("cigar_len", C.c_uint16), ("mdz_len", C.c_uint16),
+                ("mapq", C.c_uint8), ("mate", C.c_uint8), ("yt", C.c_uint8), ("yf", C.c_uint8), ("bits", C.c_uint16)]
+
+
+SAM_LINE_DTYPE = np.dtype([("read", np.uint32), ("nh", np.uint32), ("rec_off", np.uint64), ("orec_off", np.uint64), ("tlen", np.int64), ("zs", np.int32), ("oref_tidx", np.int32),
+                           ("oref_toff", np.uint32), ("aux_off", np.uint32), ("aux_len", np.uint32), ("flag", np.uint16), ("cigar_len", np.uint16), ("mdz_len", np.uint16),
+                           ("mapq", np.uint8), ("mate", np.uint8), ("yt", np.uint8), ("yf", np.uint8), ("bits", np.uint16)])
+assert SAM_LINE_DTYPE.itemsize == C.sizeof(SamLine) == 64
+SAM_LINE_HAS_ZS, SAM_LINE_HAS_YS, SAM_LINE_HAS_TLEN, SAM_LINE_STAR_SEQ, SAM_LINE_STRIP_MATE_SUFFIX, SAM_LINE_AUX_CIGAR_MDZ, SAM_LINE_WHOLE_LINE, SAM_LINE_SENSE_MATE1 = 1, 2, 4, 8, 16, 32, 64, 128
+SAM_NONE = (1 << 64) - 1     # rec_off / orec_off of a line without that record
+
+
+class SamTextStats(C.Structure):
+    _fields_ = [("bytes_uploaded", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float), ("write_kernel_ms", C.c_float)]
+
+
 EXPORTS = [
     "h2g_load_opts_init", "h2g_index_load", "h2g_index_get_info", "h2g_index_synth_sides", "h2g_index_free", "h2g_index_set_splice_sites", "h2g_index_add_splice_sites",
     "h2g_last_error", "h2g_stream_create", "h2g_stream_free", "h2g_stream_hip", "h2g_stream_sync", "h2g_stream_select_batch", "h2g_set_reads",
@@ -295,11 +314,86 @@ EXPORTS = [
     "h2g_index_dense_lsa_check",
     "h2g_window_plan_create", "h2g_window_plan_add_file", "h2g_window_plan_get_info", "h2g_window_plan_text", "h2g_window_plan_prefixes", "h2g_window_plan_segments",
     "h2g_window_plan_select", "h2g_window_plan_free", "h2g_set_reads_windows", "h2g_get_windows_stats", "h2g_fetch_reads",
+    "h2g_sam_plan_unpaired_compact", "h2g_sam_plan_paired_compact", "h2g_sam_text_unpaired", "h2g_sam_text_paired", "h2g_sam_text_from_plan_host", "h2g_get_sam_text_stats",
 ]
 
 
 class H2GError(RuntimeError):
     pass
+
+
+def _ptr(x):
+    """address of a numpy array / bytes / ctypes object, None for None"""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    if isinstance(x, bytes):                      # (the caller keeps the object alive through the call)
+        return C.cast(C.c_char_p(x), C.c_void_p).value
+    if isinstance(x, int):
+        return x
+    return C.addressof(x)
+
+
+def _sam_plan(call, n, head, tail):
+    """runs a planning call, growing the descriptor array and the pool once when the first sizes were too small (H2G_ERR_ARG with the needed counts)"""
+    line_cap, aux_cap = 2 * n + 16, 64 * n + 256
+    ends = np.zeros(max(n, 1), dtype=np.uint64)
+    for attempt in range(2):
+        lines = np.zeros(line_cap, dtype=SAM_LINE_DTYPE)
+        aux = np.zeros(max(aux_cap, 1), dtype=np.uint8)
+        nl, na = C.c_size_t(0), C.c_size_t(0)
+        rc = call(*head, n, *tail, lines.ctypes.data, line_cap, C.byref(nl), aux.ctypes.data, aux_cap, C.byref(na), ends.ctypes.data)
+        if rc == 0:
+            return lines[:nl.value], aux[:na.value], ends[:n]
+        if attempt or rc != H2G_ERR_ARG or (nl.value <= line_cap and na.value <= aux_cap):
+            _chk(rc, "h2g_sam_plan")
+        line_cap, aux_cap = max(line_cap, nl.value), max(aux_cap, na.value)
+
+
+def sam_plan_unpaired(sam, codes, offs, quals, name_bytes, name_offs, res, rec, boffs):
+    """h2g_sam_plan_unpaired_compact over the arguments of h2g_sam_format_unpaired_compact (sam: the handle of h2g_sam_open) -> (lines [SAM_LINE_DTYPE], pool bytes,
+    line_ends [n]); the handle counts what the format call would have counted"""
+    n = len(offs) - 1
+    keep = (codes, offs, quals, name_bytes, name_offs, res, rec, boffs)
+    return _sam_plan(lib().h2g_sam_plan_unpaired_compact, n, [sam] + [_ptr(x) for x in keep[:5]], [_ptr(x) for x in keep[5:]])
+
+
+def sam_plan_paired(sam, codes1, offs1, quals1, name_bytes1, name_offs1, codes2, offs2, quals2, name_bytes2, name_offs2, res, rec1, boffs1, rec2, boffs2, khits):
+    """h2g_sam_plan_paired_compact -> (lines, pool bytes, line_ends [n])"""
+    n = len(offs1) - 1
+    keep = (codes1, offs1, quals1, name_bytes1, name_offs1, codes2, offs2, quals2, name_bytes2, name_offs2, res, rec1, boffs1, rec2, boffs2)
+    return _sam_plan(lib().h2g_sam_plan_paired_compact, n, [sam] + [_ptr(x) for x in keep[:10]], [_ptr(x) for x in keep[10:]] + [khits])
+
+
+def _sam_text(call, n_lines, cap=None):
+    """runs a text call: first with `cap` (default: sized by a first call that only reports the bytes needed), -> (text bytes, line_offs [n_lines + 1])"""
+    used = C.c_size_t(0)
+    offs = np.zeros(n_lines + 1, dtype=np.uint64)
+    if cap is None:
+        rc = call(None, 0, C.byref(used), None)
+        if rc not in (0, H2G_ERR_ARG) or (rc == H2G_ERR_ARG and used.value == 0):
+            _chk(rc, "h2g_sam_text")
+        cap = used.value
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    _chk(call(out.ctypes.data, cap, C.byref(used), offs.ctypes.data), "h2g_sam_text")
+    return out[:used.value].tobytes(), offs
+
+
+def sam_text_from_plan_host(sam, set1, set2, rec1, rec2, lines, aux, cap=None):
+    """h2g_sam_text_from_plan_host: the emitter's host instantiation.  set1 / set2 = (codes, offs, quals, name_bytes, name_offs) as given to the planner (set2 None for
+    an unpaired plan) -> (text bytes, line_offs)"""
+    lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
+    aux = np.ascontiguousarray(aux, dtype=np.uint8)
+    n = len(set1[1]) - 1
+    a = [_ptr(x) for x in set1] + ([_ptr(x) for x in set2] if set2 is not None else [None] * 5)
+    nr1 = 0 if rec1 is None else len(rec1)
+    nr2 = 0 if rec2 is None else len(rec2)
+    keep = (set1, set2, rec1, rec2)
+    call = lambda out, cap_, used, offs: lib().h2g_sam_text_from_plan_host(sam, *a, n, _ptr(rec1), nr1, _ptr(rec2), nr2, lines.ctypes.data, len(lines), aux.ctypes.data, len(aux), out, cap_, used, offs)
+    r = _sam_text(call, len(lines), cap)
+    del keep
+    return r
 
 
 _lib = None
@@ -383,6 +477,13 @@ def lib():
     L.h2g_get_windows_stats.argtypes = [vp, P(WindowsStats)]
     L.h2g_fetch_reads.argtypes = [vp, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(C.c_int), vp, vp, vp, vp, vp]
     L.h2g_align_pairs_run.argtypes = [vp, P(AlignParams)]
+    sz = C.c_size_t
+    L.h2g_sam_plan_unpaired_compact.argtypes = [vp] * 6 + [sz, vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz), vp]
+    L.h2g_sam_plan_paired_compact.argtypes = [vp] * 11 + [sz, vp, vp, vp, vp, vp, u32, vp, sz, P(sz), vp, sz, P(sz), vp]
+    L.h2g_sam_text_unpaired.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, P(sz), vp]
+    L.h2g_sam_text_paired.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, P(sz), vp]
+    L.h2g_sam_text_from_plan_host.argtypes = [vp] * 11 + [sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, P(sz), vp]
+    L.h2g_get_sam_text_stats.argtypes = [vp, P(SamTextStats)]
     L.h2g_align_pairs_fetch.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_pairs_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
@@ -848,6 +949,28 @@ class Stream:
             if attempt or rc != H2G_ERR_ARG or int(offs[n]) <= cap:
                 _chk(rc, "h2g_align_fetch_compact")
             cap = int(offs[n]) + 8
+
+    sam_plan_unpaired = staticmethod(sam_plan_unpaired)
+    sam_plan_paired = staticmethod(sam_plan_paired)
+
+    def _sam_text_dev(self, f, sam, lines, aux, cap):
+        lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
+        aux = np.ascontiguousarray(aux, dtype=np.uint8)
+        call = lambda out, cap_, used, offs: f(self.h, sam, lines.ctypes.data, len(lines), aux.ctypes.data, len(aux), out, cap_, used, offs)
+        return _sam_text(call, len(lines), cap)
+
+    def sam_text_unpaired(self, sam, lines, aux, cap=None):
+        """the text of a plan on the device (h2g_sam_text_unpaired), right after align_fetch_compact of the reads the plan was made from -> (text bytes, line_offs)"""
+        return self._sam_text_dev(lib().h2g_sam_text_unpaired, sam, lines, aux, cap)
+
+    def sam_text_paired(self, sam, lines, aux, cap=None):
+        """... after align_pairs_fetch_compact (h2g_sam_text_paired)"""
+        return self._sam_text_dev(lib().h2g_sam_text_paired, sam, lines, aux, cap)
+
+    def sam_text_stats(self):
+        st = SamTextStats()
+        _chk(lib().h2g_get_sam_text_stats(self.h, C.byref(st)), "h2g_get_sam_text_stats")
+        return st
 
     def align_fetch_long_edits(self):
         """the used prefix of the stream's long-edit area (records with nedits > MAX_EDITS: edits[0].pos is their offset in it) -> (Edit array or None, n)"""

@@ -80,11 +80,13 @@ struct Pinned {
 	Pinned(const Pinned&) = delete;
 	~Pinned() { h2g_host_free(p); }
 };
-struct PinSet { Pinned res, rec1, rec2, o1, o2; std::vector<h2g_edit> long_edits; size_t nlong = 0; };
+struct PinSet { Pinned res, rec1, rec2, o1, o2; std::vector<h2g_edit> long_edits; size_t nlong = 0;
+                Pinned text, loffs; /* --h2g-device-sam: the item's SAM text and line starts as the device wrote them */ };
 
 // ---- the command line
 struct Options {
 	std::string base, outfn, stats_fn;
+	bool device_sam = false;                  // --h2g-device-sam: the SAM text is written on the device from a host-made line plan
 	std::vector<std::string> u, m1, m2, m12;
 	ReadFormat tab_fmt = FMT_TAB5;
 	bool qseq = false, qc_filter = false, from_front_end = false;
@@ -200,7 +202,8 @@ Options parse_options(int argc, char** argv) {
 		else if(a == "--quiet") o.quiet = true;                                      // gQuiet: no alignment summary on stderr (hisat2.cpp:4165)
 		else if(a == "--version") { printf("hisat2-align-amd (h2g) — output format of HISAT2 2.2.3\n"); exit(0); }
 		else if(a == "--reorder" || a == "-t" || a == "--time" || a == "--mm") {}   // output is always in read order; --mm (index mapping) has nothing to act on here
-		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on} as JSON (tests, bench)
+		else if(a == "--h2g-device-sam") o.device_sam = true;
+		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on, device_sam_lines, whole_lines} as JSON (tests, bench)
 		else if(a == "--parse-only") o.parse_only = true;                           // test hook: ingest the reads, print counts + checksums
 		else if(const int arity = h2g_align_option_arity(argv[i]); arity >= 0) { o.opts.push_back(argv[i]); if(arity) o.opts.push_back(need(argv[i])); }   // every option that ends in a field of h2g_align_params
 		else { fprintf(stderr, "hisat2-align-amd: option %s is not built (see DESIGN.md, scope)\n", a.c_str()); exit(1); }
@@ -705,6 +708,7 @@ private:
 // what the stage has counted: written only by the stage (the thread that formats), read after finish()
 struct Totals {
 	uint64_t nreads = 0, naligned = 0, novf = 0;
+	uint64_t device_sam_lines = 0, whole_lines = 0;   // --h2g-device-sam: lines written on the device; of them, those that travelled as text (records beyond H2G_MAX_EDITS)
 	std::string ovf_names;                    // the first of the reads / pairs whose lists overflowed, with the bits
 	double t_fmt = 0;
 	void note_overflow(const char* name, size_t len, uint32_t bits) {
@@ -713,7 +717,7 @@ struct Totals {
 	}
 };
 // one fetched item: its reads lie in the parse stage's slot `batch`, its records in pinned set `set`
-struct FmtJob { long batch; size_t n; uint64_t first_id; int set; bool paired; int merge; };
+struct FmtJob { long batch; size_t n; uint64_t first_id; int set; bool paired; int merge; h2g_stream* st; /* the stream whose buffers still hold the item's compact fetch */ };
 
 // ---- the formatter: SAM text of the fetched items, in fetch order, into the writer's buffers; the --un / --al files; the junctions into the database; the totals.
 // On a thread of its own (round 6) the main thread fetches item k + 1's records while item k's text is written — what the device returns goes to one of two sets of
@@ -721,7 +725,7 @@ struct FmtJob { long batch; size_t n; uint64_t first_id; int set; bool paired; i
 // before the next wave starts, and submit() formats on the caller's thread.  Either way one thread formats: everything below the queue is that thread's.
 class FormatStage {
 public:
-	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites, warn_short; uint32_t khits; };
+	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites, warn_short; uint32_t khits; bool device_sam; };
 	FormatStage(const Config& c, h2g_sam* sam, ParseStage& parse, TextWriter& writer, ReadSorter& sorter, SpliceSites& sites, const Replicas& ix)
 		: c_(c), sam_(sam), parse_(parse), writer_(writer), sorter_(sorter), sites_(sites), ix_(ix) { if(c_.async) thread_ = std::thread(&FormatStage::run, this); }
 	~FormatStage() { finish(); }
@@ -766,7 +770,8 @@ private:
 		const bool qc = c_.qc_filter && !a.filt.empty();
 		h2g_sam_set_read_filter(sam_, qc ? a.filt.data() : nullptr, qc && paired ? b.filt.data() : nullptr);
 		auto grow = [&] { buf.resize(used + 16); return true; };
-		if(paired) {
+		if(c_.device_sam) device_text(job, buf, used, ends);
+		else if(paired) {
 			h2g_pair_result* pres = (h2g_pair_result*)ps.res.p;
 			uint64_t *ao1 = (uint64_t*)ps.o1.p, *ao2 = (uint64_t*)ps.o2.p;
 			buf.resize(n * 1400 + 6 * (a.codes.size() + b.codes.size()) + 4096);
@@ -787,6 +792,54 @@ private:
 		h2g_sam_set_record_ends(sam_, nullptr);
 		h2g_sam_set_read_ids(sam_, nullptr);
 		h2g_sam_set_read_filter(sam_, nullptr, nullptr);
+	}
+	// --h2g-device-sam: the same decisions as a line plan (h2g_sam_plan_*_compact; the handle counts what the format call would), the bytes by the device from the
+	// batch and the compact records its stream still holds (h2g_sam_text_*) into the pinned set, and from there into `buf`; `ends` from the line starts.  The caller
+	// (format_item) has set the handle up; one thread both fetches and formats in this mode, so nothing has touched the stream since the fetch.
+	void device_text(const FmtJob& job, RawBuf& buf, size_t& used, std::vector<uint64_t>* ends) {
+		Batch& a = parse_.a(job.batch); Batch& b = parse_.b(job.batch);
+		PinSet& ps = pins_[job.set];
+		const size_t n = job.n;
+		size_t nl = 0, na = 0;
+		if(n == 0) { used = 0; return; }
+		if(plan_lines_.size() < 2 * n + 16) plan_lines_.resize(2 * n + 16);
+		if(plan_aux_.size() < 64 * n + 4096) plan_aux_.resize(64 * n + 4096);
+		plan_ends_.resize(n + 1);
+		auto plan = [&] {
+			if(job.paired)
+				return h2g_sam_plan_paired_compact(sam_, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, a.names.data(), a.noffs.data(),
+				                                   b.codes.data(), b.offs.data(), b.have_quals ? b.quals.data() : nullptr, b.names.data(), b.noffs.data(), n,
+				                                   (const h2g_pair_result*)ps.res.p, ps.rec1.p, (const uint64_t*)ps.o1.p, ps.rec2.p, (const uint64_t*)ps.o2.p, c_.khits,
+				                                   plan_lines_.data(), plan_lines_.size(), &nl, plan_aux_.data(), plan_aux_.size(), &na, plan_ends_.data());
+			return h2g_sam_plan_unpaired_compact(sam_, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, a.names.data(), a.noffs.data(), n,
+			                                     (const h2g_read_result*)ps.res.p, ps.rec1.p, (const uint64_t*)ps.o1.p,
+			                                     plan_lines_.data(), plan_lines_.size(), &nl, plan_aux_.data(), plan_aux_.size(), &na, plan_ends_.data());
+		};
+		retry_on_small_buffer("h2g_sam_plan_compact", plan, [&] {
+			if(nl <= plan_lines_.size() && na <= plan_aux_.size()) return false;
+			if(nl > plan_lines_.size()) plan_lines_.resize(nl);
+			if(na > plan_aux_.size()) plan_aux_.resize(na);
+			return true; });
+		ps.loffs.need((nl + 1) * 8);
+		ps.text.need(n * 1400 + 4096);
+		uint64_t* loffs = (uint64_t*)ps.loffs.p;
+		auto text = [&] {
+			return job.paired ? h2g_sam_text_paired(job.st, sam_, plan_lines_.data(), nl, plan_aux_.data(), na, (char*)ps.text.p, ps.text.cap, &used, loffs)
+			                  : h2g_sam_text_unpaired(job.st, sam_, plan_lines_.data(), nl, plan_aux_.data(), na, (char*)ps.text.p, ps.text.cap, &used, loffs);
+		};
+		retry_on_small_buffer("h2g_sam_text", text, [&] { if(used <= ps.text.cap) return false; ps.text.need(used + 16); return true; });
+		buf.resize(used + 16);
+		memcpy(buf.data(), ps.text.p, used);
+		if(ends) for(size_t i = 0; i < n; i++) (*ends)[i] = nl ? loffs[plan_ends_[i]] : 0;
+		tot_.device_sam_lines += nl;
+		for(size_t j = 0; j < nl; j++) tot_.whole_lines += (plan_lines_[j].bits & H2G_SAM_LINE_WHOLE_LINE) != 0;
+		if(job.paired) {
+			const h2g_pair_result* pres = (const h2g_pair_result*)ps.res.p;
+			for(size_t i = 0; i < n; i++) { tot_.naligned += pres[i].npairs > 0; if(pres[i].overflow) tot_.note_overflow(a.names.data() + a.noffs[i], a.noffs[i + 1] - a.noffs[i], pres[i].overflow); }
+		} else {
+			const h2g_read_result* res = (const h2g_read_result*)ps.res.p;
+			for(size_t i = 0; i < n; i++) { tot_.naligned += res[i].nselect > 0; if(res[i].overflow) tot_.note_overflow(a.names.data() + a.noffs[i], a.noffs[i + 1] - a.noffs[i], res[i].overflow); }
+		}
 	}
 	// the original text of record i of an item goes to the --un / --al files its lines [t, te) name
 	void sort_record(const Batch& a, const Batch* b, size_t i, const char* t, const char* te) {
@@ -860,6 +913,7 @@ private:
 	SpliceSites& sites_;                      // (merge_sites, which excludes async: the main thread's)
 	const Replicas& ix_;
 	Totals tot_;                              // written by the formatting thread, read after finish()
+	std::vector<h2g_sam_line> plan_lines_; std::vector<char> plan_aux_; std::vector<uint64_t> plan_ends_;   // --h2g-device-sam: the line plan of the item being formatted
 	RawBuf mtext_[2];                         // a mixed window: the text and record ends of its two items, until both are formatted; the formatting thread's
 	size_t mused_[2] = {0, 0};
 	std::vector<uint64_t> mends_[2];
@@ -1002,7 +1056,7 @@ private:
 		}
 		{ h2g_counters hc; if(h2g_get_counters(st, &hc) == H2G_OK) { nsecond += hc.n_second_pass; nfast += hc.n_fast; nhanded += hc.n_fast_bail; } }
 		t_fetch += now() - tq0;
-		const FmtJob job{sg.batch, n, sg.first_id, set, sg.paired, sg.merge};
+		const FmtJob job{sg.batch, n, sg.first_id, set, sg.paired, sg.merge, st};
 		sg.batch = -1;                                  // (the stream's rows are copied: it can take the next batch)
 		fmt_.submit(job);
 	}
@@ -1090,12 +1144,13 @@ int main(int argc, char** argv) {
 	ReadSorter sorter;
 	for(int k = 0; k < RS_KINDS; k++) if(!o.rs_arg[k].empty()) sorter.open(k, o.rs_arg[k], o.rs_gz[k]);
 	const bool merge_sites = wv.temp_ss || !o.novel_out.empty();
-	const bool async_fmt = !merge_sites && !(getenv("H2G_CLI_ASYNC_FMT") && atoi(getenv("H2G_CLI_ASYNC_FMT")) == 0);
+	// (--h2g-device-sam: no formatter thread — the SAM handle and the stream would be touched from two threads)
+	const bool async_fmt = !merge_sites && !o.device_sam && !(getenv("H2G_CLI_ASYNC_FMT") && atoi(getenv("H2G_CLI_ASYNC_FMT")) == 0);
 	const int H = ix.streams() + (async_fmt ? 3 : 2);
 	// the stages; their destructors join in the reverse order, whatever way out is taken
 	TextWriter writer(out);
 	ParseStage parse(src, H, batch, wv, ix.streams());
-	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits}, sam, parse, writer, sorter, sites, ix);
+	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits, o.device_sam}, sam, parse, writer, sorter, sites, ix);
 	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch, wp.plan}, P, wv, ix, parse, fmt);
 	double t_parse = 0;                                   // what the main thread waited for the parser
 	bool short_mates = false;
@@ -1128,8 +1183,8 @@ int main(int argc, char** argv) {
 	        t_parse, parse.busy(), tot.t_fmt, t2 - t0, dev.t_stream, dev.t_up, dev.t_fetch);
 	if(!o.stats_fn.empty()) {
 		FILE* sf = fopen(o.stats_fn.c_str(), "w");
-		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
-		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded); fclose(sf); }
+		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu, \"device_sam_lines\": %llu, \"whole_lines\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
+		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded, (unsigned long long)tot.device_sam_lines, (unsigned long long)tot.whole_lines); fclose(sf); }
 	}
 	// (Measured and not shipped, round 6: ending the process here without the frees below saves this run 0.1 s and costs the NEXT process 1.7 s — the driver reclaims 40 GB of
 	// device memory of a process that did not return it while the next one is already allocating: profiles/r06_zc_ab.log.)

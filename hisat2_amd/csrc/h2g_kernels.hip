@@ -25,6 +25,7 @@
 #include "h2g_splice_host.h"
 #include "h2g_splice_db_host.h"
 #include "h2g_windows.h"   // the -F window expansion's per-read arithmetic
+#include "h2g_sam_line.h"  // the SAM line emitter the text kernels and the host share
 #include "h2g_go_args.h"   // GoArgs + the extern "C" face of the go() units (their AlignWS layouts are opaque on this side)
 
 using namespace h2g;
@@ -231,6 +232,15 @@ struct h2g_stream {
 	unsigned long long* d_counters = nullptr;   // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
 	void* d_tmp[4] = {nullptr, nullptr, nullptr, nullptr};
 	size_t tmp_sz[4] = {0, 0, 0, 0};
+	// SAM text on the device (h2g_sam_text_*): what d_tmp holds is nobody's once another call takes a slot, so every such call (tmp_buf), every batch selection and every call
+	// that sets reads, mates or names counts tmp_gen up; a compact fetch notes the count it ended with, and the text call runs only while the two are equal
+	uint64_t tmp_gen = 0;
+	struct CompactFetch { bool valid = false, paired = false; uint64_t gen = 0; unsigned batch = 0; size_t first = 0, n = 0; const uint8_t* d_rec[2] = {nullptr, nullptr}; uint64_t bytes[2] = {0, 0}; } cfetch;
+	void* d_sam[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // descriptors, pool, line offsets (+ scan tile sums + the check's flag), text, the handle's tables
+	size_t sam_sz[5] = {0, 0, 0, 0, 0};
+	uint64_t samtab_uid = 0, samtab_gen = 0; uint32_t samtab_nrefs = 0, samtab_names = 0, samtab_rg = 0, samtab_nalts = 0; int32_t samtab_strand = 0;   // whose tables d_sam[4] holds
+	hipEvent_t ev_sam[4] = {nullptr, nullptr, nullptr, nullptr};
+	h2g_sam_text_stats sam_stats = {};
 	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows)
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
@@ -880,6 +890,9 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		HIPCHK(hipMalloc((void**)&b0.d_quals, max_bases + 64));
 		HIPCHK(hipMalloc((void**)&b0.d_offs, (max_reads + 1) * 4));
 		HIPCHK(hipMalloc((void**)&s->d_seed, max_reads * 2 * sizeof(h2g_seed_result)));
+		// (a strand without coordinates leaves its `ext` entries as they are: zero, whatever block the allocator hands out — a recycled one made tests/test_gpu_frag.py's
+		// seed stage differ from the oracle's zero-filled rows)
+		HIPCHK(hipMemset(s->d_seed, 0, max_reads * 2 * sizeof(h2g_seed_result)));
 	}
 	memset(&s->last, 0, sizeof s->last);
 	{
@@ -919,6 +932,8 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 		(void)hipFree(B.d_ids);
 	}
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
+	for(int i = 0; i < 5; i++) (void)hipFree(s->d_sam[i]);
+	for(int i = 0; i < 4; i++) if(s->ev_sam[i]) (void)hipEventDestroy(s->ev_sam[i]);
 	for(int i = 0; i < 14; i++) (void)hipEventDestroy(s->ev[i]);
 	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { (void)hipStreamDestroy(s->mst[k]); (void)hipEventDestroy(s->ev_rot[k]); } (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
 	delete s;
@@ -977,6 +992,7 @@ extern "C" h2g_status h2g_stream_select_batch(h2g_stream* s, unsigned k) {
 		HIPCHK(hipMemsetAsync(in.d_aln, 0, out.aln_alloc * sizeof(h2g_alnres), s->st));
 	}
 	s->cur_batch = k;
+	s->tmp_gen++;
 	return H2G_OK;
 }
 
@@ -992,6 +1008,7 @@ static int grow(void** p, size_t* have, size_t want, size_t unit = 1, int n = 1)
 }
 
 static int tmp_buf(h2g_stream* s, int slot, size_t bytes, void** out) {
+	s->tmp_gen++;                                                            // (whatever a compact fetch left here is about to be overwritten)
 	const int rc = grow(&s->d_tmp[slot], &s->tmp_sz[slot], bytes + 256);     // (tmp_sz: the bytes allocated, 256 beyond the largest request)
 	*out = s->d_tmp[slot];
 	return rc;
@@ -1000,6 +1017,7 @@ static int tmp_buf(h2g_stream* s, int slot, size_t bytes, void** out) {
 extern "C" h2g_status h2g_set_reads(h2g_stream* s, const uint8_t* codes, const uint32_t* offs, const char* quals, size_t n) {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
 	if(!s || !codes || !offs || n > s->max_reads) return H2G_ERR_ARG;
+	s->tmp_gen++;
 	BatchCtx& B = s->cur();
 	size_t nb = offs[n];
 	if(nb > s->max_bases) return H2G_ERR_ARG;
@@ -2158,6 +2176,7 @@ extern "C" void h2g_align_params_init(h2g_align_params* p, const h2g_index* ix) 
 extern "C" h2g_status h2g_set_read_names(h2g_stream* s, const char* bytes, const uint32_t* offs, size_t n) {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
 	if(!s || !bytes || !offs || n != s->cur().n_reads || n == 0) return H2G_ERR_ARG;
+	s->tmp_gen++;
 	HIPCHK(hipSetDevice(s->ix->device));
 	BatchCtx& B = s->cur();
 	size_t nb = offs[n];
@@ -2181,6 +2200,7 @@ extern "C" h2g_status h2g_set_mates(h2g_stream* s, const uint8_t* codes2, const 
 	if(s) HIPCHK(sync_all(s));
 	if(!s || !codes2 || !offs2 || !nb2 || !noffs2 || n != s->cur().n_reads || n == 0) return H2G_ERR_ARG;
 	if(offs2[n] > s->max_bases) return H2G_ERR_ARG;
+	s->tmp_gen++;
 	BatchCtx& B = s->cur();
 	for(size_t i = 0; i < n; i++) { const uint32_t l = offs2[i + 1] - offs2[i]; if(l > B.max_read_len) B.max_read_len = l; }
 	HIPCHK(hipSetDevice(s->ix->device));
@@ -2272,6 +2292,7 @@ extern "C" h2g_status h2g_set_reads_windows(h2g_stream* s, const uint8_t* text, 
 {
 	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
 	if(!s || !text || !segs || n_segs == 0 || n_segs >= 0xffffffffull || len == 0 || (!prefixes && n_prefix_bytes)) return H2G_ERR_ARG;
+	s->tmp_gen++;
 	BatchCtx& B = s->cur();
 	// the kernels' table: the per-segment first read and first name byte, the text range the segments touch
 	std::vector<h2g_win::DSeg> ds(n_segs + 1);
@@ -3359,6 +3380,9 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 	if(boffs1[n]) HIPCHK(hipMemcpyAsync(rec1, d_b1, boffs1[n], hipMemcpyDeviceToHost, s->st));
 	if(boffs2[n]) HIPCHK(hipMemcpyAsync(rec2, d_b2, boffs2[n], hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipStreamSynchronize(s->st));
+	// the records stay where they are: h2g_sam_text_paired reads them while nothing else has taken the slots (tmp_gen)
+	s->cfetch.valid = true; s->cfetch.paired = true; s->cfetch.gen = s->tmp_gen; s->cfetch.batch = s->cur_batch; s->cfetch.first = first; s->cfetch.n = n;
+	s->cfetch.d_rec[0] = (const uint8_t*)d_b1; s->cfetch.d_rec[1] = (const uint8_t*)d_b2; s->cfetch.bytes[0] = boffs1[n]; s->cfetch.bytes[1] = boffs2[n];
 	return H2G_OK;
 }
 
@@ -3376,13 +3400,139 @@ extern "C" h2g_status h2g_align_fetch_compact(h2g_stream* s, h2g_read_result* re
 	const h2g_status hr = h2g_align_fetch(s, res, nullptr, first, n);           // (the headers; syncs the stream)
 	if(hr != H2G_OK) return hr;
 	if(boffs[n] > cap) return H2G_ERR_ARG;
-	if(boffs[n] == 0) return H2G_OK;
 	if((rc = tmp_buf(s, 1, boffs[n] + 8, &d_b))) return (h2g_status)rc;
+	s->cfetch.valid = true; s->cfetch.paired = false; s->cfetch.gen = s->tmp_gen; s->cfetch.batch = s->cur_batch; s->cfetch.first = first; s->cfetch.n = n;
+	s->cfetch.d_rec[0] = (const uint8_t*)d_b; s->cfetch.d_rec[1] = nullptr; s->cfetch.bytes[0] = boffs[n]; s->cfetch.bytes[1] = 0;
+	if(boffs[n] == 0) return H2G_OK;
 	hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, s->cur().d_aln + first * s->cur().aln_slots, s->cur().aln_slots, cnt, (uint32_t)(sizeof(ReadOut) / 4),
 	                   (const unsigned long long*)d_o, n, (uint8_t*)d_b, (const PairOut*)nullptr, (const h2g_alnres*)nullptr, 0);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(rec, d_b, boffs[n], hipMemcpyDeviceToHost, s->st));
 	HIPCHK(hipStreamSynchronize(s->st));
+	return H2G_OK;
+}
+
+// ------------------------------------------------------------------------------------------ SAM text from a line plan (include/h2g.h)
+// One descriptor per line (made on the host: h2g_sam_plan_*_compact) -> its bytes, by the emitter of h2g_sam_line.h.  k_sam_line_sizes runs it over a sink that counts,
+// one lane per line, after checking what the descriptor names in its record (the host has checked everything else: plan_check); the offsets are the scan of the sizes;
+// k_sam_line_write runs it over a sink that stores.  Same statements, so the two passes agree on every length.
+#define H2G_SAM_LANES 16u          // lanes per line in the write kernel: four lines per wave
+#define H2G_SAM_STAGE 256u         // staging bytes per line (LDS): the head and the tail of a line pass through it
+struct SamWaveSync {
+	// the lanes of a group are lanes of one wave: its LDS accesses are issued in program order, so only the compiler has to be told
+	__host__ __device__ static __forceinline__ void sync() {
+#if defined(__HIP_DEVICE_COMPILE__)
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+	}
+};
+__global__ __launch_bounds__(256) void k_sam_line_sizes(const h2g_line::Ctx c, const h2g_sam_line* lines, size_t n, unsigned long long* sizes, unsigned int* bad) {
+	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if(i > n) return;
+	if(i == n) { sizes[n] = 0; return; }
+	if(!h2g_line::line_records_ok(c, lines[i])) { atomicOr(bad, 1u); sizes[i] = 0; return; }
+	h2g_line::CountSink k;
+	h2g_line::emit_line(c, lines[i], k);
+	sizes[i] = k.n;
+}
+__global__ __launch_bounds__(256) void k_sam_line_write(const h2g_line::Ctx c, const h2g_sam_line* lines, size_t n, const unsigned long long* offs, char* out) {
+	__shared__ char stage[256 / H2G_SAM_LANES][H2G_SAM_STAGE];
+	const uint32_t g = threadIdx.x / H2G_SAM_LANES, lane = threadIdx.x % H2G_SAM_LANES;
+	const size_t i = blockIdx.x * (size_t)(256 / H2G_SAM_LANES) + g;
+	if(i >= n) return;
+	h2g_line::GroupSink<H2G_SAM_LANES, H2G_SAM_STAGE, SamWaveSync> k(out + offs[i], stage[g], lane);
+	h2g_line::emit_line(c, lines[i], k);
+}
+
+static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
+	if(!s || !S || !used || (n_lines && !lines) || (n_aux && !aux)) return H2G_ERR_ARG;
+	*used = 0;
+	const h2g_stream::CompactFetch& cf = s->cfetch;
+	if(!cf.valid || cf.gen != s->tmp_gen || cf.batch != s->cur_batch || cf.paired != paired) {
+		snprintf(g_err, sizeof g_err, "h2g_sam_text_%s: the stream's buffers do not hold a compact %s fetch of the selected batch any more (fetch again, then call this before anything else)", paired ? "paired" : "unpaired", paired ? "paired" : "unpaired");
+		return H2G_ERR_ARG;
+	}
+	const BatchCtx& B = s->cur();
+	if(!B.has_names || (paired && !B.has_mates) || cf.first + cf.n > B.n_reads) { snprintf(g_err, sizeof g_err, "h2g_sam_text: the selected batch has no names / mates"); return H2G_ERR_ARG; }
+	if(n_lines == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
+	HIPCHK(hipSetDevice(s->ix->device));
+	for(int k = 0; k < 4; k++) if(!s->ev_sam[k]) HIPCHK(hipEventCreate(&s->ev_sam[k]));
+	{	// the handle's tables: uploaded once, again when the handle's options changed
+		uint64_t uid, gen;
+		h2g_line::sam_tables_key(S, &uid, &gen);
+		if(uid != s->samtab_uid || gen != s->samtab_gen || !s->d_sam[4]) {
+			h2g_line::Tables t;
+			h2g_line::sam_tables(S, t);
+			const size_t nr = t.refname_offs.size() - 1, ob = (nr + 1) * 4;
+			int rc;
+			if((rc = grow(&s->d_sam[4], &s->sam_sz[4], ob + t.refnames.size() + t.rg.size() + 64))) return (h2g_status)rc;
+			HIPCHK(hipStreamSynchronize(s->st));                      // (a text kernel still reading the former tables)
+			HIPCHK(hipMemcpy(s->d_sam[4], t.refname_offs.data(), ob, hipMemcpyHostToDevice));
+			if(!t.refnames.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4] + ob, t.refnames.data(), t.refnames.size(), hipMemcpyHostToDevice));
+			if(!t.rg.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4] + ob + t.refnames.size(), t.rg.data(), t.rg.size(), hipMemcpyHostToDevice));
+			s->samtab_uid = uid; s->samtab_gen = gen; s->samtab_nrefs = (uint32_t)nr; s->samtab_names = (uint32_t)t.refnames.size(); s->samtab_rg = (uint32_t)t.rg.size();
+			s->samtab_nalts = t.nalts; s->samtab_strand = t.rna_strandness;
+		}
+	}
+	if(const char* why = h2g_line::plan_check(lines, n_lines, cf.n, paired, cf.bytes[0], cf.bytes[1], n_aux, s->samtab_nrefs)) { snprintf(g_err, sizeof g_err, "h2g_sam_text: %s", why); return H2G_ERR_ARG; }
+	const size_t n1 = n_lines + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
+	int rc;
+	if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64)) ||
+	   (rc = grow(&s->d_sam[2], &s->sam_sz[2], (n1 + ntiles + 2) * 8))) return (h2g_status)rc;
+	unsigned long long* v = (unsigned long long*)s->d_sam[2];
+	unsigned long long* ts = v + n1;
+	unsigned int* d_bad = (unsigned int*)(ts + ntiles + 1);
+	HIPCHK(hipMemcpyAsync(s->d_sam[0], lines, n_lines * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
+	if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], aux, n_aux, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemsetAsync(d_bad, 0, 8, s->st));
+	h2g_line::Ctx c;
+	c.names[0] = B.d_names; c.noffs[0] = B.d_name_offs; c.codes[0] = B.d_codes; c.offs[0] = B.d_offs; c.quals[0] = B.has_quals ? B.d_quals : nullptr;
+	c.names[1] = paired ? B.d_names2 : nullptr; c.noffs[1] = paired ? B.d_name_offs2 : nullptr; c.codes[1] = paired ? B.d_codes2 : nullptr; c.offs[1] = paired ? B.d_offs2 : nullptr;
+	c.quals[1] = paired && B.has_quals2 ? B.d_quals2 : nullptr;
+	c.rec[0] = cf.d_rec[0]; c.rec[1] = cf.d_rec[1]; c.nrec[0] = cf.bytes[0]; c.nrec[1] = cf.bytes[1];
+	c.aux = (const char*)s->d_sam[1]; c.n_aux = n_aux;
+	c.refname_offs = (const uint32_t*)s->d_sam[4]; c.refnames = (const char*)s->d_sam[4] + ((size_t)s->samtab_nrefs + 1) * 4; c.nrefs = s->samtab_nrefs;
+	c.rg = c.refnames + s->samtab_names; c.rg_len = s->samtab_rg; c.rna_strandness = s->samtab_strand; c.nalts = s->samtab_nalts;
+	c.first = (uint32_t)cf.first; c.paired = paired ? 1u : 0u;
+	const h2g_sam_line* d_lines = (const h2g_sam_line*)s->d_sam[0];
+	HIPCHK(hipEventRecord(s->ev_sam[0], s->st));
+	hipLaunchKernelGGL(k_sam_line_sizes, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, c, d_lines, n_lines, v, d_bad);
+	hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, s->st, v, n1, ts);
+	hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, s->st, ts, ntiles);
+	hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, v, n1, (const unsigned long long*)ts);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev_sam[1], s->st));
+	unsigned long long total = 0; unsigned int bad = 0;
+	HIPCHK(hipMemcpyAsync(&total, v + n_lines, 8, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipStreamSynchronize(s->st));
+	if(bad) { snprintf(g_err, sizeof g_err, "h2g_sam_text: a line names a record that does not end inside its mate's bytes, keeps its edits outside itself, or lies on a reference the index does not have"); return H2G_ERR_ARG; }
+	*used = (size_t)total;
+	if(total > cap || !out) return total == 0 ? H2G_OK : H2G_ERR_ARG;     // (nothing is written: the write kernel is not launched)
+	if((rc = grow(&s->d_sam[3], &s->sam_sz[3], (size_t)total + 64))) return (h2g_status)rc;
+	HIPCHK(hipEventRecord(s->ev_sam[2], s->st));
+	hipLaunchKernelGGL(k_sam_line_write, dim3((unsigned)((n_lines + 256 / H2G_SAM_LANES - 1) / (256 / H2G_SAM_LANES))), dim3(256), 0, s->st, c, d_lines, n_lines, (const unsigned long long*)v, (char*)s->d_sam[3]);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev_sam[3], s->st));
+	HIPCHK(hipMemcpyAsync(out, s->d_sam[3], (size_t)total, hipMemcpyDeviceToHost, s->st));
+	if(line_offs) HIPCHK(hipMemcpyAsync(line_offs, v, n1 * 8, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipStreamSynchronize(s->st));
+	float a = 0, b = 0;
+	if(hipEventElapsedTime(&a, s->ev_sam[0], s->ev_sam[1]) != hipSuccess) a = 0;
+	if(hipEventElapsedTime(&b, s->ev_sam[2], s->ev_sam[3]) != hipSuccess) b = 0;
+	(void)hipGetLastError();
+	s->sam_stats.bytes_uploaded = n_lines * sizeof(h2g_sam_line) + n_aux; s->sam_stats.bytes_written = total; s->sam_stats.kernel_ms = a + b; s->sam_stats.write_kernel_ms = b;
+	return H2G_OK;
+}
+extern "C" h2g_status h2g_sam_text_unpaired(h2g_stream* s, const h2g_sam* S, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
+	return sam_text(s, S, false, lines, n_lines, aux, n_aux, out, cap, used, line_offs);
+}
+extern "C" h2g_status h2g_sam_text_paired(h2g_stream* s, const h2g_sam* S, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
+	return sam_text(s, S, true, lines, n_lines, aux, n_aux, out, cap, used, line_offs);
+}
+extern "C" h2g_status h2g_get_sam_text_stats(h2g_stream* s, h2g_sam_text_stats* out) {
+	if(!s || !out) return H2G_ERR_ARG;
+	*out = s->sam_stats;
 	return H2G_OK;
 }
 

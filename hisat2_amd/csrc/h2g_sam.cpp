@@ -15,6 +15,8 @@
 #include "../../include/h2g_sam.h"
 #include "h2g_host_index.h"
 #include "h2g_splice_db_host.h"
+#include "h2g_sam_line.h"
+#include <atomic>
 
 using namespace h2g;
 
@@ -70,6 +72,9 @@ struct h2g_sam {
 		for(size_t i = 0; i < n; i++) if(v[i].fromfile) site_stats.emplace(std::array<uint32_t, 4>{v[i].tidx, v[i].left, v[i].right, (uint32_t)v[i].dir}, SiteStat{0, 0});
 	}
 	uint64_t first_read_id = 0;                           // Read::rdid of read 0 of the next format call
+	// the device text calls (h2g_sam_text_*) keep tables made from this handle: uid tells handles apart (an address may be used again), opt_gen counts the
+	// changes to what the tables hold (reference names, RG:Z: text, --rna-strandness)
+	uint64_t uid = 0, opt_gen = 0;
 };
 
 namespace {
@@ -138,6 +143,15 @@ struct Summ {         // AlnSetSumm (aligner_result.cpp:1167-1260)
 	int64_t orefid = -1, orefoff = -1;
 };
 struct Rd { const char* name; uint32_t namelen; const uint8_t* codes; uint32_t len; const char* qual; };
+// Where append_mate's lines go: text (the format calls), or one descriptor per line and the byte pool (h2g_sam_plan_*_compact: `plan`).  In plan mode `o` is only the
+// scratch a WHOLE_LINE is written to before it moves to the pool.
+struct Sink {
+	std::string o;
+	bool plan = false;
+	std::vector<h2g_sam_line> lines; std::string aux;
+	const uint8_t* recbase[2] = {nullptr, nullptr};     // the compact bytes of mate 1 / mate 2: a record's offset is its address less this
+	uint32_t read = 0;                                  // the read / pair being formatted
+};
 
 void put(std::string& o, int64_t v) {     // itoa10
 	char b[24];
@@ -404,21 +418,8 @@ void add_splice_sites(const h2g_alnres& r, uint32_t rdlen, uint64_t rdid, std::v
 }
 
 // AlnSinkSam::appendMate aln_sink.h:3024-3260 + printAlignedOptFlags / printEmptyOptFlags sam.h:525-1100
-void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, const h2g_alnres* rs, const h2g_alnres* rso,
-                 const Summ& summ, const Flags& fl, uint64_t nh)
-{
-	if(rs == nullptr && S.no_unal) return;                 // aln_sink.h:3040
-	static thread_local Stacked st;                       // scratch reused across lines (no per-line allocations)
-	static thread_local std::string seq, qual;
-	seq_ascii(rd, rs == nullptr || FW(*rs), seq, qual);
-	// an alignment whose edits are all mismatches (nearly every line) needs no stacked form: its CIGAR is one M run between the soft
-	// clips and its MD:Z follows from the mismatch positions; what buildCigar / buildMdz would make of the stacked strings is written directly
-	bool simple = rs != nullptr;
-	if(rs) for(uint32_t i = 0; i < rs->nedits; i++) if(ED(*rs)[i].type != EDIT_MM) { simple = false; break; }
-	if(rs && !simple) stack_alignment(*rs, seq, st);
-	if(rs && S.collect_novel && tl_novel) add_splice_sites(*rs, rd.len, tl_rdid, *tl_novel);
-	put_read_name(o, rd, fl.partOfPair());
-	o.push_back('\t');
+// FLAG of a line (aln_sink.h:3060-3100)
+int sam_flag(const Flags& fl, const h2g_alnres* rs, const h2g_alnres* rso) {
 	int f = 0;
 	if(fl.partOfPair()) {
 		f |= 1;
@@ -430,6 +431,100 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	if(!fl.primary) f |= 0x100;
 	if(rs && !FW(*rs)) f |= 0x10;
 	if(!rs) f |= 4;
+	return f;
+}
+// the value of Zs:Z (sam.h:985-1030): the known variants the alignment goes through, positions relative to the previous one; empty = no tag
+void zs_value(const h2g_sam& S, const h2g_alnres& r, uint32_t rdlen, std::string& o) {
+	const size_t nalts = S.alts.size();
+	static thread_local std::vector<Ed> ed;
+	ed.resize(r.nedits);
+	for(uint32_t i = 0; i < r.nedits; i++) { ed[i].pos = ED(r)[i].pos; ed[i].type = ED(r)[i].type; ed[i].snp = ED(r)[i].type == EDIT_SPL ? 0xffffffffu : ED(r)[i].snp /* a splice edit keeps its probscore there */; ed[i].chr = ed[i].qchr = 0; }
+	const uint32_t len_trimmed = rdlen - r.trim5 - r.trim3;
+	if(!FW(r)) invert(ed, len_trimmed);
+	bool snp_first = true;
+	uint32_t prev = 0xffffffffu;
+	for(size_t i = 0; i < ed.size(); i++) {
+		if(ed[i].snp >= nalts) continue;
+		const uint32_t si = ed[i].snp;
+		const HostAlt& snp = S.alts[si];
+		if(si == prev) continue;
+		if(!snp_first) o += ",";
+		uint64_t pos = ed[i].pos;
+		size_t j = i;
+		while(j > 0) {
+			if(ed[j - 1].snp < nalts) {
+				const HostAlt& s2 = S.alts[ed[j - 1].snp];
+				if(s2.type == ALT_SGL) pos -= (ed[j - 1].pos + 1);
+				else if(s2.type == ALT_DEL) pos -= ed[j - 1].pos;
+				else if(s2.type == ALT_INS) pos -= (ed[j - 1].pos + snp.len);
+				break;
+			}
+			j--;
+		}
+		put(o, (int64_t)pos);
+		o += snp.type == ALT_SGL ? "|S|" : snp.type == ALT_DEL ? "|D|" : "|I|";
+		o += S.altnames[si];
+		snp_first = false;
+		prev = si;
+	}
+}
+
+// AlnSinkSam::appendMate aln_sink.h:3024-3260 + printAlignedOptFlags / printEmptyOptFlags sam.h:525-1100.  What a line says beyond its record (FLAG, MAPQ, TLEN, ZS:i,
+// YT / YF, NH, the CIGAR / MD:Z of a gapped alignment, Zs:Z) is worked out first, once; then the line is written as text, or — a planning sink — handed on as a descriptor
+// for the emitter of h2g_sam_line.h, which writes what the text branch below writes.
+void append_mate(const h2g_sam& S, Sink& k, const Rd& rd, const Rd* rdo, const h2g_alnres* rs, const h2g_alnres* rso,
+                 const Summ& summ, const Flags& fl, uint64_t nh)
+{
+	if(rs == nullptr && S.no_unal) return;                 // aln_sink.h:3040
+	static thread_local Stacked st;                       // scratch reused across lines (no per-line allocations)
+	static thread_local std::string seq, qual, zsz;
+	// an alignment whose edits are all mismatches (nearly every line) needs no stacked form: its CIGAR is one M run between the soft
+	// clips and its MD:Z follows from the mismatch positions; what buildCigar / buildMdz would make of the stacked strings is written directly
+	bool simple = rs != nullptr;
+	if(rs) for(uint32_t i = 0; i < rs->nedits; i++) if(ED(*rs)[i].type != EDIT_MM) { simple = false; break; }
+	// a planned line whose record keeps its edits outside itself travels as text (WHOLE_LINE): the device reads inline edits only
+	const bool whole = k.plan && rs && rs->nedits > H2G_MAX_EDITS;
+	if(!k.plan || whole || (rs && !simple)) seq_ascii(rd, rs == nullptr || FW(*rs), seq, qual);
+	if(rs && !simple) stack_alignment(*rs, seq, st);
+	if(rs && S.collect_novel && tl_novel) add_splice_sites(*rs, rd.len, tl_rdid, *tl_novel);
+	const int f = sam_flag(fl, rs, rso);
+	const bool mate1 = fl.pairing == PAIR_UNPAIRED || fl.readMate1();   // unpaired reads are ALN_RES_TYPE_UNPAIRED_MATE1 (aln_sink.h:2368)
+	const int mapq = rs ? mapq_v2(S, summ, mate1, rd.len, rdo ? rdo->len : 0) : 0;
+	// ISIZE: setMateParams computes it when the opposite mate is known and on the same reference (or concordant)
+	const bool has_tlen = rs && rso && summ.paired && (rs->tidx == rso->tidx || fl.concordant());
+	const int64_t tlen = has_tlen ? fragment_length(*rs, *rso, fl.readMate1(), fl.concordant() && S.tlen_adjust ? &S : nullptr, tl_rdid) : 0;
+	const bool star_seq = (!fl.primary && S.omit_sec_seq) || rd.len == 0;   // aln_sink.h:3190, :3206; a read without bases: '*' too (:3194, :3209)
+	const Score& sco = summ.secbest[mate1 ? 0 : 1];                       // summ.secbestMate(rd.mate < 2)
+	const int yt = fl.concordant() ? 1 : fl.discordant() ? 2 : fl.unpairedMate() ? 3 : 0, yf = !fl.lenfilt ? 1 : !fl.nfilt ? 2 : !fl.qcfilt ? 3 : 0;
+	static const char* const YT[4] = {"UU", "CP", "DP", "UP"};
+	static const char* const YF[4] = {"", "\tYF:Z:LN", "\tYF:Z:NS", "\tYF:Z:QC"};
+	zsz.clear();
+	if(rs) zs_value(S, *rs, rd.len, zsz);
+	if(k.plan && !whole) {
+		h2g_sam_line d;
+		memset(&d, 0, sizeof d);
+		d.read = k.read; d.nh = (uint32_t)nh;
+		d.rec_off = rs ? (uint64_t)(reinterpret_cast<const uint8_t*>(rs) - k.recbase[mate1 ? 0 : 1]) : ~0ull;
+		d.orec_off = rso ? (uint64_t)(reinterpret_cast<const uint8_t*>(rso) - k.recbase[mate1 ? 1 : 0]) : ~0ull;
+		d.tlen = tlen; d.zs = rs && sco.valid ? (int32_t)sco.score : 0;
+		d.oref_tidx = (int32_t)summ.orefid; d.oref_toff = summ.orefid != -1 ? (uint32_t)summ.orefoff : 0;
+		d.flag = (uint16_t)f; d.mapq = (uint8_t)mapq; d.mate = mate1 ? 0 : 1; d.yt = (uint8_t)yt; d.yf = (uint8_t)yf;
+		d.aux_off = (uint32_t)k.aux.size();
+		if(rs && !simple) {
+			write_cigar(st, k.aux); d.cigar_len = (uint16_t)(k.aux.size() - d.aux_off);
+			write_mdz(st, k.aux);   d.mdz_len = (uint16_t)(k.aux.size() - d.aux_off - d.cigar_len);
+		}
+		k.aux += zsz;
+		d.aux_len = (uint32_t)(k.aux.size() - d.aux_off);
+		d.bits = (uint16_t)((rs && sco.valid ? H2G_SAM_LINE_HAS_ZS : 0) | (rs && summ.paired && rso ? H2G_SAM_LINE_HAS_YS : 0) | (has_tlen ? H2G_SAM_LINE_HAS_TLEN : 0) |
+		                    (star_seq ? H2G_SAM_LINE_STAR_SEQ : 0) | (fl.partOfPair() ? H2G_SAM_LINE_STRIP_MATE_SUFFIX : 0) | (rs && !simple ? H2G_SAM_LINE_AUX_CIGAR_MDZ : 0) |
+		                    (mate1 ? H2G_SAM_LINE_SENSE_MATE1 : 0));
+		k.lines.push_back(d);
+		return;
+	}
+	std::string& o = k.o;
+	put_read_name(o, rd, fl.partOfPair());
+	o.push_back('\t');
 	put(o, f); o.push_back('\t');
 	if(rs) put_ref_name(o, S.refnames[rs->tidx]);
 	else if(summ.orefid != -1) put_ref_name(o, S.refnames[(size_t)summ.orefid]);
@@ -439,7 +534,7 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	else if(summ.orefid != -1) put(o, summ.orefoff + 1);
 	else o.push_back('0');
 	o.push_back('\t');
-	if(rs) put(o, mapq_v2(S, summ, fl.pairing == PAIR_UNPAIRED || fl.readMate1(), rd.len, rdo ? rdo->len : 0));
+	if(rs) put(o, mapq);
 	else o.push_back('0');
 	o.push_back('\t');
 	if(rs && simple) {
@@ -457,25 +552,20 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	else if(summ.orefid != -1) put(o, summ.orefoff + 1);
 	else o.push_back('0');
 	o.push_back('\t');
-	// ISIZE: setMateParams computes it when the opposite mate is known and on the same reference (or concordant)
-	if(rs && rso && summ.paired && (rs->tidx == rso->tidx || fl.concordant())) put(o, fragment_length(*rs, *rso, fl.readMate1(), fl.concordant() && S.tlen_adjust ? &S : nullptr, tl_rdid));
+	if(has_tlen) put(o, tlen);
 	else o.push_back('0');
 	o.push_back('\t');
-	if((!fl.primary && S.omit_sec_seq) || rd.len == 0) o += "*\t*\t";    // aln_sink.h:3190, :3206; a read without bases: '*' too (:3194, :3209)
+	if(star_seq) o += "*\t*\t";
 	else { o += seq; o.push_back('\t'); o += qual; o.push_back('\t'); }
 	if(!rs) {                                                            // printEmptyOptFlags sam.h:1033-1100
 		o += "YT:Z:";
-		o += fl.concordant() ? "CP" : fl.discordant() ? "DP" : fl.unpairedMate() ? "UP" : "UU";
-		if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS"; else if(!fl.qcfilt) o += "\tYF:Z:QC";
+		o += YT[yt]; o += YF[yf];
 		if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }   // sam.h:1102
 		o.push_back('\n');
 		return;
 	}
 	o += "AS:i:"; put(o, rs->score);
-	{
-		const Score& sco = summ.secbest[(fl.pairing == PAIR_UNPAIRED || fl.readMate1()) ? 0 : 1];      // summ.secbestMate(rd.mate < 2)
-		if(sco.valid) { o += "\tZS:i:"; put(o, sco.score); }
-	}
+	if(sco.valid) { o += "\tZS:i:"; put(o, sco.score); }
 	o += "\tXN:i:0";                                                       // refNs is never set (hi_aligner.h:6170)
 	const size_t nalts = S.alts.size();
 	size_t num_mm = 0, num_go = 0, num_gx = 0, NM = 0;
@@ -511,12 +601,11 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 	} else write_mdz(st, o);
 	if(summ.paired && rso) { o += "\tYS:i:"; put(o, rso->score); }
 	o += "\tYT:Z:";
-	o += fl.concordant() ? "CP" : fl.discordant() ? "DP" : fl.unpairedMate() ? "UP" : "UU";
-	if(!fl.lenfilt) o += "\tYF:Z:LN"; else if(!fl.nfilt) o += "\tYF:Z:NS"; else if(!fl.qcfilt) o += "\tYF:Z:QC";
+	o += YT[yt]; o += YF[yf];
 	if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }       // sam.h:780
 	if(S.rna_strandness != 0) {   // a stranded library: the tag follows from the mate and the strand it aligned to (sam.h:940-966)
 		char strand = '+';
-		const bool m1 = fl.pairing == PAIR_UNPAIRED || fl.readMate1();   // unpaired reads are ALN_RES_TYPE_UNPAIRED_MATE1 (aln_sink.h:2368)
+		const bool m1 = mate1;
 		const int rs_ = S.rna_strandness;
 		if(m1) { if(FW(*rs)) { if(rs_ == 2 || rs_ == 4) strand = '-'; } else if(rs_ == 1 || rs_ == 3) strand = '-'; }
 		else   { if(FW(*rs)) { if(rs_ == 3) strand = '-'; } else if(rs_ == 4) strand = '-'; }
@@ -535,41 +624,18 @@ void append_mate(const h2g_sam& S, std::string& o, const Rd& rd, const Rd* rdo, 
 		if(sense != 1) { o += "\tXS:A:"; o.push_back((sense == 2 || sense == 4) ? '+' : '-'); }
 	}
 	o += "\tNH:i:"; put(o, (int64_t)nh);
-	// Zs:Z (sam.h:985-1030): the known variants the alignment goes through, positions relative to the previous one
-	{
-		static thread_local std::vector<Ed> ed;
-		ed.resize(rs->nedits);
-		for(uint32_t i = 0; i < rs->nedits; i++) { ed[i].pos = ED(*rs)[i].pos; ed[i].type = ED(*rs)[i].type; ed[i].snp = ED(*rs)[i].type == EDIT_SPL ? 0xffffffffu : ED(*rs)[i].snp /* a splice edit keeps its probscore there */; ed[i].chr = ed[i].qchr = 0; }
-		const uint32_t len_trimmed = rd.len - rs->trim5 - rs->trim3;
-		if(!FW(*rs)) invert(ed, len_trimmed);
-		bool snp_first = true;
-		uint32_t prev = 0xffffffffu;
-		for(size_t i = 0; i < ed.size(); i++) {
-			if(ed[i].snp >= nalts) continue;
-			const uint32_t si = ed[i].snp;
-			const HostAlt& snp = S.alts[si];
-			if(si == prev) continue;
-			o += snp_first ? "\tZs:Z:" : ",";
-			uint64_t pos = ed[i].pos;
-			size_t j = i;
-			while(j > 0) {
-				if(ed[j - 1].snp < nalts) {
-					const HostAlt& s2 = S.alts[ed[j - 1].snp];
-					if(s2.type == ALT_SGL) pos -= (ed[j - 1].pos + 1);
-					else if(s2.type == ALT_DEL) pos -= ed[j - 1].pos;
-					else if(s2.type == ALT_INS) pos -= (ed[j - 1].pos + snp.len);
-					break;
-				}
-				j--;
-			}
-			put(o, (int64_t)pos);
-			o += snp.type == ALT_SGL ? "|S|" : snp.type == ALT_DEL ? "|D|" : "|I|";
-			o += S.altnames[si];
-			snp_first = false;
-			prev = si;
-		}
-	}
+	if(!zsz.empty()) { o += "\tZs:Z:"; o += zsz; }
 	o.push_back('\n');
+	if(whole) {      // the line just written moves to the pool
+		h2g_sam_line d;
+		memset(&d, 0, sizeof d);
+		d.read = k.read; d.nh = (uint32_t)nh; d.rec_off = d.orec_off = ~0ull; d.oref_tidx = -1;
+		d.flag = (uint16_t)f; d.mapq = (uint8_t)mapq; d.mate = mate1 ? 0 : 1; d.yt = (uint8_t)yt; d.yf = (uint8_t)yf;
+		d.aux_off = (uint32_t)k.aux.size(); d.aux_len = (uint32_t)o.size();
+		d.bits = H2G_SAM_LINE_WHOLE_LINE;
+		k.aux += o; o.clear();
+		k.lines.push_back(d);
+	}
 }
 
 // selectByScore aln_sink.h:2680-2760 on a list of AlnScore keys; RandomSource random_source.h:33
@@ -657,6 +723,8 @@ extern "C" h2g_status h2g_sam_open(const char* base, h2g_sam** out) {
 	const int rc = load_host_index(base, false, ix, true);       // (light: names, lengths, fragment table, ALTs — no sides / SA sample / reference bases)
 	if(rc != 0) return (h2g_status)rc;
 	h2g_sam* s = new h2g_sam();
+	static std::atomic<uint64_t> next_uid{1};
+	s->uid = next_uid++;
 	s->refnames = ix.names;
 	s->reflens.assign(ix.g.plen.begin(), ix.g.plen.end());
 	s->alts = ix.alts;
@@ -685,25 +753,34 @@ extern "C" size_t h2g_sam_header(const h2g_sam* S, const char* cmdline, char* ou
 
 namespace {
 // formats reads [0, n) with `one(i, text)` on S->threads host threads (contiguous ranges, concatenated in read order)
+// what a planning call hands drive() in place of a text buffer
+struct PlanOut { h2g_sam_line* lines; size_t line_cap; size_t* n_lines; char* aux; size_t aux_cap; size_t* aux_used; uint64_t* line_ends; const uint8_t* recbase[2]; };
 template <class F>
-h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_t* used) {
+h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_t* used, const PlanOut* po = nullptr) {
 	size_t T = S->threads < 1 ? 1 : (size_t)S->threads;
 	if(T > n / 2048 + 1) T = n / 2048 + 1;
 	// per-thread text and counters, each on cache lines of its own: a std::string's size field changes with every append, and two of them (or two threads' counters) in
 	// one line made eight formatter threads as slow as one (measured: 0.176 s for 60 000 pairs on 1 thread, 0.164 s on 8)
-	struct alignas(128) Part { std::string o; char pad[128 - sizeof(std::string) % 128]; };
+	struct alignas(128) Part { Sink k; };
 	struct alignas(128) PMet { Met m; };
 	std::vector<Part> parts_(T);
 	std::vector<PMet> mets_(T);
-	struct PartsView { std::vector<Part>& v; std::string& operator[](size_t t) { return v[t].o; } size_t size() const { return v.size(); } } parts{parts_};
+	struct PartsView { std::vector<Part>& v; std::string& operator[](size_t t) { return v[t].k.o; } size_t size() const { return v.size(); } } parts{parts_};
 	struct MetsView { std::vector<PMet>& v; Met& operator[](size_t t) { return v[t].m; } } mets{mets_};
 	auto work = [&](size_t t) {
 		const size_t b = n * t / T, e = n * (t + 1) / T;
-		std::string& o = parts[t];
-		o.reserve((e - b) * 760);                       // (two lines of a 101 bp pair; longer reads grow it)
+		Sink& o = parts_[t].k;
+		if(po) { o.plan = true; o.recbase[0] = po->recbase[0]; o.recbase[1] = po->recbase[1]; o.lines.reserve((e - b) * 2); }
+		else o.o.reserve((e - b) * 760);                // (two lines of a 101 bp pair; longer reads grow it)
 		tl_novel = &mets[t].novel;
 		tl_long_edits = S->long_edits; tl_long_edits_n = S->n_long_edits;
-		for(size_t i = b; i < e; i++) { tl_rdid = S->read_ids ? S->read_ids[i] : S->first_read_id + i; one(i, o, mets[t]); if(S->record_ends) S->record_ends[i] = o.size(); }
+		for(size_t i = b; i < e; i++) {
+			tl_rdid = S->read_ids ? S->read_ids[i] : S->first_read_id + i;
+			o.read = (uint32_t)i;
+			one(i, o, mets[t]);
+			if(po) { if(po->line_ends) po->line_ends[i] = o.lines.size(); }
+			else if(S->record_ends) S->record_ends[i] = o.o.size();
+		}
 		tl_novel = nullptr; tl_long_edits = nullptr; tl_long_edits_n = 0;
 	};
 	if(T == 1) work(0);
@@ -712,6 +789,22 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 		for(size_t t = 1; t < T; t++) th.emplace_back(work, t);
 		work(0);
 		for(auto& x : th) x.join();
+	}
+	if(po) {      // the descriptors and the pool side by side; a pool offset counts from its thread's part until it is placed
+		size_t nl = 0, na = 0;
+		for(size_t t = 0; t < T; t++) { nl += parts_[t].k.lines.size(); na += parts_[t].k.aux.size(); }
+		*po->n_lines = nl; *po->aux_used = na;
+		if(nl > po->line_cap || na > po->aux_cap || na > 0xffffffffull || (nl && !po->lines) || (na && !po->aux)) return H2G_ERR_ARG;
+		for(size_t t = 0; t < T; t++) { S->count_sites(mets[t].novel); S->met.add(mets[t]); }
+		size_t lb = 0, ab = 0;
+		for(size_t t = 0; t < T; t++) {
+			const Sink& k = parts_[t].k;
+			for(size_t j = 0; j < k.lines.size(); j++) { h2g_sam_line d = k.lines[j]; d.aux_off += (uint32_t)ab; po->lines[lb + j] = d; }
+			if(!k.aux.empty()) memcpy(po->aux + ab, k.aux.data(), k.aux.size());
+			if(po->line_ends && t > 0) for(size_t i = n * t / T; i < n * (t + 1) / T; i++) po->line_ends[i] += lb;
+			lb += k.lines.size(); ab += k.aux.size();
+		}
+		return H2G_OK;
 	}
 	size_t total = 0;
 	for(size_t t = 0; t < T; t++) total += parts[t].size();
@@ -839,6 +932,7 @@ extern "C" size_t h2g_sam_summary(const h2g_sam* S, char* out, size_t cap) {
 // --rg-id <text> (id != NULL) and --rg <text> (field != NULL; "ID:x" sets the id like --rg-id x), hisat2.cpp:1389-1407
 extern "C" void h2g_sam_add_read_group(h2g_sam* S, const char* id, const char* field) {
 	if(!S) return;
+	S->opt_gen++;
 	if(id) { S->rg_id = std::string("\tID:") + id; S->rg_optflag = std::string("RG:Z:") + id; }
 	if(field) {
 		const std::string f = field;
@@ -850,6 +944,7 @@ extern "C" void h2g_sam_add_read_group(h2g_sam* S, const char* id, const char* f
 // splice-site files' names, --novel-splicesite-outfile)
 extern "C" void h2g_sam_set_chrname_mode(h2g_sam* S, int mode) {
 	if(!S) return;
+	S->opt_gen++;
 	for(std::string& n : S->refnames) {
 		if(mode == 1) { if(n.compare(0, 3, "chr") == 0) n = n.substr(3); }
 		else if(mode == 2) { if(n.compare(0, 3, "chr") != 0) n = "chr" + n; }
@@ -902,7 +997,7 @@ extern "C" void h2g_sam_add_splice_sites(h2g_sam* S, const h2g_splice_site* delt
 	h2g::merge_splice_db(S->ssdb, delta, n, (uint32_t)S->refnames.size());
 	S->register_sites(delta, n);
 }
-extern "C" void h2g_sam_set_rna_strandness(h2g_sam* S, int code) { if(S) S->rna_strandness = code; }
+extern "C" void h2g_sam_set_rna_strandness(h2g_sam* S, int code) { if(S) { S->rna_strandness = code; S->opt_gen++; } }
 extern "C" void h2g_sam_set_templatelen_adjustment(h2g_sam* S, int on) { if(S) S->tlen_adjust = on != 0; }
 extern "C" void h2g_sam_collect_novel_sites(h2g_sam* S, int on) { if(S) S->collect_novel = on != 0; }
 extern "C" void h2g_sam_set_first_read_id(h2g_sam* S, uint64_t id) { if(S) S->first_read_id = id; }
@@ -962,11 +1057,11 @@ extern "C" void h2g_sam_set_n_ceil(h2g_sam* S, uint32_t type, double c, double c
 
 static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals,
                                   const char* nb, const uint32_t* noffs, size_t n, const h2g_read_result* res,
-                                  const h2g_alnres* aln, const uint64_t* aln_offs, char* out, size_t cap, size_t* used, const uint8_t* compact = nullptr)
+                                  const h2g_alnres* aln, const uint64_t* aln_offs, char* out, size_t cap, size_t* used, const uint8_t* compact = nullptr, const PlanOut* po = nullptr)
 {
 	if(compact) aln = reinterpret_cast<const h2g_alnres*>(compact);       // (aln_offs are byte offsets then)
 	if(!S || !codes || !offs || !nb || !noffs || !res || !aln || !used) return H2G_ERR_ARG;
-	auto one = [&](size_t i, std::string& o, Met& met) {
+	auto one = [&](size_t i, Sink& o, Met& met) {
 		Rd rd = {nb + noffs[i], noffs[i + 1] - noffs[i], codes + offs[i], offs[i + 1] - offs[i], quals ? quals + offs[i] : nullptr};
 		Flags fl;
 		read_filters(*S, rd, &fl.lenfilt, &fl.nfilt);
@@ -989,7 +1084,7 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 			append_mate(*S, o, rd, nullptr, &R[k], nullptr, summ, fl, nsel);
 		}
 	};
-	return drive(S, n, one, out, cap, used);
+	return drive(S, n, one, out, cap, used, po);
 }
 
 extern "C" h2g_status h2g_sam_format_unpaired(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals,
@@ -1013,11 +1108,11 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
                                 const char* nb1, const uint32_t* noffs1, const uint8_t* codes2, const uint32_t* offs2,
                                 const char* quals2, const char* nb2, const uint32_t* noffs2, size_t n,
                                 const h2g_pair_result* res, const h2g_alnres* aln1, const uint64_t* ao1, const h2g_alnres* aln2, const uint64_t* ao2,
-                                uint32_t khits, char* out, size_t cap, size_t* used, const uint8_t* compact1 = nullptr, const uint8_t* compact2 = nullptr)
+                                uint32_t khits, char* out, size_t cap, size_t* used, const uint8_t* compact1 = nullptr, const uint8_t* compact2 = nullptr, const PlanOut* po = nullptr)
 {
 	if(compact1) { aln1 = reinterpret_cast<const h2g_alnres*>(compact1); aln2 = reinterpret_cast<const h2g_alnres*>(compact2); }   // (ao1 / ao2 are byte offsets then)
 	if(!S || !codes1 || !offs1 || !nb1 || !noffs1 || !codes2 || !offs2 || !nb2 || !noffs2 || !res || !aln1 || !aln2 || !used) return H2G_ERR_ARG;
-	auto one = [&](size_t i, std::string& o, Met& met) {
+	auto one = [&](size_t i, Sink& o, Met& met) {
 		static thread_local std::vector<size_t> sel, sel1, sel2;         // (reused: the formatter allocates nothing per pair)
 		static thread_local std::vector<Score> keys;
 		sel.clear(); sel1.clear(); sel2.clear(); keys.clear();
@@ -1141,7 +1236,7 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 			} else { unal(0, nullptr); unal(1, nullptr); }
 		}
 	};
-	return drive(S, n, one, out, cap, used);
+	return drive(S, n, one, out, cap, used, po);
 }
 
 extern "C" h2g_status h2g_sam_format_paired_compact(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1,
@@ -1182,4 +1277,77 @@ extern "C" h2g_status h2g_sam_format_paired_dense(const h2g_sam* S, const uint8_
 	if(!aln_offs1 || !aln_offs2 || !S || !aln1 || !aln2) return H2G_ERR_ARG;
 	if(!long_records_ok(S, aln1, aln_offs1[n]) || !long_records_ok(S, aln2, aln_offs2[n])) return H2G_ERR_ARG;   // a long record without its area (h2g_sam_set_long_edits)
 	return format_paired(S, codes1, offs1, quals1, nb1, noffs1, codes2, offs2, quals2, nb2, noffs2, n, res, aln1, aln_offs1, aln2, aln_offs2, khits, out, cap, used);
+}
+
+// ---- the line plan and its text (include/h2g.h; the emitter: h2g_sam_line.h) -----------------------------------------------------------------
+static_assert(sizeof(h2g_sam_line) == 64 && offsetof(h2g_sam_line, rec_off) == 8 && offsetof(h2g_sam_line, tlen) == 24 && offsetof(h2g_sam_line, zs) == 32 &&
+              offsetof(h2g_sam_line, oref_toff) == 40 && offsetof(h2g_sam_line, flag) == 52 && offsetof(h2g_sam_line, mapq) == 58 && offsetof(h2g_sam_line, bits) == 62, "h2g_sam_line layout (api.py mirrors it)");
+extern "C" h2g_status h2g_sam_plan_unpaired_compact(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals, const char* nb, const uint32_t* noffs, size_t n,
+                                                    const h2g_read_result* res, const uint8_t* rec, const uint64_t* boffs, h2g_sam_line* lines, size_t line_cap, size_t* n_lines,
+                                                    char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends)
+{
+	if(!boffs || !S || !rec || !res || !n_lines || !aux_used) return H2G_ERR_ARG;
+	if(!compact_ok(S, rec, boffs, n, [&](size_t i) { return (size_t)res[i].nselect; })) return H2G_ERR_ARG;
+	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends, {rec, nullptr}};
+	size_t used = 0;
+	return format_unpaired(S, codes, offs, quals, nb, noffs, n, res, nullptr, boffs, nullptr, 0, &used, rec, &po);
+}
+extern "C" h2g_status h2g_sam_plan_paired_compact(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* nb1, const uint32_t* noffs1,
+                                                  const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* nb2, const uint32_t* noffs2, size_t n,
+                                                  const h2g_pair_result* res, const uint8_t* rec1, const uint64_t* boffs1, const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                                  h2g_sam_line* lines, size_t line_cap, size_t* n_lines, char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends)
+{
+	if(!boffs1 || !boffs2 || !S || !rec1 || !rec2 || !res || !n_lines || !aux_used) return H2G_ERR_ARG;
+	if(!compact_ok(S, rec1, boffs1, n, [](size_t) { return (size_t)0; }, true) || !compact_ok(S, rec2, boffs2, n, [](size_t) { return (size_t)0; })) return H2G_ERR_ARG;
+	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends, {rec1, rec2}};
+	size_t used = 0;
+	return format_paired(S, codes1, offs1, quals1, nb1, noffs1, codes2, offs2, quals2, nb2, noffs2, n, res, nullptr, boffs1, nullptr, boffs2, khits, nullptr, 0, &used, rec1, rec2, &po);
+}
+
+namespace h2g_line {
+void sam_tables_key(const h2g_sam* S, uint64_t* uid, uint64_t* gen) { *uid = S->uid; *gen = S->opt_gen; }
+void sam_tables(const h2g_sam* S, Tables& t) {
+	t.uid = S->uid; t.gen = S->opt_gen;
+	t.refnames.clear(); t.refname_offs.assign(1, 0);
+	for(const std::string& nm : S->refnames) { ::put_ref_name(t.refnames, nm); t.refname_offs.push_back((uint32_t)t.refnames.size()); }
+	t.rg = S->rg_optflag; t.rna_strandness = S->rna_strandness; t.nalts = (uint32_t)S->alts.size();
+}
+const char* plan_check(const h2g_sam_line* lines, size_t n_lines, size_t n_reads, bool paired, uint64_t nrec1, uint64_t nrec2, size_t n_aux, uint32_t nrefs) {
+	const uint64_t nrec[2] = {nrec1, nrec2};
+	for(size_t j = 0; j < n_lines; j++) {
+		const h2g_sam_line& L = lines[j];
+		if(L.read >= n_reads) return "a line names a read beyond the fetch";
+		if(L.mate > (paired ? 1u : 0u)) return "a line names a mate the run does not have";
+		if((uint64_t)L.aux_off + L.aux_len > n_aux) return "a line's pool range ends beyond the pool";
+		if(L.bits & H2G_SAM_LINE_WHOLE_LINE) continue;
+		if((uint32_t)L.cigar_len + L.mdz_len > L.aux_len) return "a line's CIGAR and MD:Z are longer than its pool range";
+		if(L.rec_off != ~0ull && ((L.rec_off & 7u) || L.rec_off > nrec[L.mate] || nrec[L.mate] - L.rec_off < 40)) return "a line's record offset is misaligned or outside the mate's bytes";
+		if(L.orec_off != ~0ull && (!paired || (L.orec_off & 7u) || L.orec_off > nrec[L.mate ^ 1u] || nrec[L.mate ^ 1u] - L.orec_off < 40)) return "a line's opposite record offset is misaligned or outside the other mate's bytes";
+		if(L.oref_tidx < -1 || (L.oref_tidx >= 0 && (uint32_t)L.oref_tidx >= nrefs)) return "a line names a reference the index does not have";
+	}
+	return nullptr;
+}
+}  // namespace h2g_line
+
+extern "C" h2g_status h2g_sam_text_from_plan_host(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* nb1, const uint32_t* noffs1,
+                                                  const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* nb2, const uint32_t* noffs2, size_t n,
+                                                  const uint8_t* rec1, size_t n_rec1, const uint8_t* rec2, size_t n_rec2, const h2g_sam_line* lines, size_t n_lines,
+                                                  const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs)
+{
+	if(!S || !codes1 || !offs1 || !nb1 || !noffs1 || !used || (n_lines && !lines) || (n_aux && !aux) || (n_rec1 && !rec1) || (n_rec2 && !rec2)) return H2G_ERR_ARG;
+	const bool paired = codes2 != nullptr;
+	if(paired && (!offs2 || !nb2 || !noffs2)) return H2G_ERR_ARG;
+	h2g_line::Tables t;
+	h2g_line::sam_tables(S, t);
+	h2g_line::Ctx c = {{nb1, nb2}, {noffs1, noffs2}, {codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {rec1, rec2}, {n_rec1, paired ? n_rec2 : 0}, aux, n_aux,
+	                   t.refnames.data(), t.refname_offs.data(), (uint32_t)S->refnames.size(), t.rg.data(), (uint32_t)t.rg.size(), t.rna_strandness, t.nalts, 0, paired ? 1u : 0u};
+	if(h2g_line::plan_check(lines, n_lines, n, paired, c.nrec[0], c.nrec[1], n_aux, c.nrefs)) return H2G_ERR_ARG;
+	for(size_t j = 0; j < n_lines; j++) if(!h2g_line::line_records_ok(c, lines[j])) return H2G_ERR_ARG;
+	std::vector<uint64_t> at(n_lines + 1, 0);
+	for(size_t j = 0; j < n_lines; j++) { h2g_line::CountSink k; h2g_line::emit_line(c, lines[j], k); at[j + 1] = at[j] + k.n; }
+	*used = at[n_lines];
+	if(at[n_lines] > cap || (at[n_lines] && !out)) return H2G_ERR_ARG;
+	for(size_t j = 0; j < n_lines; j++) { h2g_line::PtrSink k = {out + at[j]}; h2g_line::emit_line(c, lines[j], k); }
+	if(line_offs) memcpy(line_offs, at.data(), (n_lines + 1) * 8);
+	return H2G_OK;
 }

@@ -541,6 +541,62 @@ H2G_EXPORT void       h2g_host_free(void*);
  * the large workspace, which the flagged reads of the default units are re-run by); beyond that a read keeps overflow bit 1. */
 H2G_EXPORT h2g_status h2g_align_fetch_long_edits(h2g_stream*, h2g_edit* out, size_t cap, size_t* n);
 
+/* ---- SAM text written on the device from a host-made line plan (opt-in) -------------------------------------------------
+ * The format calls of include/h2g_sam.h decide what to print (pairing, selection, MAPQ, TLEN, filters) and write the bytes.  Here the two halves are
+ * separate calls: h2g_sam_plan_*_compact runs the same decisions over the same arguments and returns one 64-byte descriptor per line instead of text;
+ * h2g_sam_text_* turns descriptors into text on the device, from the reads, qualities and names of the selected resident batch and the compact
+ * records still lying in the stream's buffers after the fetch.  (These stand here because tests/test_abi.py pins the declaration list of h2g_sam.h.)
+ * A descriptor carries what the line takes from the decisions; POS, strand, AS:i, YS:i, RNEXT / PNEXT, trims and edits are read from the records.
+ * A line whose record has mismatch edits only, and an unaligned line, needs nothing else: CIGAR and MD:Z follow from trims and mismatch positions.  The CIGAR
+ * and the MD:Z value of a line with gaps or introns are written by the host (one copy of the left-alignment) into the `aux` byte pool, and so is a Zs:Z
+ * value (it needs the ALT names).  WHOLE_LINE: the pool holds the complete line; only for records beyond H2G_MAX_EDITS, whose edits are not inline. */
+enum { H2G_SAM_LINE_HAS_ZS = 1, H2G_SAM_LINE_HAS_YS = 2, H2G_SAM_LINE_HAS_TLEN = 4, H2G_SAM_LINE_STAR_SEQ = 8 /* --omit-sec-seq secondary or empty read */,
+       H2G_SAM_LINE_STRIP_MATE_SUFFIX = 16 /* part of a pair: a trailing /1 /2 /3 of the name goes */, H2G_SAM_LINE_AUX_CIGAR_MDZ = 32, H2G_SAM_LINE_WHOLE_LINE = 64,
+       H2G_SAM_LINE_SENSE_MATE1 = 128 /* XS:A of a stranded library reads the line as mate 1 */ };
+typedef struct {
+	uint32_t read, nh;             /* read / pair of the call (relative to `first` of the fetch for the text calls); NH:i */
+	uint64_t rec_off, orec_off;    /* byte offset of this line's record in its mate's compact bytes / of the opposite mate's record in the other mate's bytes;
+	                                * ~0 = none (unaligned line / no opposite) */
+	int64_t  tlen;
+	int32_t  zs, oref_tidx;        /* ZS:i value; reference of the aligned mate for an unaligned line, -1 = none */
+	uint32_t oref_toff, aux_off, aux_len;
+	uint16_t flag, cigar_len, mdz_len;   /* SAM FLAG; aux holds CIGAR, MD:Z value, then the Zs:Z value (aux_len - cigar_len - mdz_len bytes), back to back */
+	uint8_t  mapq, mate, yt, yf;         /* mate: 0 = the reads of h2g_set_reads, 1 = of h2g_set_mates; yt: 0 UU 1 CP 2 DP 3 UP; yf: 0 none 1 LN 2 NS 3 QC */
+	uint16_t bits;                       /* H2G_SAM_LINE_* */
+} h2g_sam_line;
+/* The planner (host only).  Arguments as h2g_sam_format_{unpaired,paired}_compact up to `khits`; side effects on the handle exactly those of the format call
+ * (summary counters, collected novel sites; first_read_id / read ids / filters / long edits honoured), so a caller can swap one for the other.  lines[0 .. *n_lines)
+ * in output order, aux[0 .. *aux_used); line_ends ([n] or NULL): lines emitted up to and including read / pair i (--no-unal lines are not planned).  A capacity that is
+ * too small: H2G_ERR_ARG with *n_lines / *aux_used = what is needed, and nothing counted into the handle. */
+H2G_EXPORT h2g_status h2g_sam_plan_unpaired_compact(const struct h2g_sam*, const uint8_t* codes, const uint32_t* offs, const char* quals, const char* name_bytes,
+                                                    const uint32_t* name_offs, size_t n_reads, const h2g_read_result* res, const uint8_t* rec, const uint64_t* boffs,
+                                                    h2g_sam_line* lines, size_t line_cap, size_t* n_lines, char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends);
+H2G_EXPORT h2g_status h2g_sam_plan_paired_compact(const struct h2g_sam*, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* name_bytes1,
+                                                  const uint32_t* name_offs1, const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* name_bytes2,
+                                                  const uint32_t* name_offs2, size_t n_reads, const h2g_pair_result* res, const uint8_t* rec1, const uint64_t* boffs1,
+                                                  const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                                  h2g_sam_line* lines, size_t line_cap, size_t* n_lines, char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends);
+/* The text of lines[0 .. n_lines) on the device: from the selected resident batch (h2g_set_reads / h2g_set_mates / h2g_set_read_names or h2g_set_reads_windows; a batch
+ * without qualities prints 'I') and the compact bytes of this stream's last h2g_align_fetch_compact (unpaired) / h2g_align_pairs_fetch_compact (paired) of (first, n):
+ * lines[].read counts from that `first`.  The stream remembers whether its buffers still hold that fetch: any call since that reuses them (another fetch, a primitive),
+ * selects another batch or sets reads, mates or names makes the text call return H2G_ERR_ARG (h2g_last_error says so) without launching anything.  Every descriptor is
+ * checked before the write kernel runs (H2G_ERR_ARG): read < n, mate against the run kind, offsets 8-aligned and the record with its inline edits inside that mate's
+ * bytes, pool ranges inside n_aux, reference indexes.  out[0 .. *used); cap too small: H2G_ERR_ARG with *used = the bytes needed, nothing written.  line_offs
+ * ([n_lines + 1] or NULL): where each line starts in out, and *used last. */
+H2G_EXPORT h2g_status h2g_sam_text_unpaired(h2g_stream*, const struct h2g_sam*, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux,
+                                            char* out, size_t cap, size_t* used, uint64_t* line_offs);
+H2G_EXPORT h2g_status h2g_sam_text_paired(h2g_stream*, const struct h2g_sam*, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux,
+                                          char* out, size_t cap, size_t* used, uint64_t* line_offs);
+/* The same emitter instantiated on the host (no device needed): host arrays in place of the stream — the read sets as given to the planner (set 2 NULL for an unpaired
+ * plan) and the compact bytes with their byte counts.  Same checks, same results. */
+H2G_EXPORT h2g_status h2g_sam_text_from_plan_host(const struct h2g_sam*, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* name_bytes1,
+                                                  const uint32_t* name_offs1, const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* name_bytes2,
+                                                  const uint32_t* name_offs2, size_t n_reads, const uint8_t* rec1, size_t n_rec1, const uint8_t* rec2, size_t n_rec2,
+                                                  const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs);
+/* HIP-event time of the kernels / bytes written by this stream's last h2g_sam_text_* call (measurement) */
+typedef struct { uint64_t bytes_uploaded, bytes_written; float kernel_ms, write_kernel_ms; /* sizes + scan + write; the write kernel alone */ } h2g_sam_text_stats;
+H2G_EXPORT h2g_status h2g_get_sam_text_stats(h2g_stream*, h2g_sam_text_stats* out);
+
 /* ---- counters (roofline numerators) ------------------------------------------------- */
 typedef struct {
 	uint64_t n_rank, n_side, n_sa_steps, n_ext, n_ref_bytes, n_queries, n_aligned, n_overflow;
