@@ -301,6 +301,14 @@ class SamTextStats(C.Structure):
     _fields_ = [("bytes_uploaded", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float), ("write_kernel_ms", C.c_float)]
 
 
+class SamPlanStats(C.Structure):
+    """h2g_sam_plan_stats: of a stream's last h2g_sam_text_*_planned call"""
+    _fields_ = [("device_planned", C.c_uint64), ("host_planned", C.c_uint64), ("n_lines", C.c_uint64), ("bytes_uploaded", C.c_uint64), ("whole_lines", C.c_uint64), ("plan_kernel_ms", C.c_float), ("host_plan_ms", C.c_float)]
+
+
+# class bytes of the split planner (csrc/h2g_sam_plan.h): 0 = handed on to the host planner
+(SAM_CLS_HOST, SAM_CLS_U_UNAL, SAM_CLS_U_UNIQ, SAM_CLS_P_CONC, SAM_CLS_P_DISC, SAM_CLS_P_NONE, SAM_CLS_P_MATE1, SAM_CLS_P_MATE2, SAM_CLS_P_BOTH) = range(9)
+
 EXPORTS = [
     "h2g_load_opts_init", "h2g_index_load", "h2g_index_get_info", "h2g_index_synth_sides", "h2g_index_free", "h2g_index_set_splice_sites", "h2g_index_add_splice_sites",
     "h2g_last_error", "h2g_stream_create", "h2g_stream_free", "h2g_stream_hip", "h2g_stream_sync", "h2g_stream_select_batch", "h2g_set_reads",
@@ -315,6 +323,7 @@ EXPORTS = [
     "h2g_window_plan_create", "h2g_window_plan_add_file", "h2g_window_plan_get_info", "h2g_window_plan_text", "h2g_window_plan_prefixes", "h2g_window_plan_segments",
     "h2g_window_plan_select", "h2g_window_plan_free", "h2g_set_reads_windows", "h2g_get_windows_stats", "h2g_fetch_reads",
     "h2g_sam_plan_unpaired_compact", "h2g_sam_plan_paired_compact", "h2g_sam_text_unpaired", "h2g_sam_text_paired", "h2g_sam_text_from_plan_host", "h2g_get_sam_text_stats",
+    "h2g_sam_text_unpaired_planned", "h2g_sam_text_paired_planned", "h2g_get_sam_plan_stats", "h2g_sam_plan_split_host",
 ]
 
 
@@ -364,6 +373,18 @@ def sam_plan_paired(sam, codes1, offs1, quals1, name_bytes1, name_offs1, codes2,
     n = len(offs1) - 1
     keep = (codes1, offs1, quals1, name_bytes1, name_offs1, codes2, offs2, quals2, name_bytes2, name_offs2, res, rec1, boffs1, rec2, boffs2)
     return _sam_plan(lib().h2g_sam_plan_paired_compact, n, [sam] + [_ptr(x) for x in keep[:10]], [_ptr(x) for x in keep[10:]] + [khits])
+
+
+def sam_plan_split_host(sam, set1, set2, res, rec1, boffs1, rec2=None, boffs2=None, khits=0):
+    """h2g_sam_plan_split_host: the plain reads planned by the shared planner of csrc/h2g_sam_plan.h, the rest by the host planner, merged in read order (no device).
+    set1 / set2 = (codes, offs, quals, name_bytes, name_offs), set2 None for an unpaired run -> (lines, pool bytes, line_ends [n], class bytes [n])"""
+    n = len(set1[1]) - 1
+    classes = np.zeros(max(n, 1), dtype=np.uint8)
+    head = [sam] + [_ptr(x) for x in set1] + ([_ptr(x) for x in set2] if set2 is not None else [None] * 5)
+    tail = [_ptr(res), _ptr(rec1), _ptr(boffs1), _ptr(rec2), _ptr(boffs2), khits]
+    call = lambda *a: lib().h2g_sam_plan_split_host(*a, classes.ctypes.data)
+    lines, aux, ends = _sam_plan(call, n, head, tail)
+    return lines, aux, ends, classes[:n]
 
 
 def _sam_text(call, n_lines, cap=None):
@@ -484,6 +505,10 @@ def lib():
     L.h2g_sam_text_paired.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, P(sz), vp]
     L.h2g_sam_text_from_plan_host.argtypes = [vp] * 11 + [sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, P(sz), vp]
     L.h2g_get_sam_text_stats.argtypes = [vp, P(SamTextStats)]
+    L.h2g_sam_text_unpaired_planned.argtypes = [vp] * 7 + [sz, vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz), vp]
+    L.h2g_sam_text_paired_planned.argtypes = [vp] * 12 + [sz, vp, vp, vp, vp, vp, u32, vp, sz, P(sz), vp, sz, P(sz), vp]
+    L.h2g_get_sam_plan_stats.argtypes = [vp, P(SamPlanStats), vp, sz]
+    L.h2g_sam_plan_split_host.argtypes = [vp] * 11 + [sz, vp, vp, vp, vp, vp, u32, vp, sz, P(sz), vp, sz, P(sz), vp, vp]
     L.h2g_align_pairs_fetch.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
     L.h2g_align_pairs_fetch_dense.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
@@ -952,6 +977,7 @@ class Stream:
 
     sam_plan_unpaired = staticmethod(sam_plan_unpaired)
     sam_plan_paired = staticmethod(sam_plan_paired)
+    sam_plan_split_host = staticmethod(sam_plan_split_host)
 
     def _sam_text_dev(self, f, sam, lines, aux, cap):
         lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
@@ -966,6 +992,43 @@ class Stream:
     def sam_text_paired(self, sam, lines, aux, cap=None):
         """... after align_pairs_fetch_compact (h2g_sam_text_paired)"""
         return self._sam_text_dev(lib().h2g_sam_text_paired, sam, lines, aux, cap)
+
+    def _sam_text_planned(self, call, n, cap):
+        """-> (text bytes, line_offs [n_lines + 1], line_ends [n]); cap None: sized by a first call that only reports what is needed (and counts nothing)"""
+        used, nl = C.c_size_t(0), C.c_size_t(0)
+        if cap is None:
+            rc = call(None, 0, C.byref(used), None, 0, C.byref(nl), None)
+            if rc not in (0, H2G_ERR_ARG) or (rc == H2G_ERR_ARG and used.value == 0):
+                _chk(rc, "h2g_sam_text_planned")
+            cap = used.value
+        else:
+            nl.value = 8 * n + 64
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(nl.value + 1, dtype=np.uint64)
+        ends = np.zeros(max(n, 1), dtype=np.uint64)
+        _chk(call(out.ctypes.data, cap, C.byref(used), offs.ctypes.data, len(offs) - 1, C.byref(nl), ends.ctypes.data), "h2g_sam_text_planned")
+        return out[:used.value].tobytes(), offs[:nl.value + 1], ends[:n]
+
+    def sam_text_unpaired_planned(self, sam, codes, offs, quals, name_bytes, name_offs, res, rec, boffs, cap=None):
+        """h2g_sam_text_unpaired_planned right after align_fetch_compact: the arguments of sam_plan_unpaired (the host copy of the fetch, for the handed-on reads)"""
+        n = len(offs) - 1
+        keep = (codes, offs, quals, name_bytes, name_offs, res, rec, boffs)
+        a = [_ptr(x) for x in keep]
+        return self._sam_text_planned(lambda *t: lib().h2g_sam_text_unpaired_planned(self.h, sam, *a[:5], n, *a[5:], *t), n, cap)
+
+    def sam_text_paired_planned(self, sam, codes1, offs1, quals1, name_bytes1, name_offs1, codes2, offs2, quals2, name_bytes2, name_offs2, res, rec1, boffs1, rec2, boffs2, khits, cap=None):
+        """... after align_pairs_fetch_compact (h2g_sam_text_paired_planned)"""
+        n = len(offs1) - 1
+        keep = (codes1, offs1, quals1, name_bytes1, name_offs1, codes2, offs2, quals2, name_bytes2, name_offs2, res, rec1, boffs1, rec2, boffs2)
+        a = [_ptr(x) for x in keep]
+        return self._sam_text_planned(lambda *t: lib().h2g_sam_text_paired_planned(self.h, sam, *a[:10], n, *a[10:], khits, *t), n, cap)
+
+    def sam_plan_stats(self, n=0):
+        """of the last *_planned call -> (SamPlanStats, class bytes [n] or None)"""
+        st = SamPlanStats()
+        cls = np.zeros(n, dtype=np.uint8) if n else None
+        _chk(lib().h2g_get_sam_plan_stats(self.h, C.byref(st), _ptr(cls), n), "h2g_get_sam_plan_stats")
+        return st, cls
 
     def sam_text_stats(self):
         st = SamTextStats()

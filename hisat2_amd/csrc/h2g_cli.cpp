@@ -86,6 +86,7 @@ struct PinSet { Pinned res, rec1, rec2, o1, o2; std::vector<h2g_edit> long_edits
 // ---- the command line
 struct Options {
 	std::string base, outfn, stats_fn;
+	bool device_plan = false;                 // --h2g-device-plan (implies --h2g-device-sam): plain reads are planned on the device too, the host plans only the rest
 	bool device_sam = false;                  // --h2g-device-sam: the SAM text is written on the device from a host-made line plan
 	std::vector<std::string> u, m1, m2, m12;
 	ReadFormat tab_fmt = FMT_TAB5;
@@ -203,7 +204,8 @@ Options parse_options(int argc, char** argv) {
 		else if(a == "--version") { printf("hisat2-align-amd (h2g) — output format of HISAT2 2.2.3\n"); exit(0); }
 		else if(a == "--reorder" || a == "-t" || a == "--time" || a == "--mm") {}   // output is always in read order; --mm (index mapping) has nothing to act on here
 		else if(a == "--h2g-device-sam") o.device_sam = true;
-		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on, device_sam_lines, whole_lines} as JSON (tests, bench)
+		else if(a == "--h2g-device-plan") o.device_sam = o.device_plan = true;
+		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on, device_sam_lines, whole_lines, device_planned, host_planned} as JSON (tests, bench)
 		else if(a == "--parse-only") o.parse_only = true;                           // test hook: ingest the reads, print counts + checksums
 		else if(const int arity = h2g_align_option_arity(argv[i]); arity >= 0) { o.opts.push_back(argv[i]); if(arity) o.opts.push_back(need(argv[i])); }   // every option that ends in a field of h2g_align_params
 		else { fprintf(stderr, "hisat2-align-amd: option %s is not built (see DESIGN.md, scope)\n", a.c_str()); exit(1); }
@@ -708,6 +710,7 @@ private:
 // what the stage has counted: written only by the stage (the thread that formats), read after finish()
 struct Totals {
 	uint64_t nreads = 0, naligned = 0, novf = 0;
+	uint64_t device_planned = 0, host_planned = 0;    // --h2g-device-plan: reads / pairs whose lines the device planned; those handed on to the host planner
 	uint64_t device_sam_lines = 0, whole_lines = 0;   // --h2g-device-sam: lines written on the device; of them, those that travelled as text (records beyond H2G_MAX_EDITS)
 	std::string ovf_names;                    // the first of the reads / pairs whose lists overflowed, with the bits
 	double t_fmt = 0;
@@ -725,7 +728,7 @@ struct FmtJob { long batch; size_t n; uint64_t first_id; int set; bool paired; i
 // before the next wave starts, and submit() formats on the caller's thread.  Either way one thread formats: everything below the queue is that thread's.
 class FormatStage {
 public:
-	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites, warn_short; uint32_t khits; bool device_sam; };
+	struct Config { bool async, qc_filter, drop_unal, temp_ss, merge_sites, warn_short; uint32_t khits; bool device_sam, device_plan; };
 	FormatStage(const Config& c, h2g_sam* sam, ParseStage& parse, TextWriter& writer, ReadSorter& sorter, SpliceSites& sites, const Replicas& ix)
 		: c_(c), sam_(sam), parse_(parse), writer_(writer), sorter_(sorter), sites_(sites), ix_(ix) { if(c_.async) thread_ = std::thread(&FormatStage::run, this); }
 	~FormatStage() { finish(); }
@@ -802,6 +805,36 @@ private:
 		const size_t n = job.n;
 		size_t nl = 0, na = 0;
 		if(n == 0) { used = 0; return; }
+		if(c_.device_plan) {   // --h2g-device-plan: classification, the plain reads' plan and the merge on the device; the host planner sees the handed-on reads only
+			ps.loffs.need((2 * n + 17) * 8);
+			ps.text.need(n * 1400 + 4096);
+			plan_ends_.resize(n + 1);
+			auto text = [&] {
+				uint64_t* lo = (uint64_t*)ps.loffs.p;
+				const size_t lcap = ps.loffs.cap / 8 - 1;
+				return job.paired ? h2g_sam_text_paired_planned(job.st, sam_, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, a.names.data(), a.noffs.data(),
+				                                                b.codes.data(), b.offs.data(), b.have_quals ? b.quals.data() : nullptr, b.names.data(), b.noffs.data(), n,
+				                                                (const h2g_pair_result*)ps.res.p, ps.rec1.p, (const uint64_t*)ps.o1.p, ps.rec2.p, (const uint64_t*)ps.o2.p, c_.khits,
+				                                                (char*)ps.text.p, ps.text.cap, &used, lo, lcap, &nl, plan_ends_.data())
+				                  : h2g_sam_text_unpaired_planned(job.st, sam_, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, a.names.data(), a.noffs.data(), n,
+				                                                  (const h2g_read_result*)ps.res.p, ps.rec1.p, (const uint64_t*)ps.o1.p,
+				                                                  (char*)ps.text.p, ps.text.cap, &used, lo, lcap, &nl, plan_ends_.data());
+			};
+			retry_on_small_buffer("h2g_sam_text_planned", text, [&] {
+				const bool small_text = used > ps.text.cap, small_lines = (nl + 1) * 8 > ps.loffs.cap;
+				if(small_text) ps.text.need(used + 16);
+				if(small_lines) ps.loffs.need((nl + 17) * 8);
+				return small_text || small_lines; });
+			const uint64_t* loffs = (const uint64_t*)ps.loffs.p;
+			buf.resize(used + 16);
+			memcpy(buf.data(), ps.text.p, used);
+			if(ends) for(size_t i = 0; i < n; i++) (*ends)[i] = nl ? loffs[plan_ends_[i]] : 0;
+			h2g_sam_plan_stats pst;
+			if(h2g_get_sam_plan_stats(job.st, &pst, nullptr, 0) == H2G_OK) { tot_.device_planned += pst.device_planned; tot_.host_planned += pst.host_planned; tot_.whole_lines += pst.whole_lines; }
+			tot_.device_sam_lines += nl;
+			count_aligned(job, a, ps);
+			return;
+		}
 		if(plan_lines_.size() < 2 * n + 16) plan_lines_.resize(2 * n + 16);
 		if(plan_aux_.size() < 64 * n + 4096) plan_aux_.resize(64 * n + 4096);
 		plan_ends_.resize(n + 1);
@@ -833,6 +866,10 @@ private:
 		if(ends) for(size_t i = 0; i < n; i++) (*ends)[i] = nl ? loffs[plan_ends_[i]] : 0;
 		tot_.device_sam_lines += nl;
 		for(size_t j = 0; j < nl; j++) tot_.whole_lines += (plan_lines_[j].bits & H2G_SAM_LINE_WHOLE_LINE) != 0;
+		count_aligned(job, a, ps);
+	}
+	void count_aligned(const FmtJob& job, Batch& a, PinSet& ps) {
+		const size_t n = job.n;
 		if(job.paired) {
 			const h2g_pair_result* pres = (const h2g_pair_result*)ps.res.p;
 			for(size_t i = 0; i < n; i++) { tot_.naligned += pres[i].npairs > 0; if(pres[i].overflow) tot_.note_overflow(a.names.data() + a.noffs[i], a.noffs[i + 1] - a.noffs[i], pres[i].overflow); }
@@ -1150,7 +1187,7 @@ int main(int argc, char** argv) {
 	// the stages; their destructors join in the reverse order, whatever way out is taken
 	TextWriter writer(out);
 	ParseStage parse(src, H, batch, wv, ix.streams());
-	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits, o.device_sam}, sam, parse, writer, sorter, sites, ix);
+	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits, o.device_sam, o.device_plan}, sam, parse, writer, sorter, sites, ix);
 	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch, wp.plan}, P, wv, ix, parse, fmt);
 	double t_parse = 0;                                   // what the main thread waited for the parser
 	bool short_mates = false;
@@ -1183,8 +1220,9 @@ int main(int argc, char** argv) {
 	        t_parse, parse.busy(), tot.t_fmt, t2 - t0, dev.t_stream, dev.t_up, dev.t_fetch);
 	if(!o.stats_fn.empty()) {
 		FILE* sf = fopen(o.stats_fn.c_str(), "w");
-		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu, \"device_sam_lines\": %llu, \"whole_lines\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
-		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded, (unsigned long long)tot.device_sam_lines, (unsigned long long)tot.whole_lines); fclose(sf); }
+		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu, \"device_sam_lines\": %llu, \"whole_lines\": %llu, \"device_planned\": %llu, \"host_planned\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
+		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded, (unsigned long long)tot.device_sam_lines, (unsigned long long)tot.whole_lines,
+		                 (unsigned long long)tot.device_planned, (unsigned long long)tot.host_planned); fclose(sf); }
 	}
 	// (Measured and not shipped, round 6: ending the process here without the frees below saves this run 0.1 s and costs the NEXT process 1.7 s — the driver reclaims 40 GB of
 	// device memory of a process that did not return it while the next one is already allocating: profiles/r06_zc_ab.log.)

@@ -26,6 +26,8 @@
 #include "h2g_splice_db_host.h"
 #include "h2g_windows.h"   // the -F window expansion's per-read arithmetic
 #include "h2g_sam_line.h"  // the SAM line emitter the text kernels and the host share
+#include "h2g_sam_plan.h"  // the planner of plain SAM lines the kernels and the host share
+#include <chrono>
 #include "h2g_go_args.h"   // GoArgs + the extern "C" face of the go() units (their AlignWS layouts are opaque on this side)
 
 using namespace h2g;
@@ -235,12 +237,20 @@ struct h2g_stream {
 	// SAM text on the device (h2g_sam_text_*): what d_tmp holds is nobody's once another call takes a slot, so every such call (tmp_buf), every batch selection and every call
 	// that sets reads, mates or names counts tmp_gen up; a compact fetch notes the count it ended with, and the text call runs only while the two are equal
 	uint64_t tmp_gen = 0;
-	struct CompactFetch { bool valid = false, paired = false; uint64_t gen = 0; unsigned batch = 0; size_t first = 0, n = 0; const uint8_t* d_rec[2] = {nullptr, nullptr}; uint64_t bytes[2] = {0, 0}; } cfetch;
+	struct CompactFetch { bool valid = false, paired = false; uint64_t gen = 0; unsigned batch = 0; size_t first = 0, n = 0; const uint8_t* d_rec[2] = {nullptr, nullptr}; uint64_t bytes[2] = {0, 0};
+	                      const uint64_t* d_boffs[2] = {nullptr, nullptr}; /* the offset arrays of the fetch (tmp slots 0 / 2), [n + 1] each */ } cfetch;
 	void* d_sam[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // descriptors, pool, line offsets (+ scan tile sums + the check's flag), text, the handle's tables
 	size_t sam_sz[5] = {0, 0, 0, 0, 0};
 	uint64_t samtab_uid = 0, samtab_gen = 0; uint32_t samtab_nrefs = 0, samtab_names = 0, samtab_rg = 0, samtab_nalts = 0; int32_t samtab_strand = 0;   // whose tables d_sam[4] holds
 	hipEvent_t ev_sam[4] = {nullptr, nullptr, nullptr, nullptr};
 	h2g_sam_text_stats sam_stats = {};
+	// h2g_sam_text_*_planned: two descriptor slots per read, class + filter bytes, line counts (+ scan tile sums, per-read source of the handed-on lines, line ends), the
+	// handed-on reads' entries, their descriptors
+	void* d_plan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	size_t plan_sz[5] = {0, 0, 0, 0, 0};
+	hipEvent_t ev_plan[4] = {nullptr, nullptr, nullptr, nullptr};
+	h2g_sam_plan_stats plan_stats = {};
+	std::vector<uint8_t> plan_classes;
 	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows)
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
@@ -934,6 +944,8 @@ extern "C" void h2g_stream_free(h2g_stream* s) {
 	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
 	for(int i = 0; i < 5; i++) (void)hipFree(s->d_sam[i]);
 	for(int i = 0; i < 4; i++) if(s->ev_sam[i]) (void)hipEventDestroy(s->ev_sam[i]);
+	for(int i = 0; i < 5; i++) (void)hipFree(s->d_plan[i]);
+	for(int i = 0; i < 4; i++) if(s->ev_plan[i]) (void)hipEventDestroy(s->ev_plan[i]);
 	for(int i = 0; i < 14; i++) (void)hipEventDestroy(s->ev[i]);
 	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { (void)hipStreamDestroy(s->mst[k]); (void)hipEventDestroy(s->ev_rot[k]); } (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
 	delete s;
@@ -3383,6 +3395,7 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 	// the records stay where they are: h2g_sam_text_paired reads them while nothing else has taken the slots (tmp_gen)
 	s->cfetch.valid = true; s->cfetch.paired = true; s->cfetch.gen = s->tmp_gen; s->cfetch.batch = s->cur_batch; s->cfetch.first = first; s->cfetch.n = n;
 	s->cfetch.d_rec[0] = (const uint8_t*)d_b1; s->cfetch.d_rec[1] = (const uint8_t*)d_b2; s->cfetch.bytes[0] = boffs1[n]; s->cfetch.bytes[1] = boffs2[n];
+	s->cfetch.d_boffs[0] = (const uint64_t*)d_o1; s->cfetch.d_boffs[1] = (const uint64_t*)d_o2;
 	return H2G_OK;
 }
 
@@ -3403,6 +3416,7 @@ extern "C" h2g_status h2g_align_fetch_compact(h2g_stream* s, h2g_read_result* re
 	if((rc = tmp_buf(s, 1, boffs[n] + 8, &d_b))) return (h2g_status)rc;
 	s->cfetch.valid = true; s->cfetch.paired = false; s->cfetch.gen = s->tmp_gen; s->cfetch.batch = s->cur_batch; s->cfetch.first = first; s->cfetch.n = n;
 	s->cfetch.d_rec[0] = (const uint8_t*)d_b; s->cfetch.d_rec[1] = nullptr; s->cfetch.bytes[0] = boffs[n]; s->cfetch.bytes[1] = 0;
+	s->cfetch.d_boffs[0] = (const uint64_t*)d_o; s->cfetch.d_boffs[1] = nullptr;
 	if(boffs[n] == 0) return H2G_OK;
 	hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, s->cur().d_aln + first * s->cur().aln_slots, s->cur().aln_slots, cnt, (uint32_t)(sizeof(ReadOut) / 4),
 	                   (const unsigned long long*)d_o, n, (uint8_t*)d_b, (const PairOut*)nullptr, (const h2g_alnres*)nullptr, 0);
@@ -3444,9 +3458,8 @@ __global__ __launch_bounds__(256) void k_sam_line_write(const h2g_line::Ctx c, c
 	h2g_line::emit_line(c, lines[i], k);
 }
 
-static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
-	if(!s || !S || !used || (n_lines && !lines) || (n_aux && !aux)) return H2G_ERR_ARG;
-	*used = 0;
+// What every text call starts with: the stream must still hold the compact fetch of the right kind; the handle's tables are uploaded when they changed.  Launches nothing.
+static h2g_status sam_text_begin(h2g_stream* s, const h2g_sam* S, bool paired) {
 	const h2g_stream::CompactFetch& cf = s->cfetch;
 	if(!cf.valid || cf.gen != s->tmp_gen || cf.batch != s->cur_batch || cf.paired != paired) {
 		snprintf(g_err, sizeof g_err, "h2g_sam_text_%s: the stream's buffers do not hold a compact %s fetch of the selected batch any more (fetch again, then call this before anything else)", paired ? "paired" : "unpaired", paired ? "paired" : "unpaired");
@@ -3454,7 +3467,6 @@ static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h
 	}
 	const BatchCtx& B = s->cur();
 	if(!B.has_names || (paired && !B.has_mates) || cf.first + cf.n > B.n_reads) { snprintf(g_err, sizeof g_err, "h2g_sam_text: the selected batch has no names / mates"); return H2G_ERR_ARG; }
-	if(n_lines == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
 	HIPCHK(hipSetDevice(s->ix->device));
 	for(int k = 0; k < 4; k++) if(!s->ev_sam[k]) HIPCHK(hipEventCreate(&s->ev_sam[k]));
 	{	// the handle's tables: uploaded once, again when the handle's options changed
@@ -3474,17 +3486,25 @@ static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h
 			s->samtab_nalts = t.nalts; s->samtab_strand = t.rna_strandness;
 		}
 	}
-	if(const char* why = h2g_line::plan_check(lines, n_lines, cf.n, paired, cf.bytes[0], cf.bytes[1], n_aux, s->samtab_nrefs)) { snprintf(g_err, sizeof g_err, "h2g_sam_text: %s", why); return H2G_ERR_ARG; }
+	return H2G_OK;
+}
+// the line offsets (+ scan tile sums + the check's flag) of n_lines lines: d_sam[2]
+static int sam_text_sizes_buf(h2g_stream* s, size_t n_lines, unsigned long long** v, unsigned long long** ts, unsigned int** d_bad) {
+	const size_t n1 = n_lines + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
+	const int rc = grow(&s->d_sam[2], &s->sam_sz[2], (n1 + ntiles + 2) * 8);
+	*v = (unsigned long long*)s->d_sam[2]; *ts = *v + n1; *d_bad = (unsigned int*)(*ts + ntiles + 1);
+	return rc;
+}
+// What every text call ends with: the descriptors lie in d_sam[0] and the pool in d_sam[1] -> sizes, scan, the capacity check, write, copy-back.  flag_is_set: the
+// check's flag was cleared (and maybe raised) by the caller's own kernels
+static h2g_status sam_text_tail(h2g_stream* s, bool paired, size_t n_lines, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs, uint64_t uploaded, bool flag_is_set) {
+	const h2g_stream::CompactFetch& cf = s->cfetch;
+	const BatchCtx& B = s->cur();
 	const size_t n1 = n_lines + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
 	int rc;
-	if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64)) ||
-	   (rc = grow(&s->d_sam[2], &s->sam_sz[2], (n1 + ntiles + 2) * 8))) return (h2g_status)rc;
-	unsigned long long* v = (unsigned long long*)s->d_sam[2];
-	unsigned long long* ts = v + n1;
-	unsigned int* d_bad = (unsigned int*)(ts + ntiles + 1);
-	HIPCHK(hipMemcpyAsync(s->d_sam[0], lines, n_lines * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
-	if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], aux, n_aux, hipMemcpyHostToDevice, s->st));
-	HIPCHK(hipMemsetAsync(d_bad, 0, 8, s->st));
+	unsigned long long *v, *ts; unsigned int* d_bad;
+	if((rc = sam_text_sizes_buf(s, n_lines, &v, &ts, &d_bad))) return (h2g_status)rc;
+	if(!flag_is_set) HIPCHK(hipMemsetAsync(d_bad, 0, 8, s->st));
 	h2g_line::Ctx c;
 	c.names[0] = B.d_names; c.noffs[0] = B.d_name_offs; c.codes[0] = B.d_codes; c.offs[0] = B.d_offs; c.quals[0] = B.has_quals ? B.d_quals : nullptr;
 	c.names[1] = paired ? B.d_names2 : nullptr; c.noffs[1] = paired ? B.d_name_offs2 : nullptr; c.codes[1] = paired ? B.d_codes2 : nullptr; c.offs[1] = paired ? B.d_offs2 : nullptr;
@@ -3521,8 +3541,22 @@ static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h
 	if(hipEventElapsedTime(&a, s->ev_sam[0], s->ev_sam[1]) != hipSuccess) a = 0;
 	if(hipEventElapsedTime(&b, s->ev_sam[2], s->ev_sam[3]) != hipSuccess) b = 0;
 	(void)hipGetLastError();
-	s->sam_stats.bytes_uploaded = n_lines * sizeof(h2g_sam_line) + n_aux; s->sam_stats.bytes_written = total; s->sam_stats.kernel_ms = a + b; s->sam_stats.write_kernel_ms = b;
+	s->sam_stats.bytes_uploaded = uploaded; s->sam_stats.bytes_written = total; s->sam_stats.kernel_ms = a + b; s->sam_stats.write_kernel_ms = b;
 	return H2G_OK;
+}
+static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
+	if(!s || !S || !used || (n_lines && !lines) || (n_aux && !aux)) return H2G_ERR_ARG;
+	*used = 0;
+	h2g_status hr = sam_text_begin(s, S, paired);
+	if(hr != H2G_OK) return hr;
+	if(n_lines == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
+	const h2g_stream::CompactFetch& cf = s->cfetch;
+	if(const char* why = h2g_line::plan_check(lines, n_lines, cf.n, paired, cf.bytes[0], cf.bytes[1], n_aux, s->samtab_nrefs)) { snprintf(g_err, sizeof g_err, "h2g_sam_text: %s", why); return H2G_ERR_ARG; }
+	int rc;
+	if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64))) return (h2g_status)rc;
+	HIPCHK(hipMemcpyAsync(s->d_sam[0], lines, n_lines * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
+	if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], aux, n_aux, hipMemcpyHostToDevice, s->st));
+	return sam_text_tail(s, paired, n_lines, n_aux, out, cap, used, line_offs, n_lines * sizeof(h2g_sam_line) + n_aux, false);
 }
 extern "C" h2g_status h2g_sam_text_unpaired(h2g_stream* s, const h2g_sam* S, const h2g_sam_line* lines, size_t n_lines, const char* aux, size_t n_aux, char* out, size_t cap, size_t* used, uint64_t* line_offs) {
 	return sam_text(s, S, false, lines, n_lines, aux, n_aux, out, cap, used, line_offs);
@@ -3533,6 +3567,201 @@ extern "C" h2g_status h2g_sam_text_paired(h2g_stream* s, const h2g_sam* S, const
 extern "C" h2g_status h2g_get_sam_text_stats(h2g_stream* s, h2g_sam_text_stats* out) {
 	if(!s || !out) return H2G_ERR_ARG;
 	*out = s->sam_stats;
+	return H2G_OK;
+}
+
+// ------------------------------------------------------------------------------------------ plain SAM lines planned on the device (include/h2g.h, csrc/h2g_sam_plan.h)
+// k_sam_plan_*: one lane per read / pair of the compact fetch.  It reads its result header, walks its records inside [boffs[i], boffs[i + 1]) and leaves a class byte (0 =
+// handed on to the host planner), its line count and, for a plain read, its descriptors in two fixed slots.  What does not parse inside its bytes is handed on, never followed.
+struct SamPlanArgs { h2g_plan::Opts O; h2g_plan::In in; size_t n; uint8_t* cls; unsigned long long* v; h2g_sam_line* slots; };
+__device__ __forceinline__ void sam_plan_done(const SamPlanArgs& a, size_t i, uint32_t c, uint32_t made) {
+	const uint32_t want = h2g_plan::lines_of_class(c, a.O.no_unal != 0);      // (what the host derives from the class byte: the two never differ)
+	if(made != want) c = h2g_plan::CLS_HOST;
+	a.cls[i] = (uint8_t)c;
+	a.v[i] = c ? want : 0u;
+}
+__global__ __launch_bounds__(256) void k_sam_plan_unpaired(const SamPlanArgs a, const ReadOut* res) {
+	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if(i > a.n) return;
+	if(i == a.n) { a.v[a.n] = 0; return; }
+	const h2g_plan::UnpHead h = {res[i].nselect, res[i].best, res[i].secbest, res[i].best_h2, res[i].secbest_h2};
+	h2g_plan::Pick pk;
+	const uint32_t c = h2g_plan::classify_unpaired(a.O, a.in, h, (uint32_t)i, &pk);
+	sam_plan_done(a, i, c, c ? h2g_plan::plan_plain_unpaired(a.O, a.in, c, pk, (uint32_t)i, a.slots + 2 * i) : 0u);
+}
+__global__ __launch_bounds__(256) void k_sam_plan_paired(const SamPlanArgs a, const h2g_pair_result* res) {
+	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if(i > a.n) return;
+	if(i == a.n) { a.v[a.n] = 0; return; }
+	h2g_plan::Pick pk;
+	const uint32_t c = h2g_plan::classify_pair(a.O, a.in, res[i], (uint32_t)i, &pk);
+	sam_plan_done(a, i, c, c ? h2g_plan::plan_plain_pair(a.O, a.in, c, pk, (uint32_t)i, a.slots + 2 * i) : 0u);
+}
+// The merge.  A handed-on read's entry: its index, its lines, its pool bytes, where its descriptors start in the upload.  The count array carries lines in its low and pool
+// bytes in its high 32 bits, so one exclusive scan yields every read's first line and the running pool offset its plain lines carry in aux_off.
+struct SamHardEntry { uint32_t idx, cnt, aux, start; };
+__global__ __launch_bounds__(256) void k_sam_plan_scatter(const SamHardEntry* e, size_t nh, size_t n, const uint8_t* cls, unsigned long long* v, uint32_t* hsrc) {
+	const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if(j >= nh) return;
+	const uint32_t i = e[j].idx;
+	if(i >= n || cls[i]) return;
+	v[i] = (unsigned long long)e[j].cnt | ((unsigned long long)e[j].aux << 32);
+	hsrc[i] = e[j].start;
+}
+__global__ __launch_bounds__(256) void k_sam_plan_place(const uint8_t* cls, const unsigned long long* v, const uint32_t* hsrc, const h2g_sam_line* slots, const h2g_sam_line* hard, size_t n_hard,
+                                                        size_t n, size_t n_lines, h2g_sam_line* lines, unsigned long long* ends, unsigned int* bad)
+{
+	const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	if(i == 0 && (uint32_t)v[n] != n_lines) atomicOr(bad, 1u);
+	const uint32_t b = (uint32_t)v[i], e = (uint32_t)v[i + 1], auxat = (uint32_t)(v[i] >> 32);
+	const bool plain = cls[i] != 0;
+	const h2g_sam_line* src = plain ? slots + 2 * i : hard + hsrc[i];
+	for(uint32_t k = 0; b + k < e; k++) {
+		if(b + k >= n_lines || (plain ? k >= 2 : (size_t)hsrc[i] + k >= n_hard)) { atomicOr(bad, 1u); break; }
+		const uint4* sw = reinterpret_cast<const uint4*>(src + k);
+		uint4 w0 = sw[0], w1 = sw[1], w2 = sw[2], w3 = sw[3];
+		if(plain) w2.w = auxat;                                             // aux_off (byte 44): the pool bytes of every read before this one
+		uint4* dw = reinterpret_cast<uint4*>(lines + b + k);
+		dw[0] = w0; dw[1] = w1; dw[2] = w2; dw[3] = w3;
+	}
+	ends[i] = e;
+}
+static_assert(offsetof(h2g_sam_line, aux_off) == 44, "k_sam_plan_place sets aux_off in the third 16-byte word");
+
+static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired, const h2g_plan::HostSets& rd, size_t n, const void* res, const uint8_t* rec1, const uint64_t* boffs1,
+                                   const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits, char* out, size_t cap, size_t* used, uint64_t* line_offs, size_t line_cap, size_t* n_lines_out, uint64_t* line_ends)
+{
+	if(!s || !S || !used || !res || !rec1 || !boffs1 || (paired && (!rec2 || !boffs2)) || (line_offs && !n_lines_out)) return H2G_ERR_ARG;
+	*used = 0;
+	if(n_lines_out) *n_lines_out = 0;
+	h2g_status hr = sam_text_begin(s, S, paired);
+	if(hr != H2G_OK) return hr;
+	const h2g_stream::CompactFetch& cf = s->cfetch;
+	if(n != cf.n || boffs1[n] != cf.bytes[0] || (paired && boffs2[n] != cf.bytes[1])) { snprintf(g_err, sizeof g_err, "h2g_sam_text_planned: the host arrays are not those of the stream's last compact fetch"); return H2G_ERR_ARG; }
+	s->plan_stats = h2g_sam_plan_stats(); s->plan_classes.clear();
+	if(n == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
+	for(int k = 0; k < 4; k++) if(!s->ev_plan[k]) HIPCHK(hipEventCreate(&s->ev_plan[k]));
+	const BatchCtx& B = s->cur();
+	SamPlanArgs a;
+	const uint8_t* qc[2] = {nullptr, nullptr};
+	h2g_plan::sam_plan_opts(S, a.O, &qc[0], &qc[1]);
+	a.O.nrefs = s->samtab_nrefs;
+	const size_t ntiles_r = (n + 1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
+	int rc;
+	// d_plan[2]: counts [n + 1], tile sums [ntiles + 1], line ends [n], sources [n]
+	if((rc = grow(&s->d_plan[0], &s->plan_sz[0], 2 * n * sizeof(h2g_sam_line))) || (rc = grow(&s->d_plan[1], &s->plan_sz[1], 3 * n + 64)) ||
+	   (rc = grow(&s->d_plan[2], &s->plan_sz[2], (n + 1 + ntiles_r + 1 + n) * 8 + n * 4 + 64))) return (h2g_status)rc;
+	uint8_t* d_cls = (uint8_t*)s->d_plan[1];
+	unsigned long long* v = (unsigned long long*)s->d_plan[2];
+	unsigned long long* ts = v + n + 1;
+	unsigned long long* d_ends = ts + ntiles_r + 1;
+	uint32_t* d_hsrc = (uint32_t*)(d_ends + n);
+	uint64_t uploaded = 0;
+	for(int m = 0; m < (paired ? 2 : 1); m++) if(qc[m]) { HIPCHK(hipMemcpyAsync(d_cls + (size_t)(m + 1) * n, qc[m], n, hipMemcpyHostToDevice, s->st)); uploaded += n; }
+	a.in.codes[0] = B.d_codes; a.in.offs[0] = B.d_offs; a.in.codes[1] = paired ? B.d_codes2 : nullptr; a.in.offs[1] = paired ? B.d_offs2 : nullptr;
+	a.in.qc[0] = qc[0] ? d_cls + n : nullptr; a.in.qc[1] = paired && qc[1] ? d_cls + 2 * n : nullptr;
+	a.in.rec[0] = cf.d_rec[0]; a.in.rec[1] = cf.d_rec[1]; a.in.boffs[0] = cf.d_boffs[0]; a.in.boffs[1] = cf.d_boffs[1]; a.in.nrec[0] = cf.bytes[0]; a.in.nrec[1] = cf.bytes[1];
+	a.in.first = (uint32_t)cf.first;
+	a.n = n; a.cls = d_cls; a.v = v; a.slots = (h2g_sam_line*)s->d_plan[0];
+	const unsigned g1 = (unsigned)((n + 1 + 255) / 256);
+	HIPCHK(hipEventRecord(s->ev_plan[0], s->st));
+	if(paired) hipLaunchKernelGGL(k_sam_plan_paired, dim3(g1), dim3(256), 0, s->st, a, reinterpret_cast<const h2g_pair_result*>(B.d_pout + cf.first));
+	else hipLaunchKernelGGL(k_sam_plan_unpaired, dim3(g1), dim3(256), 0, s->st, a, (const ReadOut*)(B.d_rout + cf.first));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev_plan[1], s->st));
+	std::vector<uint8_t> cls(n);
+	HIPCHK(hipMemcpyAsync(cls.data(), d_cls, n, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipStreamSynchronize(s->st));
+	// the host step: the handed-on reads through the host planner, the plain ones counted by class
+	std::vector<uint32_t> hard;
+	size_t n_plain_lines = 0;
+	for(size_t i = 0; i < n; i++) { if(cls[i]) n_plain_lines += h2g_plan::lines_of_class(cls[i], a.O.no_unal != 0); else hard.push_back((uint32_t)i); }
+	std::vector<h2g_sam_line> hl; std::string ha; std::vector<uint64_t> hends;
+	h2g_plan::HostPart* part = nullptr;
+	const auto t0 = std::chrono::steady_clock::now();
+	hr = h2g_plan::plan_subset(S, paired, rd, n, res, rec1, boffs1, rec2, boffs2, khits, hard.data(), hard.size(), hl, ha, hends, &part);
+	const float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if(hr != H2G_OK) { snprintf(g_err, sizeof g_err, "h2g_sam_text_planned: the host planner refused the handed-on reads (malformed records, or a long record without its area)"); return hr; }
+	struct Discard { h2g_plan::HostPart* p; ~Discard() { h2g_plan::plan_discard(p); } } guard{part};      // (until the text is delivered)
+	const size_t n_lines = n_plain_lines + hl.size(), n_aux = ha.size();
+	if(n_lines_out) *n_lines_out = n_lines;
+	if(const char* why = h2g_line::plan_check(hl.data(), hl.size(), cf.n, paired, cf.bytes[0], cf.bytes[1], n_aux, s->samtab_nrefs)) { snprintf(g_err, sizeof g_err, "h2g_sam_text_planned: %s", why); return H2G_ERR_ARG; }
+	if(n_lines >= 0xffffffffull) return H2G_ERR_ARG;
+	const bool short_lines = line_offs && n_lines > line_cap;      // (the bytes needed are still worked out: *used)
+	if(n_lines == 0) { if(line_offs) line_offs[0] = 0; }
+	else {
+		std::vector<SamHardEntry> he(hard.size());
+		for(size_t j = 0, b = 0; j < hard.size(); j++) {
+			uint64_t ab = 0;
+			for(size_t k = b; k < hends[j]; k++) ab += hl[k].aux_len;
+			he[j] = {hard[j], (uint32_t)(hends[j] - b), (uint32_t)ab, (uint32_t)b};
+			b = hends[j];
+		}
+		unsigned long long *lv, *lts; unsigned int* d_bad;
+		if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64)) ||
+		   (rc = grow(&s->d_plan[3], &s->plan_sz[3], he.size() * sizeof(SamHardEntry) + 64)) || (rc = grow(&s->d_plan[4], &s->plan_sz[4], hl.size() * sizeof(h2g_sam_line) + 64)) ||
+		   (rc = sam_text_sizes_buf(s, n_lines, &lv, &lts, &d_bad))) return (h2g_status)rc;
+		if(!he.empty()) HIPCHK(hipMemcpyAsync(s->d_plan[3], he.data(), he.size() * sizeof(SamHardEntry), hipMemcpyHostToDevice, s->st));
+		if(!hl.empty()) HIPCHK(hipMemcpyAsync(s->d_plan[4], hl.data(), hl.size() * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
+		if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], ha.data(), n_aux, hipMemcpyHostToDevice, s->st));
+		uploaded += he.size() * sizeof(SamHardEntry) + hl.size() * sizeof(h2g_sam_line) + n_aux;
+		HIPCHK(hipMemsetAsync(d_bad, 0, 8, s->st));
+		HIPCHK(hipMemsetAsync(s->d_sam[0], 0, n_lines * sizeof(h2g_sam_line), s->st));
+		HIPCHK(hipEventRecord(s->ev_plan[2], s->st));
+		if(!he.empty()) hipLaunchKernelGGL(k_sam_plan_scatter, dim3((unsigned)((he.size() + 255) / 256)), dim3(256), 0, s->st, (const SamHardEntry*)s->d_plan[3], he.size(), n, (const uint8_t*)d_cls, v, d_hsrc);
+		hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles_r), dim3(256), 0, s->st, v, n + 1, ts);
+		hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, s->st, ts, ntiles_r);
+		hipLaunchKernelGGL(k_scan_add, dim3(g1), dim3(256), 0, s->st, v, n + 1, (const unsigned long long*)ts);
+		hipLaunchKernelGGL(k_sam_plan_place, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, (const uint8_t*)d_cls, (const unsigned long long*)v, (const uint32_t*)d_hsrc,
+		                   (const h2g_sam_line*)s->d_plan[0], (const h2g_sam_line*)s->d_plan[4], hl.size(), n, n_lines, (h2g_sam_line*)s->d_sam[0], d_ends, d_bad);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(s->ev_plan[3], s->st));
+		// the shared tail; a line array that is too short: the sizes only (a capacity of 0 writes nothing)
+		hr = sam_text_tail(s, paired, n_lines, n_aux, short_lines ? nullptr : out, short_lines ? 0 : cap, used, short_lines ? nullptr : line_offs, uploaded, true);
+		if(hr != H2G_OK) return hr;
+		if(short_lines) return H2G_ERR_ARG;
+		if(*used && (!out || *used > cap)) return H2G_ERR_ARG;
+	}
+	if(line_ends) {
+		if(n_lines) { HIPCHK(hipMemcpyAsync(line_ends, d_ends, n * 8, hipMemcpyDeviceToHost, s->st)); HIPCHK(hipStreamSynchronize(s->st)); }
+		else memset(line_ends, 0, n * 8);
+	}
+	// delivered: now it counts
+	guard.p = nullptr;
+	h2g_plan::plan_commit(S, part, cls.data(), n);
+	float ka = 0, kb = 0;
+	if(hipEventElapsedTime(&ka, s->ev_plan[0], s->ev_plan[1]) != hipSuccess) ka = 0;
+	if(n_lines == 0 || hipEventElapsedTime(&kb, s->ev_plan[2], s->ev_plan[3]) != hipSuccess) kb = 0;
+	(void)hipGetLastError();
+	s->plan_stats.device_planned = n - hard.size(); s->plan_stats.host_planned = hard.size(); s->plan_stats.n_lines = n_lines; s->plan_stats.bytes_uploaded = uploaded;
+	for(const h2g_sam_line& d : hl) s->plan_stats.whole_lines += (d.bits & H2G_SAM_LINE_WHOLE_LINE) != 0;
+	s->plan_stats.plan_kernel_ms = ka + kb; s->plan_stats.host_plan_ms = host_ms;
+	s->plan_classes.swap(cls);
+	return H2G_OK;
+}
+extern "C" h2g_status h2g_sam_text_unpaired_planned(h2g_stream* s, const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals, const char* nb, const uint32_t* noffs, size_t n,
+                                                    const h2g_read_result* res, const uint8_t* rec, const uint64_t* boffs, char* out, size_t cap, size_t* used, uint64_t* line_offs, size_t line_cap,
+                                                    size_t* n_lines, uint64_t* line_ends)
+{
+	const h2g_plan::HostSets rd = {{codes, nullptr}, {offs, nullptr}, {quals, nullptr}, {nb, nullptr}, {noffs, nullptr}};
+	return sam_text_planned(s, S, false, rd, n, res, rec, boffs, nullptr, nullptr, 0, out, cap, used, line_offs, line_cap, n_lines, line_ends);
+}
+extern "C" h2g_status h2g_sam_text_paired_planned(h2g_stream* s, const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* nb1, const uint32_t* noffs1,
+                                                  const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* nb2, const uint32_t* noffs2, size_t n, const h2g_pair_result* res,
+                                                  const uint8_t* rec1, const uint64_t* boffs1, const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                                  char* out, size_t cap, size_t* used, uint64_t* line_offs, size_t line_cap, size_t* n_lines, uint64_t* line_ends)
+{
+	const h2g_plan::HostSets rd = {{codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {nb1, nb2}, {noffs1, noffs2}};
+	return sam_text_planned(s, S, true, rd, n, res, rec1, boffs1, rec2, boffs2, khits, out, cap, used, line_offs, line_cap, n_lines, line_ends);
+}
+extern "C" h2g_status h2g_get_sam_plan_stats(h2g_stream* s, h2g_sam_plan_stats* out, uint8_t* classes, size_t cap) {
+	if(!s || !out) return H2G_ERR_ARG;
+	*out = s->plan_stats;
+	if(classes) {
+		if(cap < s->plan_classes.size()) return H2G_ERR_ARG;
+		if(!s->plan_classes.empty()) memcpy(classes, s->plan_classes.data(), s->plan_classes.size());
+	}
 	return H2G_OK;
 }
 

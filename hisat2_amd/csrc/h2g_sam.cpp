@@ -16,6 +16,7 @@
 #include "h2g_host_index.h"
 #include "h2g_splice_db_host.h"
 #include "h2g_sam_line.h"
+#include "h2g_sam_plan.h"   // the leaves shared with the device planner, and the plain planner itself
 #include <atomic>
 
 using namespace h2g;
@@ -84,16 +85,10 @@ enum { EDIT_READ_GAP = 1, EDIT_REF_GAP = 2, EDIT_MM = 3, EDIT_SPL = 5 };        
 inline uint32_t spl_len(const h2g_edit& e) { return (uint32_t)e.chr | ((uint32_t)e.qchr << 8) | (((uint32_t)e.pad & 15u) << 16); }
 inline uint32_t spl_dir(const h2g_edit& e) { return ((uint32_t)e.pad >> 4) & 7u; }
 enum { ALT_SGL = 1, ALT_INS = 2, ALT_DEL = 3 };                                 // alt.h:31-39
-enum { PAIR_CONCORD_M1 = 1, PAIR_CONCORD_M2, PAIR_DISCORD_M1, PAIR_DISCORD_M2, PAIR_UNP_M1, PAIR_UNP_M2, PAIR_UNPAIRED };   // aligner_result.h:404-412
+// the pairing codes, AlnScore, AlnFlags, FLAG, hisat2_score and the ends of a fragment: h2g_sam_plan.h (one copy for the host and the device planner)
+using h2g_plan::PAIR_CONCORD_M1; using h2g_plan::PAIR_CONCORD_M2; using h2g_plan::PAIR_DISCORD_M1; using h2g_plan::PAIR_DISCORD_M2; using h2g_plan::PAIR_UNP_M1; using h2g_plan::PAIR_UNP_M2; using h2g_plan::PAIR_UNPAIRED;
+using h2g_plan::Score; using h2g_plan::Flags; using h2g_plan::hisat2_score; using h2g_plan::add; using h2g_plan::sam_flag;
 
-struct Score {        // AlnScore (aligner_result.h:44-330): score, then hisat2_score (fewer trimmed bases wins)
-	bool valid = false;
-	int64_t score = 0, h2 = 0;
-	bool gt(const Score& o) const { if(!o.valid) return valid; if(!valid) return false; return score > o.score || (score == o.score && h2 > o.h2); }
-	bool eq(const Score& o) const { return valid && o.valid && score == o.score && h2 == o.h2; }
-};
-// AlnScore::calculate_hisat2_score aligner_result.h:322-350: score, repeat (never), transcript (1 = spliced: near splice sites,
-// reportHit hi_aligner.h:6100-6143), splice score (mean intron length of the short-anchored splices / 100), trimmed bases
 // A record with more edits than its H2G_MAX_EDITS inline entries (a long deletion: one edit per base, edit.h) keeps them in the long-edit area
 // of its batch (h2g_align_fetch_long_edits -> h2g_sam_set_long_edits): edits[0].pos is their offset there.  Every reader goes through ED().
 thread_local const h2g_edit* tl_long_edits = nullptr;
@@ -106,36 +101,7 @@ inline const h2g_edit* ED(const h2g_alnres& r) {
 }
 // the strand of a record: fw may carry the transcript class above it (H2G_FW_TCLASS, include/h2g.h)
 inline bool FW(const h2g_alnres& r) { return (r.fw & H2G_FW_STRAND) != 0; }
-int64_t hisat2_score(int64_t sc, uint32_t trim, int transcript = 0, uint32_t splicescore = 0) {
-	if(sc > INT32_MAX) sc = INT32_MAX; else if(sc < INT32_MIN) sc = INT32_MIN;
-	const int64_t t = trim > 0xFFFF ? 0 : 0xFFFF - (int64_t)trim;
-	int64_t spl = (int64_t)splicescore / 100;
-	spl = spl > 255 ? 0 : 255 - spl;
-	return (int64_t)(((uint64_t)sc << 32) | ((uint64_t)transcript << 24) | ((uint64_t)spl << 16) | (uint64_t)t);
-}
-Score score_of(const h2g_alnres& r) {
-	Score s; s.valid = true; s.score = r.score;
-	int transcript = 0;                  // 2: every splice is a database site, 1: spliced (GenomeHit::spliced hi_aligner.h:1086)
-	if(r.fw & H2G_FW_TCLASS) transcript = (int)((r.fw >> H2G_FW_TCLASS_SHIFT) & 3u);   // the class reportHit gave it (--avoid-pseudogene / --tmo)
-	else {
-		bool all_known = true;
-		for(uint32_t i = 0; i < r.nedits; i++) if(ED(r)[i].type == EDIT_SPL) { transcript = 1; all_known = all_known && (ED(r)[i].pad >> 7) != 0; }
-		if(transcript && all_known) transcript = 2;
-	}
-	s.h2 = hisat2_score(r.score, r.trim5 + r.trim3, transcript, r.splicescore);
-	return s;
-}
-Score add(const Score& a, const Score& b) { Score s; s.valid = a.valid; s.score = a.score + b.score; s.h2 = a.h2 + b.h2; return s; }
-
-struct Flags {        // AlnFlags (aligner_result.h:414-640); the filters are "passed" bits
-	int  pairing = PAIR_UNPAIRED;
-	bool primary = true, oppAligned = false, oppFw = true, nfilt = true, lenfilt = true, qcfilt = true;
-	bool partOfPair() const { return pairing < PAIR_UNPAIRED; }
-	bool concordant() const { return pairing == PAIR_CONCORD_M1 || pairing == PAIR_CONCORD_M2; }
-	bool discordant() const { return pairing == PAIR_DISCORD_M1 || pairing == PAIR_DISCORD_M2; }
-	bool unpairedMate() const { return pairing == PAIR_UNP_M1 || pairing == PAIR_UNP_M2; }
-	bool readMate1() const { return pairing == PAIR_CONCORD_M1 || pairing == PAIR_DISCORD_M1 || pairing == PAIR_UNP_M1; }
-};
+inline Score score_of(const h2g_alnres& r) { return h2g_plan::score_of(r, ED(r)); }
 struct Summ {         // AlnSetSumm (aligner_result.cpp:1167-1260)
 	bool paired = false;
 	Score best[2], secbest[2], bestPaired, secbestPaired;
@@ -163,12 +129,7 @@ void put(std::string& o, int64_t v) {     // itoa10
 }
 
 // Scoring::nFilter / length filter as the worker applies them (hisat2.cpp:3404-3440): which YF:Z flag an unaligned read gets
-void read_filters(const h2g_sam& S, const Rd& r, bool* lenfilt, bool* nfilt) {
-	*lenfilt = r.len >= 2;                     // rdlens <= multiseedMms(0) || < 2  => filtered
-	uint32_t ns = 0;
-	for(uint32_t i = 0; i < r.len; i++) ns += r.codes[i] > 3;
-	*nfilt = h2g::nceil_pass(S.ncType, S.ncConst, S.ncCoeff, r.len, ns);   // the device's filter (h2g_core.h)
-}
+void read_filters(const h2g_sam& S, const Rd& r, bool* lenfilt, bool* nfilt) { h2g_plan::read_filters(S.ncType, S.ncConst, S.ncCoeff, r.codes, r.len, lenfilt, nfilt); }
 
 // BowtieMapq2::mapq unique.h:187-403 (end-to-end branch; canMax = false, exhausted = false)
 int mapq_v2(const h2g_sam& S, const Summ& s, bool mate1, uint32_t rdlen, uint32_t ordlen) {
@@ -316,36 +277,13 @@ void put_read_name(std::string& o, const Rd& r, bool omitSlashMate) {
 // SamConfig::printRefName: the name up to the first whitespace
 void put_ref_name(std::string& o, const std::string& name) { for(char c : name) { if(isspace((unsigned char)c)) break; o.push_back(c); } }
 
-// AlnRes::setFragmentLength aligner_result.h:1631-1697 with an empty splice-site database; trims extend both ends
-// (getExtendedCoords :1156).  rfextent_ does not count introns (calcRefExtent :1880) while refcoord_right() does (:1256), so
-// each alignment has two (start, end) pairs — (st, en) anchored at its left end, (st2, en2) at its right end — and the
-// upstream mate enters with the right-anchored pair: introns inside the mates do not count towards TLEN.
+// AlnRes::setFragmentLength aligner_result.h:1631-1697: the ends of the fragment (h2g_sam_plan.h: fragment_ends), then the splice-site database
 int64_t fragment_length(const h2g_alnres& me, const h2g_alnres& o, bool meMate1, const h2g_sam* S = nullptr /* concordant pairs: the splice-site database */, uint64_t rdid = 0) {
-	auto coords = [](const h2g_alnres& r, int64_t& st, int64_t& en, int64_t& st2, int64_t& en2) {
-		int64_t ext = r.len, spl = 0;
-		for(uint32_t i = 0; i < r.nedits; i++) {
-			if(ED(r)[i].type == EDIT_REF_GAP) ext--; else if(ED(r)[i].type == EDIT_READ_GAP) ext++;
-			else if(ED(r)[i].type == EDIT_SPL) spl += spl_len(ED(r)[i]);
-		}
-		st = (int64_t)r.toff - r.trim5; en = (int64_t)r.toff + ext - 1 + r.trim3;
-		st2 = st + spl; en2 = en + spl;
-	};
-	int64_t st, en, st2, en2, ost, oen, ost2, oen2;
-	coords(me, st, en, st2, en2);
-	coords(o, ost, oen, ost2, oen2);
-	bool imUpstream;
-	if(st < ost) imUpstream = true;
-	else if(st == ost) {
-		if(FW(me) && FW(o) && meMate1) imUpstream = true;
-		else if(FW(me) && !FW(o)) imUpstream = true;
-		else imUpstream = false;
-	} else imUpstream = false;
-	const int64_t up = imUpstream ? std::min(st2, ost) : std::min(st, ost2);
-	const int64_t dn = imUpstream ? std::max(en2, oen) : std::max(en, oen2);
+	const h2g_plan::FragEnds fe = h2g_plan::fragment_ends(me, ED(me), o, ED(o), meMate1);
+	const int64_t up = fe.up, dn = fe.dn;
 	int64_t intron_len = 0;
 	if(S && !S->ssdb.fw.empty() && me.tidx < S->ssdb.fw_first.size() - 1) {   // :1669-1686: the longest database intron between the mates
-		const int64_t up_right = imUpstream ? std::min(en2, oen) : std::min(en, oen2);
-		const int64_t dn_left = imUpstream ? std::max(st2, ost) : std::max(st, ost2);
+		const int64_t up_right = fe.up_right, dn_left = fe.dn_left;
 		if(up_right + 100 < dn_left) {
 			// getRightSpliceSites(ref, up_right, dn_left - up_right): sites whose left end lies in [up_right, dn_left - 1]
 			const uint32_t lo = S->ssdb.fw_first[me.tidx], hi = S->ssdb.fw_first[me.tidx + 1];
@@ -360,8 +298,7 @@ int64_t fragment_length(const h2g_alnres& me, const h2g_alnres& o, bool meMate1,
 			}
 		}
 	}
-	int64_t fl = 1 + dn - up - intron_len;
-	return imUpstream ? fl : -fl;
+	return h2g_plan::fragment_length_of(fe, intron_len);
 }
 
 thread_local std::vector<h2g_splice_site>* tl_novel = nullptr;     // where this formatter thread collects the sites of its lines
@@ -418,21 +355,6 @@ void add_splice_sites(const h2g_alnres& r, uint32_t rdlen, uint64_t rdid, std::v
 }
 
 // AlnSinkSam::appendMate aln_sink.h:3024-3260 + printAlignedOptFlags / printEmptyOptFlags sam.h:525-1100
-// FLAG of a line (aln_sink.h:3060-3100)
-int sam_flag(const Flags& fl, const h2g_alnres* rs, const h2g_alnres* rso) {
-	int f = 0;
-	if(fl.partOfPair()) {
-		f |= 1;
-		if(fl.concordant()) f |= 2;
-		if(!fl.oppAligned) f |= 8;
-		f |= fl.readMate1() ? 0x40 : 0x80;
-		if(fl.oppAligned && rso != nullptr && !FW(*rso)) f |= 0x20;
-	}
-	if(!fl.primary) f |= 0x100;
-	if(rs && !FW(*rs)) f |= 0x10;
-	if(!rs) f |= 4;
-	return f;
-}
 // the value of Zs:Z (sam.h:985-1030): the known variants the alignment goes through, positions relative to the previous one; empty = no tag
 void zs_value(const h2g_sam& S, const h2g_alnres& r, uint32_t rdlen, std::string& o) {
 	const size_t nalts = S.alts.size();
@@ -708,9 +630,7 @@ inline size_t compact_walk(const uint8_t* p, const uint8_t* end, std::vector<con
 }
 void summ_unpaired(Summ& s, int m, const Recs& lst, size_t n) {   // the rs1u_/rs2u_ loop of AlnSetSumm::init
 	for(size_t i = 0; i < n; i++) {
-		const Score sc = score_of(lst[i]);
-		if(sc.gt(s.best[m])) { s.secbest[m] = s.best[m]; s.best[m] = sc; }
-		else if(sc.gt(s.secbest[m])) s.secbest[m] = sc;
+		h2g_plan::summ_step(s.best[m], s.secbest[m], score_of(lst[i]));
 	}
 	s.numAlns[m] = n;
 }
@@ -754,7 +674,10 @@ extern "C" size_t h2g_sam_header(const h2g_sam* S, const char* cmdline, char* ou
 namespace {
 // formats reads [0, n) with `one(i, text)` on S->threads host threads (contiguous ranges, concatenated in read order)
 // what a planning call hands drive() in place of a text buffer
-struct PlanOut { h2g_sam_line* lines; size_t line_cap; size_t* n_lines; char* aux; size_t aux_cap; size_t* aux_used; uint64_t* line_ends; const uint8_t* recbase[2]; };
+struct PlanOut { h2g_sam_line* lines; size_t line_cap; size_t* n_lines; char* aux; size_t aux_cap; size_t* aux_used; uint64_t* line_ends; const uint8_t* recbase[2];
+	// the split planner (h2g_sam_plan.h plan_subset): item j of the call is read subset[j]; the lines and the pool go to vectors that take any size; what would be counted
+	// into the handle goes to *defer instead
+	const uint32_t* subset = nullptr; std::vector<h2g_sam_line>* vlines = nullptr; std::string* vaux = nullptr; Met* defer = nullptr; };
 template <class F>
 h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_t* used, const PlanOut* po = nullptr) {
 	size_t T = S->threads < 1 ? 1 : (size_t)S->threads;
@@ -774,11 +697,12 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 		else o.o.reserve((e - b) * 760);                // (two lines of a 101 bp pair; longer reads grow it)
 		tl_novel = &mets[t].novel;
 		tl_long_edits = S->long_edits; tl_long_edits_n = S->n_long_edits;
-		for(size_t i = b; i < e; i++) {
+		for(size_t j = b; j < e; j++) {
+			const size_t i = po && po->subset ? po->subset[j] : j;
 			tl_rdid = S->read_ids ? S->read_ids[i] : S->first_read_id + i;
 			o.read = (uint32_t)i;
 			one(i, o, mets[t]);
-			if(po) { if(po->line_ends) po->line_ends[i] = o.lines.size(); }
+			if(po) { if(po->line_ends) po->line_ends[j] = o.lines.size(); }
 			else if(S->record_ends) S->record_ends[i] = o.o.size();
 		}
 		tl_novel = nullptr; tl_long_edits = nullptr; tl_long_edits_n = 0;
@@ -794,13 +718,16 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 		size_t nl = 0, na = 0;
 		for(size_t t = 0; t < T; t++) { nl += parts_[t].k.lines.size(); na += parts_[t].k.aux.size(); }
 		*po->n_lines = nl; *po->aux_used = na;
-		if(nl > po->line_cap || na > po->aux_cap || na > 0xffffffffull || (nl && !po->lines) || (na && !po->aux)) return H2G_ERR_ARG;
-		for(size_t t = 0; t < T; t++) { S->count_sites(mets[t].novel); S->met.add(mets[t]); }
+		if(po->vlines) { po->vlines->resize(nl); po->vaux->resize(na); }
+		h2g_sam_line* const lines = po->vlines ? po->vlines->data() : po->lines;
+		char* const aux = po->vaux ? &(*po->vaux)[0] : po->aux;
+		if(na > 0xffffffffull || (!po->vlines && (nl > po->line_cap || na > po->aux_cap || (nl && !po->lines) || (na && !po->aux)))) return H2G_ERR_ARG;
+		for(size_t t = 0; t < T; t++) { if(po->defer) po->defer->add(mets[t]); else { S->count_sites(mets[t].novel); S->met.add(mets[t]); } }
 		size_t lb = 0, ab = 0;
 		for(size_t t = 0; t < T; t++) {
 			const Sink& k = parts_[t].k;
-			for(size_t j = 0; j < k.lines.size(); j++) { h2g_sam_line d = k.lines[j]; d.aux_off += (uint32_t)ab; po->lines[lb + j] = d; }
-			if(!k.aux.empty()) memcpy(po->aux + ab, k.aux.data(), k.aux.size());
+			for(size_t j = 0; j < k.lines.size(); j++) { h2g_sam_line d = k.lines[j]; d.aux_off += (uint32_t)ab; lines[lb + j] = d; }
+			if(!k.aux.empty()) memcpy(aux + ab, k.aux.data(), k.aux.size());
 			if(po->line_ends && t > 0) for(size_t i = n * t / T; i < n * (t + 1) / T; i++) po->line_ends[i] += lb;
 			lb += k.lines.size(); ab += k.aux.size();
 		}
@@ -844,8 +771,9 @@ inline bool long_record_ok(const h2g_sam* S, const h2g_alnres& r) {
 // the area — checked before a line is written, so that the formatter itself never meets a malformed buffer (ED() handed out a one-entry list, a failed
 // table dropped the read's lines silently)
 template <typename NEED>
-bool compact_ok(const h2g_sam* S, const uint8_t* rec, const uint64_t* boffs, size_t n, NEED&& need, bool trailers = false) {
-	for(size_t i = 0; i < n; i++) {
+bool compact_ok(const h2g_sam* S, const uint8_t* rec, const uint64_t* boffs, size_t n, NEED&& need, bool trailers = false, const uint32_t* subset = nullptr /* only reads subset[0 .. n) */) {
+	for(size_t j = 0; j < n; j++) {
+		const size_t i = subset ? subset[j] : j;
 		if(boffs[i + 1] < boffs[i]) return false;
 		const uint8_t* p = rec + boffs[i]; const uint8_t* const end = rec + boffs[i + 1];
 		size_t k = 0;
@@ -1349,5 +1277,107 @@ extern "C" h2g_status h2g_sam_text_from_plan_host(const h2g_sam* S, const uint8_
 	if(at[n_lines] > cap || (at[n_lines] && !out)) return H2G_ERR_ARG;
 	for(size_t j = 0; j < n_lines; j++) { h2g_line::PtrSink k = {out + at[j]}; h2g_line::emit_line(c, lines[j], k); }
 	if(line_offs) memcpy(line_offs, at.data(), (n_lines + 1) * 8);
+	return H2G_OK;
+}
+
+// ---- the split planner: plain reads by the shared planner of h2g_sam_plan.h, the rest by the planner above --------------------------------
+namespace h2g_plan {
+struct HostPart { Met met; };
+void sam_plan_opts(const h2g_sam* S, Opts& o, const uint8_t** qc1, const uint8_t** qc2) {
+	o.ncConst = S->ncConst; o.ncCoeff = S->ncCoeff; o.ncType = S->ncType; o.nalts = (uint32_t)S->alts.size(); o.nrefs = (uint32_t)S->refnames.size();
+	o.no_unal = S->no_unal; o.report_discordant = S->report_discordant; o.report_mixed = S->report_mixed; o.db_tlen = !S->ssdb.fw.empty() && S->tlen_adjust;
+	*qc1 = S->qc1; *qc2 = S->qc2;
+}
+h2g_status plan_subset(const h2g_sam* S, bool paired, const HostSets& rd, size_t n, const void* res, const uint8_t* rec1, const uint64_t* boffs1, const uint8_t* rec2, const uint64_t* boffs2,
+                       uint32_t khits, const uint32_t* idx, size_t nidx, std::vector<h2g_sam_line>& lines, std::string& aux, std::vector<uint64_t>& ends, HostPart** part)
+{
+	*part = nullptr;
+	lines.clear(); aux.clear(); ends.assign(nidx, 0);
+	if(!S || !res || !rec1 || !boffs1 || (paired && (!rec2 || !boffs2)) || (nidx && !idx)) return H2G_ERR_ARG;
+	for(size_t j = 0; j < nidx; j++) if(idx[j] >= n || (j && idx[j] <= idx[j - 1])) return H2G_ERR_ARG;
+	if(nidx == 0) return H2G_OK;
+	HostPart* hp = new HostPart();
+	size_t nl = 0, na = 0, used = 0;
+	PlanOut po = {nullptr, 0, &nl, nullptr, 0, &na, ends.data(), {rec1, paired ? rec2 : nullptr}};
+	po.subset = idx; po.vlines = &lines; po.vaux = &aux; po.defer = &hp->met;
+	h2g_status rc;
+	if(paired) {
+		if(!compact_ok(S, rec1, boffs1, nidx, [](size_t) { return (size_t)0; }, true, idx) || !compact_ok(S, rec2, boffs2, nidx, [](size_t) { return (size_t)0; }, false, idx)) { delete hp; return H2G_ERR_ARG; }
+		rc = format_paired(S, rd.codes[0], rd.offs[0], rd.quals[0], rd.names[0], rd.noffs[0], rd.codes[1], rd.offs[1], rd.quals[1], rd.names[1], rd.noffs[1], nidx,
+		                   static_cast<const h2g_pair_result*>(res), nullptr, boffs1, nullptr, boffs2, khits, nullptr, 0, &used, rec1, rec2, &po);
+	} else {
+		const h2g_read_result* rr = static_cast<const h2g_read_result*>(res);
+		if(!compact_ok(S, rec1, boffs1, nidx, [&](size_t i) { return (size_t)rr[i].nselect; }, false, idx)) { delete hp; return H2G_ERR_ARG; }
+		rc = format_unpaired(S, rd.codes[0], rd.offs[0], rd.quals[0], rd.names[0], rd.noffs[0], nidx, rr, nullptr, boffs1, nullptr, 0, &used, rec1, &po);
+	}
+	if(rc != H2G_OK) { delete hp; return rc; }
+	*part = hp;
+	return H2G_OK;
+}
+void plan_commit(const h2g_sam* S, HostPart* part, const uint8_t* classes, size_t n) {
+	Met m;
+	for(size_t i = 0; i < n; i++) {
+		switch(classes[i]) {
+			case CLS_U_UNAL:  m.nread++; m.nunpaired++; m.nunp_0++; break;
+			case CLS_U_UNIQ:  m.nread++; m.nunpaired++; m.nunp_uni1++; break;
+			case CLS_P_CONC:  m.nread++; m.npaired++; m.nconcord_uni1++; break;
+			case CLS_P_DISC:  m.nread++; m.npaired++; m.nconcord_0++; m.ndiscord++; break;
+			case CLS_P_NONE:  m.nread++; m.npaired++; m.nconcord_0++; m.nunp_0_0 += 2; break;
+			case CLS_P_MATE1: case CLS_P_MATE2: m.nread++; m.npaired++; m.nconcord_0++; m.nunp_0_0++; m.nunp_0_uni1++; break;
+			case CLS_P_BOTH:  m.nread++; m.npaired++; m.nconcord_0++; m.nunp_0_uni1 += 2; break;
+			default: break;                                   // handed on: counted by the host planner, in *part
+		}
+	}
+	if(part) { S->count_sites(part->met.novel); S->met.add(part->met); delete part; }   // (a plain line crosses no junction: nothing to collect for it)
+	S->met.add(m);
+}
+void plan_discard(HostPart* part) { delete part; }
+}  // namespace h2g_plan
+
+extern "C" h2g_status h2g_sam_plan_split_host(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* nb1, const uint32_t* noffs1,
+                                              const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* nb2, const uint32_t* noffs2, size_t n, const void* res,
+                                              const uint8_t* rec1, const uint64_t* boffs1, const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                              h2g_sam_line* lines, size_t line_cap, size_t* n_lines, char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends, uint8_t* classes)
+{
+	using namespace h2g_plan;
+	const bool paired = codes2 != nullptr;
+	if(!S || !codes1 || !offs1 || !nb1 || !noffs1 || !res || !rec1 || !boffs1 || !n_lines || !aux_used || (paired && (!offs2 || !nb2 || !noffs2 || !rec2 || !boffs2))) return H2G_ERR_ARG;
+	Opts O;
+	In in = {{codes1, codes2}, {offs1, offs2}, {nullptr, nullptr}, {rec1, rec2}, {boffs1, boffs2}, {boffs1[n], paired ? boffs2[n] : 0}, 0};
+	sam_plan_opts(S, O, &in.qc[0], &in.qc[1]);
+	std::vector<uint8_t> cls(n), cnt(n);
+	std::vector<h2g_sam_line> slots(2 * n);
+	std::vector<uint32_t> hard;
+	size_t nplain = 0;
+	for(size_t i = 0; i < n; i++) {
+		Pick pk;
+		if(paired) { cls[i] = (uint8_t)classify_pair(O, in, static_cast<const h2g_pair_result*>(res)[i], (uint32_t)i, &pk); if(cls[i]) cnt[i] = (uint8_t)plan_plain_pair(O, in, cls[i], pk, (uint32_t)i, &slots[2 * i]); }
+		else {
+			const h2g_read_result& r = static_cast<const h2g_read_result*>(res)[i];
+			const UnpHead h = {r.nselect, r.best, r.secbest, r.best_h2, r.secbest_h2};
+			cls[i] = (uint8_t)classify_unpaired(O, in, h, (uint32_t)i, &pk);
+			if(cls[i]) cnt[i] = (uint8_t)plan_plain_unpaired(O, in, cls[i], pk, (uint32_t)i, &slots[2 * i]);
+		}
+		if(cls[i]) nplain += cnt[i]; else hard.push_back((uint32_t)i);
+	}
+	std::vector<h2g_sam_line> hl; std::string ha; std::vector<uint64_t> hends;
+	HostPart* part = nullptr;
+	const HostSets rd = {{codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {nb1, nb2}, {noffs1, noffs2}};
+	const h2g_status rc = plan_subset(S, paired, rd, n, res, rec1, boffs1, rec2, boffs2, khits, hard.data(), hard.size(), hl, ha, hends, &part);
+	if(rc != H2G_OK) return rc;
+	*n_lines = nplain + hl.size(); *aux_used = ha.size();
+	if(*n_lines > line_cap || ha.size() > aux_cap || (*n_lines && !lines) || (ha.size() && !aux)) { plan_discard(part); return H2G_ERR_ARG; }
+	size_t pos = 0, j = 0, hstart = 0; uint32_t auxat = 0;
+	for(size_t i = 0; i < n; i++) {
+		if(cls[i]) for(uint32_t k = 0; k < cnt[i]; k++) { h2g_sam_line d = slots[2 * i + k]; d.aux_off = auxat; lines[pos++] = d; }
+		else {
+			for(; hstart < hends[j]; hstart++) { lines[pos++] = hl[hstart]; auxat = hl[hstart].aux_off + hl[hstart].aux_len; }
+			j++;
+		}
+		if(line_ends) line_ends[i] = pos;
+	}
+	if(!ha.empty()) memcpy(aux, ha.data(), ha.size());
+	if(classes && n) memcpy(classes, cls.data(), n);
+	plan_commit(S, part, cls.data(), n);
 	return H2G_OK;
 }

@@ -597,6 +597,39 @@ H2G_EXPORT h2g_status h2g_sam_text_from_plan_host(const struct h2g_sam*, const u
 typedef struct { uint64_t bytes_uploaded, bytes_written; float kernel_ms, write_kernel_ms; /* sizes + scan + write; the write kernel alone */ } h2g_sam_text_stats;
 H2G_EXPORT h2g_status h2g_get_sam_text_stats(h2g_stream*, h2g_sam_text_stats* out);
 
+/* ---- plain lines planned on the device, the rest by the host planner (opt-in) ---------------------------------------------
+ * Most reads are PLAIN: nothing aligned, or one alignment (one concordant pairing of two) whose edits are mismatches only.  Their descriptors are closed-form functions of
+ * the result header and one or two records, and the device holds all of that after a compact fetch.  These calls classify every read / pair of the fetch on the device
+ * (csrc/h2g_sam_plan.h states the predicate), plan the plain ones there, run the host planner over the HANDED-ON rest only, merge the two in read order on the device and
+ * write the text as h2g_sam_text_* does.  The bytes are those of h2g_sam_format_*_compact; the side effects on the handle too (summary counters, collected novel sites),
+ * counted once the text is delivered.
+ * Arguments: those of h2g_sam_plan_*_compact up to `khits` — the host read sets and the host copy of the fetch, for the handed-on reads — then out / cap / used as the text
+ * calls take them; line_offs ([line_cap + 1] or NULL) and *n_lines (NULL allowed without line_offs): where each line starts; line_ends ([n_reads] or NULL): lines emitted
+ * up to and including read i.  H2G_ERR_ARG without a launch when the stream's buffers do not hold that fetch any more or the fetch is of the other kind; H2G_ERR_ARG with
+ * *used (and *n_lines) = what is needed when cap (line_cap) is too small.  On any refusal nothing is written and nothing is counted into the handle. */
+H2G_EXPORT h2g_status h2g_sam_text_unpaired_planned(h2g_stream*, const struct h2g_sam*, const uint8_t* codes, const uint32_t* offs, const char* quals, const char* name_bytes,
+                                                    const uint32_t* name_offs, size_t n_reads, const h2g_read_result* res, const uint8_t* rec, const uint64_t* boffs,
+                                                    char* out, size_t cap, size_t* used, uint64_t* line_offs, size_t line_cap, size_t* n_lines, uint64_t* line_ends);
+H2G_EXPORT h2g_status h2g_sam_text_paired_planned(h2g_stream*, const struct h2g_sam*, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* name_bytes1,
+                                                  const uint32_t* name_offs1, const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* name_bytes2,
+                                                  const uint32_t* name_offs2, size_t n_reads, const h2g_pair_result* res, const uint8_t* rec1, const uint64_t* boffs1,
+                                                  const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                                  char* out, size_t cap, size_t* used, uint64_t* line_offs, size_t line_cap, size_t* n_lines, uint64_t* line_ends);
+/* Of this stream's last h2g_sam_text_*_planned call: reads / pairs planned on the device and by the host, lines, bytes uploaded for the merge (descriptors, pool, per-read
+ * entries of the handed-on reads), HIP-event time of the planner + merge kernels, wall time of the host planner over its subset.  classes ([cap] or NULL): the class byte
+ * of each read of that call, 0 = handed on (csrc/h2g_sam_plan.h); H2G_ERR_ARG when cap is smaller than the call's reads. */
+typedef struct { uint64_t device_planned, host_planned, n_lines, bytes_uploaded, whole_lines /* lines that travelled as text: records beyond H2G_MAX_EDITS, all handed on */;
+                 float plan_kernel_ms, host_plan_ms; } h2g_sam_plan_stats;
+H2G_EXPORT h2g_status h2g_get_sam_plan_stats(h2g_stream*, h2g_sam_plan_stats* out, uint8_t* classes, size_t cap);
+/* The same split with host arrays only (no device): classification and the plain planner instantiated on the host, the host planner over the handed-on reads, the merge.
+ * Arguments and results as h2g_sam_plan_paired_compact (set 2, rec2 and boffs2 NULL: an unpaired run, res = h2g_read_result[n]; else h2g_pair_result[n]); lines, aux and
+ * line_ends equal that call's byte for byte, and so do the side effects on the handle.  classes ([n_reads] or NULL) as above. */
+H2G_EXPORT h2g_status h2g_sam_plan_split_host(const struct h2g_sam*, const uint8_t* codes1, const uint32_t* offs1, const char* quals1, const char* name_bytes1,
+                                              const uint32_t* name_offs1, const uint8_t* codes2, const uint32_t* offs2, const char* quals2, const char* name_bytes2,
+                                              const uint32_t* name_offs2, size_t n_reads, const void* res, const uint8_t* rec1, const uint64_t* boffs1,
+                                              const uint8_t* rec2, const uint64_t* boffs2, uint32_t khits,
+                                              h2g_sam_line* lines, size_t line_cap, size_t* n_lines, char* aux, size_t aux_cap, size_t* aux_used, uint64_t* line_ends, uint8_t* classes);
+
 /* ---- counters (roofline numerators) ------------------------------------------------- */
 typedef struct {
 	uint64_t n_rank, n_side, n_sa_steps, n_ext, n_ref_bytes, n_queries, n_aligned, n_overflow;

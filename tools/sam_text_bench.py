@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Times the two ways from a finished paired run to its SAM text, in one process, alternating, after a warm-up of both:
+"""Times the three ways from a finished paired run to its SAM text, in one process, alternating, after a warm-up of each:
   (a) h2g_align_pairs_fetch_compact + h2g_sam_format_paired_compact on the host at 1, 8 and 32 threads — the path the command line takes by default;
   (b) h2g_align_pairs_fetch_compact + h2g_sam_plan_paired_compact (host, same thread counts) + h2g_sam_text_paired (device), split into plan / the text call's
-      upload + copy-back (its wall time less its kernels) / kernels (HIP events; the write kernel alone as well).
+      upload + copy-back (its wall time less its kernels) / kernels (HIP events; the write kernel alone as well);
+  (c) h2g_align_pairs_fetch_compact + h2g_sam_text_paired_planned: plain pairs classified and planned on the device, the host planner (same thread counts) over the
+      handed-on pairs only, merged on the device — its wall time, the planner + merge kernels, the host subset's time and share, the bytes uploaded, the share handed on.
 Medians of --repeats rounds into --out, with the write kernel's store rate against the bytes it writes and the planner's share of (b).  Needs a GPU.
 
     python tools/sam_text_bench.py --index <ht2 base> --genome <fasta[.gz]> [--pairs 1000000] [--repeats 7] [--out profiles/sam_text.json]"""
@@ -118,17 +120,48 @@ def main():
                 "bytes": used.value, "bytes_uploaded": int(s.bytes_uploaded), "lines": nl.value, "aux_bytes": na.value, "whole_lines": whole, "simple_lines": simple}, \
             dev_buf[:used.value].tobytes() if threads == 1 else None
 
+    plan_buf = pool.array("plantext", cap)
+    L.h2g_sam_text_paired_planned.argtypes = [vp] * 12 + [sz] + [vp] * 5 + [C.c_uint32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), vp]
+    lcap = {"n": 2 * n + 64}
+
+    def planned(threads):
+        L.h2g_sam_set_threads(h, threads)
+        (res, r1, b1, r2, b2), tf = fetch()
+        used, nl = sz(0), sz(0)
+        loffs = pool.array("ploffs", (lcap["n"] + 1) * 8, np.uint64)
+        ends = pool.array("pends", n * 8, np.uint64)
+        call = lambda lo, lc: L.h2g_sam_text_paired_planned(st.h, h, *ptrs, n, res.ctypes.data, r1.ctypes.data, b1.ctypes.data, r2.ctypes.data, b2.ctypes.data, khits, plan_buf.ctypes.data, cap,
+                                                            C.byref(used), lo.ctypes.data, lc, C.byref(nl), ends.ctypes.data)
+        t0 = time.perf_counter()
+        rc = call(loffs, lcap["n"])
+        if rc == api.H2G_ERR_ARG and nl.value > lcap["n"]:            # (the warm-up round sizes the line array; nothing was counted)
+            lcap["n"] = nl.value + nl.value // 8
+            loffs = pool.array("ploffs", (lcap["n"] + 1) * 8, np.uint64)
+            t0 = time.perf_counter()
+            rc = call(loffs, lcap["n"])
+        assert rc == 0, rc
+        t1 = time.perf_counter()
+        ps, _ = st.sam_plan_stats()
+        s = st.sam_text_stats()
+        return {"fetch": tf, "text_call": t1 - t0, "plan_kernels": ps.plan_kernel_ms * 1e-3, "host_subset": ps.host_plan_ms * 1e-3, "text_kernels": s.kernel_ms * 1e-3, "write_kernel": s.write_kernel_ms * 1e-3,
+                "bytes": used.value, "bytes_uploaded": int(ps.bytes_uploaded), "lines": nl.value, "device_planned": int(ps.device_planned), "host_planned": int(ps.host_planned)}, \
+            plan_buf[:used.value].tobytes() if threads == 1 else None
+
     threads = [int(t) for t in a.threads.split(",")]
     ref_text = host(1)[1]
-    identical = device(1)[1] == ref_text                # warm-up of both, and the check that they write the same bytes
+    identical = device(1)[1] == ref_text                # warm-up of each, and the check that they write the same bytes
+    identical_planned = planned(1)[1] == ref_text
     rounds = {("host", t): [] for t in threads}
     rounds.update({("device", t): [] for t in threads})
+    rounds.update({("planned", t): [] for t in threads})
     for _ in range(a.repeats):
         for t in threads:
             rounds[("host", t)].append(host(t)[0])
             rounds[("device", t)].append(device(t)[0])
+            rounds[("planned", t)].append(planned(t)[0])
     med = lambda rows, k: float(np.median([r[k] for r in rows]))
-    out = {"pairs": n, "read_length": 101, "repeats": a.repeats, "identical_text": bool(identical), "text_bytes": rounds[("host", threads[0])][0]["bytes"], "host": {}, "device": {}}
+    out = {"pairs": n, "read_length": 101, "repeats": a.repeats, "identical_text": bool(identical), "identical_text_planned": bool(identical_planned),
+           "text_bytes": rounds[("host", threads[0])][0]["bytes"], "host": {}, "device": {}, "planned": {}}
     for t in threads:
         hr, dr = rounds[("host", t)], rounds[("device", t)]
         out["host"][str(t)] = {"fetch_ms": med(hr, "fetch") * 1e3, "format_ms": med(hr, "format") * 1e3, "total_ms": (med(hr, "fetch") + med(hr, "format")) * 1e3}
@@ -138,6 +171,15 @@ def main():
         d["write_kernel_store_GBps"] = dr[0]["bytes"] / (med(dr, "write_kernel") or 1e-9) / 1e9
         d.update({k: dr[0][k] for k in ("lines", "aux_bytes", "whole_lines", "simple_lines", "bytes_uploaded")})
         out["device"][str(t)] = d
+        pr = rounds[("planned", t)]
+        c = {k + "_ms": med(pr, k) * 1e3 for k in ("fetch", "text_call", "plan_kernels", "host_subset", "text_kernels", "write_kernel")}
+        c["total_ms"] = c["fetch_ms"] + c["text_call_ms"]
+        c["host_subset_share_of_text_call"] = c["host_subset_ms"] / c["text_call_ms"]
+        c.update({k: pr[0][k] for k in ("lines", "bytes_uploaded", "device_planned", "host_planned")})
+        c["share_handed_on"] = pr[0]["host_planned"] / float(n)
+        out["planned"][str(t)] = c
+        tot = {"a": out["host"][str(t)]["total_ms"], "b": d["total_ms"], "c": c["total_ms"]}
+        c["fastest"] = min(tot, key=tot.get)
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
