@@ -3513,7 +3513,7 @@ static h2g_status sam_text_tail(h2g_stream* s, bool paired, size_t n_lines, size
 	c.aux = (const char*)s->d_sam[1]; c.n_aux = n_aux;
 	c.refname_offs = (const uint32_t*)s->d_sam[4]; c.refnames = (const char*)s->d_sam[4] + ((size_t)s->samtab_nrefs + 1) * 4; c.nrefs = s->samtab_nrefs;
 	c.rg = c.refnames + s->samtab_names; c.rg_len = s->samtab_rg; c.rna_strandness = s->samtab_strand; c.nalts = s->samtab_nalts;
-	c.first = (uint32_t)cf.first; c.paired = paired ? 1u : 0u;
+	c.first = (uint32_t)cf.first; c.paired = paired ? 1u : 0u; c.long_edits = nullptr;
 	const h2g_sam_line* d_lines = (const h2g_sam_line*)s->d_sam[0];
 	HIPCHK(hipEventRecord(s->ev_sam[0], s->st));
 	hipLaunchKernelGGL(k_sam_line_sizes, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, c, d_lines, n_lines, v, d_bad);

@@ -108,25 +108,19 @@ struct Summ {         // AlnSetSumm (aligner_result.cpp:1167-1260)
 	uint64_t numAlns[2] = {0, 0}, numAlnsPaired = 0;
 	int64_t orefid = -1, orefoff = -1;
 };
-struct Rd { const char* name; uint32_t namelen; const uint8_t* codes; uint32_t len; const char* qual; };
-// Where append_mate's lines go: text (the format calls), or one descriptor per line and the byte pool (h2g_sam_plan_*_compact: `plan`).  In plan mode `o` is only the
-// scratch a WHOLE_LINE is written to before it moves to the pool.
+struct Rd { const uint8_t* codes; uint32_t len; };
+// Where append_mate's lines go: text (the format calls: `o`), or one descriptor per line and the byte pool (h2g_sam_plan_*_compact, `plan`: `lines`, `aux`).
 struct Sink {
 	std::string o;
 	bool plan = false;
 	std::vector<h2g_sam_line> lines; std::string aux;
-	const uint8_t* recbase[2] = {nullptr, nullptr};     // the compact bytes of mate 1 / mate 2: a record's offset is its address less this
+	std::string tmp;                                    // the pool bytes (CIGAR, MD:Z, Zs:Z) of a line that is emitted at once and so keeps none
+	h2g_line::Ctx c;                                    // what the emitter reads; a record's offset is its address less c.rec[mate]
 	uint32_t read = 0;                                  // the read / pair being formatted
 };
 
-void put(std::string& o, int64_t v) {     // itoa10
-	char b[24];
-	int k = 24;
-	uint64_t u = v < 0 ? (uint64_t)(-(v + 1)) + 1 : (uint64_t)v;
-	do { b[--k] = (char)('0' + u % 10); u /= 10; } while(u);
-	if(v < 0) b[--k] = '-';
-	o.append(b + k, 24 - k);
-}
+using h2g_line::append_line;
+void put(std::string& o, int64_t v) { h2g_line::StrSink k = {o}; k.num(v); }     // a number as the emitter's sinks write it
 
 // Scoring::nFilter / length filter as the worker applies them (hisat2.cpp:3404-3440): which YF:Z flag an unaligned read gets
 void read_filters(const h2g_sam& S, const Rd& r, bool* lenfilt, bool* nfilt) { h2g_plan::read_filters(S.ncType, S.ncConst, S.ncCoeff, r.codes, r.len, lenfilt, nfilt); }
@@ -258,24 +252,14 @@ void write_mdz(const Stacked& st, std::string& o) {
 	if(mm_last || rdgap_last) o.push_back('0');
 }
 
-void seq_ascii(const Rd& r, bool fw, std::string& s, std::string& q) {
-	s.resize(r.len); q.resize(r.len);
-	for(uint32_t i = 0; i < r.len; i++) {
-		const uint32_t k = fw ? i : r.len - 1 - i;
-		const uint8_t c = r.codes[k];
-		s[i] = "ACGTN"[fw ? (c > 4 ? 4 : c) : (c > 3 ? 4 : 3 - c)];
-		q[i] = r.qual ? r.qual[k] : 'I';
-	}
+// the aligned strand of a read as text: what stack_alignment stacks the edits on
+void seq_ascii(const Rd& r, bool fw, std::string& s) {
+	s.resize(r.len);
+	h2g_line::PtrSink k = {&s[0]};
+	k.seq(r.codes, r.len, fw);
 }
-// SamConfig::printReadName sam.h:233-256 (truncQname_ = true)
-void put_read_name(std::string& o, const Rd& r, bool omitSlashMate) {
-	size_t n = r.namelen;
-	if(omitSlashMate && n >= 2 && r.name[n - 2] == '/' && (r.name[n - 1] == '1' || r.name[n - 1] == '2' || r.name[n - 1] == '3')) n -= 2;
-	if(n > 255) n = 255;
-	for(size_t i = 0; i < n; i++) { if(isspace((unsigned char)r.name[i])) return; o.push_back(r.name[i]); }
-}
-// SamConfig::printRefName: the name up to the first whitespace
-void put_ref_name(std::string& o, const std::string& name) { for(char c : name) { if(isspace((unsigned char)c)) break; o.push_back(c); } }
+// SamConfig::printRefName: the name up to the first whitespace (@SQ, the emitter's table of names, the splice-site file)
+void put_ref_name(std::string& o, const std::string& name) { for(char c : name) { if(h2g_line::is_space(c)) break; o.push_back(c); } }
 
 // AlnRes::setFragmentLength aligner_result.h:1631-1697: the ends of the fragment (h2g_sam_plan.h: fragment_ends), then the splice-site database
 int64_t fragment_length(const h2g_alnres& me, const h2g_alnres& o, bool meMate1, const h2g_sam* S = nullptr /* concordant pairs: the splice-site database */, uint64_t rdid = 0) {
@@ -391,23 +375,20 @@ void zs_value(const h2g_sam& S, const h2g_alnres& r, uint32_t rdlen, std::string
 	}
 }
 
-// AlnSinkSam::appendMate aln_sink.h:3024-3260 + printAlignedOptFlags / printEmptyOptFlags sam.h:525-1100.  What a line says beyond its record (FLAG, MAPQ, TLEN, ZS:i,
-// YT / YF, NH, the CIGAR / MD:Z of a gapped alignment, Zs:Z) is worked out first, once; then the line is written as text, or — a planning sink — handed on as a descriptor
-// for the emitter of h2g_sam_line.h, which writes what the text branch below writes.
+// AlnSinkSam::appendMate aln_sink.h:3024-3260 + printAlignedOptFlags / printEmptyOptFlags sam.h:525-1100, the deciding half.  What a line says beyond its record (FLAG,
+// MAPQ, TLEN, ZS:i, YT / YF, NH, the CIGAR / MD:Z of a gapped alignment, Zs:Z) is worked out here, once, into one descriptor.  A planning sink keeps the descriptor; a
+// text sink hands it to the emitter of h2g_sam_line.h, which alone knows the bytes of a line.  Nothing below appends to text.
 void append_mate(const h2g_sam& S, Sink& k, const Rd& rd, const Rd* rdo, const h2g_alnres* rs, const h2g_alnres* rso,
                  const Summ& summ, const Flags& fl, uint64_t nh)
 {
 	if(rs == nullptr && S.no_unal) return;                 // aln_sink.h:3040
 	static thread_local Stacked st;                       // scratch reused across lines (no per-line allocations)
-	static thread_local std::string seq, qual, zsz;
+	static thread_local std::string seq;
 	// an alignment whose edits are all mismatches (nearly every line) needs no stacked form: its CIGAR is one M run between the soft
-	// clips and its MD:Z follows from the mismatch positions; what buildCigar / buildMdz would make of the stacked strings is written directly
+	// clips and its MD:Z follows from the mismatch positions; the emitter writes what buildCigar / buildMdz would make of the stacked strings
 	bool simple = rs != nullptr;
 	if(rs) for(uint32_t i = 0; i < rs->nedits; i++) if(ED(*rs)[i].type != EDIT_MM) { simple = false; break; }
-	// a planned line whose record keeps its edits outside itself travels as text (WHOLE_LINE): the device reads inline edits only
-	const bool whole = k.plan && rs && rs->nedits > H2G_MAX_EDITS;
-	if(!k.plan || whole || (rs && !simple)) seq_ascii(rd, rs == nullptr || FW(*rs), seq, qual);
-	if(rs && !simple) stack_alignment(*rs, seq, st);
+	if(rs && !simple) { seq_ascii(rd, FW(*rs), seq); stack_alignment(*rs, seq, st); }
 	if(rs && S.collect_novel && tl_novel) add_splice_sites(*rs, rd.len, tl_rdid, *tl_novel);
 	const int f = sam_flag(fl, rs, rso);
 	const bool mate1 = fl.pairing == PAIR_UNPAIRED || fl.readMate1();   // unpaired reads are ALN_RES_TYPE_UNPAIRED_MATE1 (aln_sink.h:2368)
@@ -418,146 +399,42 @@ void append_mate(const h2g_sam& S, Sink& k, const Rd& rd, const Rd* rdo, const h
 	const bool star_seq = (!fl.primary && S.omit_sec_seq) || rd.len == 0;   // aln_sink.h:3190, :3206; a read without bases: '*' too (:3194, :3209)
 	const Score& sco = summ.secbest[mate1 ? 0 : 1];                       // summ.secbestMate(rd.mate < 2)
 	const int yt = fl.concordant() ? 1 : fl.discordant() ? 2 : fl.unpairedMate() ? 3 : 0, yf = !fl.lenfilt ? 1 : !fl.nfilt ? 2 : !fl.qcfilt ? 3 : 0;
-	static const char* const YT[4] = {"UU", "CP", "DP", "UP"};
-	static const char* const YF[4] = {"", "\tYF:Z:LN", "\tYF:Z:NS", "\tYF:Z:QC"};
-	zsz.clear();
-	if(rs) zs_value(S, *rs, rd.len, zsz);
-	if(k.plan && !whole) {
-		h2g_sam_line d;
-		memset(&d, 0, sizeof d);
-		d.read = k.read; d.nh = (uint32_t)nh;
-		d.rec_off = rs ? (uint64_t)(reinterpret_cast<const uint8_t*>(rs) - k.recbase[mate1 ? 0 : 1]) : ~0ull;
-		d.orec_off = rso ? (uint64_t)(reinterpret_cast<const uint8_t*>(rso) - k.recbase[mate1 ? 1 : 0]) : ~0ull;
-		d.tlen = tlen; d.zs = rs && sco.valid ? (int32_t)sco.score : 0;
-		d.oref_tidx = (int32_t)summ.orefid; d.oref_toff = summ.orefid != -1 ? (uint32_t)summ.orefoff : 0;
-		d.flag = (uint16_t)f; d.mapq = (uint8_t)mapq; d.mate = mate1 ? 0 : 1; d.yt = (uint8_t)yt; d.yf = (uint8_t)yf;
-		d.aux_off = (uint32_t)k.aux.size();
-		if(rs && !simple) {
-			write_cigar(st, k.aux); d.cigar_len = (uint16_t)(k.aux.size() - d.aux_off);
-			write_mdz(st, k.aux);   d.mdz_len = (uint16_t)(k.aux.size() - d.aux_off - d.cigar_len);
-		}
-		k.aux += zsz;
-		d.aux_len = (uint32_t)(k.aux.size() - d.aux_off);
-		d.bits = (uint16_t)((rs && sco.valid ? H2G_SAM_LINE_HAS_ZS : 0) | (rs && summ.paired && rso ? H2G_SAM_LINE_HAS_YS : 0) | (has_tlen ? H2G_SAM_LINE_HAS_TLEN : 0) |
-		                    (star_seq ? H2G_SAM_LINE_STAR_SEQ : 0) | (fl.partOfPair() ? H2G_SAM_LINE_STRIP_MATE_SUFFIX : 0) | (rs && !simple ? H2G_SAM_LINE_AUX_CIGAR_MDZ : 0) |
-		                    (mate1 ? H2G_SAM_LINE_SENSE_MATE1 : 0));
-		k.lines.push_back(d);
-		return;
+	// a planned line keeps its pool bytes in the plan's pool.  A text line is emitted at once; so is a planned line whose record keeps its edits outside itself, which
+	// travels as text (WHOLE_LINE): the device reads inline edits only
+	const bool whole = k.plan && rs && rs->nedits > H2G_MAX_EDITS;
+	const bool planned = k.plan && !whole;
+	std::string& pool = planned ? k.aux : k.tmp;
+	if(!planned) pool.clear();
+	h2g_sam_line d;
+	memset(&d, 0, sizeof d);
+	d.read = k.read; d.nh = (uint32_t)nh;
+	d.rec_off = rs ? (uint64_t)(reinterpret_cast<const uint8_t*>(rs) - k.c.rec[mate1 ? 0 : 1]) : ~0ull;
+	d.orec_off = rso ? (uint64_t)(reinterpret_cast<const uint8_t*>(rso) - k.c.rec[mate1 ? 1 : 0]) : ~0ull;
+	d.tlen = tlen; d.zs = rs && sco.valid ? (int32_t)sco.score : 0;
+	d.oref_tidx = (int32_t)summ.orefid; d.oref_toff = summ.orefid != -1 ? (uint32_t)summ.orefoff : 0;
+	d.flag = (uint16_t)f; d.mapq = (uint8_t)mapq; d.mate = mate1 ? 0 : 1; d.yt = (uint8_t)yt; d.yf = (uint8_t)yf;
+	d.aux_off = (uint32_t)pool.size();
+	if(rs && !simple) {
+		write_cigar(st, pool); d.cigar_len = (uint16_t)(pool.size() - d.aux_off);
+		write_mdz(st, pool);   d.mdz_len = (uint16_t)(pool.size() - d.aux_off - d.cigar_len);
 	}
-	std::string& o = k.o;
-	put_read_name(o, rd, fl.partOfPair());
-	o.push_back('\t');
-	put(o, f); o.push_back('\t');
-	if(rs) put_ref_name(o, S.refnames[rs->tidx]);
-	else if(summ.orefid != -1) put_ref_name(o, S.refnames[(size_t)summ.orefid]);
-	else o.push_back('*');
-	o.push_back('\t');
-	if(rs) put(o, (int64_t)rs->toff + 1);
-	else if(summ.orefid != -1) put(o, summ.orefoff + 1);
-	else o.push_back('0');
-	o.push_back('\t');
-	if(rs) put(o, mapq);
-	else o.push_back('0');
-	o.push_back('\t');
-	if(rs && simple) {
-		if(rs->trim5 > 0) { put(o, rs->trim5); o.push_back('S'); }
-		put(o, (int64_t)(rd.len - rs->trim5 - rs->trim3)); o.push_back('M');
-		if(rs->trim3 > 0) { put(o, rs->trim3); o.push_back('S'); }
-	} else if(rs) write_cigar(st, o); else o.push_back('*');
-	o.push_back('\t');
-	if(rs && fl.partOfPair()) {                                         // RNEXT
-		if(rso && rs->tidx != rso->tidx) put_ref_name(o, S.refnames[rso->tidx]); else o.push_back('=');
-	} else if(summ.orefid != -1) o.push_back('=');
-	else o.push_back('*');
-	o.push_back('\t');
-	if(rs && fl.partOfPair()) put(o, (int64_t)(rso ? rso->toff : rs->toff) + 1);   // PNEXT
-	else if(summ.orefid != -1) put(o, summ.orefoff + 1);
-	else o.push_back('0');
-	o.push_back('\t');
-	if(has_tlen) put(o, tlen);
-	else o.push_back('0');
-	o.push_back('\t');
-	if(star_seq) o += "*\t*\t";
-	else { o += seq; o.push_back('\t'); o += qual; o.push_back('\t'); }
-	if(!rs) {                                                            // printEmptyOptFlags sam.h:1033-1100
-		o += "YT:Z:";
-		o += YT[yt]; o += YF[yf];
-		if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }   // sam.h:1102
-		o.push_back('\n');
-		return;
-	}
-	o += "AS:i:"; put(o, rs->score);
-	if(sco.valid) { o += "\tZS:i:"; put(o, sco.score); }
-	o += "\tXN:i:0";                                                       // refNs is never set (hi_aligner.h:6170)
-	const size_t nalts = S.alts.size();
-	size_t num_mm = 0, num_go = 0, num_gx = 0, NM = 0;
-	for(uint32_t i = 0; i < rs->nedits; i++) {                            // on the edits as stored (5'-relative)
-		const h2g_edit* e = ED(*rs);
-		if(e[i].type == EDIT_SPL) continue;
-		if(e[i].type == EDIT_MM) { if(e[i].snp >= nalts) num_mm++; }
-		else if(e[i].type == EDIT_READ_GAP) {
-			if(e[i].snp >= nalts) { num_go++; num_gx++; }
-			while(i + 1 < rs->nedits && e[i + 1].pos == e[i].pos && e[i + 1].type == EDIT_READ_GAP) { i++; if(e[i].snp >= nalts) num_gx++; }
-		} else if(e[i].type == EDIT_REF_GAP) {
-			if(e[i].snp >= nalts) { num_go++; num_gx++; }
-			while(i + 1 < rs->nedits && e[i + 1].pos == e[i].pos + 1 && e[i + 1].type == EDIT_REF_GAP) { i++; if(e[i].snp >= nalts) num_gx++; }
-		}
-	}
-	for(uint32_t i = 0; i < rs->nedits; i++) if(ED(*rs)[i].type != EDIT_SPL && ED(*rs)[i].snp >= nalts) NM++;
-	o += "\tXM:i:"; put(o, (int64_t)num_mm);
-	o += "\tXO:i:"; put(o, (int64_t)num_go);
-	o += "\tXG:i:"; put(o, (int64_t)num_gx);
-	o += "\tNM:i:"; put(o, (int64_t)NM);
-	o += "\tMD:Z:";
-	if(simple) {   // writeMdz over '=' runs and 'X' cells only: a run length (0 between two mismatches and at either end), then the reference base
-		const uint32_t lt = rd.len - rs->trim5 - rs->trim3;
-		uint32_t at = 0;                                               // the next position of the aligned strand not yet accounted for
-		for(uint32_t k = 0; k < rs->nedits; k++) {
-			const h2g_edit& e = ED(*rs)[FW(*rs) ? k : rs->nedits - 1 - k];
-			const uint32_t pos = FW(*rs) ? e.pos : lt - 1 - e.pos;
-			if(pos > at) put(o, (int64_t)(pos - at)); else o.push_back('0');
-			o.push_back((char)e.chr);
-			at = pos + 1;
-		}
-		if(lt > at) put(o, (int64_t)(lt - at)); else o.push_back('0');
-	} else write_mdz(st, o);
-	if(summ.paired && rso) { o += "\tYS:i:"; put(o, rso->score); }
-	o += "\tYT:Z:";
-	o += YT[yt]; o += YF[yf];
-	if(!S.rg_optflag.empty()) { o.push_back('\t'); o += S.rg_optflag; }       // sam.h:780
-	if(S.rna_strandness != 0) {   // a stranded library: the tag follows from the mate and the strand it aligned to (sam.h:940-966)
-		char strand = '+';
-		const bool m1 = mate1;
-		const int rs_ = S.rna_strandness;
-		if(m1) { if(FW(*rs)) { if(rs_ == 2 || rs_ == 4) strand = '-'; } else if(rs_ == 1 || rs_ == 3) strand = '-'; }
-		else   { if(FW(*rs)) { if(rs_ == 3) strand = '-'; } else if(rs_ == 4) strand = '-'; }
-		o += "\tXS:A:"; o.push_back(strand);
-	} else {   // XS:A: sam.h:925-940 with AlnRes::spliced_whichsense_transcript aligner_result.h:1289 (unstranded library)
-		uint32_t sense = 1;
-		for(uint32_t i = 0; i < rs->nedits; i++) {
-			if(ED(*rs)[i].type != EDIT_SPL) continue;
-			const uint32_t d = spl_dir(ED(*rs)[i]);
-			if(sense == 1) sense = d;
-			else if(d != 1) {
-				if((sense == 2 || sense == 4) && d != 2 && d != 4) { sense = 1; break; }
-				if((sense == 3 || sense == 5) && d != 3 && d != 5) { sense = 1; break; }
-			}
-		}
-		if(sense != 1) { o += "\tXS:A:"; o.push_back((sense == 2 || sense == 4) ? '+' : '-'); }
-	}
-	o += "\tNH:i:"; put(o, (int64_t)nh);
-	if(!zsz.empty()) { o += "\tZs:Z:"; o += zsz; }
-	o.push_back('\n');
-	if(whole) {      // the line just written moves to the pool
-		h2g_sam_line d;
-		memset(&d, 0, sizeof d);
-		d.read = k.read; d.nh = (uint32_t)nh; d.rec_off = d.orec_off = ~0ull; d.oref_tidx = -1;
-		d.flag = (uint16_t)f; d.mapq = (uint8_t)mapq; d.mate = mate1 ? 0 : 1; d.yt = (uint8_t)yt; d.yf = (uint8_t)yf;
-		d.aux_off = (uint32_t)k.aux.size(); d.aux_len = (uint32_t)o.size();
-		d.bits = H2G_SAM_LINE_WHOLE_LINE;
-		k.aux += o; o.clear();
-		k.lines.push_back(d);
-	}
+	if(rs) zs_value(S, *rs, rd.len, pool);
+	d.aux_len = (uint32_t)(pool.size() - d.aux_off);
+	d.bits = (uint16_t)((rs && sco.valid ? H2G_SAM_LINE_HAS_ZS : 0) | (rs && summ.paired && rso ? H2G_SAM_LINE_HAS_YS : 0) | (has_tlen ? H2G_SAM_LINE_HAS_TLEN : 0) |
+	                    (star_seq ? H2G_SAM_LINE_STAR_SEQ : 0) | (fl.partOfPair() ? H2G_SAM_LINE_STRIP_MATE_SUFFIX : 0) | (rs && !simple ? H2G_SAM_LINE_AUX_CIGAR_MDZ : 0) |
+	                    (mate1 ? H2G_SAM_LINE_SENSE_MATE1 : 0));
+	if(planned) { k.lines.push_back(d); return; }
+	k.c.aux = pool.data(); k.c.n_aux = pool.size();
+	if(!whole) { append_line(k.c, d, k.o); return; }
+	h2g_sam_line w;      // the emitter's output for d goes to the pool; what stays of d is what says whose line it is
+	memset(&w, 0, sizeof w);
+	w.read = d.read; w.nh = d.nh; w.rec_off = w.orec_off = ~0ull; w.oref_tidx = -1;
+	w.flag = d.flag; w.mapq = d.mapq; w.mate = d.mate; w.yt = d.yt; w.yf = d.yf;
+	w.aux_off = (uint32_t)k.aux.size();
+	append_line(k.c, d, k.aux);
+	w.aux_len = (uint32_t)(k.aux.size() - w.aux_off);
+	w.bits = H2G_SAM_LINE_WHOLE_LINE;
+	k.lines.push_back(w);
 }
 
 // selectByScore aln_sink.h:2680-2760 on a list of AlnScore keys; RandomSource random_source.h:33
@@ -674,12 +551,24 @@ extern "C" size_t h2g_sam_header(const h2g_sam* S, const char* cmdline, char* ou
 namespace {
 // formats reads [0, n) with `one(i, text)` on S->threads host threads (contiguous ranges, concatenated in read order)
 // what a planning call hands drive() in place of a text buffer
-struct PlanOut { h2g_sam_line* lines; size_t line_cap; size_t* n_lines; char* aux; size_t aux_cap; size_t* aux_used; uint64_t* line_ends; const uint8_t* recbase[2];
+struct PlanOut { h2g_sam_line* lines; size_t line_cap; size_t* n_lines; char* aux; size_t aux_cap; size_t* aux_used; uint64_t* line_ends;
 	// the split planner (h2g_sam_plan.h plan_subset): item j of the call is read subset[j]; the lines and the pool go to vectors that take any size; what would be counted
 	// into the handle goes to *defer instead
 	const uint32_t* subset = nullptr; std::vector<h2g_sam_line>* vlines = nullptr; std::string* vaux = nullptr; Met* defer = nullptr; };
+// What the emitter reads in a host call: the reads, the records of either mate (rec_off counts from rec1 / rec2 in any layout; nrec: their bytes, for the calls that check
+// descriptors they were given), the handle's tables and its long-edit area.  The pool (aux) is set where the lines are.
+h2g_line::Ctx host_ctx(const h2g_sam* S, const h2g_line::Tables& t, const h2g_plan::HostSets& rd, const uint8_t* rec1, uint64_t nrec1, const uint8_t* rec2, uint64_t nrec2) {
+	h2g_line::Ctx c = {{rd.names[0], rd.names[1]}, {rd.noffs[0], rd.noffs[1]}, {rd.codes[0], rd.codes[1]}, {rd.offs[0], rd.offs[1]}, {rd.quals[0], rd.quals[1]}, {rec1, rec2}, {nrec1, nrec2},
+	                   nullptr, 0, t.refnames.data(), t.refname_offs.data(), (uint32_t)(t.refname_offs.size() - 1), t.rg.data(), (uint32_t)t.rg.size(), t.rna_strandness, t.nalts, 0,
+	                   rd.codes[1] ? 1u : 0u, S->long_edits};
+	return c;
+}
+// `rd`, `rec1`, `rec2`: the reads and the records of the call, for the emitter (its tables are made here, once per call)
 template <class F>
-h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_t* used, const PlanOut* po = nullptr) {
+h2g_status drive(const h2g_sam* S, size_t n, F one, const h2g_plan::HostSets& rd, const void* rec1, const void* rec2, char* out, size_t cap, size_t* used, const PlanOut* po = nullptr) {
+	h2g_line::Tables tables;
+	h2g_line::sam_tables(S, tables);
+	const h2g_line::Ctx ctx = host_ctx(S, tables, rd, static_cast<const uint8_t*>(rec1), 0, static_cast<const uint8_t*>(rec2), 0);
 	size_t T = S->threads < 1 ? 1 : (size_t)S->threads;
 	if(T > n / 2048 + 1) T = n / 2048 + 1;
 	// per-thread text and counters, each on cache lines of its own: a std::string's size field changes with every append, and two of them (or two threads' counters) in
@@ -693,7 +582,8 @@ h2g_status drive(const h2g_sam* S, size_t n, F one, char* out, size_t cap, size_
 	auto work = [&](size_t t) {
 		const size_t b = n * t / T, e = n * (t + 1) / T;
 		Sink& o = parts_[t].k;
-		if(po) { o.plan = true; o.recbase[0] = po->recbase[0]; o.recbase[1] = po->recbase[1]; o.lines.reserve((e - b) * 2); }
+		o.c = ctx;
+		if(po) { o.plan = true; o.lines.reserve((e - b) * 2); }
 		else o.o.reserve((e - b) * 760);                // (two lines of a 101 bp pair; longer reads grow it)
 		tl_novel = &mets[t].novel;
 		tl_long_edits = S->long_edits; tl_long_edits_n = S->n_long_edits;
@@ -990,7 +880,7 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 	if(compact) aln = reinterpret_cast<const h2g_alnres*>(compact);       // (aln_offs are byte offsets then)
 	if(!S || !codes || !offs || !nb || !noffs || !res || !aln || !used) return H2G_ERR_ARG;
 	auto one = [&](size_t i, Sink& o, Met& met) {
-		Rd rd = {nb + noffs[i], noffs[i + 1] - noffs[i], codes + offs[i], offs[i + 1] - offs[i], quals ? quals + offs[i] : nullptr};
+		Rd rd = {codes + offs[i], offs[i + 1] - offs[i]};
 		Flags fl;
 		read_filters(*S, rd, &fl.lenfilt, &fl.nfilt);
 		fl.qcfilt = !S->qc1 || S->qc1[i] != 0;
@@ -1012,7 +902,7 @@ static h2g_status format_unpaired(const h2g_sam* S, const uint8_t* codes, const 
 			append_mate(*S, o, rd, nullptr, &R[k], nullptr, summ, fl, nsel);
 		}
 	};
-	return drive(S, n, one, out, cap, used, po);
+	return drive(S, n, one, {{codes, nullptr}, {offs, nullptr}, {quals, nullptr}, {nb, nullptr}, {noffs, nullptr}}, aln, nullptr, out, cap, used, po);
 }
 
 extern "C" h2g_status h2g_sam_format_unpaired(const h2g_sam* S, const uint8_t* codes, const uint32_t* offs, const char* quals,
@@ -1046,8 +936,7 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 		sel.clear(); sel1.clear(); sel2.clear(); keys.clear();
 		met.nread++; met.npaired++;
 		const h2g_pair_result& pr = res[i];
-		Rd rd[2] = {{nb1 + noffs1[i], noffs1[i + 1] - noffs1[i], codes1 + offs1[i], offs1[i + 1] - offs1[i], quals1 ? quals1 + offs1[i] : nullptr},
-		            {nb2 + noffs2[i], noffs2[i + 1] - noffs2[i], codes2 + offs2[i], offs2[i + 1] - offs2[i], quals2 ? quals2 + offs2[i] : nullptr}};
+		Rd rd[2] = {{codes1 + offs1[i], offs1[i + 1] - offs1[i]}, {codes2 + offs2[i], offs2[i + 1] - offs2[i]}};
 		Recs r1, r2;
 		size_t n1, n2;
 		const h2g_alnres* trailer = nullptr;   // the whole concordant list of a pair beyond what h2g_pair_result carries (include/h2g.h)
@@ -1164,7 +1053,7 @@ static h2g_status format_paired(const h2g_sam* S, const uint8_t* codes1, const u
 			} else { unal(0, nullptr); unal(1, nullptr); }
 		}
 	};
-	return drive(S, n, one, out, cap, used, po);
+	return drive(S, n, one, {{codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {nb1, nb2}, {noffs1, noffs2}}, aln1, aln2, out, cap, used, po);
 }
 
 extern "C" h2g_status h2g_sam_format_paired_compact(const h2g_sam* S, const uint8_t* codes1, const uint32_t* offs1, const char* quals1,
@@ -1216,7 +1105,7 @@ extern "C" h2g_status h2g_sam_plan_unpaired_compact(const h2g_sam* S, const uint
 {
 	if(!boffs || !S || !rec || !res || !n_lines || !aux_used) return H2G_ERR_ARG;
 	if(!compact_ok(S, rec, boffs, n, [&](size_t i) { return (size_t)res[i].nselect; })) return H2G_ERR_ARG;
-	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends, {rec, nullptr}};
+	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends};
 	size_t used = 0;
 	return format_unpaired(S, codes, offs, quals, nb, noffs, n, res, nullptr, boffs, nullptr, 0, &used, rec, &po);
 }
@@ -1227,7 +1116,7 @@ extern "C" h2g_status h2g_sam_plan_paired_compact(const h2g_sam* S, const uint8_
 {
 	if(!boffs1 || !boffs2 || !S || !rec1 || !rec2 || !res || !n_lines || !aux_used) return H2G_ERR_ARG;
 	if(!compact_ok(S, rec1, boffs1, n, [](size_t) { return (size_t)0; }, true) || !compact_ok(S, rec2, boffs2, n, [](size_t) { return (size_t)0; })) return H2G_ERR_ARG;
-	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends, {rec1, rec2}};
+	const PlanOut po = {lines, line_cap, n_lines, aux, aux_cap, aux_used, line_ends};
 	size_t used = 0;
 	return format_paired(S, codes1, offs1, quals1, nb1, noffs1, codes2, offs2, quals2, nb2, noffs2, n, res, nullptr, boffs1, nullptr, boffs2, khits, nullptr, 0, &used, rec1, rec2, &po);
 }
@@ -1267,15 +1156,16 @@ extern "C" h2g_status h2g_sam_text_from_plan_host(const h2g_sam* S, const uint8_
 	if(paired && (!offs2 || !nb2 || !noffs2)) return H2G_ERR_ARG;
 	h2g_line::Tables t;
 	h2g_line::sam_tables(S, t);
-	h2g_line::Ctx c = {{nb1, nb2}, {noffs1, noffs2}, {codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {rec1, rec2}, {n_rec1, paired ? n_rec2 : 0}, aux, n_aux,
-	                   t.refnames.data(), t.refname_offs.data(), (uint32_t)S->refnames.size(), t.rg.data(), (uint32_t)t.rg.size(), t.rna_strandness, t.nalts, 0, paired ? 1u : 0u};
+	h2g_line::Ctx c = host_ctx(S, t, {{codes1, codes2}, {offs1, offs2}, {quals1, quals2}, {nb1, nb2}, {noffs1, noffs2}}, rec1, n_rec1, rec2, paired ? n_rec2 : 0);
+	c.aux = aux; c.n_aux = n_aux;
 	if(h2g_line::plan_check(lines, n_lines, n, paired, c.nrec[0], c.nrec[1], n_aux, c.nrefs)) return H2G_ERR_ARG;
 	for(size_t j = 0; j < n_lines; j++) if(!h2g_line::line_records_ok(c, lines[j])) return H2G_ERR_ARG;
+	std::string text;
 	std::vector<uint64_t> at(n_lines + 1, 0);
-	for(size_t j = 0; j < n_lines; j++) { h2g_line::CountSink k; h2g_line::emit_line(c, lines[j], k); at[j + 1] = at[j] + k.n; }
-	*used = at[n_lines];
-	if(at[n_lines] > cap || (at[n_lines] && !out)) return H2G_ERR_ARG;
-	for(size_t j = 0; j < n_lines; j++) { h2g_line::PtrSink k = {out + at[j]}; h2g_line::emit_line(c, lines[j], k); }
+	for(size_t j = 0; j < n_lines; j++) { append_line(c, lines[j], text); at[j + 1] = text.size(); }
+	*used = text.size();
+	if(text.size() > cap || (text.size() && !out)) return H2G_ERR_ARG;
+	if(!text.empty()) memcpy(out, text.data(), text.size());
 	if(line_offs) memcpy(line_offs, at.data(), (n_lines + 1) * 8);
 	return H2G_OK;
 }
@@ -1298,7 +1188,7 @@ h2g_status plan_subset(const h2g_sam* S, bool paired, const HostSets& rd, size_t
 	if(nidx == 0) return H2G_OK;
 	HostPart* hp = new HostPart();
 	size_t nl = 0, na = 0, used = 0;
-	PlanOut po = {nullptr, 0, &nl, nullptr, 0, &na, ends.data(), {rec1, paired ? rec2 : nullptr}};
+	PlanOut po = {nullptr, 0, &nl, nullptr, 0, &na, ends.data()};
 	po.subset = idx; po.vlines = &lines; po.vaux = &aux; po.defer = &hp->met;
 	h2g_status rc;
 	if(paired) {

@@ -1,7 +1,9 @@
-// h2g_sam_line.h — one SAM line from its descriptor (include/h2g.h h2g_sam_line), the resident reads and the compact records: the byte-producing half of
-// append_mate (h2g_sam.cpp), as code that the host and the kernels share.  The emitter is templated on a sink, so the pass that sizes a line (CountSink), the host's
-// writer (PtrSink) and the kernels' lane-group writer (GroupSink) run the same statements and cannot disagree on a length.
-// Nothing here decides anything: FLAG, MAPQ, TLEN, ZS:i, YT / YF, NH and the CIGAR / MD:Z of gapped lines come with the descriptor (h2g_sam_plan_*_compact).
+// h2g_sam_line.h — one SAM line from its descriptor (include/h2g.h h2g_sam_line), the reads and the records: the byte-producing half of append_mate (h2g_sam.cpp),
+// and the only place that states the bytes of a line.  The host's format calls (every record layout), its plan-to-text call and the kernels all write through
+// emit_line.  It is templated on a sink, so the pass that sizes a line (CountSink), the host's writer (StrSink) and the kernels' lane-group writer (GroupSink) run
+// the same statements and cannot disagree on a length.
+// Nothing here decides anything: FLAG, MAPQ, TLEN, ZS:i, YT / YF, NH and the CIGAR / MD:Z of gapped lines come with the descriptor (append_mate; make_line of
+// h2g_sam_plan.h for the plain lines planned on the device).
 #ifndef H2G_SAM_LINE_H_
 #define H2G_SAM_LINE_H_
 #include <stdint.h>
@@ -25,13 +27,15 @@ struct Ctx {
 	const char* names[2]; const uint32_t* noffs[2];        // read names of mate 1 / mate 2 (unpaired runs: [0] only)
 	const uint8_t* codes[2]; const uint32_t* offs[2];      // codes 0..4 (above: N), one byte per base
 	const char* quals[2];                                  // phred+33, or nullptr: 'I'
-	const uint8_t* rec[2]; uint64_t nrec[2];               // the compact records of the fetch (h2g_align_*_fetch_compact) and their byte counts
+	const uint8_t* rec[2]; uint64_t nrec[2];               // what a line's rec_off / orec_off count from, per mate, and the bytes there: the compact records of the fetch
+	                                                       // (h2g_align_*_fetch_compact); in the host's format calls the records of any layout (nrec is not read there)
 	const char* aux; uint64_t n_aux;
 	const char* refnames; const uint32_t* refname_offs; uint32_t nrefs;   // cut at the first blank, after the chrname mode
 	const char* rg; uint32_t rg_len;                       // "RG:Z:<id>" or empty
 	int32_t rna_strandness; uint32_t nalts;
 	uint32_t first;                                        // lines[].read counts from here
 	uint32_t paired;
+	const h2g_edit* long_edits;                            // host only: the batch's long-edit area (h2g_sam_set_long_edits), or nullptr.  The kernels do not read it
 };
 
 H2G_HD bool is_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // isspace of the C locale
@@ -49,7 +53,7 @@ struct CountSink {
 	H2G_HD void finish() {}
 };
 
-// one writer (the host's text call)
+// one writer into memory that has room (the pieces of the host's StrSink below; tests/samtext/line_check.cpp)
 struct PtrSink {
 	char* p;
 	H2G_HD void ch(char c) { *p++ = c; }
@@ -121,6 +125,15 @@ struct GroupSink {
 enum { EDIT_READ_GAP = 1, EDIT_REF_GAP = 2, EDIT_MM = 3, EDIT_SPL = 5 };
 #define H2G_LINE_LIT(k, s) (k).lit(s, (uint32_t)(sizeof(s) - 1))
 
+// The edits of a record.  One with more than H2G_MAX_EDITS keeps them in the long-edit area, edits[0].pos their offset there: the host's format calls reach them (they
+// have checked the area's extent), the kernels never meet such a record (record_ok refuses it; the host sends its line whole).
+H2G_HD const h2g_edit* edits_of(const Ctx& c, const h2g_alnres* rs) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+	if(rs->nedits > H2G_MAX_EDITS) return c.long_edits + rs->edits[0].pos;
+#endif
+	return rs->edits;
+}
+
 template <class Sink>
 H2G_HD void put_ref_name(Sink& k, const Ctx& c, uint32_t tidx) { k.bytes(c.refnames + c.refname_offs[tidx], c.refname_offs[tidx + 1] - c.refname_offs[tidx]); }
 
@@ -185,7 +198,7 @@ H2G_HD void emit_line(const Ctx& c, const h2g_sam_line& L, Sink& k) {
 	if(L.bits & H2G_SAM_LINE_HAS_ZS) { H2G_LINE_LIT(k, "\tZS:i:"); k.num(L.zs); }
 	H2G_LINE_LIT(k, "\tXN:i:0");
 	const uint32_t ne = rs->nedits;
-	const h2g_edit* e = rs->edits;
+	const h2g_edit* e = edits_of(c, rs);
 	uint32_t num_mm = 0, num_go = 0, num_gx = 0, NM = 0;
 	for(uint32_t j = 0; j < ne; j++) {
 		if(e[j].type == EDIT_SPL) continue;
@@ -262,6 +275,34 @@ H2G_HD bool line_records_ok(const Ctx& c, const h2g_sam_line& L) {
 }
 
 // ---- host side of the text calls (h2g_sam.cpp) ---------------------------------------------------------------------------------
+// The host's writer, for the format calls and for h2g_sam_text_from_plan_host: the line goes to the end of a string, in one pass (no sizing pass: the string grows).
+// SEQ and QUAL pass through a buffer on the stack, PtrSink's loops filling it, so that the string's new bytes are written once.
+struct StrSink {
+	std::string& o;
+	void ch(char c) { o.push_back(c); }
+	void lit(const char* s, uint32_t len) { o.append(s, len); }
+	void num(int64_t v) {      // backwards from the end of a buffer: no digit count first
+		char b[24];
+		int k = 24;
+		uint64_t u = v < 0 ? (uint64_t)(-(v + 1)) + 1 : (uint64_t)v;
+		do { b[--k] = (char)('0' + u % 10); u /= 10; } while(u);
+		if(v < 0) b[--k] = '-';
+		o.append(b + k, (size_t)(24 - k));
+	}
+	void bytes(const char* s, uint64_t len) { o.append(s, (size_t)len); }
+	void seq(const uint8_t* c, uint32_t len, bool fw) {
+		char b[256];
+		for(uint32_t at = 0; at < len; at += 256) { const uint32_t m = len - at < 256 ? len - at : 256; PtrSink k = {b}; k.seq(c + (fw ? at : len - at - m), m, fw); o.append(b, m); }
+	}
+	void qual(const char* q, uint32_t len, bool fw) {
+		if(q && fw) { o.append(q, len); return; }
+		if(!q) { o.append(len, 'I'); return; }
+		char b[256];
+		for(uint32_t at = 0; at < len; at += 256) { const uint32_t m = len - at < 256 ? len - at : 256; PtrSink k = {b}; k.qual(q + (len - at - m), m, false); o.append(b, m); }
+	}
+	void finish() {}
+};
+inline void append_line(const Ctx& c, const h2g_sam_line& L, std::string& o) { StrSink k = {o}; emit_line(c, L, k); }
 // the per-handle tables a text call needs: rebuilt when uid / gen differ from what the caller holds
 struct Tables { uint64_t uid = 0, gen = 0; std::string refnames; std::vector<uint32_t> refname_offs; std::string rg; int32_t rna_strandness = 0; uint32_t nalts = 0; };
 void sam_tables_key(const struct ::h2g_sam* S, uint64_t* uid, uint64_t* gen);

@@ -2,7 +2,8 @@
 // descriptors (include/h2g.h) that h2g_sam_plan_*_compact makes, field for field, for the reads whose lines are closed-form functions of their result header and their
 // one or two records.  Every other read is HANDED ON to the host planner, which stays in one copy (selection with draws, the MAPQ ladder, left-alignment, Zs:Z, the
 // splice-site database in TLEN, add_splice_sites).  The leaves both planners need (hisat2_score / score_of, sam_flag, the ends of a fragment, the read filters) live here
-// and h2g_sam.cpp calls them.
+// and h2g_sam.cpp calls them.  Neither planner writes text: a descriptor becomes bytes in the emitter of h2g_sam_line.h alone, in the kernels or, for the host's format
+// calls, right where append_mate has filled it.
 //
 // The predicate "plain" (stated here once; tests/sam_split_util.py restates it independently):
 //   A record PARSES when its 40-byte prefix and its inline edits lie inside its read's bytes [boffs[i], boffs[i + 1]) and it is no pair trailer.  A read's bytes parse when
@@ -265,7 +266,7 @@ H2G_HD uint32_t classify_pair(const Opts& O, const In& in, const h2g_pair_result
 	return u0 && u1 ? CLS_P_BOTH : u0 ? CLS_P_MATE1 : u1 ? CLS_P_MATE2 : CLS_P_NONE;
 }
 
-// One descriptor, as append_mate's planning branch fills it for a record without pool bytes (or for no record).  aux_off is left 0: the merge sets it.
+// One descriptor, as append_mate fills it for a record without pool bytes (or for no record).  aux_off is left 0: the merge sets it.
 struct LineIn {
 	uint32_t read, rdlen, nh;
 	const h2g_alnres* rs; const h2g_alnres* rso; uint64_t rec_off, orec_off;

@@ -3,6 +3,7 @@ of sam_lines.load_sam_lib() that lets every call through and, at each h2g_sam_fo
 emitter's host instantiation on twin handles set up by replaying the setter calls the handle under test has seen.  Whatever helper formats records through
 sam_lines (test_sam_lines, test_long_edits_cpu, temp_splice, ...) is checked without a change to it."""
 import ctypes as C
+import hashlib
 
 import numpy as np
 
@@ -11,6 +12,7 @@ from hisat2_amd import api
 vp, sz = C.c_void_p, C.c_size_t
 REPLAYED = ("h2g_sam_set_", "h2g_sam_add_", "h2g_sam_collect_")
 STATS = {"calls": 0, "lines": 0, "whole": 0, "aux_lines": 0, "simple": 0, "refused": 0, "novel": 0}
+DIGESTS = None            # a list: every h2g_sam_format_* call through a PlanCheckLib appends format_digests() of itself (test_sam_plan_cpu.text_digests)
 
 
 def _val(h):
@@ -66,6 +68,56 @@ def has_long_record(rec, nbytes):
             return True
         at += (40 + 12 * ne + 7) & ~7
     return False
+
+
+def _sha(*parts):
+    d = hashlib.sha256()
+    for p in parts:
+        p = p if isinstance(p, bytes) else repr(p).encode()
+        d.update(b"%d:" % len(p))
+        d.update(p)
+    return d.hexdigest()
+
+
+def _mem(x, nbytes):
+    return b"" if x is None else bytes(x[:nbytes]) if isinstance(x, bytes) else C.string_at(_addr(x), nbytes)
+
+
+def format_inputs(L, name, a, log):
+    """everything a format call reads, as bytes: the handle's header (reference names and lengths) and the setter calls it has seen (`log`, with the long-edit area's
+    entries), then every array at the size the call's own counts and offsets give it.  name / a: the h2g_sam_format_* function and its arguments"""
+    paired = "unpaired" not in name
+    nsets = 2 if paired else 1
+    n = a[1 + 5 * nsets]
+    rest = a[2 + 5 * nsets:]                                  # res, then the records in the layout the name says
+    hb = C.create_string_buffer(1 << 16)
+    L.h2g_sam_header.argtypes = [vp, C.c_char_p, vp, sz]
+    L.h2g_sam_header.restype = sz
+    parts = [name, n, hb.raw[:L.h2g_sam_header(a[0], b"", hb, 1 << 16)]]
+    for nm, ar in log:
+        if nm == "h2g_sam_set_record_ends":                    # (an output array)
+            continue
+        if nm == "h2g_sam_set_long_edits":
+            parts += [nm, ar[2], _mem(ar[1], ar[2] * C.sizeof(api.Edit))]
+        else:
+            parts += [nm] + [x if isinstance(x, (int, float, bytes, type(None))) else bytes(x) for x in ar[1:]]
+    for m in range(nsets):
+        codes, offs, quals, nb, noffs = a[1 + 5 * m:6 + 5 * m]
+        o = np.frombuffer(_mem(offs, 4 * (n + 1)), dtype=np.uint32)
+        no = np.frombuffer(_mem(noffs, 4 * (n + 1)), dtype=np.uint32)
+        parts += [o.tobytes(), _mem(codes, int(o[n])), _mem(quals, int(o[n])), no.tobytes(), _mem(nb, int(no[n]))]
+    parts.append(_mem(rest[0], n * C.sizeof(api.PairResult if paired else api.ReadResult)))
+    rs, cap = C.sizeof(api.AlnRes), api.PAIR_RES_CAP if paired else api.ALN_CAP
+    if name.endswith(("_dense", "_compact")):                  # records, offsets [n + 1] per mate: counted in records / in bytes
+        unit = rs if name.endswith("_dense") else 1
+        for m in range(nsets):
+            bo = np.frombuffer(_mem(rest[2 + 2 * m], 8 * (n + 1)), dtype=np.uint64)
+            parts += [bo.tobytes(), _mem(rest[1 + 2 * m], int(bo[n]) * unit)]
+    else:
+        parts += [_mem(rest[1 + m], n * cap * rs) for m in range(nsets)]
+    if paired:
+        parts.append(rest[-4])                                # khits
+    return parts
 
 
 def plan_and_text(L, h, paired, a, with_ends=True):
@@ -143,6 +195,17 @@ class PlanCheckLib:
             getattr(self._L, name)(h, *args[1:])
         return h
 
+    def _format(self, name, real, a, st):
+        """the format call itself; with DIGESTS set, also what it read, what it wrote and the handle's summary after it, each as a SHA-256"""
+        if DIGESTS is None:
+            return real(*a)
+        inputs = _sha(*format_inputs(self._L, name, a, st["log"]))
+        rc = real(*a)
+        out, used = a[-3], a[-1]._obj.value
+        text = b"" if rc != 0 else out.raw[:used] if hasattr(out, "raw") else C.string_at(_addr(out), used)
+        DIGESTS.append({"call": name, "rc": rc, "inputs": inputs, "text": _sha(text), "summary": _sha(summary(self._L, a[0]))})
+        return rc
+
     def _call(self, name, real, a):
         L = self._L
         if name == "h2g_sam_open":
@@ -164,6 +227,7 @@ class PlanCheckLib:
         if name not in ("h2g_sam_format_unpaired_compact", "h2g_sam_format_paired_compact"):
             if name.startswith("h2g_sam_format_"):
                 st["formats"] += 1
+                return self._format(name, real, a, st)
             return real(*a)
         paired = name.endswith("paired_compact") and "unpaired" not in name
         n = a[11] if paired else a[6]
@@ -176,7 +240,7 @@ class PlanCheckLib:
         if not st["own_ends"]:
             L.h2g_sam_set_record_ends.argtypes = [vp, vp]
             L.h2g_sam_set_record_ends(a[0], ends.ctypes.data)
-        rc = real(*a)
+        rc = self._format(name, real, a, st)
         if not st["own_ends"]:
             L.h2g_sam_set_record_ends(a[0], None)
         st["formats"] += 1

@@ -1,6 +1,7 @@
 // line_check.cpp — stand-alone host check of the SAM line emitter (hisat2_amd/csrc/h2g_sam_line.h): for every case it builds the arrays a line reads, exactly sized on
-// the heap, and asserts that the counting sink's byte count, the single writer's text and the text the lane-group sink leaves — driven lane by lane, sixteen lanes a
-// line as the write kernel runs it, each lane with a staging buffer of its own, into a buffer of exactly the counted size — all equal a naive string build.
+// the heap, and asserts that the counting sink's byte count, the single writer's text, what the host's string sink appends and the text the lane-group sink leaves —
+// driven lane by lane, sixteen lanes a line as the write kernel runs it, each lane with a staging buffer of its own, into a buffer of exactly the counted size — all
+// equal a naive string build.  A record beyond H2G_MAX_EDITS keeps its edits in a long-edit area, as the host's format calls meet it.
 // Built with -fsanitize=address,undefined by tests/test_sam_plan_cpu.py; it has no device code and never runs on a GPU.
 #include <stdint.h>
 #include <stdio.h>
@@ -140,11 +141,16 @@ static void run_case(const char* what, const Case& c) {
 	std::string names = "before" + c.name + "after";
 	std::vector<uint32_t> noffs = {0, 6, 6 + (uint32_t)c.name.size(), 11 + (uint32_t)c.name.size()};
 	// records: the line's, then (other mate's bytes) the opposite one; each ends where its edits end
-	auto record = [](uint32_t fw, uint32_t tidx, uint32_t toff, uint32_t len, uint32_t t5, uint32_t t3, int64_t score, const std::vector<Ed>& ed) {
-		std::vector<uint64_t> b((40 + 12 * ed.size() + 7) / 8);
+	// (a record beyond H2G_MAX_EDITS holds one entry, the offset of its edits in the long-edit area; the area starts with entries of other records)
+	const bool is_long = c.edits.size() > H2G_MAX_EDITS;
+	std::vector<h2g_edit> area(is_long ? 3 + c.edits.size() : 0);
+	auto record = [&area](uint32_t fw, uint32_t tidx, uint32_t toff, uint32_t len, uint32_t t5, uint32_t t3, int64_t score, const std::vector<Ed>& ed) {
+		const bool lng = ed.size() > H2G_MAX_EDITS;
+		std::vector<uint64_t> b((40 + 12 * (lng ? 1 : ed.size()) + 7) / 8);
 		h2g_alnres* r = reinterpret_cast<h2g_alnres*>(b.data());
 		r->fw = fw; r->tidx = tidx; r->toff = toff; r->len = len; r->trim5 = t5; r->trim3 = t3; r->nedits = (uint32_t)ed.size(); r->splicescore = 0; r->score = score;
 		h2g_edit* e = reinterpret_cast<h2g_edit*>(reinterpret_cast<uint8_t*>(b.data()) + 40);
+		if(lng) { e[0].pos = 3; e[0].snp = 0x4c4f4e47u; e = area.data() + 3; }
 		for(size_t j = 0; j < ed.size(); j++) { e[j].pos = ed[j].pos; e[j].chr = (uint8_t)ed[j].chr; e[j].qchr = 'A'; e[j].type = ed[j].type; e[j].pad = ed[j].pad; e[j].snp = ed[j].snp; }
 		return b;
 	};
@@ -174,7 +180,8 @@ static void run_case(const char* what, const Case& c) {
 	x.rec[m] = reinterpret_cast<const uint8_t*>(rec.data()); x.nrec[m] = rec.size() * 8; x.rec[m ^ 1] = reinterpret_cast<const uint8_t*>(orec.data()); x.nrec[m ^ 1] = orec.size() * 8;
 	x.aux = x_aux->data(); x.n_aux = aux.size(); x.refnames = x_ref->data(); x.refname_offs = roffs.data(); x.nrefs = (uint32_t)REFS.size();
 	x.rg = x_rg->data(); x.rg_len = (uint32_t)c.rg.size(); x.rna_strandness = c.strandness; x.nalts = c.nalts; x.first = 0; x.paired = 1;
-	CHECK(line_records_ok(x, L), "%s: the case's own records are refused", what);
+	x.long_edits = is_long ? area.data() : nullptr;
+	CHECK(line_records_ok(x, L) == !is_long, "%s: the case's own records are refused, or a record the kernels cannot read is let through", what);
 	const std::string want = naive(c, rd, q);
 	CountSink cs;
 	emit_line(x, L, cs);
@@ -184,6 +191,9 @@ static void run_case(const char* what, const Case& c) {
 		PtrSink ps = {out->data()};
 		emit_line(x, L, ps);
 		CHECK(ps.p == out->data() + want.size() && std::string(out->data(), out->size()) == want, "%s: the single writer wrote\n  %s  for\n  %s", what, std::string(out->data(), out->size()).c_str(), want.c_str());
+		std::string text = "the line before\n";
+		append_line(x, L, text);
+		CHECK(text == "the line before\n" + want, "%s: the string sink appended\n  %s  for\n  %s", what, text.c_str(), want.c_str());
 		std::vector<char>* gout = new std::vector<char>(want.size(), (char)0x7f);
 		for(uint32_t lane = 0; lane < NL; lane++) {
 			std::vector<char>* stage = new std::vector<char>(STAGE, (char)0x7e);
@@ -230,6 +240,12 @@ int main() {
 	for(uint32_t t5 : {0u, 1u, 12u}) for(uint32_t t3 : {0u, 2u, 30u}) for(uint32_t ne : {0u, 1u, 32u}) for(int fw = 0; fw < 2; fw++) for(int ends = 0; ends < 2; ends++) {
 		Case c; c.rdlen = 101; c.trim5 = t5; c.trim3 = t3; c.fw = fw; c.flag = fw ? 0 : 16; c.edits = mismatches(ne, 101 - t5 - t3, ends);
 		snprintf(what, sizeof what, "trims %u / %u, %u mismatches, fw %d, ends %d", t5, t3, ne, fw, ends); run_case(what, c);
+	}
+	// a record beyond H2G_MAX_EDITS: its mismatches are read from the long-edit area
+	for(uint32_t ne : {33u, 40u, 97u}) for(int fw = 0; fw < 2; fw++) {
+		Case c; c.rdlen = 101; c.trim5 = 1; c.trim3 = 2; c.fw = fw; c.flag = fw ? 0 : 16; c.nalts = 2; c.edits = mismatches(ne, 98, true);
+		c.edits[5].snp = 1;
+		snprintf(what, sizeof what, "%u mismatches in the long-edit area, fw %d", ne, fw); run_case(what, c);
 	}
 	// POS, TLEN, NH, MAPQ, ZS, the opposite record
 	for(uint32_t toff : {0u, 0xffffffffu}) for(int64_t tlen : {(int64_t)0, (int64_t)1 << 62, -((int64_t)1 << 62), (int64_t)-1}) for(uint32_t nh : {0u, 9u, 10u, 128u}) for(int opp = 0; opp < 3; opp++) {

@@ -8,6 +8,8 @@ Two sources of record sets:
   * synthetic records built here (no reference binary needed): every kind of edit, trims, both strands, a record beyond MAX_EDITS, pairs of every class, and the
     options that reach the emitter's tables."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -355,3 +357,90 @@ def test_emitter_lane_by_lane_under_sanitizers(tmp_path):
                     os.path.join(root, "tests", "samtext", "line_check.cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 failures" in r.stdout and int(r.stdout.split()[0]) > 2000, r.stdout + r.stderr
+
+
+# ---- the formatter's bytes, pinned -----------------------------------------------------------------------------------------------------------
+# Since the format calls write through the emitter, PlanCheckLib compares the emitter with itself.  What the formatter wrote before that change is kept as SHA-256
+# digests in tests/golden/sam_text_digests.json: per case, every h2g_sam_format_* call (slot, dense and compact layouts) with a digest of everything it reads, of its
+# text and of the handle's summary after it (sam_plan_util.format_inputs / PlanCheckLib._format).  Written by `PYTHONPATH=. python tests/test_sam_plan_cpu.py` at the
+# commit the file names; a change that is meant to alter a line's bytes writes it again and says so.
+DIGEST_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sam_text_digests.json")
+
+
+def _format_unpaired_sets(base, snps, opts):
+    reads, names, res, aln, led = _unpaired_case(base, 9100 + snps, snps)
+    quals = np.random.default_rng(5).integers(33, 74, size=sum(len(r) for r in reads)).astype(np.uint8)
+    for q in (None, quals):
+        SL.format_unpaired(SL.load_sam_lib(), base, reads, names, res, aln, quals=q, options=list(opts), long_edits=led)
+
+
+def _format_paired_sets(base, snps, opts):
+    m1, m2, n1, n2, res, a1, a2 = _paired_case(base, 9200 + snps, snps)
+    rng = np.random.default_rng(6)
+    quals = [rng.integers(33, 74, size=sum(len(r) for r in m)).astype(np.uint8) for m in (m1, m2)]
+    for q in (None, quals):
+        SL.format_paired(SL.load_sam_lib(), base, m1, m2, n1, n2, res, a1, a2, 1 if "-k" in opts else 5, options=[o for o in opts if o not in ("-k", "1")], quals=q)
+
+
+def _digest_cases():
+    """id -> run(index): every parametrization of the two synthetic tests above, with and without qualities, and every record set test_long_edits_cpu formats (its
+    tests themselves, whatever their skip marks say: without oracle/_ref they fail here)"""
+    cases = {}
+    for index, snps in (("g1_index", 0), ("g1s_index", 3)):
+        for k, opts in enumerate(OPTION_SETS):
+            cases["unpaired-%s-opts%d" % (index, k)] = (lambda ix, index=index, snps=snps, opts=opts: _format_unpaired_sets(ix(index), snps, opts))
+        for k, opts in enumerate(OPTION_SETS + [("-k", "1")]):
+            cases["paired-%s-opts%d" % (index, k)] = (lambda ix, index=index, snps=snps, opts=opts: _format_paired_sets(ix(index), snps, opts))
+    beyond = _TLE.test_records_beyond_32_edits_equal_the_reference
+    for mark in beyond.pytestmark:
+        if mark.name == "parametrize":
+            for case in mark.args[1]:
+                cases["long-edits-seed%d" % case["seed"]] = (lambda ix, case=case: beyond(case))
+    cases["long-edits-N-run"] = lambda ix: _TLE.test_reads_across_a_50_base_N_run_equal_the_reference()
+    return cases
+
+
+DIGEST_CASES = _digest_cases()
+
+
+def text_digests(case, index):
+    """the digests of every format call of a case; index: the name of an index fixture -> its basename"""
+    PU.DIGESTS = got = []
+    try:
+        DIGEST_CASES[case](index)
+    finally:
+        PU.DIGESTS = None
+    return got
+
+
+@pytest.mark.parametrize("case", sorted(DIGEST_CASES))
+def test_text_equals_the_recorded_digests(request, case):
+    with open(DIGEST_FILE) as f:
+        want = json.load(f)["cases"]
+    assert sorted(want) == sorted(DIGEST_CASES), "the recorded cases are not the cases of this module"
+    got = text_digests(case, request.getfixturevalue)
+    assert got and [(g["call"], g["rc"], g["inputs"]) for g in got] == [(w["call"], w["rc"], w["inputs"]) for w in want[case]], "inputs changed: the case no longer formats what was recorded"
+    for g, w in zip(got, want[case]):
+        assert g["text"] == w["text"], "formatter regression: %s of %s writes other bytes than recorded" % (g["call"], case)
+        assert g["summary"] == w["summary"], "formatter regression: the summary after %s of %s differs from the recorded one" % (g["call"], case)
+
+
+if __name__ == "__main__":
+    import gzip
+    import subprocess
+    import tempfile
+    real = SL.load_sam_lib
+    SL.load_sam_lib = lambda path=None: PU.PlanCheckLib(real(path))
+    tmp = tempfile.mkdtemp(prefix="h2gdigest")
+
+    def unpack(fixture):
+        stem = fixture[:-len("_index")]
+        for k in range(1, 9):
+            with gzip.open(os.path.join(os.path.dirname(DIGEST_FILE), "%s.%d.ht2.gz" % (stem, k)), "rb") as f, open(os.path.join(tmp, "%s.%d.ht2" % (stem, k)), "wb") as o:
+                o.write(f.read())
+        return os.path.join(tmp, stem)
+
+    commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=os.path.dirname(DIGEST_FILE), check=True, capture_output=True, text=True).stdout.strip()
+    with open(DIGEST_FILE, "w") as f:
+        json.dump({"formatter_commit": commit, "cases": {c: text_digests(c, unpack) for c in sorted(DIGEST_CASES)}}, f, indent=1)
+        f.write("\n")

@@ -5,9 +5,11 @@
       upload + copy-back (its wall time less its kernels) / kernels (HIP events; the write kernel alone as well);
   (c) h2g_align_pairs_fetch_compact + h2g_sam_text_paired_planned: plain pairs classified and planned on the device, the host planner (same thread counts) over the
       handed-on pairs only, merged on the device — its wall time, the planner + merge kernels, the host subset's time and share, the bytes uploaded, the share handed on.
-Medians of --repeats rounds into --out, with the write kernel's store rate against the bytes it writes and the planner's share of (b).  Needs a GPU.
+Medians of --repeats rounds into --out (for the host's format call the smallest and the largest round as well: their distance is the margin a comparison of two
+builds has to allow), with the write kernel's store rate against the bytes it writes and the planner's share of (b).  --legs a times (a) alone.  --key <name> keeps
+the result under that name beside the other names --out already holds (two builds of the library, H2G_LIB, side by side: one name per commit).  Needs a GPU.
 
-    python tools/sam_text_bench.py --index <ht2 base> --genome <fasta[.gz]> [--pairs 1000000] [--repeats 7] [--out profiles/sam_text.json]"""
+    python tools/sam_text_bench.py --index <ht2 base> --genome <fasta[.gz]> [--pairs 1000000] [--repeats 7] [--legs abc] [--key <name>] [--out profiles/sam_text.json]"""
 import argparse
 import ctypes as C
 import gzip
@@ -50,6 +52,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=1000000)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--threads", default="1,8,32")
+    ap.add_argument("--legs", default="abc")
+    ap.add_argument("--key", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sam_text.json"))
     a = ap.parse_args()
     n = a.pairs
@@ -149,22 +153,27 @@ def main():
 
     threads = [int(t) for t in a.threads.split(",")]
     ref_text = host(1)[1]
-    identical = device(1)[1] == ref_text                # warm-up of each, and the check that they write the same bytes
-    identical_planned = planned(1)[1] == ref_text
+    identical = device(1)[1] == ref_text if "b" in a.legs else None               # warm-up of each, and the check that they write the same bytes
+    identical_planned = planned(1)[1] == ref_text if "c" in a.legs else None
     rounds = {("host", t): [] for t in threads}
     rounds.update({("device", t): [] for t in threads})
     rounds.update({("planned", t): [] for t in threads})
     for _ in range(a.repeats):
         for t in threads:
             rounds[("host", t)].append(host(t)[0])
-            rounds[("device", t)].append(device(t)[0])
-            rounds[("planned", t)].append(planned(t)[0])
+            if "b" in a.legs:
+                rounds[("device", t)].append(device(t)[0])
+            if "c" in a.legs:
+                rounds[("planned", t)].append(planned(t)[0])
     med = lambda rows, k: float(np.median([r[k] for r in rows]))
-    out = {"pairs": n, "read_length": 101, "repeats": a.repeats, "identical_text": bool(identical), "identical_text_planned": bool(identical_planned),
+    out = {"pairs": n, "read_length": 101, "repeats": a.repeats, "identical_text": identical, "identical_text_planned": identical_planned,
            "text_bytes": rounds[("host", threads[0])][0]["bytes"], "host": {}, "device": {}, "planned": {}}
     for t in threads:
         hr, dr = rounds[("host", t)], rounds[("device", t)]
-        out["host"][str(t)] = {"fetch_ms": med(hr, "fetch") * 1e3, "format_ms": med(hr, "format") * 1e3, "total_ms": (med(hr, "fetch") + med(hr, "format")) * 1e3}
+        out["host"][str(t)] = {"fetch_ms": med(hr, "fetch") * 1e3, "format_ms": med(hr, "format") * 1e3, "total_ms": (med(hr, "fetch") + med(hr, "format")) * 1e3,
+                               "format_min_ms": min(r["format"] for r in hr) * 1e3, "format_max_ms": max(r["format"] for r in hr) * 1e3}
+        if "b" not in a.legs or "c" not in a.legs:
+            continue
         d = {k + "_ms": med(dr, k) * 1e3 for k in ("fetch", "plan", "text_call", "kernels", "write_kernel", "upload_copyback")}
         d["total_ms"] = d["fetch_ms"] + d["plan_ms"] + d["text_call_ms"]
         d["planner_share_of_plan_plus_text"] = d["plan_ms"] / (d["plan_ms"] + d["text_call_ms"])
@@ -182,6 +191,9 @@ def main():
         c["fastest"] = min(tot, key=tot.get)
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.key:
+        held = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        out = dict({k: v for k, v in held.items() if isinstance(v, dict) and "pairs" in v}, **{a.key: out})
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
