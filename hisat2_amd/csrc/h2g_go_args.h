@@ -3,6 +3,7 @@
 // as byte pools with strides, the results as fixed-layout records.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "h2g_align.h"
 #include "h2g_graph.h"
 #include "h2g_fast.h"
@@ -36,6 +37,98 @@ __device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long 
 	if((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
 }
 
+// The scheduler's state of one workgroup, in LDS: NQ rings of 16-bit slot ids over SLOTS slots, ring 0 the free slots.  A slot id is in one ring or in one lane.
+// Waves reserve positions with one aggregated add on `tail`, take them with a CAS on `head`, and wait on the sentinel for a reserved position to be written.
+// Nothing crosses the workgroup: relaxed LDS atomics here, the workgroup-scope fences around the slots' data are the callers'.
+template <int NQ, int SLOTS>
+struct SlotRings {
+	static_assert(NQ <= 64, "the census is one lane per ring");
+	static_assert(SLOTS > 0 && (SLOTS & (SLOTS - 1)) == 0, "positions wrap with a mask");
+	static_assert(SLOTS <= 0xffff, "a slot id is 16 bits, 0xffff the sentinel");
+	static constexpr uint16_t EMPTY = 0xffffu;   // a position that holds no slot id (yet)
+	uint32_t head[NQ], tail[NQ];
+	uint16_t ring[NQ][SLOTS];
+
+	// every thread of the workgroup: all rings empty, every slot free; ends behind a barrier
+	__device__ __forceinline__ void init() {
+		for(uint32_t k = threadIdx.x; k < (uint32_t)NQ * SLOTS; k += blockDim.x) (&ring[0][0])[k] = EMPTY;
+		if(threadIdx.x < (uint32_t)NQ) { head[threadIdx.x] = 0; tail[threadIdx.x] = 0; }
+		__syncthreads();
+		for(uint32_t k = threadIdx.x; k < (uint32_t)SLOTS; k += blockDim.x) ring[0][k] = (uint16_t)k;
+		if(threadIdx.x == 0) tail[0] = SLOTS;
+		__syncthreads();
+	}
+	// the census: slots in ring `lane` (0 for the lanes behind the last ring)
+	__device__ __forceinline__ uint32_t count(int lane) const {
+		return lane < NQ ? __atomic_load_n(&tail[lane], __ATOMIC_RELAXED) - __atomic_load_n(&head[lane], __ATOMIC_RELAXED) : 0u;
+	}
+	// pushes this lane's slot (if `valid`) into ring q; lanes of the wave may push to different rings
+	__device__ __forceinline__ void push(bool valid, uint32_t q, uint32_t slot, int lane) {
+		unsigned long long todo = __ballot(valid);
+		while(todo) {                                                  // one aggregated reservation per ring present in the wave
+			const int first = __ffsll((long long)todo) - 1;
+			const uint32_t k = (uint32_t)__shfl((int)q, first);
+			const unsigned long long m = __ballot(valid && q == k);
+			uint32_t base = 0;
+			if(lane == first) base = atomicAdd(&tail[k], (uint32_t)__popcll(m));
+			base = (uint32_t)__shfl((int)base, first);
+			if(valid && q == k) {
+				const uint32_t pos = (base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (SLOTS - 1);
+				__atomic_store_n(&ring[k][pos], (uint16_t)slot, __ATOMIC_RELAXED);
+			}
+			todo &= ~m;
+		}
+	}
+	// pops one slot of ring q for each lane with `want` set, in lane order, as far as the ring holds any: `got` says whether THIS lane has one (then in `slot`).
+	// Returns the count popped (wave-uniform).
+	__device__ __forceinline__ uint32_t pop(uint32_t q, int lane, bool want, uint32_t* slot, bool* got) {
+		const unsigned long long wm = __ballot(want);
+		*got = false;
+		if(wm == 0) return 0;
+		return take(q, lane, want, (uint32_t)__popcll(wm), (uint32_t)__popcll(wm & ((1ull << lane) - 1ull)), slot, got);
+	}
+	// the same for the lanes [from, 64) of a full wave (`from` wave-uniform): what a ballot would count is known from the lane index
+	__device__ __forceinline__ uint32_t pop_from(uint32_t q, int lane, uint32_t from, uint32_t* slot, bool* got) {
+		return take(q, lane, (uint32_t)lane >= from, 64u - from, (uint32_t)lane - from, slot, got);
+	}
+	// the protocol behind both: lane 0 reserves up to `nwant` positions, the wanting lane of rank r < that count takes position r
+	__device__ __forceinline__ uint32_t take(uint32_t q, int lane, bool want, uint32_t nwant, uint32_t r, uint32_t* slot, bool* got) {
+		uint32_t n = 0, h = 0;
+		if(lane == 0) {
+			for(;;) {
+				h = __atomic_load_n(&head[q], __ATOMIC_RELAXED);
+				const uint32_t t = __atomic_load_n(&tail[q], __ATOMIC_RELAXED);
+				n = t - h;
+				if(n == 0) break;
+				if(n > nwant) n = nwant;
+				if(atomicCAS(&head[q], h, h + n) == h) break;
+			}
+		}
+		n = (uint32_t)__shfl((int)n, 0); h = (uint32_t)__shfl((int)h, 0);
+		*got = want && r < n;
+		if(*got) {
+			const uint32_t pos = (h + r) & (SLOTS - 1);
+			uint16_t v;
+			while((v = __atomic_load_n(&ring[q][pos], __ATOMIC_RELAXED)) == EMPTY) __builtin_amdgcn_s_sleep(1);   // reserved, being written
+			__atomic_store_n(&ring[q][pos], EMPTY, __ATOMIC_RELAXED);
+			*slot = v;
+		}
+		return n;
+	}
+};
+
+// Launches kernel K with `lds` bytes of dynamic LDS.  More than 64 KB of it is an opt-in per kernel and per DEVICE (a process may drive several:
+// hisat2-align-amd --gpus N), made once: the flag is a mask over device ids, one per kernel.
+template <auto K, class... Args>
+static int launch_large_lds(unsigned grid, unsigned threads, unsigned lds, hipStream_t st, const Args&... args) {
+	static std::atomic<unsigned long long> lds_ok{0};
+	int dev = 0; (void)hipGetDevice(&dev);
+	const unsigned long long bit = 1ull << (dev & 63);
+	if(!(lds_ok.load(std::memory_order_relaxed) & bit)) { if(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit, std::memory_order_relaxed); }
+	hipLaunchKernelGGL(K, dim3(grid), dim3(threads), lds, st, args...);
+	return (int)hipGetLastError();
+}
+
 struct GoArgs {
 	h2g::DGfm g; h2g::DRef ref; h2g::DLocalSet ls; h2g::DAlts alts; h2g::DSpliceDB ssdb;
 	h2g::DReads rd1, rd2;                 // rd2 only when paired
@@ -59,10 +152,19 @@ struct GoArgs {
 };
 #define H2G_PK_LANE_WORDS_HOST (H2G_PK_WORDS + H2G_PK_WORDS / 2)
 
-#define H2G_GO_DECLARE(NAME) \
-	extern "C" size_t h2g_go_ws_bytes_##NAME(); extern "C" size_t h2g_go_gws_bytes_##NAME(); extern "C" int h2g_go_waves_##NAME(); \
-	extern "C" size_t h2g_go_slot_off_##NAME(); extern "C" size_t h2g_go_gsl_off_##NAME(); extern "C" void h2g_go_geometry_##NAME(uint32_t*); extern "C" size_t h2g_go_sw_bytes_##NAME(uint32_t, int); \
-	extern "C" void h2g_go_caps_##NAME(uint32_t*); extern "C" int h2g_go_launch_##NAME(const GoArgs*, const h2g::DExonTbl*, const h2g::XlPairs*, unsigned, hipStream_t);
+// What h2g_kernels.hip knows of one machine unit (a translation unit of h2g_go_kernels.h with its own AL_MAX_* capacities): the layout of a slot,
+// the launch geometry, the capacities, and the two things that are code
+struct GoUnitDesc {
+	size_t ws_bytes, slot_off, gsl_off;   // per read in flight (slot): AlignWS, then GoSlot at slot_off, then GraphSlot at gsl_off (graph units)
+	size_t gws_bytes;                     // GraphWS per lane; 0 in the linear units
+	int waves;                            // waves per SIMD the kernel is bounded to
+	uint32_t threads, slots;              // threads per workgroup, reads in flight per workgroup
+	uint32_t lds_ring_bytes, lds_pack_bytes;   // LDS per workgroup: the rings + one packed-read region per mate
+	uint32_t caps[5];                     // AL_MAX_GHITS, _RESULTS, _SEARCHED, _DEPTH, _PARTIAL
+	size_t (*sw_bytes)(uint32_t maxlen, int wide);   // Smith-Waterman scratch per lane (SwLaneState holds H2G_GHIT_EDITS of THIS unit)
+	int (*launch)(const GoArgs*, const h2g::DExonTbl*, const h2g::XlPairs*, unsigned grid, hipStream_t);
+};
+#define H2G_GO_DECLARE(NAME) extern "C" const GoUnitDesc* h2g_go_unit_##NAME();
 H2G_GO_DECLARE(linear) H2G_GO_DECLARE(graph) H2G_GO_DECLARE(linear_big) H2G_GO_DECLARE(graph_big)
 H2G_GO_DECLARE(linear_spl) H2G_GO_DECLARE(linear_spl_big) H2G_GO_DECLARE(graph_spl) H2G_GO_DECLARE(graph_spl_big)   // spliced alignment (linear indexes): with the splice-site database joins
 H2G_GO_DECLARE(linear_xl) H2G_GO_DECLARE(graph_xl) H2G_GO_DECLARE(linear_spl_xl) H2G_GO_DECLARE(graph_spl_xl)       // -k / --max-seeds beyond the large workspace (h2g_go_xl.h)
@@ -97,15 +199,15 @@ struct FastArgs {
 	h2g::DSpliceDB ssdb;
 	uint32_t rdid_base;
 };
-extern "C" int h2g_go_fast_launch(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" int h2g_go_fast_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" int h2g_go_fast_am_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" int h2g_go_fast_graph_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" void h2g_go_fast_geometry(uint32_t* g);   // [0] threads per workgroup [1] LDS bytes per workgroup [2] slots per workgroup [3] bytes per slot
-extern "C" int h2g_go_fast_am_launch(const FastArgs*, unsigned grid, hipStream_t);         // h2g_k_go_fast_am.hip: alignMate in the pass (FG_ALIGN_MATE = 1)
-extern "C" void h2g_go_fast_am_geometry(uint32_t* g);
-extern "C" int h2g_go_fast_graph_launch(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" void h2g_go_fast_graph_geometry(uint32_t* g);   // ... [4] bytes of GraphWS per lane
-extern "C" int h2g_go_fast_spl_launch(const FastArgs*, unsigned grid, hipStream_t);        // h2g_k_go_fast_spl.hip: the pass under the spliced rules (FG_SPLICED = 1)
-extern "C" int h2g_go_fast_spl_launch_drain(const FastArgs*, unsigned grid, hipStream_t);
-extern "C" void h2g_go_fast_spl_geometry(uint32_t* g);
+// What h2g_kernels.hip knows of one build of the pass (h2g_k_go_fast.hip and the units that compile it again); `a` of both launchers is the argument block in DEVICE memory
+struct FastUnitDesc {
+	int (*launch)(const FastArgs* a, unsigned grid, hipStream_t);
+	int (*launch_drain)(const FastArgs* a, unsigned grid, hipStream_t);
+	uint32_t threads, lds_bytes;          // per workgroup
+	uint32_t slots, slot_bytes;           // reads in flight per workgroup, bytes of one
+	uint32_t gws_bytes;                   // GraphWS per lane in global memory; 0 where the build keeps it private (and in the linear builds)
+};
+extern "C" const FastUnitDesc* h2g_go_fast_unit();
+extern "C" const FastUnitDesc* h2g_go_fast_am_unit();      // h2g_k_go_fast_am.hip: alignMate in the pass (FG_ALIGN_MATE = 1)
+extern "C" const FastUnitDesc* h2g_go_fast_graph_unit();
+extern "C" const FastUnitDesc* h2g_go_fast_spl_unit();     // h2g_k_go_fast_spl.hip: the pass under the spliced rules (FG_SPLICED = 1)

@@ -11,10 +11,9 @@
 //
 // Compiled once per translation unit with that unit's capacities (-DAL_MAX_*): h2g_k_go_linear.hip, h2g_k_go_graph.hip and
 // their *_big.hip siblings (large workspaces: the second pass over reads whose lists overflowed, and option sets beyond the
-// default capacities) and *_xl.hip siblings (h2g_go_xl.h: -k / --max-seeds beyond the large workspace).  h2g_kernels.hip sees only GoArgs and the extern "C" launchers of H2G_GO_UNIT.
+// default capacities) and *_xl.hip siblings (h2g_go_xl.h: -k / --max-seeds beyond the large workspace).  h2g_kernels.hip sees only GoArgs and the GoUnitDesc of H2G_GO_UNIT.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include "h2g_core.h"
 #include "h2g_align.h"
 #include "h2g_go_args.h"
@@ -29,7 +28,6 @@ using namespace h2g;
 #endif
 #define H2G_GO_NQ ((int)SITE_COUNT)   // one ring per request site of the machine (h2g_machine.h H2G_MACH_SITES); ring 0 holds the free slots
 #define H2G_PK_LANE_WORDS (H2G_PK_WORDS + H2G_PK_WORDS / 2)
-#define H2G_RING_EMPTY 0xffffu
 
 // per-read state of a slot beside its AlignWS: the machine registers between two primitives, and the packed read(s)
 struct GoSlot {
@@ -69,77 +67,8 @@ __device__ __forceinline__ bool pack_read(const DReads& rd, uint32_t i, uint32_t
 	return true;
 }
 
-static_assert(H2G_GO_NQ <= 64, "the ring census is one lane per ring");
-struct GoLds {
-	uint32_t head[H2G_GO_NQ], tail[H2G_GO_NQ];
-	uint16_t ring[H2G_GO_NQ][H2G_GO_SLOTS];
-};
+typedef SlotRings<H2G_GO_NQ, H2G_GO_SLOTS> GoLds;
 
-// pushes this lane's slot (if `valid`) into ring q; lanes of the wave may push to different rings
-__device__ __forceinline__ void ring_push(GoLds* Q, bool valid, uint32_t q, uint32_t slot, int lane) {
-	unsigned long long todo = __ballot(valid);
-	while(todo) {                                                  // one aggregated reservation per ring present in the wave
-		const int first = __ffsll((long long)todo) - 1;
-		const uint32_t k = (uint32_t)__shfl((int)q, first);
-		const unsigned long long m = __ballot(valid && q == k);
-		uint32_t base = 0;
-		if(lane == first) base = atomicAdd(&Q->tail[k], (uint32_t)__popcll(m));
-		base = (uint32_t)__shfl((int)base, first);
-		if(valid && q == k) {
-			const uint32_t pos = (base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (H2G_GO_SLOTS - 1);
-			__atomic_store_n(&Q->ring[k][pos], (uint16_t)slot, __ATOMIC_RELAXED);
-		}
-		todo &= ~m;
-	}
-}
-
-// pops up to 64 slots of ring q for the wave: returns the count (wave-uniform); lane i < count gets its slot
-__device__ __forceinline__ uint32_t ring_pop(GoLds* Q, uint32_t q, int lane, uint32_t* slot) {
-	uint32_t n = 0, h = 0;
-	if(lane == 0) {
-		for(;;) {
-			h = __atomic_load_n(&Q->head[q], __ATOMIC_RELAXED);
-			const uint32_t t = __atomic_load_n(&Q->tail[q], __ATOMIC_RELAXED);
-			n = t - h;
-			if(n == 0) break;
-			if(n > 64) n = 64;
-			if(atomicCAS(&Q->head[q], h, h + n) == h) break;
-		}
-	}
-	n = (uint32_t)__shfl((int)n, 0); h = (uint32_t)__shfl((int)h, 0);
-	if((uint32_t)lane < n) {
-		const uint32_t pos = (h + (uint32_t)lane) & (H2G_GO_SLOTS - 1);
-		uint16_t v;
-		while((v = __atomic_load_n(&Q->ring[q][pos], __ATOMIC_RELAXED)) == H2G_RING_EMPTY) __builtin_amdgcn_s_sleep(1);   // reserved, being written
-		__atomic_store_n(&Q->ring[q][pos], (uint16_t)H2G_RING_EMPTY, __ATOMIC_RELAXED);
-		*slot = v;
-	}
-	return n;
-}
-
-// as ring_pop, for the lanes [at, at + room) of the wave: tops a thin trip up from another ring of the same primitive.  Returns the count popped.
-__device__ __forceinline__ uint32_t ring_pop_at(GoLds* Q, uint32_t q, int lane, uint32_t at, uint32_t room, uint32_t* slot) {
-	uint32_t n = 0, h = 0;
-	if(lane == 0) {
-		for(;;) {
-			h = __atomic_load_n(&Q->head[q], __ATOMIC_RELAXED);
-			const uint32_t t = __atomic_load_n(&Q->tail[q], __ATOMIC_RELAXED);
-			n = t - h;
-			if(n == 0) break;
-			if(n > room) n = room;
-			if(atomicCAS(&Q->head[q], h, h + n) == h) break;
-		}
-	}
-	n = (uint32_t)__shfl((int)n, 0); h = (uint32_t)__shfl((int)h, 0);
-	if((uint32_t)lane >= at && (uint32_t)lane < at + n) {
-		const uint32_t pos = (h + (uint32_t)lane - at) & (H2G_GO_SLOTS - 1);
-		uint16_t v;
-		while((v = __atomic_load_n(&Q->ring[q][pos], __ATOMIC_RELAXED)) == H2G_RING_EMPTY) __builtin_amdgcn_s_sleep(1);
-		__atomic_store_n(&Q->ring[q][pos], (uint16_t)H2G_RING_EMPTY, __ATOMIC_RELAXED);
-		*slot = v;
-	}
-	return n;
-}
 // the rings (request sites) that wait for primitive `op`, as a bit set over ring ids
 __device__ __forceinline__ unsigned long long mach_rings_of_op(uint32_t op) {
 	unsigned long long m = 0;
@@ -179,12 +108,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 	const int lane = (int)(threadIdx.x & 63);
 	const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
 	const bool paired = A.paired != 0;
-	for(uint32_t k = threadIdx.x; k < (uint32_t)H2G_GO_NQ * H2G_GO_SLOTS; k += blockDim.x) (&Q->ring[0][0])[k] = H2G_RING_EMPTY;
-	if(threadIdx.x < (uint32_t)H2G_GO_NQ) { Q->head[threadIdx.x] = 0; Q->tail[threadIdx.x] = 0; }
-	__syncthreads();
-	for(uint32_t k = threadIdx.x; k < H2G_GO_SLOTS; k += blockDim.x) Q->ring[0][k] = (uint16_t)k;   // every slot starts free
-	if(threadIdx.x == 0) Q->tail[0] = H2G_GO_SLOTS;
-	__syncthreads();
+	Q->init();                                                // every slot starts free
 	AlnCtx C; C.g = &A.g; C.ref = &A.ref; C.ls = &A.ls; C.P = &A.P;
 	C.sw = A.sw_base ? A.sw_base + tid * A.sw_stride : nullptr;
 	// combineWith temp_scores: one block per wave, lane-interleaved
@@ -225,8 +149,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 #endif
 	for(;;) {
 		// ---- choose: the primitive with the longest ring; free slots are refilled when reads remain and nothing is long
-		uint32_t cnt = 0;
-		if(lane < H2G_GO_NQ) cnt = __atomic_load_n(&Q->tail[lane], __ATOMIC_RELAXED) - __atomic_load_n(&Q->head[lane], __ATOMIC_RELAXED);
+		const uint32_t cnt = Q->count(lane);
 		const uint32_t nfree = (uint32_t)__shfl((int)cnt, 0);
 		uint32_t bestc = (lane >= 1 && lane < H2G_GO_NQ) ? cnt : 0, bestq = (uint32_t)lane;
 		for(int o = 32; o > 0; o >>= 1) {
@@ -236,11 +159,12 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 		bestc = (uint32_t)__shfl((int)bestc, 0); bestq = (uint32_t)__shfl((int)bestq, 0);
 		const bool fetch = more && nfree > 0 && (bestc < 64 || nfree >= H2G_GO_SLOTS / 4);
 		bool have = false;          // this lane carries a slot in this trip
+		bool popped;                // ... out of the latest pop.  Every pop below fills the wave from lane 0 upwards: after n slots the trip's lanes are [0, n)
 		uint32_t slot = 0;
 		GoSlot* gs = nullptr;
 		if(fetch) {
 			// ---- new reads into free slots
-			const uint32_t n = ring_pop(Q, 0, lane, &slot);
+			const uint32_t n = Q->pop_from(0, lane, 0, &slot, &popped);
 			if(n == 0) continue;
 #ifdef H2G_GO_PROF
 			trip_op = 0;
@@ -249,8 +173,8 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 			if(lane == 0) base = atomicAdd(A.work, n);
 			base = (uint32_t)__shfl((int)base, 0);
 			if(base + n >= total) more = false;
-			const bool got = (uint32_t)lane < n && base + (uint32_t)lane < total;
-			ring_push(Q, (uint32_t)lane < n && !got, 0, slot, lane);      // slots without a read go back
+			const bool got = popped && base + (uint32_t)lane < total;
+			Q->push(popped && !got, 0, slot, lane);    // slots without a read go back
 			if(got) {
 				have = true;
 				const uint32_t i = A.list ? A.list[base + (uint32_t)lane] : base + (uint32_t)lane;
@@ -281,7 +205,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 				continue;
 			}
 			const uint32_t op = mach_site_op(bestq);      // the ring is a request site: one primitive, one resume pc
-			uint32_t n = ring_pop(Q, bestq, lane, &slot);
+			uint32_t n = Q->pop_from(bestq, lane, 0, &slot, &popped);
 			if(n == 0) continue;
 			// A thin trip (the machine behind a fast pass works on the hard reads only: a few hundred slots over ~34 rings) is topped up from the
 			// other request sites of the SAME primitive: the primitive still runs at one code site for every lane, the control flow behind it
@@ -291,7 +215,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 				while(cand && n < 64) {
 					const uint32_t q2 = (uint32_t)__ffsll((long long)cand) - 1u;
 					cand &= cand - 1ull;
-					n += ring_pop_at(Q, q2, lane, n, 64u - n, &slot);
+					n += Q->pop_from(q2, lane, n, &slot, &popped);      // the lanes [n, 64) take what ring q2 holds
 				}
 			}
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -335,7 +259,7 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 			}
 		}
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		ring_push(Q, have, nextq, slot, lane);
+		Q->push(have, nextq, slot, lane);
 #ifdef H2G_GO_PROF
 		tp1 = __builtin_readcyclecounter(); prof[1] += tp1 - tp0; prof_ctl[trip_op] += tp1 - tp0; tp0 = tp1;
 #endif
@@ -351,22 +275,22 @@ __global__ __launch_bounds__(H2G_GO_THREADS, WAVES_PER_SIMD) void k_go(GoArgs A 
 	wave_add(A.counters + H2G_CNT_OVERFLOW, novf);
 }
 
-// the extern "C" face of one translation unit (declared in h2g_go_args.h)
+// what h2g_kernels.hip sees of one translation unit: its GoUnitDesc (h2g_go_args.h)
 #define H2G_GO_ALIGN256(X) (((X) + 255) & ~(size_t)255)
-#define H2G_GO_UNIT(NAME, GRAPH, WAVES, UNIT) \
-	extern "C" size_t h2g_go_ws_bytes_##NAME() { return H2G_GO_ALIGN256(sizeof(AlignWS)) + H2G_GO_ALIGN256(sizeof(GoSlot)) + ((GRAPH) ? H2G_GO_ALIGN256(sizeof(GraphSlot)) : 0); } \
-	extern "C" size_t h2g_go_slot_off_##NAME() { return H2G_GO_ALIGN256(sizeof(AlignWS)); } \
-	extern "C" size_t h2g_go_gsl_off_##NAME() { return H2G_GO_ALIGN256(sizeof(AlignWS)) + H2G_GO_ALIGN256(sizeof(GoSlot)); } \
-	extern "C" size_t h2g_go_gws_bytes_##NAME() { return (GRAPH) ? H2G_GO_ALIGN256(sizeof(GraphWS)) : 0; } \
-	extern "C" size_t h2g_go_sw_bytes_##NAME(uint32_t maxlen, int wide) { return sw_scratch_bytes(maxlen, wide != 0); }   /* SwLaneState holds H2G_GHIT_EDITS of THIS unit */ \
-	extern "C" int h2g_go_waves_##NAME() { return (WAVES); } \
-	extern "C" void h2g_go_geometry_##NAME(uint32_t* g) { g[0] = H2G_GO_THREADS; g[1] = H2G_GO_SLOTS; \
-		g[2] = (uint32_t)((sizeof(GoLds) + 3) / 4 * 4); g[3] = H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; /* LDS: rings + one pack region per mate */ } \
-	extern "C" void h2g_go_caps_##NAME(uint32_t* c) { c[0] = AL_MAX_GHITS; c[1] = AL_MAX_RESULTS; c[2] = AL_MAX_SEARCHED; c[3] = AL_MAX_DEPTH; c[4] = AL_MAX_PARTIAL; } \
-	extern "C" int h2g_go_launch_##NAME(const GoArgs* a, const DExonTbl* x, const XlPairs* xp, unsigned grid, hipStream_t st) { \
-		const unsigned lds = (unsigned)((sizeof(GoLds) + 3) / 4 * 4) + (a->paired ? 2u : 1u) * H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u; \
-		static std::atomic<unsigned long long> lds_ok{0};   /* more than 64 KB of dynamic LDS is an opt-in, per device: a mask over device ids */ \
-		int dev_ = 0; (void)hipGetDevice(&dev_); const unsigned long long bit_ = 1ull << (dev_ & 63); \
-		if(!(lds_ok.load(std::memory_order_relaxed) & bit_)) { if(hipFuncSetAttribute((const void*)k_go<GRAPH, WAVES, UNIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit_, std::memory_order_relaxed); } \
-		(void)x; (void)xp; hipLaunchKernelGGL((k_go<GRAPH, WAVES, UNIT>), dim3(grid), dim3(H2G_GO_THREADS), lds, st, *a H2G_GO_EXONS_ARG(x) H2G_GO_XL_ARG(xp)); \
-		return (int)hipGetLastError(); }
+#define H2G_GO_LDS_RINGS ((uint32_t)((sizeof(GoLds) + 3) / 4 * 4))
+#define H2G_GO_LDS_PACK  (H2G_PK_LANE_WORDS * H2G_GO_THREADS * 4u)
+template <bool GRAPH, int WAVES, int UNIT>
+static int go_launch(const GoArgs* a, const DExonTbl* x, const XlPairs* xp, unsigned grid, hipStream_t st) {
+	(void)x; (void)xp;
+	return launch_large_lds<k_go<GRAPH, WAVES, UNIT>>(grid, H2G_GO_THREADS, H2G_GO_LDS_RINGS + (a->paired ? 2u : 1u) * H2G_GO_LDS_PACK, st, *a H2G_GO_EXONS_ARG(x) H2G_GO_XL_ARG(xp));
+}
+static size_t go_sw_bytes(uint32_t maxlen, int wide) { return sw_scratch_bytes(maxlen, wide != 0); }
+template <bool GRAPH, int WAVES, int UNIT>
+static const GoUnitDesc* go_unit_desc() {
+	constexpr size_t ws = H2G_GO_ALIGN256(sizeof(AlignWS)), gs = H2G_GO_ALIGN256(sizeof(GoSlot));
+	static const GoUnitDesc d = {ws + gs + (GRAPH ? H2G_GO_ALIGN256(sizeof(GraphSlot)) : 0), ws, ws + gs, GRAPH ? H2G_GO_ALIGN256(sizeof(GraphWS)) : 0,
+		WAVES, H2G_GO_THREADS, H2G_GO_SLOTS, H2G_GO_LDS_RINGS, H2G_GO_LDS_PACK,
+		{AL_MAX_GHITS, AL_MAX_RESULTS, AL_MAX_SEARCHED, AL_MAX_DEPTH, AL_MAX_PARTIAL}, go_sw_bytes, go_launch<GRAPH, WAVES, UNIT>};
+	return &d;
+}
+#define H2G_GO_UNIT(NAME, GRAPH, WAVES, UNIT) extern "C" const GoUnitDesc* h2g_go_unit_##NAME() { return go_unit_desc<GRAPH, WAVES, UNIT>(); }

@@ -7,7 +7,6 @@
 // code site, let every lane run its read's control flow on registers / LDS up to the next request, store the state and push the slot to
 // the queue of what it asked for.  Reads that leave the fast path go to the general machine's list.
 // h2g_k_go_fast_graph.hip compiles this file once more with FG_GRAPH = 1 (graph indexes: h2g_fast.h) under its own symbol names.
-#include <atomic>
 #include "h2g_go_args.h"
 #include "h2g_fast_prof.h"
 
@@ -15,13 +14,11 @@ using namespace h2g;
 
 #ifndef FG_KERNEL
 #define FG_KERNEL   k_go_fast
-#define FG_LAUNCH   h2g_go_fast_launch
-#define FG_GEOMETRY h2g_go_fast_geometry
+#define FG_UNIT     h2g_go_fast_unit
 #endif
 #define FG_CAT_(a, b) a##b
 #define FG_CAT(a, b) FG_CAT_(a, b)
 #define FG_KERNEL_DRAIN FG_CAT(FG_KERNEL, _drain)      // the same loop over the reads a launch of FG_KERNEL left in flight (FastArgs::adopt_list)
-#define FG_LAUNCH_DRAIN FG_CAT(FG_LAUNCH, _drain)
 
 #ifndef H2G_FAST_THREADS
 #define H2G_FAST_THREADS 512
@@ -40,61 +37,13 @@ using namespace h2g;
 #define FG_STAGE_WORDS (FW_HOT + 2 * H2G_PK_WORDS)                     // staged in LDS per lane: hot words + packed reads
 #define FG_SLOT_WORDS  (((FS_WORDS + FW_HOT + 2 * H2G_PK_WORDS + FW_COLD) + 3) & ~3)   // 16-byte multiple
 #define FG_NQ ((int)FQ_COUNT)
-#define FG_RING_EMPTY 0xffffu
-static_assert(FG_NQ <= 64, "the queue census is one lane per queue");
 static_assert(FS_WORDS % 4 == 0, "16-byte loads of the state");
 
-struct FastLds {
-	uint32_t head[FG_NQ], tail[FG_NQ];
+// one queue of slot ids per request site, queue 0 the free slots (SlotRings, h2g_go_args.h)
+struct FastLds : SlotRings<FG_NQ, H2G_FAST_SLOTS> {
 	uint32_t quit;                      // the workgroup hands its reads in flight on (FastArgs::orphan_T)
 	uint32_t parked;                    // slots that hold a read listed for the drain launch already (FastArgs::mate_handover): not free, not in flight
-	uint16_t ring[FG_NQ][H2G_FAST_SLOTS];
 };
-
-__device__ __forceinline__ void fq_push(FastLds* Q, bool valid, uint32_t q, uint32_t slot, int lane) {
-	unsigned long long todo = __ballot(valid);
-	while(todo) {                                                  // one aggregated reservation per queue present in the wave
-		const int first = __ffsll((long long)todo) - 1;
-		const uint32_t k = (uint32_t)__shfl((int)q, first);
-		const unsigned long long m = __ballot(valid && q == k);
-		uint32_t base = 0;
-		if(lane == first) base = atomicAdd(&Q->tail[k], (uint32_t)__popcll(m));
-		base = (uint32_t)__shfl((int)base, first);
-		if(valid && q == k) {
-			const uint32_t pos = (base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (H2G_FAST_SLOTS - 1);
-			__atomic_store_n(&Q->ring[k][pos], (uint16_t)slot, __ATOMIC_RELAXED);
-		}
-		todo &= ~m;
-	}
-}
-// Pops up to one slot of queue `q` for every lane with `want` set (in lane order).  Returns whether THIS lane got one.
-__device__ __forceinline__ bool fq_pop_into(FastLds* Q, uint32_t q, int lane, bool want, uint32_t* slot) {
-	const unsigned long long wm = __ballot(want);
-	if(wm == 0) return false;
-	const uint32_t nwant = (uint32_t)__popcll(wm);
-	uint32_t n = 0, h = 0;
-	if(lane == 0) {
-		for(;;) {
-			h = __atomic_load_n(&Q->head[q], __ATOMIC_RELAXED);
-			const uint32_t t = __atomic_load_n(&Q->tail[q], __ATOMIC_RELAXED);
-			n = t - h;
-			if(n == 0) break;
-			if(n > nwant) n = nwant;
-			if(atomicCAS(&Q->head[q], h, h + n) == h) break;
-		}
-	}
-	n = (uint32_t)__shfl((int)n, 0); h = (uint32_t)__shfl((int)h, 0);
-	const uint32_t r = (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
-	const bool got = want && r < n;
-	if(got) {
-		const uint32_t pos = (h + r) & (H2G_FAST_SLOTS - 1);
-		uint16_t v;
-		while((v = __atomic_load_n(&Q->ring[q][pos], __ATOMIC_RELAXED)) == FG_RING_EMPTY) __builtin_amdgcn_s_sleep(1);   // reserved, being written
-		__atomic_store_n(&Q->ring[q][pos], (uint16_t)FG_RING_EMPTY, __ATOMIC_RELAXED);
-		*slot = v;
-	}
-	return got;
-}
 
 __device__ __forceinline__ void fk_ctx(const FastArgs* A, uint32_t* stage, uint32_t* sm, FCtx& C, FWords& W) {
 	const bool paired = A->paired != 0;
@@ -214,13 +163,8 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 	const int lane = (int)(threadIdx.x & 63);
 	const unsigned long long lt = (1ull << lane) - 1ull;
 	const bool paired = A->paired != 0;
-	for(uint32_t k = threadIdx.x; k < (uint32_t)FG_NQ * H2G_FAST_SLOTS; k += blockDim.x) (&Q->ring[0][0])[k] = FG_RING_EMPTY;
-	if(threadIdx.x < (uint32_t)FG_NQ) { Q->head[threadIdx.x] = 0; Q->tail[threadIdx.x] = 0; }
 	if(threadIdx.x == 0) { Q->quit = 0; Q->parked = 0; }
-	__syncthreads();
-	for(uint32_t k = threadIdx.x; k < H2G_FAST_SLOTS; k += blockDim.x) Q->ring[0][k] = (uint16_t)k;   // every slot starts free
-	if(threadIdx.x == 0) Q->tail[0] = H2G_FAST_SLOTS;
-	__syncthreads();
+	Q->init();                                                // every slot starts free (its barriers cover the two words above)
 	uint32_t* const pk0 = stage + FW_HOT * H2G_FAST_THREADS;
 	uint32_t* const pk1 = pk0 + H2G_PK_WORDS * H2G_FAST_THREADS;
 	uint32_t* const slots0 = A->slots + (size_t)blockIdx.x * H2G_FAST_SLOTS * FG_SLOT_WORDS;
@@ -238,8 +182,8 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 	__builtin_memset(&S, 0, sizeof S);
 	for(;;) {
 		// ---- choose: per site, the lanes a trip would fill = this wave's own lanes waiting for it + its queue
-		uint32_t cnt = 0, own = 0;
-		if(lane < FG_NQ) cnt = __atomic_load_n(&Q->tail[lane], __ATOMIC_RELAXED) - __atomic_load_n(&Q->head[lane], __ATOMIC_RELAXED);
+		uint32_t own = 0;
+		const uint32_t cnt = Q->count(lane);
 #pragma unroll
 		for(uint32_t q = 0; q < (uint32_t)FG_NQ; q++) { const uint32_t c = (uint32_t)__popcll(__ballot(keep && myq == q)); if((uint32_t)lane == q) own = c; }
 		const uint32_t nfree = (uint32_t)__shfl((int)cnt, 0), own_free = (uint32_t)__shfl((int)own, 0);
@@ -277,7 +221,7 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 			FPROF(2);
 			if(__ballot(out)) {
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-				fq_push(Q, out, myq, slot, lane);
+				Q->push(out, myq, slot, lane);
 			}
 			if(out) keep = false;
 			FPROF(17);
@@ -291,7 +235,8 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 		bool active = false, tail = false, fresh = false;
 		uint32_t begin = H2G_MAX, packed_ok = 0, trip_op = FOP_NONE;
 		if(fetch) {
-			const bool got = fq_pop_into(Q, FQ_FREE, lane, !keep, &slot);    // (a lane whose read is over re-uses its slot without the queue)
+			bool got;
+			Q->pop(FQ_FREE, lane, !keep, &slot, &got);                       // (a lane whose read is over re-uses its slot without the queue)
 			const bool has = keep || got;
 			const unsigned long long hm = __ballot(has);
 			const uint32_t n = (uint32_t)__popcll(hm);
@@ -331,7 +276,7 @@ __device__ __forceinline__ void fk_loop(const FastArgs* __restrict__ A, uint32_t
 			FPROF(15);
 		} else {
 			trip_op = fg_queue_op(qstar);
-			fresh = fq_pop_into(Q, qstar, lane, !keep, &slot);
+			Q->pop(qstar, lane, !keep, &slot, &fresh);
 			if(__ballot(fresh)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 			active = keep || fresh;
 			// (FastArgs::tail: the last reads in flight of an exhausted batch are a few latency chains per workgroup; they can go to the general
@@ -429,27 +374,11 @@ __global__ __launch_bounds__(H2G_FAST_THREADS) void FG_KERNEL_DRAIN(const FastAr
 }
 
 #define FG_LDS_BYTES ((unsigned)(((sizeof(FastLds) + 3) / 4 + (size_t)FG_STAGE_WORDS * H2G_FAST_THREADS) * 4))
-extern "C" void FG_GEOMETRY(uint32_t* g) {
-	g[0] = H2G_FAST_THREADS; g[1] = FG_LDS_BYTES; g[2] = H2G_FAST_SLOTS; g[3] = FG_SLOT_WORDS * 4u;
-#if FG_GRAPH
-	g[4] = FG_GWS_PRIVATE ? 0u : (uint32_t)sizeof(GraphWS);
-#endif
-}
-// `a` is the argument block in DEVICE memory
-extern "C" int FG_LAUNCH(const FastArgs* a, unsigned grid, hipStream_t st) {
-	// more than 64 KB of dynamic LDS is an opt-in — per DEVICE (a process may drive several: hisat2-align-amd --gpus N), so the flag is a mask over device ids
-	static std::atomic<unsigned long long> lds_ok{0};
-	int dev = 0; (void)hipGetDevice(&dev);
-	const unsigned long long bit = 1ull << (dev & 63);
-	if(!(lds_ok.load(std::memory_order_relaxed) & bit)) { if(hipFuncSetAttribute((const void*)FG_KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit, std::memory_order_relaxed); }
-	hipLaunchKernelGGL(FG_KERNEL, dim3(grid), dim3(H2G_FAST_THREADS), FG_LDS_BYTES, st, a);
-	return (int)hipGetLastError();
-}
-extern "C" int FG_LAUNCH_DRAIN(const FastArgs* a, unsigned grid, hipStream_t st) {
-	static std::atomic<unsigned long long> lds_ok{0};
-	int dev = 0; (void)hipGetDevice(&dev);
-	const unsigned long long bit = 1ull << (dev & 63);
-	if(!(lds_ok.load(std::memory_order_relaxed) & bit)) { if(hipFuncSetAttribute((const void*)FG_KERNEL_DRAIN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError(); lds_ok.fetch_or(bit, std::memory_order_relaxed); }
-	hipLaunchKernelGGL(FG_KERNEL_DRAIN, dim3(grid), dim3(H2G_FAST_THREADS), FG_LDS_BYTES, st, a);
-	return (int)hipGetLastError();
+// what h2g_kernels.hip sees of this build of the pass (FastUnitDesc, h2g_go_args.h)
+static int fk_launch(const FastArgs* a, unsigned grid, hipStream_t st) { return launch_large_lds<FG_KERNEL>(grid, H2G_FAST_THREADS, FG_LDS_BYTES, st, a); }
+static int fk_launch_drain(const FastArgs* a, unsigned grid, hipStream_t st) { return launch_large_lds<FG_KERNEL_DRAIN>(grid, H2G_FAST_THREADS, FG_LDS_BYTES, st, a); }
+extern "C" const FastUnitDesc* FG_UNIT() {
+	static const FastUnitDesc d = {fk_launch, fk_launch_drain, H2G_FAST_THREADS, FG_LDS_BYTES, H2G_FAST_SLOTS, FG_SLOT_WORDS * 4u,
+		FG_GRAPH && !FG_GWS_PRIVATE ? (uint32_t)sizeof(GraphWS) : 0u};
+	return &d;
 }

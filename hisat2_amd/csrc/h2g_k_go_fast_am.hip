@@ -3,6 +3,5 @@
 // (h2g_stream_tune "align_mate"; profiles/r04_NOTES.md has the measurements behind the default).
 #define FG_ALIGN_MATE 1
 #define FG_KERNEL   k_go_fast_am
-#define FG_LAUNCH   h2g_go_fast_am_launch
-#define FG_GEOMETRY h2g_go_fast_am_geometry
+#define FG_UNIT     h2g_go_fast_am_unit
 #include "h2g_k_go_fast.hip"

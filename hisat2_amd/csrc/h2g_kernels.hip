@@ -2459,28 +2459,25 @@ static int need_alignable(h2g_stream* s) {
 	return H2G_ERR_UNSUPPORTED;
 }
 
-// the go() units: [linear?][tier: default, big, extra-large]
-struct GoUnit {
-	size_t (*ws_bytes)(); size_t (*gws_bytes)(); int (*waves)(); void (*caps)(uint32_t*); int (*launch)(const GoArgs*, const DExonTbl*, const XlPairs*, unsigned, hipStream_t);
-	size_t (*slot_off)(); size_t (*gsl_off)(); void (*geometry)(uint32_t*); size_t (*sw_bytes)(uint32_t, int);
-};
-static const GoUnit& go_unit(bool linear, bool big, bool spliced = false, bool xl = false) {
-	// spliced alignment: the units whose machine carries the splice-site database joins
-#define H2G_UNIT_ROW(N) {h2g_go_ws_bytes_##N, h2g_go_gws_bytes_##N, h2g_go_waves_##N, h2g_go_caps_##N, h2g_go_launch_##N, h2g_go_slot_off_##N, h2g_go_gsl_off_##N, h2g_go_geometry_##N, h2g_go_sw_bytes_##N}
-	const int tier = xl ? 2 : big ? 1 : 0;
-	static const GoUnit spl[2][3] = {{H2G_UNIT_ROW(graph_spl), H2G_UNIT_ROW(graph_spl_big), H2G_UNIT_ROW(graph_spl_xl)}, {H2G_UNIT_ROW(linear_spl), H2G_UNIT_ROW(linear_spl_big), H2G_UNIT_ROW(linear_spl_xl)}};
-	if(spliced) return spl[linear ? 1 : 0][tier];
-	static const GoUnit u[2][3] = {{H2G_UNIT_ROW(graph), H2G_UNIT_ROW(graph_big), H2G_UNIT_ROW(graph_xl)}, {H2G_UNIT_ROW(linear), H2G_UNIT_ROW(linear_big), H2G_UNIT_ROW(linear_xl)}};
-	return u[linear ? 1 : 0][tier];
+// the go() units (GoUnitDesc, h2g_go_args.h): [spliced?][linear?][tier: default, big, extra-large].  Spliced: the units whose machine carries the splice-site database joins
+static const GoUnitDesc& go_unit(bool linear, bool big, bool spliced = false, bool xl = false) {
+	static const GoUnitDesc* (*const u[2][2][3])() = {
+		{{h2g_go_unit_graph, h2g_go_unit_graph_big, h2g_go_unit_graph_xl}, {h2g_go_unit_linear, h2g_go_unit_linear_big, h2g_go_unit_linear_xl}},
+		{{h2g_go_unit_graph_spl, h2g_go_unit_graph_spl_big, h2g_go_unit_graph_spl_xl}, {h2g_go_unit_linear_spl, h2g_go_unit_linear_spl_big, h2g_go_unit_linear_spl_xl}}};
+	return *u[spliced ? 1 : 0][linear ? 1 : 0][xl ? 2 : big ? 1 : 0]();
+}
+// the builds of the fast pass (FastUnitDesc): graph indexes; on a linear index spliced runs, alignMate in the pass, or neither
+static const FastUnitDesc& fast_unit(bool linear, bool spliced, bool align_mate) {
+	return *(!linear ? h2g_go_fast_graph_unit : spliced ? h2g_go_fast_spl_unit : align_mate ? h2g_go_fast_am_unit : h2g_go_fast_unit)();
 }
 
 // sizes the per-lane scratch of one pass and fills the pool fields of `a`
-static int go_pool_for(h2g_stream* s, int which, const GoUnit& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
+static int go_pool_for(h2g_stream* s, int which, const GoUnitDesc& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
 	h2g_stream::GoPool& pl = s->pool[which];
-	const size_t wsb = u.ws_bytes(), gwb = u.gws_bytes();
+	const size_t wsb = u.ws_bytes, gwb = u.gws_bytes;
 	int rc;
 	if((rc = grow((void**)&pl.ws, &pl.ws_bytes, slots * wsb))) return rc;
-	a->pool = pl.ws; a->ws_stride = wsb; a->slot_off = u.slot_off(); a->gsl_off = u.gsl_off();
+	a->pool = pl.ws; a->ws_stride = wsb; a->slot_off = u.slot_off; a->gsl_off = u.gsl_off;
 	a->gws_base = nullptr; a->gws_stride = gwb;
 	if(gwb) {
 		if((rc = grow((void**)&pl.gws, &pl.gws_bytes, lanes * gwb))) return rc;
@@ -2554,8 +2551,7 @@ static int go_check(h2g_stream* s, const h2g_align_params* p, bool paired) {
 struct GoPlan {
 	bool linear, spl, xl, big_main, fast, second;
 	bool fast_spl;                 // the fast pass is the build for spliced runs (h2g_k_go_fast_spl.hip): its hand-ons go to the spliced machine units
-	const GoUnit *U, *L;           // the main pass's unit; the large-workspace unit (the second pass, the machine streams' warm-up)
-	uint32_t geo[4], lgeo[4];      // their geometries: [0] threads per workgroup, [1] reads in flight per workgroup
+	const GoUnitDesc *U, *L;       // the main pass's unit; the large-workspace unit (the second pass, the machine streams' warm-up)
 	unsigned grid, M, bgrid;       // workgroups of the main pass; lanes (per-run buffers: M + 1 deep; area parts: M); workgroups of a second pass
 	unsigned S;                    // machine streams in rotation: lane m's pass runs on mst[m % S]
 	unsigned mach_cap, pool_cap;   // workgroups of one machine pass behind a fast pass, and what its pools are sized for
@@ -2582,9 +2578,8 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 	const bool ext_opts = pe_flags_from(*p) != H2G_PE_DEFAULT || p->min_frag_len != 0 || p->transcriptome_mapping_only || (p->avoid_pseudogene && !p->no_spliced_alignment);
 	g->spl = !p->no_spliced_alignment || (p->use_haplotype && !g->linear) || ext_opts;
 	const uint32_t maxsz = p->khits > p->kseeds ? p->khits : p->kseeds;
-	uint32_t caps[5], bcaps[5];
 	g->L = &go_unit(g->linear, true, g->spl);
-	go_unit(g->linear, false, g->spl).caps(caps); g->L->caps(bcaps);
+	const uint32_t* const caps = go_unit(g->linear, false, g->spl).caps, * const bcaps = g->L->caps;   // ([0]: AL_MAX_GHITS)
 	// a run beyond what the large units hold (more alignments selected than H2G_SELECT_CAP, or a list beyond their AL_MAX_GHITS) runs on the
 	// extra-large units (h2g_go_xl.h), whole: no fast pass, no second pass
 	g->xl = p->khits > H2G_SELECT_CAP || maxsz > bcaps[0];
@@ -2597,15 +2592,14 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 	g->fast_spl = s->tune.fast && s->tune.fast_spliced && g->linear && !p->no_spliced_alignment && !ext_opts && !g->big_main && !p->secondary && !p->bowtie2_dp;
 	if(g->fast_spl) g->fast = true;
 	g->second = !g->big_main && !s->tune.no_second_pass;     // (no_second_pass: a measurement / debugging knob)
-	// geometry of the unit: workgroups of geo[0] threads own geo[1] reads in flight; resident workgroups per CU = what the
+	// geometry of the unit: workgroups of `threads` threads own `slots` reads in flight; resident workgroups per CU = what the
 	// unit's waves per SIMD and the LDS (rings + one packed-read region per mate) allow
-	g->U->geometry(g->geo); g->L->geometry(g->lgeo);
-	size_t per_cu = (size_t)g->U->waves() * 256 / g->geo[0];
-	const size_t lds_blocks = (160u * 1024u) / (g->geo[2] + (paired ? 2u : 1u) * g->geo[3]);
+	size_t per_cu = (size_t)g->U->waves * 256 / g->U->threads;
+	const size_t lds_blocks = (160u * 1024u) / (g->U->lds_ring_bytes + (paired ? 2u : 1u) * g->U->lds_pack_bytes);
 	if(per_cu > lds_blocks) per_cu = lds_blocks;
 	if(per_cu < 1) per_cu = 1;
 	if(s->tune.blocks_per_cu > 0) per_cu = (size_t)s->tune.blocks_per_cu;
-	const size_t want = (n_reads + g->geo[1] - 1) / g->geo[1];
+	const size_t want = (n_reads + g->U->slots - 1) / g->U->slots;
 	size_t maxblocks = 256 * per_cu;
 	if(g->big_main && maxblocks > 32) maxblocks = 32;        // ~1.3 MB of workspace per read in flight
 	if(g->xl && maxblocks > 12) maxblocks = 12;              // XL: 18.7 MB per read in flight, 12 x 128 of them (h2g_go_xl.h)
@@ -2631,7 +2625,7 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 // the fast pass's share of a run (h2g_fast.h), decided by fast_policy
 struct FastPlan {
 	bool use_am, mate_ho;          // alignMate in the pass; pairs that need it parked for the drain launch (its alignMate build)
-	uint32_t fgeo[5], dgeo[5];     // geometry of the fast launch's build and of the drain launch's
+	const FastUnitDesc *FU, *DU;   // the fast launch's build of the pass and the drain launch's
 	unsigned fgrid, mgrid, dgrid;  // workgroups of the fast launch, of the machine pass behind it, of the drain launch
 	uint32_t orphan_T, psel;       // > 0: the end of the batch goes to a drain launch; the slot pool of the fast launch ...
 	size_t slot_bytes;             // ... and its size
@@ -2693,8 +2687,8 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 		// (Small batches keep allocating a machine stream's pools when it is first used.)
 		GoArgs scratch = *A;
 		for(unsigned m = 0; m < g.S && s->gen >= 1; m++) {
-			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, &scratch))) return rc;
-			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &scratch))) return rc;
+			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, &scratch))) return rc;
+			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &scratch))) return rc;
 			// ... and its overflow list
 			if(!s->d_ovf_list[m]) { HIPCHK(hipMalloc((void**)&s->d_ovf_list[m], (s->max_reads + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
 		}
@@ -2704,7 +2698,7 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
 		}
 	}
-	return go_pool_for(s, g.fast ? 2 * (int)((s->gen % g.M) % g.S) : 0, *g.U, pgrid * g.geo[1], pgrid * g.geo[0], p->bowtie2_dp, A);
+	return go_pool_for(s, g.fast ? 2 * (int)((s->gen % g.M) % g.S) : 0, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, A);
 }
 
 // the batch's result rows (grown to this run's -k), the pairs' overflow area and the XL units' side area
@@ -2796,7 +2790,7 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	const bool linear = g.linear;
 	*f = FastPlan();
 	f->use_am = linear && paired && s->tune.align_mate != 0 && !g.fast_spl;      // (alignMate differs in spliced mode: such pairs are the machine's)
-	if(!linear) h2g_go_fast_graph_geometry(f->fgeo); else if(g.fast_spl) h2g_go_fast_spl_geometry(f->fgeo); else if(f->use_am) h2g_go_fast_am_geometry(f->fgeo); else h2g_go_fast_geometry(f->fgeo);
+	f->FU = &fast_unit(linear, g.fast_spl, f->use_am);
 	// CUs: one persistent fast workgroup each (LDS-bound), minus the few the machine pass of the PREVIOUS run may still hold
 	// (the machine takes ~150 hand-ons per workgroup in half the time of a fast pass; the count is the last finished fast pass's)
 	const unsigned NB = g.M + 1;
@@ -2831,24 +2825,23 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	if(reserve > 192) reserve = 192;
 	const unsigned fmax = 256 - reserve;
 	f->fgrid = (unsigned)(fwant < 1 ? 1 : (fwant > fmax ? fmax : fwant));
-	f->slot_bytes = (size_t)256 * f->fgeo[2] * f->fgeo[3];
+	f->slot_bytes = (size_t)256 * f->FU->slots * f->FU->slot_bytes;
 	// the end of the batch goes to a drain launch (h2g_k_go_fast.hip) when the batch is large enough to have one
 	f->orphan_T = s->tune.orphan >= 0 ? (uint32_t)s->tune.orphan : (g.units >= H2G_ORPHAN_MIN_UNITS ? (uint32_t)H2G_ORPHAN_T : 0u);
-	if(f->orphan_T > f->fgeo[2]) f->orphan_T = f->fgeo[2];
-	if(!linear && f->fgeo[4] != 0) f->orphan_T = 0;                     // (a graph unit with GraphWS in global memory: its scratch is sized for one launch)
+	if(f->orphan_T > f->FU->slots) f->orphan_T = f->FU->slots;
+	if(f->FU->gws_bytes != 0) f->orphan_T = 0;                          // (a graph unit with GraphWS in global memory: its scratch is sized for one launch)
 	f->dgrid = (unsigned)(s->tune.drain_grid < 1 ? 1 : s->tune.drain_grid);
 	// pairs that need alignMate (hi_aligner.h:5579): with a drain launch there, the fast launch parks them and the drain launch is the alignMate build of the pass (k_go_fast_am_drain)
 	// — the hot loop keeps the lighter build, the machine sees neither them nor the tail (h2g_stream_tune "mate_handover": -1 this policy, 0 off, 1 on)
 	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && !g.fast_spl && s->tune.mate_handover != 0;
-	for(int k = 0; k < 5; k++) f->dgeo[k] = f->fgeo[k];
-	if(f->mate_ho) h2g_go_fast_am_geometry(f->dgeo);
+	f->DU = &fast_unit(linear, g.fast_spl, f->use_am || f->mate_ho);
 	f->psel = f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
 }
 
 // every buffer of the two launches exists (and has been written once: fresh device memory costs its first writer the mapping) before the first run that could need it
 static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
-	const size_t ocap = (size_t)256 * f.fgeo[2], dbytes = (size_t)f.dgrid * f.dgeo[2] * f.dgeo[3];
-	const size_t dsc = g.linear ? 0 : (size_t)f.dgrid * f.fgeo[0] * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
+	const size_t ocap = (size_t)256 * f.FU->slots, dbytes = (size_t)f.dgrid * f.DU->slots * f.DU->slot_bytes;
+	const size_t dsc = g.linear ? 0 : (size_t)f.dgrid * f.FU->threads * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
 	bool need = s->fast_slot_bytes[f.psel] < f.slot_bytes;
 	if(f.orphan_T) {
 		for(unsigned q = 0; q < H2G_FAST_POOLS; q++) need = need || s->fast_slot_bytes[q] < f.slot_bytes;
@@ -2907,10 +2900,10 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
 	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
 	if(!g.linear) {   // per-lane scratch of the graph primitives (every CU may hold a workgroup)
-		const size_t lanes = (size_t)256 * f.fgeo[0];
-		if((rc = grow((void**)&s->d_fast_gws, &s->fast_gws_bytes, lanes * f.fgeo[4])) ||
+		const size_t lanes = (size_t)256 * f.FU->threads;
+		if((rc = grow((void**)&s->d_fast_gws, &s->fast_gws_bytes, lanes * f.FU->gws_bytes)) ||
 		   (rc = grow((void**)&s->d_fast_sc, &s->fast_sc_bytes, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))))) return rc;
-		F.gws_base = s->d_fast_gws; F.gws_stride = f.fgeo[4]; F.sc_base = s->d_fast_sc;
+		F.gws_base = s->d_fast_gws; F.gws_stride = f.FU->gws_bytes; F.sc_base = s->d_fast_sc;
 	}
 	if(!s->d_fast_args[gsel]) HIPCHK(hipMalloc((void**)&s->d_fast_args[gsel], sizeof(FastArgs)));
 	FastArgs D = F;
@@ -2918,7 +2911,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		uint32_t* const ol = s->d_orphans[gsel];
 		HIPCHK(hipMemsetAsync(ol + s->orphan_cap, 0, 16, s->st));
 		F.orphan_T = f.orphan_T; F.orphan_list = ol; F.orphan_count = ol + s->orphan_cap; F.mate_handover = f.mate_ho ? 1u : 0u;
-		D.adopt_slot_words = f.fgeo[3] / 4;
+		D.adopt_slot_words = f.FU->slot_bytes / 4;
 		// The drain launch's own tail (the last reads of each of its workgroups go to the machine).  With few hand-ons the machine's passes are short and the tail is a third of
 		// what they get: the drain launch finishes its reads itself (lease ZE, random genome: 11.48 -> 11.16 ms per step, hand-ons 2 830 -> 1 880); where the machine's passes are
 		// the step (more than 1.5 % handed on: the policy of mach_total) they absorb the tail for nothing and a drain launch that runs to its last read would be the longer one
@@ -2944,7 +2937,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		*hD = D;
 		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
 	}
-	if((!g.linear ? h2g_go_fast_graph_launch : g.fast_spl ? h2g_go_fast_spl_launch : f.use_am ? h2g_go_fast_am_launch : h2g_go_fast_launch)(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
+	if(f.FU->launch(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
 	r->A.list = bl; r->A.nlist = bl + s->max_reads;
 	return H2G_OK;
 }
@@ -2959,10 +2952,9 @@ static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	if(f.mgrid < r->mach_grid) r->mach_grid = f.mgrid;
 	if(f.orphan_T) {
 		// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
-		const bool use_am = f.use_am || f.mate_ho;
 		HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
 		HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
-		if((!g.linear ? h2g_go_fast_graph_launch_drain : g.fast_spl ? h2g_go_fast_spl_launch_drain : use_am ? h2g_go_fast_am_launch_drain : h2g_go_fast_launch_drain)(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
+		if(f.DU->launch_drain(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
 		HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
 		HIPCHK(hipEventRecord(s->ev_pool[f.psel], s->dst));
 		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
@@ -3022,7 +3014,7 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 	for(unsigned m = 0; m < g.S; m++) {
 		if(m == r.ssel || ((s->warm_mask >> m) & 1u) || !s->d_ovf_list[m]) continue;
 		GoArgs W1 = r.A;
-		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.geo[1], (size_t)g.geo[0], p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
+		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.U->slots, (size_t)g.U->threads, p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
 		W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_MAIN);
 		W1.list = reinterpret_cast<uint32_t*>(s->d_warm_rows); W1.nlist = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_NO_SECOND);   // a count of zero
 		memset(&W1.O, 0, sizeof W1.O);
@@ -3037,7 +3029,7 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 		if(g.U->launch(&W1, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		if(g.second) {
 			GoArgs W2 = W1;
-			if((rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.lgeo[1], (size_t)g.lgeo[0], p->bowtie2_dp, &W2))) return rc;
+			if((rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.L->slots, (size_t)g.L->threads, p->bowtie2_dp, &W2))) return rc;
 			W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_SECOND);
 			if(g.L->launch(&W2, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		}
@@ -3055,7 +3047,7 @@ static int go_mach(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, Go
 	if(g.second) {
 		GoArgs A2 = r->A;
 		int rc;
-		if((rc = go_pool_for(s, 2 * r->qsel + 1, *g.L, (size_t)g.bgrid * g.lgeo[1], (size_t)g.bgrid * g.lgeo[0], p->bowtie2_dp, &A2))) return rc;
+		if((rc = go_pool_for(s, 2 * r->qsel + 1, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &A2))) return rc;
 		A2.counters = r->cblk + H2G_CNT_SECOND;           // (a region of its own: in H2G_GO_PROF builds a pass writes up to 96 words behind its counters)
 		A2.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_SECOND);
 		A2.list = r->ovl; A2.nlist = r->ovl + s->max_reads;   // (the count is filled by the main pass itself: MachOut::defer_list)

@@ -165,11 +165,17 @@ def fam(tmp_path_factory):
 @pytest.mark.parametrize("opts,k,want_min,small", [
     (("--no-spliced-alignment", "-k", "100"), 100, 20000, False),
     (("-k", "50", "--max-seeds", "150", "--secondary", "--no-temp-splicesite"), 50, SMALL_MIN["u50"], True),
+    # unspliced on an SNP-graph index: the extra-large graph unit WITHOUT the splice-site joins, which no other case runs (the small family's reads, as -k 31 below:
+    # at least 200 lines beyond -k 30)
+    (("--no-spliced-alignment", "-k", "100"), 100, 200, "graph"),
 ])
-def test_unpaired_large_k(fam, opts, k, want_min, small):
+def test_unpaired_large_k(fam, tmp_path, opts, k, want_min, small):
     t, base, rfa = fam[:3]
     if small:
         rfa = os.path.join(t, "rs.fa")
+    if small == "graph":
+        t = str(tmp_path)
+        base = build(t, fam[5], snp_seed=911)
     tag = "u" + "".join(o.strip("-")[:3] for o in opts)
     want = both(t, tag, base, ["-U", rfa], opts)
     k30 = [o if o != str(k) else "30" for o in opts]
