@@ -277,6 +277,20 @@ class WindowsStats(C.Structure):     # h2g_windows_stats
     _fields_ = [("bytes_uploaded", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float), ("pad", C.c_float)]
 
 
+class FastqOpts(C.Structure):        # h2g_fastq_opts
+    _fields_ = [("trim5", C.c_uint32), ("trim3", C.c_uint32), ("phred64", C.c_uint8), ("final1", C.c_uint8), ("final2", C.c_uint8), ("pad", C.c_uint8), ("max_records", C.c_uint64)]
+
+
+class FastqResult(C.Structure):      # h2g_fastq_result
+    _fields_ = [("n_records", C.c_uint64), ("consumed1", C.c_uint64), ("consumed2", C.c_uint64), ("n_bases1", C.c_uint64), ("n_bases2", C.c_uint64),
+                ("n_name_bytes1", C.c_uint64), ("n_name_bytes2", C.c_uint64), ("n_not_plain", C.c_uint64), ("first_not_plain", C.c_uint64),
+                ("max_read_len", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class FastqStats(C.Structure):       # h2g_fastq_stats
+    _fields_ = [("bytes_uploaded", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float), ("pad", C.c_float)]
+
+
 WINDOW_SEG_DTYPE = np.dtype([("text_start", np.uint64), ("name_off0", np.uint64), ("rdid0", np.uint64), ("n_windows", np.uint32), ("prefix_start", np.uint32),
                              ("prefix_len", np.uint32), ("pad", np.uint32)])
 assert WINDOW_SEG_DTYPE.itemsize == C.sizeof(WindowSeg)
@@ -322,6 +336,7 @@ EXPORTS = [
     "h2g_index_dense_lsa_check",
     "h2g_window_plan_create", "h2g_window_plan_add_file", "h2g_window_plan_get_info", "h2g_window_plan_text", "h2g_window_plan_prefixes", "h2g_window_plan_segments",
     "h2g_window_plan_select", "h2g_window_plan_free", "h2g_set_reads_windows", "h2g_get_windows_stats", "h2g_fetch_reads",
+    "h2g_set_reads_fastq", "h2g_fetch_read_set", "h2g_get_fastq_stats",
     "h2g_sam_plan_unpaired_compact", "h2g_sam_plan_paired_compact", "h2g_sam_text_unpaired", "h2g_sam_text_paired", "h2g_sam_text_from_plan_host", "h2g_get_sam_text_stats",
     "h2g_sam_text_unpaired_planned", "h2g_sam_text_paired_planned", "h2g_get_sam_plan_stats", "h2g_sam_plan_split_host",
 ]
@@ -329,6 +344,9 @@ EXPORTS = [
 
 class H2GError(RuntimeError):
     pass
+
+
+_EMPTY = np.zeros(16, np.uint8)      # the address an empty text is handed by
 
 
 def _ptr(x):
@@ -497,6 +515,9 @@ def lib():
     L.h2g_set_reads_windows.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, u32, u32, vp, C.c_size_t]
     L.h2g_get_windows_stats.argtypes = [vp, P(WindowsStats)]
     L.h2g_fetch_reads.argtypes = [vp, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(C.c_int), vp, vp, vp, vp, vp]
+    L.h2g_set_reads_fastq.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, P(FastqOpts), P(FastqResult)]
+    L.h2g_fetch_read_set.argtypes = [vp, C.c_int, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), vp, vp, vp, vp, vp]
+    L.h2g_get_fastq_stats.argtypes = [vp, P(FastqStats)]
     L.h2g_align_pairs_run.argtypes = [vp, P(AlignParams)]
     sz = C.c_size_t
     L.h2g_sam_plan_unpaired_compact.argtypes = [vp] * 6 + [sz, vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz), vp]
@@ -714,6 +735,48 @@ class Stream:
         _chk(lib().h2g_fetch_reads(self.h, C.byref(n), C.byref(nb), C.byref(nn), C.byref(hi), codes.ctypes.data, offs.ctypes.data, names.ctypes.data if nn.value else None,
                                    noffs.ctypes.data if nn.value else None, None if ids is None else ids.ctypes.data), "h2g_fetch_reads")
         return {"codes": codes, "offs": offs, "names": names.tobytes(), "name_offs": noffs, "ids": ids}
+
+    def set_reads_fastq(self, text1, text2=None, *, trim5=0, trim3=0, phred64=False, max_records=0, final=True):
+        """FASTQ records parsed on the device (h2g_set_reads_fastq): for the selected batch what set_reads + set_read_names (+ set_mates) do with a host parser's
+        arrays of the same bytes.  text1 / text2: bytes-like, beginning at a record start; final: the texts end their input (a pair (final1, final2) sets them apart).
+        Returns the FastqResult; with n_not_plain > 0 the batch is left empty and the caller parses the bytes itself.  An H2GError carries the result as .result."""
+        t1 = np.frombuffer(bytes(text1), dtype=np.uint8)
+        t2 = None if text2 is None else np.frombuffer(bytes(text2), dtype=np.uint8)
+        f1, f2 = final if isinstance(final, tuple) else (final, final)
+        opts = FastqOpts(trim5, trim3, 1 if phred64 else 0, 1 if f1 else 0, 1 if f2 else 0, 0, max_records)
+        res = FastqResult()
+        # (an unpaired call hands NULL for text2; an empty text still needs an address that is not NULL)
+        rc = lib().h2g_set_reads_fastq(self.h, t1.ctypes.data if len(t1) else _EMPTY.ctypes.data, len(t1),
+                                       None if t2 is None else (t2.ctypes.data if len(t2) else _EMPTY.ctypes.data), 0 if t2 is None else len(t2), C.byref(opts), C.byref(res))
+        self.n_reads = int(res.n_records) if rc == 0 and res.n_not_plain == 0 else 0
+        try:
+            _chk(rc, "h2g_set_reads_fastq")
+        except H2GError as e:
+            e.result = res
+            raise
+        return res
+
+    def fetch_read_set(self, mate=0):
+        """one mate of the selected batch as the device holds it (h2g_fetch_read_set): dict(codes, offs, quals (None without qualities), names (bytes), name_offs)"""
+        n, nb, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _chk(lib().h2g_fetch_read_set(self.h, mate, C.byref(n), C.byref(nb), C.byref(nn), None, None, None, None, None), "h2g_fetch_read_set")
+        codes = np.zeros(nb.value, np.uint8); offs = np.zeros(n.value + 1, np.uint32)
+        quals = np.zeros(nb.value, np.uint8)
+        names = np.zeros(nn.value, np.uint8); noffs = np.zeros(n.value + 1, np.uint32)
+        have_n = n.value and nn.value
+        rc = lib().h2g_fetch_read_set(self.h, mate, C.byref(n), C.byref(nb), C.byref(nn), codes.ctypes.data, offs.ctypes.data, quals.ctypes.data,
+                                      names.ctypes.data if have_n else None, noffs.ctypes.data if have_n else None)
+        if rc == -4:     # H2G_ERR_ARG: a set without qualities (any other status is an error of its own)
+            quals = None
+            rc = lib().h2g_fetch_read_set(self.h, mate, C.byref(n), C.byref(nb), C.byref(nn), codes.ctypes.data, offs.ctypes.data, None,
+                                          names.ctypes.data if have_n else None, noffs.ctypes.data if have_n else None)
+        _chk(rc, "h2g_fetch_read_set")
+        return {"codes": codes, "offs": offs, "quals": quals, "names": names.tobytes(), "name_offs": noffs}
+
+    def fastq_stats(self):
+        st = FastqStats()
+        _chk(lib().h2g_get_fastq_stats(self.h, C.byref(st)), "h2g_get_fastq_stats")
+        return st
 
     def rank(self, rows, cs, variant=0, repeats=1):
         rows = np.ascontiguousarray(rows, dtype=np.uint32)

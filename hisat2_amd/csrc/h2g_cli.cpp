@@ -87,6 +87,7 @@ struct PinSet { Pinned res, rec1, rec2, o1, o2; std::vector<h2g_edit> long_edits
 struct Options {
 	std::string base, outfn, stats_fn;
 	bool device_plan = false;                 // --h2g-device-plan (implies --h2g-device-sam): plain reads are planned on the device too, the host plans only the rest
+	bool device_parse = false;                // --h2g-device-parse: the FASTQ records are parsed on the device (h2g_set_reads_fastq); the host parses only the items it hands back
 	bool device_sam = false;                  // --h2g-device-sam: the SAM text is written on the device from a host-made line plan
 	std::vector<std::string> u, m1, m2, m12;
 	ReadFormat tab_fmt = FMT_TAB5;
@@ -205,7 +206,8 @@ Options parse_options(int argc, char** argv) {
 		else if(a == "--reorder" || a == "-t" || a == "--time" || a == "--mm") {}   // output is always in read order; --mm (index mapping) has nothing to act on here
 		else if(a == "--h2g-device-sam") o.device_sam = true;
 		else if(a == "--h2g-device-plan") o.device_sam = o.device_plan = true;
-		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on, device_sam_lines, whole_lines, device_planned, host_planned} as JSON (tests, bench)
+		else if(a == "--h2g-device-parse") o.device_parse = true;
+		else if(a == "--h2g-stats") o.stats_fn = need("--h2g-stats");               // writes {reads, second_pass, overflow, runs, fast, handed_on, device_sam_lines, whole_lines, device_planned, host_planned, device_parsed, host_parsed} as JSON (tests, bench)
 		else if(a == "--parse-only") o.parse_only = true;                           // test hook: ingest the reads, print counts + checksums
 		else if(const int arity = h2g_align_option_arity(argv[i]); arity >= 0) { o.opts.push_back(argv[i]); if(arity) o.opts.push_back(need(argv[i])); }   // every option that ends in a field of h2g_align_params
 		else { fprintf(stderr, "hisat2-align-amd: option %s is not built (see DESIGN.md, scope)\n", a.c_str()); exit(1); }
@@ -227,6 +229,16 @@ int Options::check() {
 		if(h2g_align_params_apply_options(&P, &presets, opts.data(), opts.size(), err, sizeof err) != H2G_OK) { fprintf(stderr, "%s\n", err); return 1; }
 	}
 	for(int k = 0; k < RS_KINDS; k++) sorting = sorting || !rs_arg[k].empty();
+	if(device_parse) {
+		// the device parses four-line FASTQ records with character qualities; every other reader, and what needs the host's copy of a record's text, is refused by name
+		const char* with = windows ? "-F" : fasta ? "-f" : raw_input ? "-r" : cmdline_input ? "-c" : !m12.empty() ? "--tab5/--tab6/--12" : qseq ? "--qseq" : qcoding.ints ? "--int-quals"
+		                   : qcoding.solexa ? "--solexa-quals" : parse_only ? "--parse-only" : nullptr;
+		if(with) { fprintf(stderr, "hisat2-align-amd: --h2g-device-parse is not built together with %s: it takes FASTQ files with character qualities (see DESIGN.md, scope)\n", with); return 1; }
+		for(int k = 0; k < RS_KINDS; k++) if(!rs_arg[k].empty()) {
+			fprintf(stderr, "hisat2-align-amd: --h2g-device-parse is not built together with --%s%s and its kin: they need the host's copy of every record's text (see DESIGN.md, scope)\n", rs_names[k], rs_gz[k] ? "-gz" : "");
+			return 1;
+		}
+	}
 	if(windows) {
 		// -F cuts its reads out of the -U files and nothing else: what would need another reader or a second mate is refused by name
 		const char* with = !m1.empty() || !m2.empty() ? "-1/-2" : !m12.empty() ? "--tab5/--tab6/--12" : qseq ? "--qseq" : cmdline_input ? "-c" : raw_input ? "-r" : nullptr;
@@ -969,7 +981,8 @@ private:
 // device) before the next wave starts (the exchange between two waves is the junction list, tens of bytes per site).
 class DeviceStage {
 public:
-	struct Config { bool qc_filter, arbitrary_random; size_t batch; const h2g_window_plan* plan; /* -F, or null */ };
+	struct Config { bool qc_filter, arbitrary_random; size_t batch; const h2g_window_plan* plan; /* -F, or null */
+	                const Reader* reader; /* --h2g-device-parse: the reader whose options the items' text is parsed under, or null */ uint32_t trim5, trim3; bool phred64; };
 	DeviceStage(const Config& c, const h2g_align_params& P, const Waves& wv, const Replicas& ix, ParseStage& parse, FormatStage& fmt)
 		: c_(c), P_(P), wv_(wv), ix_(ix), parse_(parse), fmt_(fmt), G_(ix.streams()), S_((size_t)ix.streams()), wave_left_(wv.wave) {
 		// --non-deterministic: every read / pair takes two draws, mate 1's seed then mate 2's, from one RandomSource seeded with time(0) (hisat2.cpp:3273,
@@ -991,8 +1004,9 @@ public:
 		}
 		complete(g);                                   // the batch this stream still carries (k - G): the oldest one in flight
 		Str& sg = S_[(size_t)g];
-		size_t bases = a.codes.size();
-		if(it.paired && b.codes.size() > bases) bases = b.codes.size();
+		const bool raw = c_.reader && a.raw_n;         // --h2g-device-parse: the item travels as text (its bases are fewer than its bytes)
+		size_t bases = raw ? a.raw.size() : a.codes.size();
+		if(it.paired && (raw ? b.raw.size() : b.codes.size()) > bases) bases = raw ? b.raw.size() : b.codes.size();
 		if(!sg.st || n > sg.reads || bases > sg.bases) {
 			if(sg.st) h2g_stream_free(sg.st);
 			sg.reads = n > c_.batch ? n : c_.batch; sg.bases = bases + bases / 4 + 1024;
@@ -1001,13 +1015,14 @@ public:
 			t_stream += now() - ts;
 		}
 		const double tq0 = now();
+		const bool on_device = raw && parse_on_device(sg.st, it, a, b);      // (true: the batch is resident and `a` / `b` hold its arrays; no upload call follows)
 		if(!it.wsegs.empty()) {
 			// -F: the device cuts the windows out of the text itself (codes, names and ids; the host's copies are for the SAM text)
 			h2g_window_plan_info pi;
 			h2g_window_plan_get_info(c_.plan, &pi);
 			if(h2g_set_reads_windows(sg.st, h2g_window_plan_text(c_.plan), pi.n_text, it.wsegs.data(), it.wsegs.size(), pi.len, pi.step, h2g_window_plan_prefixes(c_.plan),
 			                         pi.n_prefix_bytes) != H2G_OK) die("h2g_set_reads_windows");
-		} else {
+		} else if(!on_device) {
 			if(h2g_set_reads(sg.st, a.codes.data(), a.offs.data(), a.have_quals ? a.quals.data() : nullptr, n) != H2G_OK) die("h2g_set_reads");
 			if(h2g_set_read_names(sg.st, a.names.data(), a.noffs.data(), n) != H2G_OK) die("h2g_set_read_names");
 			// read ids are 32 bits in the splice-site window test (DSpliceSite::readid): past that the temporary sites' visibility would wrap silently
@@ -1019,7 +1034,7 @@ public:
 		sg.first_id = it.first_id;
 		nsubmitted_ += n;
 		warn_of_long_chain(n);
-		if(it.paired) {
+		if(it.paired && !on_device) {
 			if(h2g_set_mates(sg.st, b.codes.data(), b.offs.data(), b.have_quals ? b.quals.data() : nullptr, b.names.data(), b.noffs.data(), n) != H2G_OK) die("h2g_set_mates");
 		}
 		if(c_.arbitrary_random) {                      // this batch's draws, in read order (the batches are submitted in read order whatever the device); the skipped reads draw too
@@ -1052,10 +1067,38 @@ public:
 	}
 	void free_streams() { for(Str& sg : S_) if(sg.st) { h2g_stream_free(sg.st); sg.st = nullptr; } }
 	uint64_t nsecond = 0, nruns = 0;          // reads that took the second pass; device runs
+	uint64_t ndevice_parsed = 0, nhost_parsed = 0;   // --h2g-device-parse: records the device parsed; records of the items it handed back to the host parser
 	uint64_t nfast = 0, nhanded = 0;          // reads / pairs the fast pass completed; handed on to the general machine (summed over the runs)
 	double t_gpu = 0, t_up = 0, t_fetch = 0, t_stream = 0;
 private:
 	struct Str { h2g_stream* st = nullptr; size_t reads = 0, bases = 0; long batch = -1; size_t n = 0; uint64_t first_id = 0; bool paired = false; int merge = 0; };
+	// --h2g-device-parse: the item's text becomes the stream's batch (h2g_set_reads_fastq) and the arrays the formatter reads are fetched from it; false: a record of the
+	// item is not plain — the host parser has filled `a` / `b` from the same text (or ended the run with its message) and the three upload calls follow
+	bool parse_on_device(h2g_stream* st, const Item& it, Batch& a, Batch& b) {
+		h2g_fastq_opts fo;
+		memset(&fo, 0, sizeof fo);
+		fo.trim5 = c_.trim5; fo.trim3 = c_.trim3; fo.phred64 = c_.phred64 ? 1 : 0; fo.final1 = fo.final2 = 1;
+		h2g_fastq_result fr;
+		if(h2g_set_reads_fastq(st, a.raw.data(), a.raw.size(), it.paired ? b.raw.data() : nullptr, it.paired ? b.raw.size() : 0, &fo, &fr) != H2G_OK) die("h2g_set_reads_fastq");
+		if(fr.n_not_plain || fr.n_records != it.n) {
+			c_.reader->parse_raw(a, it.n);
+			if(it.paired) c_.reader->parse_raw(b, it.n);      // (a -2 file with more records than its -1 file: the surplus is nobody's, as without the flag)
+			if(a.n() != it.n || (it.paired && b.n() != it.n)) { fprintf(stderr, "hisat2-align-amd: the host parser found %zu records where the record scan found %zu\n", a.n(), it.n); exit(1); }
+			nhost_parsed += it.n;
+			return false;
+		}
+		Batch* m[2] = {&a, &b};
+		const uint64_t nb[2] = {fr.n_bases1, fr.n_bases2}, nn[2] = {fr.n_name_bytes1, fr.n_name_bytes2};
+		for(int k = 0; k < (it.paired ? 2 : 1); k++) {
+			Batch& s = *m[k];
+			s.have_quals = true;
+			s.codes.resize(nb[k]); s.quals.resize(nb[k]); s.names.resize(nn[k]); s.offs.resize(it.n + 1); s.noffs.resize(it.n + 1);
+			if(h2g_fetch_read_set(st, k, nullptr, nullptr, nullptr, s.codes.data(), s.offs.data(), &s.quals[0], &s.names[0], s.noffs.data()) != H2G_OK) die("h2g_fetch_read_set");
+			s.raw.clear(); s.raw_n = 0;
+		}
+		ndevice_parsed += it.n;
+		return true;
+	}
 	// fetch the item that stream `g` carries into a pinned set and hand it to the formatter
 	void complete(int g) {
 		Str& sg = S_[(size_t)g];
@@ -1176,7 +1219,7 @@ int main(int argc, char** argv) {
 	h2g_sam_set_no_unal(sam, o.no_unal && !drop_unal ? 1 : 0);
 	// (-s / -u: the record stream skips and counts, Source::next; -u counts the reads after the skipped ones, qUpto += skipReads hisat2.cpp:1959-1963)
 	std::unique_ptr<Source> src_owner(o.windows ? new Source(wp.plan, wp.first, wp.n)
-	                                            : new Source(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, o.sorting, o.skip, o.upto));
+	                                            : new Source(o.m1, o.m2, o.u, o.m12, o.fmt, o.threads, o.trim5, o.trim3, o.qcoding, o.sorting, o.skip, o.upto, o.device_parse));
 	Source& src = *src_owner;
 	ReadSorter sorter;
 	for(int k = 0; k < RS_KINDS; k++) if(!o.rs_arg[k].empty()) sorter.open(k, o.rs_arg[k], o.rs_gz[k]);
@@ -1188,7 +1231,7 @@ int main(int argc, char** argv) {
 	TextWriter writer(out);
 	ParseStage parse(src, H, batch, wv, ix.streams());
 	FormatStage fmt(FormatStage::Config{async_fmt, o.qc_filter, drop_unal, wv.temp_ss, merge_sites, !o.quiet, P.khits, o.device_sam, o.device_plan}, sam, parse, writer, sorter, sites, ix);
-	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch, wp.plan}, P, wv, ix, parse, fmt);
+	DeviceStage dev(DeviceStage::Config{o.qc_filter, o.arbitrary_random, batch, wp.plan, o.device_parse ? src.any_reader() : nullptr, o.trim5, o.trim3, o.qcoding.phred64}, P, wv, ix, parse, fmt);
 	double t_parse = 0;                                   // what the main thread waited for the parser
 	bool short_mates = false;
 	for(long k = 0;; k++) {
@@ -1220,9 +1263,9 @@ int main(int argc, char** argv) {
 	        t_parse, parse.busy(), tot.t_fmt, t2 - t0, dev.t_stream, dev.t_up, dev.t_fetch);
 	if(!o.stats_fn.empty()) {
 		FILE* sf = fopen(o.stats_fn.c_str(), "w");
-		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu, \"device_sam_lines\": %llu, \"whole_lines\": %llu, \"device_planned\": %llu, \"host_planned\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
+		if(sf) { fprintf(sf, "{\"reads\": %llu, \"second_pass\": %llu, \"overflow\": %llu, \"runs\": %llu, \"fast\": %llu, \"handed_on\": %llu, \"device_sam_lines\": %llu, \"whole_lines\": %llu, \"device_planned\": %llu, \"host_planned\": %llu, \"device_parsed\": %llu, \"host_parsed\": %llu}\n", (unsigned long long)tot.nreads, (unsigned long long)dev.nsecond, (unsigned long long)tot.novf, (unsigned long long)dev.nruns,
 		                 (unsigned long long)dev.nfast, (unsigned long long)dev.nhanded, (unsigned long long)tot.device_sam_lines, (unsigned long long)tot.whole_lines,
-		                 (unsigned long long)tot.device_planned, (unsigned long long)tot.host_planned); fclose(sf); }
+		                 (unsigned long long)tot.device_planned, (unsigned long long)tot.host_planned, (unsigned long long)dev.ndevice_parsed, (unsigned long long)dev.nhost_parsed); fclose(sf); }
 	}
 	// (Measured and not shipped, round 6: ending the process here without the frees below saves this run 0.1 s and costs the NEXT process 1.7 s — the driver reclaims 40 GB of
 	// device memory of a process that did not return it while the next one is already allocating: profiles/r06_zc_ab.log.)

@@ -29,8 +29,15 @@ struct Batch {
 	std::vector<uint8_t>  filt;                  // QSEQ sources only, one per read: 0 = the record's filter field is '0' (--qc-filter), 1 = it passes
 	std::string           orig;                  // --un / --al ...: the records' text as it stood in the input, record i = [ooffs[i], ooffs[i + 1]); kept only when asked for
 	std::vector<uint64_t> ooffs;
+	// --h2g-device-parse: the FASTQ text of the batch's raw_n records for h2g_set_reads_fastq, every record exactly four lines: a file's last record is cut behind its fourth
+	// line (blank lines behind it are not the record's) and, where the file ends earlier, filled up with '\n' — raw_short then has (record, its bytes in the file), so that the
+	// host parser sees it as it stood.  The arrays above are filled from the device afterwards.  raw_first: the running number of its first record (the name of a record without one)
+	std::string           raw;
+	size_t                raw_n = 0;
+	uint64_t              raw_first = 0;
+	std::vector<std::pair<size_t, size_t> > raw_short;
 	size_t n() const { return offs.empty() ? 0 : offs.size() - 1; }
-	void clear() { codes.clear(); offs.assign(1, 0); noffs.assign(1, 0); quals.clear(); names.clear(); filt.clear(); orig.clear(); ooffs.assign(1, 0); }
+	void clear() { codes.clear(); offs.assign(1, 0); noffs.assign(1, 0); quals.clear(); names.clear(); filt.clear(); orig.clear(); ooffs.assign(1, 0); raw.clear(); raw_n = 0; raw_first = 0; raw_short.clear(); }
 	// appends the reads of `pb` (parsed with the same options)
 	void append(const Batch& pb) {
 		const uint32_t cb = (uint32_t)codes.size(), nb = (uint32_t)names.size();
@@ -143,6 +150,19 @@ public:
 		while(got < max) {
 			if(cur_ >= nrec()) { if(!next_file()) break; continue; }
 			const size_t take = std::min(max - got, nrec() - cur_);
+			if(raw_) {      // the records' bytes travel as they are; records of two files are concatenated
+				if(b.raw_n == 0) b.raw_first = count_;
+				size_t end = starts_[cur_ + take], lines = 4;
+				if(cur_ + take == nrec()) {      // the file's last record ends behind its fourth line, or with the file
+					lines = 0;
+					for(end = starts_[nrec() - 1]; end < n_ && lines < 4; end++) lines += p_[end] == '\n';
+				}
+				b.raw.append(p_ + starts_[cur_], end - starts_[cur_]);
+				b.raw_n += take;
+				if(lines < 4) { b.raw_short.emplace_back(b.raw_n - 1, end - starts_[nrec() - 1]); b.raw.append(4 - lines, '\n'); }
+				cur_ += take; got += take; count_ += take;
+				continue;
+			}
 			const size_t T = std::min<size_t>((size_t)T_, take / 4096 + 1);
 			std::vector<Batch> part(T), part2(tabbed ? T : 0);
 			std::vector<std::vector<uint8_t> > pk(tabbed ? T : 0);
@@ -171,6 +191,28 @@ public:
 			cur_ += take; got += take; count_ += take;
 		}
 		return got;
+	}
+	// the records of b.raw through parse_record, under this reader's options: what fill() would have made of them (the names of records without one and the
+	// messages of malformed ones included).  For the items h2g_set_reads_fastq hands back to the host, and for the records -s skips.  max: the first so many records only
+	// (a -2 file may hold more records than its -1 file: nobody looks at them)
+	void parse_raw(Batch& b, size_t max = ~(size_t)0) const {
+		Reader t(std::vector<std::string>(), fmt_, 1, trim5_, trim3_);
+		t.qc_ = qc_;
+		std::string text;
+		text.swap(b.raw);
+		const uint64_t first = b.raw_first;
+		std::vector<std::pair<size_t, size_t> > shorter;
+		shorter.swap(b.raw_short);
+		b.clear();
+		b.have_quals = true;
+		t.p_ = text.data(); t.n_ = text.size(); t.count_ = first;
+		size_t line = 0;
+		if(t.n_) t.starts_.push_back(0);
+		for(size_t i = 0; i < t.n_; i++) if(t.p_[i] == '\n') { line++; if((line & 3) == 0) t.starts_.push_back(i + 1); }      // (every record of the text is four lines)
+		t.ends_.assign(t.starts_.begin() + (t.starts_.empty() ? 0 : 1), t.starts_.end());
+		for(const auto& x : shorter) if(x.first < t.ends_.size()) t.ends_[x.first] = t.starts_[x.first] + x.second;
+		for(size_t r = 0; r < t.nrec() && r < max; r++) t.parse_record(r, b);
+		t.p_ = nullptr; t.starts_.clear();                                                  // (the text is not a mapped file)
 	}
 private:
 	size_t nrec() const { return starts_.empty() ? 0 : starts_.size() - 1; }
@@ -268,7 +310,7 @@ private:
 	}
 	void parse_record(size_t r, Batch& b) const {
 		const char* q = p_ + starts_[r];
-		const char* end = p_ + starts_[r + 1];
+		const char* end = p_ + (ends_.empty() ? starts_[r + 1] : ends_[r]);
 		q++;                                                         // '>' or '@'
 		const char* nm = q;
 		while(q < end && *q != '\n') q++;
@@ -405,6 +447,7 @@ private:
 public:
 	QualCoding qc_;
 	bool keep_orig_ = false;        // --un / --al ...: the batches carry the records' original text
+	bool raw_ = false;              // --h2g-device-parse (FASTQ): fill() hands on the records' bytes (Batch::raw) instead of parsing them
 private:
 	std::vector<std::string> files_;
 	ReadFormat fmt_;
@@ -415,6 +458,7 @@ private:
 	const char* p_ = nullptr;
 	size_t n_ = 0, cur_ = 0;
 	std::vector<size_t> starts_;
+	std::vector<size_t> ends_;      // parse_raw only: where record r ends when that is not where record r + 1 starts
 	std::vector<char> inflated_;
 	uint64_t count_ = 0;
 };
@@ -439,8 +483,8 @@ struct Win {
 class Source {
 public:
 	Source(const std::vector<std::string>& m1, const std::vector<std::string>& m2, const std::vector<std::string>& u, const std::vector<std::string>& tab,
-	       ReadFormat fmt, int threads, uint32_t trim5, uint32_t trim3, const QualCoding& qc, bool keep_orig, uint64_t skip, uint64_t upto) : skip_(skip), upto_(upto) {
-		auto mk = [&](const std::vector<std::string>& files) { Reader* r = new Reader(files, fmt, threads, trim5, trim3); r->qc_ = qc; r->keep_orig_ = keep_orig; return r; };
+	       ReadFormat fmt, int threads, uint32_t trim5, uint32_t trim3, const QualCoding& qc, bool keep_orig, uint64_t skip, uint64_t upto, bool raw = false) : skip_(skip), upto_(upto) {
+		auto mk = [&](const std::vector<std::string>& files) { Reader* r = new Reader(files, fmt, threads, trim5, trim3); r->qc_ = qc; r->keep_orig_ = keep_orig; r->raw_ = raw && fmt == FMT_FASTQ; return r; };
 		if(!tab.empty()) segs_.push_back(Seg{mk(tab), nullptr, true});
 		else {
 			if(!m1.empty() && !m2.empty()) segs_.push_back(Seg{mk(m1), mk(m2), false});
@@ -452,6 +496,8 @@ public:
 	~Source() { for(Seg& s : segs_) { delete s.a; delete s.b; } }
 	Source(const Source&) = delete;
 	bool short_mates() const { return short_mates_; }         // the -2 files ran out before the -1 files
+	// the reader whose options a batch's raw text is parsed under when the device hands it back (every reader of a source has the same)
+	const Reader* any_reader() const { return segs_.empty() ? nullptr : segs_[0].a; }
 	bool next(Win& w, size_t max) {
 		w.a.clear(); w.b.clear(); w.kinds.clear(); w.n = w.npairs = 0; w.skipped = 0; w.paired = false;
 		w.wsegs.clear(); w.ids64.clear();
@@ -466,12 +512,13 @@ public:
 					ja.clear(); jb.clear(); jk.clear();
 					const size_t g = fill(s, ja, jb, jk, (size_t)std::min<uint64_t>(left, 1u << 20));
 					if(!g) break;
+					parse_if_raw(s, ja, jb, g);                     // (no device sees them: a malformed one among them ends the run as it does without --h2g-device-parse)
 					left -= g; s.id += g; w.skipped += g;
 				}
 			}
 			if(s.budget == 0) {                                   // -u reached: with records left here the run ends, else the next segment starts
 				ja.clear(); jb.clear();
-				if(fill(s, ja, jb, jk, 1)) { si_ = segs_.size(); return false; }
+				if(fill(s, ja, jb, jk, 1)) { parse_if_raw(s, ja, jb, 1); si_ = segs_.size(); return false; }
 				si_++;
 				continue;
 			}
@@ -528,6 +575,11 @@ private:
 		tb.join();
 		if(nb < n) short_mates_ = true;                           // (-2 ran out before -1: the reference's error; a longer -2 is not looked at)
 		return n;
+	}
+	// --h2g-device-parse: records that are read and dropped (-s, the probe behind -u) go through the host parser, as they do without the flag
+	static void parse_if_raw(const Seg& s, Batch& a, Batch& b, size_t n) {
+		if(a.raw_n) s.a->parse_raw(a, n);
+		if(s.b && b.raw_n) s.b->parse_raw(b, n);
 	}
 	std::vector<Seg> segs_;
 	size_t si_ = 0;

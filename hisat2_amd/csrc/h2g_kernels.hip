@@ -25,6 +25,7 @@
 #include "h2g_splice_host.h"
 #include "h2g_splice_db_host.h"
 #include "h2g_windows.h"   // the -F window expansion's per-read arithmetic
+#include "h2g_fastq.h"     // the record arithmetic of FASTQ parsing on the device
 #include "h2g_sam_line.h"  // the SAM line emitter the text kernels and the host share
 #include "h2g_sam_plan.h"  // the planner of plain SAM lines the kernels and the host share
 #include <chrono>
@@ -251,10 +252,11 @@ struct h2g_stream {
 	hipEvent_t ev_plan[4] = {nullptr, nullptr, nullptr, nullptr};
 	h2g_sam_plan_stats plan_stats = {};
 	std::vector<uint8_t> plan_classes;
-	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows)
+	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows / h2g_set_reads_fastq)
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
 	h2g_windows_stats win_stats = {};           // of the last h2g_set_reads_windows
+	h2g_fastq_stats fq_stats = {};              // of the last h2g_set_reads_fastq
 	unsigned long long* d_warm_cnt = nullptr;   // counter block of the machine streams' empty first launches (go_warmup); word H2G_CNT_NO_SECOND, which nobody writes, is their list's count
 	uint8_t* d_warm_rows = nullptr;             // ... and the result rows they are given: never the current batch's
 };
@@ -3349,6 +3351,308 @@ static int compact_offsets(h2g_stream* s, const h2g_alnres* d_src, uint32_t slot
 		hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, v, n1, (const unsigned long long*)ts);
 	}
 	HIPCHK(hipGetLastError());
+	return H2G_OK;
+}
+
+// ------------------------------------------------------------------------------------------ FASTQ records parsed on the device
+// The text of one mate -> the batch's codes, qualities, names and their offsets.  The record arithmetic (what a plain record is, its outputs in closed form, the cursor over
+// output bytes) is h2g_fastq.h's; the kernels are the loads, the scans and the stores around it.
+// 1. newlines: a lane loads 16 consecutive bytes (one dwordx4, 1 KB contiguous per wave) and counts its '\n'; a workgroup (4 KB of text) leaves one count
+__global__ __launch_bounds__(256) void k_fq_count(const uint8_t* __restrict__ text, uint32_t n_text, unsigned long long* __restrict__ blk) {
+	__shared__ uint32_t part[4];
+	const uint64_t b0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+	uint32_t c = 0;
+	if(b0 < n_text) {
+		const uint4 v = *(const uint4*)(text + b0);
+		const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+		c = h2g_fq::popc16(h2g_fq::nl_mask16(w, n_text - b0 < 16 ? (uint32_t)(n_text - b0) : 16u));
+	}
+	for(int d = 32; d; d >>= 1) c += __shfl_xor(c, d);
+	if((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+	__syncthreads();
+	if(threadIdx.x == 0) blk[blockIdx.x] = (unsigned long long)part[0] + part[1] + part[2] + part[3];
+}
+// ... and, once the workgroups' counts are scanned (k_scan_*), every newline's index follows from a scan across the wave and the workgroup: nlpos[j] = position of newline j, j < cap
+__global__ __launch_bounds__(256) void k_fq_lines(const uint8_t* __restrict__ text, uint32_t n_text, const unsigned long long* __restrict__ blk, uint32_t* __restrict__ nlpos, uint64_t cap) {
+	__shared__ uint32_t part[4];
+	const uint64_t b0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint32_t mask = 0;
+	if(b0 < n_text) {
+		const uint4 v = *(const uint4*)(text + b0);
+		const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+		mask = h2g_fq::nl_mask16(w, n_text - b0 < 16 ? (uint32_t)(n_text - b0) : 16u);
+	}
+	const uint32_t c = h2g_fq::popc16(mask);
+	uint32_t incl = c;
+	for(uint32_t d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if(lane >= d) incl += t; }
+	if(lane == 63) part[wave] = incl;
+	__syncthreads();
+	uint64_t idx = blk[blockIdx.x] + (incl - c);
+	for(uint32_t k = 0; k < wave; k++) idx += part[k];
+	for(uint32_t m = mask; m; m &= m - 1, idx++) if(idx < cap) nlpos[idx] = (uint32_t)b0 + (uint32_t)(__ffs(m) - 1);
+}
+// 2. one lane per record: its four lines, the predicate, its lengths, sources and plain bit; lane n closes the two size arrays.  res: {not plain, first not plain, longest L}
+__global__ __launch_bounds__(256) void k_fq_table(const char* __restrict__ text, uint32_t n_text, const uint32_t* __restrict__ nlpos, uint64_t n_nl_known, uint32_t n, h2g_fq::Opts o,
+                                                  unsigned long long* __restrict__ lsz, unsigned long long* __restrict__ nsz, uint32_t* __restrict__ src, uint8_t* __restrict__ bits,
+                                                  const uint8_t* __restrict__ prev /* mate 1's bits when this is mate 2: a record is counted once */, uint32_t* __restrict__ res)
+{
+	__shared__ uint32_t sbad, sfirst, smax;
+	if(threadIdx.x == 0) { sbad = 0; sfirst = 0xffffffffu; smax = 0; }
+	__syncthreads();
+	const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if(r < n) {
+		const h2g_fq::Rec x = h2g_fq::eval_record(text, h2g_fq::record_lines(nlpos, n_nl_known, n_text, r), o);
+		lsz[r] = x.L; nsz[r] = x.name_len;
+		src[r] = x.name_src; src[(uint64_t)n + r] = x.seq_src; src[2ull * n + r] = x.qual_src;
+		bits[r] = (uint8_t)x.plain;
+		if(!x.plain) { if(!prev || prev[r]) atomicAdd(&sbad, 1u); atomicMin(&sfirst, (uint32_t)r); }
+		else atomicMax(&smax, x.L);
+	} else if(r == n) { lsz[r] = 0; nsz[r] = 0; }
+	__syncthreads();
+	if(threadIdx.x == 0) {
+		if(sbad) atomicAdd(&res[0], sbad);
+		if(sfirst != 0xffffffffu) atomicMin(&res[1], sfirst);
+		if(smax) atomicMax(&res[2], smax);
+	}
+}
+// 3. (k_scan_* over both size arrays) the batch's 32-bit offsets
+__global__ __launch_bounds__(256) void k_fq_offs(const unsigned long long* __restrict__ lsz, const unsigned long long* __restrict__ nsz, uint32_t n, uint32_t* __restrict__ offs, uint32_t* __restrict__ name_offs) {
+	const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if(r <= n) { offs[r] = (uint32_t)lsz[r]; name_offs[r] = (uint32_t)nsz[r]; }
+}
+// 4. a lane owns 16 consecutive OUTPUT bytes and stores them as one dwordx4 (k_win_codes' scheme): its record by binary search over the scanned lengths, then the cursor walks across
+// records.  SEQ: codes and qualities share their offsets, so one pass writes both; else the names, by the same cursor over their own offsets.  The sources are byte gathers from the text.
+template<bool SEQ> __global__ __launch_bounds__(256) void k_fq_write(const uint8_t* __restrict__ text, const unsigned long long* __restrict__ offs, const uint32_t* __restrict__ src_a,
+                                                                     const uint32_t* __restrict__ src_b, uint32_t n, uint64_t n_bytes, uint32_t phred64, uint8_t* __restrict__ out_a, uint8_t* __restrict__ out_b)
+{
+	const uint64_t chunks = (n_bytes + 15) / 16;
+	for(uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t b0 = c * 16;
+		const uint32_t m = n_bytes - b0 < 16 ? (uint32_t)(n_bytes - b0) : 16u;      // (the bytes past the end of the last chunk are written as 0: the buffers have 64 spare)
+		h2g_fq::Cursor cur;
+		cur.seek(offs, src_a, n, b0);
+		uint32_t wa[4] = {0, 0, 0, 0}, wb[4] = {0, 0, 0, 0};
+		uint32_t last = 0xffffffffu, delta = 0;
+#pragma unroll
+		for(uint32_t k = 0; k < 16; k++) if(k < m) {
+			if(SEQ && cur.r != last) { last = cur.r; delta = src_b[last] - src_a[last]; }
+			const uint32_t at = cur.next();
+			if(SEQ) {
+				wa[k >> 2] |= (uint32_t)h2g_fq::fq_code(text[at]) << (8 * (k & 3));
+				wb[k >> 2] |= (uint32_t)(uint8_t)h2g_fq::fq_qual(text[at + delta], phred64) << (8 * (k & 3));
+			} else wa[k >> 2] |= (uint32_t)text[at] << (8 * (k & 3));
+		}
+		*(uint4*)(out_a + b0) = make_uint4(wa[0], wa[1], wa[2], wa[3]);
+		if(SEQ) *(uint4*)(out_b + b0) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+	}
+}
+
+static void scan64(h2g_stream* s, unsigned long long* v, size_t n1) {      // exclusive, in place; the tile sums live behind v[0 .. n1)
+	const size_t ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
+	unsigned long long* ts = v + n1;
+	hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, s->st, v, n1, ts);
+	hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, s->st, ts, ntiles);
+	hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, v, n1, (const unsigned long long*)ts);
+}
+static size_t scan64_bytes(size_t n1) { return (n1 + n1 / H2G_SCAN_TILE + 2) * 8; }
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size_t n1, const char* text2, size_t n2, const h2g_fastq_opts* opts, h2g_fastq_result* out) {
+	if(s) HIPCHK(sync_all(s));        // (a machine pass of the previous batch may still read the buffers this call replaces)
+	if(!s || !opts || !out || (!text1 && n1) || (!text2 && n2)) return H2G_ERR_ARG;
+	memset(out, 0, sizeof *out);
+	s->tmp_gen++;
+	BatchCtx& B = s->cur();
+	// whatever happens below, the batch holds no read of its former set
+	B.n_reads = 0; B.max_read_len = 0;
+	B.has_quals = B.has_quals2 = B.has_names = B.has_mates = false;
+	B.has_seeds = B.has_seeds2 = false; B.has_qc = false; B.has_ids = false;
+	s->ledits_touched = 0;
+	s->fq_stats = h2g_fastq_stats{};
+	const int M = text2 ? 2 : 1;
+	const char* text[2] = {text1, text2};
+	const size_t nt[2] = {n1, n2};
+	const bool fin[2] = {opts->final1 != 0, opts->final2 != 0};
+	if(n1 >= (1ull << 32) || n2 >= (1ull << 32)) { snprintf(g_err, sizeof g_err, "h2g_set_reads_fastq: a text of 4 GB or more (offsets into it are 32 bits)"); return H2G_ERR_ARG; }
+	HIPCHK(hipSetDevice(s->ix->device));
+	float ms = 0, ms_total = 0;
+	// ---- phase A: the texts, their newlines per 4 KB, the scan -> how many records there are
+	uint8_t* d_text[2] = {nullptr, nullptr};
+	size_t nblk[2] = {0, 0}, cnt_at[2] = {0, 0};
+	for(int m = 0; m < M; m++) { nblk[m] = (nt[m] + 4095) / 4096; cnt_at[m] = m ? up16(scan64_bytes(nblk[0] + 1)) : 0; }
+	void* d_cnt;
+	int rc;
+	for(int m = 0; m < M; m++) { void* p; if((rc = tmp_buf(s, m, nt[m] + 16, &p))) return (h2g_status)rc; d_text[m] = (uint8_t*)p; }
+	if((rc = tmp_buf(s, 2, cnt_at[M - 1] + scan64_bytes(nblk[M - 1] + 1), &d_cnt))) return (h2g_status)rc;
+	for(int m = 0; m < M; m++) if(nt[m]) HIPCHK(hipMemcpyAsync(d_text[m], text[m], nt[m], hipMemcpyHostToDevice, s->st));
+	unsigned long long nl[2] = {0, 0};
+	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	for(int m = 0; m < M; m++) {
+		unsigned long long* v = (unsigned long long*)((uint8_t*)d_cnt + cnt_at[m]);
+		HIPCHK(hipMemsetAsync(v + nblk[m], 0, 8, s->st));
+		if(nblk[m]) hipLaunchKernelGGL(k_fq_count, dim3((unsigned)nblk[m]), dim3(256), 0, s->st, (const uint8_t*)d_text[m], (uint32_t)nt[m], v);
+		scan64(s, v, nblk[m] + 1);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	for(int m = 0; m < M; m++) HIPCHK(hipMemcpyAsync(&nl[m], (unsigned long long*)((uint8_t*)d_cnt + cnt_at[m]) + nblk[m], 8, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(sync_all(s));
+	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	// whole records, and the one a text that ends the input may still hold behind them (h2g_fastq.h)
+	uint64_t n = opts->max_records ? opts->max_records : UINT64_MAX;
+	for(int m = 0; m < M; m++) {
+		const bool rest = nl[m] % 4 != 0 || (nt[m] && text[m][nt[m] - 1] != '\n');
+		n = std::min<uint64_t>(n, h2g_fq::whole_records(nl[m]) + (fin[m] && rest ? 1 : 0));
+	}
+	out->n_records = n;
+	out->first_not_plain = UINT64_MAX;
+	s->fq_stats.bytes_uploaded = n1 + n2;
+	if(n == 0) { out->first_not_plain = 0; s->fq_stats.kernel_ms = ms_total; return H2G_OK; }
+	// ---- phase B: line starts, the per-record table, the scans of the lengths
+	struct Lay { size_t nlpos, lsz, nsz, src, bits, res; } lay[2];
+	size_t at = 0;
+	for(int m = 0; m < M; m++) {
+		Lay& l = lay[m];
+		l.nlpos = at; at = up16(at + (4 * n + 1) * 4);
+		l.lsz = at;   at = up16(at + scan64_bytes(n + 1));
+		l.nsz = at;   at = up16(at + scan64_bytes(n + 1));
+		l.src = at;   at = up16(at + 3 * n * 4);
+		l.bits = at;  at = up16(at + n);
+		l.res = at;   at = up16(at + 16);
+	}
+	void* d_tab;
+	if((rc = tmp_buf(s, 3, at, &d_tab))) return (h2g_status)rc;
+	uint8_t* T = (uint8_t*)d_tab;
+	const h2g_fq::Opts fo = {opts->trim5, opts->trim3, opts->phred64 ? 1u : 0u};
+	static const uint32_t res0[4] = {0, 0xffffffffu, 0, 0};
+	uint32_t hres[2][4];
+	unsigned long long tot_l[2] = {0, 0}, tot_n[2] = {0, 0};
+	uint32_t last_nl[2] = {0, 0};
+	uint64_t known[2];
+	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	for(int m = 0; m < M; m++) {
+		const Lay& l = lay[m];
+		known[m] = std::min<uint64_t>(nl[m], 4 * n);
+		HIPCHK(hipMemcpyAsync(T + l.res, res0, 16, hipMemcpyHostToDevice, s->st));
+		const unsigned long long* v = (const unsigned long long*)((uint8_t*)d_cnt + cnt_at[m]);
+		hipLaunchKernelGGL(k_fq_lines, dim3((unsigned)nblk[m]), dim3(256), 0, s->st, (const uint8_t*)d_text[m], (uint32_t)nt[m], v, (uint32_t*)(T + l.nlpos), known[m]);
+		hipLaunchKernelGGL(k_fq_table, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, (const char*)d_text[m], (uint32_t)nt[m], (const uint32_t*)(T + l.nlpos), known[m], (uint32_t)n, fo,
+		                   (unsigned long long*)(T + l.lsz), (unsigned long long*)(T + l.nsz), (uint32_t*)(T + l.src), T + l.bits,
+		                   m ? (const uint8_t*)(T + lay[0].bits) : (const uint8_t*)nullptr, (uint32_t*)(T + l.res));
+		scan64(s, (unsigned long long*)(T + l.lsz), n + 1);
+		scan64(s, (unsigned long long*)(T + l.nsz), n + 1);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	for(int m = 0; m < M; m++) {
+		const Lay& l = lay[m];
+		HIPCHK(hipMemcpyAsync(hres[m], T + l.res, 16, hipMemcpyDeviceToHost, s->st));
+		HIPCHK(hipMemcpyAsync(&tot_l[m], (unsigned long long*)(T + l.lsz) + n, 8, hipMemcpyDeviceToHost, s->st));
+		HIPCHK(hipMemcpyAsync(&tot_n[m], (unsigned long long*)(T + l.nsz) + n, 8, hipMemcpyDeviceToHost, s->st));
+		if(known[m] == 4 * n) HIPCHK(hipMemcpyAsync(&last_nl[m], (uint32_t*)(T + l.nlpos) + (4 * n - 1), 4, hipMemcpyDeviceToHost, s->st));
+	}
+	HIPCHK(sync_all(s));
+	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	s->fq_stats.kernel_ms = ms_total;
+	const uint64_t consumed[2] = {known[0] == 4 * n ? (uint64_t)last_nl[0] + 1 : n1, M == 2 ? (known[1] == 4 * n ? (uint64_t)last_nl[1] + 1 : n2) : 0};
+	out->consumed1 = consumed[0]; out->consumed2 = consumed[1];
+	out->n_bases1 = tot_l[0]; out->n_bases2 = tot_l[1];
+	out->n_name_bytes1 = tot_n[0]; out->n_name_bytes2 = tot_n[1];
+	out->n_not_plain = (uint64_t)hres[0][0] + (M == 2 ? hres[1][0] : 0u);      // (mate 2's count leaves out the records mate 1 counted)
+	out->max_read_len = std::max(hres[0][2], M == 2 ? hres[1][2] : 0u);
+	if(out->n_not_plain) { out->first_not_plain = std::min(hres[0][1], M == 2 ? hres[1][1] : 0xffffffffu); return H2G_OK; }
+	out->first_not_plain = n;
+	if(n > s->max_reads || tot_l[0] > s->max_bases || tot_l[1] > s->max_bases || tot_n[0] > 0xffffffffull || tot_n[1] > 0xffffffffull) {
+		snprintf(g_err, sizeof g_err, "h2g_set_reads_fastq: %llu records of %llu / %llu bases exceed the stream's %zu reads / %zu bases, or their names 4 GB", (unsigned long long)n,
+		         tot_l[0], tot_l[1], s->max_reads, s->max_bases);
+		return H2G_ERR_ARG;
+	}
+	// ---- phase C: the batch's arrays
+	if(B.names_cap < tot_n[0] || !B.d_name_offs) {      // (grows as h2g_set_read_names does)
+		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
+		B.d_names = nullptr; B.d_name_offs = nullptr; B.names_cap = 0;
+		HIPCHK(hipMalloc((void**)&B.d_names, tot_n[0] + 64));
+		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
+		B.names_cap = tot_n[0];
+	}
+	if(M == 2) {                                        // (as h2g_set_mates does)
+		if(!B.d_codes2) {
+			HIPCHK(hipMalloc((void**)&B.d_codes2, s->max_bases + 64));
+			HIPCHK(hipMalloc((void**)&B.d_quals2, s->max_bases + 64));
+			HIPCHK(hipMalloc((void**)&B.d_offs2, (s->max_reads + 1) * 4));
+			HIPCHK(hipMalloc((void**)&B.d_name_offs2, (s->max_reads + 1) * 4));
+		}
+		(void)hipFree(B.d_names2); B.d_names2 = nullptr;
+		HIPCHK(hipMalloc((void**)&B.d_names2, tot_n[1] + 64));
+	}
+	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	for(int m = 0; m < M; m++) {
+		const Lay& l = lay[m];
+		const unsigned long long* lsz = (const unsigned long long*)(T + l.lsz);
+		const unsigned long long* nsz = (const unsigned long long*)(T + l.nsz);
+		const uint32_t* src = (const uint32_t*)(T + l.src);
+		uint8_t* codes = m ? B.d_codes2 : B.d_codes;
+		uint8_t* quals = (uint8_t*)(m ? B.d_quals2 : B.d_quals);
+		uint8_t* names = (uint8_t*)(m ? B.d_names2 : B.d_names);
+		hipLaunchKernelGGL(k_fq_offs, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, lsz, nsz, (uint32_t)n, m ? B.d_offs2 : B.d_offs, m ? B.d_name_offs2 : B.d_name_offs);
+		if(tot_l[m]) hipLaunchKernelGGL(k_fq_write<true>, dim3(grid_for((tot_l[m] + 15) / 16, 256)), dim3(256), 0, s->st, (const uint8_t*)d_text[m], lsz, src + n, src + 2 * n, (uint32_t)n, (uint64_t)tot_l[m],
+		                                fo.phred64, codes, quals);
+		if(tot_n[m]) hipLaunchKernelGGL(k_fq_write<false>, dim3(grid_for((tot_n[m] + 15) / 16, 256)), dim3(256), 0, s->st, (const uint8_t*)d_text[m], nsz, src, (const uint32_t*)nullptr, (uint32_t)n,
+		                                (uint64_t)tot_n[m], 0u, names, (uint8_t*)nullptr);
+		s->fq_stats.bytes_written += 2 * tot_l[m] + tot_n[m] + 2 * (n + 1) * 4;
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(sync_all(s));
+	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	s->fq_stats.kernel_ms = ms_total;
+	B.n_reads = n;
+	B.max_read_len = out->max_read_len;
+	B.has_quals = true;
+	B.has_names = true;
+	B.has_mates = M == 2;
+	B.has_quals2 = M == 2;
+	return H2G_OK;
+}
+extern "C" h2g_status h2g_get_fastq_stats(h2g_stream* s, h2g_fastq_stats* out) {
+	if(!s || !out) return H2G_ERR_ARG;
+	*out = s->fq_stats;
+	return H2G_OK;
+}
+
+extern "C" h2g_status h2g_fetch_read_set(h2g_stream* s, int mate, size_t* n_reads, size_t* n_bases, size_t* n_name_bytes, uint8_t* codes, uint32_t* offs, char* quals, char* names,
+                                         uint32_t* name_offs)
+{
+	if(!s || mate < 0 || mate > 1) return H2G_ERR_ARG;
+	HIPCHK(sync_all(s));
+	const BatchCtx& B = s->cur();
+	const size_t n = B.n_reads;
+	if(n_reads) *n_reads = n;
+	if(n_bases) *n_bases = 0;
+	if(n_name_bytes) *n_name_bytes = 0;
+	if(n == 0) return H2G_OK;
+	if(mate == 1 && !B.has_mates) return H2G_ERR_ARG;
+	const uint8_t* dc = mate ? B.d_codes2 : B.d_codes;
+	const uint32_t* dof = mate ? B.d_offs2 : B.d_offs;
+	const char* dq = mate ? B.d_quals2 : B.d_quals;
+	const char* dn = mate ? B.d_names2 : B.d_names;
+	const uint32_t* dno = mate ? B.d_name_offs2 : B.d_name_offs;
+	const bool hq = mate ? B.has_quals2 : B.has_quals, hn = mate ? true : B.has_names;
+	uint32_t nb = 0, nn = 0;
+	HIPCHK(hipSetDevice(s->ix->device));
+	HIPCHK(hipMemcpyAsync(&nb, dof + n, 4, hipMemcpyDeviceToHost, s->st));
+	if(hn) HIPCHK(hipMemcpyAsync(&nn, dno + n, 4, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipStreamSynchronize(s->st));
+	if(n_bases) *n_bases = nb;
+	if(n_name_bytes) *n_name_bytes = nn;
+	if((quals && !hq) || ((names || name_offs) && !hn)) return H2G_ERR_ARG;
+	if(codes && nb) HIPCHK(hipMemcpyAsync(codes, dc, nb, hipMemcpyDeviceToHost, s->st));
+	if(offs) HIPCHK(hipMemcpyAsync(offs, dof, (n + 1) * 4, hipMemcpyDeviceToHost, s->st));
+	if(quals && nb) HIPCHK(hipMemcpyAsync(quals, dq, nb, hipMemcpyDeviceToHost, s->st));
+	if(names && nn) HIPCHK(hipMemcpyAsync(names, dn, nn, hipMemcpyDeviceToHost, s->st));
+	if(name_offs) HIPCHK(hipMemcpyAsync(name_offs, dno, (n + 1) * 4, hipMemcpyDeviceToHost, s->st));
+	HIPCHK(hipStreamSynchronize(s->st));
 	return H2G_OK;
 }
 

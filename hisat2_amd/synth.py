@@ -249,6 +249,35 @@ def write_reads_fasta(path, reads, start_id=0):
             f.write(txt[i].tobytes() + b"\n")
 
 
+def write_reads_fastq(path, reads, start_id=0, seed=0, suffix=b""):
+    """reads[n, L] as FASTQ records "@<id><suffix>" with seeded Phred+33 qualities in [2, 41]; written a decimal width of ids at a time, without a loop over the reads"""
+    n, L = reads.shape
+    rng = np.random.default_rng(seed)
+    suf = np.frombuffer(bytes(suffix), dtype=np.uint8)
+    with open(path, "wb") as f:
+        lo = 0
+        while lo < n:
+            w = len(str(start_id + lo))
+            hi = min(n, 10 ** w - start_id, lo + (1 << 20))
+            m = hi - lo
+            ids = np.arange(start_id + lo, start_id + hi, dtype=np.int64)
+            rec = np.empty((m, 1 + w + len(suf) + 1 + L + 3 + L + 1), dtype=np.uint8)
+            rec[:, 0] = ord("@")
+            for k in range(w):
+                rec[:, 1 + k] = ord("0") + (ids // 10 ** (w - 1 - k)) % 10
+            at = 1 + w
+            rec[:, at:at + len(suf)] = suf
+            at += len(suf)
+            rec[:, at] = 10
+            rec[:, at + 1:at + 1 + L] = _ALPHA[reads[lo:hi]]
+            at += 1 + L
+            rec[:, at:at + 3] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+            rec[:, at + 3:at + 3 + L] = rng.integers(35, 75, size=(m, L), dtype=np.uint8)
+            rec[:, at + 3 + L] = 10
+            f.write(rec.tobytes())
+            lo = hi
+
+
 def flatten_reads(reads):
     """(codes flat uint8, offsets uint32[n+1]) layout used by the C-ABI."""
     n, L = reads.shape

@@ -468,6 +468,29 @@ H2G_EXPORT h2g_status h2g_get_windows_stats(h2g_stream*, h2g_windows_stats* out)
  * sizes the second; any pointer may be NULL. */
 H2G_EXPORT h2g_status h2g_fetch_reads(h2g_stream*, size_t* n_reads, size_t* n_bases, size_t* n_name_bytes, int* has_ids,
                                       uint8_t* codes, uint32_t* offs, char* names, uint32_t* name_offs, uint32_t* ids);
+/* ---- FASTQ records parsed on the device (opt-in) ------------------------------------------------------------------------
+ * For the selected resident batch, what h2g_set_reads + h2g_set_read_names (+ h2g_set_mates with text2) do with the arrays a host parser makes of the same bytes
+ * (FastqPatternSource, pat.cpp:725-1010): the texts are uploaded into the stream's temporary device memory and kernels write the batch's codes, qualities, names and offsets.
+ * text1 (and text2) begin at a record start; records are four lines, cut at every fourth '\n'.  final1 / final2: that text ends its input, so a last line without '\n'
+ * is complete (else the record it belongs to stays unconsumed).  n_records = min(records of text1, records of text2, max_records; max_records == 0: no bound) are parsed,
+ * and consumed1 / consumed2 are the bytes of each text they occupy.  trim5 / trim3 / phred64: -5 / -3 / --phred64.
+ * The device parses PLAIN records only (csrc/h2g_fastq.h states the predicate: a non-empty name, a sequence line of '.' and letters only, a '+' line, Lraw or Lraw + 1
+ * qualities without a blank, under phred64 every kept quality in [64, 128)).  When any of the n records is not plain the call returns H2G_OK with n_not_plain > 0 and
+ * first_not_plain, and the batch is left EMPTY (n_reads == 0): the caller parses those bytes itself.  With all of them plain first_not_plain == n_records, the batch holds
+ * them (qualities, names, mates set; seeds, filter and ids cleared) and h2g_align(_pairs)_run, the fetches and h2g_sam_text_* work on it unchanged.
+ * H2G_ERR_ARG (h2g_last_error), with the counts in *out where they are known and the batch empty: a text of 2^32 bytes or more; more records or bases than the stream's
+ * max_reads / max_bases; name bytes past 32-bit offsets.  Synchronises as h2g_set_reads does. */
+typedef struct { uint32_t trim5, trim3; uint8_t phred64, final1, final2, pad; uint64_t max_records; } h2g_fastq_opts;
+typedef struct { uint64_t n_records, consumed1, consumed2, n_bases1, n_bases2, n_name_bytes1, n_name_bytes2, n_not_plain, first_not_plain; uint32_t max_read_len, pad; } h2g_fastq_result;
+H2G_EXPORT h2g_status h2g_set_reads_fastq(h2g_stream*, const char* text1, size_t n1, const char* text2 /* NULL: unpaired */, size_t n2, const h2g_fastq_opts*, h2g_fastq_result* out);
+/* Read-back of one mate (0: the reads of h2g_set_reads, 1: of h2g_set_mates) of the selected resident batch, qualities included.  The three counts are always set, so a
+ * first call with NULL arrays sizes the second; any pointer may be NULL.  H2G_ERR_ARG: mate 1 of a batch without mates, quals of a set without qualities, names of a
+ * set without names. */
+H2G_EXPORT h2g_status h2g_fetch_read_set(h2g_stream*, int mate, size_t* n_reads, size_t* n_bases, size_t* n_name_bytes, uint8_t* codes, uint32_t* offs, char* quals, char* names,
+                                         uint32_t* name_offs);
+/* bytes uploaded / written and HIP-event time of the kernels of this stream's last h2g_set_reads_fastq (measurement) */
+typedef struct { uint64_t bytes_uploaded, bytes_written; float kernel_ms, pad; } h2g_fastq_stats;
+H2G_EXPORT h2g_status h2g_get_fastq_stats(h2g_stream*, h2g_fastq_stats* out);
 /* GenomeHit::combineWith (hi_aligner.h:1420-2025) as a primitive of its own: a[i] (the left hit) absorbs b[i] — concatenation, the mismatch rescan of the joint,
  * an insertion or deletion, or (spliced alignment) an intron placed by the donor / acceptor scan — over the resident reads; ok[i] = the function's return value.  `p` carries
  * scoring and splice policy (NULL: h2g_align_params_init's defaults for this index).  Inside go() the same device function runs as OP_COMBINE. */
