@@ -16,6 +16,7 @@
 #define H2G_EXT_OPTS 0      // likewise -I / --fr --rf --ff / --nofw --norc (h2g_align.h): go() units only
 #define H2G_HAPLOTYPE 0     // the primitive kernels of this unit (k_extend_alts, k_adjust_alt) run without haplotype lists; go() units: h2g_graph.h
 #include "h2g_core.h"
+#include "h2g_dev.h"     // DevBuf / PinnedBuf / DevEvent / DevStream: who holds one owns it
 #include "h2g_host_index.h"
 #include "h2g_align.h"
 #include "h2g_graph.h"
@@ -44,7 +45,9 @@ static int set_err(const char* what, hipError_t e) {
 extern "C" const char* h2g_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------ handles
+// Ownership (h2g_dev.h): a stream is declared before every buffer and event, so it is destroyed after them; the destructor waits for it first.
 struct h2g_index {
+	DevStream dense_st;                                    // the dense tables' builds (lowest priority)
 	HostIndex host;
 	bool synthetic = false;
 	int device = 0;
@@ -58,28 +61,30 @@ struct h2g_index {
 	std::vector<h2g_splice_site> alt_sites;               // splice-site ALTs of a --ss index: part of every database (SpliceSiteDB::read(gfm, alts))
 	DSpliceDB dssdb;                                       // h2g_index_set_splice_sites (device arrays; freed and replaced on every call)
 	DExonTbl dexons;                                       // the exons of a --ss/--exon index (--avoid-pseudogene); n == 0 without
-	void* d_ssdb[4] = {nullptr, nullptr, nullptr, nullptr};
-	size_t ssdb_cap[4] = {0, 0, 0, 0};                     // bytes behind each (they grow by doubling: temporary splice sites arrive wave after wave)
+	DevBuf<uint8_t> d_ssdb[4];                             // (they grow by doubling: temporary splice sites arrive wave after wave)
 	HostSpliceDB h_ssdb;                                   // the host copy h2g_index_add_splice_sites merges into
 	const float* d_spl[3] = {nullptr, nullptr, nullptr};   // SpliceSiteDB::probscore tables (donor, acceptor halves), uploaded with the index
 	std::vector<DLocalDesc> h_ldesc;   // host copy of the local-index descriptors (bucketing of h2g_ext_search)
-	std::vector<void*> allocs;
+	std::vector<DevBuf<uint8_t>> allocs;                   // every array of the index; dg, dr, dls, dalts, d_spl and the dense tables' pointers below are views of them
 	uint64_t device_bytes = 0;
 	// the dense SA table of a linear index (h2g_core.h sa_resolve_row): built by k_sa_dense_build on a stream of the index's own behind the uploads.
 	// `dg` never carries its pointers: a run takes them through dg_now(), which hands them out once the build is over (dense_ready)
-	uint32_t* d_sa_dense = nullptr; uint8_t* d_sa_dist = nullptr;
-	hipStream_t dense_st = nullptr; hipEvent_t dense_ev = nullptr;
+	uint32_t* d_sa_dense = nullptr; uint8_t* d_sa_dist = nullptr;   // (views: `allocs` owns them)
+	DevEvent dense_ev;
 	std::atomic<bool> dense_ready{false};
 	double dense_ms = 0.0;                                 // (H2G_DENSE_SA=2: the build, timed on the host)
 	bool dense_synced = false;                             // the uploads are known to be over (one device-wide wait, before the first build is queued)
 	// the dense table of the local rows (h2g_align.h lsa_resolve_row): built by k_lsa_dense_build behind the global table's build on dense_st, with an
 	// event of its own.  `dls` never carries its pointers: dls_now()
-	uint32_t* d_lsa = nullptr; uint64_t* d_lsa_base = nullptr;
+	uint32_t* d_lsa = nullptr; uint64_t* d_lsa_base = nullptr;      // (views: `allocs` owns them)
 	uint64_t lsa_rows = 0;
-	hipEvent_t lsa_ev = nullptr;
+	DevEvent lsa_ev;
 	std::atomic<bool> lsa_ready{false};
 	double lsa_ms = 0.0;                                   // (H2G_DENSE_LSA=2: the build, timed on the host)
+	~h2g_index() { if(dense_st) { (void)hipSetDevice(device); (void)hipStreamSynchronize(dense_st); } }
 };
+struct IndexFree { void operator()(h2g_index* ix) const { h2g_index_free(ix); } };
+typedef std::unique_ptr<h2g_index, IndexFree> IndexPtr;
 // the index's DGfm as a run queued now may use it: with the dense SA table from the moment its build is over (polled, never waited for)
 static DGfm dg_now(h2g_index* ix) {
 	DGfm g = ix->dg;
@@ -149,117 +154,141 @@ static DLocalSet dls_now(h2g_index* ix) {
 #define H2G_MAX_BATCHES 16
 struct BatchCtx {
 	size_t n_reads = 0; uint32_t max_read_len = 0;
-	uint8_t* d_codes = nullptr; uint32_t* d_offs = nullptr; char* d_quals = nullptr; bool has_quals = false;
-	char* d_names = nullptr; uint32_t* d_name_offs = nullptr; size_t names_cap = 0; bool has_names = false;
-	uint8_t* d_codes2 = nullptr; uint32_t* d_offs2 = nullptr; char* d_quals2 = nullptr; char* d_names2 = nullptr; uint32_t* d_name_offs2 = nullptr; bool has_mates = false, has_quals2 = false;
-	// result rows: aln_slots (>= -k) records per read in d_aln, pair_slots (>= H2G_PAIR_RES_CAP) per mate in d_paln; aln_alloc / paln_alloc records behind them
-	ReadOut* d_rout = nullptr; h2g_alnres* d_aln = nullptr; size_t aln_alloc = 0; uint32_t aln_slots = 0;
-	PairOut* d_pout = nullptr; h2g_alnres* d_paln[2] = {nullptr, nullptr}; size_t paln_alloc = 0; uint32_t pair_slots = 0;
+	DevBuf<uint8_t> d_codes; DevBuf<uint32_t> d_offs; DevBuf<char> d_quals; bool has_quals = false;
+	DevBuf<char> d_names; DevBuf<uint32_t> d_name_offs; bool has_names = false;      // (d_names: the name bytes it holds room for + 64)
+	DevBuf<uint8_t> d_codes2; DevBuf<uint32_t> d_offs2; DevBuf<char> d_quals2, d_names2; DevBuf<uint32_t> d_name_offs2; bool has_mates = false, has_quals2 = false;
+	// result rows: aln_slots (>= -k) records per read in d_aln, pair_slots (>= H2G_PAIR_RES_CAP) per mate in d_paln
+	DevBuf<ReadOut> d_rout; DevBuf<h2g_alnres> d_aln; uint32_t aln_slots = 0;
+	DevBuf<PairOut> d_pout; DevBuf<h2g_alnres> d_paln[2]; uint32_t pair_slots = 0;
 	// explicit PRNG seeds (h2g_set_read_seeds): mate 1's at [0, max_reads), mate 2's at [max_reads, 2 max_reads); a run reads them when has_seeds
-	uint32_t* d_seeds = nullptr; bool has_seeds = false, has_seeds2 = false;
+	DevBuf<uint32_t> d_seeds; bool has_seeds = false, has_seeds2 = false;
 	// --qc-filter bytes (h2g_set_read_filter), laid out like the seeds: 1 = the read passes; a run reads them when has_qc
-	uint8_t* d_qc = nullptr; bool has_qc = false;
-	uint32_t* d_ids = nullptr; bool has_ids = false;      // explicit read ids (h2g_set_read_ids)
+	DevBuf<uint8_t> d_qc; bool has_qc = false;
+	DevBuf<uint32_t> d_ids; bool has_ids = false;         // explicit read ids (h2g_set_read_ids)
+	// the read buffers of a batch's first use (h2g_stream_create for batch 0, h2g_stream_select_batch for the others)
+	hipError_t ensure_reads(size_t max_reads, size_t max_bases) {
+		hipError_t e = d_codes.ensure(max_bases + 64);
+		if(e == hipSuccess) e = d_quals.ensure(max_bases + 64);
+		return e != hipSuccess ? e : d_offs.ensure(max_reads + 1);
+	}
+	// room for nb name bytes (h2g_set_read_names, h2g_set_reads_windows, h2g_set_reads_fastq): when they do not fit, the names and their offsets are both replaced
+	hipError_t reserve_names(size_t nb, size_t max_reads) {
+		if(d_names.size() >= nb + 64 && d_name_offs) return hipSuccess;
+		const hipError_t e = d_names.reset(nb + 64);
+		return e != hipSuccess ? e : d_name_offs.reset(max_reads + 1);
+	}
+	// mate 2's buffers, at a batch's first mates (h2g_set_mates, h2g_set_reads_fastq); its names are allocated for every set (nb2 bytes)
+	hipError_t ensure_mates(size_t max_reads, size_t max_bases, size_t nb2) {
+		hipError_t e = d_codes2.ensure(max_bases + 64);
+		if(e == hipSuccess) e = d_quals2.ensure(max_bases + 64);
+		if(e == hipSuccess) e = d_offs2.ensure(max_reads + 1);
+		if(e == hipSuccess) e = d_name_offs2.ensure(max_reads + 1);
+		return e != hipSuccess ? e : d_names2.reset(nb2 + 64);
+	}
 };
+// Ownership (h2g_dev.h): every device buffer, event and HIP stream below is a handle, and deleting the context gives them all back.  THE STREAMS ARE DECLARED FIRST, so they
+// are destroyed last, after every buffer and event; the destructor waits for them before anything goes.  A member that is a raw pointer owns nothing and says whose memory it views.
 struct h2g_stream {
-	h2g_index* ix = nullptr;
-	hipStream_t st = nullptr;
+	h2g_index* ix = nullptr;          // (the caller's: an index outlives its streams)
+	DevStream st;
 	// the general machine's pass over a fast pass's hand-ons runs on one of these, next to the fast passes of the FOLLOWING two batches:
 	// its few reads are long latency chains (about a fast pass's duration whatever their number), so two such passes are kept in flight
-	hipStream_t mst[H2G_MSTREAMS_MAX] = {};     // all created with the context (h2g_stream_create: their order matters); mst[0 .. n_mst) have entered the rotation, only those ever held work
-	hipEvent_t ev_rot[H2G_MSTREAMS_MAX] = {};   // what a machine stream holds when the rotation changes
+	DevStream mst[H2G_MSTREAMS_MAX];            // all created with the context (h2g_stream_create: their order matters); mst[0 .. n_mst) have entered the rotation, only those ever held work
+	DevStream dst;                              // the drain launches' stream: one after the other, each next to the following run's fast launch
+	DevEvent ev_rot[H2G_MSTREAMS_MAX];          // what a machine stream holds when the rotation changes
 	unsigned n_mst = 0;
 	unsigned mstreams = 0;                      // pinned (1 .. H2G_MSTREAMS_MAX): lanes = machine streams in rotation = this; 0: S follows the load
 	unsigned mstreams_light = H2G_MSTREAMS_LIGHT_DEFAULT;   // S of the light regime
 	unsigned rot = 0;                           // machine streams in rotation for the last run behind a fast pass (0: there was none yet)
 	unsigned warm_mask = 0;                     // bit j: mst[j] has run both machine kernels once
 	bool st2_busy = false;            // a machine stream may hold work
-	hipEvent_t ev_fast[H2G_NBUF], ev_mach[H2G_NBUF];
+	DevEvent ev_fast[H2G_NBUF], ev_mach[H2G_NBUF];
 	unsigned gen = 0;                 // go_run generation: bail list, counters and argument block are buffered H2G_NBUF deep by gen % H2G_NBUF
-	unsigned long long* cnt_cur = nullptr;   // the counter block of the last go_run
+	unsigned long long* cnt_cur = nullptr;   // the counter block of the last go_run (a view into d_counters)
 	uint32_t last_bails = 0;
-	uint32_t* h_bails = nullptr;      // pinned: the hand-on count of the last two fast passes (sizes the machine's share of the CUs)
+	PinnedBuf<uint32_t> h_bails;      // pinned: the hand-on count of the last two fast passes (sizes the machine's share of the CUs)
 	size_t max_reads = 0, max_bases = 0;
 	BatchCtx batch[H2G_MAX_BATCHES];  // the resident batches: read sets and their result rows
 	unsigned cur_batch = 0;
 	BatchCtx& cur() { return batch[cur_batch]; }   // the selected one
 	const BatchCtx& cur() const { return batch[cur_batch]; }
-	h2g_seed_result* d_seed = nullptr;
+	DevBuf<h2g_seed_result> d_seed;
 	// per-lane scratch of the go() kernels: [0] the main pass, [1] the second pass over overflowed reads (large workspace)
 	struct GoPool {
-		uint8_t* ws = nullptr;  size_t ws_bytes = 0;      // AlignWS x lanes of the unit last run
-		uint8_t* gws = nullptr; size_t gws_bytes = 0;     // GraphWS x lanes (graph indexes only)
-		uint8_t* sw = nullptr;  size_t sw_stride = 0, sw_lanes = 0;   // Smith-Waterman scratch (only with bowtie2_dp != 0)
-		uint8_t* sc = nullptr;  size_t sc_bytes = 0;                  // combineWith temp_scores per lane
+		DevBuf<uint8_t> ws;                               // AlignWS x lanes of the unit last run
+		DevBuf<uint8_t> gws;                              // GraphWS x lanes (graph indexes only)
+		DevBuf<uint8_t> sw; size_t sw_stride = 0, sw_lanes = 0;   // Smith-Waterman scratch (only with bowtie2_dp != 0): what it is laid out for
+		DevBuf<uint8_t> sc;                               // combineWith temp_scores per lane
 	} pool[2 * H2G_MSTREAMS_MAX];     // [2 * m + 0] main pass, [2 * m + 1] second pass of machine stream m (m = 0 also: passes on the first stream)
-	uint32_t* dbg_buf = nullptr;      // development hook (H2G_GO_DBG_READ)
-	uint32_t* d_ovf_list[H2G_MSTREAMS_MAX] = {};   // per machine stream: read ids whose workspace overflowed in the main pass (+ their count behind the list)
+	DevBuf<uint32_t> dbg_buf;         // development hook (H2G_GO_DBG_READ)
+	DevBuf<uint32_t> d_ovf_list[H2G_MSTREAMS_MAX]; // per machine stream: read ids whose workspace overflowed in the main pass (+ their count behind the list)
 	unsigned ovf_cur = 0;             // the one the last run used
-	uint32_t* d_bail_list[H2G_NBUF] = {};  // read ids the fast pass handed on to the general machine (+ their count behind the list)
-	void* d_fast_args[2 * H2G_NBUF] = {};  // [gen % NBUF] the fast launch's, [NBUF + gen % NBUF] its drain launch's
-	void* h_fast_args = nullptr;      // pinned staging of the argument blocks (H2G_NBUF of them): the upload never makes the host wait for the stream      // the fast pass's argument block (device copy)
+	DevBuf<uint32_t> d_bail_list[H2G_NBUF]; // read ids the fast pass handed on to the general machine (+ their count behind the list)
+	DevBuf<FastArgs> d_fast_args[2 * H2G_NBUF]; // [gen % NBUF] the fast launch's, [NBUF + gen % NBUF] its drain launch's
+	PinnedBuf<FastArgs> h_fast_args;  // pinned staging of the argument blocks (H2G_NBUF of them): the upload never makes the host wait for the stream      // the fast pass's argument block (device copy)
 	// the fast pass's reads in flight (h2g_k_go_fast.hip): pool gen % 3 — the drain launch of run k reads run k's pool while the fast passes of runs k + 1 and k + 2 run
-	uint32_t* d_fast_slots[H2G_FAST_POOLS] = {}; size_t fast_slot_bytes[H2G_FAST_POOLS] = {};
-	hipEvent_t ev_pool[H2G_FAST_POOLS];                              // the drain launch that last read pool p is over
-	uint32_t* d_orphans[H2G_NBUF] = {};                              // slots a fast launch left in flight (+ their count behind the list)
+	DevBuf<uint8_t> d_fast_slots[H2G_FAST_POOLS];
+	DevEvent ev_pool[H2G_FAST_POOLS];                                // the drain launch that last read pool p is over
+	DevBuf<uint32_t> d_orphans[H2G_NBUF];                            // slots a fast launch left in flight (+ their count behind the list)
 	size_t orphan_cap = 0;
-	hipStream_t dst = nullptr;                                       // the drain launches' stream: one after the other, each next to the following run's fast launch
-	uint32_t* d_drain_slots = nullptr; size_t drain_slot_bytes = 0;  // the drain launch's own pool
-	uint8_t* d_drain_sc = nullptr; size_t drain_sc_bytes = 0;        // graph indexes: its combineWith scores per lane
-	hipEvent_t ev_drain[H2G_NBUF];                                   // run k's drain launch is over (its machine pass waits for it)
+	DevBuf<uint8_t> d_drain_slots;                                   // the drain launch's own pool
+	DevBuf<uint8_t> d_drain_sc;                                      // graph indexes: its combineWith scores per lane
+	DevEvent ev_drain[H2G_NBUF];                                     // run k's drain launch is over (its machine pass waits for it)
 	bool dst_busy = false;
-	hipEvent_t ev_bails[H2G_NBUF];                                   // h_bails[gen % NBUF] has arrived
-	hipEvent_t ev_dr[2];                                             // (timed) around the last drain launch
+	DevEvent ev_bails[H2G_NBUF];                                     // h_bails[gen % NBUF] has arrived
+	DevEvent ev_dr[2];                                               // (timed) around the last drain launch
 	bool ran_drain = false;
-	const uint32_t* orph_cur = nullptr;                              // the orphan count of the last run
-	uint8_t* d_fast_gws = nullptr; size_t fast_gws_bytes = 0;       // graph indexes: GraphWS per lane of the fast kernel (scratch of one primitive)
-	uint8_t* d_fast_sc = nullptr; size_t fast_sc_bytes = 0;         // ... and combineWith's temp_scores per lane
+	const uint32_t* orph_cur = nullptr;                              // the orphan count of the last run (a view into d_orphans)
+	DevBuf<uint8_t> d_fast_gws;                                     // graph indexes: GraphWS per lane of the fast kernel (scratch of one primitive)
+	DevBuf<uint8_t> d_fast_sc;                                      // ... and combineWith's temp_scores per lane
 	bool ran_fast = false;
 	// development / measurement knobs (h2g_stream_tune; their H2G_* environment names are read ONCE, when the stream is created)
 	struct Tune { int fast = 1, blocks_per_cu = 0, pair_slots = 0, no_second_pass = 0; unsigned mach_div = 0 /* auto */, mach_min = 4, mach_total = H2G_MACH_TOTAL; int mach_total_auto = 1; int fast_reserve = H2G_FAST_RESERVE_DEFAULT; long dbg_read = -1;
 	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */;
 	              int fast_spliced = H2G_DEFAULT_FAST_SPLICED; /* the fast pass of spliced runs on a linear index (h2g_k_go_fast_spl.hip) */ } tune;
 	h2g_align_params last_p; int last_paired = -1;   // the option set of the last go_run (a different one waits for the machine streams)
-	uint8_t* d_sw_ws = nullptr;   // h2g_sw_align: H/E/F workspace of one batch of problems
-	size_t sw_ws_bytes = 0;
-	SwLaneState* d_sw_states = nullptr;
-	size_t sw_states = 0;
+	DevBuf<uint8_t> d_sw_ws;      // h2g_sw_align: H/E/F workspace of one batch of problems
+	DevBuf<SwLaneState> d_sw_states;
 	// records with more than H2G_MAX_EDITS edits keep their lists here (MachOut::ledits): one part of ledits_cap edits and one cursor per machine stream
-	h2g_edit* d_ledits = nullptr; uint32_t* d_ledits_cur = nullptr; size_t ledits_cap = 0; unsigned ledits_parts = 0;
+	DevBuf<h2g_edit> d_ledits; DevBuf<uint32_t> d_ledits_cur; size_t ledits_cap = 0; unsigned ledits_parts = 0;
 	unsigned ledits_touched = 0;   // parts a run has written to since the last h2g_set_reads (bit per machine stream): the span h2g_align_fetch_long_edits reports
-	h2g_alnres* d_paln_ovf = nullptr; size_t paln_ovf_cap = 0; unsigned paln_ovf_parts = 0;   // pairs with more records than pair_slots per mate (MachOut::ovf): one part of paln_ovf_cap records per machine stream
+	DevBuf<h2g_alnres> d_paln_ovf; size_t paln_ovf_cap = 0; unsigned paln_ovf_parts = 0;   // pairs with more records than pair_slots per mate (MachOut::ovf): one part of paln_ovf_cap records per machine stream
 	// the XL units' concordant lists that PairOut cannot carry (XlPairs): per read of the batch where its list starts, the lists (one part of xlp_cap words per
-	// machine stream) and one cursor per part.  xlp_pout: the result rows of the batch the last XL paired run wrote (nullptr: no list is current)
-	uint32_t* d_xlp_at = nullptr; size_t xlp_at_cap = 0; uint32_t* d_xlp = nullptr; size_t xlp_cap = 0; unsigned xlp_parts = 0; uint32_t* d_xlp_cur = nullptr;
+	// machine stream) and one cursor per part.  xlp_pout: the result rows of the batch the last XL paired run wrote (a view of that batch's d_pout; nullptr: no list is current)
+	DevBuf<uint32_t> d_xlp_at, d_xlp; size_t xlp_cap = 0; unsigned xlp_parts = 0; DevBuf<uint32_t> d_xlp_cur;
 	const PairOut* xlp_pout = nullptr;
-	unsigned long long* d_counters = nullptr;   // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
-	void* d_tmp[4] = {nullptr, nullptr, nullptr, nullptr};
-	size_t tmp_sz[4] = {0, 0, 0, 0};
+	DevBuf<unsigned long long> d_counters;      // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
+	DevBuf<uint8_t> d_tmp[4];                   // scratch of one call (tmp_buf): each 256 bytes beyond its largest request
 	// SAM text on the device (h2g_sam_text_*): what d_tmp holds is nobody's once another call takes a slot, so every such call (tmp_buf), every batch selection and every call
 	// that sets reads, mates or names counts tmp_gen up; a compact fetch notes the count it ended with, and the text call runs only while the two are equal
 	uint64_t tmp_gen = 0;
 	struct CompactFetch { bool valid = false, paired = false; uint64_t gen = 0; unsigned batch = 0; size_t first = 0, n = 0; const uint8_t* d_rec[2] = {nullptr, nullptr}; uint64_t bytes[2] = {0, 0};
-	                      const uint64_t* d_boffs[2] = {nullptr, nullptr}; /* the offset arrays of the fetch (tmp slots 0 / 2), [n + 1] each */ } cfetch;
-	void* d_sam[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // descriptors, pool, line offsets (+ scan tile sums + the check's flag), text, the handle's tables
-	size_t sam_sz[5] = {0, 0, 0, 0, 0};
+	                      const uint64_t* d_boffs[2] = {nullptr, nullptr}; /* the offset arrays of the fetch (tmp slots 0 / 2), [n + 1] each; d_rec and these are views into d_tmp */ } cfetch;
+	DevBuf<uint8_t> d_sam[5];                   // descriptors, pool, line offsets (+ scan tile sums + the check's flag), text, the handle's tables
 	uint64_t samtab_uid = 0, samtab_gen = 0; uint32_t samtab_nrefs = 0, samtab_names = 0, samtab_rg = 0, samtab_nalts = 0; int32_t samtab_strand = 0;   // whose tables d_sam[4] holds
-	hipEvent_t ev_sam[4] = {nullptr, nullptr, nullptr, nullptr};
+	DevEvent ev_sam[4];                         // (created by the first text call)
 	h2g_sam_text_stats sam_stats = {};
 	// h2g_sam_text_*_planned: two descriptor slots per read, class + filter bytes, line counts (+ scan tile sums, per-read source of the handed-on lines, line ends), the
 	// handed-on reads' entries, their descriptors
-	void* d_plan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-	size_t plan_sz[5] = {0, 0, 0, 0, 0};
-	hipEvent_t ev_plan[4] = {nullptr, nullptr, nullptr, nullptr};
+	DevBuf<uint8_t> d_plan[5];
+	DevEvent ev_plan[4];                        // (created by the first planned call)
 	h2g_sam_plan_stats plan_stats = {};
 	std::vector<uint8_t> plan_classes;
-	hipEvent_t ev[14];                          // ([12], [13]: around the kernels of h2g_set_reads_windows / h2g_set_reads_fastq)
+	DevEvent ev[14];                            // ([12], [13]: around the kernels of h2g_set_reads_windows / h2g_set_reads_fastq)
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
 	h2g_windows_stats win_stats = {};           // of the last h2g_set_reads_windows
 	h2g_fastq_stats fq_stats = {};              // of the last h2g_set_reads_fastq
-	unsigned long long* d_warm_cnt = nullptr;   // counter block of the machine streams' empty first launches (go_warmup); word H2G_CNT_NO_SECOND, which nobody writes, is their list's count
-	uint8_t* d_warm_rows = nullptr;             // ... and the result rows they are given: never the current batch's
+	DevBuf<unsigned long long> d_warm_cnt;      // counter block of the machine streams' empty first launches (go_warmup); word H2G_CNT_NO_SECOND, which nobody writes, is their list's count
+	DevBuf<uint8_t> d_warm_rows;                // ... and the result rows they are given: never the current batch's
+	// whatever is queued ends before its buffers, events and streams go (h2g_stream_free's contract; any other path that drops a context gets it too)
+	~h2g_stream() {
+		if(st) (void)hipStreamSynchronize(st);
+		if(dst) (void)hipStreamSynchronize(dst);
+		for(unsigned k = 0; k < n_mst; k++) (void)hipStreamSynchronize(mst[k]);
+	}
 };
+struct StreamFree { void operator()(h2g_stream* s) const { h2g_stream_free(s); } };
 
 // Large arrays travel through page-locked staging buffers filled by several threads: a pageable hipMemcpy of a human-size index (4.7 GB) was most of its 1.2 s load (round 6).
 // Chunk k of a copy is thread k mod T's: wait for its staging buffer, memcpy (from a host vector or straight from a mapped index file: the page faults spread over the threads
@@ -267,18 +296,17 @@ struct h2g_stream {
 struct Stager {
 	enum { T = 6, NB = 2 };
 	static constexpr size_t CH = (size_t)16 << 20;
-	uint8_t* buf[T][NB] = {}; hipStream_t st[T] = {}; hipEvent_t ev[T][NB] = {};
+	DevStream st[T]; PinnedBuf<uint8_t> buf[T][NB]; DevEvent ev[T][NB];
 	int device = 0; bool ok = false;
 	bool init(int dev) {
 		device = dev; ok = true;
 		for(int t = 0; t < T && ok; t++) {
-			ok = hipStreamCreateWithFlags(&st[t], hipStreamNonBlocking) == hipSuccess;
-			for(int b = 0; b < NB && ok; b++) ok = hipHostMalloc((void**)&buf[t][b], CH, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev[t][b], hipEventDisableTiming) == hipSuccess;
+			ok = st[t].create(hipStreamNonBlocking) == hipSuccess;
+			for(int b = 0; b < NB && ok; b++) ok = buf[t][b].ensure(CH) == hipSuccess && ev[t][b].create(hipEventDisableTiming) == hipSuccess;
 		}
 		if(!ok) (void)hipGetLastError();
 		return ok;
 	}
-	~Stager() { for(int t = 0; t < T; t++) { for(int b = 0; b < NB; b++) { if(buf[t][b]) (void)hipHostFree(buf[t][b]); if(ev[t][b]) (void)hipEventDestroy(ev[t][b]); } if(st[t]) (void)hipStreamDestroy(st[t]); } }
 	bool copy(void* dst, const void* src, size_t bytes) {
 		return gather(dst, bytes, [src](uint8_t* out, size_t off, size_t len) { memcpy(out, (const uint8_t*)src + off, len); });
 	}
@@ -305,13 +333,20 @@ struct Stager {
 		return good;
 	}
 };
-static int upload_raw(h2g_index* ix, const void* src, size_t n, const void** out, size_t pad, Stager* sg) {
-	void* p = nullptr;
-	const size_t bytes = n + pad;
-	HIPCHK(hipMalloc(&p, bytes));
-	ix->allocs.push_back(p);
+// a device array of the index: allocated into a handle of this scope, which `allocs` takes over; counted in device_bytes
+static int index_alloc(h2g_index* ix, size_t bytes, uint8_t** out) {
+	DevBuf<uint8_t> b;
+	HIPCHK(b.reset(bytes));
+	*out = b;
+	ix->allocs.push_back(std::move(b));
 	ix->device_bytes += bytes;
-	HIPCHK(hipMemset((uint8_t*)p + n, 0, pad));                       // (the padding only: the rest is about to be written)
+	return H2G_OK;
+}
+static int upload_raw(h2g_index* ix, const void* src, size_t n, const void** out, size_t pad, Stager* sg) {
+	uint8_t* p = nullptr;
+	int rc;
+	if((rc = index_alloc(ix, n + pad, &p))) return rc;
+	HIPCHK(hipMemset(p + n, 0, pad));                                // (the padding only: the rest is about to be written)
 	if(n) {
 		if(sg && sg->ok && n >= ((size_t)32 << 20)) { if(!sg->copy(p, src, n)) { snprintf(g_err, sizeof g_err, "index upload through the staging buffers failed"); return H2G_ERR_DEVICE; } }
 		else HIPCHK(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
@@ -362,36 +397,30 @@ static void dense_sa_start(h2g_index* ix) {
 	size_t free_b = 0, total_b = 0;
 	// it fits when it takes at most a quarter of the memory that is free now, with the index uploaded: a caller's own pools are not squeezed
 	if(hipMemGetInfo(&free_b, &total_b) != hipSuccess || b_dense + b_dist > free_b / 4) { (void)hipGetLastError(); return; }
-	void *pd = nullptr, *pt = nullptr;
-	hipStream_t st = nullptr; hipEvent_t e = nullptr;
-	bool ok = hipMalloc(&pd, b_dense) == hipSuccess && hipMalloc(&pt, b_dist) == hipSuccess &&
-	          hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+	// built into handles of this scope, which become the index's once everything is queued: a failure on the way drops them
+	DevStream st; DevEvent e;
+	DevBuf<uint8_t> pd, pt;
+	bool ok = pd.reset(b_dense) == hipSuccess && pt.reset(b_dist) == hipSuccess && e.create(hipEventDisableTiming) == hipSuccess;
 	if(ok) {   // at the lowest priority: runs queued while it is under way get their workgroups placed first
 		int least = 0, greatest = 0;
-		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess;
+		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && st.create_with_priority(hipStreamNonBlocking, least) == hipSuccess;
 	}
 	ok = ok && hipDeviceSynchronize() == hipSuccess;                  // the uploads (their padding is set on the null stream) are over
 	ix->dense_synced = ok;
 	const auto t0 = std::chrono::steady_clock::now();
 	if(ok) {
 		const uint64_t waves = ((uint64_t)rows + H2G_DENSE_CHUNK - 1) / H2G_DENSE_CHUNK;
-		hipLaunchKernelGGL(k_sa_dense_build, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, g, (uint32_t*)pd, (uint8_t*)pt);
+		hipLaunchKernelGGL(k_sa_dense_build, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, g, (uint32_t*)pd.get(), pt.get());
 		ok = hipGetLastError() == hipSuccess && hipEventRecord(e, st) == hipSuccess;
 		if(!ok && st) (void)hipStreamSynchronize(st);
 	}
-	if(!ok) {
-		(void)hipGetLastError();
-		if(pd) (void)hipFree(pd);
-		if(pt) (void)hipFree(pt);
-		if(e) (void)hipEventDestroy(e);
-		if(st) (void)hipStreamDestroy(st);
-		return;
-	}
-	ix->allocs.push_back(pd); ix->allocs.push_back(pt);
+	if(!ok) { (void)hipGetLastError(); return; }
 	ix->device_bytes += b_dense + b_dist;
-	ix->d_sa_dense = (uint32_t*)pd; ix->d_sa_dist = (uint8_t*)pt; ix->dense_st = st; ix->dense_ev = e;
+	ix->d_sa_dense = (uint32_t*)pd.get(); ix->d_sa_dist = pt.get();
+	ix->allocs.push_back(std::move(pd)); ix->allocs.push_back(std::move(pt));
+	ix->dense_st = std::move(st); ix->dense_ev = std::move(e);
 	if(mode >= 2) {
-		if(hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }       // (the table stays unused: dense_ready is never set by a failed event)
+		if(hipStreamSynchronize(ix->dense_st) != hipSuccess) { (void)hipGetLastError(); return; }       // (the table stays unused: dense_ready is never set by a failed event)
 		ix->dense_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		ix->dense_ready.store(true, std::memory_order_release);
 	}
@@ -443,33 +472,28 @@ static void dense_lsa_start(h2g_index* ix) {
 	const size_t rows = base[n], b_tab = rows * 4 + 64, b_base = (n + 1) * 8;
 	size_t free_b = 0, total_b = 0;
 	if(hipMemGetInfo(&free_b, &total_b) != hipSuccess || b_tab + b_base > free_b / 4) { (void)hipGetLastError(); return; }
-	void *pt = nullptr, *pb = nullptr;
-	hipStream_t st = ix->dense_st; hipEvent_t e = nullptr;
-	bool ok = hipMalloc(&pt, b_tab) == hipSuccess && hipMalloc(&pb, b_base) == hipSuccess &&
-	          hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-	if(ok && !st) {
+	DevStream own_st; DevEvent e;                            // (own_st: only when the global table's build left no stream)
+	DevBuf<uint8_t> pt, pb;
+	bool ok = pt.reset(b_tab) == hipSuccess && pb.reset(b_base) == hipSuccess && e.create(hipEventDisableTiming) == hipSuccess;
+	if(ok && !ix->dense_st) {
 		int least = 0, greatest = 0;
-		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess;
+		ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && own_st.create_with_priority(hipStreamNonBlocking, least) == hipSuccess;
 	}
+	const hipStream_t st = ix->dense_st ? ix->dense_st.get() : own_st.get();
 	if(ok && !ix->dense_synced) { ok = hipDeviceSynchronize() == hipSuccess; ix->dense_synced = ok; }
 	ok = ok && hipMemcpy(pb, base.data(), b_base, hipMemcpyHostToDevice) == hipSuccess;
 	const auto t0 = std::chrono::steady_clock::now();
 	if(ok) {
-		hipLaunchKernelGGL(k_lsa_dense_build, dim3((unsigned)n), dim3(256), 0, st, ix->dls, (const uint64_t*)pb, (uint32_t*)pt);
+		hipLaunchKernelGGL(k_lsa_dense_build, dim3((unsigned)n), dim3(256), 0, st, ix->dls, (const uint64_t*)pb.get(), (uint32_t*)pt.get());
 		ok = hipGetLastError() == hipSuccess && hipEventRecord(e, st) == hipSuccess;
 		if(!ok && st) (void)hipStreamSynchronize(st);
 	}
-	if(!ok) {
-		(void)hipGetLastError();
-		if(pt) (void)hipFree(pt);
-		if(pb) (void)hipFree(pb);
-		if(e) (void)hipEventDestroy(e);
-		if(st && !ix->dense_st) (void)hipStreamDestroy(st);
-		return;
-	}
-	ix->allocs.push_back(pt); ix->allocs.push_back(pb);
+	if(!ok) { (void)hipGetLastError(); return; }
 	ix->device_bytes += b_tab + b_base;
-	ix->d_lsa = (uint32_t*)pt; ix->d_lsa_base = (uint64_t*)pb; ix->lsa_rows = rows; ix->dense_st = st; ix->lsa_ev = e;
+	ix->d_lsa = (uint32_t*)pt.get(); ix->d_lsa_base = (uint64_t*)pb.get(); ix->lsa_rows = rows;
+	ix->allocs.push_back(std::move(pt)); ix->allocs.push_back(std::move(pb));
+	if(own_st) ix->dense_st = std::move(own_st);
+	ix->lsa_ev = std::move(e);
 	if(mode >= 2) {
 		if(hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }
 		ix->lsa_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -497,7 +521,8 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	if(e != hipSuccess || ndev <= 0) { snprintf(g_err, sizeof g_err, "no HIP device (libh2g has no CPU path)"); return H2G_ERR_DEVICE; }
 	if(o.device < 0 || o.device >= ndev) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(o.device));
-	h2g_index* ix = new h2g_index();
+	IndexPtr ixp(new h2g_index());                           // (every early return below frees what the index holds by then)
+	h2g_index* const ix = ixp.get();
 	ix->device = o.device;
 	// the local indexes (.5 / .6: 2.1 GB of a human-size index) are packed on a thread of their own, straight from the files, while the global
 	// index is read, parsed and uploaded here
@@ -517,43 +542,43 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	sg.init(o.device);
 	try { rc = load_host_index(base, false, ix->host, false, &bv); } catch(...) { rc = -2; }
 	const double t_parse = lsec();   // a length read from a corrupt file: an allocation failure is a format error, not std::terminate across the C ABI
-	if(rc != 0) { if(tlocal.joinable()) tlocal.join(); delete ix; snprintf(g_err, sizeof g_err, "cannot read index %s", base); return rc == -1 ? H2G_ERR_IO : H2G_ERR_FORMAT; }
+	if(rc != 0) { snprintf(g_err, sizeof g_err, "cannot read index %s", base); return rc == -1 ? H2G_ERR_IO : H2G_ERR_FORMAT; }
 	const HostGfm& g = ix->host.g;
 	fill_dgfm(g, ix->host.minK, &ix->dg);
 	int s = H2G_OK;
 	{
 		const void *ds_ = nullptr, *do_ = nullptr;
-		if((s = upload_raw(ix, bv.sides, bv.sides_n, &ds_, 256, &sg)) || (s = upload_raw(ix, bv.offs, bv.offs_n, &do_, 64, &sg))) { h2g_index_free(ix); return s; }
+		if((s = upload_raw(ix, bv.sides, bv.sides_n, &ds_, 256, &sg)) || (s = upload_raw(ix, bv.offs, bv.offs_n, &do_, 64, &sg))) return s;
 		ix->dg.sides = (const uint8_t*)ds_; ix->dg.offs = (const uint32_t*)do_;
 	}
 	if((s = upload(ix, g.ftab, &ix->dg.ftab)) ||
 	   (s = upload(ix, g.eftab, &ix->dg.eftab)) ||
 	   (s = upload(ix, g.rstarts, &ix->dg.rstarts)) || (s = upload(ix, g.plen, &ix->dg.plen)) ||
-	   (s = upload(ix, g.zOffs, &ix->dg.zoffs))) { h2g_index_free(ix); return s; }
+	   (s = upload(ix, g.zOffs, &ix->dg.zoffs))) return s;
 	const HostRef& r = ix->host.r;
 	ix->dr.nrefs = r.nrefs;
 	{
 		const void* db_ = nullptr;
-		if((s = upload_raw(ix, bv.buf, bv.buf_n, &db_, 64, &sg))) { h2g_index_free(ix); return s; }
+		if((s = upload_raw(ix, bv.buf, bv.buf_n, &db_, 64, &sg))) return s;
 		ix->dr.buf = (const uint8_t*)db_;
 	}
 	const double t_global = lsec();
 	if((s = upload(ix, r.rec_start, &ix->dr.rec_start)) ||
 	   (s = upload(ix, r.rec_len, &ix->dr.rec_len)) || (s = upload(ix, r.rec_bufoff, &ix->dr.rec_bufoff)) ||
-	   (s = upload(ix, r.refRecOffs, &ix->dr.refRecOffs)) || (s = upload(ix, r.refLens, &ix->dr.refLens))) { h2g_index_free(ix); return s; }
+	   (s = upload(ix, r.refRecOffs, &ix->dr.refRecOffs)) || (s = upload(ix, r.refLens, &ix->dr.refLens))) return s;
 	static_assert(sizeof(HostAlt) == sizeof(DAlt), "HostAlt mirrors DAlt");
 	ix->dalts.a = nullptr; ix->dalts.n = 0; ix->dalts.maxAltsTried = 16;      // --max-altstried default hisat2.cpp:521
 	if(!g.p.linear && !ix->host.alts.empty()) {
 		std::vector<uint64_t> packed;                      // the ALTs followed by the haplotype table (pack_alts, h2g_graph.h)
 		pack_alts(ix->host.alts, ix->host.hap_left, ix->host.hap_right, ix->host.hap_maxright, ix->host.hap_first, ix->host.hap_ids, packed);
 		const uint64_t* da = nullptr;
-		if((s = upload(ix, packed, &da))) { h2g_index_free(ix); return s; }
+		if((s = upload(ix, packed, &da))) return s;
 		ix->dalts.a = reinterpret_cast<const DAlt*>(da);
 		ix->dalts.n = (uint32_t)ix->host.alts.size();
 		std::vector<uint32_t> bk;
 		alt_buckets(reinterpret_cast<const DAlt*>(ix->host.alts.data()), ix->dalts.n, bk);
 		const uint32_t* dbk = nullptr;
-		if(!bk.empty()) { if((s = upload(ix, bk, &dbk))) { h2g_index_free(ix); return s; } ix->dalts.bucket = dbk; ix->dalts.nbucket = (uint32_t)bk.size(); }
+		if(!bk.empty()) { if((s = upload(ix, bk, &dbk))) return s; ix->dalts.bucket = dbk; ix->dalts.nbucket = (uint32_t)bk.size(); }
 		// a --ss index: its splice-site ALTs are graph edges AND known sites of the database (SpliceSiteDB::read(gfm, alts))
 		splice_sites_of_alts(reinterpret_cast<const uint32_t*>(ix->host.alts.data()), ix->host.alts.size(), sizeof(HostAlt) / 4, g.rstarts.data(), g.nFrag, g.p.len, ix->alt_sites);
 		for(const HostAlt& a : ix->host.alts) if(a.type == 5) ix->dalts.has_splice = 1;
@@ -562,23 +587,22 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 		exons_of_alts(reinterpret_cast<const uint32_t*>(ix->host.alts.data()), ix->host.alts.size(), sizeof(HostAlt) / 4, g.rstarts.data(), g.nFrag, g.p.len, g.plen.data(), g.nPat, ex);
 		if(!ex.empty()) {
 			const DExon* de = nullptr;
-			if((s = upload(ix, ex, &de))) { h2g_index_free(ix); return s; }
+			if((s = upload(ix, ex, &de))) return s;
 			ix->dexons.e = de; ix->dexons.n = (uint32_t)ex.size();
 		}
 	}
 	memset(&ix->dls, 0, sizeof ix->dls);
 	if(tlocal.joinable()) tlocal.join();
 	const double t_join = lsec();
-	if(lrc == -2) { h2g_index_free(ix); snprintf(g_err, sizeof g_err, "cannot read the local indexes of %s", base); return H2G_ERR_FORMAT; }
+	if(lrc == -2) { snprintf(g_err, sizeof g_err, "cannot read the local indexes of %s", base); return H2G_ERR_FORMAT; }
 	if(o.load_local && lrc == 0 && !lp.desc.empty()) {
 		while(lp.first.size() <= g.nPat) lp.first.push_back((uint32_t)lp.desc.size());
 		const DLocalDesc* dd; const uint8_t* ds = nullptr; const uint16_t* dw = nullptr; const uint32_t* df; const uint32_t* dz;
 		{	// the two packed arrays (sides: 128-byte aligned per index, 256 bytes of padding behind; 16-bit words: 64 entries of padding), gathered chunk by chunk out of the files
 			const size_t sb = lpl.nsides_tot + 256, wb = (lpl.nwords_tot + 64) * 2;
-			void *ps = nullptr, *pw = nullptr;
-			HIPCHK(hipMalloc(&ps, sb + 64)); ix->allocs.push_back(ps); ix->device_bytes += sb + 64;
-			HIPCHK(hipMalloc(&pw, wb + 64)); ix->allocs.push_back(pw); ix->device_bytes += wb + 64;
-			HIPCHK(hipMemset((uint8_t*)ps + sb, 0, 64)); HIPCHK(hipMemset((uint8_t*)pw + wb, 0, 64));
+			uint8_t *ps = nullptr, *pw = nullptr;
+			if((s = index_alloc(ix, sb + 64, &ps)) || (s = index_alloc(ix, wb + 64, &pw))) return s;
+			HIPCHK(hipMemset(ps + sb, 0, 64)); HIPCHK(hipMemset(pw + wb, 0, 64));
 			bool okc = sg.ok;
 			if(okc) okc = sg.gather(ps, sb, [&](uint8_t* out_, size_t off_, size_t len_) { local_fill_sides(lpl, out_, off_, len_); }) &&
 			              sg.gather(pw, wb, [&](uint8_t* out_, size_t off_, size_t len_) { local_fill_words(lpl, out_, off_, len_); });
@@ -589,7 +613,7 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 			}
 			ds = (const uint8_t*)ps; dw = (const uint16_t*)pw;
 		}
-		if((s = upload(ix, lp.desc, &dd)) || (s = upload(ix, lp.first, &df)) || (s = upload(ix, lp.zoffs, &dz))) { h2g_index_free(ix); return s; }
+		if((s = upload(ix, lp.desc, &dd)) || (s = upload(ix, lp.first, &df)) || (s = upload(ix, lp.zoffs, &dz))) return s;
 		ix->dls = lp.view(dd, ds, dw, df, dz);
 		ix->h_ldesc = lp.desc;
 		ix->host.local_first = lp.first;                     // (h2g_local_index_of)
@@ -600,9 +624,9 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	{   // splice-site probability tables (spliced alignment): 1.4 MB, index-independent
 		std::vector<float> d, a1, a2;
 		splice_tables(d, a1, a2);
-		if((s = upload(ix, d, &ix->d_spl[0])) || (s = upload(ix, a1, &ix->d_spl[1])) || (s = upload(ix, a2, &ix->d_spl[2]))) { h2g_index_free(ix); return s; }
+		if((s = upload(ix, d, &ix->d_spl[0])) || (s = upload(ix, a1, &ix->d_spl[1])) || (s = upload(ix, a2, &ix->d_spl[2]))) return s;
 	}
-	if(!ix->alt_sites.empty()) { h2g_index* tmp_ = ix; const h2g_status rs_ = h2g_index_set_splice_sites(tmp_, nullptr, 0, 0); if(rs_ != H2G_OK) { h2g_index_free(ix); return rs_; } }
+	if(!ix->alt_sites.empty()) { const h2g_status rs_ = h2g_index_set_splice_sites(ix, nullptr, 0, 0); if(rs_ != H2G_OK) return rs_; }
 	sgp.reset();
 	const double t_up = lsec();
 	dense_sa_start(ix);
@@ -613,7 +637,7 @@ extern "C" h2g_status h2g_index_load(const char* base, const h2g_load_opts* opts
 	                  !ix->d_sa_dist ? "none" : ix->dense_ready.load() ? "built" : "queued", t_sa - t_up, ix->dense_ms,
 	                  !ix->d_lsa ? "none" : ix->lsa_ready.load() ? "built" : "queued", lsec() - t_sa, ix->lsa_ms, ix->d_lsa ? (ix->lsa_rows * 4 + 64 + (ix->h_ldesc.size() + 1) * 8) / 1e9 : 0.0,
 	                  lsec(), ix->device_bytes / 1e9);
-	*out = ix;
+	*out = ixp.release();
 	return H2G_OK;
 }
 
@@ -638,17 +662,11 @@ static h2g_status upload_splice_db(h2g_index* ix) {
 	const void* src[4] = {h.fw.data(), h.bw.data(), h.fw_first.data(), h.bw_first.data()};
 	const size_t bytes[4] = {h.fw.size() * sizeof(DSpliceSite), h.bw.size() * sizeof(DSpliceSite), h.fw_first.size() * 4, h.bw_first.size() * 4};
 	for(int k = 0; k < 4; k++) {
-		if(ix->ssdb_cap[k] < bytes[k]) {
-			if(ix->d_ssdb[k]) (void)hipFree(ix->d_ssdb[k]);
-			ix->d_ssdb[k] = nullptr; ix->ssdb_cap[k] = 0;
-			const size_t cap = bytes[k] * 2 < 4096 ? 4096 : bytes[k] * 2;
-			HIPCHK(hipMalloc(&ix->d_ssdb[k], cap));
-			ix->ssdb_cap[k] = cap;
-		}
+		if(ix->d_ssdb[k].size() < bytes[k]) HIPCHK(ix->d_ssdb[k].reset(bytes[k] * 2 < 4096 ? 4096 : bytes[k] * 2));
 		HIPCHK(hipMemcpy(ix->d_ssdb[k], src[k], bytes[k], hipMemcpyHostToDevice));
 	}
-	ix->dssdb.fw = (const DSpliceSite*)ix->d_ssdb[0]; ix->dssdb.bw = (const DSpliceSite*)ix->d_ssdb[1];
-	ix->dssdb.fw_first = (const uint32_t*)ix->d_ssdb[2]; ix->dssdb.bw_first = (const uint32_t*)ix->d_ssdb[3];
+	ix->dssdb.fw = (const DSpliceSite*)ix->d_ssdb[0].get(); ix->dssdb.bw = (const DSpliceSite*)ix->d_ssdb[1].get();
+	ix->dssdb.fw_first = (const uint32_t*)ix->d_ssdb[2].get(); ix->dssdb.bw_first = (const uint32_t*)ix->d_ssdb[3].get();
 	ix->dssdb.n = (uint32_t)h.fw.size();
 	return H2G_OK;
 }
@@ -705,17 +723,16 @@ extern "C" h2g_status h2g_index_dense_sa_check(h2g_index* ix, uint32_t* state, u
 	if(!g.sa_dist) return H2G_OK;
 	if(state) *state = 1;
 	if(!rows_differ) return H2G_OK;
-	unsigned long long* dn = nullptr;
-	HIPCHK(hipMalloc(&dn, sizeof *dn));
+	DevBuf<unsigned long long> dn;
+	HIPCHK(dn.reset(1));
 	unsigned long long hn = 0;
-	hipError_t e = hipMemsetAsync(dn, 0, sizeof *dn, ix->dense_st);
+	hipError_t e = hipMemsetAsync(dn, 0, sizeof hn, ix->dense_st);
 	if(e == hipSuccess) {
-		hipLaunchKernelGGL(k_sa_dense_check, dim3(8192), dim3(256), 0, ix->dense_st, ix->dg, (const uint32_t*)g.sa_dense, (const uint8_t*)g.sa_dist, dn);
+		hipLaunchKernelGGL(k_sa_dense_check, dim3(8192), dim3(256), 0, ix->dense_st, ix->dg, (const uint32_t*)g.sa_dense, (const uint8_t*)g.sa_dist, dn.get());
 		e = hipGetLastError();
 	}
 	if(e == hipSuccess) e = hipMemcpyAsync(&hn, dn, sizeof hn, hipMemcpyDeviceToHost, ix->dense_st);
 	if(e == hipSuccess) e = hipStreamSynchronize(ix->dense_st);
-	(void)hipFree(dn);
 	if(e != hipSuccess) return (h2g_status)set_err("h2g_index_dense_sa_check", e);
 	*rows_differ = hn;
 	return H2G_OK;
@@ -734,34 +751,22 @@ extern "C" h2g_status h2g_index_dense_lsa_check(h2g_index* ix, uint32_t* state, 
 	if(!l.lsa) return H2G_OK;
 	if(state) *state = 1;
 	if(!rows_differ) return H2G_OK;
-	unsigned long long* dn = nullptr;
-	HIPCHK(hipMalloc(&dn, sizeof *dn));
+	DevBuf<unsigned long long> dn;
+	HIPCHK(dn.reset(1));
 	unsigned long long hn = 0;
-	hipError_t e = hipMemsetAsync(dn, 0, sizeof *dn, ix->dense_st);
+	hipError_t e = hipMemsetAsync(dn, 0, sizeof hn, ix->dense_st);
 	if(e == hipSuccess) {
-		hipLaunchKernelGGL(k_lsa_dense_check, dim3(l.n < 8192u ? l.n : 8192u), dim3(256), 0, ix->dense_st, ix->dls, l.lsa_base, l.lsa, dn);
+		hipLaunchKernelGGL(k_lsa_dense_check, dim3(l.n < 8192u ? l.n : 8192u), dim3(256), 0, ix->dense_st, ix->dls, l.lsa_base, l.lsa, dn.get());
 		e = hipGetLastError();
 	}
 	if(e == hipSuccess) e = hipMemcpyAsync(&hn, dn, sizeof hn, hipMemcpyDeviceToHost, ix->dense_st);
 	if(e == hipSuccess) e = hipStreamSynchronize(ix->dense_st);
-	(void)hipFree(dn);
 	if(e != hipSuccess) return (h2g_status)set_err("h2g_index_dense_lsa_check", e);
 	*rows_differ = hn;
 	return H2G_OK;
 }
 
-extern "C" void h2g_index_free(h2g_index* ix) {
-	if(!ix) return;
-	if(ix->dense_st) {
-		(void)hipSetDevice(ix->device); (void)hipStreamSynchronize(ix->dense_st);
-		if(ix->dense_ev) (void)hipEventDestroy(ix->dense_ev);
-		if(ix->lsa_ev) (void)hipEventDestroy(ix->lsa_ev);
-		(void)hipStreamDestroy(ix->dense_st);
-	}
-	for(void* p : ix->d_ssdb) if(p) (void)hipFree(p);
-	for(void* p : ix->allocs) (void)hipFree(p);
-	delete ix;
-}
+extern "C" void h2g_index_free(h2g_index* ix) { delete ix; }      // (~h2g_index waits for the dense tables' builds; the handles do the rest)
 
 // ------------------------------------------------------------------------------------------ synthetic sides
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
@@ -825,30 +830,35 @@ static h2g_status synth_sides(uint64_t num_sides, uint64_t seed, int device, uin
 	int ndev = 0;
 	if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { snprintf(g_err, sizeof g_err, "no HIP device"); return H2G_ERR_DEVICE; }
 	HIPCHK(hipSetDevice(device));
-	h2g_index* ix = new h2g_index();
+	IndexPtr ixp(new h2g_index());
+	h2g_index* const ix = ixp.get();
 	ix->synthetic = true;
 	ix->device = device;
-	void *sides = nullptr, *cnt = nullptr, *tot = nullptr;
+	DevBuf<uint8_t> sbuf;
+	DevBuf<uint32_t> cnt, tot, chunk;                        // scratch of this call
 	const size_t bytes = num_sides * sideSz + 256;
-	{   // measurement knob: H2G_SIDES_MTYPE=uncached|finegrained allocates the side array with that memory type
+	{   // measurement knob: H2G_SIDES_MTYPE=uncached|finegrained allocates the side array with that memory type (adopted by the handle: hipFree takes either)
 		const char* mt = getenv("H2G_SIDES_MTYPE");
-		if(mt && !strcmp(mt, "uncached")) HIPCHK(hipExtMallocWithFlags(&sides, bytes, hipDeviceMallocUncached));
-		else if(mt && !strcmp(mt, "finegrained")) HIPCHK(hipExtMallocWithFlags(&sides, bytes, hipDeviceMallocFinegrained));
-		else HIPCHK(hipMalloc(&sides, bytes));
+		const bool unc = mt && !strcmp(mt, "uncached");
+		if(unc || (mt && !strcmp(mt, "finegrained"))) {
+			void* p = nullptr;
+			HIPCHK(hipExtMallocWithFlags(&p, bytes, unc ? hipDeviceMallocUncached : hipDeviceMallocFinegrained));
+			sbuf = DevBuf<uint8_t>((uint8_t*)p, bytes);
+		}
+		else HIPCHK(sbuf.reset(bytes));
 	}
-	HIPCHK(hipMalloc(&cnt, num_sides * 16));
-	HIPCHK(hipMalloc(&tot, 16));
-	ix->allocs.push_back(sides);
+	uint8_t* const sides = sbuf;
+	HIPCHK(cnt.reset(num_sides * 4));
+	HIPCHK(tot.reset(4));
+	ix->allocs.push_back(std::move(sbuf));
 	ix->device_bytes = num_sides * sideSz;
-	hipLaunchKernelGGL(k_synth_fill, dim3((unsigned)((num_sides + 255) / 256)), dim3(256), 0, 0, (uint8_t*)sides, (uint32_t*)cnt, num_sides, seed, sideSz);
-	void* chunk = nullptr;
-	HIPCHK(hipMalloc(&chunk, SYNTH_CHUNKS * 16));
-	hipLaunchKernelGGL(k_synth_chunk_sum, dim3(SYNTH_CHUNKS / 256), dim3(256), 0, 0, (const uint32_t*)cnt, num_sides, (uint32_t*)chunk);
-	hipLaunchKernelGGL(k_synth_chunk_scan, dim3(1), dim3(64), 0, 0, (uint32_t*)chunk, (uint32_t*)tot);
-	hipLaunchKernelGGL(k_synth_write, dim3(SYNTH_CHUNKS / 256), dim3(256), 0, 0, (uint8_t*)sides, (const uint32_t*)cnt, num_sides, (const uint32_t*)chunk, sideSz);
+	hipLaunchKernelGGL(k_synth_fill, dim3((unsigned)((num_sides + 255) / 256)), dim3(256), 0, 0, sides, cnt.get(), num_sides, seed, sideSz);
+	HIPCHK(chunk.reset(SYNTH_CHUNKS * 4));
+	hipLaunchKernelGGL(k_synth_chunk_sum, dim3(SYNTH_CHUNKS / 256), dim3(256), 0, 0, (const uint32_t*)cnt, num_sides, chunk.get());
+	hipLaunchKernelGGL(k_synth_chunk_scan, dim3(1), dim3(64), 0, 0, chunk.get(), tot.get());
+	hipLaunchKernelGGL(k_synth_write, dim3(SYNTH_CHUNKS / 256), dim3(256), 0, 0, sides, (const uint32_t*)cnt, num_sides, (const uint32_t*)chunk, sideSz);
 	uint32_t totals[4];
-	HIPCHK(hipMemcpy(totals, tot, 16, hipMemcpyDeviceToHost));
-	(void)hipFree(cnt); (void)hipFree(tot); (void)hipFree(chunk);
+	HIPCHK(hipMemcpy(totals, tot, 16, hipMemcpyDeviceToHost));      // (waits for the kernels: the scratch goes at the end of the call)
 	GfmParams& p = ix->host.g.p;
 	uint32_t len = (uint32_t)(num_sides * syms - 1);
 	if(sideSz == 64) p.init(len, len + 1, len + 1, 6, 4, 10, 0, 4);
@@ -857,9 +867,9 @@ static h2g_status synth_sides(uint64_t num_sides, uint64_t seed, int device, uin
 	ix->host.g.fchr[0] = 0;
 	for(int c = 0; c < 4; c++) ix->host.g.fchr[c + 1] = ix->host.g.fchr[c] + totals[c];
 	fill_dgfm(ix->host.g, 16, &ix->dg);
-	ix->dg.sides = (const uint8_t*)sides;
+	ix->dg.sides = sides;
 	ix->dg.nZ = 0;
-	*out = ix;
+	*out = ixp.release();
 	return H2G_OK;
 }
 extern "C" h2g_status h2g_index_synth_sides(uint64_t num_sides, uint64_t seed, int device, h2g_index** out) {
@@ -879,32 +889,30 @@ extern "C" h2g_status h2g_index_synth_graph_sides(uint64_t num_sides, uint64_t s
 extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t max_bases, h2g_stream** out) {
 	if(!ix || !out) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(ix->device));
-	h2g_stream* s = new h2g_stream();
+	std::unique_ptr<h2g_stream, StreamFree> sp(new h2g_stream());      // (every early return below gives back what exists by then)
+	h2g_stream* const s = sp.get();
 	s->ix = ix; s->max_reads = max_reads; s->max_bases = max_bases;
 	// Every HIP stream of the context is created here, in this order, whatever the rotation will be: the runtime places a stream on a hardware queue by its place among the
 	// process's streams, and the place decides which launches serialise (profiles/r08_mstreams.md §2: the same two machine streams in rotation, created on first use
 	// behind the drain stream, 18.4 ms per step; created here, 10.8).  A stream that never enters the rotation never runs a kernel, holds no pools and costs nothing.
-	HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { HIPCHK(hipStreamCreateWithFlags(&s->mst[k], hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&s->ev_rot[k], hipEventDisableTiming)); }
-	HIPCHK(hipStreamCreateWithFlags(&s->dst, hipStreamNonBlocking));
-	HIPCHK(hipHostMalloc((void**)&s->h_fast_args, sizeof(FastArgs) * 2 * H2G_NBUF));
-	HIPCHK(hipHostMalloc((void**)&s->h_bails, 4 * H2G_NBUF)); for(int k = 0; k < H2G_NBUF; k++) s->h_bails[k] = 0;
-	for(int k = 0; k < H2G_NBUF; k++) { HIPCHK(hipEventCreateWithFlags(&s->ev_fast[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_mach[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_bails[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->ev_drain[k], hipEventDisableTiming)); }
-	for(int k = 0; k < H2G_FAST_POOLS; k++) HIPCHK(hipEventCreateWithFlags(&s->ev_pool[k], hipEventDisableTiming));
-	for(int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&s->ev_dr[k]));
-	for(int i = 0; i < 14; i++) HIPCHK(hipEventCreate(&s->ev[i]));
-	HIPCHK(hipMalloc((void**)&s->d_counters, H2G_NBUF * H2G_CNT_BLOCK * sizeof(unsigned long long)));
-	HIPCHK(hipMemset(s->d_counters, 0, H2G_NBUF * H2G_CNT_BLOCK * sizeof(unsigned long long)));
+	HIPCHK(s->st.create(hipStreamNonBlocking));
+	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { HIPCHK(s->mst[k].create(hipStreamNonBlocking)); HIPCHK(s->ev_rot[k].create(hipEventDisableTiming)); }
+	HIPCHK(s->dst.create(hipStreamNonBlocking));
+	HIPCHK(s->h_fast_args.ensure(2 * H2G_NBUF));
+	HIPCHK(s->h_bails.ensure(H2G_NBUF)); for(int k = 0; k < H2G_NBUF; k++) s->h_bails[k] = 0;
+	for(int k = 0; k < H2G_NBUF; k++) { HIPCHK(s->ev_fast[k].create(hipEventDisableTiming)); HIPCHK(s->ev_mach[k].create(hipEventDisableTiming)); HIPCHK(s->ev_bails[k].create(hipEventDisableTiming)); HIPCHK(s->ev_drain[k].create(hipEventDisableTiming)); }
+	for(int k = 0; k < H2G_FAST_POOLS; k++) HIPCHK(s->ev_pool[k].create(hipEventDisableTiming));
+	for(int k = 0; k < 2; k++) HIPCHK(s->ev_dr[k].create());
+	for(int i = 0; i < 14; i++) HIPCHK(s->ev[i].create());
+	HIPCHK(s->d_counters.ensure(H2G_NBUF * H2G_CNT_BLOCK));
+	HIPCHK(hipMemset(s->d_counters, 0, s->d_counters.bytes()));
 	s->cnt_cur = s->d_counters;
 	if(max_reads) {
-		BatchCtx& b0 = s->batch[0];
-		HIPCHK(hipMalloc((void**)&b0.d_codes, max_bases + 64));
-		HIPCHK(hipMalloc((void**)&b0.d_quals, max_bases + 64));
-		HIPCHK(hipMalloc((void**)&b0.d_offs, (max_reads + 1) * 4));
-		HIPCHK(hipMalloc((void**)&s->d_seed, max_reads * 2 * sizeof(h2g_seed_result)));
+		HIPCHK(s->batch[0].ensure_reads(max_reads, max_bases));
+		HIPCHK(s->d_seed.ensure(max_reads * 2));
 		// (a strand without coordinates leaves its `ext` entries as they are: zero, whatever block the allocator hands out — a recycled one made tests/test_gpu_frag.py's
 		// seed stage differ from the oracle's zero-filled rows)
-		HIPCHK(hipMemset(s->d_seed, 0, max_reads * 2 * sizeof(h2g_seed_result)));
+		HIPCHK(hipMemset(s->d_seed, 0, s->d_seed.bytes()));
 	}
 	memset(&s->last, 0, sizeof s->last);
 	{
@@ -920,38 +928,11 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		if(getenv("H2G_MSTREAMS")) s->mstreams = clampm(env("H2G_MSTREAMS", 0));   // pinned
 		s->mstreams_light = clampm(env("H2G_MSTREAMS_LIGHT", H2G_MSTREAMS_LIGHT_DEFAULT));
 	}
-	*out = s;
+	*out = sp.release();
 	return H2G_OK;
 }
 
-extern "C" void h2g_stream_free(h2g_stream* s) {
-	if(!s) return;
-	(void)hipStreamSynchronize(s->st); (void)hipStreamSynchronize(s->dst); for(unsigned k = 0; k < s->n_mst; k++) (void)hipStreamSynchronize(s->mst[k]);
-	(void)hipFree(s->d_seed);
-	(void)hipFree(s->d_counters); for(int k = 0; k < 2 * H2G_MSTREAMS_MAX; k++) { (void)hipFree(s->pool[k].ws); (void)hipFree(s->pool[k].gws); (void)hipFree(s->pool[k].sw); (void)hipFree(s->pool[k].sc); }
-	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) (void)hipFree(s->d_ovf_list[k]);
-	for(int k = 0; k < H2G_NBUF; k++) { (void)hipFree(s->d_bail_list[k]); (void)hipFree(s->d_fast_args[k]); (void)hipFree(s->d_fast_args[H2G_NBUF + k]); (void)hipFree(s->d_orphans[k]); (void)hipEventDestroy(s->ev_fast[k]); (void)hipEventDestroy(s->ev_mach[k]); (void)hipEventDestroy(s->ev_bails[k]); (void)hipEventDestroy(s->ev_drain[k]); }
-	for(int k = 0; k < H2G_FAST_POOLS; k++) { (void)hipFree(s->d_fast_slots[k]); (void)hipEventDestroy(s->ev_pool[k]); }
-	(void)hipFree(s->d_drain_slots); (void)hipFree(s->d_drain_sc);
-	for(int k = 0; k < 2; k++) (void)hipEventDestroy(s->ev_dr[k]);
-	(void)hipFree(s->d_fast_gws); (void)hipFree(s->d_fast_sc); (void)hipFree(s->d_sw_ws); (void)hipFree(s->d_sw_states); (void)hipFree(s->dbg_buf);
-	(void)hipFree(s->d_paln_ovf); (void)hipFree(s->d_xlp_at); (void)hipFree(s->d_xlp); (void)hipFree(s->d_xlp_cur); (void)hipFree(s->d_ledits); (void)hipFree(s->d_ledits_cur); (void)hipFree(s->d_warm_cnt); (void)hipFree(s->d_warm_rows);
-	for(const BatchCtx& B : s->batch) {
-		(void)hipFree(B.d_codes); (void)hipFree(B.d_offs); (void)hipFree(B.d_quals); (void)hipFree(B.d_names); (void)hipFree(B.d_name_offs); (void)hipFree(B.d_codes2); (void)hipFree(B.d_offs2);
-		(void)hipFree(B.d_quals2); (void)hipFree(B.d_names2); (void)hipFree(B.d_name_offs2); (void)hipFree(B.d_rout); (void)hipFree(B.d_aln); (void)hipFree(B.d_pout); (void)hipFree(B.d_paln[0]); (void)hipFree(B.d_paln[1]);
-		(void)hipFree(B.d_seeds);
-		(void)hipFree(B.d_qc);
-		(void)hipFree(B.d_ids);
-	}
-	for(int i = 0; i < 4; i++) (void)hipFree(s->d_tmp[i]);
-	for(int i = 0; i < 5; i++) (void)hipFree(s->d_sam[i]);
-	for(int i = 0; i < 4; i++) if(s->ev_sam[i]) (void)hipEventDestroy(s->ev_sam[i]);
-	for(int i = 0; i < 5; i++) (void)hipFree(s->d_plan[i]);
-	for(int i = 0; i < 4; i++) if(s->ev_plan[i]) (void)hipEventDestroy(s->ev_plan[i]);
-	for(int i = 0; i < 14; i++) (void)hipEventDestroy(s->ev[i]);
-	(void)hipStreamDestroy(s->st); (void)hipStreamDestroy(s->dst); for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { (void)hipStreamDestroy(s->mst[k]); (void)hipEventDestroy(s->ev_rot[k]); } (void)hipHostFree(s->h_bails); (void)hipHostFree(s->h_fast_args);
-	delete s;
-}
+extern "C" void h2g_stream_free(h2g_stream* s) { delete s; }      // (~h2g_stream waits for everything queued; the handles give the rest back)
 
 // the machine streams, when one may hold work (st2_busy): waits for every one of them, then clears the flag
 static hipError_t sync_mach(h2g_stream* s) {
@@ -982,50 +963,37 @@ extern "C" h2g_status h2g_stream_select_batch(h2g_stream* s, unsigned k) {
 	HIPCHK(hipSetDevice(s->ix->device));
 	const BatchCtx& out = s->cur();
 	BatchCtx& in = s->batch[k];
-	if(s->max_reads) {      // first use: the read buffers h2g_stream_create gives batch 0
-		if(!in.d_codes) HIPCHK(hipMalloc((void**)&in.d_codes, s->max_bases + 64));
-		if(!in.d_quals) HIPCHK(hipMalloc((void**)&in.d_quals, s->max_bases + 64));
-		if(!in.d_offs) HIPCHK(hipMalloc((void**)&in.d_offs, (s->max_reads + 1) * 4));
-	}
+	if(s->max_reads) HIPCHK(in.ensure_reads(s->max_reads, s->max_bases));      // first use: the read buffers h2g_stream_create gives batch 0
 	// ... and result rows as large as the rows of the batch that is leaving (the option set a streaming caller runs every batch with): a batch's first run then
-	// allocates nothing — an allocation of gigabytes in the middle of a queue of runs waits for all of them.  (Their sizes are recorded once every allocation has succeeded.)
-	if(!in.d_pout && out.d_pout && out.paln_alloc) {
-		HIPCHK(hipMalloc((void**)&in.d_pout, s->max_reads * sizeof(PairOut)));
-		for(int m = 0; m < 2; m++) if(!in.d_paln[m]) HIPCHK(hipMalloc((void**)&in.d_paln[m], out.paln_alloc * sizeof(h2g_alnres)));
-		in.paln_alloc = out.paln_alloc; in.pair_slots = out.pair_slots;
+	// allocates nothing — an allocation of gigabytes in the middle of a queue of runs waits for all of them.  Every buffer knows what it holds, and each block is entered
+	// while its last buffer is missing: a call that failed half way is completed by the next one (or by the batch's first run, go_rows).
+	if(!in.d_paln[1] && out.d_pout && out.d_paln[1]) {
+		HIPCHK(in.d_pout.ensure(s->max_reads));
+		for(int m = 0; m < 2; m++) HIPCHK(in.d_paln[m].reserve(out.d_paln[m].size()));
+		in.pair_slots = out.pair_slots;
 		// (written once here: the first kernel to store into fresh device memory pays for its mapping — measured in bench.py's loop, lease F: 20 timed steps over 10 batches
 		// of which 5 had never been run took 18.5 ms each, 60 steps 12.1)
-		HIPCHK(hipMemsetAsync(in.d_pout, 0, s->max_reads * sizeof(PairOut), s->st));
-		for(int m = 0; m < 2; m++) HIPCHK(hipMemsetAsync(in.d_paln[m], 0, out.paln_alloc * sizeof(h2g_alnres), s->st));
+		HIPCHK(hipMemsetAsync(in.d_pout, 0, in.d_pout.bytes(), s->st));
+		for(int m = 0; m < 2; m++) HIPCHK(hipMemsetAsync(in.d_paln[m], 0, in.d_paln[m].bytes(), s->st));
 	}
-	if(!in.d_rout && out.d_rout && out.aln_alloc) {
-		HIPCHK(hipMalloc((void**)&in.d_rout, s->max_reads * sizeof(ReadOut)));
-		if(!in.d_aln) HIPCHK(hipMalloc((void**)&in.d_aln, out.aln_alloc * sizeof(h2g_alnres)));
-		in.aln_alloc = out.aln_alloc; in.aln_slots = out.aln_slots;
-		HIPCHK(hipMemsetAsync(in.d_rout, 0, s->max_reads * sizeof(ReadOut), s->st));
-		HIPCHK(hipMemsetAsync(in.d_aln, 0, out.aln_alloc * sizeof(h2g_alnres), s->st));
+	if(!in.d_aln && out.d_rout && out.d_aln) {
+		HIPCHK(in.d_rout.ensure(s->max_reads));
+		HIPCHK(in.d_aln.reserve(out.d_aln.size()));
+		in.aln_slots = out.aln_slots;
+		HIPCHK(hipMemsetAsync(in.d_rout, 0, in.d_rout.bytes(), s->st));
+		HIPCHK(hipMemsetAsync(in.d_aln, 0, in.d_aln.bytes(), s->st));
 	}
 	s->cur_batch = k;
 	s->tmp_gen++;
 	return H2G_OK;
 }
 
-// Growth of a device buffer (or of n buffers of one size): when *have < want, frees them, allocates want x unit bytes each and records want.
-// A failed allocation leaves *have at 0, so the next call allocates again.
-static int grow(void** p, size_t* have, size_t want, size_t unit = 1, int n = 1) {
-	if(*have >= want) return H2G_OK;
-	for(int k = 0; k < n; k++) { (void)hipFree(p[k]); p[k] = nullptr; }
-	*have = 0;
-	for(int k = 0; k < n; k++) HIPCHK(hipMalloc(&p[k], want * unit));
-	*have = want;
-	return H2G_OK;
-}
-
+// scratch slot `slot` of the stream with room for `bytes` (and 256 beyond: the largest request so far)
 static int tmp_buf(h2g_stream* s, int slot, size_t bytes, void** out) {
 	s->tmp_gen++;                                                            // (whatever a compact fetch left here is about to be overwritten)
-	const int rc = grow(&s->d_tmp[slot], &s->tmp_sz[slot], bytes + 256);     // (tmp_sz: the bytes allocated, 256 beyond the largest request)
+	const hipError_t e = s->d_tmp[slot].reserve(bytes + 256);
 	*out = s->d_tmp[slot];
-	return rc;
+	return e == hipSuccess ? H2G_OK : set_err("tmp_buf", e);
 }
 
 extern "C" h2g_status h2g_set_reads(h2g_stream* s, const uint8_t* codes, const uint32_t* offs, const char* quals, size_t n) {
@@ -1425,7 +1393,7 @@ __global__ __launch_bounds__(512) void k_rank_chain(DGfm g, uint64_t seed, int s
 // out[j] = result j * stride of the LAST h2g_rank_bench_synth run of this stream (its device buffer is still there): what a sampled comparison with the
 // CPU's mapLF needs of a 2^28-query run
 extern "C" h2g_status h2g_rank_bench_synth_sample(h2g_stream* s, size_t stride, size_t nsample, uint32_t* out) {
-	if(!s || !out || stride == 0 || nsample == 0 || !s->d_tmp[2] || s->tmp_sz[2] < ((nsample - 1) * stride + 1) * 4) return H2G_ERR_ARG;
+	if(!s || !out || stride == 0 || nsample == 0 || s->d_tmp[2].size() < ((nsample - 1) * stride + 1) * 4) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
 	HIPCHK(sync_all(s));
 	HIPCHK(hipMemcpy2D(out, 4, s->d_tmp[2], stride * 4, 4, nsample, hipMemcpyDeviceToHost));
@@ -2024,10 +1992,10 @@ extern "C" h2g_status h2g_sw_align(h2g_stream* s, const h2g_sw_query* q, size_t 
 	if(batch < 256) batch = 256;
 	if(batch > n) batch = n;
 	const size_t bt_threads = ((batch + 255) / 256) * 256;
-	if((rc = grow((void**)&s->d_sw_ws, &s->sw_ws_bytes, batch * ws.stride))) return rc;
-	if(s->sw_states < bt_threads) {
-		if((rc = grow((void**)&s->d_sw_states, &s->sw_states, bt_threads, sizeof(SwLaneState)))) return rc;
-		HIPCHK(hipMemset(s->d_sw_states, 0, bt_threads * sizeof(SwLaneState)));   // mask-table generations start at 0
+	HIPCHK(s->d_sw_ws.reserve(batch * ws.stride));
+	if(s->d_sw_states.size() < bt_threads) {
+		HIPCHK(s->d_sw_states.reserve(bt_threads));
+		HIPCHK(hipMemset(s->d_sw_states, 0, s->d_sw_states.bytes()));   // mask-table generations start at 0
 	}
 	ws.base = s->d_sw_ws;
 	void *dq, *dout;
@@ -2194,13 +2162,7 @@ extern "C" h2g_status h2g_set_read_names(h2g_stream* s, const char* bytes, const
 	HIPCHK(hipSetDevice(s->ix->device));
 	BatchCtx& B = s->cur();
 	size_t nb = offs[n];
-	if(B.names_cap < nb || !B.d_name_offs) {
-		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
-		B.d_names = nullptr; B.d_name_offs = nullptr;
-		HIPCHK(hipMalloc((void**)&B.d_names, nb + 64));
-		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
-		B.names_cap = nb;
-	}
+	HIPCHK(B.reserve_names(nb, s->max_reads));
 	HIPCHK(hipMemcpyAsync(B.d_names, bytes, nb, hipMemcpyHostToDevice, s->st));
 	HIPCHK(hipMemcpyAsync(B.d_name_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
@@ -2218,14 +2180,7 @@ extern "C" h2g_status h2g_set_mates(h2g_stream* s, const uint8_t* codes2, const 
 	BatchCtx& B = s->cur();
 	for(size_t i = 0; i < n; i++) { const uint32_t l = offs2[i + 1] - offs2[i]; if(l > B.max_read_len) B.max_read_len = l; }
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(!B.d_codes2) {
-		HIPCHK(hipMalloc((void**)&B.d_codes2, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&B.d_quals2, s->max_bases + 64));
-		HIPCHK(hipMalloc((void**)&B.d_offs2, (s->max_reads + 1) * 4));
-		HIPCHK(hipMalloc((void**)&B.d_name_offs2, (s->max_reads + 1) * 4));
-	}
-	(void)hipFree(B.d_names2); B.d_names2 = nullptr;
-	HIPCHK(hipMalloc((void**)&B.d_names2, noffs2[n] + 64));
+	HIPCHK(B.ensure_mates(s->max_reads, s->max_bases, noffs2[n]));
 	HIPCHK(hipMemcpyAsync(B.d_codes2, codes2, offs2[n], hipMemcpyHostToDevice, s->st));
 	HIPCHK(hipMemcpyAsync(B.d_offs2, offs2, (n + 1) * 4, hipMemcpyHostToDevice, s->st));
 	B.has_quals2 = quals2 != nullptr;
@@ -2244,7 +2199,7 @@ extern "C" h2g_status h2g_set_read_seeds(h2g_stream* s, const uint32_t* seeds1, 
 	if(!seeds1) { B.has_seeds = B.has_seeds2 = false; return H2G_OK; }
 	if(n != B.n_reads || n == 0) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(!B.d_seeds) HIPCHK(hipMalloc((void**)&B.d_seeds, 2 * s->max_reads * sizeof(uint32_t)));
+	HIPCHK(B.d_seeds.ensure(2 * s->max_reads));
 	HIPCHK(hipMemcpyAsync(B.d_seeds, seeds1, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
 	if(seeds2) HIPCHK(hipMemcpyAsync(B.d_seeds + s->max_reads, seeds2, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
@@ -2260,7 +2215,7 @@ extern "C" h2g_status h2g_set_read_ids(h2g_stream* s, const uint32_t* ids) {
 	const size_t n = B.n_reads;
 	if(n == 0 || n > s->max_reads) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(!B.d_ids) HIPCHK(hipMalloc((void**)&B.d_ids, s->max_reads * sizeof(uint32_t)));
+	HIPCHK(B.d_ids.ensure(s->max_reads));
 	HIPCHK(hipMemcpyAsync(B.d_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
 	HIPCHK(sync_all(s));
 	B.has_ids = true;
@@ -2333,14 +2288,8 @@ extern "C" h2g_status h2g_set_reads_windows(h2g_stream* s, const uint8_t* text, 
 	memset(&ds[n_segs], 0, sizeof ds[n_segs]);
 	ds[n_segs].first_read = (uint32_t)n; ds[n_segs].name_first = (uint32_t)nb;
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(B.names_cap < nb || !B.d_name_offs) {      // (grows as h2g_set_read_names does)
-		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
-		B.d_names = nullptr; B.d_name_offs = nullptr; B.names_cap = 0;
-		HIPCHK(hipMalloc((void**)&B.d_names, nb + 64));
-		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
-		B.names_cap = nb;
-	}
-	if(!B.d_ids) HIPCHK(hipMalloc((void**)&B.d_ids, s->max_reads * sizeof(uint32_t)));
+	HIPCHK(B.reserve_names(nb, s->max_reads));
+	HIPCHK(B.d_ids.ensure(s->max_reads));
 	void *d_text, *d_segs, *d_pre;
 	int rc;
 	if((rc = tmp_buf(s, 0, hi - lo, &d_text)) || (rc = tmp_buf(s, 1, ds.size() * sizeof(h2g_win::DSeg), &d_segs)) || (rc = tmp_buf(s, 2, n_prefix_bytes, &d_pre))) return (h2g_status)rc;
@@ -2407,7 +2356,7 @@ extern "C" h2g_status h2g_set_read_filter(h2g_stream* s, const uint8_t* pass1, c
 	const size_t n = B.n_reads;
 	if(n == 0 || n > s->max_reads) return H2G_ERR_ARG;
 	HIPCHK(hipSetDevice(s->ix->device));
-	if(!B.d_qc) HIPCHK(hipMalloc((void**)&B.d_qc, 2 * s->max_reads));
+	HIPCHK(B.d_qc.ensure(2 * s->max_reads));
 	// a set without bytes passes as a whole
 	if(pass1) HIPCHK(hipMemcpyAsync(B.d_qc, pass1, n, hipMemcpyHostToDevice, s->st)); else HIPCHK(hipMemsetAsync(B.d_qc, 1, n, s->st));
 	if(pass2) HIPCHK(hipMemcpyAsync(B.d_qc + s->max_reads, pass2, n, hipMemcpyHostToDevice, s->st)); else HIPCHK(hipMemsetAsync(B.d_qc + s->max_reads, 1, n, s->st));
@@ -2477,15 +2426,14 @@ static const FastUnitDesc& fast_unit(bool linear, bool spliced, bool align_mate)
 static int go_pool_for(h2g_stream* s, int which, const GoUnitDesc& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
 	h2g_stream::GoPool& pl = s->pool[which];
 	const size_t wsb = u.ws_bytes, gwb = u.gws_bytes;
-	int rc;
-	if((rc = grow((void**)&pl.ws, &pl.ws_bytes, slots * wsb))) return rc;
+	HIPCHK(pl.ws.reserve(slots * wsb));
 	a->pool = pl.ws; a->ws_stride = wsb; a->slot_off = u.slot_off; a->gsl_off = u.gsl_off;
 	a->gws_base = nullptr; a->gws_stride = gwb;
 	if(gwb) {
-		if((rc = grow((void**)&pl.gws, &pl.gws_bytes, lanes * gwb))) return rc;
+		HIPCHK(pl.gws.reserve(lanes * gwb));
 		a->gws_base = pl.gws;
 	}
-	if((rc = grow((void**)&pl.sc, &pl.sc_bytes, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))))) return rc;
+	HIPCHK(pl.sc.reserve(lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))));
 	a->sc_base = pl.sc;
 	a->sw_base = nullptr; a->sw_stride = 0;
 	if(bowtie2_dp) {
@@ -2494,8 +2442,8 @@ static int go_pool_for(h2g_stream* s, int which, const GoUnitDesc& u, size_t slo
 		for(uint32_t l = 1; l <= swlen && !wide; l++) wide = sw_wide_for(min_score_for(a->P, l));
 		const size_t stride = (u.sw_bytes(swlen, wide ? 1 : 0) + 255) & ~(size_t)255;   // the unit's own SwLaneState (the large-workspace units hold 192-edit records)
 		if(pl.sw_stride < stride || pl.sw_lanes < lanes) {      // (either one short: the pool is allocated again)
-			size_t had = 0; pl.sw_stride = 0; pl.sw_lanes = 0;
-			if((rc = grow((void**)&pl.sw, &had, stride * lanes))) return rc;
+			pl.sw_stride = 0; pl.sw_lanes = 0;
+			HIPCHK(pl.sw.reset(stride * lanes));
 			HIPCHK(hipMemset(pl.sw, 0, stride * lanes));   // SwLaneState: mask-table generations start at 0
 			pl.sw_stride = stride; pl.sw_lanes = lanes;
 		}
@@ -2692,12 +2640,12 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, &scratch))) return rc;
 			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &scratch))) return rc;
 			// ... and its overflow list
-			if(!s->d_ovf_list[m]) { HIPCHK(hipMalloc((void**)&s->d_ovf_list[m], (s->max_reads + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
+			if(!s->d_ovf_list[m]) { HIPCHK(s->d_ovf_list[m].ensure(s->max_reads + 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
 		}
 		for(unsigned b = 0; b < g.M + 1; b++) {      // the per-run buffers of every generation
-			if(!s->d_bail_list[b]) HIPCHK(hipMalloc((void**)&s->d_bail_list[b], (s->max_reads + 4) * 4));
-			if(!s->d_fast_args[b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[b], sizeof(FastArgs)));
-			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
+			HIPCHK(s->d_bail_list[b].ensure(s->max_reads + 4));
+			HIPCHK(s->d_fast_args[b].ensure(1));
+			HIPCHK(s->d_fast_args[H2G_NBUF + b].ensure(1));
 		}
 	}
 	return go_pool_for(s, g.fast ? 2 * (int)((s->gen % g.M) % g.S) : 0, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, A);
@@ -2707,21 +2655,20 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const GoPlan& g, GoRun* r) {
 	BatchCtx& b = s->cur();
 	GoArgs& A = r->A;
-	int rc;
 	memset(&A.O, 0, sizeof A.O);
 	if(!paired) {
-		if(!b.d_rout) HIPCHK(hipMalloc((void**)&b.d_rout, s->max_reads * sizeof(ReadOut)));
+		HIPCHK(b.d_rout.ensure(s->max_reads));
 		const uint32_t slots = p->khits;
-		if((rc = grow((void**)&b.d_aln, &b.aln_alloc, s->max_reads * (size_t)slots, sizeof(h2g_alnres)))) return rc;
+		HIPCHK(b.d_aln.reserve(s->max_reads * (size_t)slots));
 		b.aln_slots = slots;
 		A.O.rout = b.d_rout; A.O.aln = b.d_aln; A.O.aln_slots = slots;
 	} else {
-		if(!b.d_pout) HIPCHK(hipMalloc((void**)&b.d_pout, s->max_reads * sizeof(PairOut)));
+		HIPCHK(b.d_pout.ensure(s->max_reads));
 		// a mate can report more alignments than -k before the pair is settled: 2 k + 4 slots, at least H2G_PAIR_RES_CAP
 		uint32_t pslots = p->khits * 2 + 4;
 		if(pslots < H2G_PAIR_RES_CAP) pslots = H2G_PAIR_RES_CAP;
 		if(s->tune.pair_slots > 0) pslots = (uint32_t)s->tune.pair_slots;   // test knob: tiny rows push pairs through the overflow area (dense fetch only)
-		if((rc = grow((void**)b.d_paln, &b.paln_alloc, s->max_reads * (size_t)pslots, sizeof(h2g_alnres), 2))) return rc;
+		for(int m = 0; m < 2; m++) HIPCHK(b.d_paln[m].reserve(s->max_reads * (size_t)pslots));
 		b.pair_slots = pslots;
 		A.O.pout = b.d_pout; A.O.paln[0] = b.d_paln[0]; A.O.paln[1] = b.d_paln[1]; A.O.pair_slots = pslots;
 		// One part per lane: the machine passes of M queued runs may be in flight together and each takes its blocks
@@ -2730,8 +2677,8 @@ static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const 
 		if(s->paln_ovf_cap < ovf_cap || s->paln_ovf_parts < g.M) {
 			HIPCHK(sync_mach(s));
 			HIPCHK(hipStreamSynchronize(s->st));
-			size_t had = 0; s->paln_ovf_cap = 0; s->paln_ovf_parts = 0;
-			if((rc = grow((void**)&s->d_paln_ovf, &had, g.M * ovf_cap, sizeof(h2g_alnres)))) return rc;
+			s->paln_ovf_cap = 0; s->paln_ovf_parts = 0;
+			HIPCHK(s->d_paln_ovf.reset(g.M * ovf_cap));
 			s->paln_ovf_cap = ovf_cap; s->paln_ovf_parts = g.M;
 		}
 		A.O.ovf = s->d_paln_ovf;
@@ -2741,11 +2688,12 @@ static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const 
 		// the XL units' side area: a word per read, and per machine stream a part of lists with a cursor (an XL run is never behind a fast pass: it
 		// runs on the first stream and uses part 0, but the area is partitioned the way the overflow area is)
 		const size_t xcap = s->max_reads * 64 > ((size_t)1 << 20) ? s->max_reads * 64 : ((size_t)1 << 20);      // words per part
-		if(s->xlp_at_cap < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < g.M) {
+		if(s->d_xlp_at.size() < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < g.M) {
 			HIPCHK(hipStreamSynchronize(s->st));
-			size_t had = 0; s->xlp_at_cap = 0; s->xlp_cap = 0; s->xlp_parts = 0;
-			if((rc = grow((void**)&s->d_xlp_at, &s->xlp_at_cap, s->max_reads, 4)) || (rc = grow((void**)&s->d_xlp, &had, g.M * xcap, 4))) return rc;
-			if(!s->d_xlp_cur) HIPCHK(hipMalloc((void**)&s->d_xlp_cur, H2G_MSTREAMS_MAX * 4));
+			s->xlp_cap = 0; s->xlp_parts = 0;
+			HIPCHK(s->d_xlp_at.reset(s->max_reads));
+			HIPCHK(s->d_xlp.reset(g.M * xcap));
+			HIPCHK(s->d_xlp_cur.ensure(H2G_MSTREAMS_MAX));
 			s->xlp_cap = xcap; s->xlp_parts = g.M;
 		}
 		const unsigned part = 0;
@@ -2775,7 +2723,7 @@ static int go_counters(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	}
 	A.list = nullptr; A.nlist = nullptr;
 	if(s->tune.dbg_read >= 0) {
-		if(!s->dbg_buf) HIPCHK(hipMalloc((void**)&s->dbg_buf, (1u << 20) * 4));      // (the stream's own: a device's memory, not the process's)
+		HIPCHK(s->dbg_buf.ensure(1u << 20));      // (the stream's own: a device's memory, not the process's)
 		HIPCHK(hipMemsetAsync(s->dbg_buf, 0, (1u << 20) * 4, s->st));
 		A.dbg_buf = s->dbg_buf; A.dbg_read = (uint32_t)s->tune.dbg_read;
 	}
@@ -2844,32 +2792,29 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 	const size_t ocap = (size_t)256 * f.FU->slots, dbytes = (size_t)f.dgrid * f.DU->slots * f.DU->slot_bytes;
 	const size_t dsc = g.linear ? 0 : (size_t)f.dgrid * f.FU->threads * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
-	bool need = s->fast_slot_bytes[f.psel] < f.slot_bytes;
+	bool need = s->d_fast_slots[f.psel].size() < f.slot_bytes;
 	if(f.orphan_T) {
-		for(unsigned q = 0; q < H2G_FAST_POOLS; q++) need = need || s->fast_slot_bytes[q] < f.slot_bytes;
-		need = need || s->drain_slot_bytes < dbytes || s->drain_sc_bytes < dsc;
+		for(unsigned q = 0; q < H2G_FAST_POOLS; q++) need = need || s->d_fast_slots[q].size() < f.slot_bytes;
+		need = need || s->d_drain_slots.size() < dbytes || s->d_drain_sc.size() < dsc;
 		for(unsigned b = 0; b < g.M + 1; b++) need = need || !s->d_orphans[b] || !s->d_fast_args[H2G_NBUF + b];
 		need = need || s->orphan_cap < ocap;
 	}
 	if(!need) return H2G_OK;
 	// (every stream, whatever st2_busy and dst_busy say: the pools about to be freed may be any launch's)
 	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
-	auto grow_zeroed = [s](void** ptr, size_t* have, size_t want) -> int {     // (fresh memory is written once, on the first stream)
-		if(*have >= want) return H2G_OK;
-		const int rc = grow(ptr, have, want);
-		if(rc == H2G_OK) HIPCHK(hipMemsetAsync(*ptr, 0, want, s->st));
-		return rc;
-	};
-	int rc;
-	for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) if((rc = grow_zeroed((void**)&s->d_fast_slots[f.orphan_T ? q : f.psel], &s->fast_slot_bytes[f.orphan_T ? q : f.psel], f.slot_bytes))) return rc;
+	// (fresh memory is written once, on the first stream)
+	for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) {
+		DevBuf<uint8_t>& fs = s->d_fast_slots[f.orphan_T ? q : f.psel];
+		if(fs.size() < f.slot_bytes) { HIPCHK(fs.reserve(f.slot_bytes)); HIPCHK(hipMemsetAsync(fs, 0, f.slot_bytes, s->st)); }
+	}
 	if(f.orphan_T) {
-		if(s->orphan_cap < ocap) { for(int b = 0; b < H2G_NBUF; b++) { (void)hipFree(s->d_orphans[b]); s->d_orphans[b] = nullptr; } s->orphan_cap = ocap; }
+		if(s->orphan_cap < ocap) { for(int b = 0; b < H2G_NBUF; b++) s->d_orphans[b] = DevBuf<uint32_t>(); s->orphan_cap = ocap; }
 		for(unsigned b = 0; b < g.M + 1; b++) {
-			if(!s->d_orphans[b]) { HIPCHK(hipMalloc((void**)&s->d_orphans[b], (s->orphan_cap + 4) * 4)); HIPCHK(hipMemsetAsync(s->d_orphans[b], 0, (s->orphan_cap + 4) * 4, s->st)); }
-			if(!s->d_fast_args[H2G_NBUF + b]) HIPCHK(hipMalloc((void**)&s->d_fast_args[H2G_NBUF + b], sizeof(FastArgs)));
+			if(!s->d_orphans[b]) { HIPCHK(s->d_orphans[b].ensure(s->orphan_cap + 4)); HIPCHK(hipMemsetAsync(s->d_orphans[b], 0, (s->orphan_cap + 4) * 4, s->st)); }
+			HIPCHK(s->d_fast_args[H2G_NBUF + b].ensure(1));
 		}
-		if((rc = grow_zeroed((void**)&s->d_drain_slots, &s->drain_slot_bytes, dbytes))) return rc;
-		if((rc = grow_zeroed((void**)&s->d_drain_sc, &s->drain_sc_bytes, dsc))) return rc;
+		if(s->d_drain_slots.size() < dbytes) { HIPCHK(s->d_drain_slots.reserve(dbytes)); HIPCHK(hipMemsetAsync(s->d_drain_slots, 0, dbytes, s->st)); }
+		if(s->d_drain_sc.size() < dsc) { HIPCHK(s->d_drain_sc.reserve(dsc)); HIPCHK(hipMemsetAsync(s->d_drain_sc, 0, dsc, s->st)); }
 	}
 	HIPCHK(hipStreamSynchronize(s->st));
 	return H2G_OK;
@@ -2880,18 +2825,17 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	const FastPlan& f = r->f;
 	const GoArgs& A = r->A;
 	const unsigned gsel = r->gsel;
-	int rc;
 	// run k - 3's drain launch is done with this pool — and a run WITHOUT a drain launch (a small resident batch queued behind a large one) uses pool 0, which the drain launch
 	// of an earlier run may still be reading: every fast launch waits for the last reader of its pool
 	HIPCHK(hipStreamWaitEvent(s->st, s->ev_pool[f.psel], 0));
-	if(!s->d_bail_list[gsel]) HIPCHK(hipMalloc((void**)&s->d_bail_list[gsel], (s->max_reads + 4) * 4));
+	HIPCHK(s->d_bail_list[gsel].ensure(s->max_reads + 4));
 	uint32_t* const bl = s->d_bail_list[gsel];
 	HIPCHK(hipMemsetAsync(bl + s->max_reads, 0, 16, s->st));
 	FastArgs F;
 	memset(&F, 0, sizeof F);
 	F.g = A.g; F.ref = A.ref; F.ls = A.ls; F.rd1 = A.rd1; F.rd2 = A.rd2; F.P = A.P;
 	F.names1 = A.names1; F.noffs1 = A.noffs1; F.names2 = A.names2; F.noffs2 = A.noffs2;
-	F.slots = s->d_fast_slots[f.psel];
+	F.slots = (uint32_t*)s->d_fast_slots[f.psel].get();
 	F.O.rout = A.O.rout; F.O.aln = A.O.aln; F.O.aln_slots = A.O.aln_slots; F.O.pout = A.O.pout; F.O.paln[0] = A.O.paln[0]; F.O.paln[1] = A.O.paln[1]; F.O.pair_slots = A.O.pair_slots;
 	F.counters = r->cblk; F.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_FAST);
 	F.bail_list = bl; F.bail_count = bl + s->max_reads;
@@ -2903,11 +2847,11 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
 	if(!g.linear) {   // per-lane scratch of the graph primitives (every CU may hold a workgroup)
 		const size_t lanes = (size_t)256 * f.FU->threads;
-		if((rc = grow((void**)&s->d_fast_gws, &s->fast_gws_bytes, lanes * f.FU->gws_bytes)) ||
-		   (rc = grow((void**)&s->d_fast_sc, &s->fast_sc_bytes, lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))))) return rc;
+		HIPCHK(s->d_fast_gws.reserve(lanes * f.FU->gws_bytes));
+		HIPCHK(s->d_fast_sc.reserve(lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))));
 		F.gws_base = s->d_fast_gws; F.gws_stride = f.FU->gws_bytes; F.sc_base = s->d_fast_sc;
 	}
-	if(!s->d_fast_args[gsel]) HIPCHK(hipMalloc((void**)&s->d_fast_args[gsel], sizeof(FastArgs)));
+	HIPCHK(s->d_fast_args[gsel].ensure(1));
 	FastArgs D = F;
 	if(f.orphan_T) {
 		uint32_t* const ol = s->d_orphans[gsel];
@@ -2919,7 +2863,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		// the step (more than 1.5 % handed on: the policy of mach_total) they absorb the tail for nothing and a drain launch that runs to its last read would be the longer one
 		// (repeat-structured: 37.8 -> 39.0 ms with it): the tail stays.  A caller's own setting (H2G_FAST_TAIL, "tail") is kept as it is.
 		if(s->tune.tail_auto) D.tail = g.linear && paired && (size_t)s->last_bails * 1000 > g.units * 15 ? (uint32_t)H2G_DEFAULT_TAIL : 0u;
-		D.slots = s->d_drain_slots;
+		D.slots = (uint32_t*)s->d_drain_slots.get();
 		D.adopt_list = ol; D.adopt_count = ol + s->orphan_cap; D.adopt_slots = F.slots;
 		D.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_DRAIN);
 		D.cnt_off = H2G_CNT_DRAIN_OFF;                               // its own rank / side / step / aligned counters
@@ -2931,15 +2875,15 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	// pass), and the chip would idle while the host queues this run.  The staging block of this buffer set was last read by the upload
 	// of run k - H2G_NBUF, which is over once that run's fast pass is
 	if(s->gen >= g.M + 1 && hipEventQuery(s->ev_fast[gsel]) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipEventSynchronize(s->ev_fast[gsel])); }
-	FastArgs* const hF = reinterpret_cast<FastArgs*>(s->h_fast_args) + gsel;
+	FastArgs* const hF = s->h_fast_args + gsel;
 	*hF = F;
 	HIPCHK(hipMemcpyAsync(s->d_fast_args[gsel], hF, sizeof F, hipMemcpyHostToDevice, s->st));
 	if(f.orphan_T) {
-		FastArgs* const hD = reinterpret_cast<FastArgs*>(s->h_fast_args) + H2G_NBUF + gsel;
+		FastArgs* const hD = s->h_fast_args + H2G_NBUF + gsel;
 		*hD = D;
 		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
 	}
-	if(f.FU->launch(reinterpret_cast<const FastArgs*>(s->d_fast_args[gsel]), f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
+	if(f.FU->launch(s->d_fast_args[gsel], f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
 	r->A.list = bl; r->A.nlist = bl + s->max_reads;
 	return H2G_OK;
 }
@@ -2956,7 +2900,7 @@ static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
 		HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
 		HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
-		if(f.DU->launch_drain(reinterpret_cast<const FastArgs*>(s->d_fast_args[H2G_NBUF + gsel]), f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
+		if(f.DU->launch_drain(s->d_fast_args[H2G_NBUF + gsel], f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
 		HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
 		HIPCHK(hipEventRecord(s->ev_pool[f.psel], s->dst));
 		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
@@ -2977,7 +2921,7 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 	GoArgs& A = r->A;
 	const unsigned psel = r->psel, qsel = r->qsel;
 	s->ovf_cur = qsel;
-	if(!s->d_ovf_list[qsel]) HIPCHK(hipMalloc((void**)&s->d_ovf_list[qsel], (s->max_reads + 4) * 4));
+	HIPCHK(s->d_ovf_list[qsel].ensure(s->max_reads + 4));
 	r->ovl = s->d_ovf_list[qsel];
 	HIPCHK(hipMemsetAsync(r->ovl + s->max_reads, 0, 16, r->ms));
 	// the long-edit area: part psel and its cursor belong to this lane (the pass that used them last is over: it ran on the same stream, or go_rotation made this stream wait for it)
@@ -2986,10 +2930,9 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 		// (the flag stays: this run's own fast pass, already queued, has set it)
 		if(s->st2_busy) for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
 		HIPCHK(hipStreamSynchronize(s->st));
-		size_t had = 0; s->ledits_cap = 0; s->ledits_parts = 0;
-		int rc;
-		if((rc = grow((void**)&s->d_ledits, &had, g.M * lcap, sizeof(h2g_edit)))) return rc;
-		if(!s->d_ledits_cur) HIPCHK(hipMalloc((void**)&s->d_ledits_cur, H2G_MSTREAMS_MAX * 4));
+		s->ledits_cap = 0; s->ledits_parts = 0;
+		HIPCHK(s->d_ledits.reset(g.M * lcap));
+		HIPCHK(s->d_ledits_cur.ensure(H2G_MSTREAMS_MAX));
 		s->ledits_cap = lcap; s->ledits_parts = g.M;
 		for(unsigned m = 0; m < H2G_MSTREAMS_MAX; m++) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_ledits_cur + m), (int)(m < g.M ? m * lcap : 0), 1, s->st));
 		HIPCHK(hipStreamSynchronize(s->st));
@@ -3011,18 +2954,18 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, const GoRun& r) {
 	int rc;
 	const size_t warm_rows = (size_t)1 << 16;
-	if(!s->d_warm_cnt) { HIPCHK(hipMalloc((void**)&s->d_warm_cnt, H2G_CNT_BLOCK * sizeof(unsigned long long))); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
-	if(!s->d_warm_rows) { HIPCHK(hipMalloc((void**)&s->d_warm_rows, warm_rows)); HIPCHK(hipMemset(s->d_warm_rows, 0, warm_rows)); }
+	if(!s->d_warm_cnt) { HIPCHK(s->d_warm_cnt.ensure(H2G_CNT_BLOCK)); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
+	if(!s->d_warm_rows) { HIPCHK(s->d_warm_rows.ensure(warm_rows)); HIPCHK(hipMemset(s->d_warm_rows, 0, warm_rows)); }
 	for(unsigned m = 0; m < g.S; m++) {
 		if(m == r.ssel || ((s->warm_mask >> m) & 1u) || !s->d_ovf_list[m]) continue;
 		GoArgs W1 = r.A;
 		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.U->slots, (size_t)g.U->threads, p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
 		W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_MAIN);
-		W1.list = reinterpret_cast<uint32_t*>(s->d_warm_rows); W1.nlist = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_NO_SECOND);   // a count of zero
+		W1.list = reinterpret_cast<uint32_t*>(s->d_warm_rows.get()); W1.nlist = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_NO_SECOND);   // a count of zero
 		memset(&W1.O, 0, sizeof W1.O);
-		W1.O.rout = reinterpret_cast<ReadOut*>(s->d_warm_rows); W1.O.aln = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.aln_slots = r.A.O.aln_slots;
-		W1.O.pout = reinterpret_cast<PairOut*>(s->d_warm_rows); W1.O.paln[0] = W1.O.paln[1] = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.pair_slots = r.A.O.pair_slots;
-		W1.O.ovf = reinterpret_cast<h2g_alnres*>(s->d_warm_rows); W1.O.ledits = reinterpret_cast<h2g_edit*>(s->d_warm_rows);      // (both areas with a capacity of zero)
+		W1.O.rout = reinterpret_cast<ReadOut*>(s->d_warm_rows.get()); W1.O.aln = reinterpret_cast<h2g_alnres*>(s->d_warm_rows.get()); W1.O.aln_slots = r.A.O.aln_slots;
+		W1.O.pout = reinterpret_cast<PairOut*>(s->d_warm_rows.get()); W1.O.paln[0] = W1.O.paln[1] = reinterpret_cast<h2g_alnres*>(s->d_warm_rows.get()); W1.O.pair_slots = r.A.O.pair_slots;
+		W1.O.ovf = reinterpret_cast<h2g_alnres*>(s->d_warm_rows.get()); W1.O.ledits = reinterpret_cast<h2g_edit*>(s->d_warm_rows.get());      // (both areas with a capacity of zero)
 		W1.O.ovf_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_OVF_CURSOR); W1.O.ledits_cursor = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_LEDITS_CURSOR);
 		W1.defer_overflow = 0;
 		// The count is zero ON THIS STREAM before its kernels read it: the hipMemset above runs on the null stream, which the (non-blocking) machine streams do not wait
@@ -3569,23 +3512,8 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		return H2G_ERR_ARG;
 	}
 	// ---- phase C: the batch's arrays
-	if(B.names_cap < tot_n[0] || !B.d_name_offs) {      // (grows as h2g_set_read_names does)
-		(void)hipFree(B.d_names); (void)hipFree(B.d_name_offs);
-		B.d_names = nullptr; B.d_name_offs = nullptr; B.names_cap = 0;
-		HIPCHK(hipMalloc((void**)&B.d_names, tot_n[0] + 64));
-		HIPCHK(hipMalloc((void**)&B.d_name_offs, (s->max_reads + 1) * 4));
-		B.names_cap = tot_n[0];
-	}
-	if(M == 2) {                                        // (as h2g_set_mates does)
-		if(!B.d_codes2) {
-			HIPCHK(hipMalloc((void**)&B.d_codes2, s->max_bases + 64));
-			HIPCHK(hipMalloc((void**)&B.d_quals2, s->max_bases + 64));
-			HIPCHK(hipMalloc((void**)&B.d_offs2, (s->max_reads + 1) * 4));
-			HIPCHK(hipMalloc((void**)&B.d_name_offs2, (s->max_reads + 1) * 4));
-		}
-		(void)hipFree(B.d_names2); B.d_names2 = nullptr;
-		HIPCHK(hipMalloc((void**)&B.d_names2, tot_n[1] + 64));
-	}
+	HIPCHK(B.reserve_names(tot_n[0], s->max_reads));
+	if(M == 2) HIPCHK(B.ensure_mates(s->max_reads, s->max_bases, tot_n[1]));
 	HIPCHK(hipEventRecord(s->ev[12], s->st));
 	for(int m = 0; m < M; m++) {
 		const Lay& l = lay[m];
@@ -3593,8 +3521,8 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		const unsigned long long* nsz = (const unsigned long long*)(T + l.nsz);
 		const uint32_t* src = (const uint32_t*)(T + l.src);
 		uint8_t* codes = m ? B.d_codes2 : B.d_codes;
-		uint8_t* quals = (uint8_t*)(m ? B.d_quals2 : B.d_quals);
-		uint8_t* names = (uint8_t*)(m ? B.d_names2 : B.d_names);
+		uint8_t* quals = (uint8_t*)(m ? B.d_quals2 : B.d_quals).get();
+		uint8_t* names = (uint8_t*)(m ? B.d_names2 : B.d_names).get();
 		hipLaunchKernelGGL(k_fq_offs, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, lsz, nsz, (uint32_t)n, m ? B.d_offs2 : B.d_offs, m ? B.d_name_offs2 : B.d_name_offs);
 		if(tot_l[m]) hipLaunchKernelGGL(k_fq_write<true>, dim3(grid_for((tot_l[m] + 15) / 16, 256)), dim3(256), 0, s->st, (const uint8_t*)d_text[m], lsz, src + n, src + 2 * n, (uint32_t)n, (uint64_t)tot_l[m],
 		                                fo.phred64, codes, quals);
@@ -3764,7 +3692,7 @@ static h2g_status sam_text_begin(h2g_stream* s, const h2g_sam* S, bool paired) {
 	const BatchCtx& B = s->cur();
 	if(!B.has_names || (paired && !B.has_mates) || cf.first + cf.n > B.n_reads) { snprintf(g_err, sizeof g_err, "h2g_sam_text: the selected batch has no names / mates"); return H2G_ERR_ARG; }
 	HIPCHK(hipSetDevice(s->ix->device));
-	for(int k = 0; k < 4; k++) if(!s->ev_sam[k]) HIPCHK(hipEventCreate(&s->ev_sam[k]));
+	for(int k = 0; k < 4; k++) if(!s->ev_sam[k]) HIPCHK(s->ev_sam[k].create());
 	{	// the handle's tables: uploaded once, again when the handle's options changed
 		uint64_t uid, gen;
 		h2g_line::sam_tables_key(S, &uid, &gen);
@@ -3772,12 +3700,11 @@ static h2g_status sam_text_begin(h2g_stream* s, const h2g_sam* S, bool paired) {
 			h2g_line::Tables t;
 			h2g_line::sam_tables(S, t);
 			const size_t nr = t.refname_offs.size() - 1, ob = (nr + 1) * 4;
-			int rc;
-			if((rc = grow(&s->d_sam[4], &s->sam_sz[4], ob + t.refnames.size() + t.rg.size() + 64))) return (h2g_status)rc;
+			HIPCHK(s->d_sam[4].reserve(ob + t.refnames.size() + t.rg.size() + 64));
 			HIPCHK(hipStreamSynchronize(s->st));                      // (a text kernel still reading the former tables)
 			HIPCHK(hipMemcpy(s->d_sam[4], t.refname_offs.data(), ob, hipMemcpyHostToDevice));
-			if(!t.refnames.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4] + ob, t.refnames.data(), t.refnames.size(), hipMemcpyHostToDevice));
-			if(!t.rg.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4] + ob + t.refnames.size(), t.rg.data(), t.rg.size(), hipMemcpyHostToDevice));
+			if(!t.refnames.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4].get() + ob, t.refnames.data(), t.refnames.size(), hipMemcpyHostToDevice));
+			if(!t.rg.empty()) HIPCHK(hipMemcpy((char*)s->d_sam[4].get() + ob + t.refnames.size(), t.rg.data(), t.rg.size(), hipMemcpyHostToDevice));
 			s->samtab_uid = uid; s->samtab_gen = gen; s->samtab_nrefs = (uint32_t)nr; s->samtab_names = (uint32_t)t.refnames.size(); s->samtab_rg = (uint32_t)t.rg.size();
 			s->samtab_nalts = t.nalts; s->samtab_strand = t.rna_strandness;
 		}
@@ -3787,9 +3714,9 @@ static h2g_status sam_text_begin(h2g_stream* s, const h2g_sam* S, bool paired) {
 // the line offsets (+ scan tile sums + the check's flag) of n_lines lines: d_sam[2]
 static int sam_text_sizes_buf(h2g_stream* s, size_t n_lines, unsigned long long** v, unsigned long long** ts, unsigned int** d_bad) {
 	const size_t n1 = n_lines + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
-	const int rc = grow(&s->d_sam[2], &s->sam_sz[2], (n1 + ntiles + 2) * 8);
-	*v = (unsigned long long*)s->d_sam[2]; *ts = *v + n1; *d_bad = (unsigned int*)(*ts + ntiles + 1);
-	return rc;
+	HIPCHK(s->d_sam[2].reserve((n1 + ntiles + 2) * 8));
+	*v = (unsigned long long*)s->d_sam[2].get(); *ts = *v + n1; *d_bad = (unsigned int*)(*ts + ntiles + 1);
+	return H2G_OK;
 }
 // What every text call ends with: the descriptors lie in d_sam[0] and the pool in d_sam[1] -> sizes, scan, the capacity check, write, copy-back.  flag_is_set: the
 // check's flag was cleared (and maybe raised) by the caller's own kernels
@@ -3806,11 +3733,11 @@ static h2g_status sam_text_tail(h2g_stream* s, bool paired, size_t n_lines, size
 	c.names[1] = paired ? B.d_names2 : nullptr; c.noffs[1] = paired ? B.d_name_offs2 : nullptr; c.codes[1] = paired ? B.d_codes2 : nullptr; c.offs[1] = paired ? B.d_offs2 : nullptr;
 	c.quals[1] = paired && B.has_quals2 ? B.d_quals2 : nullptr;
 	c.rec[0] = cf.d_rec[0]; c.rec[1] = cf.d_rec[1]; c.nrec[0] = cf.bytes[0]; c.nrec[1] = cf.bytes[1];
-	c.aux = (const char*)s->d_sam[1]; c.n_aux = n_aux;
-	c.refname_offs = (const uint32_t*)s->d_sam[4]; c.refnames = (const char*)s->d_sam[4] + ((size_t)s->samtab_nrefs + 1) * 4; c.nrefs = s->samtab_nrefs;
+	c.aux = (const char*)s->d_sam[1].get(); c.n_aux = n_aux;
+	c.refname_offs = (const uint32_t*)s->d_sam[4].get(); c.refnames = (const char*)s->d_sam[4].get() + ((size_t)s->samtab_nrefs + 1) * 4; c.nrefs = s->samtab_nrefs;
 	c.rg = c.refnames + s->samtab_names; c.rg_len = s->samtab_rg; c.rna_strandness = s->samtab_strand; c.nalts = s->samtab_nalts;
 	c.first = (uint32_t)cf.first; c.paired = paired ? 1u : 0u; c.long_edits = nullptr;
-	const h2g_sam_line* d_lines = (const h2g_sam_line*)s->d_sam[0];
+	const h2g_sam_line* d_lines = (const h2g_sam_line*)s->d_sam[0].get();
 	HIPCHK(hipEventRecord(s->ev_sam[0], s->st));
 	hipLaunchKernelGGL(k_sam_line_sizes, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s->st, c, d_lines, n_lines, v, d_bad);
 	hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, s->st, v, n1, ts);
@@ -3825,9 +3752,9 @@ static h2g_status sam_text_tail(h2g_stream* s, bool paired, size_t n_lines, size
 	if(bad) { snprintf(g_err, sizeof g_err, "h2g_sam_text: a line names a record that does not end inside its mate's bytes, keeps its edits outside itself, or lies on a reference the index does not have"); return H2G_ERR_ARG; }
 	*used = (size_t)total;
 	if(total > cap || !out) return total == 0 ? H2G_OK : H2G_ERR_ARG;     // (nothing is written: the write kernel is not launched)
-	if((rc = grow(&s->d_sam[3], &s->sam_sz[3], (size_t)total + 64))) return (h2g_status)rc;
+	HIPCHK(s->d_sam[3].reserve((size_t)total + 64));
 	HIPCHK(hipEventRecord(s->ev_sam[2], s->st));
-	hipLaunchKernelGGL(k_sam_line_write, dim3((unsigned)((n_lines + 256 / H2G_SAM_LANES - 1) / (256 / H2G_SAM_LANES))), dim3(256), 0, s->st, c, d_lines, n_lines, (const unsigned long long*)v, (char*)s->d_sam[3]);
+	hipLaunchKernelGGL(k_sam_line_write, dim3((unsigned)((n_lines + 256 / H2G_SAM_LANES - 1) / (256 / H2G_SAM_LANES))), dim3(256), 0, s->st, c, d_lines, n_lines, (const unsigned long long*)v, (char*)s->d_sam[3].get());
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(s->ev_sam[3], s->st));
 	HIPCHK(hipMemcpyAsync(out, s->d_sam[3], (size_t)total, hipMemcpyDeviceToHost, s->st));
@@ -3848,8 +3775,8 @@ static h2g_status sam_text(h2g_stream* s, const h2g_sam* S, bool paired, const h
 	if(n_lines == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
 	const h2g_stream::CompactFetch& cf = s->cfetch;
 	if(const char* why = h2g_line::plan_check(lines, n_lines, cf.n, paired, cf.bytes[0], cf.bytes[1], n_aux, s->samtab_nrefs)) { snprintf(g_err, sizeof g_err, "h2g_sam_text: %s", why); return H2G_ERR_ARG; }
-	int rc;
-	if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64))) return (h2g_status)rc;
+	HIPCHK(s->d_sam[0].reserve(n_lines * sizeof(h2g_sam_line) + 64));
+	HIPCHK(s->d_sam[1].reserve(n_aux + 64));
 	HIPCHK(hipMemcpyAsync(s->d_sam[0], lines, n_lines * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
 	if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], aux, n_aux, hipMemcpyHostToDevice, s->st));
 	return sam_text_tail(s, paired, n_lines, n_aux, out, cap, used, line_offs, n_lines * sizeof(h2g_sam_line) + n_aux, false);
@@ -3937,7 +3864,7 @@ static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired,
 	if(n != cf.n || boffs1[n] != cf.bytes[0] || (paired && boffs2[n] != cf.bytes[1])) { snprintf(g_err, sizeof g_err, "h2g_sam_text_planned: the host arrays are not those of the stream's last compact fetch"); return H2G_ERR_ARG; }
 	s->plan_stats = h2g_sam_plan_stats(); s->plan_classes.clear();
 	if(n == 0) { if(line_offs) line_offs[0] = 0; return H2G_OK; }
-	for(int k = 0; k < 4; k++) if(!s->ev_plan[k]) HIPCHK(hipEventCreate(&s->ev_plan[k]));
+	for(int k = 0; k < 4; k++) if(!s->ev_plan[k]) HIPCHK(s->ev_plan[k].create());
 	const BatchCtx& B = s->cur();
 	SamPlanArgs a;
 	const uint8_t* qc[2] = {nullptr, nullptr};
@@ -3946,10 +3873,11 @@ static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired,
 	const size_t ntiles_r = (n + 1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
 	int rc;
 	// d_plan[2]: counts [n + 1], tile sums [ntiles + 1], line ends [n], sources [n]
-	if((rc = grow(&s->d_plan[0], &s->plan_sz[0], 2 * n * sizeof(h2g_sam_line))) || (rc = grow(&s->d_plan[1], &s->plan_sz[1], 3 * n + 64)) ||
-	   (rc = grow(&s->d_plan[2], &s->plan_sz[2], (n + 1 + ntiles_r + 1 + n) * 8 + n * 4 + 64))) return (h2g_status)rc;
-	uint8_t* d_cls = (uint8_t*)s->d_plan[1];
-	unsigned long long* v = (unsigned long long*)s->d_plan[2];
+	HIPCHK(s->d_plan[0].reserve(2 * n * sizeof(h2g_sam_line)));
+	HIPCHK(s->d_plan[1].reserve(3 * n + 64));
+	HIPCHK(s->d_plan[2].reserve((n + 1 + ntiles_r + 1 + n) * 8 + n * 4 + 64));
+	uint8_t* d_cls = s->d_plan[1];
+	unsigned long long* v = (unsigned long long*)s->d_plan[2].get();
 	unsigned long long* ts = v + n + 1;
 	unsigned long long* d_ends = ts + ntiles_r + 1;
 	uint32_t* d_hsrc = (uint32_t*)(d_ends + n);
@@ -3959,7 +3887,7 @@ static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired,
 	a.in.qc[0] = qc[0] ? d_cls + n : nullptr; a.in.qc[1] = paired && qc[1] ? d_cls + 2 * n : nullptr;
 	a.in.rec[0] = cf.d_rec[0]; a.in.rec[1] = cf.d_rec[1]; a.in.boffs[0] = cf.d_boffs[0]; a.in.boffs[1] = cf.d_boffs[1]; a.in.nrec[0] = cf.bytes[0]; a.in.nrec[1] = cf.bytes[1];
 	a.in.first = (uint32_t)cf.first;
-	a.n = n; a.cls = d_cls; a.v = v; a.slots = (h2g_sam_line*)s->d_plan[0];
+	a.n = n; a.cls = d_cls; a.v = v; a.slots = (h2g_sam_line*)s->d_plan[0].get();
 	const unsigned g1 = (unsigned)((n + 1 + 255) / 256);
 	HIPCHK(hipEventRecord(s->ev_plan[0], s->st));
 	if(paired) hipLaunchKernelGGL(k_sam_plan_paired, dim3(g1), dim3(256), 0, s->st, a, reinterpret_cast<const h2g_pair_result*>(B.d_pout + cf.first));
@@ -3995,9 +3923,11 @@ static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired,
 			b = hends[j];
 		}
 		unsigned long long *lv, *lts; unsigned int* d_bad;
-		if((rc = grow(&s->d_sam[0], &s->sam_sz[0], n_lines * sizeof(h2g_sam_line) + 64)) || (rc = grow(&s->d_sam[1], &s->sam_sz[1], n_aux + 64)) ||
-		   (rc = grow(&s->d_plan[3], &s->plan_sz[3], he.size() * sizeof(SamHardEntry) + 64)) || (rc = grow(&s->d_plan[4], &s->plan_sz[4], hl.size() * sizeof(h2g_sam_line) + 64)) ||
-		   (rc = sam_text_sizes_buf(s, n_lines, &lv, &lts, &d_bad))) return (h2g_status)rc;
+		HIPCHK(s->d_sam[0].reserve(n_lines * sizeof(h2g_sam_line) + 64));
+		HIPCHK(s->d_sam[1].reserve(n_aux + 64));
+		HIPCHK(s->d_plan[3].reserve(he.size() * sizeof(SamHardEntry) + 64));
+		HIPCHK(s->d_plan[4].reserve(hl.size() * sizeof(h2g_sam_line) + 64));
+		if((rc = sam_text_sizes_buf(s, n_lines, &lv, &lts, &d_bad))) return (h2g_status)rc;
 		if(!he.empty()) HIPCHK(hipMemcpyAsync(s->d_plan[3], he.data(), he.size() * sizeof(SamHardEntry), hipMemcpyHostToDevice, s->st));
 		if(!hl.empty()) HIPCHK(hipMemcpyAsync(s->d_plan[4], hl.data(), hl.size() * sizeof(h2g_sam_line), hipMemcpyHostToDevice, s->st));
 		if(n_aux) HIPCHK(hipMemcpyAsync(s->d_sam[1], ha.data(), n_aux, hipMemcpyHostToDevice, s->st));
@@ -4005,12 +3935,12 @@ static h2g_status sam_text_planned(h2g_stream* s, const h2g_sam* S, bool paired,
 		HIPCHK(hipMemsetAsync(d_bad, 0, 8, s->st));
 		HIPCHK(hipMemsetAsync(s->d_sam[0], 0, n_lines * sizeof(h2g_sam_line), s->st));
 		HIPCHK(hipEventRecord(s->ev_plan[2], s->st));
-		if(!he.empty()) hipLaunchKernelGGL(k_sam_plan_scatter, dim3((unsigned)((he.size() + 255) / 256)), dim3(256), 0, s->st, (const SamHardEntry*)s->d_plan[3], he.size(), n, (const uint8_t*)d_cls, v, d_hsrc);
+		if(!he.empty()) hipLaunchKernelGGL(k_sam_plan_scatter, dim3((unsigned)((he.size() + 255) / 256)), dim3(256), 0, s->st, (const SamHardEntry*)s->d_plan[3].get(), he.size(), n, (const uint8_t*)d_cls, v, d_hsrc);
 		hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles_r), dim3(256), 0, s->st, v, n + 1, ts);
 		hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, s->st, ts, ntiles_r);
 		hipLaunchKernelGGL(k_scan_add, dim3(g1), dim3(256), 0, s->st, v, n + 1, (const unsigned long long*)ts);
 		hipLaunchKernelGGL(k_sam_plan_place, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, (const uint8_t*)d_cls, (const unsigned long long*)v, (const uint32_t*)d_hsrc,
-		                   (const h2g_sam_line*)s->d_plan[0], (const h2g_sam_line*)s->d_plan[4], hl.size(), n, n_lines, (h2g_sam_line*)s->d_sam[0], d_ends, d_bad);
+		                   (const h2g_sam_line*)s->d_plan[0].get(), (const h2g_sam_line*)s->d_plan[4].get(), hl.size(), n, n_lines, (h2g_sam_line*)s->d_sam[0].get(), d_ends, d_bad);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(s->ev_plan[3], s->st));
 		// the shared tail; a line array that is too short: the sizes only (a capacity of 0 writes nothing)
@@ -4127,7 +4057,7 @@ extern "C" __attribute__((visibility("default"))) long h2g_stream_probe(const h2
 	if(k == "mstreams_used") return (long)s->n_mst;
 	if(k == "mstreams_created") { long n = 0; for(hipStream_t m : s->mst) n += m != nullptr; return n; }
 	if(k == "lanes") return (long)(s->mstreams ? s->mstreams : H2G_MSTREAMS_MAX);
-	if(k == "pools") { long n = 0; for(const h2g_stream::GoPool& pl : s->pool) n += pl.ws != nullptr; return n; }
+	if(k == "pools") { long n = 0; for(const h2g_stream::GoPool& pl : s->pool) n += bool(pl.ws); return n; }
 	return -1;
 }
 
