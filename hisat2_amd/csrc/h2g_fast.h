@@ -221,6 +221,7 @@ struct FCtx {
 	// a wave waits for its slowest lane, and with a third of the reads near a variant every trip had one (lease P: E:HS 308 us per trip against 29 on a linear index)
 	uint32_t defer_slow = 0;
 	uint32_t mate_handover = 0;                    // 1 (a build without alignMate): a pair that needs alignMate stops at FPC_AFTER_LOOP with FOP_HANDOVER instead of leaving the fast path
+	const uint32_t* ps0 = nullptr;                 // the pre-pass's records (fg_ps0_*, below): the first partial search of every (read, mate, strand) of the batch; nullptr: every search is a trip
 #if FG_GRAPH
 	const DAlts* alts;                             // the ALT database
 	GraphWS* gws;                                  // this LANE's scratch of one primitive (group walk, ALT-aware extension): nothing in it outlives a trip
@@ -814,6 +815,31 @@ H2G_HD bool fg_pack_read(const DReads& rd, uint32_t i, uint32_t* pk, uint32_t st
 	}
 	return anyn == 0;
 }
+// ---- the first partial searches.  A strand at cur == 0 is always picked first (FPC_NB_PICK), and what its search gives is a function of the read, the index
+// and pseudogeneStop / anchorStop / khits alone: k_ps0 (h2g_k_ps0.hip) runs these searches in front of the loop, one lane per (read, mate, strand), and leaves one 16-byte
+// record each — record (read * 4 + mate * 2 + strand), a pair's four one 64 B line: top, bot, fast_op_psearch's a2 word, cur | nrank << 8 | nside << 20.  A read the pass
+// refuses at fast_begin (too long, an N, --qc-filter) has FG_PS0_ABSENT there and costs no search.
+#define FG_PS0_WORDS 4
+#define FG_PS0_ABSENT 0xffffffffu
+H2G_HD uint32_t fg_ps_a2(const h2g_fm_hit& fh) {
+	return (fh.len & 0xffu) | (fh.hit_type << 8) | ((fh.done ? 1u : 0u) << 16) | ((fh.anchorStop ? 1u : 0u) << 17) | (fh.numUniqueSearch << 18);
+}
+H2G_HD void fg_ps0_pack(const h2g_fm_hit& fh, uint32_t rec[FG_PS0_WORDS]) {   // (a read of at most H2G_PK_MAXLEN bases: cur <= 128, nrank and nside <= 256)
+	rec[0] = fh.top; rec[1] = fh.bot; rec[2] = fg_ps_a2(fh); rec[3] = (fh.cur & 0xffu) | ((fh.nrank & 0xfffu) << 8) | ((fh.nside & 0xfffu) << 20);
+}
+// a0 - a5 as fast_op_psearch leaves them for a search at offset 0; false: no record
+H2G_HD bool fg_ps0_load(const uint32_t* tbl, uint32_t read, uint32_t x, FState& S) {
+	const uint32_t* p = tbl + ((size_t)read * 4 + x) * FG_PS0_WORDS;
+	uint32_t r0, r1, r2, r3;
+#if defined(__HIP_DEVICE_COMPILE__)
+	{ const uint4 v = *reinterpret_cast<const uint4*>(p); r0 = v.x; r1 = v.y; r2 = v.z; r3 = v.w; }
+#else
+	r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3];
+#endif
+	if(r3 == FG_PS0_ABSENT) return false;
+	S.a0 = r0; S.a1 = r1; S.a2 = r2; S.a3 = r3 & 0xffu; S.a4 = ((r3 >> 8) & 0xfffu) | ((r3 >> 20) << 16); S.a5 = 0;
+	return true;
+}
 // result summaries: tidx, toff, fw | nedits << 1 | extent << 4 | (score + 32768) << 16
 H2G_HD uint32_t fg_res_base(uint32_t m, uint32_t k) { return FW_RES + (m * FG_NRES + k) * 3; }
 // ... and the hit behind each summary.  A completed read's output (records + ReadOut / PairOut) is written in ONE place, FPC_FINISH, as a pure
@@ -1033,6 +1059,9 @@ again:
 		S.nb_rdi = rdi; S.nb_fwi = fwi;
 		S.sv_rdi = (uint32_t)rdi; S.sv_fw = fwi == 0;
 		S.a0 = fs_b4(S.rb_cur, x);
+#if !FG_GRAPH && !FG_SPLICED
+		if(C.ps0 && S.a0 == 0 && fg_ps0_load(C.ps0, S.read, x, S)) F_GOTO(FPC_NB_AFTER_PS);   // a fresh strand: its search ran in front of the loop — no request, no trip
+#endif
 		F_OP(FOP_PSEARCH, FPC_NB_AFTER_PS);
 	}
 	case FPC_NB_AFTER_PS: {
@@ -2144,7 +2173,7 @@ H2G_HD void fast_op_psearch(const FCtx& C, FState& S) {
 #endif
 	S.a5 = S.a0;
 	S.a0 = fh.top; S.a1 = fh.bot;
-	S.a2 = (fh.len & 0xffu) | (fh.hit_type << 8) | ((fh.done ? 1u : 0u) << 16) | ((fh.anchorStop ? 1u : 0u) << 17) | (fh.numUniqueSearch << 18);
+	S.a2 = fg_ps_a2(fh);
 	S.a3 = fh.cur; S.a4 = (fh.nrank & 0xffffu) | (fh.nside << 16);
 }
 // SA walks are chunked: in lock-step a wave waits for its longest walk (the walk length is geometric: mean 15, the longest of 60 about 65),

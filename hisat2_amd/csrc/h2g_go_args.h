@@ -198,7 +198,12 @@ struct FastArgs {
 	// spliced runs only (h2g_k_go_fast_spl.hip; at the end: the other builds' fields keep their offsets): the splice-site database and Read::rdid of read 0 of the batch (rd1.ids: per-read ids)
 	h2g::DSpliceDB ssdb;
 	uint32_t rdid_base;
+	// the linear non-spliced builds only: the first partial searches of the batch (h2g_k_ps0.hip writes them in front of the fast launch; FCtx::ps0), FG_PS0_WORDS words per
+	// (read, mate, strand); nullptr: no pre-pass ran
+	uint32_t* ps0;
 };
+// the pre-pass: `a` is the fast launch's argument block in device memory, `units` its reads / pairs
+extern "C" int h2g_ps0_launch(const FastArgs* a, uint32_t units, bool paired, hipStream_t st);
 // What h2g_kernels.hip knows of one build of the pass (h2g_k_go_fast.hip and the units that compile it again); `a` of both launchers is the argument block in DEVICE memory
 struct FastUnitDesc {
 	int (*launch)(const FastArgs* a, unsigned grid, hipStream_t);

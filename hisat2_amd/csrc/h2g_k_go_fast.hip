@@ -68,6 +68,7 @@ __device__ __forceinline__ void fk_ctx(const FastArgs* A, uint32_t* stage, uint3
 #endif
 	C.O = A->O;
 	C.mate_handover = FG_ALIGN_MATE ? 0u : A->mate_handover;
+	C.ps0 = A->ps0;
 	C.defer_slow = FG_GRAPH ? 1u : 0u;
 	C.name[0] = C.name[1] = nullptr; C.namelen[0] = C.namelen[1] = 0;
 }

@@ -139,6 +139,11 @@ static DLocalSet dls_now(h2g_index* ix) {
 #define H2G_ORPHAN_MIN_UNITS 200000
 #define H2G_DRAIN_GRID 64
 #define H2G_FAST_POOLS 3
+// The first partial searches of the fast pass in a pre-pass kernel (h2g_k_ps0.hip): 1 = on for the linear non-spliced builds (9.40 -> 8.98 ms per step,
+// profiles/ps0_ab.md); H2G_FAST_PS0=0 / h2g_stream_tune "ps0" is the code path of before
+#ifndef H2G_DEFAULT_PS0
+#define H2G_DEFAULT_PS0 1
+#endif
 #define H2G_DEFAULT_ALIGN_MATE 0
 // the fast pass of SPLICED runs on a linear index (h2g_k_go_fast_spl.hip; env H2G_FAST_SPLICED, h2g_stream_tune "fast_spliced").  OFF by default: 1 M pairs drawn from a spliced transcript
 // model (36 % with a junction) take 225 ms per run with it and 70 ms with the machine alone — version 1 hands 44 % of the pairs on, and a machine pass behind a fast pass has at most
@@ -229,6 +234,7 @@ struct h2g_stream {
 	// the fast pass's reads in flight (h2g_k_go_fast.hip): pool gen % 3 — the drain launch of run k reads run k's pool while the fast passes of runs k + 1 and k + 2 run
 	DevBuf<uint8_t> d_fast_slots[H2G_FAST_POOLS];
 	DevEvent ev_pool[H2G_FAST_POOLS];                                // the drain launch that last read pool p is over
+	DevBuf<uint32_t> d_ps0[H2G_FAST_POOLS];                          // the pre-pass's records of the run on pool p (h2g_k_ps0.hip): read by its fast launch and its drain launch
 	DevBuf<uint32_t> d_orphans[H2G_NBUF];                            // slots a fast launch left in flight (+ their count behind the list)
 	size_t orphan_cap = 0;
 	DevBuf<uint8_t> d_drain_slots;                                   // the drain launch's own pool
@@ -245,6 +251,7 @@ struct h2g_stream {
 	// development / measurement knobs (h2g_stream_tune; their H2G_* environment names are read ONCE, when the stream is created)
 	struct Tune { int fast = 1, blocks_per_cu = 0, pair_slots = 0, no_second_pass = 0; unsigned mach_div = 0 /* auto */, mach_min = 4, mach_total = H2G_MACH_TOTAL; int mach_total_auto = 1; int fast_reserve = H2G_FAST_RESERVE_DEFAULT; long dbg_read = -1;
 	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */;
+	              int ps0 = -1; /* the first partial searches in a pre-pass (h2g_k_ps0.hip): -1 the policy (H2G_DEFAULT_PS0), 0 off, 1 on */
 	              int fast_spliced = H2G_DEFAULT_FAST_SPLICED; /* the fast pass of spliced runs on a linear index (h2g_k_go_fast_spl.hip) */ } tune;
 	h2g_align_params last_p; int last_paired = -1;   // the option set of the last go_run (a different one waits for the machine streams)
 	DevBuf<uint8_t> d_sw_ws;      // h2g_sw_align: H/E/F workspace of one batch of problems
@@ -921,7 +928,7 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		s->tune.no_second_pass = (int)env("H2G_GO_NO_SECOND_PASS", 0); s->tune.mach_div = (unsigned)env("H2G_MACH_DIV", 0); s->tune.mach_min = (unsigned)env("H2G_MACH_MIN", 4);
 		s->tune.dbg_read = env("H2G_GO_DBG_READ", -1);
 		s->tune.tail = (int)env("H2G_FAST_TAIL", H2G_DEFAULT_TAIL); s->tune.tail_auto = getenv("H2G_FAST_TAIL") ? 0 : 1; s->tune.align_mate = (int)env("H2G_FAST_AM", H2G_DEFAULT_ALIGN_MATE);
-		s->tune.orphan = (int)env("H2G_FAST_ORPHAN", -1); s->tune.drain_grid = (int)env("H2G_DRAIN_GRID", H2G_DRAIN_GRID); s->tune.mate_handover = (int)env("H2G_FAST_MATE_HANDOVER", -1);
+		s->tune.orphan = (int)env("H2G_FAST_ORPHAN", -1); s->tune.drain_grid = (int)env("H2G_DRAIN_GRID", H2G_DRAIN_GRID); s->tune.mate_handover = (int)env("H2G_FAST_MATE_HANDOVER", -1); s->tune.ps0 = (int)env("H2G_FAST_PS0", -1);
 		s->tune.fast_spliced = (int)env("H2G_FAST_SPLICED", H2G_DEFAULT_FAST_SPLICED);
 		s->tune.mach_total = (unsigned)env("H2G_MACH_TOTAL", H2G_MACH_TOTAL); s->tune.mach_total_auto = getenv("H2G_MACH_TOTAL") ? 0 : 1; s->tune.fast_reserve = (int)env("H2G_FAST_RESERVE", H2G_FAST_RESERVE_DEFAULT);
 		auto clampm = [](long m) { return (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); };
@@ -2575,6 +2582,7 @@ static GoPlan go_plan(const h2g_stream* s, const h2g_align_params* p, bool paire
 // the fast pass's share of a run (h2g_fast.h), decided by fast_policy
 struct FastPlan {
 	bool use_am, mate_ho;          // alignMate in the pass; pairs that need it parked for the drain launch (its alignMate build)
+	bool ps0;                      // the first partial searches run in a pre-pass in front of the fast launch (h2g_k_ps0.hip)
 	const FastUnitDesc *FU, *DU;   // the fast launch's build of the pass and the drain launch's
 	unsigned fgrid, mgrid, dgrid;  // workgroups of the fast launch, of the machine pass behind it, of the drain launch
 	uint32_t orphan_T, psel;       // > 0: the end of the batch goes to a drain launch; the slot pool of the fast launch ...
@@ -2786,6 +2794,8 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && !g.fast_spl && s->tune.mate_handover != 0;
 	f->DU = &fast_unit(linear, g.fast_spl, f->use_am || f->mate_ho);
 	f->psel = f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
+	// the first partial searches in front of the loop: the linear non-spliced builds (h2g_stream_tune "ps0": -1 this policy, 0 off, 1 on)
+	f->ps0 = linear && !g.fast_spl && (s->tune.ps0 < 0 ? H2G_DEFAULT_PS0 != 0 : s->tune.ps0 != 0);
 }
 
 // every buffer of the two launches exists (and has been written once: fresh device memory costs its first writer the mapping) before the first run that could need it
@@ -2799,6 +2809,8 @@ static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 		for(unsigned b = 0; b < g.M + 1; b++) need = need || !s->d_orphans[b] || !s->d_fast_args[H2G_NBUF + b];
 		need = need || s->orphan_cap < ocap;
 	}
+	const size_t pswords = (size_t)s->max_reads * 4 * FG_PS0_WORDS;     // one record per (unit, mate, strand)
+	if(f.ps0) for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) need = need || s->d_ps0[f.orphan_T ? q : f.psel].size() < pswords;
 	if(!need) return H2G_OK;
 	// (every stream, whatever st2_busy and dst_busy say: the pools about to be freed may be any launch's)
 	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
@@ -2806,6 +2818,8 @@ static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 	for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) {
 		DevBuf<uint8_t>& fs = s->d_fast_slots[f.orphan_T ? q : f.psel];
 		if(fs.size() < f.slot_bytes) { HIPCHK(fs.reserve(f.slot_bytes)); HIPCHK(hipMemsetAsync(fs, 0, f.slot_bytes, s->st)); }
+		DevBuf<uint32_t>& ps = s->d_ps0[f.orphan_T ? q : f.psel];
+		if(f.ps0 && ps.size() < pswords) { HIPCHK(ps.reserve(pswords)); HIPCHK(hipMemsetAsync(ps, 0xff, pswords * 4, s->st)); }
 	}
 	if(f.orphan_T) {
 		if(s->orphan_cap < ocap) { for(int b = 0; b < H2G_NBUF; b++) s->d_orphans[b] = DevBuf<uint32_t>(); s->orphan_cap = ocap; }
@@ -2842,6 +2856,7 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	F.total = (uint32_t)s->cur().n_reads; F.paired = paired ? 1u : 0u;
 	F.alts = A.alts; F.gws_base = nullptr; F.gws_stride = 0; F.sc_base = nullptr;
 	F.dbg_read = A.dbg_read; F.dbg_buf = A.dbg_buf;
+	F.ps0 = f.ps0 ? s->d_ps0[f.psel].get() : nullptr;                   // (the drain launch reads run k's table beside run k + 1: D = F below)
 	F.ssdb = A.ssdb; F.rdid_base = A.rdid_base;                          // (spliced runs: the database of this run — a wave of the temporary-splice-site mode brings its own)
 	// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
 	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
@@ -2883,6 +2898,8 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		*hD = D;
 		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
 	}
+	// the pre-pass: behind whatever produced the reads and behind the last reader of its table (stream order, ev_pool above), in front of the loop that reads it
+	if(f.ps0 && h2g_ps0_launch(s->d_fast_args[gsel], F.total, paired, s->st) != 0) return set_err("go() first-search pre-pass launch", hipGetLastError());
 	if(f.FU->launch(s->d_fast_args[gsel], f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
 	r->A.list = bl; r->A.nlist = bl + s->max_reads;
 	return H2G_OK;
@@ -4040,6 +4057,7 @@ extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream
 	else if(k == "mach_total") { s->tune.mach_total_auto = v <= 0; s->tune.mach_total = v <= 0 ? H2G_MACH_TOTAL : (unsigned)v; }      // (0 = the default policy)
 	else if(k == "fast_reserve") s->tune.fast_reserve = (int)v;
 	else if(k == "mate_handover") s->tune.mate_handover = (int)v;
+	else if(k == "ps0") s->tune.ps0 = (int)v;
 	else if(k == "fast_spliced") s->tune.fast_spliced = (int)v;
 	else if(k == "orphan") s->tune.orphan = (int)v; else if(k == "drain_grid") s->tune.drain_grid = (int)(v < 1 ? 1 : v > 128 ? 128 : v);
 	else if(k == "mstreams") { s->mstreams = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v); s->gen = 0; }   // pins lanes = machine streams (nothing is in flight: every buffer set is free)
