@@ -17,6 +17,7 @@
 #define H2G_HAPLOTYPE 0     // the primitive kernels of this unit (k_extend_alts, k_adjust_alt) run without haplotype lists; go() units: h2g_graph.h
 #include "h2g_core.h"
 #include "h2g_dev.h"     // DevBuf / PinnedBuf / DevEvent / DevStream: who holds one owns it
+#include "h2g_parts.h"   // PartArea: a device area in equal parts, one per lane
 #include "h2g_host_index.h"
 #include "h2g_align.h"
 #include "h2g_graph.h"
@@ -114,9 +115,9 @@ static DLocalSet dls_now(h2g_index* ix) {
 // fast pass on repeat-structured sequence (profiles/r04_NOTES.md §4-§6).  The stream therefore keeps such passes in flight next to the fast passes of
 // the following runs.  Two numbers describe that, and they are not the same thing (profiles/r08_mstreams.md):
 //   LANES (M, H2G_MSTREAMS_MAX unless pinned): run k is lane k % M.  Everything that OUTLIVES a pass rotates by lane — the parts of the pair-overflow,
-//     long-edit and XL areas and their cursors, ledits_touched, ev_mach, and the hand-on list, counters and argument block, buffered M + 1 deep.  This is
+//     long-edit and XL areas (PartArea) and their cursors, ledits_touched, and the per-run buffer sets (h2g_stream::RunSet: events, hand-on list, counters, argument blocks), M + 1 deep.  This is
 //     the caller's contract (fetch a batch before M further runs are queued) and does not follow the load.
-//   MACHINE STREAMS IN ROTATION (S <= M): lane m's pass runs on HIP stream mst[m % S] with that stream's workspace pools and overflow list, which a pass
+//   MACHINE STREAMS IN ROTATION (S <= M): lane m's pass runs on HIP stream mst[m % S] with that stream's workspace pools and overflow list (h2g_stream::MachStream), which a pass
 //     only needs while it runs (passes on one HIP stream are in order).  HIP streams share the few hardware queues of a process and serialise there, so S
 //     follows the load (mstreams_policy): H2G_MSTREAMS_LIGHT_DEFAULT while a linear index's fast pass hands on little — the passes are short and two in
 //     flight cover them — and H2G_MSTREAMS_MAX once it hands on more than 1.5 % of the batch, or on a graph index.
@@ -191,6 +192,16 @@ struct BatchCtx {
 		return e != hipSuccess ? e : d_names2.reset(nb2 + 64);
 	}
 };
+// a stream's timing events (h2g_stream::tm; the pairs h2g_get_counters and the bench entry points read)
+enum Tm {
+	TM_PRIM0, TM_PRIM1,                     // around the kernels of one primitive call
+	TM_SEED0, TM_SEED_MID, TM_SEED1,        // the seed stage: search | resolve + extend
+	TM_RUN0, TM_MAIN1, TM_MAIN0, TM_RUN1,   // a go_run: its start, the main pass (TM_MAIN0 .. TM_MAIN1), the end of its last pass
+	TM_EXT1,                                // the extended search's HBM stage ends (it starts at TM_PRIM1)
+	TM_FAST1,                               // the fast launch has been queued (TM_RUN0 .. TM_FAST1: pre-pass + fast pass)
+	TM_SET0, TM_SET1,                       // around the kernels of h2g_set_reads_windows / h2g_set_reads_fastq
+	TM_N
+};
 // Ownership (h2g_dev.h): every device buffer, event and HIP stream below is a handle, and deleting the context gives them all back.  THE STREAMS ARE DECLARED FIRST, so they
 // are destroyed last, after every buffer and event; the destructor waits for them before anything goes.  A member that is a raw pointer owns nothing and says whose memory it views.
 struct h2g_stream {
@@ -200,71 +211,89 @@ struct h2g_stream {
 	// its few reads are long latency chains (about a fast pass's duration whatever their number), so two such passes are kept in flight
 	DevStream mst[H2G_MSTREAMS_MAX];            // all created with the context (h2g_stream_create: their order matters); mst[0 .. n_mst) have entered the rotation, only those ever held work
 	DevStream dst;                              // the drain launches' stream: one after the other, each next to the following run's fast launch
-	DevEvent ev_rot[H2G_MSTREAMS_MAX];          // what a machine stream holds when the rotation changes
 	unsigned n_mst = 0;
 	unsigned mstreams = 0;                      // pinned (1 .. H2G_MSTREAMS_MAX): lanes = machine streams in rotation = this; 0: S follows the load
 	unsigned mstreams_light = H2G_MSTREAMS_LIGHT_DEFAULT;   // S of the light regime
 	unsigned rot = 0;                           // machine streams in rotation for the last run behind a fast pass (0: there was none yet)
-	unsigned warm_mask = 0;                     // bit j: mst[j] has run both machine kernels once
 	bool st2_busy = false;            // a machine stream may hold work
-	DevEvent ev_fast[H2G_NBUF], ev_mach[H2G_NBUF];
-	unsigned gen = 0;                 // go_run generation: bail list, counters and argument block are buffered H2G_NBUF deep by gen % H2G_NBUF
+	unsigned gen = 0;                 // go_run generation: run k takes buffer set k % (M + 1), fast pool k % H2G_FAST_POOLS, lane k % M and machine stream lane % S
+	// What a run works on is one record per index space, and a run (GoRun) holds a reference to its record of each: an index of one space never subscripts another's.
+	// PER-RUN SET, run[gen % (M + 1)]: the fast pass's hand-on list, its counters and the two launches' argument blocks, M + 1 deep — the machine's pass over
+	// run k's hand-ons may still be under way while the fast passes of the following runs run
+	struct RunSet {
+		DevEvent ev_fast, ev_mach;              // the run's fast pass / machine pass is over
+		DevEvent ev_bails;                      // h_bail(set) has arrived
+		DevEvent ev_drain;                      // the run's drain launch is over (its machine pass waits for it)
+		DevBuf<uint32_t> bail_list;             // read ids the fast pass handed on to the general machine (+ their count behind the list)
+		DevBuf<uint32_t> orphans;               // slots a fast launch left in flight (+ their count behind the list)
+		DevBuf<FastArgs> fast_args, drain_args; // the argument block of the fast launch and of its drain launch (device copies)
+	} run[H2G_NBUF];
+	// ... and what belongs to a set but lives in one allocation for all of them: its counter block (h2g_go_args.h), the pinned hand-on count of its fast pass
+	// (sizes the machine's share of the CUs) and the pinned staging of its two argument blocks (the upload never makes the host wait for the stream)
+	DevBuf<unsigned long long> d_counters;      // H2G_NBUF counter blocks of H2G_CNT_BLOCK words
+	PinnedBuf<uint32_t> h_bails;
+	PinnedBuf<FastArgs> h_fast_args;            // 2 * H2G_NBUF blocks
+	unsigned long long* counters(const RunSet& b) const { return d_counters + (&b - run) * H2G_CNT_BLOCK; }
+	uint32_t& h_bail(const RunSet& b) const { return h_bails[&b - run]; }
+	FastArgs* h_fast(const RunSet& b) const { return h_fast_args + 2 * (&b - run); }
+	FastArgs* h_drain(const RunSet& b) const { return h_fast_args + 2 * (&b - run) + 1; }
 	unsigned long long* cnt_cur = nullptr;   // the counter block of the last go_run (a view into d_counters)
 	uint32_t last_bails = 0;
-	PinnedBuf<uint32_t> h_bails;      // pinned: the hand-on count of the last two fast passes (sizes the machine's share of the CUs)
 	size_t max_reads = 0, max_bases = 0;
 	BatchCtx batch[H2G_MAX_BATCHES];  // the resident batches: read sets and their result rows
 	unsigned cur_batch = 0;
 	BatchCtx& cur() { return batch[cur_batch]; }   // the selected one
 	const BatchCtx& cur() const { return batch[cur_batch]; }
 	DevBuf<h2g_seed_result> d_seed;
-	// per-lane scratch of the go() kernels: [0] the main pass, [1] the second pass over overflowed reads (large workspace)
+	// per-lane scratch of one pass of the go() kernels
 	struct GoPool {
 		DevBuf<uint8_t> ws;                               // AlignWS x lanes of the unit last run
 		DevBuf<uint8_t> gws;                              // GraphWS x lanes (graph indexes only)
 		DevBuf<uint8_t> sw; size_t sw_stride = 0, sw_lanes = 0;   // Smith-Waterman scratch (only with bowtie2_dp != 0): what it is laid out for
 		DevBuf<uint8_t> sc;                               // combineWith temp_scores per lane
-	} pool[2 * H2G_MSTREAMS_MAX];     // [2 * m + 0] main pass, [2 * m + 1] second pass of machine stream m (m = 0 also: passes on the first stream)
+	};
+	// MACHINE STREAM, mach[lane % S] (its HIP stream: mst[] above, stream_of): what a pass only needs while it runs.  mach[0] also serves the passes on the first stream
+	struct MachStream {
+		DevEvent ev_rot;                    // what the stream holds when the rotation changes
+		GoPool main, second;                // the main pass's scratch; the second pass's over overflowed reads (large workspace)
+		DevBuf<uint32_t> ovf_list;          // read ids whose workspace overflowed in the main pass (+ their count behind the list)
+		bool warmed = false;                // the stream has run both machine kernels once
+	} mach[H2G_MSTREAMS_MAX];
+	hipStream_t stream_of(const MachStream& m) const { return mst[&m - mach]; }
+	const MachStream* ovf_cur = mach;       // the one whose overflow list the last run used
 	DevBuf<uint32_t> dbg_buf;         // development hook (H2G_GO_DBG_READ)
-	DevBuf<uint32_t> d_ovf_list[H2G_MSTREAMS_MAX]; // per machine stream: read ids whose workspace overflowed in the main pass (+ their count behind the list)
-	unsigned ovf_cur = 0;             // the one the last run used
-	DevBuf<uint32_t> d_bail_list[H2G_NBUF]; // read ids the fast pass handed on to the general machine (+ their count behind the list)
-	DevBuf<FastArgs> d_fast_args[2 * H2G_NBUF]; // [gen % NBUF] the fast launch's, [NBUF + gen % NBUF] its drain launch's
-	PinnedBuf<FastArgs> h_fast_args;  // pinned staging of the argument blocks (H2G_NBUF of them): the upload never makes the host wait for the stream      // the fast pass's argument block (device copy)
-	// the fast pass's reads in flight (h2g_k_go_fast.hip): pool gen % 3 — the drain launch of run k reads run k's pool while the fast passes of runs k + 1 and k + 2 run
-	DevBuf<uint8_t> d_fast_slots[H2G_FAST_POOLS];
-	DevEvent ev_pool[H2G_FAST_POOLS];                                // the drain launch that last read pool p is over
-	DevBuf<uint32_t> d_ps0[H2G_FAST_POOLS];                          // the pre-pass's records of the run on pool p (h2g_k_ps0.hip): read by its fast launch and its drain launch
-	DevBuf<uint32_t> d_orphans[H2G_NBUF];                            // slots a fast launch left in flight (+ their count behind the list)
+	// FAST POOL, fpool[gen % H2G_FAST_POOLS]: the fast pass's reads in flight (h2g_k_go_fast.hip) — the drain launch of run k reads run k's pool while the fast passes of runs k + 1 and k + 2 run
+	struct FastPool {
+		DevBuf<uint8_t> slots;
+		DevBuf<uint32_t> ps0;               // the pre-pass's records of the run on this pool (h2g_k_ps0.hip): read by its fast launch and its drain launch
+		DevEvent ev_last;                   // the drain launch that last read the pool is over
+	} fpool[H2G_FAST_POOLS];
 	size_t orphan_cap = 0;
 	DevBuf<uint8_t> d_drain_slots;                                   // the drain launch's own pool
 	DevBuf<uint8_t> d_drain_sc;                                      // graph indexes: its combineWith scores per lane
-	DevEvent ev_drain[H2G_NBUF];                                     // run k's drain launch is over (its machine pass waits for it)
 	bool dst_busy = false;
-	DevEvent ev_bails[H2G_NBUF];                                     // h_bails[gen % NBUF] has arrived
 	DevEvent ev_dr[2];                                               // (timed) around the last drain launch
 	bool ran_drain = false;
-	const uint32_t* orph_cur = nullptr;                              // the orphan count of the last run (a view into d_orphans)
+	const uint32_t* orph_cur = nullptr;                              // the orphan count of the last run (a view into a buffer set's orphans)
 	DevBuf<uint8_t> d_fast_gws;                                     // graph indexes: GraphWS per lane of the fast kernel (scratch of one primitive)
 	DevBuf<uint8_t> d_fast_sc;                                      // ... and combineWith's temp_scores per lane
 	bool ran_fast = false;
-	// development / measurement knobs (h2g_stream_tune; their H2G_* environment names are read ONCE, when the stream is created)
-	struct Tune { int fast = 1, blocks_per_cu = 0, pair_slots = 0, no_second_pass = 0; unsigned mach_div = 0 /* auto */, mach_min = 4, mach_total = H2G_MACH_TOTAL; int mach_total_auto = 1; int fast_reserve = H2G_FAST_RESERVE_DEFAULT; long dbg_read = -1;
-	              int tail = H2G_DEFAULT_TAIL, tail_auto = 1, align_mate = H2G_DEFAULT_ALIGN_MATE; int orphan = -1 /* auto */, drain_grid = H2G_DRAIN_GRID, mate_handover = -1 /* auto */;
-	              int ps0 = -1; /* the first partial searches in a pre-pass (h2g_k_ps0.hip): -1 the policy (H2G_DEFAULT_PS0), 0 off, 1 on */
-	              int fast_spliced = H2G_DEFAULT_FAST_SPLICED; /* the fast pass of spliced runs on a linear index (h2g_k_go_fast_spl.hip) */ } tune;
+	// development / measurement knobs: the table g_knobs below names each one, with its default, its h2g_stream_tune key and its H2G_* environment name (read ONCE,
+	// when the stream is created, which also sets the defaults).  tail_auto / mach_total_auto: nobody has set the knob, its policy decides
+	struct Tune { int fast, blocks_per_cu, pair_slots, no_second_pass; unsigned mach_div, mach_min, mach_total; int mach_total_auto = 1; int fast_reserve; long dbg_read;
+	              int tail, tail_auto = 1, align_mate, orphan, drain_grid, mate_handover, ps0, fast_spliced; } tune = {};
 	h2g_align_params last_p; int last_paired = -1;   // the option set of the last go_run (a different one waits for the machine streams)
 	DevBuf<uint8_t> d_sw_ws;      // h2g_sw_align: H/E/F workspace of one batch of problems
 	DevBuf<SwLaneState> d_sw_states;
-	// records with more than H2G_MAX_EDITS edits keep their lists here (MachOut::ledits): one part of ledits_cap edits and one cursor per machine stream
-	DevBuf<h2g_edit> d_ledits; DevBuf<uint32_t> d_ledits_cur; size_t ledits_cap = 0; unsigned ledits_parts = 0;
-	unsigned ledits_touched = 0;   // parts a run has written to since the last h2g_set_reads (bit per machine stream): the span h2g_align_fetch_long_edits reports
-	DevBuf<h2g_alnres> d_paln_ovf; size_t paln_ovf_cap = 0; unsigned paln_ovf_parts = 0;   // pairs with more records than pair_slots per mate (MachOut::ovf): one part of paln_ovf_cap records per machine stream
-	// the XL units' concordant lists that PairOut cannot carry (XlPairs): per read of the batch where its list starts, the lists (one part of xlp_cap words per
-	// machine stream) and one cursor per part.  xlp_pout: the result rows of the batch the last XL paired run wrote (a view of that batch's d_pout; nullptr: no list is current)
-	DevBuf<uint32_t> d_xlp_at, d_xlp; size_t xlp_cap = 0; unsigned xlp_parts = 0; DevBuf<uint32_t> d_xlp_cur;
+	// LANE, gen % M: the three areas below are partitioned by lane (PartArea, h2g_parts.h: part m is the lane's, with a cursor of its own)
+	// records with more than H2G_MAX_EDITS edits keep their lists here (MachOut::ledits); the cursors: d_ledits_cur[lane]
+	PartArea<h2g_edit> ledits; DevBuf<uint32_t> d_ledits_cur;
+	unsigned ledits_touched = 0;   // parts a run has written to since the last h2g_set_reads (bit per lane): the span h2g_align_fetch_long_edits reports
+	PartArea<h2g_alnres> paln_ovf; // pairs with more records than pair_slots per mate (MachOut::ovf); the cursor is a word of the run's counter block
+	// the XL units' concordant lists that PairOut cannot carry (XlPairs): per read of the batch where its list starts, the lists and their cursors, d_xlp_cur[lane].
+	// xlp_pout: the result rows of the batch the last XL paired run wrote (a view of that batch's d_pout; nullptr: no list is current)
+	DevBuf<uint32_t> d_xlp_at; PartArea<uint32_t> xlp; DevBuf<uint32_t> d_xlp_cur;
 	const PairOut* xlp_pout = nullptr;
-	DevBuf<unsigned long long> d_counters;      // H2G_NBUF counter blocks of H2G_CNT_BLOCK words (h2g_go_args.h)
 	DevBuf<uint8_t> d_tmp[4];                   // scratch of one call (tmp_buf): each 256 bytes beyond its largest request
 	// SAM text on the device (h2g_sam_text_*): what d_tmp holds is nobody's once another call takes a slot, so every such call (tmp_buf), every batch selection and every call
 	// that sets reads, mates or names counts tmp_gen up; a compact fetch notes the count it ended with, and the text call runs only while the two are equal
@@ -281,7 +310,7 @@ struct h2g_stream {
 	DevEvent ev_plan[4];                        // (created by the first planned call)
 	h2g_sam_plan_stats plan_stats = {};
 	std::vector<uint8_t> plan_classes;
-	DevEvent ev[14];                            // ([12], [13]: around the kernels of h2g_set_reads_windows / h2g_set_reads_fastq)
+	DevEvent tm[TM_N];
 	bool ran_seed = false, ran_align = false;
 	h2g_counters last;
 	h2g_windows_stats win_stats = {};           // of the last h2g_set_reads_windows
@@ -887,6 +916,36 @@ extern "C" h2g_status h2g_index_synth_graph_sides(uint64_t num_sides, uint64_t s
 }
 
 // ------------------------------------------------------------------------------------------ stream
+// The knobs of go_run, for development and measurement: a row is a knob's h2g_stream_tune key, its environment name (read once, by h2g_stream_create), its default
+// and how a value is stored in h2g_stream::Tune; is_auto: the flag that says "nobody has set this knob, its policy decides", cleared by whoever sets it.
+//   fast 0: every run goes to the machine whole.  blocks_per_cu / pair_slots > 0: override the geometry / the pair rows (tests).  mach_div 0: the policy of fast_policy.
+//   dbg_read: a read id whose primitive requests are traced, -1 none.  tail: reads a workgroup hands on at the end of an exhausted batch.  align_mate: alignMate inside
+//   the pass.  orphan: -1 the policy, 0 no drain launch, n its threshold.  mate_handover, ps0: -1 the policy, 0 off, 1 on.  fast_spliced 0: spliced runs go to the machine
+//   whole.  mach_total: workgroups of all machine passes in flight together.  fast_reserve: CUs the fast pass leaves free, -1 = as many as the machine passes may hold.
+struct Knob { const char *key, *env; long def; void (*set)(h2g_stream::Tune&, long); int h2g_stream::Tune::* is_auto; };
+#define H2G_KNOB(key, env, def, member, is_auto) {key, env, def, [](h2g_stream::Tune& t, long v) { t.member = (decltype(t.member))v; }, is_auto}
+static const Knob g_knobs[] = {
+	H2G_KNOB("fast",           "H2G_GO_FAST",            1,                        fast,           nullptr),
+	H2G_KNOB("blocks_per_cu",  "H2G_GO_BLOCKS_PER_CU",   0,                        blocks_per_cu,  nullptr),
+	H2G_KNOB("pair_slots",     "H2G_PAIR_SLOTS",         0,                        pair_slots,     nullptr),
+	H2G_KNOB("no_second_pass", "H2G_GO_NO_SECOND_PASS",  0,                        no_second_pass, nullptr),
+	H2G_KNOB("mach_div",       "H2G_MACH_DIV",           0,                        mach_div,       nullptr),
+	H2G_KNOB("mach_min",       "H2G_MACH_MIN",           4,                        mach_min,       nullptr),
+	H2G_KNOB("dbg_read",       "H2G_GO_DBG_READ",        -1,                       dbg_read,       nullptr),
+	H2G_KNOB("tail",           "H2G_FAST_TAIL",          H2G_DEFAULT_TAIL,         tail,           &h2g_stream::Tune::tail_auto),
+	H2G_KNOB("align_mate",     "H2G_FAST_AM",            H2G_DEFAULT_ALIGN_MATE,   align_mate,     nullptr),
+	H2G_KNOB("orphan",         "H2G_FAST_ORPHAN",        -1,                       orphan,         nullptr),
+	H2G_KNOB("drain_grid",     "H2G_DRAIN_GRID",         H2G_DRAIN_GRID,           drain_grid,     nullptr),
+	H2G_KNOB("mate_handover",  "H2G_FAST_MATE_HANDOVER", -1,                       mate_handover,  nullptr),
+	H2G_KNOB("ps0",            "H2G_FAST_PS0",           -1,                       ps0,            nullptr),
+	H2G_KNOB("fast_spliced",   "H2G_FAST_SPLICED",       H2G_DEFAULT_FAST_SPLICED, fast_spliced,   nullptr),
+	H2G_KNOB("mach_total",     "H2G_MACH_TOTAL",         H2G_MACH_TOTAL,           mach_total,     &h2g_stream::Tune::mach_total_auto),
+	H2G_KNOB("fast_reserve",   "H2G_FAST_RESERVE",       H2G_FAST_RESERVE_DEFAULT, fast_reserve,   nullptr),
+};
+#undef H2G_KNOB
+// ("mstreams" / H2G_MSTREAMS and "mstreams_light" / H2G_MSTREAMS_LIGHT are the stream's own members, both clamped to the HIP streams that exist)
+static unsigned clamp_mstreams(long m) { return (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); }
+
 // A stream of this library USES 2 + S HIP streams (the fast launches', the drain launches', and the S <= H2G_MSTREAMS_MAX machine streams in rotation: 2 while the fast pass hands on little) whose kernels must be able to run side by side.  ROCclr maps HIP streams onto
 // GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue serialise — measured: four machine passes "in flight" on the
 // default 4 queues ran one after the other (repeat-structured leg: 127 ms per step against 78 ms with 16 queues; profiles/r05_NOTES.md), and a machine pass or a drain launch in
@@ -903,14 +962,14 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 	// process's streams, and the place decides which launches serialise (profiles/r08_mstreams.md §2: the same two machine streams in rotation, created on first use
 	// behind the drain stream, 18.4 ms per step; created here, 10.8).  A stream that never enters the rotation never runs a kernel, holds no pools and costs nothing.
 	HIPCHK(s->st.create(hipStreamNonBlocking));
-	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { HIPCHK(s->mst[k].create(hipStreamNonBlocking)); HIPCHK(s->ev_rot[k].create(hipEventDisableTiming)); }
+	for(int k = 0; k < H2G_MSTREAMS_MAX; k++) { HIPCHK(s->mst[k].create(hipStreamNonBlocking)); HIPCHK(s->mach[k].ev_rot.create(hipEventDisableTiming)); }
 	HIPCHK(s->dst.create(hipStreamNonBlocking));
 	HIPCHK(s->h_fast_args.ensure(2 * H2G_NBUF));
 	HIPCHK(s->h_bails.ensure(H2G_NBUF)); for(int k = 0; k < H2G_NBUF; k++) s->h_bails[k] = 0;
-	for(int k = 0; k < H2G_NBUF; k++) { HIPCHK(s->ev_fast[k].create(hipEventDisableTiming)); HIPCHK(s->ev_mach[k].create(hipEventDisableTiming)); HIPCHK(s->ev_bails[k].create(hipEventDisableTiming)); HIPCHK(s->ev_drain[k].create(hipEventDisableTiming)); }
-	for(int k = 0; k < H2G_FAST_POOLS; k++) HIPCHK(s->ev_pool[k].create(hipEventDisableTiming));
+	for(h2g_stream::RunSet& b : s->run) { HIPCHK(b.ev_fast.create(hipEventDisableTiming)); HIPCHK(b.ev_mach.create(hipEventDisableTiming)); HIPCHK(b.ev_bails.create(hipEventDisableTiming)); HIPCHK(b.ev_drain.create(hipEventDisableTiming)); }
+	for(h2g_stream::FastPool& fp : s->fpool) HIPCHK(fp.ev_last.create(hipEventDisableTiming));
 	for(int k = 0; k < 2; k++) HIPCHK(s->ev_dr[k].create());
-	for(int i = 0; i < 14; i++) HIPCHK(s->ev[i].create());
+	for(DevEvent& e : s->tm) HIPCHK(e.create());
 	HIPCHK(s->d_counters.ensure(H2G_NBUF * H2G_CNT_BLOCK));
 	HIPCHK(hipMemset(s->d_counters, 0, s->d_counters.bytes()));
 	s->cnt_cur = s->d_counters;
@@ -922,19 +981,14 @@ extern "C" h2g_status h2g_stream_create(h2g_index* ix, size_t max_reads, size_t 
 		HIPCHK(hipMemset(s->d_seed, 0, s->d_seed.bytes()));
 	}
 	memset(&s->last, 0, sizeof s->last);
-	{
-		auto env = [](const char* k, long d) { const char* e = getenv(k); return e ? atol(e) : d; };
-		s->tune.fast = (int)env("H2G_GO_FAST", 1); s->tune.blocks_per_cu = (int)env("H2G_GO_BLOCKS_PER_CU", 0); s->tune.pair_slots = (int)env("H2G_PAIR_SLOTS", 0);
-		s->tune.no_second_pass = (int)env("H2G_GO_NO_SECOND_PASS", 0); s->tune.mach_div = (unsigned)env("H2G_MACH_DIV", 0); s->tune.mach_min = (unsigned)env("H2G_MACH_MIN", 4);
-		s->tune.dbg_read = env("H2G_GO_DBG_READ", -1);
-		s->tune.tail = (int)env("H2G_FAST_TAIL", H2G_DEFAULT_TAIL); s->tune.tail_auto = getenv("H2G_FAST_TAIL") ? 0 : 1; s->tune.align_mate = (int)env("H2G_FAST_AM", H2G_DEFAULT_ALIGN_MATE);
-		s->tune.orphan = (int)env("H2G_FAST_ORPHAN", -1); s->tune.drain_grid = (int)env("H2G_DRAIN_GRID", H2G_DRAIN_GRID); s->tune.mate_handover = (int)env("H2G_FAST_MATE_HANDOVER", -1); s->tune.ps0 = (int)env("H2G_FAST_PS0", -1);
-		s->tune.fast_spliced = (int)env("H2G_FAST_SPLICED", H2G_DEFAULT_FAST_SPLICED);
-		s->tune.mach_total = (unsigned)env("H2G_MACH_TOTAL", H2G_MACH_TOTAL); s->tune.mach_total_auto = getenv("H2G_MACH_TOTAL") ? 0 : 1; s->tune.fast_reserve = (int)env("H2G_FAST_RESERVE", H2G_FAST_RESERVE_DEFAULT);
-		auto clampm = [](long m) { return (unsigned)(m < 1 ? 1 : m > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : m); };
-		if(getenv("H2G_MSTREAMS")) s->mstreams = clampm(env("H2G_MSTREAMS", 0));   // pinned
-		s->mstreams_light = clampm(env("H2G_MSTREAMS_LIGHT", H2G_MSTREAMS_LIGHT_DEFAULT));
+	// the knobs: each one's default, or what its environment name says; a knob set there is no longer its policy's
+	for(const Knob& k : g_knobs) {
+		const char* const e = getenv(k.env);
+		k.set(s->tune, e ? atol(e) : k.def);
+		if(e && k.is_auto) s->tune.*k.is_auto = 0;
 	}
+	if(const char* const e = getenv("H2G_MSTREAMS")) s->mstreams = clamp_mstreams(atol(e));   // pinned
+	if(const char* const e = getenv("H2G_MSTREAMS_LIGHT")) s->mstreams_light = clamp_mstreams(atol(e));
 	*out = sp.release();
 	return H2G_OK;
 }
@@ -1270,7 +1324,7 @@ static int launch_rank(h2g_stream* s, const uint32_t* d_rows, const uint8_t* d_c
 	if(!graph && (!g.linear || g.lineRate != 6)) { snprintf(g_err, sizeof g_err, "rank kernels: 64 B linear or 128 B graph sides only"); return H2G_ERR_UNSUPPORTED; }
 	if(graph && g.nZ > 1 && variant == 1) variant = 0;   // the cooperative kernel handles a single '$' row
 	if(repeats < 1) repeats = 1;
-	HIPCHK(hipEventRecord(s->ev[0], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		if(graph) {
 			if(variant == 0) hipLaunchKernelGGL(k_rank_g0, dim3(grid_for(n, 256)), dim3(256), 0, s->st, g, d_rows, d_cs, d_out, n, seed, synth);
@@ -1301,11 +1355,11 @@ static int launch_rank(h2g_stream* s, const uint32_t* d_rows, const uint8_t* d_c
 			hipLaunchKernelGGL(k_rank_v0, dim3(blocks), dim3(256), 0, s->st, g, d_rows, d_cs, d_out, n, seed, synth);
 		} else return H2G_ERR_ARG;
 	}
-	HIPCHK(hipEventRecord(s->ev[1], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM1], s->st));
 	HIPCHK(sync_all(s));
 	HIPCHK(hipGetLastError());
 	float t = 0;
-	HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+	HIPCHK(hipEventElapsedTime(&t, s->tm[TM_PRIM0], s->tm[TM_PRIM1]));
 	s->last.ms_rank = t / repeats;
 	if(ms) *ms = t / repeats;
 	return H2G_OK;
@@ -1425,19 +1479,19 @@ extern "C" H2G_EXPORT h2g_status h2g_rank_chain_bench(h2g_stream* s, size_t ncha
 #undef H2G_CHAIN_CASE
 	if(lds_bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) (void)hipGetLastError();
 	unsigned long long* dsum = s->d_counters + H2G_CNT_BENCH_CHECKSUM;
-	HIPCHK(hipEventRecord(s->ev[0], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		HIPCHK(hipMemsetAsync(dsum, 0, 8, s->st));
 		void* args[] = {(void*)&g, (void*)&seed, (void*)&steps, (void*)&nlanes, (void*)&dsum};
 		HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3((unsigned)block), args, (size_t)lds_bytes, s->st));
 	}
-	HIPCHK(hipEventRecord(s->ev[1], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM1], s->st));
 	unsigned long long v = 0;
 	HIPCHK(hipMemcpyAsync(&v, dsum, 8, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
 	HIPCHK(hipGetLastError());
 	float t = 0;
-	HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+	HIPCHK(hipEventElapsedTime(&t, s->tm[TM_PRIM0], s->tm[TM_PRIM1]));
 	if(kernel_ms) *kernel_ms = t / repeats;
 	if(checksum) *checksum = v;
 	return H2G_OK;
@@ -1501,19 +1555,19 @@ extern "C" H2G_EXPORT h2g_status h2g_glf_chain_bench(h2g_stream* s, size_t nchai
 	const void* fn = chains_per_lane == 1 ? (const void*)k_glf_chain<1> : chains_per_lane == 2 ? (const void*)k_glf_chain<2> : (const void*)k_glf_chain<4>;
 	if(lds_bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) (void)hipGetLastError();
 	unsigned long long* dsum = s->d_counters + H2G_CNT_BENCH_CHECKSUM;
-	HIPCHK(hipEventRecord(s->ev[0], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		HIPCHK(hipMemsetAsync(dsum, 0, 8, s->st));
 		void* args[] = {(void*)&g, (void*)&seed, (void*)&steps, (void*)&nlanes, (void*)&staged, (void*)&dsum};
 		HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3((unsigned)block), args, (size_t)lds_bytes, s->st));
 	}
-	HIPCHK(hipEventRecord(s->ev[1], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM1], s->st));
 	unsigned long long v = 0;
 	HIPCHK(hipMemcpyAsync(&v, dsum, 8, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
 	HIPCHK(hipGetLastError());
 	float t = 0;
-	HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+	HIPCHK(hipEventElapsedTime(&t, s->tm[TM_PRIM0], s->tm[TM_PRIM1]));
 	if(kernel_ms) *kernel_ms = t / repeats;
 	if(checksum) *checksum = v;
 	return H2G_OK;
@@ -1951,26 +2005,26 @@ extern "C" h2g_status h2g_ext_search(h2g_stream* s, const h2g_ext_search_query* 
 	align_params_defaults(&ap, !graph);
 	const AlnParams P = aln_params_from(ap, true, !graph);
 	const uint32_t minK = s->ix->dg.minK, minKl = P.minK_local, kseeds = P.kseeds;
-	HIPCHK(hipEventRecord(s->ev[0], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM0], s->st));
 	if(!buckets.empty()) {
 		const unsigned grid = (unsigned)(buckets.size() < 256 * 8 ? buckets.size() : 256 * 8);
 		hipLaunchKernelGGL(k_ext_search_lds, dim3(grid), dim3(256), max_stage, s->st, s->ix->dg, dls_now(s->ix), dreads(s), (const h2g_ext_search_query*)dq, d_olds,
 		                   (const uint2*)dbk, (uint32_t)buckets.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
 	}
-	HIPCHK(hipEventRecord(s->ev[1], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM1], s->st));
 	if(!o_hbm.empty()) {
 		if(graph) hipLaunchKernelGGL((k_ext_search_hbm<true>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, dls_now(s->ix), dreads(s),
 		                             (const h2g_ext_search_query*)dq, d_ohbm, o_hbm.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
 		else hipLaunchKernelGGL((k_ext_search_hbm<false>), dim3(grid_for(o_hbm.size(), 256)), dim3(256), 0, s->st, s->ix->dg, dls_now(s->ix), dreads(s),
 		                        (const h2g_ext_search_query*)dq, d_ohbm, o_hbm.size(), minK, minKl, kseeds, (h2g_ext_search_hit*)dout);
 	}
-	HIPCHK(hipEventRecord(s->ev[9], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_EXT1], s->st));
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, dout, n * sizeof *out, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
 	float t = 0;
-	if(hipEventElapsedTime(&t, s->ev[0], s->ev[1]) == hipSuccess) st.ms_staged = t;
-	if(hipEventElapsedTime(&t, s->ev[1], s->ev[9]) == hipSuccess) st.ms_hbm = t;
+	if(hipEventElapsedTime(&t, s->tm[TM_PRIM0], s->tm[TM_PRIM1]) == hipSuccess) st.ms_staged = t;
+	if(hipEventElapsedTime(&t, s->tm[TM_PRIM1], s->tm[TM_EXT1]) == hipSuccess) st.ms_hbm = t;
 	if(stats) *stats = st;
 	return H2G_OK;
 }
@@ -2010,7 +2064,7 @@ extern "C" h2g_status h2g_sw_align(h2g_stream* s, const h2g_sw_query* q, size_t 
 	HIPCHK(hipMemcpyAsync(dq, q, n * sizeof *q, hipMemcpyHostToDevice, s->st));
 	SwParams P;
 	if(repeats < 1) repeats = 1;
-	HIPCHK(hipEventRecord(s->ev[0], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM0], s->st));
 	for(int r = 0; r < repeats; r++) {
 		for(size_t first = 0; first < n; first += batch) {
 			const size_t nb = n - first < batch ? n - first : batch;
@@ -2019,12 +2073,12 @@ extern "C" h2g_status h2g_sw_align(h2g_stream* s, const h2g_sw_query* q, size_t 
 			                   (const h2g_sw_query*)dq + first, nb, ws, s->d_sw_states, (h2g_sw_result*)dout + first);
 		}
 	}
-	HIPCHK(hipEventRecord(s->ev[1], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_PRIM1], s->st));
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, dout, n * sizeof *out, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
 	float t = 0;
-	HIPCHK(hipEventElapsedTime(&t, s->ev[0], s->ev[1]));
+	HIPCHK(hipEventElapsedTime(&t, s->tm[TM_PRIM0], s->tm[TM_PRIM1]));
 	if(kernel_ms) *kernel_ms = t / repeats;
 	return H2G_OK;
 }
@@ -2135,11 +2189,11 @@ extern "C" h2g_status h2g_seed_extend_run(h2g_stream* s, const h2g_seed_params* 
 	const size_t n = s->cur().n_reads * 2;
 	HIPCHK(hipMemsetAsync(s->d_counters, 0, 4 * sizeof(unsigned long long), s->st));
 	DScoring sc;
-	HIPCHK(hipEventRecord(s->ev[2], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SEED0], s->st));
 	hipLaunchKernelGGL(k_seed_search, dim3(grid_for(n, 256)), dim3(256), 0, s->st, s->ix->dg, dreads(s), *p, s->d_seed, s->d_counters);
-	HIPCHK(hipEventRecord(s->ev[3], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SEED_MID], s->st));
 	hipLaunchKernelGGL(k_seed_resolve_extend, dim3(grid_for(n, 256)), dim3(256), 0, s->st, dg_now(s->ix), s->ix->dr, dreads(s), sc, s->d_seed, s->d_counters);
-	HIPCHK(hipEventRecord(s->ev[4], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SEED1], s->st));
 	HIPCHK(hipGetLastError());
 	s->ran_seed = true;
 	return H2G_OK;
@@ -2304,15 +2358,15 @@ extern "C" h2g_status h2g_set_reads_windows(h2g_stream* s, const uint8_t* text, 
 	HIPCHK(hipMemcpyAsync(d_segs, ds.data(), ds.size() * sizeof(h2g_win::DSeg), hipMemcpyHostToDevice, s->st));
 	if(n_prefix_bytes) HIPCHK(hipMemcpyAsync(d_pre, prefixes, n_prefix_bytes, hipMemcpyHostToDevice, s->st));
 	const uint64_t n_bytes = n * len;
-	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET0], s->st));
 	k_win_codes<<<grid_for((n_bytes + 15) / 16, 256), 256, 0, s->st>>>((const uint8_t*)d_text, (const h2g_win::DSeg*)d_segs, (uint32_t)n_segs, len, step, n_bytes, B.d_codes);
 	k_win_meta<<<grid_for(n + 1, 256), 256, 0, s->st>>>((const h2g_win::DSeg*)d_segs, (uint32_t)n_segs, len, step, (uint32_t)n, (const char*)d_pre, B.d_offs, B.d_ids, B.d_name_offs, B.d_names);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET1], s->st));
 	HIPCHK(sync_all(s));
 	s->win_stats.bytes_uploaded = (hi - lo) + ds.size() * sizeof(h2g_win::DSeg) + n_prefix_bytes;
 	s->win_stats.bytes_written = n_bytes + (n + 1) * 8 + n * 4 + nb;
-	HIPCHK(hipEventElapsedTime(&s->win_stats.kernel_ms, s->ev[12], s->ev[13]));
+	HIPCHK(hipEventElapsedTime(&s->win_stats.kernel_ms, s->tm[TM_SET0], s->tm[TM_SET1]));
 	B.n_reads = n;
 	B.max_read_len = len;
 	B.has_quals = false;
@@ -2430,8 +2484,7 @@ static const FastUnitDesc& fast_unit(bool linear, bool spliced, bool align_mate)
 }
 
 // sizes the per-lane scratch of one pass and fills the pool fields of `a`
-static int go_pool_for(h2g_stream* s, int which, const GoUnitDesc& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
-	h2g_stream::GoPool& pl = s->pool[which];
+static int go_pool_for(h2g_stream* s, h2g_stream::GoPool& pl, const GoUnitDesc& u, size_t slots, size_t lanes, uint32_t bowtie2_dp, GoArgs* a) {
 	const size_t wsb = u.ws_bytes, gwb = u.gws_bytes;
 	HIPCHK(pl.ws.reserve(slots * wsb));
 	a->pool = pl.ws; a->ws_stride = wsb; a->slot_off = u.slot_off; a->gsl_off = u.gsl_off;
@@ -2585,17 +2638,20 @@ struct FastPlan {
 	bool ps0;                      // the first partial searches run in a pre-pass in front of the fast launch (h2g_k_ps0.hip)
 	const FastUnitDesc *FU, *DU;   // the fast launch's build of the pass and the drain launch's
 	unsigned fgrid, mgrid, dgrid;  // workgroups of the fast launch, of the machine pass behind it, of the drain launch
-	uint32_t orphan_T, psel;       // > 0: the end of the batch goes to a drain launch; the slot pool of the fast launch ...
+	uint32_t orphan_T;             // > 0: the end of the batch goes to a drain launch
+	h2g_stream::FastPool* pool;    // the slot pool of the fast launch (gen % H2G_FAST_POOLS with a drain launch, the first without) ...
 	size_t slot_bytes;             // ... and its size
 };
-// what a run queued now carries through to the end of go_run
+// what a run queued now carries through to the end of go_run: its record of each index space (h2g_stream)
 struct GoRun {
 	GoArgs A; DExonTbl X; XlPairs XP;   // the main pass's arguments (X: --avoid-pseudogene's exons, an argument of their own)
-	unsigned gsel, msel, ssel;     // the per-run buffer set (gen % (M + 1)), the lane (gen % M) and its machine stream (lane % S)
-	unsigned long long* cblk;      // the run's counter block (h2g_go_args.h)
+	h2g_stream::RunSet* set;       // the per-run buffer set, gen % (M + 1) ...
+	unsigned long long* cblk;      // ... and its counter block (h2g_go_args.h)
+	unsigned lane;                 // the run's parts of the three areas: gen % M behind a fast pass, 0 otherwise
+	h2g_stream::MachStream* mach;  // the machine stream of the lane, lane % S: its pools and overflow list are the main pass's ...
+	hipStream_t ms;                // ... which runs on its HIP stream behind a fast pass, on the first stream otherwise ...
+	unsigned mach_grid;            // ... on this many workgroups
 	FastPlan f;
-	hipStream_t ms;                // the stream of the machine's passes ...
-	unsigned mach_grid, psel, qsel;   // ... the main pass's workgroups there, its long-edit part (the lane's), and its pools and overflow list (the stream's)
 	uint32_t* ovl;                 // the main pass's overflow list (+ its count behind it)
 };
 
@@ -2620,21 +2676,29 @@ static void go_args(const h2g_stream* s, const h2g_align_params* p, bool paired,
 	A.paired = paired ? 1u : 0u;
 }
 
+// the run's record of each index space (h2g_stream).  A run that is not behind a fast pass is lane 0 on the first stream, with machine stream 0's pools and overflow list
+static void go_select(h2g_stream* s, const GoPlan& g, GoRun* r) {
+	r->set = &s->run[s->gen % (g.M + 1)];
+	r->cblk = s->counters(*r->set);
+	r->lane = g.fast ? s->gen % g.M : 0u;
+	r->mach = &s->mach[r->lane % g.S];
+}
+
 // The machine streams in rotation for a run behind a fast pass: mst[0 .. S); n_mst counts those that ever entered (the others hold nothing to wait for).  When S changes, lane m moves from stream
 // m % S' to m % S: what it shares with its earlier passes (its parts' cursors, the rows of a batch) was ordered by the stream, so every stream of the new
 // rotation waits for everything queued on the streams in use — on the device: the host never waits here.
 static int go_rotation(h2g_stream* s, const GoPlan& g) {
 	if(s->n_mst < g.S) s->n_mst = g.S;
 	if(s->rot && s->rot != g.S && s->st2_busy) {
-		for(unsigned j = 0; j < s->rot; j++) HIPCHK(hipEventRecord(s->ev_rot[j], s->mst[j]));
-		for(unsigned k = 0; k < g.S; k++) for(unsigned j = 0; j < s->rot; j++) if(j != k) HIPCHK(hipStreamWaitEvent(s->mst[k], s->ev_rot[j], 0));
+		for(unsigned j = 0; j < s->rot; j++) HIPCHK(hipEventRecord(s->mach[j].ev_rot, s->mst[j]));
+		for(unsigned k = 0; k < g.S; k++) for(unsigned j = 0; j < s->rot; j++) if(j != k) HIPCHK(hipStreamWaitEvent(s->mst[k], s->mach[j].ev_rot, 0));
 	}
 	s->rot = g.S;
 	return H2G_OK;
 }
 
-// the main pass's per-lane scratch: behind a fast pass the machine works on stream (gen % M) % S with that stream's pools, on at most mach_cap workgroups
-static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoArgs* A) {
+// the main pass's per-lane scratch: behind a fast pass the machine works on the lane's machine stream with that stream's pools, on at most mach_cap workgroups
+static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoRun* r) {
 	const size_t pgrid = g.fast && g.grid > g.pool_cap ? (size_t)g.pool_cap : (size_t)g.grid;
 	int rc;
 	if(g.fast && s->cur().n_reads >= 200000) {
@@ -2643,20 +2707,22 @@ static int go_pools(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, G
 		// batch — a command line over a million pairs — never needs streams 1 .. S - 1: their 30 GB of pools were a second of its three); a stream that enters the
 		// rotation later (the regime turns heavy) gets its pools then.
 		// (Small batches keep allocating a machine stream's pools when it is first used.)
-		GoArgs scratch = *A;
-		for(unsigned m = 0; m < g.S && s->gen >= 1; m++) {
-			if((rc = go_pool_for(s, 2 * (int)m, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, &scratch))) return rc;
-			if(g.second && (rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &scratch))) return rc;
+		GoArgs scratch = r->A;
+		for(unsigned k = 0; k < g.S && s->gen >= 1; k++) {
+			h2g_stream::MachStream& m = s->mach[k];
+			if((rc = go_pool_for(s, m.main, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, &scratch))) return rc;
+			if(g.second && (rc = go_pool_for(s, m.second, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &scratch))) return rc;
 			// ... and its overflow list
-			if(!s->d_ovf_list[m]) { HIPCHK(s->d_ovf_list[m].ensure(s->max_reads + 4)); HIPCHK(hipMemsetAsync(s->d_ovf_list[m] + s->max_reads, 0, 16, s->mst[m])); }
+			if(!m.ovf_list) { HIPCHK(m.ovf_list.ensure(s->max_reads + 4)); HIPCHK(hipMemsetAsync(m.ovf_list + s->max_reads, 0, 16, s->stream_of(m))); }
 		}
-		for(unsigned b = 0; b < g.M + 1; b++) {      // the per-run buffers of every generation
-			HIPCHK(s->d_bail_list[b].ensure(s->max_reads + 4));
-			HIPCHK(s->d_fast_args[b].ensure(1));
-			HIPCHK(s->d_fast_args[H2G_NBUF + b].ensure(1));
+		for(unsigned k = 0; k < g.M + 1; k++) {      // the per-run buffers of every generation
+			h2g_stream::RunSet& b = s->run[k];
+			HIPCHK(b.bail_list.ensure(s->max_reads + 4));
+			HIPCHK(b.fast_args.ensure(1));
+			HIPCHK(b.drain_args.ensure(1));
 		}
 	}
-	return go_pool_for(s, g.fast ? 2 * (int)((s->gen % g.M) % g.S) : 0, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, A);
+	return go_pool_for(s, r->mach->main, *g.U, pgrid * g.U->slots, pgrid * g.U->threads, p->bowtie2_dp, &r->A);
 }
 
 // the batch's result rows (grown to this run's -k), the pairs' overflow area and the XL units' side area
@@ -2682,52 +2748,43 @@ static int go_rows(h2g_stream* s, const h2g_align_params* p, bool paired, const 
 		// One part per lane: the machine passes of M queued runs may be in flight together and each takes its blocks
 		// from its own cursor.  Block offsets (PairOut::pad) are relative to the whole area, so whichever pass wrote a pair last, its block is found.
 		const size_t ovf_cap = s->max_reads / 4 > 65536 ? s->max_reads / 4 : 65536;   // records per part
-		if(s->paln_ovf_cap < ovf_cap || s->paln_ovf_parts < g.M) {
+		if(!s->paln_ovf.fits(g.M, ovf_cap)) {
 			HIPCHK(sync_mach(s));
 			HIPCHK(hipStreamSynchronize(s->st));
-			s->paln_ovf_cap = 0; s->paln_ovf_parts = 0;
-			HIPCHK(s->d_paln_ovf.reset(g.M * ovf_cap));
-			s->paln_ovf_cap = ovf_cap; s->paln_ovf_parts = g.M;
+			HIPCHK(s->paln_ovf.reset(g.M, ovf_cap));
 		}
-		A.O.ovf = s->d_paln_ovf;
+		A.O.ovf = s->paln_ovf;
 	}
 	memset(&r->XP, 0, sizeof r->XP);
 	if(paired && g.xl) {
-		// the XL units' side area: a word per read, and per machine stream a part of lists with a cursor (an XL run is never behind a fast pass: it
+		// the XL units' side area: a word per read, and per lane a part of lists with a cursor (an XL run is never behind a fast pass: it
 		// runs on the first stream and uses part 0, but the area is partitioned the way the overflow area is)
 		const size_t xcap = s->max_reads * 64 > ((size_t)1 << 20) ? s->max_reads * 64 : ((size_t)1 << 20);      // words per part
-		if(s->d_xlp_at.size() < s->max_reads || s->xlp_cap < xcap || s->xlp_parts < g.M) {
+		if(s->d_xlp_at.size() < s->max_reads || !s->xlp.fits(g.M, xcap) || !s->d_xlp_cur) {
 			HIPCHK(hipStreamSynchronize(s->st));
-			s->xlp_cap = 0; s->xlp_parts = 0;
 			HIPCHK(s->d_xlp_at.reset(s->max_reads));
-			HIPCHK(s->d_xlp.reset(g.M * xcap));
+			HIPCHK(s->xlp.reset(g.M, xcap));
 			HIPCHK(s->d_xlp_cur.ensure(H2G_MSTREAMS_MAX));
-			s->xlp_cap = xcap; s->xlp_parts = g.M;
 		}
-		const unsigned part = 0;
 		HIPCHK(hipMemsetAsync(s->d_xlp_at, 0, b.n_reads * 4, s->st));
-		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_xlp_cur + part), (int)(part * s->xlp_cap), 1, s->st));
-		r->XP.at = s->d_xlp_at; r->XP.list = s->d_xlp; r->XP.cursor = s->d_xlp_cur + part; r->XP.cap = (uint32_t)((part + 1) * s->xlp_cap);
+		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_xlp_cur + r->lane), (int)s->xlp.lo(r->lane), 1, s->st));
+		r->XP.at = s->d_xlp_at; r->XP.list = s->xlp; r->XP.cursor = s->d_xlp_cur + r->lane; r->XP.cap = (uint32_t)s->xlp.hi(r->lane);
 	}
 	if(paired) s->xlp_pout = g.xl ? b.d_pout : (s->xlp_pout == b.d_pout ? nullptr : s->xlp_pout);
 	return H2G_OK;
 }
 
-// the run's counter block and cursors: the fast pass's hand-on list, the counters and its argument block are buffered H2G_NBUF deep — the general machine's
-// pass over run k's hand-ons (lane k % M, on machine stream lane % S) may still be under way while the fast passes of the following runs run
+// the run's counter block (its buffer set's: h2g_stream::RunSet) and cursors
 static int go_counters(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	GoArgs& A = r->A;
-	r->gsel = s->gen % (g.M + 1); r->msel = s->gen % g.M; r->ssel = r->msel % g.S;
-	r->cblk = s->d_counters + H2G_CNT_BLOCK * r->gsel;
-	HIPCHK(hipStreamWaitEvent(s->st, s->ev_mach[r->gsel], 0));          // run k - NB's machine pass: done with this set of buffers
+	HIPCHK(hipStreamWaitEvent(s->st, r->set->ev_mach, 0));          // run k - NB's machine pass: done with this set of buffers
 	HIPCHK(hipMemsetAsync(r->cblk, 0, H2G_CNT_BLOCK * sizeof(unsigned long long), s->st));
 	A.counters = r->cblk;
 	A.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_MAIN);
 	if(paired) {   // the cursor starts at this lane's part of the area
-		const uint32_t half = g.fast ? r->msel : 0u;
 		A.O.ovf_cursor = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_OVF_CURSOR);
-		A.O.ovf_cap = (uint32_t)((half + 1) * s->paln_ovf_cap);
-		if(half) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ovf_cursor, (int)(half * s->paln_ovf_cap), 1, s->st));
+		A.O.ovf_cap = (uint32_t)s->paln_ovf.hi(r->lane);
+		if(r->lane) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ovf_cursor, (int)s->paln_ovf.lo(r->lane), 1, s->st));
 	}
 	A.list = nullptr; A.nlist = nullptr;
 	if(s->tune.dbg_read >= 0) {
@@ -2753,8 +2810,8 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	// (the machine takes ~150 hand-ons per workgroup in half the time of a fast pass; the count is the last finished fast pass's)
 	const unsigned NB = g.M + 1;
 	for(unsigned back = 1; back < NB && back <= s->gen; back++) {                           // the latest fast pass that is over
-		const unsigned b = (s->gen - back) % NB;
-		if(hipEventQuery(s->ev_bails[b]) == hipSuccess) { s->last_bails = s->h_bails[b]; break; }
+		const h2g_stream::RunSet& b = s->run[(s->gen - back) % NB];
+		if(hipEventQuery(b.ev_bails) == hipSuccess) { s->last_bails = s->h_bail(b); break; }
 	}
 	(void)hipGetLastError();
 	// hand-ons per machine workgroup (latency chains, two passes in flight).  Linear index: 400 — the fast pass is short and the machine's pass bounds the
@@ -2793,7 +2850,7 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 	// — the hot loop keeps the lighter build, the machine sees neither them nor the tail (h2g_stream_tune "mate_handover": -1 this policy, 0 off, 1 on)
 	f->mate_ho = f->orphan_T != 0 && linear && paired && !f->use_am && !g.fast_spl && s->tune.mate_handover != 0;
 	f->DU = &fast_unit(linear, g.fast_spl, f->use_am || f->mate_ho);
-	f->psel = f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u;
+	f->pool = &s->fpool[f->orphan_T ? s->gen % H2G_FAST_POOLS : 0u];
 	// the first partial searches in front of the loop: the linear non-spliced builds (h2g_stream_tune "ps0": -1 this policy, 0 off, 1 on)
 	f->ps0 = linear && !g.fast_spl && (s->tune.ps0 < 0 ? H2G_DEFAULT_PS0 != 0 : s->tune.ps0 != 0);
 }
@@ -2802,30 +2859,34 @@ static void fast_policy(h2g_stream* s, bool paired, const GoPlan& g, FastPlan* f
 static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 	const size_t ocap = (size_t)256 * f.FU->slots, dbytes = (size_t)f.dgrid * f.DU->slots * f.DU->slot_bytes;
 	const size_t dsc = g.linear ? 0 : (size_t)f.dgrid * f.FU->threads * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t));
-	bool need = s->d_fast_slots[f.psel].size() < f.slot_bytes;
+	// the pools a run may meet: with a drain launch all of them (the following runs' go round), without one its own
+	h2g_stream::FastPool* const pools = f.orphan_T ? s->fpool : f.pool;
+	const unsigned npools = f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u;
+	bool need = f.pool->slots.size() < f.slot_bytes;
 	if(f.orphan_T) {
-		for(unsigned q = 0; q < H2G_FAST_POOLS; q++) need = need || s->d_fast_slots[q].size() < f.slot_bytes;
+		for(unsigned q = 0; q < npools; q++) need = need || pools[q].slots.size() < f.slot_bytes;
 		need = need || s->d_drain_slots.size() < dbytes || s->d_drain_sc.size() < dsc;
-		for(unsigned b = 0; b < g.M + 1; b++) need = need || !s->d_orphans[b] || !s->d_fast_args[H2G_NBUF + b];
+		for(unsigned b = 0; b < g.M + 1; b++) need = need || !s->run[b].orphans || !s->run[b].drain_args;
 		need = need || s->orphan_cap < ocap;
 	}
 	const size_t pswords = (size_t)s->max_reads * 4 * FG_PS0_WORDS;     // one record per (unit, mate, strand)
-	if(f.ps0) for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) need = need || s->d_ps0[f.orphan_T ? q : f.psel].size() < pswords;
+	if(f.ps0) for(unsigned q = 0; q < npools; q++) need = need || pools[q].ps0.size() < pswords;
 	if(!need) return H2G_OK;
 	// (every stream, whatever st2_busy and dst_busy say: the pools about to be freed may be any launch's)
 	HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipStreamSynchronize(s->dst)); for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
 	// (fresh memory is written once, on the first stream)
-	for(unsigned q = 0; q < (f.orphan_T ? (unsigned)H2G_FAST_POOLS : 1u); q++) {
-		DevBuf<uint8_t>& fs = s->d_fast_slots[f.orphan_T ? q : f.psel];
+	for(unsigned q = 0; q < npools; q++) {
+		DevBuf<uint8_t>& fs = pools[q].slots;
 		if(fs.size() < f.slot_bytes) { HIPCHK(fs.reserve(f.slot_bytes)); HIPCHK(hipMemsetAsync(fs, 0, f.slot_bytes, s->st)); }
-		DevBuf<uint32_t>& ps = s->d_ps0[f.orphan_T ? q : f.psel];
+		DevBuf<uint32_t>& ps = pools[q].ps0;
 		if(f.ps0 && ps.size() < pswords) { HIPCHK(ps.reserve(pswords)); HIPCHK(hipMemsetAsync(ps, 0xff, pswords * 4, s->st)); }
 	}
 	if(f.orphan_T) {
-		if(s->orphan_cap < ocap) { for(int b = 0; b < H2G_NBUF; b++) s->d_orphans[b] = DevBuf<uint32_t>(); s->orphan_cap = ocap; }
-		for(unsigned b = 0; b < g.M + 1; b++) {
-			if(!s->d_orphans[b]) { HIPCHK(s->d_orphans[b].ensure(s->orphan_cap + 4)); HIPCHK(hipMemsetAsync(s->d_orphans[b], 0, (s->orphan_cap + 4) * 4, s->st)); }
-			HIPCHK(s->d_fast_args[H2G_NBUF + b].ensure(1));
+		if(s->orphan_cap < ocap) { for(h2g_stream::RunSet& b : s->run) b.orphans = DevBuf<uint32_t>(); s->orphan_cap = ocap; }
+		for(unsigned k = 0; k < g.M + 1; k++) {
+			h2g_stream::RunSet& b = s->run[k];
+			if(!b.orphans) { HIPCHK(b.orphans.ensure(s->orphan_cap + 4)); HIPCHK(hipMemsetAsync(b.orphans, 0, (s->orphan_cap + 4) * 4, s->st)); }
+			HIPCHK(b.drain_args.ensure(1));
 		}
 		if(s->d_drain_slots.size() < dbytes) { HIPCHK(s->d_drain_slots.reserve(dbytes)); HIPCHK(hipMemsetAsync(s->d_drain_slots, 0, dbytes, s->st)); }
 		if(s->d_drain_sc.size() < dsc) { HIPCHK(s->d_drain_sc.reserve(dsc)); HIPCHK(hipMemsetAsync(s->d_drain_sc, 0, dsc, s->st)); }
@@ -2838,25 +2899,25 @@ static int fast_buffers(h2g_stream* s, const GoPlan& g, const FastPlan& f) {
 static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	const FastPlan& f = r->f;
 	const GoArgs& A = r->A;
-	const unsigned gsel = r->gsel;
+	h2g_stream::RunSet& set = *r->set;
 	// run k - 3's drain launch is done with this pool — and a run WITHOUT a drain launch (a small resident batch queued behind a large one) uses pool 0, which the drain launch
 	// of an earlier run may still be reading: every fast launch waits for the last reader of its pool
-	HIPCHK(hipStreamWaitEvent(s->st, s->ev_pool[f.psel], 0));
-	HIPCHK(s->d_bail_list[gsel].ensure(s->max_reads + 4));
-	uint32_t* const bl = s->d_bail_list[gsel];
+	HIPCHK(hipStreamWaitEvent(s->st, f.pool->ev_last, 0));
+	HIPCHK(set.bail_list.ensure(s->max_reads + 4));
+	uint32_t* const bl = set.bail_list;
 	HIPCHK(hipMemsetAsync(bl + s->max_reads, 0, 16, s->st));
 	FastArgs F;
 	memset(&F, 0, sizeof F);
 	F.g = A.g; F.ref = A.ref; F.ls = A.ls; F.rd1 = A.rd1; F.rd2 = A.rd2; F.P = A.P;
 	F.names1 = A.names1; F.noffs1 = A.noffs1; F.names2 = A.names2; F.noffs2 = A.noffs2;
-	F.slots = (uint32_t*)s->d_fast_slots[f.psel].get();
+	F.slots = (uint32_t*)f.pool->slots.get();
 	F.O.rout = A.O.rout; F.O.aln = A.O.aln; F.O.aln_slots = A.O.aln_slots; F.O.pout = A.O.pout; F.O.paln[0] = A.O.paln[0]; F.O.paln[1] = A.O.paln[1]; F.O.pair_slots = A.O.pair_slots;
 	F.counters = r->cblk; F.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_FAST);
 	F.bail_list = bl; F.bail_count = bl + s->max_reads;
 	F.total = (uint32_t)s->cur().n_reads; F.paired = paired ? 1u : 0u;
 	F.alts = A.alts; F.gws_base = nullptr; F.gws_stride = 0; F.sc_base = nullptr;
 	F.dbg_read = A.dbg_read; F.dbg_buf = A.dbg_buf;
-	F.ps0 = f.ps0 ? s->d_ps0[f.psel].get() : nullptr;                   // (the drain launch reads run k's table beside run k + 1: D = F below)
+	F.ps0 = f.ps0 ? f.pool->ps0.get() : nullptr;                        // (the drain launch reads run k's table beside run k + 1: D = F below)
 	F.ssdb = A.ssdb; F.rdid_base = A.rdid_base;                          // (spliced runs: the database of this run — a wave of the temporary-splice-site mode brings its own)
 	// (single-end batches and graph indexes: there the machine's pass is the longer of the two already — NOTES §1, §3: 47 -> 53 ms per 500 k graph pairs with it)
 	F.tail = g.linear && paired && s->tune.tail > 0 ? (uint32_t)s->tune.tail : 0u;
@@ -2866,10 +2927,10 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 		HIPCHK(s->d_fast_sc.reserve(lanes * (size_t)(2 * H2G_COMBINE_MAXLEN * sizeof(int64_t))));
 		F.gws_base = s->d_fast_gws; F.gws_stride = f.FU->gws_bytes; F.sc_base = s->d_fast_sc;
 	}
-	HIPCHK(s->d_fast_args[gsel].ensure(1));
+	HIPCHK(set.fast_args.ensure(1));
 	FastArgs D = F;
 	if(f.orphan_T) {
-		uint32_t* const ol = s->d_orphans[gsel];
+		uint32_t* const ol = set.orphans;
 		HIPCHK(hipMemsetAsync(ol + s->orphan_cap, 0, 16, s->st));
 		F.orphan_T = f.orphan_T; F.orphan_list = ol; F.orphan_count = ol + s->orphan_cap; F.mate_handover = f.mate_ho ? 1u : 0u;
 		D.adopt_slot_words = f.FU->slot_bytes / 4;
@@ -2889,46 +2950,46 @@ static int fast_launch(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	// through pinned memory: a pageable source would make this call wait for everything queued on the stream (the previous run's fast
 	// pass), and the chip would idle while the host queues this run.  The staging block of this buffer set was last read by the upload
 	// of run k - H2G_NBUF, which is over once that run's fast pass is
-	if(s->gen >= g.M + 1 && hipEventQuery(s->ev_fast[gsel]) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipEventSynchronize(s->ev_fast[gsel])); }
-	FastArgs* const hF = s->h_fast_args + gsel;
+	if(s->gen >= g.M + 1 && hipEventQuery(set.ev_fast) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipEventSynchronize(set.ev_fast)); }
+	FastArgs* const hF = s->h_fast(set);
 	*hF = F;
-	HIPCHK(hipMemcpyAsync(s->d_fast_args[gsel], hF, sizeof F, hipMemcpyHostToDevice, s->st));
+	HIPCHK(hipMemcpyAsync(set.fast_args, hF, sizeof F, hipMemcpyHostToDevice, s->st));
 	if(f.orphan_T) {
-		FastArgs* const hD = s->h_fast_args + H2G_NBUF + gsel;
+		FastArgs* const hD = s->h_drain(set);
 		*hD = D;
-		HIPCHK(hipMemcpyAsync(s->d_fast_args[H2G_NBUF + gsel], hD, sizeof D, hipMemcpyHostToDevice, s->st));
+		HIPCHK(hipMemcpyAsync(set.drain_args, hD, sizeof D, hipMemcpyHostToDevice, s->st));
 	}
-	// the pre-pass: behind whatever produced the reads and behind the last reader of its table (stream order, ev_pool above), in front of the loop that reads it
-	if(f.ps0 && h2g_ps0_launch(s->d_fast_args[gsel], F.total, paired, s->st) != 0) return set_err("go() first-search pre-pass launch", hipGetLastError());
-	if(f.FU->launch(s->d_fast_args[gsel], f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
+	// the pre-pass: behind whatever produced the reads and behind the last reader of its table (stream order, the pool's ev_last above), in front of the loop that reads it
+	if(f.ps0 && h2g_ps0_launch(set.fast_args, F.total, paired, s->st) != 0) return set_err("go() first-search pre-pass launch", hipGetLastError());
+	if(f.FU->launch(set.fast_args, f.fgrid, s->st) != 0) return set_err("go() fast pass launch", hipGetLastError());
 	r->A.list = bl; r->A.nlist = bl + s->max_reads;
 	return H2G_OK;
 }
 
-// the stream hand-off behind a fast pass: the machine works on machine stream ssel (a short list on few workgroups: the next run's fast pass does not wait for it),
+// the stream hand-off behind a fast pass: the machine works on the lane's machine stream (a short list on few workgroups: the next run's fast pass does not wait for it),
 // after the drain launch when there is one
 static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 	const FastPlan& f = r->f;
-	const unsigned gsel = r->gsel;
-	HIPCHK(hipEventRecord(s->ev_fast[gsel], s->st));
-	r->ms = s->mst[r->ssel]; s->st2_busy = true;
+	h2g_stream::RunSet& set = *r->set;
+	HIPCHK(hipEventRecord(set.ev_fast, s->st));
+	r->ms = s->stream_of(*r->mach); s->st2_busy = true;
 	if(f.mgrid < r->mach_grid) r->mach_grid = f.mgrid;
 	if(f.orphan_T) {
 		// the drain launch: the reads the fast launch's workgroups left in flight, on the drain stream next to the following run's fast launch; the machine's pass needs its hand-ons too
-		HIPCHK(hipStreamWaitEvent(s->dst, s->ev_fast[gsel], 0));
+		HIPCHK(hipStreamWaitEvent(s->dst, set.ev_fast, 0));
 		HIPCHK(hipEventRecord(s->ev_dr[0], s->dst));
-		if(f.DU->launch_drain(s->d_fast_args[H2G_NBUF + gsel], f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
+		if(f.DU->launch_drain(set.drain_args, f.dgrid, s->dst) != 0) return set_err("go() drain launch", hipGetLastError());
 		HIPCHK(hipEventRecord(s->ev_dr[1], s->dst));
-		HIPCHK(hipEventRecord(s->ev_pool[f.psel], s->dst));
-		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
-		HIPCHK(hipEventRecord(s->ev_drain[gsel], s->dst));
-		HIPCHK(hipEventRecord(s->ev_bails[gsel], s->dst));
-		HIPCHK(hipStreamWaitEvent(r->ms, s->ev_drain[gsel], 0));
+		HIPCHK(hipEventRecord(f.pool->ev_last, s->dst));
+		HIPCHK(hipMemcpyAsync(&s->h_bail(set), set.bail_list + s->max_reads, 4, hipMemcpyDeviceToHost, s->dst));
+		HIPCHK(hipEventRecord(set.ev_drain, s->dst));
+		HIPCHK(hipEventRecord(set.ev_bails, s->dst));
+		HIPCHK(hipStreamWaitEvent(r->ms, set.ev_drain, 0));
 		s->ran_drain = true; s->dst_busy = true;
 	} else {
-		HIPCHK(hipMemcpyAsync(&s->h_bails[gsel], s->d_bail_list[gsel] + s->max_reads, 4, hipMemcpyDeviceToHost, s->st));
-		HIPCHK(hipEventRecord(s->ev_bails[gsel], s->st));
-		HIPCHK(hipStreamWaitEvent(r->ms, s->ev_fast[gsel], 0));
+		HIPCHK(hipMemcpyAsync(&s->h_bail(set), set.bail_list + s->max_reads, 4, hipMemcpyDeviceToHost, s->st));
+		HIPCHK(hipEventRecord(set.ev_bails, s->st));
+		HIPCHK(hipStreamWaitEvent(r->ms, set.ev_fast, 0));
 	}
 	return H2G_OK;
 }
@@ -2936,27 +2997,25 @@ static int fast_handoff(h2g_stream* s, bool paired, const GoPlan& g, GoRun* r) {
 // the machine stream's overflow list and the lane's part of the long-edit area
 static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 	GoArgs& A = r->A;
-	const unsigned psel = r->psel, qsel = r->qsel;
-	s->ovf_cur = qsel;
-	HIPCHK(s->d_ovf_list[qsel].ensure(s->max_reads + 4));
-	r->ovl = s->d_ovf_list[qsel];
+	const unsigned lane = r->lane;
+	s->ovf_cur = r->mach;
+	HIPCHK(r->mach->ovf_list.ensure(s->max_reads + 4));
+	r->ovl = r->mach->ovf_list;
 	HIPCHK(hipMemsetAsync(r->ovl + s->max_reads, 0, 16, r->ms));
-	// the long-edit area: part psel and its cursor belong to this lane (the pass that used them last is over: it ran on the same stream, or go_rotation made this stream wait for it)
+	// the long-edit area: this lane's part and its cursor (the pass that used them last is over: it ran on the same stream, or go_rotation made this stream wait for it)
 	const size_t lcap = s->max_reads > (1u << 20) ? s->max_reads : (size_t)(1u << 20);
-	if(s->ledits_cap < lcap || s->ledits_parts < g.M) {
+	if(!s->ledits.fits(g.M, lcap) || !s->d_ledits_cur) {
 		// (the flag stays: this run's own fast pass, already queued, has set it)
 		if(s->st2_busy) for(unsigned k = 0; k < s->n_mst; k++) HIPCHK(hipStreamSynchronize(s->mst[k]));
 		HIPCHK(hipStreamSynchronize(s->st));
-		s->ledits_cap = 0; s->ledits_parts = 0;
-		HIPCHK(s->d_ledits.reset(g.M * lcap));
+		HIPCHK(s->ledits.reset(g.M, lcap));
 		HIPCHK(s->d_ledits_cur.ensure(H2G_MSTREAMS_MAX));
-		s->ledits_cap = lcap; s->ledits_parts = g.M;
-		for(unsigned m = 0; m < H2G_MSTREAMS_MAX; m++) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_ledits_cur + m), (int)(m < g.M ? m * lcap : 0), 1, s->st));
+		for(unsigned m = 0; m < H2G_MSTREAMS_MAX; m++) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(s->d_ledits_cur + m), (int)(m < g.M ? s->ledits.lo(m) : 0), 1, s->st));
 		HIPCHK(hipStreamSynchronize(s->st));
 	}
-	A.O.ledits = s->d_ledits; A.O.ledits_cursor = s->d_ledits_cur + psel; A.O.ledits_cap = (uint32_t)((psel + 1) * s->ledits_cap);
-	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ledits_cursor, (int)(psel * s->ledits_cap), 1, r->ms));
-	s->ledits_touched |= 1u << psel;
+	A.O.ledits = s->ledits; A.O.ledits_cursor = s->d_ledits_cur + lane; A.O.ledits_cap = (uint32_t)s->ledits.hi(lane);
+	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)A.O.ledits_cursor, (int)s->ledits.lo(lane), 1, r->ms));
+	s->ledits_touched |= 1u << lane;
 	if(g.second) { A.O.defer_list = r->ovl; A.O.defer_count = r->ovl + s->max_reads; }     // overflowed reads: listed for the second pass, their rows untouched
 	return H2G_OK;
 }
@@ -2968,15 +3027,21 @@ static int go_mach_lists(h2g_stream* s, const GoPlan& g, GoRun* r) {
 // of streams 5-7: 18.5 ms per step where the steady state is 12-13).  A stream that enters the rotation later is warmed by the run that brings it in.
 // The launches own everything they could write: a list whose count is a word no kernel writes (a machine stream's overflow list may hold the deferred count of an
 // earlier run) and which every warmed stream zeroes itself in front of its launches, rows and cursors of their own.
+static bool go_cold(const h2g_stream* s, const GoPlan& g, const GoRun& r) {      // a machine stream in rotation, other than the run's, that has not been warmed
+	for(unsigned k = 0; k < g.S; k++) if(&s->mach[k] != r.mach && !s->mach[k].warmed) return true;
+	return false;
+}
 static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, const GoRun& r) {
 	int rc;
 	const size_t warm_rows = (size_t)1 << 16;
 	if(!s->d_warm_cnt) { HIPCHK(s->d_warm_cnt.ensure(H2G_CNT_BLOCK)); HIPCHK(hipMemset(s->d_warm_cnt, 0, H2G_CNT_BLOCK * sizeof(unsigned long long))); }
 	if(!s->d_warm_rows) { HIPCHK(s->d_warm_rows.ensure(warm_rows)); HIPCHK(hipMemset(s->d_warm_rows, 0, warm_rows)); }
-	for(unsigned m = 0; m < g.S; m++) {
-		if(m == r.ssel || ((s->warm_mask >> m) & 1u) || !s->d_ovf_list[m]) continue;
+	for(unsigned k = 0; k < g.S; k++) {
+		h2g_stream::MachStream& m = s->mach[k];
+		const hipStream_t ms = s->stream_of(m);
+		if(&m == r.mach || m.warmed || !m.ovf_list) continue;
 		GoArgs W1 = r.A;
-		if((rc = go_pool_for(s, 2 * (int)m, *g.U, (size_t)g.U->slots, (size_t)g.U->threads, p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
+		if((rc = go_pool_for(s, m.main, *g.U, (size_t)g.U->slots, (size_t)g.U->threads, p->bowtie2_dp, &W1))) return rc;      // (the stream's pools exist: nothing is allocated here)
 		W1.counters = s->d_warm_cnt; W1.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_MAIN);
 		W1.list = reinterpret_cast<uint32_t*>(s->d_warm_rows.get()); W1.nlist = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_NO_SECOND);   // a count of zero
 		memset(&W1.O, 0, sizeof W1.O);
@@ -2987,15 +3052,15 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 		W1.defer_overflow = 0;
 		// The count is zero ON THIS STREAM before its kernels read it: the hipMemset above runs on the null stream, which the (non-blocking) machine streams do not wait
 		// for, and the host does not have to either — a launch that went out first read whatever the fresh block held as its count and the row block as read ids.
-		HIPCHK(hipMemsetAsync(s->d_warm_cnt + H2G_CNT_NO_SECOND, 0, 8 * sizeof(unsigned long long), s->mst[m]));
-		if(g.U->launch(&W1, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+		HIPCHK(hipMemsetAsync(s->d_warm_cnt + H2G_CNT_NO_SECOND, 0, 8 * sizeof(unsigned long long), ms));
+		if(g.U->launch(&W1, &r.X, nullptr, 1, ms) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		if(g.second) {
 			GoArgs W2 = W1;
-			if((rc = go_pool_for(s, 2 * (int)m + 1, *g.L, (size_t)g.L->slots, (size_t)g.L->threads, p->bowtie2_dp, &W2))) return rc;
+			if((rc = go_pool_for(s, m.second, *g.L, (size_t)g.L->slots, (size_t)g.L->threads, p->bowtie2_dp, &W2))) return rc;
 			W2.work = reinterpret_cast<uint32_t*>(s->d_warm_cnt + H2G_CNT_WORK_SECOND);
-			if(g.L->launch(&W2, &r.X, nullptr, 1, s->mst[m]) != 0) return set_err("go() warm-up launch", hipGetLastError());
+			if(g.L->launch(&W2, &r.X, nullptr, 1, ms) != 0) return set_err("go() warm-up launch", hipGetLastError());
 		}
-		s->warm_mask |= 1u << m;
+		m.warmed = true;
 	}
 	s->st2_busy = true;
 	return H2G_OK;
@@ -3003,21 +3068,21 @@ static int go_warmup(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, 
 
 // the main pass, then the second pass over the reads it flagged (large workspace), whose results replace theirs
 static int go_mach(h2g_stream* s, const h2g_align_params* p, const GoPlan& g, GoRun* r) {
-	HIPCHK(hipEventRecord(s->ev[7], r->ms));
+	HIPCHK(hipEventRecord(s->tm[TM_MAIN0], r->ms));
 	if(g.U->launch(&r->A, &r->X, &r->XP, r->mach_grid, r->ms) != 0) return set_err("go() launch", hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[6], r->ms));
+	HIPCHK(hipEventRecord(s->tm[TM_MAIN1], r->ms));
 	if(g.second) {
 		GoArgs A2 = r->A;
 		int rc;
-		if((rc = go_pool_for(s, 2 * r->qsel + 1, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &A2))) return rc;
+		if((rc = go_pool_for(s, r->mach->second, *g.L, (size_t)g.bgrid * g.L->slots, (size_t)g.bgrid * g.L->threads, p->bowtie2_dp, &A2))) return rc;
 		A2.counters = r->cblk + H2G_CNT_SECOND;           // (a region of its own: in H2G_GO_PROF builds a pass writes up to 96 words behind its counters)
 		A2.work = reinterpret_cast<uint32_t*>(r->cblk + H2G_CNT_WORK_SECOND);
 		A2.list = r->ovl; A2.nlist = r->ovl + s->max_reads;   // (the count is filled by the main pass itself: MachOut::defer_list)
 		A2.defer_overflow = 0; A2.O.defer_list = nullptr; A2.O.defer_count = nullptr;
 		if(g.L->launch(&A2, &r->X, nullptr, g.bgrid, r->ms) != 0) return set_err("go() second pass launch", hipGetLastError());
 	}
-	HIPCHK(hipEventRecord(s->ev[8], r->ms));
-	if(g.fast) { HIPCHK(hipEventRecord(s->ev_mach[r->gsel], r->ms)); s->warm_mask |= 1u << r->ssel; }
+	HIPCHK(hipEventRecord(s->tm[TM_RUN1], r->ms));
+	if(g.fast) { HIPCHK(hipEventRecord(r->set->ev_mach, r->ms)); r->mach->warmed = true; }
 	return H2G_OK;
 }
 
@@ -3036,25 +3101,24 @@ static h2g_status go_run(h2g_stream* s, const h2g_align_params* p, bool paired) 
 	s->last_p = *p; s->last_paired = paired ? 1 : 0;
 	GoRun r = {};
 	go_args(s, p, paired, g, &r);
+	go_select(s, g, &r);
 	if(!g.fast) HIPCHK(sync_mach(s));   // (the machine streams' pools are about to be used on the first stream)
 	else if((rc = go_rotation(s, g))) return rc;
-	if((rc = go_pools(s, p, g, &r.A)) || (rc = go_rows(s, p, paired, g, &r))) return rc;
+	if((rc = go_pools(s, p, g, &r)) || (rc = go_rows(s, p, paired, g, &r))) return rc;
 	(void)hipGetLastError();
 	if((rc = go_counters(s, paired, g, &r))) return rc;
-	HIPCHK(hipEventRecord(s->ev[5], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_RUN0], s->st));
 	s->ran_fast = g.fast;
 	if(g.fast) {
 		fast_policy(s, paired, g, &r.f);
 		if((rc = fast_buffers(s, g, r.f)) || (rc = fast_launch(s, paired, g, &r))) return rc;
 	}
-	HIPCHK(hipEventRecord(s->ev[10], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_FAST1], s->st));
 	r.ms = s->st; r.mach_grid = g.grid;
 	s->ran_drain = false;
 	if(g.fast && (rc = fast_handoff(s, paired, g, &r))) return rc;
-	r.psel = g.fast ? r.msel : 0u;          // the lane's part of the long-edit area
-	r.qsel = g.fast ? r.ssel : 0u;          // workspace pools and the overflow list of this machine stream
 	if((rc = go_mach_lists(s, g, &r))) return rc;
-	if(g.fast && s->cur().n_reads >= 200000 && s->gen >= 1 && (~s->warm_mask & ((1u << g.S) - 1u) & ~(1u << r.ssel)) && (rc = go_warmup(s, p, g, r))) return rc;
+	if(g.fast && s->cur().n_reads >= 200000 && s->gen >= 1 && go_cold(s, g, r) && (rc = go_warmup(s, p, g, r))) return rc;
 	if((rc = go_mach(s, p, g, &r))) return rc;
 	s->cnt_cur = r.cblk; s->gen++;
 	HIPCHK(hipGetLastError());
@@ -3151,7 +3215,7 @@ static int gather_dense(h2g_stream* s, const h2g_alnres* d_src, uint32_t slots, 
 	if((rc = tmp_buf(s, tmp_slot, (n + 1) * 8, &d_offs)) || (rc = tmp_buf(s, tmp_slot + 1, tot * sizeof(h2g_alnres), &d_dense))) return rc;
 	HIPCHK(hipMemcpyAsync(d_offs, offs, (n + 1) * 8, hipMemcpyHostToDevice, s->st));
 	hipLaunchKernelGGL(k_gather_aln, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, d_src, slots, d_cnt, cnt_stride,
-	                   (const unsigned long long*)d_offs, n, (h2g_alnres*)d_dense, d_pout, (const h2g_alnres*)s->d_paln_ovf, mate);
+	                   (const unsigned long long*)d_offs, n, (h2g_alnres*)d_dense, d_pout, (const h2g_alnres*)s->paln_ovf, mate);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, d_dense, tot * sizeof(h2g_alnres), hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
@@ -3300,8 +3364,8 @@ static int compact_offsets(h2g_stream* s, const h2g_alnres* d_src, uint32_t slot
                            const uint32_t* xat = nullptr) {
 	int rc;
 	if((rc = tmp_buf(s, slot, (n + 1) * 8 + ((n + 1) / H2G_SCAN_TILE + 2) * 8, d_offs))) return rc;      // offsets [n + 1], then the scan's tile sums
-	hipLaunchKernelGGL(k_compact_sizes, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, d_src, slots, d_cnt, cnt_stride, n, (unsigned long long*)*d_offs, d_pout, (const h2g_alnres*)s->d_paln_ovf, mate,
-	                   xat, xat ? (const uint32_t*)s->d_xlp : (const uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_compact_sizes, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s->st, d_src, slots, d_cnt, cnt_stride, n, (unsigned long long*)*d_offs, d_pout, (const h2g_alnres*)s->paln_ovf, mate,
+	                   xat, xat ? (const uint32_t*)s->xlp : (const uint32_t*)nullptr);
 	{	// exclusive scan of the n + 1 sizes (the last one is 0: its slot becomes the total); the tile sums live behind the offsets
 		const size_t n1 = n + 1, ntiles = (n1 + H2G_SCAN_TILE - 1) / H2G_SCAN_TILE;
 		unsigned long long* v = (unsigned long long*)*d_offs;
@@ -3447,7 +3511,7 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 	if((rc = tmp_buf(s, 2, cnt_at[M - 1] + scan64_bytes(nblk[M - 1] + 1), &d_cnt))) return (h2g_status)rc;
 	for(int m = 0; m < M; m++) if(nt[m]) HIPCHK(hipMemcpyAsync(d_text[m], text[m], nt[m], hipMemcpyHostToDevice, s->st));
 	unsigned long long nl[2] = {0, 0};
-	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET0], s->st));
 	for(int m = 0; m < M; m++) {
 		unsigned long long* v = (unsigned long long*)((uint8_t*)d_cnt + cnt_at[m]);
 		HIPCHK(hipMemsetAsync(v + nblk[m], 0, 8, s->st));
@@ -3455,10 +3519,10 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		scan64(s, v, nblk[m] + 1);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET1], s->st));
 	for(int m = 0; m < M; m++) HIPCHK(hipMemcpyAsync(&nl[m], (unsigned long long*)((uint8_t*)d_cnt + cnt_at[m]) + nblk[m], 8, hipMemcpyDeviceToHost, s->st));
 	HIPCHK(sync_all(s));
-	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	HIPCHK(hipEventElapsedTime(&ms, s->tm[TM_SET0], s->tm[TM_SET1])); ms_total += ms;
 	// whole records, and the one a text that ends the input may still hold behind them (h2g_fastq.h)
 	uint64_t n = opts->max_records ? opts->max_records : UINT64_MAX;
 	for(int m = 0; m < M; m++) {
@@ -3490,7 +3554,7 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 	unsigned long long tot_l[2] = {0, 0}, tot_n[2] = {0, 0};
 	uint32_t last_nl[2] = {0, 0};
 	uint64_t known[2];
-	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET0], s->st));
 	for(int m = 0; m < M; m++) {
 		const Lay& l = lay[m];
 		known[m] = std::min<uint64_t>(nl[m], 4 * n);
@@ -3504,7 +3568,7 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		scan64(s, (unsigned long long*)(T + l.nsz), n + 1);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET1], s->st));
 	for(int m = 0; m < M; m++) {
 		const Lay& l = lay[m];
 		HIPCHK(hipMemcpyAsync(hres[m], T + l.res, 16, hipMemcpyDeviceToHost, s->st));
@@ -3513,7 +3577,7 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		if(known[m] == 4 * n) HIPCHK(hipMemcpyAsync(&last_nl[m], (uint32_t*)(T + l.nlpos) + (4 * n - 1), 4, hipMemcpyDeviceToHost, s->st));
 	}
 	HIPCHK(sync_all(s));
-	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	HIPCHK(hipEventElapsedTime(&ms, s->tm[TM_SET0], s->tm[TM_SET1])); ms_total += ms;
 	s->fq_stats.kernel_ms = ms_total;
 	const uint64_t consumed[2] = {known[0] == 4 * n ? (uint64_t)last_nl[0] + 1 : n1, M == 2 ? (known[1] == 4 * n ? (uint64_t)last_nl[1] + 1 : n2) : 0};
 	out->consumed1 = consumed[0]; out->consumed2 = consumed[1];
@@ -3531,7 +3595,7 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 	// ---- phase C: the batch's arrays
 	HIPCHK(B.reserve_names(tot_n[0], s->max_reads));
 	if(M == 2) HIPCHK(B.ensure_mates(s->max_reads, s->max_bases, tot_n[1]));
-	HIPCHK(hipEventRecord(s->ev[12], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET0], s->st));
 	for(int m = 0; m < M; m++) {
 		const Lay& l = lay[m];
 		const unsigned long long* lsz = (const unsigned long long*)(T + l.lsz);
@@ -3548,9 +3612,9 @@ extern "C" h2g_status h2g_set_reads_fastq(h2g_stream* s, const char* text1, size
 		s->fq_stats.bytes_written += 2 * tot_l[m] + tot_n[m] + 2 * (n + 1) * 4;
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(s->ev[13], s->st));
+	HIPCHK(hipEventRecord(s->tm[TM_SET1], s->st));
 	HIPCHK(sync_all(s));
-	HIPCHK(hipEventElapsedTime(&ms, s->ev[12], s->ev[13])); ms_total += ms;
+	HIPCHK(hipEventElapsedTime(&ms, s->tm[TM_SET0], s->tm[TM_SET1])); ms_total += ms;
 	s->fq_stats.kernel_ms = ms_total;
 	B.n_reads = n;
 	B.max_read_len = out->max_read_len;
@@ -3625,10 +3689,10 @@ extern "C" h2g_status h2g_align_pairs_fetch_compact(h2g_stream* s, h2g_pair_resu
 	if((rc = tmp_buf(s, 1, boffs1[n] + 8, &d_b1)) || (rc = tmp_buf(s, 3, boffs2[n] + 8, &d_b2))) return (h2g_status)rc;
 	const unsigned g = (unsigned)((n + 255) / 256);
 	if(boffs1[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->cur().d_paln[0] + first * s->cur().pair_slots, s->cur().pair_slots, cnt, (uint32_t)(sizeof(PairOut) / 4),
-	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->cur().d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 0,
-	                                 xat, xat ? (const uint32_t*)s->d_xlp : (const uint32_t*)nullptr);
+	                                 (const unsigned long long*)d_o1, n, (uint8_t*)d_b1, s->cur().d_pout + first, (const h2g_alnres*)s->paln_ovf, 0,
+	                                 xat, xat ? (const uint32_t*)s->xlp : (const uint32_t*)nullptr);
 	if(boffs2[n]) hipLaunchKernelGGL(k_compact_gather, dim3(g), dim3(256), 0, s->st, s->cur().d_paln[1] + first * s->cur().pair_slots, s->cur().pair_slots, cnt + 1, (uint32_t)(sizeof(PairOut) / 4),
-	                                 (const unsigned long long*)d_o2, n, (uint8_t*)d_b2, s->cur().d_pout + first, (const h2g_alnres*)s->d_paln_ovf, 1);
+	                                 (const unsigned long long*)d_o2, n, (uint8_t*)d_b2, s->cur().d_pout + first, (const h2g_alnres*)s->paln_ovf, 1);
 	HIPCHK(hipGetLastError());
 	if(boffs1[n]) HIPCHK(hipMemcpyAsync(rec1, d_b1, boffs1[n], hipMemcpyDeviceToHost, s->st));
 	if(boffs2[n]) HIPCHK(hipMemcpyAsync(rec2, d_b2, boffs2[n], hipMemcpyDeviceToHost, s->st));
@@ -4017,53 +4081,41 @@ extern "C" void h2g_host_free(void* p) { if(p) (void)hipHostFree(p); }
 extern "C" h2g_status h2g_align_fetch_long_edits(h2g_stream* s, h2g_edit* out, size_t cap, size_t* n) {
 	if(!s || !n) return H2G_ERR_ARG;
 	*n = 0;
-	if(!s->ran_align || !s->d_ledits || !s->d_ledits_cur) return H2G_OK;
+	if(!s->ran_align || !s->ledits || !s->d_ledits_cur) return H2G_OK;
 	HIPCHK(hipSetDevice(s->ix->device));
 	HIPCHK(sync_mach(s));
 	HIPCHK(hipStreamSynchronize(s->st));
 	uint32_t cur[H2G_MSTREAMS_MAX];
 	HIPCHK(hipMemcpy(cur, s->d_ledits_cur, sizeof cur, hipMemcpyDeviceToHost));
-	size_t hi = 0;
-	// (only the parts the runs since the last upload wrote to: a part left over from an earlier batch keeps its cursor until its machine stream is used again — ADVICE r5)
-	for(unsigned m = 0; m < s->ledits_parts; m++) if(!((s->ledits_touched >> m) & 1u)) cur[m] = (uint32_t)(m * s->ledits_cap);
-	for(unsigned m = 0; m < s->ledits_parts; m++) {
-		size_t end = cur[m]; const size_t lo = m * s->ledits_cap, top = (m + 1) * s->ledits_cap;
-		if(end > top) end = top;                       // (a full part: the reads that found no room are flagged)
-		if(end > lo) hi = end;
-	}
+	// (only the parts the runs since the last upload wrote to: a part left over from an earlier batch keeps its cursor until its lane is used again — ADVICE r5;
+	// a full part's cursor is clamped: the reads that found no room are flagged)
+	PartSpan span[H2G_MSTREAMS_MAX];
+	const size_t hi = part_spans(cur, s->ledits_touched, s->ledits.parts, s->ledits.cap, span);
 	*n = hi;
 	if(hi == 0) return H2G_OK;
 	if(!out || cap < hi) return H2G_ERR_ARG;
-	for(unsigned m = 0; m < s->ledits_parts; m++) {
-		size_t end = cur[m]; const size_t lo = m * s->ledits_cap, top = (m + 1) * s->ledits_cap;
-		if(end > top) end = top;
-		if(end > lo) HIPCHK(hipMemcpy(out + lo, s->d_ledits + lo, (end - lo) * sizeof(h2g_edit), hipMemcpyDeviceToHost));
-	}
+	for(unsigned m = 0; m < s->ledits.parts; m++)
+		if(span[m].end > span[m].lo) HIPCHK(hipMemcpy(out + span[m].lo, s->ledits + span[m].lo, (span[m].end - span[m].lo) * sizeof(h2g_edit), hipMemcpyDeviceToHost));
 	return H2G_OK;
 }
 
-// development hook: measurement / debugging knobs of go_run by name.  Everything in flight is waited for first, so a change never meets a
-// queued run.  "fast" 0/1, "blocks_per_cu", "pair_slots", "no_second_pass", "mach_div", "mach_min", "dbg_read" (-1 = off), "tail", "align_mate", "fast_spliced" (0: spliced runs go to the machine whole),
-// "mstreams" (pins lanes = machine streams in rotation, 1..H2G_MSTREAMS_MAX), "mstreams_light" (machine streams in rotation while the fast pass hands on little), "mach_total" (workgroups of all of them together), "fast_reserve" (CUs the fast pass leaves
-// free: -1 = as many as the machine passes in flight may hold)
+// development hook: measurement / debugging knobs of go_run by name (g_knobs, and "mstreams" / "mstreams_light").  Everything in flight is waited for first, so a
+// change never meets a queued run.
 extern "C" __attribute__((visibility("default"))) int h2g_stream_tune(h2g_stream* s, const char* key, long v) {
 	if(!s || !key) return H2G_ERR_ARG;
 	HIPCHK(sync_all(s));
 	for(unsigned k_ = 0; k_ < s->n_mst; k_++) HIPCHK(hipStreamSynchronize(s->mst[k_]));   // (whatever st2_busy says: a change never meets a queued run)
 	const std::string k(key);
-	if(k == "fast") s->tune.fast = (int)v; else if(k == "blocks_per_cu") s->tune.blocks_per_cu = (int)v; else if(k == "pair_slots") s->tune.pair_slots = (int)v;
-	else if(k == "no_second_pass") s->tune.no_second_pass = (int)v; else if(k == "mach_div") s->tune.mach_div = (unsigned)v; else if(k == "mach_min") s->tune.mach_min = (unsigned)v;
-	else if(k == "dbg_read") s->tune.dbg_read = v; else if(k == "tail") { s->tune.tail = (int)v; s->tune.tail_auto = 0; } else if(k == "align_mate") s->tune.align_mate = (int)v;
-	else if(k == "mach_total") { s->tune.mach_total_auto = v <= 0; s->tune.mach_total = v <= 0 ? H2G_MACH_TOTAL : (unsigned)v; }      // (0 = the default policy)
-	else if(k == "fast_reserve") s->tune.fast_reserve = (int)v;
-	else if(k == "mate_handover") s->tune.mate_handover = (int)v;
-	else if(k == "ps0") s->tune.ps0 = (int)v;
-	else if(k == "fast_spliced") s->tune.fast_spliced = (int)v;
-	else if(k == "orphan") s->tune.orphan = (int)v; else if(k == "drain_grid") s->tune.drain_grid = (int)(v < 1 ? 1 : v > 128 ? 128 : v);
-	else if(k == "mstreams") { s->mstreams = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v); s->gen = 0; }   // pins lanes = machine streams (nothing is in flight: every buffer set is free)
-	else if(k == "mstreams_light") s->mstreams_light = (unsigned)(v < 1 ? 1 : v > H2G_MSTREAMS_MAX ? H2G_MSTREAMS_MAX : v);   // S of the light regime (mstreams_policy)
-	else return H2G_ERR_ARG;
-	return H2G_OK;
+	if(k == "mstreams") { s->mstreams = clamp_mstreams(v); s->gen = 0; return H2G_OK; }   // pins lanes = machine streams (nothing is in flight: every buffer set is free)
+	if(k == "mstreams_light") { s->mstreams_light = clamp_mstreams(v); return H2G_OK; }   // S of the light regime (mstreams_policy)
+	if(k == "mach_total" && v <= 0) { s->tune.mach_total_auto = 1; s->tune.mach_total = H2G_MACH_TOTAL; return H2G_OK; }      // (0 = the default policy)
+	if(k == "drain_grid") v = v < 1 ? 1 : v > 128 ? 128 : v;
+	for(const Knob& kn : g_knobs) if(k == kn.key) {
+		kn.set(s->tune, v);
+		if(kn.is_auto) s->tune.*kn.is_auto = 0;
+		return H2G_OK;
+	}
+	return H2G_ERR_ARG;
 }
 
 // development hook (tests): what a stream holds for the machine's passes, by name — "mstreams_rotation" (machine streams in rotation for the last run behind a
@@ -4075,7 +4127,7 @@ extern "C" __attribute__((visibility("default"))) long h2g_stream_probe(const h2
 	if(k == "mstreams_used") return (long)s->n_mst;
 	if(k == "mstreams_created") { long n = 0; for(hipStream_t m : s->mst) n += m != nullptr; return n; }
 	if(k == "lanes") return (long)(s->mstreams ? s->mstreams : H2G_MSTREAMS_MAX);
-	if(k == "pools") { long n = 0; for(const h2g_stream::GoPool& pl : s->pool) n += bool(pl.ws); return n; }
+	if(k == "pools") { long n = 0; for(const h2g_stream::MachStream& m : s->mach) n += bool(m.main.ws) + bool(m.second.ws); return n; }
 	return -1;
 }
 
@@ -4125,17 +4177,17 @@ extern "C" h2g_status h2g_get_counters(h2g_stream* s, h2g_counters* c) {
 	s->last.n_rank = v[0] + v[8]; s->last.n_side = v[1] + v[9]; s->last.n_sa_steps = v[2] + v[10]; s->last.n_ext = v[3];
 	s->last.n_aligned = v[4] + v[12];
 	uint32_t nsecond = 0;
-	if(s->d_ovf_list[s->ovf_cur] && s->ran_align) HIPCHK(hipMemcpy(&nsecond, s->d_ovf_list[s->ovf_cur] + s->max_reads, 4, hipMemcpyDeviceToHost));
+	if(s->ovf_cur->ovf_list && s->ran_align) HIPCHK(hipMemcpy(&nsecond, s->ovf_cur->ovf_list + s->max_reads, 4, hipMemcpyDeviceToHost));
 	s->last.n_second_pass = nsecond;
 	s->last.n_overflow = nsecond ? v[13] : v[5];   // reads still flagged after the last pass that saw them
 	s->last.n_queries = s->cur().n_reads * 2;
 	float t = 0;
 	if(s->ran_seed) {
-		if(hipEventElapsedTime(&t, s->ev[2], s->ev[3]) == hipSuccess) s->last.ms_search = t;
-		if(hipEventElapsedTime(&t, s->ev[3], s->ev[4]) == hipSuccess) s->last.ms_resolve_extend = t;
+		if(hipEventElapsedTime(&t, s->tm[TM_SEED0], s->tm[TM_SEED_MID]) == hipSuccess) s->last.ms_search = t;
+		if(hipEventElapsedTime(&t, s->tm[TM_SEED_MID], s->tm[TM_SEED1]) == hipSuccess) s->last.ms_resolve_extend = t;
 	}
-	if(s->ran_align && hipEventElapsedTime(&t, s->ev[7], s->ev[6]) == hipSuccess) s->last.ms_align_kernel = t;
-	if(s->ran_align && hipEventElapsedTime(&t, s->ev[5], s->ev[8]) == hipSuccess) s->last.ms_align = t;   // every pass
+	if(s->ran_align && hipEventElapsedTime(&t, s->tm[TM_MAIN0], s->tm[TM_MAIN1]) == hipSuccess) s->last.ms_align_kernel = t;
+	if(s->ran_align && hipEventElapsedTime(&t, s->tm[TM_RUN0], s->tm[TM_RUN1]) == hipSuccess) s->last.ms_align = t;   // every pass
 	s->last.n_fast = 0; s->last.n_fast_bail = 0; s->last.ms_fast_kernel = 0; s->last.pad_ = 0; s->last.n_fast_side = 0; s->last.n_fast_sa_steps = 0;
 	s->last.ms_drain_kernel = 0; s->last.pad2_ = 0; s->last.n_drain_side = 0; s->last.n_drain_sa_steps = 0; s->last.n_adopted = 0;
 	if(s->ran_align && s->ran_fast) {
@@ -4146,7 +4198,7 @@ extern "C" h2g_status h2g_get_counters(h2g_stream* s, h2g_counters* c) {
 		s->last.n_fast = f[0]; s->last.n_fast_bail = f[1];
 		s->last.n_fast_side = fc[1]; s->last.n_fast_sa_steps = fc[2];
 		s->last.n_rank += fc[0]; s->last.n_side += fc[1]; s->last.n_sa_steps += fc[2]; s->last.n_aligned += fc[3];
-		if(hipEventElapsedTime(&t, s->ev[5], s->ev[10]) == hipSuccess) s->last.ms_fast_kernel = t;
+		if(hipEventElapsedTime(&t, s->tm[TM_RUN0], s->tm[TM_FAST1]) == hipSuccess) s->last.ms_fast_kernel = t;
 		if(s->ran_drain) {
 			unsigned long long dc[4]; uint32_t nad = 0;
 			HIPCHK(hipMemcpy(dc, s->cnt_cur + H2G_CNT_FAST_RANK + H2G_CNT_DRAIN_OFF, sizeof dc, hipMemcpyDeviceToHost));

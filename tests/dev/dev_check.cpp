@@ -1,4 +1,5 @@
-// dev_check.cpp — the resource handles of csrc/h2g_dev.h over malloc / free, under the host sanitizers (tests/test_dev_handles_cpu.py).
+// dev_check.cpp — the resource handles of csrc/h2g_dev.h and the partitioned areas of csrc/h2g_parts.h over malloc / free, under the host sanitizers
+// (tests/test_dev_handles_cpu.py).
 // The eight entry points the handles call are defined HERE: they keep a log of calls and a count of live objects, and fail the k-th creation on request.
 // No HIP runtime is linked and no GPU is needed.
 #include <stdio.h>
@@ -9,6 +10,7 @@
 #include <utility>
 #include <vector>
 #include "../../hisat2_amd/csrc/h2g_dev.h"
+#include "../../hisat2_amd/csrc/h2g_parts.h"
 
 using namespace h2g;
 
@@ -219,7 +221,70 @@ static void check_context() {
 	CHECK(g_double_free == 0);
 }
 
+// The partitioned areas (h2g_parts.h).  Every expected number below is written out from m * cap by hand
+static void check_parts() {
+	{
+		PartArea<uint32_t> a;
+		CHECK(!a && a.cap == 0 && a.parts == 0 && !a.fits(1, 1) && a.fits(0, 0));
+		g_log.clear();
+		CHECK(a.reset(8, 1000) == hipSuccess && a && a.parts == 8 && a.cap == 1000 && a.buf.size() == 8000 && g_log.size() == 1 && g_log[0].bytes == 32000);
+		CHECK(a.lo(0) == 0 && a.hi(0) == 1000);
+		CHECK(a.lo(1) == 1000 && a.hi(1) == 2000);
+		CHECK(a.lo(7) == 7000 && a.hi(7) == 8000);
+		uint32_t* const p = a;
+		p[7999] = 1;      // (the last element of the last part is inside the allocation: ASan)
+		// fits: both numbers have to be there
+		CHECK(a.fits(8, 1000) && a.fits(2, 1000) && a.fits(8, 1) && a.fits(1, 999));
+		CHECK(!a.fits(9, 1000) && !a.fits(8, 1001) && !a.fits(9, 1) && !a.fits(1, 1001));
+		// a failed allocation: no area, and the next reset allocates
+		fail_creation(0);
+		CHECK(a.reset(8, 2000) == hipErrorOutOfMemory && !a && a.parts == 0 && a.cap == 0 && !a.fits(1, 1) && live() == 0);
+		g_fail_at = -1;
+		CHECK(a.reset(2, 2000) == hipSuccess && a && a.parts == 2 && a.cap == 2000 && a.lo(1) == 2000 && a.hi(1) == 4000 && live() == 1);
+		// a reset to something smaller is still a new area (the free comes first)
+		g_log.clear();
+		CHECK(a.reset(1, 10) == hipSuccess && a.parts == 1 && a.cap == 10 && g_log.size() == 2 && !g_log[0].create && g_log[1].create && g_log[1].bytes == 40);
+	}
+	CHECK(live() == 0 && g_double_free == 0);
+	// the spans the cursors describe: 8 parts of 1000
+	PartSpan sp[8];
+	const auto empty = [&sp](unsigned m, size_t lo) { return sp[m].lo == lo && sp[m].end == lo; };
+	{	// nothing touched: whatever the cursors hold (leftovers of an earlier batch), every part is empty
+		const uint32_t cur[8] = {500, 1500, 2000, 3999, 4000, 5001, 6000, 7999};
+		CHECK(part_spans(cur, 0u, 8, 1000, sp) == 0);
+		CHECK(empty(0, 0) && empty(1, 1000) && empty(2, 2000) && empty(3, 3000) && empty(4, 4000) && empty(5, 5000) && empty(6, 6000) && empty(7, 7000));
+	}
+	{	// one touched part whose cursor still stands at its start: empty
+		const uint32_t cur[8] = {0, 1000, 2000, 3000, 4000, 5000, 6000, 7000};
+		CHECK(part_spans(cur, 1u << 3, 8, 1000, sp) == 0);
+		CHECK(empty(3, 3000) && empty(0, 0) && empty(7, 7000));
+	}
+	{	// a touched part in the middle; an untouched one with a moved cursor beside it stays empty
+		const uint32_t cur[8] = {0, 1000, 2345, 3100, 4000, 5000, 6000, 7000};
+		CHECK(part_spans(cur, 1u << 2, 8, 1000, sp) == 2345);
+		CHECK(sp[2].lo == 2000 && sp[2].end == 2345 && empty(3, 3000) && empty(1, 1000) && empty(0, 0));
+	}
+	{	// a cursor beyond its part (the part is full): clamped to the part's end; one below its part (never written by a run): empty
+		const uint32_t cur[8] = {0, 2600, 2000, 3000, 4000, 77, 6000, 7000};
+		CHECK(part_spans(cur, (1u << 1) | (1u << 5), 8, 1000, sp) == 2000);
+		CHECK(sp[1].lo == 1000 && sp[1].end == 2000 && empty(5, 5000) && empty(2, 2000));
+	}
+	{	// the last part touched, and the first: the span reaches into the last
+		const uint32_t cur[8] = {12, 1000, 2000, 3000, 4000, 5000, 6000, 7001};
+		CHECK(part_spans(cur, (1u << 0) | (1u << 7), 8, 1000, sp) == 7001);
+		CHECK(sp[0].lo == 0 && sp[0].end == 12 && sp[7].lo == 7000 && sp[7].end == 7001 && empty(4, 4000));
+	}
+	{	// fewer parts than cursors: the ones beyond `parts` are nobody's
+		const uint32_t cur[8] = {1, 1001, 2002, 3003, 0, 0, 0, 0};
+		sp[2].lo = sp[2].end = 99;
+		CHECK(part_spans(cur, 0xffu, 2, 1000, sp) == 1001);
+		CHECK(sp[0].end == 1 && sp[1].lo == 1000 && sp[1].end == 1001 && sp[2].lo == 99 && sp[2].end == 99);
+	}
+}
+
 int main() {
+	check_parts();
+	printf("dev_check: the areas in parts, %d checks\n", g_checks);
 	check_verbs();
 	check_failures();
 	check_moves();

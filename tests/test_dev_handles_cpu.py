@@ -41,6 +41,20 @@ def test_the_header_stands_alone():
     assert "hip/hip_runtime_api.h" in inc and not [i for i in inc if i.startswith("h2g")]
 
 
+def test_partitioned_areas_under_sanitizers(checker):
+    """csrc/h2g_parts.h in the same program: reset / fits / lo / hi of an area in parts, a failed allocation that leaves no area, and the spans the cursors describe
+    (nothing touched, a cursor at its part's start, a part in the middle, a cursor beyond its part, the last part), every expected number written out by hand"""
+    r = subprocess.run([checker], capture_output=True, text=True)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
+    assert int(re.search(r"the areas in parts, (\d+) checks", r.stdout).group(1)) >= 20
+
+
+def test_the_parts_header_stands_alone():
+    """h2g_parts.h includes h2g_dev.h and nothing else of the project"""
+    inc = re.findall(r'^\s*#\s*include\s*[<"]([^>"]+)[>"]', open(os.path.join(CSRC, "h2g_parts.h")).read(), re.M)
+    assert [i for i in inc if i.startswith("h2g")] == ["h2g_dev.h"] and not [i for i in inc if "/" in i]
+
+
 def test_the_c_abi_unit_releases_nothing_by_hand():
     """every device buffer, event and stream of h2g_kernels.hip is a handle: the unit itself names no release call (h2g_host_free hands raw page-locked memory back to a caller)"""
     src = open(os.path.join(CSRC, "h2g_kernels.hip")).read()
